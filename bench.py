@@ -13,7 +13,9 @@ columns N ways (north_star / configs[2]); the global batch grows with N (256 per
 N = 4 as configs[2] names) so per-GPU GEMM work is fixed -> "scaling": "weak"; per-shard top-k lists
 are exchanged with one RCCL all-gather and merged (K4).
 
-Rank 0 prints ONE JSON line.  Extra objects:
+Rank 0 prints ONE JSON line.  A plain run sets up, primes, warms up, times the K steps and prints the headline
+(`value`, `ms_per_step`, `config`); `--dump-outputs DIR` also writes the top-k lists the last timed step returned.
+`--full` adds everything else the line can carry (the --no-* switches thin it), among them:
   roofline      -- the dominant kernel (fp32 MFMA decode with the threshold-filter epilogue):
                    algorithmic FLOP per launch / its average duration (hipEvents on the launch
                    stream, recorded inside the timed region) against the 157.3 TFLOP/s fp32 peak.
@@ -41,6 +43,7 @@ if ROOT not in sys.path:
 PEAK_F32_TFLOPS = 157.3      # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 = fp32 vector peak
 PEAK_BF16_TFLOPS = 2500.0    # dense bf16 MFMA (the 5 PF headline figure includes 2:1 sparsity)
 PEAK_HBM_GBS = 8000.0        # HBM3E spec
+DUMP_MAX_BYTES = 60 * 10**6  # --dump-outputs: all files together (.npy headers included, under 64 MB)
 
 
 def parse():
@@ -99,6 +102,14 @@ def parse():
     ap.add_argument("--no-hard-rows", action="store_true", help="skip the exact_bf16_hard / trained_model rows")
     ap.add_argument("--train-model-steps", type=int, default=1500, help="training steps of the trained_model rows' model")
     ap.add_argument("--verbose-out", default="", help="also write the verbose record (one JSON object) to this file")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the dominant kernel's roofline (event pairs in the timed region), "
+                         "the spread, clock, isolated-launch and encode measurements, the CPU baseline, the extra rows "
+                         "(thinned by the --no-* switches above) and the N > 1 side rows.  Off: set up, warm up, time the "
+                         "steps, print the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last of them returned (top-k scores and column ids) as "
+                         "DIR/<name>.npy (float32 / float64)")
     return ap.parse_args()
 
 
@@ -165,7 +176,8 @@ def compact_line(out):
                       ("sustained_clock", ("ghz_mean", "mfma_frac_at_clock")), ("pmc", ("mfma_busy_frac_of_kernel",))):
         if isinstance(r.get(sub), dict):
             rc[sub] = {k_: _num(r[sub][k_]) for k_ in keys if k_ in r[sub]}
-    c["roofline"] = rc
+    if "roofline" in out:                        # (--full only)
+        c["roofline"] = rc
     cb = out.get("cpu_baseline")
     if isinstance(cb, dict):
         cc = {k_: cb[k_] for k_ in ("value", "unit", "cores", "kind") if k_ in cb}
@@ -886,8 +898,8 @@ def main():
     rankers = {}
     if sharded:
         # the product's own sharded-scoring objects (what DAE.shard_scoring builds): one ShardedRanker per batch in
-        # flight and exchange, with preallocated receive buffers
-        for ex in ("alltoall", "allgather"):
+        # flight and exchange, with preallocated receive buffers (the exchange not chosen only for --full's extra row)
+        for ex in (("alltoall", "allgather") if args.full else (args.exchange,)):
             rankers[ex] = []
             for c in ctxs:
                 st = HipRankStages(c, d_We, d_be, rank_bound, DT)
@@ -984,14 +996,18 @@ def main():
         for _ in range(8):
             step()
         torch.cuda.synchronize()
+    # the prime ran as many steps as fit its time: count afresh, so that step i of the warm-up + timed sequence takes stream
+    # i % n_str and resident batch i % n_batches on every run (--dump-outputs compares the same batch from run to run)
+    step_no[0] = 0
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
     if sharded:
         dist.barrier()
     torch.cuda.synchronize()
-    for c in ctxs:
-        c.profile_enable(True)
+    if args.full:                            # event pairs around the dominant launch: the roofline's duration
+        for c in ctxs:
+            c.profile_enable(True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
@@ -1002,15 +1018,20 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     kern_ms, kern_n = 0.0, 0
-    for c in ctxs:
-        ms_, n_ = c.profile_read()
-        kern_ms += ms_; kern_n += n_
-        c.profile_enable(False)
+    if args.full:
+        for c in ctxs:
+            ms_, n_ = c.profile_read()
+            kern_ms += ms_; kern_n += n_
+            c.profile_enable(False)
     plan = ctx.last_plan()
+    last_out = None
+    if args.dump_outputs and rank == 0:      # what the last timed step returned, before anything else reuses its buffers
+        s_last = (step_no[0] - 1) % n_str
+        last_out = (last[s_last][0].cpu().numpy(), last[s_last][1].cpu().numpy())
     # the spread of the timed region: the SAME K steps four more times, after the headline one (VERDICT r5 Weak #10: K = 20 steps
     # are 3.7 ms; `value` stays the first region's, as the contract times exactly K steps once)
     value_runs = None
-    if not sharded:
+    if args.full and not sharded:
         value_runs = []
         for _rep in range(4):
             t_r = time.perf_counter()
@@ -1025,6 +1046,30 @@ def main():
         elapsed = float(t.item())
     ms_per_step = elapsed / args.steps * 1e3
     value = B * args.steps / elapsed
+    out = {
+        "metric": "playlists scored/sec (encode+decode+top-500) at |vocab|~170k",
+        "value": round(value, 1), "unit": "playlists/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+        "config": {"workload": "untied DAE scoring: encode+decode(all %d cols)+top-%d over %d track cols, "
+                               "hidden=%d, batch=%d/GPU (global %d), ids=%s, b_dec=%s, "
+                               "BASELINE.json configs[%d]" % (V, k, n_tracks, H, args.batch_per_gpu, B,
+                                                               args.dist, args.bias, 1 if world == 1 else 2),
+                   "vocab": V, "n_tracks": n_tracks, "hidden": H, "global_batch": B, "k": k,
+                   "parallelism": ("SIMULATED rank %d of %d (compute only, no exchange)" % (args.sim_rank, sim)) if sim else
+                                  ("1 GPU" if world == 1 else
+                                   "vocab column shard x%d + RCCL %s of the per-shard top-%d" % (
+                                       world, "all-to-all (each rank merges the %d rows it owns)" % (B // world)
+                                       if args.exchange == "alltoall" else "all-gather (each rank merges all rows)", k)),
+                   "plan": plan, "streams": n_str, "decode_gate": bool(gate_events), "tau_exchange": bool(args.tau_exchange and sharded),
+                   "host_issue_ms_per_step": round(t_enq / args.steps * 1e3, 4), "prepack_ms": round(prepack_ms, 2), "prime_ms": args.prime_ms,
+                   "decoder_prepacked": "once at model load (outside the timed region)"},
+    }
+    if last_out is not None:
+        _dump_outputs(args.dump_outputs, *last_out)
+    if not args.full:
+        _emit(out, args, rank, dist, sharded, saved_stdout_fd)
+        return
 
     # ---- roofline of the dominant kernel (this rank's launch) -----------------------------------
     ncols_rank = col_hi - col_lo
@@ -1232,26 +1277,7 @@ def main():
         with torch.cuda.stream(st):
             c.bind_stream()
 
-    out = {
-        "metric": "playlists scored/sec (encode+decode+top-500) at |vocab|~170k",
-        "value": round(value, 1), "unit": "playlists/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-        "config": {"workload": "untied DAE scoring: encode+decode(all %d cols)+top-%d over %d track cols, "
-                               "hidden=%d, batch=%d/GPU (global %d), ids=%s, b_dec=%s, "
-                               "BASELINE.json configs[%d]" % (V, k, n_tracks, H, args.batch_per_gpu, B,
-                                                               args.dist, args.bias, 1 if world == 1 else 2),
-                   "vocab": V, "n_tracks": n_tracks, "hidden": H, "global_batch": B, "k": k,
-                   "parallelism": ("SIMULATED rank %d of %d (compute only, no exchange)" % (args.sim_rank, sim)) if sim else
-                                  ("1 GPU" if world == 1 else
-                                   "vocab column shard x%d + RCCL %s of the per-shard top-%d" % (
-                                       world, "all-to-all (each rank merges the %d rows it owns)" % (B // world)
-                                       if args.exchange == "alltoall" else "all-gather (each rank merges all rows)", k)),
-                   "plan": plan, "streams": n_str, "decode_gate": bool(gate_events), "tau_exchange": bool(args.tau_exchange and sharded),
-                   "host_issue_ms_per_step": round(t_enq / args.steps * 1e3, 4), "prepack_ms": round(prepack_ms, 2), "prime_ms": args.prime_ms,
-                   "decoder_prepacked": "once at model load (outside the timed region)"},
-        "roofline": roofline, "roofline_encode": roofline_encode,
-    }
+    out["roofline"], out["roofline_encode"] = roofline, roofline_encode
     if value_runs:
         out["value_runs_M"] = value_runs     # M playlists/s of four more repetitions of the same K-step region (the spread)
     if roofline.get("traffic") is not None:
@@ -1719,6 +1745,24 @@ def main():
         except Exception as e:                       # the row is an extra: never lose the headline over it
             out["training_step"] = {"error": repr(e)}
 
+    _emit(out, args, rank, dist, sharded, saved_stdout_fd)
+
+
+def _dump_outputs(dirname, score, idx):
+    """--dump-outputs: the top-k lists the last timed step returned, as its caller receives them -- scores (float32) and
+    column ids (as float64, exact) -- [rows, k].  Beyond DUMP_MAX_BYTES in all, a fixed seeded sample of the rows
+    (their indices in sampled_rows.npy)."""
+    os.makedirs(dirname, exist_ok=True)
+    per_row = score.shape[1] * (4 + 8)
+    if score.shape[0] * per_row > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(score.shape[0], DUMP_MAX_BYTES // (per_row + 8), replace=False))
+        score, idx = score[rows], idx[rows]
+        np.save(os.path.join(dirname, "sampled_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(dirname, "topk_scores.npy"), np.ascontiguousarray(score, dtype=np.float32))
+    np.save(os.path.join(dirname, "topk_ids.npy"), idx.astype(np.float64))
+
+
+def _emit(out, args, rank, dist, sharded, saved_stdout_fd):
     if sharded:
         dist.barrier()
         dist.destroy_process_group()

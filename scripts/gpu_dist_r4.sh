@@ -1,7 +1,7 @@
 # round 4: the N > 1 code paths on one GPU -- simulated ranks (compute only), 1-rank RCCL, 2-rank gloo rehearsal
 cd $GRAFT_REPO_ROOT
 o=gpurun_out; mkdir -p $o
-X="--no-train-row --no-cpu-baseline --no-bf16-row --no-extra-rows"
+X="--full --no-train-row --no-cpu-baseline --no-bf16-row --no-extra-rows"
 for n in 2 4 8; do python bench.py --sim-world $n $X > $o/r04_bench_sim$n.json 2> $o/err_sim$n.txt; done
 python bench.py --sim-world 8 --sim-rank 7 $X > $o/r04_bench_sim8_rank7.json 2> $o/err_sim8r7.txt
 python bench.py --sim-world 8 --no-tau-exchange $X > $o/r04_bench_sim8_notau.json 2> $o/err_sim8notau.txt

@@ -3,12 +3,13 @@
 # summaries bench.py reads (copy them to profiles/: traffic_decode.json, traffic_encode.json).
 #   usage: bash scripts/gpu_pmc_round6.sh
 mkdir -p $GRAFT_REPO_ROOT/gpurun_out
+R=$(cd "$(dirname "$0")/.." && pwd)      # the repository root (the passes run outside it)
 cd /tmp && export TMPDIR=/tmp
 pass() {  # cfg set-name counters... -- bench args
   cfg=$1; name=$2; shift 2; ctrs=""
   while [ "$1" != "--" ]; do ctrs="$ctrs $1"; shift; done; shift
   d=/tmp/pmc6_${cfg}_${name}; rm -rf $d
-  timeout 400 rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d $d -o p -- python $GRAFT_REPO_ROOT/bench.py --steps 6 --warmup 2 --prime-ms 0 --no-cpu-baseline --no-train-row --no-bf16-row --no-extra-rows --streams 1 "$@" > $d.log 2>&1
+  timeout 400 rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d $d -o p -- python $R/bench.py --full --steps 6 --warmup 2 --prime-ms 0 --no-cpu-baseline --no-train-row --no-bf16-row --no-extra-rows --streams 1 "$@" > $d.log 2>&1
   echo "pass $cfg/$name rc=$?"
   f=$(find $d -name "*counter_collection.csv" | head -1)
   [ -n "$f" ] && cp $f $GRAFT_REPO_ROOT/gpurun_out/r06_pmc_${cfg}_${name}.csv

@@ -6,9 +6,9 @@ o=gpurun_out; mkdir -p $o
 if [ "$1" != notests ]; then
   timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | tail -6 | tee $o/r06_gputests.log
 fi
-python bench.py --gpus 1 --steps 20 --warmup 5 --verbose-out $o/r06_bench_verbose.json > $o/r06_bench_default.json 2> $o/err_default.txt
+python bench.py --gpus 1 --steps 20 --warmup 5 --full --verbose-out $o/r06_bench_verbose.json > $o/r06_bench_default.json 2> $o/err_default.txt
 tail -c 7000 $o/r06_bench_default.json; echo; wc -c $o/r06_bench_default.json
-bash scripts/gpu_kprof.sh r06_headline 7 python $GRAFT_REPO_ROOT/bench.py --no-extra-rows --no-train-row --no-cpu-baseline --no-bf16-row
+bash scripts/gpu_kprof.sh r06_headline 7 python $PWD/bench.py --full --no-extra-rows --no-train-row --no-cpu-baseline --no-bf16-row
 for B in 256 1024 2048; do
   bash scripts/gpu_kprof.sh r06_exact_b${B}_1stream 8 python $GRAFT_REPO_ROOT/scripts/time_modes.py $B zipf exact 1
 done
