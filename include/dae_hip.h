@@ -381,7 +381,9 @@ int dae_set_train_dtype(dae_ctx* ctx, int dtype);
  * of the feed).  n_batch = the fixed graph batch the mean divides by (DAEs.py:100).
  * tied != 0: W_dec aliases W_enc (DAE_tied); gW_dec is then ignored and gW_enc receives both
  * gradients.  Gradients are dense fp32 buffers the caller owns (overwritten).
- * cost_out: device scalar = mean_rows(L) + reg_lambda * l2 (DAEs.py:79-82/:147-150, :100). */
+ * cost_out: device scalar = mean_rows(L) + reg_lambda * l2 (DAEs.py:79-82/:147-150, :100).
+ * A target row may hold any number of entries (one per column: the CSR contract), under every train dtype;
+ * the same holds for dae_train_shard_decode. */
 int dae_train_forward_backward(dae_ctx* ctx,
         const int32_t* x_row_ptr, const int32_t* x_col, const float* x_val,
         const int32_t* y_row_ptr, const int32_t* y_col, const float* y_val,

@@ -226,3 +226,200 @@ class NumpyTrainStages:
 def _t(a):
     import torch
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+
+
+# ---- bf16 training step (dae_set_train_dtype(BF16)): float64 arithmetic, bf16 rounding where the kernels round ----------
+
+U32 = 2.0 ** -24                       # unit roundoff of fp32
+
+
+def bf16_round(a):
+    """Nearest bf16 value, ties to even.  float32 input: the bit form of train.hip bf16_value / pk_bf16 (v_cvt_pk_bf16_f32),
+    returned as float32.  float64 (any other) input: rounded once, directly from the float64 value (no double rounding
+    through fp32), returned as float64; subnormals on bf16's grid (spacing 2^-133)."""
+    a = np.asarray(a)
+    if a.dtype == np.float32:
+        u = a.view(np.uint32).astype(np.uint64)
+        u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
+        return u.astype(np.uint32).view(np.float32)
+    x = a.astype(np.float64)
+    e = np.maximum(np.frexp(x)[1], -125) - 8                       # bf16 keeps 8 significant bits
+    return np.ldexp(np.round(np.ldexp(x, -e)), e)                   # (np.round: half to even)
+
+
+def bf16_ulp(x):
+    """Spacing of the bf16 grid at |x| (float64): the gap between the two bf16 neighbours of x."""
+    return np.ldexp(1.0, np.maximum(np.frexp(np.abs(np.asarray(x, np.float64)))[1], -125) - 8)
+
+
+def grads_bf16(x, y, W_enc, b_enc, W_dec, b_dec, n_batch, tied, reg_lambda=0.0,
+               input_keep_mask=None, ikp=1.0, hidden_keep_mask=None, kp=1.0,
+               h=None, round_dz=None, round_ops=True):
+    """Gradient of the training step under dae_set_train_dtype(BF16), as the kernels round it: float64 everywhere except
+    where the kernels round an operand to bf16 (spotify_recsys_challenge_2018_amd/csrc, line numbers of this revision):
+
+      forward logits   z = bf16(h) . bf16(W_dec)^T + b_dec, for the negatives (K5: the prepack / pack_h kernels, the
+                       row-major K5's staged rows decode_f32.hip ~L679 and decode_loss_dh_bf16_kernel ~L891 round both
+                       operands with v_cvt_pk_bf16_f32, RNE) and for the positives alike (train.hip loss_fixup_kernel<BF16>:
+                       bf16_value on h ~L97 and on W ~L130-151, an fmaf chain from +0, then + bias).
+      H % 128 == 0     dz is stored as bf16 (loss_fixup_kernel<.., DZ16> ~L164; the K5 epilogues with p.dz16,
+                       decode_f32.hip ~L521 / ~L735 / ~L805), and gW_dec = dz^T h (grad_wdec_t_kernel: pk_bf16 of h ~L619,
+                       the bf16 dz^T read as is), dh = dz W_dec (grad_hidden_kernel<4, true, true>, or the fused K5 + K7
+                       plus the fix-up's correction sum (bf16(dz) - bf16(dz as a negative)) bf16(W), train.hip ~L187-194)
+                       run on bf16(dz), bf16(h), bf16(W_dec).  gb_dec sums the bf16 dz: grad_wdec_t_kernel forms it as an
+                       MFMA of the bf16 dz^T with a ones operand (~L623, stored ~L683).
+      H % 128 != 0     only the forward GEMM is bf16: the backward GEMMs (grad_wdec_kernel<2|1>, grad_hidden_kernel<2|1>)
+                       are fp32 on the unrounded dz, h and W_dec, and so is gb_dec.
+      everything else  loss, dpre, the encoder gradient and l2 are fp32 in the kernels, float64 here.
+
+    h: the fp32 hidden activations after dropout, [B, H].  Pass oracle.encode(..., ikp, kp, seed): the training step's K1
+    is dae_launch_encode, which tests/test_gpu_parity.py::test_encode_dropout_bit_exact pins bit for bit to orc_encode
+    (same fmaf chain per hidden unit in entry order, same sigmoid, the dropout as (x / kp) * floor(kp + u)), so bf16(h) has
+    no ambiguity.  None: h = the float64 activation (then nothing is bit-exact, for CPU-only use).
+    round_dz: store dz as bf16 (default: H % 128 == 0); round_ops=False leaves h and W_dec unrounded in every GEMM --
+    with round_dz=False that is grads() itself.  The masks and keep probabilities are grads()'.
+    Returns grads()' keys plus "_aux" (the intermediates bf16_bounds / bf16_backward need)."""
+    D = np.float64
+    x = np.asarray(x, D); y = np.asarray(y, D)
+    We = W_enc.astype(D); be = b_enc.astype(D); bd = b_dec.astype(D)
+    Wd32 = np.asarray(W_enc if tied else W_dec, np.float32)
+    H = We.shape[1]
+    xd = x / ikp
+    if input_keep_mask is not None:
+        xd = xd * input_keep_mask
+    xh = xd / (xd.sum(axis=1, keepdims=True) + 1e-10)
+    sg = 1.0 / (1.0 + np.exp(-(xh @ We + be)))
+    m = (np.ones_like(sg) if hidden_keep_mask is None else hidden_keep_mask.astype(D)) / kp
+    h64 = sg * m if h is None else np.asarray(h, np.float32).astype(D)
+    Wd = Wd32.astype(D)
+    if round_ops:
+        hb = bf16_round(h64) if h is None else bf16_round(np.asarray(h, np.float32)).astype(D)
+        Wb = bf16_round(Wd32).astype(D)
+    else:
+        hb, Wb = h64, Wd
+    if round_dz is None:
+        round_dz = (H % 128) == 0
+    z = hb @ Wb.T + bd
+    p = 1.0 / (1.0 + np.exp(-z))
+    eps = 1e-10
+    L = -np.sum(y * np.log(p + eps) + 0.55 * (1 - y) * np.log(1 - p + eps), axis=1)
+    cost = L.sum() / n_batch
+    dz = -(y / (p + eps) - 0.55 * (1 - y) / (1 - p + eps)) * p * (1 - p) / n_batch
+    aux = dict(x=x, y=y, xh=xh, sg=sg, m=m, h=h64, hb=hb, W=Wd, Wb=Wb, bd=bd, We=We, be=be, Wd_own=W_dec.astype(D),
+               z=z, p=p, dz=dz, dz16=bool(round_dz), bwd16=bool(round_dz) and round_ops, n_batch=n_batch, tied=tied,
+               lam=reg_lambda)
+    r = bf16_backward(aux, dz)
+    l2 = (We ** 2).sum() + (bd ** 2).sum() + (be ** 2).sum() + (0.0 if tied else (W_dec.astype(D) ** 2).sum())
+    r.update(cost=cost + reg_lambda * 0.5 * l2, y_pred=p, h=h64, _aux=aux)
+    return r
+
+
+def bf16_backward(aux, dz, rounded=False):
+    """The backward half of grads_bf16 from a given dz [B, V] (float64): bf16(dz) when the step stores it so (rounded=True:
+    dz is already on the bf16 grid), then gW_dec, gb_dec, dh, dpre, the encoder gradient and the lambda terms."""
+    a = aux
+    if a["dz16"]:
+        dzb = dz if rounded else bf16_round(dz)
+        hB, WB = (a["hb"], a["Wb"]) if a["bwd16"] else (a["h"], a["W"])
+    else:
+        dzb, hB, WB = dz, a["h"], a["W"]
+    lam = a["lam"]
+    gWd = dzb.T @ hB
+    gbd = dzb.sum(axis=0) + lam * a["bd"]
+    dh = dzb @ WB
+    dpre = dh * a["m"] * a["sg"] * (1 - a["sg"])
+    gWe = a["xh"].T @ dpre + lam * a["We"]
+    gbe = dpre.sum(axis=0) + lam * a["be"]
+    if a["tied"]:
+        gWe = gWe + gWd
+        gWd = None
+    else:
+        gWd = gWd + lam * a["Wd_own"]
+    return dict(gW_enc=gWe, gb_enc=gbe, gW_dec=gWd, gb_dec=gbd, dh=dh, dzb=dzb)
+
+
+def bf16_bounds(ref, c=2.0, h_rel=0.0):
+    """Element-wise bounds |kernel - grads_bf16| <= bound for gW_dec, gb_dec, gW_enc, gb_enc (and dh), from ref = grads_bf16().
+
+    Derivation.  A sum of n fp32 terms (any order, any tree, products exact or once rounded) is off its exact value by at
+    most (n + 2) u sum|terms|, u = 2^-24; c (2) leaves room for the fused launch, whose dh is the negatives' sum plus the
+    fix-up's correction (sum|terms| up to twice the exact one).  Products of two bf16 values are exact in fp32.
+    The rest is dz.  The kernel's fp32 dz differs from the float64 dz by at most
+        delta = p(1-p)(|y| + 0.55|1-y|)/n_batch * dz_err   (d dz / d z times the logit error)
+              + 2^-18 |dz|                                  (hardware exp2 / log / rcp, a few ulp each, with margin)
+              + 2^-21 (|y| + 0.55|1-y|)/n_batch  [y != 0]   (absolute: 1 - p of a positive with p -> 1 keeps no
+                                                             relative precision in fp32)
+        dz_err = (H + 2) u (sum_k |bf16(h_k) bf16(w_k)| + |b|)  (the fp32 logit: H exact products, H adds, the bias)
+    (the float64 p must not saturate where fp32's does: |z| < ~16, which the tests' weights keep).
+    With dz stored as bf16 (H % 128 == 0) the two agree after rounding except where the float64 dz lies within delta of a
+    rounding midpoint: those "ambiguous" elements may land one bf16 ulp apart, so each contributes ulp_bf16(dz) times
+    |the other operand| to its sums.  Without the bf16 store every element contributes delta times |the other operand|.
+        gW_dec[v,k] <= c (B+2) u sum_r |dz h| + sum_r A[r,v] |h[r,k]|      gb_dec[v] <= c (B+2) u sum_r |dz| + sum_r A[r,v]
+        dh[r,k]     <= c (V+2) u sum_v |dz W| + sum_v A[r,v] |W[v,k]|
+    dpre = dh m s(1-s) inherits dh's bound times |m s(1-s)|, plus 4u |dh m| (fp32 sigmoid's 1 - s is absolute) and 8u |dpre|;
+    gW_enc and gb_enc sum it over the batch: sum_r |xhat| bound(dpre) + c (B+2) u sum|terms| (tied: plus gW_dec's bound).
+    Lambda terms: 4u (|g| + lam |param|).  h_rel > 0 (the sharded stages, whose h comes from an all-reduced pre and is not
+    bit-exact): h elements within h_rel |h| of a bf16 midpoint may round either way, adding ulp_bf16(h) |W| to the logit
+    error and ulp_bf16(h) |dz| to gW_dec.
+    Returns dict of bound arrays (keys as grads(), plus "dh") and "amb", the ambiguous-dz mask."""
+    a = ref["_aux"]
+    u = U32
+    D = np.float64
+    B, H = a["h"].shape
+    V = a["W"].shape[0]
+    nb = a["n_batch"]
+    y, p, dz = a["y"], a["p"], a["dz"]
+    hB = a["hb"] if a["bwd16"] else a["h"]
+    WB = a["Wb"] if a["bwd16"] else a["W"]
+    habs = np.abs(a["hb"])
+    zerr = (H + 2) * u * (habs @ np.abs(a["Wb"]).T + np.abs(a["bd"]))
+    hA = np.zeros_like(habs)
+    if h_rel > 0:
+        hh = a["h"]
+        hamb = bf16_round(hh * (1 - h_rel)) != bf16_round(hh * (1 + h_rel))
+        hA = hamb * bf16_ulp(hh)
+        zerr = zerr + hA @ np.abs(a["Wb"]).T
+    wy = np.abs(y) + 0.55 * np.abs(1 - y)
+    delta = p * (1 - p) * wy / nb * zerr + 2.0 ** -18 * np.abs(dz) + 2.0 ** -21 * wy * (y != 0) / nb
+    if a["dz16"]:
+        amb = bf16_round(dz - delta) != bf16_round(dz + delta)
+        A = amb * bf16_ulp(dz)
+    else:
+        amb = np.zeros(dz.shape, bool)
+        A = delta
+    dzb = np.abs(ref["dzb"] if "dzb" in ref else dz)
+    hBa, WBa = np.abs(hB), np.abs(WB)
+    lam = a["lam"]
+    b_gWd = c * (B + 2) * u * (dzb.T @ hBa) + A.T @ hBa + (dzb.T @ hA if h_rel > 0 else 0.0)
+    b_gbd = c * (B + 2) * u * dzb.sum(axis=0) + A.sum(axis=0) + 4 * u * (np.abs(ref["gb_dec"]) + lam * np.abs(a["bd"]))
+    b_dh = c * (V + 2) * u * (dzb @ WBa) + A @ WBa
+    ms = np.abs(a["m"]) * a["sg"] * (1 - a["sg"])
+    dpre = ref["dh"] * a["m"] * a["sg"] * (1 - a["sg"])
+    b_dpre = b_dh * ms + 4 * u * np.abs(ref["dh"] * a["m"]) + 8 * u * np.abs(dpre)
+    xa = np.abs(a["xh"])
+    b_gWe = xa.T @ b_dpre + c * (B + 2) * u * (xa.T @ np.abs(dpre)) + 4 * u * (np.abs(ref["gW_enc"]) + lam * np.abs(a["We"]))
+    b_gbe = b_dpre.sum(axis=0) + c * (B + 2) * u * np.abs(dpre).sum(axis=0) + 4 * u * (np.abs(ref["gb_enc"]) + lam * np.abs(a["be"]))
+    out = dict(gW_enc=b_gWe, gb_enc=b_gbe, gb_dec=b_gbd, dh=b_dh, amb=amb, delta=delta)
+    if a["tied"]:
+        out["gW_enc"] = b_gWe + b_gWd
+        out["gW_dec"] = None
+    else:
+        out["gW_dec"] = b_gWd + 4 * u * (np.abs(ref["gW_dec"]) + lam * np.abs(a["Wd_own"]))
+    return out
+
+
+def bf16_check(got, ref, bounds, keys=("gW_enc", "gb_enc", "gW_dec", "gb_dec")):
+    """{key: max |got - ref| / bound} over the elements (inf where a non-finite value or a nonzero error meets a zero
+    bound).  got: arrays by grads() key; keys whose ref is None (tied gW_dec) are skipped.  Passes when every ratio <= 1."""
+    out = {}
+    for k in keys:
+        if ref.get(k) is None or k not in got:
+            continue
+        g = np.asarray(got[k], np.float64)
+        err = np.abs(g - ref[k])
+        bd = bounds[k]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            q = np.where(err == 0, 0.0, err / bd)
+        q = np.where(np.isfinite(g), q, np.inf)
+        out[k] = float(q.max()) if q.size else 0.0
+    return out

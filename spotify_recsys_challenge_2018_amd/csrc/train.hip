@@ -99,61 +99,105 @@ __global__ __launch_bounds__(256) void loss_fixup_kernel(const int32_t* __restri
     }
     __syncthreads();
     float corr = 0.0f;
-    for (int i = row_ptr[row] + tid; i < row_ptr[row + 1]; i += 256) {
-        const int c = col[i];
-        if (c < col_lo || c >= col_hi) continue;
-        const int lc = c - col_lo;
-        const float y = val[i];
-        const float4* w = reinterpret_cast<const float4*>(Wd + (size_t)lc * H);
-        float z = 0.0f;
-        int k = 0;
-        for (; k + 16 <= H4; k += 16) {                        // (16 loads in flight: the same chain, half the round trips)
-            float4 wv[16];
+    // CORR: the row's entries go in windows of CCAP (a row may be of any length): a window's (cdel, ccol) are staged in LDS, then
+    // summed into the correction; wave g takes the entries g, g + 4, ... of the row across all windows (CCAP % 4 == 0), each lane
+    // its hidden quads k4 = lane + 64 j in registers, so the sums run in entry order whatever the row's length
+    constexpr int KJ = CORR ? FIX_MAXH / 256 : 1;
+    float4 cacc_r[KJ];
 #pragma unroll
-            for (int u = 0; u < 16; ++u) wv[u] = w[k + u];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) {
-                if (BF16) wv[u] = make_float4(bf16_value(wv[u].x), bf16_value(wv[u].y), bf16_value(wv[u].z), bf16_value(wv[u].w));
-                const float4 hv = sh[k + u];
-                z = fmaf(wv[u].x, hv.x, z); z = fmaf(wv[u].y, hv.y, z);
-                z = fmaf(wv[u].z, hv.z, z); z = fmaf(wv[u].w, hv.w, z);
+    for (int j = 0; j < KJ; ++j) cacc_r[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int beg = row_ptr[row], end = row_ptr[row + 1];
+    const int wlen = CORR ? CCAP : end - beg;
+    for (int w0 = beg; w0 < end; w0 += wlen) {
+        const int wend = min(w0 + wlen, end);
+        for (int i = w0 + tid; i < wend; i += 256) {
+            const int c = col[i];
+            if (c < col_lo || c >= col_hi) {
+                if (CORR) { cdel[i - w0] = 0.0f; ccol[i - w0] = 0; }      // (another shard's entry: nothing to correct)
+                continue;
             }
-        }
-        for (; k + 8 <= H4; k += 8) {
-            float4 wv[8];
+            const int lc = c - col_lo;
+            const float y = val[i];
+            const float4* w = reinterpret_cast<const float4*>(Wd + (size_t)lc * H);
+            float z = 0.0f;
+            int k = 0;
+            for (; k + 16 <= H4; k += 16) {                        // (16 loads in flight: the same chain, half the round trips)
+                float4 wv[16];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) wv[u] = w[k + u];
+                for (int u = 0; u < 16; ++u) wv[u] = w[k + u];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                if (BF16) wv[u] = make_float4(bf16_value(wv[u].x), bf16_value(wv[u].y), bf16_value(wv[u].z), bf16_value(wv[u].w));
-                const float4 hv = sh[k + u];
-                z = fmaf(wv[u].x, hv.x, z); z = fmaf(wv[u].y, hv.y, z);
-                z = fmaf(wv[u].z, hv.z, z); z = fmaf(wv[u].w, hv.w, z);
+                for (int u = 0; u < 16; ++u) {
+                    if (BF16) wv[u] = make_float4(bf16_value(wv[u].x), bf16_value(wv[u].y), bf16_value(wv[u].z), bf16_value(wv[u].w));
+                    const float4 hv = sh[k + u];
+                    z = fmaf(wv[u].x, hv.x, z); z = fmaf(wv[u].y, hv.y, z);
+                    z = fmaf(wv[u].z, hv.z, z); z = fmaf(wv[u].w, hv.w, z);
+                }
             }
-        }
-        for (; k < H4; ++k) {
-            float4 wv = w[k];
-            const float4 hv = sh[k];
-            if (BF16) wv = make_float4(bf16_value(wv.x), bf16_value(wv.y), bf16_value(wv.z), bf16_value(wv.w));
-            z = fmaf(wv.x, hv.x, z); z = fmaf(wv.y, hv.y, z); z = fmaf(wv.z, hv.z, z); z = fmaf(wv.w, hv.w, z);
-        }
-        z += bias[lc];
-        const float pr = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * z));
-        const float a1 = pr + 1e-10f, a0 = 1.0f - pr + 1e-10f;
-        const float l1 = __builtin_amdgcn_logf(a1), l0 = __builtin_amdgcn_logf(a0);
-        // L(y) - L(0) = -ln2 * y * (log2 a1 - 0.55 log2 a0)
-        corr -= 0.69314718f * y * (l1 - 0.55f * l0);
-        const float dzv = -(y * __builtin_amdgcn_rcpf(a1) - 0.55f * (1.0f - y) * __builtin_amdgcn_rcpf(a0)) *
-                          pr * (1.0f - pr) * inv_nb;
-        if (DZ16) {
-            unsigned short* dst = reinterpret_cast<unsigned short*>(dzT) + (size_t)lc * ldT + row;
-            const unsigned short nw = (unsigned short)(pk_bf16(dzv, 0.0f) & 0xFFFFu);
-            if (CORR) {
-                const int e = i - row_ptr[row];
-                if (e < CCAP) { cdel[e] = __uint_as_float((unsigned)nw << 16) - __uint_as_float((unsigned)*dst << 16); ccol[e] = lc; }
+            for (; k + 8 <= H4; k += 8) {
+                float4 wv[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) wv[u] = w[k + u];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    if (BF16) wv[u] = make_float4(bf16_value(wv[u].x), bf16_value(wv[u].y), bf16_value(wv[u].z), bf16_value(wv[u].w));
+                    const float4 hv = sh[k + u];
+                    z = fmaf(wv[u].x, hv.x, z); z = fmaf(wv[u].y, hv.y, z);
+                    z = fmaf(wv[u].z, hv.z, z); z = fmaf(wv[u].w, hv.w, z);
+                }
             }
-            *dst = nw;
-        } else dzT[(size_t)lc * ldT + row] = dzv;
+            for (; k < H4; ++k) {
+                float4 wv = w[k];
+                const float4 hv = sh[k];
+                if (BF16) wv = make_float4(bf16_value(wv.x), bf16_value(wv.y), bf16_value(wv.z), bf16_value(wv.w));
+                z = fmaf(wv.x, hv.x, z); z = fmaf(wv.y, hv.y, z); z = fmaf(wv.z, hv.z, z); z = fmaf(wv.w, hv.w, z);
+            }
+            z += bias[lc];
+            const float pr = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * z));
+            const float a1 = pr + 1e-10f, a0 = 1.0f - pr + 1e-10f;
+            const float l1 = __builtin_amdgcn_logf(a1), l0 = __builtin_amdgcn_logf(a0);
+            // L(y) - L(0) = -ln2 * y * (log2 a1 - 0.55 log2 a0)
+            corr -= 0.69314718f * y * (l1 - 0.55f * l0);
+            const float dzv = -(y * __builtin_amdgcn_rcpf(a1) - 0.55f * (1.0f - y) * __builtin_amdgcn_rcpf(a0)) *
+                              pr * (1.0f - pr) * inv_nb;
+            if (DZ16) {
+                unsigned short* dst = reinterpret_cast<unsigned short*>(dzT) + (size_t)lc * ldT + row;
+                const unsigned short nw = (unsigned short)(pk_bf16(dzv, 0.0f) & 0xFFFFu);
+                if (CORR) { cdel[i - w0] = __uint_as_float((unsigned)nw << 16) - __uint_as_float((unsigned)*dst << 16); ccol[i - w0] = lc; }
+                *dst = nw;
+            } else dzT[(size_t)lc * ldT + row] = dzv;
+        }
+        if (CORR) {
+            // wave g takes the window's entries g, g + 4, ... (a lane = four hidden units: plain 1 KB row reads, 8 in flight)
+            const int n = wend - w0;
+            __syncthreads();
+            const int wv_ = tid >> 6, ln_ = tid & 63;
+#pragma unroll
+            for (int j = 0; j < KJ; ++j) {
+                const int k4 = ln_ + 64 * j;
+                if (k4 >= H4) break;
+                float4 a = cacc_r[j];
+                int e = wv_;
+                for (; e + 28 < n; e += 32) {
+                    float4 wv[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) wv[u] = reinterpret_cast<const float4*>(Wd + (size_t)ccol[e + 4 * u] * H)[k4];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        const float d = cdel[e + 4 * u];
+                        a.x = fmaf(d, bf16_value(wv[u].x), a.x); a.y = fmaf(d, bf16_value(wv[u].y), a.y);
+                        a.z = fmaf(d, bf16_value(wv[u].z), a.z); a.w = fmaf(d, bf16_value(wv[u].w), a.w);
+                    }
+                }
+                for (; e < n; e += 4) {
+                    const float4 w1 = reinterpret_cast<const float4*>(Wd + (size_t)ccol[e] * H)[k4];
+                    const float d = cdel[e];
+                    a.x = fmaf(d, bf16_value(w1.x), a.x); a.y = fmaf(d, bf16_value(w1.y), a.y);
+                    a.z = fmaf(d, bf16_value(w1.z), a.z); a.w = fmaf(d, bf16_value(w1.w), a.w);
+                }
+                cacc_r[j] = a;
+            }
+            __syncthreads();                                           // (the next window restages cdel / ccol)
+        }
     }
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) corr += __shfl_xor(corr, d);
@@ -161,48 +205,20 @@ __global__ __launch_bounds__(256) void loss_fixup_kernel(const int32_t* __restri
     __syncthreads();
     if (tid == 0) loss_part[row] = (wsum[0] + wsum[1] + wsum[2] + wsum[3]) * inv_nb;
     if (CORR) {
-        // entries outside [col_lo, col_hi) wrote nothing: mark them (a second sweep over the row's entries, in entry order)
-        // (a row holds at most CCAP = 1 024 targets here -- a playlist's <= 250 tracks and their artists, spotify_reader.py:84 --;
-        // a longer one poisons its dh row with NaN rather than dropping entries silently)
-        const bool too_long = row_ptr[row + 1] - row_ptr[row] > CCAP;
-        const int beg = row_ptr[row], n = min(row_ptr[row + 1] - beg, CCAP);
-        __syncthreads();
-        for (int e = tid; e < n; e += 256) { const int c = col[beg + e]; if (c < col_lo || c >= col_hi) { cdel[e] = 0.0f; ccol[e] = 0; } }
-        __syncthreads();
-        // wave g takes the entries g, g + 4, ... (a lane = four hidden units: plain 1 KB row reads, 8 in flight), the four partial
-        // sums meet in LDS and are added in wave order: a fixed order, whatever the timing
+        // the four waves' sums meet in LDS and are added in wave order: a fixed order, whatever the timing
         float4* const cacc = sh;                                    // (the hidden row is no longer needed: [4][H / 4] float4 fit)
-        __syncthreads();
         const int wv_ = tid >> 6, ln_ = tid & 63;
-        for (int k4 = ln_; k4 < (H >> 2); k4 += 64) {
-            float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-            int e = wv_;
-            for (; e + 28 < n; e += 32) {
-                float4 wv[8];
 #pragma unroll
-                for (int u = 0; u < 8; ++u) wv[u] = reinterpret_cast<const float4*>(Wd + (size_t)ccol[e + 4 * u] * H)[k4];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const float d = cdel[e + 4 * u];
-                    a.x = fmaf(d, bf16_value(wv[u].x), a.x); a.y = fmaf(d, bf16_value(wv[u].y), a.y);
-                    a.z = fmaf(d, bf16_value(wv[u].z), a.z); a.w = fmaf(d, bf16_value(wv[u].w), a.w);
-                }
-            }
-            for (; e < n; e += 4) {
-                const float4 w1 = reinterpret_cast<const float4*>(Wd + (size_t)ccol[e] * H)[k4];
-                const float d = cdel[e];
-                a.x = fmaf(d, bf16_value(w1.x), a.x); a.y = fmaf(d, bf16_value(w1.y), a.y);
-                a.z = fmaf(d, bf16_value(w1.z), a.z); a.w = fmaf(d, bf16_value(w1.w), a.w);
-            }
-            cacc[wv_ * (FIX_MAXH / 16) + k4] = a;
+        for (int j = 0; j < KJ; ++j) {
+            const int k4 = ln_ + 64 * j;
+            if (k4 < H4) cacc[wv_ * (FIX_MAXH / 16) + k4] = cacc_r[j];
         }
         __syncthreads();
-        for (int k4 = tid; k4 < (H >> 2); k4 += 256) {
+        for (int k4 = tid; k4 < H4; k4 += 256) {
             const float4 p0 = cacc[k4], p1 = cacc[(FIX_MAXH / 16) + k4], p2 = cacc[2 * (FIX_MAXH / 16) + k4], p3 = cacc[3 * (FIX_MAXH / 16) + k4];
             reinterpret_cast<float4*>(corr_out + (size_t)row * H)[k4] =
-                too_long ? make_float4(__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""))
-                         : make_float4(((p0.x + p1.x) + p2.x) + p3.x, ((p0.y + p1.y) + p2.y) + p3.y, ((p0.z + p1.z) + p2.z) + p3.z,
-                                       ((p0.w + p1.w) + p2.w) + p3.w);
+                make_float4(((p0.x + p1.x) + p2.x) + p3.x, ((p0.y + p1.y) + p2.y) + p3.y, ((p0.z + p1.z) + p2.z) + p3.z,
+                            ((p0.w + p1.w) + p2.w) + p3.w);
         }
     }
 }

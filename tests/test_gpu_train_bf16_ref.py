@@ -1,0 +1,233 @@
+"""GPU (-m gpu): the bf16 training step (dae_set_train_dtype(BF16), BASELINE.json configs[3]) against the rounding-aware
+float64 reference (oracle/dae_numpy.py grads_bf16) under the element-wise bound bf16_bounds derives, and the same case in
+fp32 against grads() at the fp32 tolerance of tests/test_gpu_train.py (rtol 2e-4, atol 2e-7).  The cases reach every
+kernel variant train_plan / train_decode_backward select: the fused K5 + K7 launch with the fix-up's correction (hidden
+256, batch > 64), the packed K5 with the bf16 dz store (hidden 128 / 256 with batch <= 64 / 384 / 512), the bf16 forward
+with fp32 backward GEMMs (hidden 64 / 96), K6's full-batch form (32-row padded batch 256) and the rest; vocabularies of
+one and two 32-row tiles, partial last tiles, more tiles than workgroups; targets at column 0, V - 1 and in the last
+partial tile; trailing rows empty in x, in y or both; target rows longer than the fix-up's staging window (1 024)."""
+import numpy as np
+import pytest
+
+import oracle
+from oracle import dae_numpy as dn
+from spotify_recsys_challenge_2018_amd import _lib
+from spotify_recsys_challenge_2018_amd.sharding import HipTrainStages, all_shard_bounds
+from spotify_recsys_challenge_2018_amd.utils.synthetic import make_playlists, make_weights
+
+pytestmark = pytest.mark.gpu
+KEYS = ("gW_enc", "gb_enc", "gW_dec", "gb_dec")
+OUT = dict(gW_enc="gWe", gb_enc="gbe", gW_dec="gWd", gb_dec="gbd")
+SEED = 4242
+
+
+def _dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _csr(dense):
+    r, c = np.nonzero(dense)
+    rp = np.zeros(dense.shape[0] + 1, np.int32)
+    np.add.at(rp, r + 1, 1)
+    return np.cumsum(rp).astype(np.int32), c.astype(np.int32), dense[r, c].astype(np.float32)
+
+
+def _uniform(stream, rows, cols):
+    l = oracle.lib()
+    return np.array([[l.orc_uniform(SEED, stream, int(r), int(c)) for c in cols] for r in rows], np.float32)
+
+
+def make_case(V, nt, H, B, tied=False, lam=0.0, ikp=1.0, kp=1.0, n_batch=None, yvals=False, long_rows=(), seed=6):
+    W_enc, b_enc, W_dec, b_dec = make_weights(V, H, seed=4, bias="zipf", n_tracks=nt, tied=tied)
+    b_enc = (np.random.default_rng(2).standard_normal(H) * 0.1).astype(np.float32)
+    pos, ones, _ = make_playlists(B, nt, V - nt, seed=seed, seed_counts=(3, 9, 20))
+    x = dn.sparse_to_dense(pos[pos[:, 1] < nt], ones[pos[:, 1] < nt], B, V)
+    y = dn.sparse_to_dense(pos, np.ones(len(pos), np.float32), B, V)
+    last_tile = V - 1 - (V % 32) // 2 if V % 32 else V - 17
+    for r, c in ((0, 0), (min(1, B - 1), V - 1), (min(2, B - 1), max(0, last_tile))):
+        y[r, c] = 1.0
+    rng = np.random.default_rng(seed + 1)
+    for r, n in enumerate(long_rows):                      # rows with n targets (distinct columns)
+        y[r] = 0.0
+        y[r, rng.choice(V, n, replace=False)] = 1.0
+    if yvals:                                              # targets of other values than 1
+        nz = np.argwhere(y[:, :V] != 0)
+        y[nz[::3, 0], nz[::3, 1]] = 0.5
+        y[nz[1::3, 0], nz[1::3, 1]] = 2.0
+    if B >= 6 and not long_rows:                           # the padded last batch: trailing rows empty in x, in y, in both
+        x[B - 3] = 0.0
+        y[B - 2] = 0.0
+        x[B - 1] = 0.0
+        y[B - 1] = 0.0
+    xr, xc, xv = _csr(x)
+    yr, yc, yv = _csr(y)
+    im = None
+    if ikp < 1.0:
+        im = np.ones((B, V))
+        for r in range(B):
+            cols = xc[xr[r]:xr[r + 1]]
+            im[r, cols] = np.floor(np.float32(ikp) + _uniform(0, [r], cols)[0])
+    hm = np.floor(np.float32(kp) + _uniform(1, range(B), range(H))) if kp < 1.0 else None
+    h = oracle.encode(xr, xc, xv, W_enc, b_enc, ikp=ikp, kp=kp, seed=SEED)
+    return dict(V=V, H=H, B=B, tied=tied, lam=lam, ikp=ikp, kp=kp, n_batch=n_batch or B, x=x, y=y,
+                csr=(xr, xc, xv, yr, yc, yv), W=(W_enc, b_enc, W_dec, b_dec), im=im, hm=hm, h=h)
+
+
+def run_step(ctx, c, dtype):
+    import torch
+    V, H, B = c["V"], c["H"], c["B"]
+    P = _lib._ptr
+    csr = [_dev(a if a.size else np.zeros(1, a.dtype)) for a in c["csr"]]
+    d = [_dev(a) for a in c["W"]]
+    out = dict(gWe=torch.zeros((V, H), device="cuda"), gbe=torch.zeros(H, device="cuda"),
+               gWd=torch.zeros((V, H), device="cuda"), gbd=torch.zeros(V, device="cuda"), cost=torch.zeros(1, device="cuda"))
+    ctx.set_train_dtype(dtype)
+    ctx.check(ctx.lib.dae_train_forward_backward(
+        ctx.h, P(csr[0]), P(csr[1]), P(csr[2]), P(csr[3]), P(csr[4]), P(csr[5]), P(d[0]), P(d[1]), P(d[2]), P(d[3]),
+        V, H, B, c["n_batch"], 1 if c["tied"] else 0, float(c["ikp"]), float(c["kp"]), SEED, float(c["lam"]),
+        P(out["gWe"]), P(out["gbe"]), None if c["tied"] else P(out["gWd"]), P(out["gbd"]), P(out["cost"])))
+    torch.cuda.synchronize()
+    ctx.set_train_dtype(_lib.DAE_DTYPE_F32)
+    o = {k: v.cpu().numpy() for k, v in out.items()}
+    return {k: o[OUT[k]] for k in KEYS} | {"cost": float(o["cost"][0])}
+
+
+def reference(c, **kw):
+    W_enc, b_enc, W_dec, b_dec = c["W"]
+    return dn.grads_bf16(c["x"], c["y"], W_enc, b_enc, W_enc if c["tied"] else W_dec, b_dec, n_batch=c["n_batch"],
+                         tied=c["tied"], reg_lambda=c["lam"], input_keep_mask=c["im"], ikp=c["ikp"],
+                         hidden_keep_mask=c["hm"], kp=c["kp"], h=c["h"], **kw)
+
+
+def check_bf16(got, c, cost_rtol=1e-5, h_rel=0.0, witness=False):
+    ref = reference(c)
+    r = dn.bf16_check(got, ref, dn.bf16_bounds(ref, h_rel=h_rel))
+    print("bf16 error / bound:", {k: round(v, 4) for k, v in r.items()})
+    assert all(np.isfinite(got[k]).all() for k in KEYS if ref[k] is not None)
+    assert max(r.values()) <= 1.0, r
+    assert abs(got["cost"] - ref["cost"]) <= cost_rtol * abs(ref["cost"]), (got["cost"], ref["cost"])
+    if witness:
+        # the bf16 path really ran: the result fails the same bound around the all-fp32-operand reference on gW_dec
+        # (gW_enc for the tied model, which holds the decoder gradient)
+        r32 = reference(c, round_dz=False, round_ops=False)
+        k = "gW_enc" if c["tied"] else "gW_dec"
+        w = dn.bf16_check(got, r32, dn.bf16_bounds(r32, h_rel=h_rel), keys=(k,))[k]
+        print("against the fp32-operand reference: %s %.3g" % (k, w))
+        assert w > 1.0, w
+    return r
+
+
+def check_f32(got, c):
+    W_enc, b_enc, W_dec, b_dec = c["W"]
+    ref = dn.grads(c["x"], c["y"], W_enc, b_enc, W_enc if c["tied"] else W_dec, b_dec, n_batch=c["n_batch"],
+                   tied=c["tied"], reg_lambda=c["lam"], input_keep_mask=c["im"], ikp=c["ikp"],
+                   hidden_keep_mask=c["hm"], kp=c["kp"])
+    assert abs(got["cost"] - ref["cost"]) <= 1e-5 * abs(ref["cost"])
+    for k in KEYS:
+        if ref[k] is not None:
+            assert np.allclose(got[k], ref[k], rtol=2e-4, atol=2e-7), k
+
+
+CASES = [
+    # V, nt, H, B, options                                           what it reaches
+    (20000, 16000, 256, 65, dict(ikp=0.75, kp=0.8)),                 # fused K5 + K7 (B > 64), > tiles than workgroups
+    (3001, 2500, 256, 64, dict(tied=True, lam=0.01)),                # hidden 256, B <= 64: packed K5, K7; tied, lambda
+    (2001, 1600, 256, 225, dict(n_batch=256, kp=0.8)),               # fused; K6 full form (padded batch 256); n_batch > B
+    (2000, 1600, 256, 224, dict(ikp=0.75)),                          # fused; K6 general form (padded batch 224)
+    (2003, 1600, 256, 250, dict(tied=True)),                         # fused, tied
+    (1500, 1200, 128, 37, dict(yvals=True, kp=0.8)),                 # hidden 128; targets 0.5 / 2.0
+    (20000, 16000, 128, 256, dict()),                                # hidden 128, full batch, many tiles
+    (33, 20, 512, 250, dict(kp=0.8)),                                # two tiles (the second of one row); hidden 512
+    (32, 20, 384, 5, dict(tied=True)),                               # one tile; hidden 384
+    (1000, 800, 64, 1, dict()),                                      # hidden 64: bf16 forward, fp32 backward; one row
+    (999, 800, 96, 256, dict(ikp=0.75, kp=0.8)),                     # hidden 96 (one 32-unit tile per wave)
+    (1100, 900, 128, 65, dict()),                                    # hidden 128 across the 64 / 65 line
+]
+
+
+@pytest.mark.parametrize("V,nt,H,B,opt", CASES)
+def test_bf16_step_against_the_rounding_aware_reference(V, nt, H, B, opt):
+    c = make_case(V, nt, H, B, **opt)
+    ctx = _lib.Context(0)
+    try:
+        b16 = run_step(ctx, c, _lib.DAE_DTYPE_BF16)
+        f32 = run_step(ctx, c, _lib.DAE_DTYPE_F32)
+    finally:
+        ctx.close()
+    check_bf16(b16, c, witness=(H % 128 == 0))
+    check_f32(f32, c)
+
+
+LONG = (1023, 1024, 1025, 2500)
+
+
+@pytest.mark.parametrize("H,B", [(256, 80), (128, 40)])
+def test_long_target_rows(H, B):
+    """Target rows of 1 023 .. 2 500 entries (the fix-up's correction stages 1 024 at a time): finite, within the bound."""
+    c = make_case(6000, 5000, H, B, long_rows=LONG, kp=0.8)
+    ctx = _lib.Context(0)
+    try:
+        b16 = run_step(ctx, c, _lib.DAE_DTYPE_BF16)
+        f32 = run_step(ctx, c, _lib.DAE_DTYPE_F32)
+    finally:
+        ctx.close()
+    check_bf16(b16, c)
+    check_f32(f32, c)
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_long_target_rows_through_the_sharded_stages(world):
+    """The same rows through HipTrainStages (the shard boundaries cut every long row): concatenated gradients within the
+    bound; h comes from an all-reduced pre-activation there (not bit-exact), so h may round either way near a midpoint."""
+    import torch
+    V, nt, H, B = 6000, 5000, 256, 80
+    c = make_case(V, nt, H, B, long_rows=LONG)
+    W_enc, b_enc, W_dec, b_dec = c["W"]
+    ctx = _lib.Context(0)
+    ctx.set_train_dtype(_lib.DAE_DTYPE_BF16)
+    st = HipTrainStages(ctx)
+    x = tuple(_dev(a) for a in c["csr"][:3])
+    y = tuple(_dev(a) for a in c["csr"][3:])
+    be = _dev(b_enc)
+    sh = []
+    bounds = all_shard_bounds(V, world)
+    assert all(any(lo < col < hi for col in c["csr"][4][c["csr"][3][0]:c["csr"][3][1]]) for lo, hi in bounds)
+    for lo, hi in bounds:
+        d = dict(lo=lo, hi=hi, We=_dev(W_enc[lo:hi]), bd=_dev(b_dec[lo:hi]), Wd=_dev(W_dec[lo:hi]))
+        d.update(gWe=torch.zeros((hi - lo, H), device="cuda"), gbd=torch.zeros(hi - lo, device="cuda"),
+                 gWd=torch.zeros((hi - lo, H), device="cuda"), gbe=torch.zeros(H, device="cuda"),
+                 pre=torch.zeros((B, H), device="cuda"), dh=torch.zeros((B, H), device="cuda"),
+                 cost=torch.zeros(1, device="cuda"))
+        sh.append(d)
+    for d in sh:
+        st.encode(x, d["We"], d["lo"], d["hi"], 1.0, SEED, d["pre"])
+    pre = sum(d["pre"] for d in sh)
+    for d in sh:
+        st.decode(pre, be, y, d["We"], d["Wd"], d["bd"], d["lo"], d["hi"], B, False, 1.0, SEED, 0.0,
+                  d["gWd"], d["gbd"], d["dh"], d["cost"])
+    dh = sum(d["dh"] for d in sh)
+    cost = float(sum(d["cost"] for d in sh).item())
+    for d in sh:
+        st.decode(pre, be, y, d["We"], d["Wd"], d["bd"], d["lo"], d["hi"], B, False, 1.0, SEED, 0.0,
+                  d["gWd"], d["gbd"], d["dh"], d["cost"])      # re-establish this shard's scratch
+        st.finish(dh, x, d["We"], be, d["Wd"], d["bd"], d["lo"], d["hi"], False, 1.0, 1.0, SEED, 0.0,
+                  d["gWe"], d["gbe"], d["gWd"], d["gbd"])
+    torch.cuda.synchronize()
+    got = dict(gW_enc=torch.cat([d["gWe"] for d in sh]).cpu().numpy(), gb_enc=sh[0]["gbe"].cpu().numpy(),
+               gW_dec=torch.cat([d["gWd"] for d in sh]).cpu().numpy(), gb_dec=torch.cat([d["gbd"] for d in sh]).cpu().numpy(),
+               cost=cost)
+    ctx.close()
+    check_bf16(got, c, h_rel=2.0 ** -20)
+
+
+def test_full_size_bf16_step_against_the_rounding_aware_reference():
+    """V = 170 000, H = 256, B = 256 (the model default shape): all four gradients within the element-wise bound, the
+    cost within 1e-4 relative."""
+    c = make_case(170000, 140000, 256, 256, ikp=0.75, kp=0.8)
+    ctx = _lib.Context(0)
+    try:
+        b16 = run_step(ctx, c, _lib.DAE_DTYPE_BF16)
+    finally:
+        ctx.close()
+    check_bf16(b16, c, cost_rtol=1e-4, witness=True)
