@@ -612,8 +612,8 @@ int dae_launch_title_conv_backward(dae_ctx* ctx, const int32_t* titles, int B, i
     if (rc) return rc;
     p.argmax = const_cast<int32_t*>(argmax);
     p.feat_raw = const_cast<float*>(feat_raw);
+    if (F > 256) return dae_fail(ctx, DAE_ERR_ARG, "filter_num %d > 256", F);       // title_wgrad_kernel: one workgroup of F
     DAE_HIP_CHECK(ctx, hipMemsetAsync(g_emb, 0, (size_t)n_char * E * sizeof(float), ctx->stream));
-    if (F > 256) return dae_fail(ctx, DAE_ERR_ARG, "filter_num %d > 256", F);
     p.B = B;
     rc = dae_reserve(ctx, ctx->train_c, (size_t)B * n_sizes * F * sizeof(float));
     if (rc) return rc;

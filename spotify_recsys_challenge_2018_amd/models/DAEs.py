@@ -557,7 +557,8 @@ class DAE_tied:
         scores, the lists leave through the copy engine.  Rows are scored independently: every feed gets the bits
         `recommend` returns for it alone (tests/test_gpu_stream_loop.py)."""
         if self._score_shard is not None:
-            for x_positions, x_ones, seeds, n_rows in feeds:         # the exchange is a collective: no run-ahead
+            for f in feeds:                                           # the exchange is a collective: no run-ahead
+                x_positions, x_ones, seeds, n_rows = f[:4]
                 idx, score = self.recommend(x_positions, x_ones, seeds, k=k, n_rows=n_rows, dtype=dtype)
                 yield idx, (score if want_scores else None)
             return
@@ -573,9 +574,15 @@ class DAE_tied:
             return
         for f in feeds:                  # (device_csr = False: host-built CSRs -- the per-batch call)
             x_positions, x_ones, seeds, n_rows = f[:4]
-            kw = {} if len(f) <= 4 else {"titles": f[4], "titles_use": f[5] if len(f) > 5 else None}
-            idx, score = self.recommend(x_positions, x_ones, seeds, k=k, n_rows=n_rows, dtype=dtype, **kw)
+            idx, score = self.recommend(x_positions, x_ones, seeds, k=k, n_rows=n_rows, dtype=dtype, **self._feed_title_kw(f))
             yield idx, (score if want_scores else None)
+
+    def _feed_title_kw(self, f):
+        """The title arguments of a 5- or 6-item feed, for `recommend`: only a DAE_title takes them; a plain DAE scores the
+        feed's first four items and ignores the rest."""
+        if len(f) <= 4 or not isinstance(self, DAE_title):
+            return {}
+        return {"titles": f[4], "titles_use": f[5] if len(f) > 5 else None}
 
     def _native_pipe(self, dtype, k, want_scores):
         """The model's dae_pipeline for (dtype, k, scores wanted): created on first use, again after the weights changed."""
@@ -660,7 +667,7 @@ class DAE_tied:
                             titles[:nt] = np.asarray(t, np.int64).reshape(-1, L_)[:nt]
                         use = np.zeros(self.n_batch, np.float32)
                         use[:min(u.size, nt)] = u[:nt]                                # (no title, no use)
-                unfit = len(f) > 4 and pipe.title_len is None
+                unfit = len(f) > 4 and pipe.title_len is None and isinstance(self, DAE_title)     # (a plain DAE ignores titles)
                 if not unfit:                                    # a feed larger than a launch slot: through recommend(), not a DaeError
                     nnz_f = int(np.shape(x_positions)[0]) if np.ndim(x_positions) == 2 else len(x_positions)
                     unfit = nnz_f > pipe.max_nnz
@@ -668,8 +675,8 @@ class DAE_tied:
                     pipe.flush()                                 # a feed the pipeline does not take: in order, through recommend()
                     while pipe.pending:
                         yield out(pipe.poll(True))
-                    kw = {} if len(f) <= 4 else {"titles": f[4], "titles_use": f[5] if len(f) > 5 else None}
-                    idx, score = self.recommend(x_positions, x_ones, seeds, k=k, n_rows=n_rows, dtype=dtype, **kw)
+                    idx, score = self.recommend(x_positions, x_ones, seeds, k=k, n_rows=n_rows, dtype=dtype,
+                                                **self._feed_title_kw(f))
                     yield idx, (score if want_scores else None)
                     continue
                 while not pipe.submit(x_positions, x_ones, self.n_batch, titles, use):      # every lane full: hand the oldest lists out first
@@ -954,6 +961,7 @@ class DAE_title(DAE):
         if titles is None:
             raise ValueError("DAE_title trains the title scorer: titles are required")
         tm = self.title_model
+        tm.check_trainable()
         seed = int(self._rng.randint(0, 2 ** 31 - 1))
         self._ensure_packed()
         self.ctx.bind_stream()

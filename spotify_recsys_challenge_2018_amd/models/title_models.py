@@ -21,6 +21,13 @@ import numpy as np
 from .. import _lib
 
 
+T_MAX_EMB = 128          # csrc/title.hip T_MAX_EMB
+T_MAX_LEN = 64           # csrc/title.hip T_MAX_LEN
+T_MAX_SIZES = 8          # csrc/dae_internal.h DAE_TITLE_MAX_SIZES
+T_MAX_TRAIN_FILTERS = 256    # title_wgrad_kernel: one thread per filter, one workgroup of at most 256
+T_MAX_F32_FEATURES = 1024    # the fp32 decoder prepack (dae_launch_prepack_f32): hidden <= 1024
+
+
 def get_model(conf):
     """models/title_get.py:11-26."""
     if conf.char_model != 'Char_CNN':
@@ -46,6 +53,19 @@ class Char_CNN:
         # feature row length the GEMM kernels take: a multiple of 64 lets the backward GEMMs own two hidden tiles
         # per wave (400 features -> 448; 416 measured 4 % slower, 512 no better)
         self.ld = (self.n_feat + 63) // 64 * 64
+        # the shapes csrc/title.hip runs (title_fill, the LDS image of a title, the table): refused here, before any launch
+        if self.embedding > T_MAX_EMB:
+            raise ValueError("[TITLE] char_emb = %d: the title kernels take at most %d" % (self.embedding, T_MAX_EMB))
+        if not 1 <= self.input_len <= T_MAX_LEN:
+            raise ValueError("[TITLE] strmaxlen = %d: the title kernels take 1 to %d characters" % (self.input_len, T_MAX_LEN))
+        if not 1 <= len(self.filter_sizes) <= T_MAX_SIZES:
+            raise ValueError("[TITLE] filter_size has %d sizes: the title kernels take 1 to %d"
+                             % (len(self.filter_sizes), T_MAX_SIZES))
+        for fs in self.filter_sizes:
+            if not 1 <= fs <= self.input_len:
+                raise ValueError("[TITLE] filter_size %d: every size must be in [1, strmaxlen = %d]" % (fs, self.input_len))
+        if self.filter_num < 1:
+            raise ValueError("[TITLE] filter_num = %d: must be at least 1" % self.filter_num)
         self.device_index = int(getattr(conf, "device_index", 0))
         self.init_seed = int(getattr(conf, "title_init_seed", 0))
         self.learning_rate = float(getattr(conf, "title_lr", 0.001))
@@ -188,7 +208,21 @@ class Char_CNN:
             float(keep_prob), int(seed), P(feat), self.ld, P(arg), P(raw)))
         return (feat, d_t, arg, raw) if keep_for_backward else feat
 
+    def check_trainable(self):
+        """A training step's shape limits, checked before any of its kernels runs."""
+        if self.filter_num > T_MAX_TRAIN_FILTERS:
+            raise ValueError("[TITLE] filter_num = %d: training takes at most %d filters per size"
+                             % (self.filter_num, T_MAX_TRAIN_FILTERS))
+        self._check_f32_features()
+
+    def _check_f32_features(self):
+        if self.ld > T_MAX_F32_FEATURES:
+            raise ValueError("[TITLE] filter_num x filter_size = %d features (%d padded): fp32 title scoring takes at most %d"
+                             % (self.n_feat, self.ld, T_MAX_F32_FEATURES))
+
     def _ensure_packed(self, dtype=_lib.DAE_DTYPE_F32, features_table=True):
+        if dtype == _lib.DAE_DTYPE_F32:
+            self._check_f32_features()
         if features_table:                   # (scoring; a training step passes False: its forward keeps argmax / raw features)
             self._ensure_features_table()
         if self._packed_dirty:
@@ -227,6 +261,7 @@ class Char_CNN:
                           seed, cost_out):
         """Gradients of the mixed-score loss w.r.t. the title variables, then one TF1-Adam step on each."""
         import torch
+        self.check_trainable()
         g = self._train_state()
         ctx, lib, P = self.ctx, self.ctx.lib, _lib._ptr
         B, V = z_title.shape

@@ -116,24 +116,6 @@ def test_table_features_follow_the_variables_and_agree_with_the_chains():
     assert np.array_equal(again.view(np.uint32), chain2.view(np.uint32))
 
 
-def _fma32(a, b, c):
-    """fmaf(a, b, c) for float32 arrays, exactly: the product is exact in float64 (24 + 24 bits); the sum is rounded
-    to ODD in float64 (TwoSum gives its error), so the final rounding to float32 is the single rounding of the exact
-    a * b + c (Boldo & Melquiond: 53 >= 2 * 24 + 2)."""
-    p = a.astype(np.float64) * b.astype(np.float64)
-    c = c.astype(np.float64)
-    s = p + c
-    bb = s - p
-    err = (p - (s - bb)) + (c - bb)                    # p + c == s + err exactly
-    bits = s.view(np.int64)
-    inexact = err != 0.0
-    # the exact sum lies between s and its neighbour in the direction of err: of the two, take the one with an odd
-    # last bit.  s is even here -> step one ulp towards err (same sign as s: magnitude up, else magnitude down).
-    step = np.where((err > 0) == (s > 0), 1, -1).astype(np.int64)
-    adj = np.where(inexact & ((bits & 1) == 0) & (s != 0.0), bits + step, bits)
-    return adj.view(np.float64).astype(np.float32)
-
-
 def test_features_are_the_fmaf_chain_bit_for_bit():
     """csrc/title.hip computes the convolutions with v_mfma_f32_32x32x2_f32, accumulators preset to the bias: the same
     chain acc = fmaf(x[q], W[q][f], acc), q ascending, as the scalar kernels -- same bits, same
@@ -158,7 +140,7 @@ def test_features_are_the_fmaf_chain_bit_for_bit():
         win = np.stack([x[:, p:p + fs, :].reshape(B, fs * 50) for p in range(P)], axis=1)   # [B, P, q]
         acc = np.broadcast_to(b, (B, P, 100)).astype(np.float32).copy()
         for q in range(fs * 50):
-            acc = _fma32(win[:, :, q:q + 1], W[q][None, None, :], acc)
+            acc = tn.fma32(win[:, :, q:q + 1], W[q][None, None, :], acc)
         conv = np.maximum(acc, np.float32(0.0))
         want, want_arg = conv.max(axis=1), conv.argmax(axis=1)                              # argmax: first maximum
         got = raw[:, i * 100:(i + 1) * 100]

@@ -37,15 +37,17 @@ def _titles(B, seed=0):
     return t
 
 
-def _model(tmp_path, conf, bias="zipf", w_scale=1.0, title_seed=4, feat_scale=1.0, out_scale=1.0, flat_title=False, boost=None):
+def _model(tmp_path, conf, bias="zipf", w_scale=1.0, title_seed=4, feat_scale=1.0, out_scale=1.0, flat_title=False, boost=None,
+           filter_num=100):
     W_enc, b_enc, W_dec, b_dec = make_weights(conf.n_input, conf.hidden, seed=1, bias=bias, n_tracks=conf.n_tracks)
     W_dec = (W_dec * np.float32(w_scale)).astype(np.float32)
     p = tmp_path / ("w_dae_%s_%g" % (bias, w_scale))
     with open(p, "wb") as f:
         pickle.dump([W_enc, W_dec, b_enc, b_dec], f)
     conf.DAEval = str(p)
+    conf.filter_num = filter_num
     mt = get_model(conf)
-    host = tn.make_params(41, 50, FS, 100, conf.n_output, seed=title_seed)
+    host = tn.make_params(41, 50, FS, filter_num, conf.n_output, seed=title_seed)
     if feat_scale != 1.0:                              # features far outside [0, 1]: the bound scales with the row's largest
         for i in range(len(FS)):
             host["Conv_W%d" % i] = (host["Conv_W%d" % i] * np.float32(feat_scale)).astype(np.float32)
@@ -98,6 +100,29 @@ def test_exact_title_mix_returns_the_fp32_lists(tmp_path, bias, w_scale, feat_sc
         _same(got, want)
         st = tm.ctx.exact_stats_read()
         assert st["rows"] == conf.batch and st["candidates_per_row"] >= min(k, 1)      # the two-GEMM launches ran
+        assert tm.ctx.exact_guard_read()[0] == 0
+    assert not getattr(m, "_guard_fallbacks", 0)
+
+
+@pytest.mark.parametrize("filter_num", [112, 97])
+def test_exact_title_mix_other_feature_counts(tmp_path, filter_num):
+    """The exact mix at its feature row length 448 with 448 real features (4 x 112: no zero column) and with 388 (4 x 97:
+    60 zero columns, more than the shipped 48): the fp32 lists, indices and score bits."""
+    conf = _conf()
+    m = _model(tmp_path, conf, filter_num=filter_num)
+    tm = m.title_model
+    assert tm.ld == 448 and tm.n_feat == 4 * filter_num
+    for trial, k in enumerate((100, 37)):
+        pos, ones, seeds = _feed(conf, 15 + trial, empty_rows=(3,))
+        titles = _titles(conf.batch, seed=16 + trial)
+        use = (np.arange(conf.batch) % 3 != trial).astype(np.float32)
+        use[3] = 1.0
+        want = m.recommend(pos, ones, seeds, k=k, titles=titles, titles_use=use, dtype="f32")
+        with warnings.catch_warnings():
+            warnings.simplefilter("error")
+            got = m.recommend(pos, ones, seeds, k=k, titles=titles, titles_use=use, dtype="exact_bf16")
+        _same(got, want)
+        assert tm.ctx.exact_stats_read()["rows"] == conf.batch                 # the two-GEMM launch ran
         assert tm.ctx.exact_guard_read()[0] == 0
     assert not getattr(m, "_guard_fallbacks", 0)
 
