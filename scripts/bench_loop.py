@@ -12,7 +12,7 @@ import numpy as np
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from spotify_recsys_challenge_2018_amd import _lib                                        # noqa: E402
-if os.environ.get("DAE_LIB_AB"):       # A/B against another build of the library (scripts/build_exp.py)
+if os.environ.get("DAE_LIB_AB"):       # A/B against another build of the library
     _lib.LIB_PATH = os.environ["DAE_LIB_AB"]
 from spotify_recsys_challenge_2018_amd.models.DAEs import DAE, SEEDS_FROM_INPUT          # noqa: E402
 from spotify_recsys_challenge_2018_amd.utils.synthetic import make_playlists, make_weights   # noqa: E402

@@ -20,9 +20,6 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
          # (only what is left of it: "loop not unrolled" notes for `#pragma unroll` loops of the generic-hidden-size template
          # instances of decode_f32_kernel, whose trip counts are run-time values there)
          "-Wno-pass-failed"]
-if os.environ.get("DAE_EXPERIMENTS"):          # A/B switches and stage early-outs (csrc/dae_internal.h); never the default
-    FLAGS.append("-DDAE_EXPERIMENTS")
-FLAGS += os.environ.get("DAE_EXTRA_FLAGS", "").split()        # e.g. -DDAE_SMALL_PRIO=0 for an A/B build
 
 
 def _deps_mtime():

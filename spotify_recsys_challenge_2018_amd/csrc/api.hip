@@ -474,11 +474,7 @@ static int topk_phase_a(dae_ctx* ctx, const dae_packed* pk, const dae_rowgeom& g
     const int n_simd = g.nb_rg * 4;
     int rounds = (int)(((double)ntiles / 8.0) / n_simd + 0.5);
     if (rounds < 1) rounds = 1;
-    static const int rounds_env = dae_exp_env("DAE_SAMPLE_ROUNDS") ? atoi(dae_exp_env("DAE_SAMPLE_ROUNDS")) : 0;   // experiments
-    if (rounds_env > 0) rounds = rounds_env;
     int S = (ntiles + rounds * n_simd - 1) / (rounds * n_simd);
-    static const int s_env = dae_exp_env("DAE_SAMPLE_S") ? atoi(dae_exp_env("DAE_SAMPLE_S")) : 0;                   // experiments
-    if (s_env > 1) S = s_env;
     // exact mode: the same launches whatever the size (a small problem's "sample" is every tile: S = 1)
     if (exact && S < 2) S = 1;
     const bool fused = (S >= 2 || exact) && nrank > 0;
@@ -495,12 +491,11 @@ static int topk_phase_a(dae_ctx* ctx, const dae_packed* pk, const dae_rowgeom& g
     // Same sample tiles, same logits; the groups (the tiles one wave decodes, n_ws places apart in the bias order) change, i.e.
     // only how tight tau is.  Only where that kernel applies (bf16 image of hidden 256, 128-row groups, no title mix).
     const bool mixed = ctx->mixT != nullptr;               // dae_set_score_mix: the launches rank the MIXED score
-    static const bool no_whole = dae_exp_env("DAE_BF16_KEEP_SAMPLE") != nullptr;       // A/B
     // does a launch of geometry gg take per-WAVE groups?  (the one predicate behind `wave_groups` below)
     auto takes_wave_groups = [&](const dae_rowgeom& gg) {
         const int n_ws = gg.nb_rg * gg.waves;
         const bool enough = (int64_t)((n_samp + n_ws - 1) / n_ws) * gg.nb_rg * 32 >= 4 * (int64_t)k;      // (else: one value per wave slot)
-        return fused && enough && dtype == DAE_DTYPE_BF16 && !mixed && (!no_whole || exact) && dae_sample_wave_groups(gg, pk->Hp, n_samp);
+        return fused && enough && dtype == DAE_DTYPE_BF16 && !mixed && dae_sample_wave_groups(gg, pk->Hp, n_samp);
     };
     dae_rowgeom gA = g;
     {
@@ -510,8 +505,6 @@ static int topk_phase_a(dae_ctx* ctx, const dae_packed* pk, const dae_rowgeom& g
         // launches of few row groups, ~8 from 8 row groups on
         const int per_slot = g.n_rg >= 8 ? 8 : 4;
         int nbA = ctx->overlap_hint ? ((n_samp + 8 * per_slot - 1) / (8 * per_slot) + DAE_NUM_XCD - 1) / DAE_NUM_XCD * DAE_NUM_XCD : g.nb_rg;
-        static const int nba_env = dae_exp_env("DAE_SAMPLE_NB") ? atoi(dae_exp_env("DAE_SAMPLE_NB")) : 0;            // A/B (experiments)
-        if (nba_env > 0) nbA = nba_env / DAE_NUM_XCD * DAE_NUM_XCD;
         if (nbA < DAE_NUM_XCD) nbA = DAE_NUM_XCD;
         if (nbA < g.nb_rg) {
             dae_rowgeom t = g;
@@ -534,12 +527,11 @@ static int topk_phase_a(dae_ctx* ctx, const dae_packed* pk, const dae_rowgeom& g
         // bf16 launches whose sample takes several rounds of the phase-A workgroups (many rows: few workgroups per row group): the
         // sample re-dealt so that a workgroup's tiles of a round come from different popularity bands (decode_f32.hip
         // tile_band_kernel); the list is this context's, rebuilt when the order or the geometry changes
-        static const bool no_band = dae_exp_env("DAE_NO_BAND") != nullptr;                    // A/B (experiments build)
         const int n_ws_s = gA.nb_rg * gA.waves;
         // (not when the launch takes per-WAVE groups -- see wave_groups below: there the plain order IS band-dealt)
         const bool wg_early = dtype == DAE_DTYPE_BF16 && ctx->mixT == nullptr && dae_sample_wave_groups(gA, pk->Hp, n_samp) &&
                               ((int64_t)((n_samp + n_ws_s - 1) / n_ws_s) * gA.nb_rg * 32 >= 4 * (int64_t)k);
-        if (dtype == DAE_DTYPE_BF16 && n_samp > n_ws_s && !no_band && !wg_early) {
+        if (dtype == DAE_DTYPE_BF16 && n_samp > n_ws_s && !wg_early) {
             const void* band_was = ctx->tile_band.p;
             rc = dae_reserve(ctx, ctx->tile_band, (size_t)ntiles * sizeof(int));
             if (rc) return rc;
@@ -568,8 +560,7 @@ static int topk_phase_a(dae_ctx* ctx, const dae_packed* pk, const dae_rowgeom& g
     if (wave_groups) {
         // (fewer than four tiles per wave slot: waves w and w + 4 share a group -- value 4 -- so that a row has 4 nb_rg x 32 maxima:
         // 4 096 at 1 024 rows, the threshold kernel's 16-key shape)
-        static const bool no_pair = dae_exp_env("DAE_WAVEMAX_NOPAIR") != nullptr;            // A/B (experiments build)
-        const bool pair = n_samp < 4 * gA.nb_rg * 8 && (int64_t)4 * gA.nb_rg * 32 >= 4 * (int64_t)k && !no_pair;
+        const bool pair = n_samp < 4 * gA.nb_rg * 8 && (int64_t)4 * gA.nb_rg * 32 >= 4 * (int64_t)k;
         gmax_per_wave = pair ? 4 : 3;
         ld_g = (int64_t)(pair ? 4 : 8) * gA.nb_rg * 32;
     }
@@ -586,7 +577,7 @@ static int topk_phase_a(dae_ctx* ctx, const dae_packed* pk, const dae_rowgeom& g
     // exact mode (DAE_DTYPE_BF16_EXACT): always so, on BOUNDS -- phase A decodes with the bias b - eps (its maxima are
     // lower bounds of fp32 logits, so tau is a valid threshold for the fp32 ranking), the filter launch with b + eps
     // (nothing whose fp32 logit reaches tau is dropped), and the refine step recomputes every survivor in fp32
-    const bool whole_b = fused && dtype == DAE_DTYPE_BF16 && ((gmax_per_wave != 1 && !mixed && !no_whole) || exact);
+    const bool whole_b = fused && dtype == DAE_DTYPE_BF16 && ((gmax_per_wave != 1 && !mixed) || exact);
     if (whole_b) g_plan.n_other = ntiles;
     if (!fused) { rc = prof_begin(ctx); if (rc) return rc; }
     // (gA != g only with per-wave groups: the generic kernels run on the filter launch's geometry)
@@ -700,8 +691,7 @@ static int topk_phase_b(dae_ctx* ctx, const float* tau_src, const int32_t* seed_
         // k <= 512: the refine launch ends the call itself -- a row's workgroup has its recomputed survivors in LDS, takes the
         // seeds out and orders the k best there (round 5: the selection launch that read them back was 10.6 / 24.0 us of the
         // step at 256 / 1024 rows); larger k keeps the two launches
-        static const bool no_fuse = dae_exp_env("DAE_RF_NOFUSE") != nullptr;                  // A/B (experiments build)
-        const bool fuse = !no_fuse && dae_exact_refine_can_fuse(ta);
+        const bool fuse = dae_exact_refine_can_fuse(ta);
         rc = dae_launch_exact_refine(ctx, g1, xs, B, k, seed_row_ptr, rf, rf_cnt, DAE_REFINED_CAP, static_cast<int*>(ctx->refstat.p),
                                      fuse ? &ta : nullptr);
         // every audit_every-th launch: a sample of the columns the filter launch DROPPED against its own promise (audit.hip) --

@@ -440,8 +440,7 @@ int launch_coo_to_csr(dae_ctx* ctx, const PT* positions, const float* values, in
     float* t_val = reinterpret_cast<float*>(t_feed + nnz);
     int* k_col = reinterpret_cast<int*>(t_val + nnz);
     float* k_val = reinterpret_cast<float*>(k_col + nnz);
-    static const bool no_small = dae_exp_env("DAE_CSR_GENERIC") != nullptr;            // A/B against the 6-launch path
-    if (n_rows <= CSR_SMALL_ROWS && !no_small) {
+    if (n_rows <= CSR_SMALL_ROWS) {
         // cnt | cursor are adjacent, the caller's status word is cleared with them by one small kernel-free memset each
         DAE_HIP_CHECK(ctx, hipMemsetAsync(cnt, 0, (2 * nr + 4) * sizeof(int), st));
         const int blocks = (int)((nnz + 1023) / 1024) > 0 ? (int)((nnz + 1023) / 1024) : 1;

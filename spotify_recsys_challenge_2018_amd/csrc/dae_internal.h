@@ -173,16 +173,8 @@ int dae_reserve(dae_ctx* ctx, dae_buf& b, size_t bytes);
 
 static inline int dae_round_up(int x, int m) { return (x + m - 1) / m * m; }
 
-// Experiment switches (A/B variants, stage bisection: DESIGN.md section 6b) exist only in builds made with
-// -DDAE_EXPERIMENTS (`DAE_EXPERIMENTS=1 python -m spotify_recsys_challenge_2018_amd.build --force`): the default
-// library reads no environment variable and its kernels carry no early-outs.
-#ifdef DAE_EXPERIMENTS
-static inline const char* dae_exp_env(const char* name) { return getenv(name); }
-#define DAE_EXP_ON(x) (x)
-#else
-static inline const char* dae_exp_env(const char*) { return nullptr; }
-#define DAE_EXP_ON(x) false
-#endif
+// The library reads no environment variable: an A/B of two kernel variants is two source trees, each built with build()
+// (DESIGN.md section 8).
 
 // ---------------------------------------------------------------------------------------------
 // canonical scalar device functions -- the SPECIFICATION is DESIGN.md "canonical order"; the
@@ -312,7 +304,7 @@ int dae_launch_decode_loss_f32(dae_ctx* ctx, const dae_rowgeom& g, int B, float 
 
 int dae_launch_decode_loss_rowmajor(dae_ctx* ctx, const dae_rowgeom& g, int B, int V, int H, const float* W,
                                     const float* bias, const float* h, float inv_n_batch, float* dzT, int64_t ldT,
-                                    float* loss_part, int dtype = DAE_DTYPE_F32, int dz16 = 0);
+                                    float* loss_part);
 
 int dae_launch_decode_loss_dh(dae_ctx* ctx, const dae_rowgeom& g, int B, int V, int H, const float* W, const float* bias,
                               const float* h, float inv_n_batch, float* dzT, int64_t ldT, float* loss_part, float* part, int Bpad64);

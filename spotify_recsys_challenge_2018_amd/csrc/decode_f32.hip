@@ -74,7 +74,6 @@ struct DecP {
     // = popularity ranks the winners are packed into the first tiles, and a group then holds at most one of them
     // (maxima over neighbouring columns would lose 7 of 8: measured, 4 000 instead of 600 survivors per row).
     float* gmax; int64_t ld_gmax;
-    long long* stamps;             // experiments build: stage stamps of workgroup 0 / wave 0 (DAE_DBG_A)
     int gmax_per_wave;             // small samples (vocabulary shards): no cross-wave maximum, slot = (round * n_ws + wave * nb_rg + bir)
     // filter epilogue
     const float* tau; int n_valid_col; uint2* cand; int* cand_cnt; int cap;
@@ -94,11 +93,6 @@ __device__ __forceinline__ int tile_of_item(const dae_tileset& ts, int i)
     return ts.list[i];          // always a list (the identity for "all tiles"): no branch around a load
 }
 
-#ifdef DAE_EXPERIMENTS
-#define ASTAMP(i) if (EPI == EPI_GMAX && p.stamps && blockIdx.x == 0 && threadIdx.x == 0) p.stamps[i] = __builtin_readcyclecounter();
-#else
-#define ASTAMP(i)
-#endif
 
 // GT > 0: hidden size known at compile time (G = GT groups of 8 k) -> the k loop is fully
 // unrolled, so no loop header sits between the register-ring loads and their use (hipcc drains
@@ -126,7 +120,6 @@ __global__ __launch_bounds__(NW * 64, HALF ? 2 : NW / 4) void decode_f32_kernel(
     const int rg = rem / DAE_NUM_XCD;
     const int bir = q * DAE_NUM_XCD + (rem % DAE_NUM_XCD);
 
-    ASTAMP(0)
     // wave-major slots: consecutive tiles go to different workgroups, so a partial round of tiles is
     // spread over all CUs (and, with two waves per SIMD, over all SIMDs) instead of filling a few
     const int n_ws = p.nb_rg * NW;
@@ -170,7 +163,6 @@ __global__ __launch_bounds__(NW * 64, HALF ? 2 : NW / 4) void decode_f32_kernel(
         }
     }
 
-    ASTAMP(1)
     float loss_acc = 0.0f;
     // W stream: the wave's tiles back to back; the register ring always holds the next 4 groups
     // of that stream, so the prefetch runs across tile boundaries (and under the epilogue).
@@ -409,7 +401,6 @@ __global__ __launch_bounds__(NW * 64, HALF ? 2 : NW / 4) void decode_f32_kernel(
         }
 #undef DAE_STEP
 
-        ASTAMP(2)
         // ---- epilogue -----------------------------------------------------------------------
         // lane holds, for playlist j of row block rb, the columns
         //   v_local(reg) = (reg & 3) + 8 * (reg >> 2) + 4 * hi          (reg = 0..15)
@@ -487,13 +478,9 @@ __global__ __launch_bounds__(NW * 64, HALF ? 2 : NW / 4) void decode_f32_kernel(
                     }
                 }
             }
-            ASTAMP(3)
             if (EPI == EPI_GMAX) gmax_round(true, (item - item0) / n_ws, acc, bq, tcol0);
-            ASTAMP(4)
         } else if (EPI == EPI_GMAX) {
-            ASTAMP(3)
             gmax_round(true, (item - item0) / n_ws, acc, bq, tcol0);      // maxima AND the dense rows, through LDS
-            ASTAMP(4)
         } else if (EPI == EPI_LOSS) {
             // Every element is treated as a NEGATIVE (target 0) here; the few positives of the batch (~100
             // of 170 000 columns per row) are redone from their own dot products by loss_fixup_kernel
@@ -620,212 +607,15 @@ struct LossRmP {
     float inv_nb; float* dzT; int64_t ldT; float* loss_part;
 };
 
-// ---- K5, bf16 operands, hidden 256, batches of at most 256 playlists: the W tile through LDS (round 6) ---------------
-// Until round 6 a wave was a tile of 32 decoder rows x 128 playlists, every lane reading ITS decoder row in 32-byte pieces:
-// 64 lanes, 32 rows -- 64 different cache lines per load
-// instruction, one tag lookup each.  Measured (rocprofv3 counters + the launch with one part removed at a time,
-// profiles/r06_notes.md 8): 90 us with, 48 us without the W loads; halving the epilogue's instruction count changed nothing.
-// Here a workgroup of 8 waves takes a tile x ALL playlists (58.8 us):
-//   * the 8 waves fetch the tile's 32 rows as 32 plain 1 KB row reads (4 per wave), round them to bf16 and put them in LDS
-//     ([row][k], 528-byte rows: conflict-free both ways), two tiles in rotation, one barrier per tile;
-//   * a wave is one block of 32 playlists: its hidden fragments (16 k-steps x 16 B) live in REGISTERS for the whole launch,
-//     the A fragments (decoder rows) come from LDS, 16 MFMAs per tile, then the epilogue of its 32 x 32 logits;
-//   * every W byte is read once per launch by one workgroup (the 128-row kernel read it per row group, through L2).
-// The k order of every dot product is what the 128-row kernel's was (16 steps of 16, fp32 accumulate in the matrix pipe): the
-// same loss, bit for bit.
-template <bool DZ16>
-__global__ __launch_bounds__(512, 1) void decode_loss_shared_bf16_kernel(const LossRmP p)
-{
-    constexpr int NW = 8, LDW = 132;                                   // dwords per staged decoder row (128 + 4 of padding)
-    __shared__ __attribute__((aligned(16))) unsigned wt[2][32 * LDW];
-    __shared__ float wsum[NW];
-    const int tid = threadIdx.x, lane = tid & 63, hi = lane >> 5, j = lane & 31;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int row = wave * 32 + j;                                     // this lane's playlist
-    const int H4 = p.H >> 2;                                           // (64)
-    const float4* W4 = reinterpret_cast<const float4*>(p.W);
-    const int n_tiles = (p.V + 31) >> 5;
-    const int nb = gridDim.x;
-
-    // hidden fragments of the lane's playlist: step s = k 16 s + 8 hi .. + 7 (zeros past the batch)
-    uint4 hb[16];
-    {
-        const float4* hr = reinterpret_cast<const float4*>(p.h) + (size_t)(row < p.B ? row : 0) * H4 + 2 * hi;
-        float4 ha[16], hc[16];                                         // (all 32 loads in flight at once)
-#pragma unroll
-        for (int s_ = 0; s_ < 16; ++s_) { ha[s_] = hr[4 * s_]; hc[s_] = hr[4 * s_ + 1]; }
-        const unsigned keep = row < p.B ? 0xFFFFFFFFu : 0u;            // bf16(0) = 0
-#pragma unroll
-        for (int s_ = 0; s_ < 16; ++s_) {
-            const float4 a = ha[s_], b = hc[s_];
-            hb[s_] = make_uint4((bf16_rne(a.x) | (bf16_rne(a.y) << 16)) & keep, (bf16_rne(a.z) | (bf16_rne(a.w) << 16)) & keep,
-                                (bf16_rne(b.x) | (bf16_rne(b.y) << 16)) & keep, (bf16_rne(b.z) | (bf16_rne(b.w) << 16)) & keep);
-        }
-    }
-    // the wave's four rows of a tile: lane l holds floats 4 l .. 4 l + 3 of each (rows past V: the last row, masked later)
-    auto load_rows = [&](int t, float4 (&wr)[4]) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int v = t * 32 + 4 * wave + r;
-            wr[r] = W4[(size_t)(v < p.V ? v : p.V - 1) * H4 + lane];
-        }
-    };
-    auto stage_rows = [&](int buf, const float4 (&wr)[4]) {
-        typedef float f32x4_t __attribute__((ext_vector_type(4)));
-        typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const f32x4_t f = {wr[r].x, wr[r].y, wr[r].z, wr[r].w};
-            const uint2 pk = __builtin_bit_cast(uint2, __builtin_convertvector(f, bf16x4_t));        // 2 x v_cvt_pk_bf16_f32 (RNE)
-            *reinterpret_cast<uint2*>(&wt[buf][(4 * wave + r) * LDW + 2 * lane]) = pk;
-        }
-    };
-
-    // the bias of the lane's 16 columns of a tile (columns past V: b[V - 1], never used)
-    auto load_bias = [&](int t, float4 (&b)[4]) {
-        if (t * 32 + 32 <= p.V) {
-#pragma unroll
-            for (int qd = 0; qd < 4; ++qd) b[qd] = *reinterpret_cast<const float4*>(p.bias + t * 32 + 4 * hi + 8 * qd);
-        } else {
-#pragma unroll
-            for (int qd = 0; qd < 4; ++qd) {
-                const int c = t * 32 + 4 * hi + 8 * qd, last = p.V - 1;
-                b[qd] = make_float4(p.bias[c < last ? c : last], p.bias[c + 1 < last ? c + 1 : last],
-                                    p.bias[c + 2 < last ? c + 2 : last], p.bias[c + 3 < last ? c + 3 : last]);
-            }
-        }
-    };
-
-    float loss_acc = 0.0f;
-    float4 wr[4], bq[4], bq_n[4];
-    int t = blockIdx.x;
-#pragma unroll
-    for (int qd = 0; qd < 4; ++qd) bq[qd] = bq_n[qd] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (t < n_tiles) {
-        load_rows(t, wr);
-        load_bias(t, bq);
-        stage_rows(0, wr);
-        if (t + nb < n_tiles) load_rows(t + nb, wr);
-    }
-    __syncthreads();
-    const float k1 = 0.55f * p.inv_nb;
-    const bool rows_in = wave * 32 + 32 <= p.B;                        // wave-uniform
-    int buf = 0;
-    for (; t < n_tiles; t += nb, buf ^= 1) {
-        // everything requested one iteration ago has arrived: W rows of tile t + nb (registers), this tile's bias
-        if (t + nb < n_tiles) {
-            stage_rows(buf ^ 1, wr);                                   // (that buffer's readers passed the barrier)
-            load_bias(t + nb, bq_n);
-        }
-        if (t + 2 * nb < n_tiles) load_rows(t + 2 * nb, wr);           // consumed one iteration from now
-        f32x16 acc;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
-        const unsigned* wl = &wt[buf][j * LDW + 4 * hi];
-#pragma unroll
-        for (int s_ = 0; s_ < 16; ++s_) {
-            const uint4 af = *reinterpret_cast<const uint4*>(wl + 8 * s_);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(af), as_bf16x8(hb[s_]), acc, 0, 0, 0);
-        }
-        // epilogue: lane (j, hi) holds, for playlist `row`, the columns t 32 + 4 hi + 8 qd + e
-        if (t * 32 + 32 <= p.V && rows_in) {
-            const unsigned lane_off = (unsigned)(4 * hi) * (unsigned)p.ldT + (unsigned)row;
-            unsigned short* const d16 = reinterpret_cast<unsigned short*>(p.dzT) + (size_t)t * 32 * p.ldT;
-            float* const d32 = p.dzT + (size_t)t * 32 * p.ldT;
-            if (DZ16) {
-                // dL/dz = 0.55 y (1 - y) / (1 - y + 1e-10) (DAEs.py:98-99's negatives); the quotient is 1 to 2^-13 -- far below a
-                // bf16's half unit -- unless 1 - y < 1e-6 (a logit above 13.8): those elements are redone below
-                float q_min = 1.0f;
-#pragma unroll
-                for (int qd = 0; qd < 4; ++qd) {
-                    const float zb[4] = {bq[qd].x, bq[qd].y, bq[qd].z, bq[qd].w};
-#pragma unroll
-                    for (int e = 0; e < 4; e += 2) {
-                        float dzv[2];
-#pragma unroll
-                        for (int u = 0; u < 2; ++u) {
-                            const float zz = acc[4 * qd + e + u] + zb[e + u];
-                            const float pr = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * zz));
-                            const float q = 1.0f - pr;
-                            loss_acc -= (0.69314718f * 0.55f) * __builtin_amdgcn_logf(q + 1e-10f);
-                            q_min = fminf(q_min, q);
-                            dzv[u] = k1 * pr;
-                        }
-                        typedef float f32x2_t __attribute__((ext_vector_type(2)));
-                        typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-                        const f32x2_t d2 = {dzv[0], dzv[1]};
-                        const unsigned pk = __builtin_bit_cast(unsigned, __builtin_convertvector(d2, bf16x2_t));
-                        (d16 + (size_t)(8 * qd + e) * p.ldT)[lane_off] = (unsigned short)(pk & 0xFFFFu);
-                        (d16 + (size_t)(8 * qd + e + 1) * p.ldT)[lane_off] = (unsigned short)(pk >> 16);
-                    }
-                }
-                if (__builtin_expect(__ballot(q_min < 1e-6f) != 0ull, 0)) {
-#pragma unroll
-                    for (int qd = 0; qd < 4; ++qd) {
-                        const float zb[4] = {bq[qd].x, bq[qd].y, bq[qd].z, bq[qd].w};
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const float zz = acc[4 * qd + e] + zb[e];
-                            const float pr = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * zz));
-                            const float q = 1.0f - pr;
-                            if (q < 1e-6f)
-                                (d16 + (size_t)(8 * qd + e) * p.ldT)[lane_off] =
-                                    (unsigned short)bf16_rne(k1 * __builtin_amdgcn_rcpf(q + 1e-10f) * pr * q);
-                        }
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int qd = 0; qd < 4; ++qd) {
-                    const float zb[4] = {bq[qd].x, bq[qd].y, bq[qd].z, bq[qd].w};
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float zz = acc[4 * qd + e] + zb[e];
-                        const float pr = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * zz));
-                        const float a0 = 1.0f - pr + 1e-10f;
-                        loss_acc -= (0.69314718f * 0.55f) * __builtin_amdgcn_logf(a0);
-                        (d32 + (size_t)(8 * qd + e) * p.ldT)[lane_off] = 0.55f * __builtin_amdgcn_rcpf(a0) * pr * (1.0f - pr) * p.inv_nb;
-                    }
-                }
-            }
-        } else if (row < p.B) {
-            const int tcol0 = t * 32 + 4 * hi;
-#pragma unroll
-            for (int qd = 0; qd < 4; ++qd) {
-                const int lc = tcol0 + 8 * qd;
-                const float zb[4] = {bq[qd].x, bq[qd].y, bq[qd].z, bq[qd].w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    if (lc + e < p.V) {
-                        const float zz = acc[4 * qd + e] + zb[e];
-                        const float pr = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * zz));
-                        const float a0 = 1.0f - pr + 1e-10f;
-                        loss_acc -= (0.69314718f * 0.55f) * __builtin_amdgcn_logf(a0);
-                        const float dzv = 0.55f * __builtin_amdgcn_rcpf(a0) * pr * (1.0f - pr) * p.inv_nb;
-                        if (DZ16)
-                            reinterpret_cast<unsigned short*>(p.dzT)[(size_t)(lc + e) * p.ldT + row] = (unsigned short)bf16_rne(dzv);
-                        else
-                            p.dzT[(size_t)(lc + e) * p.ldT + row] = dzv;
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int qd = 0; qd < 4; ++qd) bq[qd] = bq_n[qd];
-        __syncthreads();
-    }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) loss_acc += __shfl_xor(loss_acc, d);
-    if (lane == 0) wsum[wave] = loss_acc;
-    __syncthreads();
-    if (tid == 0) {
-        float sm = 0.0f;
-        for (int w = 0; w < NW; ++w) sm += wsum[w];
-        p.loss_part[blockIdx.x] = sm * p.inv_nb;
-    }
-}
-
 // ---- K5 + K7 in one launch (bf16 operands, dz^T as bf16, hidden 256, batches <= 256): dh folded into the forward (round 6) ----
+// The forward (K5): a workgroup of 8 waves takes a tile of 32 decoder rows x ALL playlists.  (Until round 6 a wave was a tile of
+// 32 decoder rows x 128 playlists, every lane reading ITS decoder row in 32-byte pieces: 64 different cache lines per load
+// instruction, one tag lookup each -- 90 us with, 48 us without the W loads; profiles/r06_notes.md 8.)
+//   * the 8 waves fetch the tile's 32 rows as plain 1 KB row reads (4 per wave), round them to bf16 and put them in LDS
+//     ([row][k], 528-byte rows: conflict-free both ways), two tiles in rotation;
+//   * a wave is one block of 32 playlists: its hidden fragments (16 k-steps x 16 B) stay on chip for the whole launch, the A
+//     fragments (decoder rows) come from LDS, 16 MFMAs per tile, then the epilogue of its 32 x 32 logits;
+//   * every W byte is read once per launch by one workgroup.
 // K7 (train.hip grad_hidden_kernel) reads the whole decoder a second time and dz^T back from HBM to form dh = dz W_dec.  Here
 // the tile of decoder rows is in LDS already and a lane holds its playlist's 16 dz values of the tile when the epilogue ends:
 // the wave multiplies them (A operand: straight from the epilogue's packed bf16 pairs -- the MFMA's k-slots are assigned to
@@ -1382,8 +1172,8 @@ __global__ __launch_bounds__(256, 1) void decode_f32_h256_filter_kernel(const De
 // A wave owns NT column tiles x RB row blocks.  Measured (profiles/r01_notes.md, us at batch 256 / 1024):
 //   <NT = 1, RB = 4, ring 8, 2 waves per SIMD>  19.9 / 55.7   <- default: 4 accumulators per wave
 //   <NT = 1, RB = 4, ring 16, 1 wave per SIMD>  23.9 / 65.3
-//   <NT = 2, RB = 4, ring 16, 1 wave per SIMD>  25.6 / 61.5   (DAE_BF16_PAIR: a hidden fragment feeds 2 MFMAs)
-//   <NT = 1, RB = 8, ring 16, 1 wave per SIMD>  27.6 / 64.1   (DAE_BF16_RTILE=256: W read once at batch 256)
+//   <NT = 2, RB = 4, ring 16, 1 wave per SIMD>  25.6 / 61.5   (a hidden fragment feeds 2 MFMAs)
+//   <NT = 1, RB = 8, ring 16, 1 wave per SIMD>  27.6 / 64.1   (256-row groups: W read once at batch 256)
 //   3 and 4 waves per SIMD spill (168 / 128 registers) and are slower.
 // A micro-benchmark of the inner pattern (scripts/micro/mfma_peak.hip: 4 accumulators, hidden fragments
 // from LDS one step ahead, no global memory) reaches 2.3-2.4 PFLOP/s, so neither LDS nor the MFMA issue
@@ -1552,12 +1342,6 @@ __global__ __launch_bounds__(NW * 64, 1) void decode_bf16_h256_filter_kernel(con
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int hi = lane >> 5;
     const int j = lane & 31;
-#ifdef DAE_EXPERIMENTS          // stage stamps of wave 0 of workgroups 0 and 100 (DAE_DBG_F): cycle counter at the marked points
-#define FSTAMP(i) if (p.stamps && threadIdx.x == 0 && (blockIdx.x == 0 || blockIdx.x == 100)) p.stamps[(blockIdx.x ? 16 : 0) + (i)] = __builtin_readcyclecounter();
-#else
-#define FSTAMP(i)
-#endif
-    FSTAMP(0)
 
     const int gs = DAE_NUM_XCD * p.n_rg;
     const int q = blockIdx.x / gs, rem = blockIdx.x % gs;
@@ -1585,7 +1369,7 @@ __global__ __launch_bounds__(NW * 64, 1) void decode_bf16_h256_filter_kernel(con
     // WHICH groups a wave decodes: its first two by position (wave w: the w-th and the (NW + w)-th group of the workgroup's
     // share {bir + m nb_rg}), every further one CLAIMED from a counter in LDS, two groups ahead of its use.  A wave that
     // drew one of the hottest tiles of the bias-ordered list (nearly every value passes: 16 - 20 k cycles of appends against
-    // 4 k for an ordinary tile, stage stamps DAE_DBG_F) then simply takes fewer tiles, instead of setting the end of the
+    // 4 k for an ordinary tile, stage stamps) then simply takes fewer tiles, instead of setting the end of the
     // launch with the static share it had before (42 k cycles against 32 k for a workgroup without a hot tile).
     int t[NT], u[NT];                                            // tiles of this / the next group (uniform)
     int tv0[NT], tv1[NT];
@@ -1647,9 +1431,7 @@ __global__ __launch_bounds__(NW * 64, 1) void decode_bf16_h256_filter_kernel(con
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) wq[nt][k] = Wq[(size_t)t[nt] * (NS * 64) + k * 64 + lane];
     __builtin_amdgcn_sched_barrier(0);
-    FSTAMP(1)                                                    // every request of the prologue is out
     __syncthreads();
-    FSTAMP(2)                                                    // the workgroup has met
 
     float tau_r[RB];
 #pragma unroll
@@ -1658,7 +1440,6 @@ __global__ __launch_bounds__(NW * 64, 1) void decode_bf16_h256_filter_kernel(con
     for (int rb = 0; rb < RB; ++rb) cb[0][rb] = ldsq[rb * 64 + lane];
 
     int g_nxt = grp0 + n_ws;
-    [[maybe_unused]] int n_done = 0;                            // (the stage stamps of the experiments build count tiles with it)
     for (int grp = grp0; grp < n_grp;) {
         int g_nn;
         {
@@ -1786,16 +1567,11 @@ __global__ __launch_bounds__(NW * 64, 1) void decode_bf16_h256_filter_kernel(con
         }
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) { t[nt] = u[nt]; u[nt] = __builtin_amdgcn_readfirstlane(wv[nt]); }
-        FSTAMP(3 + (n_done < 9 ? n_done : 9))                    // tile (group) done, epilogue included
-        ++n_done;
         grp = g_nxt; g_nxt = g_nn;
     }
-    FSTAMP(13)
     __syncthreads();
-    FSTAMP(14)
     for (int i = tid; i < R_TILE; i += NW * 64) p.cand_cnt[(size_t)bir * p.Bpad + rg * R_TILE + i] = lcnt[i];
 }
-#undef FSTAMP
 
 // ---- bf16, hidden = 256, filter epilogue, MFMA-bound batches (>= 512 playlists per launch) ------------------------------
 // The kernel above reads every B operand (hidden fragment) of every MFMA from LDS: 1 KiB per v_mfma_f32_32x32x16_bf16,
@@ -1809,162 +1585,7 @@ __global__ __launch_bounds__(NW * 64, 1) void decode_bf16_h256_filter_kernel(con
 // MEASURED AND NOT THE DEFAULT (round 4, batch 1024, one batch in flight): 0.157 ms per step with two row blocks in
 // registers against 0.146 ms for the all-LDS kernel, 0.225 ms with three (hipcc then spills fragments to scratch and reloads
 // them every tile).  With one wave per SIMD hipcc issues a tile's 68 MFMAs back to back and the epilogue after them; the
-// second wave per SIMD of the all-LDS kernel hides more than the LDS reads cost.  Experiments build only (DAE_BF16_REGB).
-#ifdef DAE_EXPERIMENTS
-template <int RBR, int QR>
-__global__ __launch_bounds__(256, 1) void decode_bf16_h256_regb_filter_kernel(const DecP p)
-{
-    constexpr int NS = 16, RB = 4, RBL = RB - RBR, R_TILE = 128, NW = 4;
-    __shared__ int lcnt[R_TILE];
-    __shared__ uint4 hl[NS * RBL * 64];      // the fragments of the row blocks RBR .. 3 (16 KiB each): see below
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int hi = lane >> 5;
-    const int j = lane & 31;
-    const int gs = DAE_NUM_XCD * p.n_rg;
-    const int q = blockIdx.x / gs, rem = blockIdx.x % gs;
-    const int rg = rem / DAE_NUM_XCD;
-    const int bir = q * DAE_NUM_XCD + (rem % DAE_NUM_XCD);
-    const int n_items = p.ts.n_items;
-    const int n_ws = p.nb_rg * NW;
-    const int it0 = wave * p.nb_rg + bir;
-    const uint4* Wq = reinterpret_cast<const uint4*>(p.Wp);
-    const uint4 ones = bf16_ones_fragment(hi);
-
-    // tile ids two ahead, the thresholds, the hidden tile -> registers, the first tile's W ring
-    const bool has = it0 < n_items;
-    const int tv0 = tile_of_item(p.ts, has ? it0 : 0);
-    const int tv1 = tile_of_item(p.ts, has && it0 + n_ws < n_items ? it0 + n_ws : (has ? it0 : 0));
-    float tau_r[RB];
-#pragma unroll
-    for (int rb = 0; rb < RB; ++rb) {
-        const int row = rg * R_TILE + rb * 32 + j;
-        tau_r[rb] = row < p.B ? p.tau[row] : __builtin_inff();
-    }
-    // Register budget of the lane (512): 3 of the 4 row blocks' fragments (192), two accumulator sets (128), a W ring one whole
-    // tile deep (64: 2 176 cycles of prefetch distance).  The fourth row block's fragments would be 64 more -- hipcc then
-    // parks 64 of them in scratch and reloads them every tile -- so they stay in LDS (16 KiB, shared by the four waves):
-    // one ds_read_b128 per step and wave, a quarter of the LDS traffic that bounds the all-LDS kernel.
-    uint4 hf[NS][RBR];
-    {
-        const uint4* hsrc = reinterpret_cast<const uint4*>(p.hp) + (size_t)rg * (NS * RB * 64);
-#pragma unroll
-        for (int s = 0; s < NS; ++s)
-#pragma unroll
-            for (int rb = 0; rb < RBR; ++rb) hf[s][rb] = hsrc[(s * RB + rb) * 64 + lane];
-#pragma unroll
-        for (int e = 0; e < NS * RBL * 64 / (NW * 64); ++e) {
-            const int i = e * (NW * 64) + tid;                   // ((step, row block - RBR), lane)
-            const int f = i >> 6;
-            hl[i] = hsrc[((f / RBL) * RB + RBR + f % RBL) * 64 + (i & 63)];
-        }
-    }
-    if (tid < R_TILE) lcnt[tid] = 0;
-    int t = __builtin_amdgcn_readfirstlane(tv0), u = __builtin_amdgcn_readfirstlane(tv1);
-    uint4 wq[QR];
-    uint4 bfr = p.bias16[(size_t)t * 64 + lane];
-#pragma unroll
-    for (int s = 0; s < QR; ++s) wq[s] = Wq[(size_t)t * (NS * 64) + s * 64 + lane];
-    __syncthreads();
-
-    // the filter epilogue of one finished tile (see decode_bf16_h256_filter_kernel): `mx` = the lane's maxima per row block
-    auto appends = [&](const f32x16 (&acc)[RB], const float (&mx)[RB], int tt) {
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb) {
-            const float tv = tau_r[rb];
-            if (mx[rb] >= tv) {
-                unsigned m = 0;
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg) {
-                    const int lc = tt * 32 + 4 * hi + (reg & 3) + 8 * (reg >> 2);
-                    if (acc[rb][reg] >= tv && lc < p.ncols && p.col_lo + lc < p.n_valid_col) m |= 1u << reg;
-                }
-                if (m) {
-                    int at = atomicAdd(&lcnt[rb * 32 + j], __popc(m));
-                    uint2* dst = p.cand + ((size_t)bir * p.Bpad + rg * R_TILE + rb * 32 + j) * (size_t)p.cap;
-                    const int cg = p.col_lo + tt * 32 + 4 * hi;
-#pragma unroll
-                    for (int reg = 0; reg < 16; ++reg)
-                        if (m & (1u << reg))
-                            dst[at++] = make_uint2(__float_as_uint(acc[rb][reg]), (unsigned)(cg + (reg & 3) + 8 * (reg >> 2)));
-                }
-            }
-        }
-    };
-    auto maxima = [&](const f32x16 (&acc)[RB], float (&mx)[RB]) {
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb) {
-            float m = acc[rb][0];
-#pragma unroll
-            for (int reg = 1; reg < 16; ++reg) m = fmaxf(m, acc[rb][reg]);
-            mx[rb] = m;
-        }
-    };
-    // one tile: accumulators start at the bias (through the matrix pipe, as every bf16 kernel), 16 steps; after step s the
-    // ring slot s takes the same step of the NEXT tile
-    auto tile = [&](f32x16 (&acc)[RB], int tc, int tn) {
-        const uint4* cur = Wq + (size_t)tc * (NS * 64) + lane;
-        const uint4* nxt = Wq + (size_t)tn * (NS * 64) + lane;
-        const uint4 bc = bfr;
-        bfr = p.bias16[(size_t)tn * 64 + lane];
-        const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb)
-            acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(bc), as_bf16x8(ones), zero, 0, 0, 0);
-        uint4 cb[RBL];
-#pragma unroll
-        for (int r = 0; r < RBL; ++r) cb[r] = hl[r * 64 + lane];
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const uint4 a = wq[s % QR];
-            uint4 cbn[RBL];                                       // the LDS-resident fragments of the next step
-#pragma unroll
-            for (int r = 0; r < RBL; ++r) cbn[r] = hl[(((s + 1) % NS) * RBL + r) * 64 + lane];
-#pragma unroll
-            for (int rb = 0; rb < RBR; ++rb)
-                acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a), as_bf16x8(hf[s][rb]), acc[rb], 0, 0, 0);
-#pragma unroll
-            for (int r = 0; r < RBL; ++r) {
-                acc[RBR + r] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a), as_bf16x8(cb[r]), acc[RBR + r], 0, 0, 0);
-                cb[r] = cbn[r];
-            }
-            wq[s % QR] = (s + QR < NS) ? cur[(s + QR) * 64] : nxt[(s + QR - NS) * 64];
-        }
-    };
-
-    f32x16 accA[RB], accB[RB];
-    float mx[RB];
-    int it = it0;
-    int t_prev = 0;
-    bool pending = false;                                        // accB / accA of the previous tile still wait for their epilogue
-    // two tiles per trip: A then B; the epilogue of each runs after the MFMAs of the following tile have been issued
-    while (it < n_items) {
-        const int i1 = it + n_ws, i2 = i1 + n_ws;
-        const int w1 = tile_of_item(p.ts, i2 < n_items ? i2 : it);      // ids two tiles ahead
-        const int w2 = tile_of_item(p.ts, i2 + n_ws < n_items ? i2 + n_ws : it);
-        tile(accA, t, u);                                        // tile t; the ring refills with tile u
-        if (pending) { maxima(accB, mx); appends(accB, mx, t_prev); }
-        const int tA = t;
-        t = u; u = __builtin_amdgcn_readfirstlane(w1);
-        if (i1 < n_items) {
-            tile(accB, t, u);
-            maxima(accA, mx); appends(accA, mx, tA);
-            t_prev = t;
-            t = u; u = __builtin_amdgcn_readfirstlane(w2);
-            pending = true;
-        } else {
-            maxima(accA, mx); appends(accA, mx, tA);
-            pending = false;
-        }
-        it = i2;
-    }
-    if (pending) { maxima(accB, mx); appends(accB, mx, t_prev); }
-    __syncthreads();
-    for (int i = tid; i < R_TILE; i += NW * 64) p.cand_cnt[(size_t)bir * p.Bpad + rg * R_TILE + i] = lcnt[i];
-}
-
-#endif  // DAE_EXPERIMENTS
+// second wave per SIMD of the all-LDS kernel hides more than the LDS reads cost.  (The kernel is not kept.)
 
 // ---- prepack: W_dec rows -> MFMA A-operand order ----------------------------------------------
 // One workgroup per 32-column tile: the tile's 32 rows of W (32 x H floats, contiguous 4 H bytes each) are read
@@ -2175,8 +1796,6 @@ __global__ __launch_bounds__(256) void tile_iota_kernel(int n, int* __restrict__
     for (int t = blockIdx.x * 256 + threadIdx.x; t < n; t += gridDim.x * 256) out[t] = t;
 }
 
-// fallback for images of more than ORDER_MAX_TILES tiles (and the DAE_SAMPLE=strided experiment):
-// every S-th tile first, then the others
 // The threshold sample re-dealt for a launch of several ROUNDS (dae_launch_tile_band).  Phase A takes, per (row, position in the
 // tile), the maximum over the `waves` tiles a workgroup decodes together in a round; the threshold is the (k + seeds)-th largest
 // of these maxima, so two winners in one group cost one of them.  Item i of the sample goes to round i / n_ws, wave (i % n_ws) /
@@ -2202,6 +1821,7 @@ __global__ __launch_bounds__(256) void tile_band_kernel(const int* __restrict__ 
     }
 }
 
+// fallback for images of more than ORDER_MAX_TILES tiles: every S-th tile first, then the others
 __global__ __launch_bounds__(256) void tile_order_strided_kernel(int ntiles, int n_samp, int S,
                                                                  int* __restrict__ order)
 {
@@ -2299,10 +1919,10 @@ int launch_decode(dae_ctx* ctx, const dae_rowgeom& g, const DecP& p)
 template <int EPI>
 int launch_decode_rb(dae_ctx* ctx, const dae_rowgeom& g, const DecP& p)
 {
-    // the shipped configs all use hidden = 256 (config.ini:12): G = 32 gets the unrolled body
-    if (g.R_TILE == 128 && p.G == 32) {
-        return launch_decode<4, EPI, 32, 4, DT_F32>(ctx, g, p);
-    }
+    // the shipped configs all use hidden = 256 (config.ini:12): G = 32 gets the unrolled body (not the loss epilogue: hidden
+    // 256 in 128-row groups trains through the row-major K5, dae_launch_decode_loss_rowmajor)
+    if constexpr (EPI != EPI_LOSS)
+        if (g.R_TILE == 128 && p.G == 32) return launch_decode<4, EPI, 32, 4, DT_F32>(ctx, g, p);
     if (g.waves != 4) return dae_fail(ctx, DAE_ERR_ARG, "bad wave count %d", g.waves);
     switch (g.R_TILE) {
         case 128: return launch_decode<4, EPI, 0, 4, DT_F32>(ctx, g, p);
@@ -2317,10 +1937,10 @@ int launch_decode_rb_bf16(dae_ctx* ctx, const dae_rowgeom& g, const DecP& p)
 {
     // hidden = 256 -> 16 steps of K = 16: unrolled body with the 8-deep register ring
     // two waves per SIMD here: with 16x faster MFMAs the VALU epilogue of a tile is comparable to
-    // its matrix time, and the second wave's MFMAs cover it (DAE_DECODE_WAVES_BF16=4 for the A/B)
+    // its matrix time, and the second wave's MFMAs cover it
     if (g.waves != 4) return dae_fail(ctx, DAE_ERR_ARG, "bad wave count %d", g.waves);
-    if (g.R_TILE == 256 && p.G == 16) return launch_decode<8, EPI, 16, 4, DT_BF16>(ctx, g, p);
-    if (g.R_TILE == 128 && p.G == 16) return launch_decode<4, EPI, 16, 4, DT_BF16>(ctx, g, p);
+    if constexpr (EPI != EPI_LOSS)                            // (the loss epilogue: as in launch_decode_rb)
+        if (g.R_TILE == 128 && p.G == 16) return launch_decode<4, EPI, 16, 4, DT_BF16>(ctx, g, p);
     switch (g.R_TILE) {
         case 128: return launch_decode<4, EPI, 0, 4, DT_BF16>(ctx, g, p);
         case 64:  return launch_decode<2, EPI, 0, 4, DT_BF16>(ctx, g, p);
@@ -2329,26 +1949,10 @@ int launch_decode_rb_bf16(dae_ctx* ctx, const dae_rowgeom& g, const DecP& p)
     return dae_fail(ctx, DAE_ERR_ARG, "bad R_TILE %d", g.R_TILE);
 }
 
-bool bf16_pair_variant()
-{
-    static const bool v = dae_exp_env("DAE_BF16_PAIR") != nullptr;     // A/B: two column tiles per wave, one wave per SIMD
-    return v;
-}
-// the dedicated phase-B kernel: hidden = 256 (16 steps), one wave per SIMD, 128- or 256-row groups
+// the dedicated phase-B kernel: hidden = 256 (16 steps), 128-row groups
 bool bf16_fast_filter(const dae_rowgeom& g, int dtype, int G)
 {
-    static const bool off = dae_exp_env("DAE_BF16_GENERIC") != nullptr;                // A/B against the generic body
-    return dtype == DAE_DTYPE_BF16 && G == 16 && g.waves == 4 && (g.R_TILE == 128 || g.R_TILE == 256) && !off;
-}
-
-// ... and its MFMA-bound form (hidden fragments in registers, decode_bf16_h256_regb_filter_kernel): launches of four or
-// more row groups (>= 385 playlists), where W passes through every CU's L1 once per row group and the all-LDS kernel
-// is bound by its LDS reads.  0 = off; 2 / 3 = row blocks held in registers (experiments: DAE_BF16_REGB).
-int bf16_regb_variant(const dae_rowgeom& g)
-{
-    static const int env = dae_exp_env("DAE_BF16_REGB") ? atoi(dae_exp_env("DAE_BF16_REGB")) : -1;
-    if (g.R_TILE != 128) return 0;
-    return (env == 2 || env == 3) ? env : 0;                 // measured slower than the all-LDS kernel: never the default
+    return dtype == DAE_DTYPE_BF16 && G == 16 && g.waves == 4 && g.R_TILE == 128;
 }
 
 int fill_common(dae_ctx* ctx, const dae_rowgeom& g, int B, const dae_tileset& ts, DecP& p,
@@ -2384,12 +1988,8 @@ int dae_filter_block_tiles(const dae_rowgeom& g, int n_items, int dtype, int Hp,
 {
     const int n_ws = g.nb_rg * g.waves;
     if (bf16_fast_filter(g, dtype, Hp / 16) && !mixed) {
-        const bool pair = g.R_TILE != 256 && bf16_pair_variant();
-        const int nt = pair ? 2 : 1;
-        const int nw = (g.R_TILE == 256 || pair || bf16_regb_variant(g)) ? 4 : 8;
-        const int n_grp = (n_items + nt - 1) / nt;
-        const int n_ws2 = g.nb_rg * nw;
-        return nt * nw * ((n_grp + n_ws2 - 1) / n_ws2);
+        const int n_ws8 = g.nb_rg * 8;                       // (decode_bf16_h256_filter_kernel<1, 4, 8, 8>: 8 waves, a tile each)
+        return 8 * ((n_items + n_ws8 - 1) / n_ws8);
     }
     return g.waves * ((n_items + n_ws - 1) / n_ws);
 }
@@ -2420,9 +2020,8 @@ dae_rowgeom dae_row_geometry_bf16(int B, int Hp)
 {
     dae_rowgeom g;
     // 128-playlist row groups.  256-row groups (every W fragment feeds 8 MFMAs, a batch of 256 reads W
-    // exactly once) measured the same kernel time but a slower phase A: DAE_BF16_RTILE=256 for the A/B.
+    // exactly once) measured the same kernel time but a slower phase A.
     int rt = 128;
-    if (const char* e = dae_exp_env("DAE_BF16_RTILE")) { if (atoi(e) == 256 && Hp == 256 && B > 128) rt = 256; }
     while (rt > 32 && (size_t)rt * Hp * 2 > 128 * 1024) rt >>= 1;
     while (rt > 32 && B <= rt / 2) rt >>= 1;
     g.R_TILE = rt;
@@ -2566,8 +2165,7 @@ int dae_launch_tile_order(dae_ctx* ctx, dae_packed& pk, int nrank, int n_samp, i
     if (pk.order_nrank == nrank && pk.order_nsamp == n_samp && pk.order.p) return DAE_OK;
     int rc = dae_reserve(ctx, pk.order, (size_t)pk.ntiles * sizeof(int));
     if (rc) return rc;
-    static const bool strided = dae_exp_env("DAE_SAMPLE") && !strcmp(dae_exp_env("DAE_SAMPLE"), "strided");
-    if (pk.ntiles > ORDER_MAX_TILES || strided) {
+    if (pk.ntiles > ORDER_MAX_TILES) {
         hipLaunchKernelGGL(tile_order_strided_kernel, dim3((pk.ntiles + 255) / 256), dim3(256), 0, ctx->stream,
                            pk.ntiles, n_samp, S, static_cast<int*>(pk.order.p));
     } else {
@@ -2585,8 +2183,7 @@ int dae_launch_tile_order(dae_ctx* ctx, dae_packed& pk, int nrank, int n_samp, i
 // that gives each of the 8 wave slots per workgroup at least two tiles
 bool dae_sample_wave_groups(const dae_rowgeom& g, int Hp, int n_samp)
 {
-    static const bool off = dae_exp_env("DAE_NO_WAVEMAX") != nullptr;                    // A/B (experiments build)
-    return !off && Hp == 256 && g.R_TILE == 128 && g.waves == 4 && n_samp >= 2 * g.nb_rg * 8;
+    return Hp == 256 && g.R_TILE == 128 && g.waves == 4 && n_samp >= 2 * g.nb_rg * 8;
 }
 
 int dae_launch_tile_band(dae_ctx* ctx, const int* order, int ntiles, int n_samp, int nb_rg, int waves, int* band)
@@ -2623,21 +2220,6 @@ int dae_launch_decode_dense_f32(dae_ctx* ctx, const dae_rowgeom& g, int B, const
     p.out = out; p.ld = ld; p.apply_sigmoid = apply_sigmoid; p.mask_from_col = mask_from_col;
     p.gmax = gmax; p.ld_gmax = ld_gmax; p.gmax_per_wave = gmax_per_wave;
     if (!out && !gmax) return dae_fail(ctx, DAE_ERR_ARG, "dense decode without an output");
-#ifdef DAE_EXPERIMENTS
-    static const bool dbgA = dae_exp_env("DAE_DBG_A") != nullptr;
-    static long long* abuf = nullptr;
-    static int acalls = 0;
-    if (dbgA && gmax) {
-        if (!abuf) (void)hipMalloc(&abuf, 8 * 8);
-        p.stamps = abuf;
-        if ((++acalls % 50) == 0) {
-            long long h[8];
-            (void)hipStreamSynchronize(ctx->stream);
-            (void)hipMemcpy(h, abuf, sizeof(h), hipMemcpyDeviceToHost);
-            fprintf(stderr, "PHASE_A wg0: fill %lld  prologue+kloop %lld  dense epi %lld  gmax %lld\n", h[1] - h[0], h[2] - h[1], h[3] - h[2], h[4] - h[3]);
-        }
-    }
-#endif
     // fill_pad: the (internal) buffer covers whole tiles; columns past the image get -inf
     p.fill_pad = (out && fill_pad && ld >= (int64_t)ts.n_items * 32) ? 1 : 0;
     p.vec_ok = ((ld % 4) == 0 && (reinterpret_cast<uintptr_t>(out) % 16) == 0) ? 1 : 0;
@@ -2656,8 +2238,7 @@ int dae_launch_decode_dense_f32(dae_ctx* ctx, const dae_rowgeom& g, int B, const
     }
     if (gmax) {
         if (g.waves != 4) return dae_fail(ctx, DAE_ERR_ARG, "group maxima need 4-wave workgroups");
-        static const bool no_half = dae_exp_env("DAE_GMAX_FULL") != nullptr;             // A/B against one workgroup per CU
-        if (dtype == DAE_DTYPE_F32 && g.R_TILE == 128 && p.G == 32 && !gmax_per_wave && !p.mixT && !no_half &&
+        if (dtype == DAE_DTYPE_F32 && g.R_TILE == 128 && p.G == 32 && !gmax_per_wave && !p.mixT &&
             ts.n_items <= g.nb_rg * 4) {
             // one round of tiles (the threshold sample at batch <= 256): half row groups, two workgroups per CU
             p.n_rg = 2 * g.n_rg;
@@ -2693,22 +2274,13 @@ int dae_launch_decode_scaled_T(dae_ctx* ctx, const dae_rowgeom& g, int B, const 
 // K5 from the row-major decoder (fp32, hidden = 256, 128-row groups); returns DAE_ERR_STATE when the shape does not apply
 int dae_launch_decode_loss_rowmajor(dae_ctx* ctx, const dae_rowgeom& g, int B, int V, int H, const float* W,
                                     const float* bias, const float* h, float inv_n_batch, float* dzT, int64_t ldT,
-                                    float* loss_part, int dtype, int dz16)
+                                    float* loss_part)
 {
     if (H != 256 || g.R_TILE != 128 || g.waves != 4) return DAE_ERR_STATE;
     if ((uint64_t)ldT * 4 + (uint64_t)g.Bpad >= (1ull << 30)) return DAE_ERR_STATE;          // (32-bit lane offsets in the epilogues)
     LossRmP p;
     p.W = W; p.bias = bias; p.h = h; p.V = V; p.H = H; p.B = B; p.n_rg = g.n_rg; p.nb_rg = g.nb_rg;
     p.inv_nb = inv_n_batch; p.dzT = dzT; p.ldT = ldT; p.loss_part = loss_part;
-    if (dtype == DAE_DTYPE_BF16) {
-        // the W tile through LDS, a workgroup per tile x all playlists (training batches are <= 256: train.hip): g.grid
-        // workgroups, one loss partial each, as the caller sized them
-        if (B > 256) return DAE_ERR_STATE;
-        if (dz16) hipLaunchKernelGGL(decode_loss_shared_bf16_kernel<true>, dim3(g.grid), dim3(512), 0, ctx->stream, p);
-        else hipLaunchKernelGGL(decode_loss_shared_bf16_kernel<false>, dim3(g.grid), dim3(512), 0, ctx->stream, p);
-        DAE_CHECK_LAUNCH(ctx, "decode_loss_shared_bf16_kernel");
-        return DAE_OK;
-    }
     if (B > 256) return DAE_ERR_STATE;
     const size_t lds_s = ((size_t)2 * 32 * 260 + 8) * sizeof(float);
     static const char rs_key = 0;
@@ -2749,18 +2321,8 @@ int dae_launch_decode_loss_f32(dae_ctx* ctx, const dae_rowgeom& g, int B, float 
     if (rc) return rc;
     p.dzT = dzT; p.ldT = ldT; p.loss_part = loss_part; p.inv_nb = inv_n_batch;
     p.dz16 = (dtype == DAE_DTYPE_BF16 && dz16) ? 1 : 0;
-    if (dtype == DAE_DTYPE_BF16) {
-        // bf16 operands, fp32 accumulate (BASELINE.json configs[3]): the matrix time drops to ~1/16, the launch is
-        // bound by its VALU epilogue and the dz^T store; two waves per SIMD overlap those with the MFMAs
-        if (g.R_TILE == 128 && p.G == 16) return launch_decode<4, EPI_LOSS, 16, 8, DT_BF16>(ctx, g, p);
-        return launch_decode_rb_bf16<EPI_LOSS>(ctx, g, p);
-    }
-    // A/B: DAE_LOSS_WAVES=8 runs two waves per SIMD on the 128-row image so that one wave's VALU epilogue
-    // (4 transcendentals per element) sits under the other's MFMAs; measured 240 us against 229 us for the
-    // default one wave per SIMD (V = 170 000, B = 256)
-    static const bool w8 = dae_exp_env("DAE_LOSS_WAVES") && atoi(dae_exp_env("DAE_LOSS_WAVES")) == 8;
-    if (g.R_TILE == 128 && p.G == 32 && w8) return launch_decode<4, EPI_LOSS, 32, 8, DT_F32>(ctx, g, p);
-    return launch_decode_rb<EPI_LOSS>(ctx, g, p);
+    // (hidden 256 in 128-row groups takes the row-major K5 launches above: train.hip train_plan `rm`)
+    return dtype == DAE_DTYPE_BF16 ? launch_decode_rb_bf16<EPI_LOSS>(ctx, g, p) : launch_decode_rb<EPI_LOSS>(ctx, g, p);
 }
 
 int dae_launch_decode_filter_f32(dae_ctx* ctx, const dae_rowgeom& g, int B, const dae_tileset& ts,
@@ -2771,8 +2333,7 @@ int dae_launch_decode_filter_f32(dae_ctx* ctx, const dae_rowgeom& g, int B, cons
     int rc = fill_common(ctx, g, B, ts, p, dtype, bias_sel);
     if (rc) return rc;
     p.tau = tau; p.n_valid_col = n_valid_col; p.cand = cand; p.cand_cnt = cand_cnt; p.cap = cap;
-    static const bool f32_generic = dae_exp_env("DAE_F32_GENERIC") != nullptr;          // A/B against the generic body
-    if (dtype == DAE_DTYPE_F32 && g.R_TILE == 128 && p.G == 32 && g.waves == 4 && !f32_generic && !p.mixT) {
+    if (dtype == DAE_DTYPE_F32 && g.R_TILE == 128 && p.G == 32 && g.waves == 4 && !p.mixT) {
         const size_t lds = (size_t)4 * 64 * 32 * sizeof(float4) + 128 * sizeof(int) + 128 * sizeof(float);
         static const char attr_set_key = 0;
         if (dae_first_use(ctx, &attr_set_key)) {
@@ -2791,72 +2352,21 @@ int dae_launch_decode_filter_f32(dae_ctx* ctx, const dae_rowgeom& g, int B, cons
         return DAE_OK;
     }
     if (bf16_fast_filter(g, dtype, p.G) && !p.mixT) {
-#ifdef DAE_EXPERIMENTS
-        static const bool dbgF = dae_exp_env("DAE_DBG_F") != nullptr;     // stage stamps of the dedicated bf16 filter kernel
-        static long long* fbuf = nullptr;
-        static int fcalls = 0;
-        if (dbgF) {
-            if (!fbuf) { (void)hipMalloc(&fbuf, 32 * 8); (void)hipMemset(fbuf, 0, 32 * 8); }
-            p.stamps = fbuf;
-            if ((++fcalls % 100) == 0) {
-                long long h[32];
-                (void)hipStreamSynchronize(ctx->stream);
-                (void)hipMemcpy(h, fbuf, sizeof(h), hipMemcpyDeviceToHost);
-                for (int w = 0; w < 2; ++w) {
-                    fprintf(stderr, "FILTER wg%d:", w ? 100 : 0);
-                    for (int i = 1; i < 15; ++i) if (h[16 * w + i]) fprintf(stderr, " [%d]%lld", i, h[16 * w + i] - h[16 * w]);
-                    fprintf(stderr, "\n");
-                }
-            }
-        }
-#endif
         const size_t lds = (size_t)(g.R_TILE / 32) * 64 * 16 * sizeof(float4) + (size_t)g.R_TILE * (sizeof(int) + sizeof(float)) + 16;     // (+ the claim counter)
         static const char attr_set_key = 0;
         if (dae_first_use(ctx, &attr_set_key)) {
             DAE_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_bf16_h256_filter_kernel<1, 4, 8, 8>),
                                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            DAE_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_bf16_h256_filter_kernel<2, 4, 16, 4>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            DAE_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_bf16_h256_filter_kernel<1, 8, 16, 4>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         }
         hipEvent_t e0 = nullptr, e1 = nullptr;
-        const int regb = bf16_regb_variant(g);
-#ifdef DAE_EXPERIMENTS
-        if (regb) {
-            if (ctx->prof_armed) {
-                e0 = ctx->prof_ev[ctx->prof_used]; e1 = ctx->prof_ev[ctx->prof_used + 1];
-                ctx->prof_armed = false;
-                ctx->prof_used += 2;
-                ctx->prof_kernel = regb == 2 ? "decode_bf16_h256_regb_filter_kernel<2, 16>" : "decode_bf16_h256_regb_filter_kernel<3, 8>";
-            }
-            if (regb == 2)
-                hipExtLaunchKernelGGL((decode_bf16_h256_regb_filter_kernel<2, 16>), dim3(g.grid), dim3(256), 0, ctx->stream, e0, e1, 0, p);
-            else
-                hipExtLaunchKernelGGL((decode_bf16_h256_regb_filter_kernel<3, 8>), dim3(g.grid), dim3(256), 0, ctx->stream, e0, e1, 0, p);
-            DAE_CHECK_LAUNCH(ctx, "decode_bf16_h256_regb_filter_kernel");
-            return DAE_OK;
-        }
-#else
-        (void)regb;
-#endif
         if (ctx->prof_armed) {
             e0 = ctx->prof_ev[ctx->prof_used]; e1 = ctx->prof_ev[ctx->prof_used + 1];
             ctx->prof_armed = false;
             ctx->prof_used += 2;
-            ctx->prof_kernel = g.R_TILE == 256 ? "decode_bf16_h256_filter_kernel<1, 8, 16, 4>"
-                             : bf16_pair_variant() ? "decode_bf16_h256_filter_kernel<2, 4, 16, 4>"
-                                                   : "decode_bf16_h256_filter_kernel<1, 4, 8, 8>";
+            ctx->prof_kernel = "decode_bf16_h256_filter_kernel<1, 4, 8, 8>";
         }
-        if (g.R_TILE == 256)
-            hipExtLaunchKernelGGL((decode_bf16_h256_filter_kernel<1, 8, 16, 4>), dim3(g.grid), dim3(256), lds,
-                                  ctx->stream, e0, e1, 0, p);
-        else if (bf16_pair_variant())
-            hipExtLaunchKernelGGL((decode_bf16_h256_filter_kernel<2, 4, 16, 4>), dim3(g.grid), dim3(256), lds,
-                                  ctx->stream, e0, e1, 0, p);
-        else
-            hipExtLaunchKernelGGL((decode_bf16_h256_filter_kernel<1, 4, 8, 8>), dim3(g.grid), dim3(512), lds,
-                                  ctx->stream, e0, e1, 0, p);
+        hipExtLaunchKernelGGL((decode_bf16_h256_filter_kernel<1, 4, 8, 8>), dim3(g.grid), dim3(512), lds,
+                              ctx->stream, e0, e1, 0, p);
         DAE_CHECK_LAUNCH(ctx, "decode_bf16_h256_filter_kernel");
         return DAE_OK;
     }

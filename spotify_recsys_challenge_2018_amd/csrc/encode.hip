@@ -56,8 +56,6 @@ struct EncP {
     float* sg_out;       // [B,H] sigmoid BEFORE hidden dropout (training backward) or null
     float* xhat_out;     // [nnz] normalised, dropped-out input weights (training backward) or null
     unsigned w_bytes;    // V * H * 4 (< 4 GiB: buffer descriptor range)
-    int dbg_row0;        // experiment: read row 0 instead of the real rows
-    int dbg_stop;        // experiment: leave the kernel after stage n
 };
 
 // issue the loads of one group of 16 non-zeros (indices base..base+15 of the current 64-chunk);
@@ -205,10 +203,8 @@ __global__ __launch_bounds__(64 * WGW) void encode_split_kernel(const EncP p)
     const int hq = H / HS;                       // hidden units of this wave (multiple of 4)
     const int hbytes = H * 4;
     const __amdgpu_buffer_rsrc_t rs = w_rsrc(p.W, p.w_bytes);
-    if (DAE_EXP_ON(p.dbg_stop == 1)) return;
     const int beg = p.row_ptr[row], end = p.row_ptr[row + 1];
     const int nnz = end - beg;
-    if (DAE_EXP_ON(p.dbg_stop == 2)) { if (nnz == -7) p.h_out[0] = 0.f; return; }
 
     // Typical rows (<= 256 non-zeros: a playlist holds <= 250 items, spotify_reader.py:84) keep
     // their (column, value) entries in 4 registers per lane, fetched by 8 INDEPENDENT loads; the
@@ -228,7 +224,6 @@ __global__ __launch_bounds__(64 * WGW) void encode_split_kernel(const EncP p)
             if (64 * c + lane < nnz)
                 xl[c] = (xl[c] / p.ikp) * floorf(p.ikp + dae_uniform(p.seed, 0U, (uint32_t)row, (uint32_t)cl[c]));
     }
-    if (DAE_EXP_ON(p.dbg_stop == 3)) { if (xl[0] + xl[1] + xl[2] + xl[3] + cl[0] == -7.f) p.h_out[0] = 0.f; return; }
     // s = sum of the weights in column order (sequential: canonical order)
     float s = 0.0f;
 #pragma unroll
@@ -247,7 +242,6 @@ __global__ __launch_bounds__(64 * WGW) void encode_split_kernel(const EncP p)
         for (int i = 0; i < n; ++i) s += rl_f(x, i);
     }
     const float denom = s + 1e-10f;
-    if (DAE_EXP_ON(p.dbg_stop == 4)) { if (denom == -7.f) p.h_out[0] = 0.f; return; }
     float wl[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -327,7 +321,6 @@ __global__ __launch_bounds__(64 * WGW) void encode_split_kernel(const EncP p)
                 ENC_CHAIN(xb, w_l, CK, n - CK, CK)
             }
         }
-        if (DAE_EXP_ON(p.dbg_stop == 5)) { if (acc == -7.f) p.h_out[0] = 0.f; return; }
         if (active) {
             float hv = dae_sigmoidf(acc + p.b_enc[hu]);
             if (p.sg_out) p.sg_out[(size_t)row * H + hu] = hv;
@@ -374,15 +367,9 @@ int dae_launch_encode(dae_ctx* ctx, const int32_t* row_ptr, const int32_t* col, 
     if ((size_t)V * H * 4 >= 0xFFFFFFFFull)
         return dae_fail(ctx, DAE_ERR_ARG, "W_enc of %d x %d exceeds the 4 GiB buffer range", V, H);
     p.w_bytes = (unsigned)((size_t)V * H * 4);
-    static const int dbg_row0 = dae_exp_env("DAE_DBG_ENC_ROW0") ? atoi(dae_exp_env("DAE_DBG_ENC_ROW0")) : 0;
-    p.dbg_row0 = dbg_row0;
-    static const int dbg_stop = dae_exp_env("DAE_DBG_ENC_STOP") ? atoi(dae_exp_env("DAE_DBG_ENC_STOP")) : 0;
-    p.dbg_stop = dbg_stop;
     if (B <= 1024 && (H % 16) == 0 && H >= 64) {
         // small batch: latency bound -> 4 waves per row (by hidden units), 4x the bytes in flight
-        static const bool enc_wg1 = dae_exp_env("DAE_ENC_WG1") != nullptr;                     // A/B: one wave per workgroup
-        if (enc_wg1) hipLaunchKernelGGL((encode_split_kernel<4, 1>), dim3(B * 4), dim3(64), 0, ctx->stream, p);
-        else hipLaunchKernelGGL((encode_split_kernel<4, 4>), dim3(B), dim3(256), 0, ctx->stream, p);
+        hipLaunchKernelGGL((encode_split_kernel<4, 4>), dim3(B), dim3(256), 0, ctx->stream, p);
     } else if (B <= 2048) {
         // few rows: one wave per workgroup spreads the rows over all CUs
         hipLaunchKernelGGL(encode_kernel<1>, dim3(B), dim3(64), 0, ctx->stream, p);

@@ -128,7 +128,6 @@ struct MixP {
     int B, n_rg, nb_rg, Bpad;
     uint4* cand; int* cand_cnt; int cap;         // filter: [bir][Bpad][cap] entries (u_t, u_d, column, 0) + [bir][Bpad] counts
     float* samp; int64_t ld_s;                   // sample: [B][ld_s] maxima of 4-column groups, element item * 8 + 4 hi + qd
-    int exp_mode;                                // experiments build: 1 = no epilogue at all, 2 = the maxima's test only
 };
 
 template <int NSD, int NST, int RB, int QR, int NW, int MODE>
@@ -281,14 +280,6 @@ __global__ __launch_bounds__(NW * 64, 1) void mix_bf16_kernel(const MixP p)
         }
 
         // ---- epilogue: lane = playlist j of row block rb; register reg is column 32 t + 4 hi + (reg & 3) + 8 (reg >> 2)
-#ifdef DAE_EXPERIMENTS
-        if (p.exp_mode == 1) {
-            float sink = 0.0f;
-#pragma unroll
-            for (int rb = 0; rb < RB; ++rb) sink += accT[rb][0] + accD[rb][5];
-            if (sink == 123.456f) p.cand_cnt[0] = 1;
-        } else
-#endif
         if (MODE == 0) {
 #pragma unroll
             for (int rb = 0; rb < RB; ++rb) {
@@ -297,9 +288,6 @@ __global__ __launch_bounds__(NW * 64, 1) void mix_bf16_kernel(const MixP p)
 #pragma unroll
                 for (int reg = 1; reg < 16; ++reg) { mT = fmaxf(mT, accT[rb][reg]); mD = fmaxf(mD, accD[rb][reg]); }
                 // (the pair of maxima bounds every pair of the lane's 16 columns)
-#ifdef DAE_EXPERIMENTS
-                if (p.exp_mode == 2) { if (mix_can_reach(mT, mD, wt, wp, tv) && tv == 123.456f) p.cand_cnt[0] = 1; continue; }
-#endif
                 if (mix_can_reach(mT, mD, wt, wp, tv)) {
                     // one compare pair per element first (mix_thresholds); the exact test only for the registers in which SOME lane
                     // of the wave still has a column in play (wave-uniform: __ballot)
@@ -526,7 +514,6 @@ struct MixRefP {
     uint2* out; int* out_cnt; int out_cap;
     int* guard;                        // {violations, a violating column}
     int* stat;                         // [B][2] {candidates, recomputed}
-    long long* stamps;                 // experiments build: stage stamps of row 0's workgroup (DAE_DBG_MR)
     // FUSED SELECTION (round 5, as refine.hip; k <= 512): the launch ends the call -- the row's seeds out, its k best mixed
     // scores in order (main_challenge.py:26-36 on DAEs.py:180's y) to fo.out_score / out_idx; `out` then only takes the rows
     // with more survivors than the ordering stage holds
@@ -609,11 +596,6 @@ __device__ __forceinline__ float two_down(float x) { return dae_okey_inv(dae_oke
 
 // (The library is built with -fno-vectorize: hipcc's loop vectorizer miscompiled this kernel's per-lane staging loop in round 4 --
 // spotify_recsys_challenge_2018_amd/build.py, scripts/probe/vec_repro.hip.)
-#ifdef DAE_EXPERIMENTS
-#define MSTAMP(i) if (p.stamps && blockIdx.x == 0 && threadIdx.x == 0) p.stamps[i] = __builtin_readcyclecounter();
-#else
-#define MSTAMP(i)
-#endif
 __global__ __launch_bounds__(MR_THREADS, 1) void mix_refine_kernel(const MixRefP p)
 {
     __shared__ int seg_prefix[MR_MAX_SEG + 2];
@@ -662,7 +644,6 @@ __global__ __launch_bounds__(MR_THREADS, 1) void mix_refine_kernel(const MixRefP
     }
     __syncthreads();
     const int total = seg_prefix[nseg];
-    MSTAMP(0)
     auto give_up = [&](int code) {
         // a row the launch cannot vouch for (more candidates than its buffers hold): counted like a bound failure -- the
         // callers then re-score the launch with the fp32 kernels
@@ -774,7 +755,6 @@ __global__ __launch_bounds__(MR_THREADS, 1) void mix_refine_kernel(const MixRefP
         const unsigned a = __shfl_xor(kmx, d), b = __shfl_xor(kmn, d);
         kmx = a > kmx ? a : kmx; kmn = b < kmn ? b : kmn;
     }
-    MSTAMP(1)
     if (lane == 0) { atomicMax(&cnts[0], kmx); atomicMin(&cnts[1], kmn); }
     unsigned* hist = reinterpret_cast<unsigned*>(tb);
     for (int i = tid; i < MR_BINS; i += MR_THREADS) hist[i] = 0u;
@@ -885,7 +865,6 @@ __global__ __launch_bounds__(MR_THREADS, 1) void mix_refine_kernel(const MixRefP
     }
     __syncthreads();                                             // (the last reads of kl and of the histogram)
 
-    MSTAMP(2)
     // ---- 3. the survivors: upper bound >= tau'.  Their flat indices take kl's place.
     if (staged) {
         for (int c0 = 0; c0 < total; c0 += MR_THREADS) {
@@ -897,7 +876,6 @@ __global__ __launch_bounds__(MR_THREADS, 1) void mix_refine_kernel(const MixRefP
     const int n = s_n;
     if (tid == 0 && p.stat) { p.stat[2 * row] = total; p.stat[2 * row + 1] = n; }
     if (n > p.out_cap) { give_up(-3); return; }
-    MSTAMP(3)
     const bool fast = p.fuse && n <= DAE_RANK_MAX;               // the survivors' keys stay in LDS
     if (p.fuse) build_bitmap();
 
@@ -935,7 +913,6 @@ __global__ __launch_bounds__(MR_THREADS, 1) void mix_refine_kernel(const MixRefP
             if (lane == 0 && mx != 0u) { atomicMin(&f_range[0], mn); atomicMax(&f_range[1], mx); }
         }
     }
-    MSTAMP(4)
     if (tid == 0) p.out_cnt[row] = n;
     if (!p.fuse) return;
     __syncthreads();                                             // the recomputation is over: its buffers become the ordering stage's
@@ -946,7 +923,6 @@ __global__ __launch_bounds__(MR_THREADS, 1) void mix_refine_kernel(const MixRefP
         select_from_list(n);
     }
 }
-#undef MSTAMP
 
 // ---- the audit of dropped columns (round 6; the plain exact mode's is audit.hip) ---------------------------------------------
 // The refine launch's guard sees survivors only; a column the filter launch dropped is never recomputed.  Every N-th launch
@@ -1125,14 +1101,6 @@ int dae_mix_topk_exact_impl(dae_ctx* tc, dae_ctx* dc, const float* feat, int64_t
     const size_t lds = (size_t)RB * 64 * NS * sizeof(uint4) + (size_t)R_TILE * 8 + 16;
     auto kf = mix_bf16_kernel<NSD, NST, RB, QR, NW, 0>;
     auto ks = mix_bf16_kernel<NSD, NST, RB, QR, NW, 1>;
-#ifdef DAE_EXPERIMENTS
-    static const int exp_mode = dae_exp_env("DAE_MIX_EXP") ? atoi(dae_exp_env("DAE_MIX_EXP")) : 0;   // stage bisection of the filter launch
-    p.exp_mode = exp_mode;
-    static const int qr_env = dae_exp_env("DAE_MIX_QR") ? atoi(dae_exp_env("DAE_MIX_QR")) : 0;      // A/B: W ring depth
-    if (qr_env == 12) { kf = mix_bf16_kernel<NSD, NST, RB, 12, NW, 0>; ks = mix_bf16_kernel<NSD, NST, RB, 12, NW, 1>; }
-    if (qr_env == 16) { kf = mix_bf16_kernel<NSD, NST, RB, 16, NW, 0>; ks = mix_bf16_kernel<NSD, NST, RB, 16, NW, 1>; }
-    if (qr_env == 4) { kf = mix_bf16_kernel<NSD, NST, RB, 4, NW, 0>; ks = mix_bf16_kernel<NSD, NST, RB, 4, NW, 1>; }
-#endif
     static const char attr_key = 0;
     if (dae_first_use(tc, &attr_key)) {
         DAE_HIP_CHECK(tc, hipFuncSetAttribute(reinterpret_cast<const void*>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1155,8 +1123,6 @@ int dae_mix_topk_exact_impl(dae_ctx* tc, dae_ctx* dc, const float* feat, int64_t
             nb_s = ((n_samp + 8 * NW - 1) / (8 * NW) + DAE_NUM_XCD - 1) / DAE_NUM_XCD * DAE_NUM_XCD;
             if (nb_s > nb) nb_s = nb;
         }
-        static const int nbs_env = dae_exp_env("DAE_MIX_SAMPLE_NB") ? atoi(dae_exp_env("DAE_MIX_SAMPLE_NB")) : 0;       // A/B (experiments build)
-        if (nbs_env > 0) nb_s = nbs_env >= nb ? nb : nbs_env / DAE_NUM_XCD * DAE_NUM_XCD;
         if (nb_s < DAE_NUM_XCD) nb_s = DAE_NUM_XCD;
         MixP ps = p;
         ps.nb_rg = nb_s;
@@ -1209,27 +1175,12 @@ int dae_mix_topk_exact_impl(dae_ctx* tc, dae_ctx* dc, const float* feat, int64_t
     r.fo = dae_rank_out{k, DAE_OUT_LOGIT, out_score, out_idx};   // (the mixed score is a probability already: it goes out as it is)
     r.seed_col = seed_col;
     if (nb > MR_MAX_SEG) return dae_fail(tc, DAE_ERR_ARG, "too many candidate segments (%d)", nb);
-#ifdef DAE_EXPERIMENTS
-    static const bool dbg_mr = dae_exp_env("DAE_DBG_MR") != nullptr;
-    static long long* mr_stamps = nullptr;
-    static int mr_calls = 0;
-    if (dbg_mr) { if (!mr_stamps) (void)hipMalloc(&mr_stamps, 8 * 8); r.stamps = mr_stamps; }
-#endif
     static const char ref_key = 0;
     if (dae_first_use(tc, &ref_key))
         DAE_HIP_CHECK(tc, hipFuncSetAttribute(reinterpret_cast<const void*>(mix_refine_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                               (int)(2 * MR_STAGE * sizeof(unsigned))));
     hipLaunchKernelGGL(mix_refine_kernel, dim3(B), dim3(MR_THREADS), 2 * MR_STAGE * sizeof(unsigned), st, r);
     DAE_CHECK_LAUNCH(tc, "mix_refine_kernel");
-#ifdef DAE_EXPERIMENTS
-    if (dbg_mr && (++mr_calls % 4) == 0) {
-        long long hst[8];
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(hst, mr_stamps, sizeof(hst), hipMemcpyDeviceToHost);
-        fprintf(stderr, "MIX_REFINE row0 cycles: bounds %lld | threshold %lld | list %lld | recompute %lld\n", hst[1] - hst[0], hst[2] - hst[1],
-                hst[3] - hst[2], hst[4] - hst[3]);
-    }
-#endif
 
     if (!fuse) {
         dae_topk_args ta;

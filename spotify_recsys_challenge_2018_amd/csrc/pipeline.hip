@@ -57,16 +57,14 @@ struct Slot {                     // one launch from staging to its last polled 
     int32_t* d_idx = nullptr; float* d_score = nullptr;    // the launch's lists on the device (moved out on the OUT stream, round 6)
     int32_t* d_flags = nullptr;                            // {csr status, guard violations, guard column} as the launch left them
     hipEvent_t ev_scored = nullptr;                        // the scoring call's last kernel (the out stream waits for it)
-    bool sync_fetch = true;                                // ev_fetch was recorded by issue() (modes 0, 1): the wait ends on it
     int32_t* h_titles = nullptr; float* h_use = nullptr;   // titled pipelines: [group_rows][L] characters, [group_rows] titles_use
     int32_t* d_titles = nullptr; float* d_use = nullptr;
     int titled = 0;               // this launch ranks the title-mixed score (its feeds came through dae_pipeline_submit_titled)
-    hipEvent_t dbg_t0 = nullptr, dbg_t1 = nullptr; bool dbg_used = false;      // experiments build (DAE_DBG_PIPE)
     unsigned polls = 0;           // non-waiting polls of this issue that found its word missing (every 256th asks the runtime)
     int32_t seq = 0;              // the sequence word this launch's last kernel writes into h_flags[3] (the caller's wait watches it)
     int ran_dtype = 0;            // arithmetic the launch was issued with (a paused exact mode issues DAE_DTYPE_F32)
-    hipEvent_t ev_fetch = nullptr, ev_h2d = nullptr, ev_gate = nullptr;
-    int state = 0;                // 0 free, 1 staging (open launch), 2 queued for the worker, 3 issued (ev_fetch recorded)
+    hipEvent_t ev_h2d = nullptr, ev_gate = nullptr;
+    int state = 0;                // 0 free, 1 staging (open launch), 2 queued for the worker, 3 issued
     int rows = 0; int64_t nnz = 0;
     int block = -1, lane = -1;
     std::vector<Feed> feeds;
@@ -88,7 +86,7 @@ struct dae_pipeline {
     hipStream_t prep_stream = nullptr;
     dae_ctx* prep_ctx = nullptr;
     dae_ctx* prep_tctx = nullptr;         // titled pipelines: the title scorer's context of the prep stream (its convolution table)
-    hipStream_t out_stream = nullptr;     // the lists' way out (out_mode 2): the out thread's copies
+    hipStream_t out_stream = nullptr;     // the lists' way out: the out thread's copies
     hipStream_t copy_stream = nullptr;    // uploads: hipMemcpyAsync on a stream that still has kernels queued blocks its caller
                                           // until they have run (measured: 0.43 ms per launch next to the fp32 decode) -- on a
                                           // stream of their own the uploads run ahead and the lane waits for their event
@@ -99,11 +97,10 @@ struct dae_pipeline {
     std::thread worker;
     bool stop = false;
     // how a launch's lists reach the host (round 6, measured in profiles/r06_notes.md 5: M playlists/s through the loop, exact /
-    // bf16): 0 = the scoring call's last kernel stores them straight into the pinned block (round 5: 7.9 - 8.1 / 8.8), 2 = the copy
-    // ENGINE, driven by a thread of its own that makes no HIP call until the launch's "scored" word has arrived (8.3 / 9.05: the
-    // last scoring kernel no longer sits on its CUs while the link takes 4 MB).  (A 32-workgroup copy kernel on a stream of its
-    // own lost: 6.7 / 7.5.  Without any copy-out the loop runs at 9.9 / 11.4: the link is what the loop pays for.)
-    int out_mode = 2;
+    // bf16): the copy ENGINE, driven by a thread of its own that makes no HIP call until the launch's "scored" word has arrived
+    // (8.3 / 9.05).  Stores straight into the pinned block from the scoring call's last kernel (round 5) lost: 7.9 - 8.1 / 8.8,
+    // that kernel sat on its CUs while the link took 4 MB.  (A 32-workgroup copy kernel on a stream of its own lost: 6.7 / 7.5.
+    // Without any copy-out the loop runs at 9.9 / 11.4: the link is what the loop pays for.)
     std::thread out_worker;
     std::deque<int> out_queue;
     std::mutex out_mu;
@@ -121,21 +118,11 @@ struct dae_pipeline {
     uint64_t guard_fallbacks = 0, launches = 0, seq_counter = 0;
     bool has_title = false;       // dae_pipeline_create_titled
     TitleW tw;
-    double dbg_dev_ms = 0.0; uint64_t dbg_dev_n = 0;
-    std::vector<std::pair<int, uint64_t>> dbg_log;   // experiments build: (tag * 100 + slot, ns) host timeline
-    uint64_t dbg_ns[4] = {0, 0, 0, 0};            // experiments build: cumulative stage stamps of issue()
     int exact_pause = 0, overflow_streak = 0;      // titled + exact: launches left on the fp32 kernels / overflow events in a row
     uint64_t issue_ns = 0, idle_ns = 0, submit_ns = 0, wait_ns = 0;      // where the host side of the loop spends its time (dae_pipeline_times)
 };
 
 namespace {
-
-#ifdef DAE_EXPERIMENTS
-#define PLOG(p, tag, slot) do { if (dae_exp_env("DAE_DBG_PIPE") && (p)->dbg_log.size() < 100000) (p)->dbg_log.emplace_back((tag) * 100 + (slot), \
-    (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count()); } while (0)
-#else
-#define PLOG(p, tag, slot)
-#endif
 
 thread_local std::string g_pipe_err;
 
@@ -176,8 +163,8 @@ struct DeviceGuard {
 // hipEventQuery in a loop -- slows the library thread's enqueueing down (measured on the titled loop, one lane: 0.94 ms per
 // launch = staging + issue + device + fetch one after the other, against 0.58 ms of kernels; a consumer that idled 80 us per
 // feed OUTSIDE HIP made the loop faster; profiles/r05_notes.md).
-// So the wait watches the launch's SEQUENCE WORD -- the last word flags_to_host_kernel, the last kernel of the launch, writes
-// into the slot's pinned flags -- without any HIP call, and only then takes the (completed) event for the formal ordering.
+// So the wait watches the launch's SEQUENCE WORD -- the last word the out thread writes into the slot's pinned flags, once the
+// launch's lists and flags have arrived -- without any HIP call.
 hipError_t wait_launch(const Slot& S)
 {
     const volatile int32_t* seq = S.h_flags + 3;
@@ -185,15 +172,14 @@ hipError_t wait_launch(const Slot& S)
         if (spins < 200) std::this_thread::yield();
         else std::this_thread::sleep_for(std::chrono::microseconds(20));
         if ((spins & 1023) == 1023) {                        // (a failed launch never writes its word: ask the runtime now and then)
-            // ev_scored: recorded by issue() behind the scoring call on the lane's stream (ev_fetch is recorded later in the copy-
-            // engine mode: until then it still holds its previous, completed record).  Complete but no word yet = the lists are
-            // on their way out: keep waiting
+            // ev_scored: recorded by issue() behind the scoring call on the lane's stream.  Complete but no word yet = the lists
+            // are on their way out: keep waiting
             const hipError_t q = hipEventQuery(S.ev_scored);
             if (q != hipErrorNotReady && q != hipSuccess) return q;
         }
     }
     __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    return S.sync_fetch ? hipEventSynchronize(S.ev_fetch) : hipSuccess;
+    return hipSuccess;
 }
 
 // {csr status, guard violations, guard column} as the launch's own stream leaves them -> the slot's device words (the lane's
@@ -204,19 +190,7 @@ __global__ void flags_snapshot_kernel(int32_t* dst, const int32_t* status, const
         dst[0] = status[0];
         dst[1] = guard ? guard[0] : 0;
         dst[2] = guard ? guard[1] : -1;
-        if (scored_host) { __threadfence_system(); *scored_host = seq; }         // (copy-engine mode: the out thread watches this word)
-    }
-}
-
-// {csr status, guard violations, guard column} of a launch -> its pinned flag words
-__global__ void flags_to_host_kernel(int32_t* dst, const int32_t* snap, int32_t seq)
-{
-    if (threadIdx.x == 0) {
-        dst[0] = snap[0];
-        dst[1] = snap[1];
-        dst[2] = snap[2];
-        __threadfence_system();
-        dst[3] = seq;                                            // (last: the caller's wait watches this word)
+        if (scored_host) { __threadfence_system(); *scored_host = seq; }         // (the out thread watches this word)
     }
 }
 
@@ -256,15 +230,6 @@ int ensure_f32(dae_pipeline* p, int lane)
 int issue(dae_pipeline* p, Slot& S, int dtype)
 {
     Lane& L = p->lanes[S.lane];
-#ifdef DAE_EXPERIMENTS         // where a launch's issue time goes (DAE_DBG_PIPE=1 prints the sums when the pipeline is destroyed)
-    static const bool dbg_pipe = dae_exp_env("DAE_DBG_PIPE") != nullptr;
-    const auto t_a = std::chrono::steady_clock::now();
-    auto lap = [&](int i) {
-        if (dbg_pipe) p->dbg_ns[i] += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_a).count();
-    };
-#else
-    auto lap = [&](int) {};
-#endif
     // (plain launches stage 32-bit (row, col) pairs -- submit_impl narrows them while it copies -- titled ones the int64 feed)
     PIPE_HIP(p, hipMemcpyAsync(S.d_pos, S.h_pos, (size_t)S.nnz * 2 * (S.titled ? sizeof(int64_t) : sizeof(int32_t)), hipMemcpyHostToDevice,
                                p->copy_stream));
@@ -283,25 +248,13 @@ int issue(dae_pipeline* p, Slot& S, int dtype)
     }
     int rc;
     S.ran_dtype = dtype;
-#ifdef DAE_EXPERIMENTS
-    if (dbg_pipe) {                                          // device time of the launch: a timing event pair on the lane's stream
-        if (!S.dbg_t0) { (void)hipEventCreate(&S.dbg_t0); (void)hipEventCreate(&S.dbg_t1); }
-        else if (S.dbg_used) { float ms = 0.f; if (hipEventElapsedTime(&ms, S.dbg_t0, S.dbg_t1) == hipSuccess) { p->dbg_dev_ms += ms; ++p->dbg_dev_n; } }
-        (void)hipEventRecord(S.dbg_t0, L.stream);
-        S.dbg_used = true;
-    }
-#endif
-    // NO DOWNLOADS: the last kernel of a launch writes its lists straight into the launch's pinned result block (host memory
-    // the device reaches over the link: 1.5 - 4 MB of coalesced stores per launch), and a one-wave kernel leaves the launch's
-    // flags next to them.  A hipMemcpyAsync device-to-host blocks its caller until everything queued before it has run --
-    // whichever stream it is put on (measured: on the lane's stream and on a fetch stream behind an event alike): the
+    // NO DOWNLOADS from this thread: a hipMemcpyAsync device-to-host blocks its caller until everything queued before it has
+    // run -- whichever stream it is put on (measured: on the lane's stream and on a fetch stream behind an event alike): the
     // library thread sat in those calls for the length of every launch and a second launch was never in flight
-    // (0.77 of a titled launch's 0.9 ms of issue time; profiles/r05_notes.md).
-    OutBlock& ob = p->blocks[S.block];
-    const bool direct = p->out_mode == 0;
-    int32_t* const out_idx = direct ? ob.idx : S.d_idx;
-    float* const out_score = !p->want_scores ? L.d_score : direct ? ob.score : S.d_score;     // (scores nobody fetches stay on the lane)
-    lap(0);
+    // (0.77 of a titled launch's 0.9 ms of issue time; profiles/r05_notes.md).  The lists stay on the device; the out thread
+    // moves them (out_worker_main).
+    int32_t* const out_idx = S.d_idx;
+    float* const out_score = p->want_scores ? S.d_score : L.d_score;     // (scores nobody fetches stay on the lane)
     if (S.titled) {
         // main_challenge.py:80-90 with DAE_title: the whole titled launch in one library call (api.hip dae_title_score)
         const TitleW& t = p->tw;
@@ -320,7 +273,6 @@ int issue(dae_pipeline* p, Slot& S, int dtype)
         PIPE_HIP(p, hipStreamWaitEvent(L.stream, S.ev_prep, 0));
         rc = dae_title_rank(L.tctx, L.ctx, dtype, S.rows, p->V, p->H, t.ld_feat, tb, p->n_tracks, p->k, out_score, out_idx, L.d_guard);
         if (rc) return pfatal(p, rc, dae_last_error(L.tctx));
-        lap(1);
     } else {
         // the feed -> CSR and the seed lists (the playlist's own tracks) in ONE group of four launches (round 6: six + a wider feed)
         // ... on the prep stream, behind the upload; the lane's stream only waits for the finished CSR
@@ -334,11 +286,8 @@ int issue(dae_pipeline* p, Slot& S, int dtype)
                             S.d_srp, S.d_scol, p->k, DAE_OUT_SCORE, out_score, out_idx);
         if (rc) return pfatal(p, rc, dae_last_error(L.ctx));
     }
-    // The downloads go to the lane's FETCH stream, behind an event of the launch: a hipMemcpyAsync on a stream that still has
-    // kernels queued blocks its caller until they have run (as for the uploads above) -- on the lane's own stream the library
-    // thread sat in these calls for the length of the launch (0.77 ms of a titled launch's 0.9 ms issue time, stage stamps of
-    // issue(): profiles/r05_notes.md), and no second launch was in flight.  The small words first pass through one device
-    // block (flags: status, guard words), so a launch costs two or three copies.
+    // The small words first pass through one device block (flags: status, guard words), so the out thread's copies of a
+    // launch are two or three.
     const int32_t* gw = nullptr;                             // the guard words as this launch left them (titled fp32: zeros)
     if (S.titled) {
         gw = L.d_guard;
@@ -351,33 +300,19 @@ int issue(dae_pipeline* p, Slot& S, int dtype)
     S.seq = (int32_t)(((++p->seq_counter << 1) | 1u) & 0x7FFFFFFFu);
     S.polls = 0;
     hipLaunchKernelGGL(flags_snapshot_kernel, dim3(1), dim3(64), 0, L.stream, S.d_flags, S.d_status, gw,
-                       p->out_mode == 2 ? S.h_flags + 4 : nullptr, S.seq);
+                       S.h_flags + 4, S.seq);
     PIPE_HIP(p, hipGetLastError());
-#ifdef DAE_EXPERIMENTS
-    if (dbg_pipe) (void)hipEventRecord(S.dbg_t1, L.stream);
-#endif
     PIPE_HIP(p, hipEventRecord(S.ev_scored, L.stream));
-    if (p->out_mode == 2) {
-        // the copy engine, from the out thread: nothing more to enqueue here
-        S.sync_fetch = false;
-        {
-            std::lock_guard<std::mutex> g(p->out_mu);
-            p->out_queue.push_back((int)(&S - p->slots.data()));
-        }
-        p->cv_out.notify_one();
-        lap(2);
-        return DAE_OK;
+    // the copy engine, from the out thread: nothing more to enqueue here
+    {
+        std::lock_guard<std::mutex> g(p->out_mu);
+        p->out_queue.push_back((int)(&S - p->slots.data()));
     }
-    S.sync_fetch = true;
-    hipStream_t fs = L.stream;
-    hipLaunchKernelGGL(flags_to_host_kernel, dim3(1), dim3(64), 0, fs, S.h_flags, S.d_flags, S.seq);
-    PIPE_HIP(p, hipGetLastError());
-    PIPE_HIP(p, hipEventRecord(S.ev_fetch, fs));
-    lap(2);
+    p->cv_out.notify_one();
     return DAE_OK;
 }
 
-// out_mode 2: the lists of every issued launch, in issue order, through the copy engine.  The thread makes no HIP call until the
+// The out thread: the lists of every issued launch, in issue order, through the copy engine.  The thread makes no HIP call until the
 // launch's "scored" word (written by flags_snapshot_kernel, the scoring call's last kernel) has arrived -- a thread parked inside
 // hipEventSynchronize slowed the issuing thread's enqueueing down (profiles/r05_notes.md) -- then three asynchronous copies on the
 // out stream (nothing is queued there: they do not block), one synchronize, and the sequence word the caller's wait watches.
@@ -439,9 +374,7 @@ void worker_main(dae_pipeline* p)
             std::lock_guard<std::mutex> g(p->issue_mu);
             int dt = p->dtype;
             if (S.titled && dt == DAE_DTYPE_BF16_EXACT && p->exact_pause > 0) { --p->exact_pause; dt = DAE_DTYPE_F32; }
-            PLOG(p, 2, si);
             (void)issue(p, S, dt);
-            PLOG(p, 3, si);
         }
         lk.lock();
         p->issue_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_iss).count();
@@ -465,7 +398,6 @@ int close_open(dae_pipeline* p)
     p->next_lane = (p->next_lane + 1) % (int)p->lanes.size();
     S.state = 2;
     S.next_feed = 0;
-    PLOG(p, 1, p->open_slot);
     p->queue.push_back(p->open_slot);
     p->open_slot = -1;
     p->cv_worker.notify_one();
@@ -538,31 +470,6 @@ int dae_pipeline_destroy(dae_pipeline* p)
     p->cv_out.notify_all();
     if (p->out_worker.joinable()) p->out_worker.join();
     DeviceGuard dev_guard(p->device);
-#ifdef DAE_EXPERIMENTS
-    if (dae_exp_env("DAE_DBG_PIPE"))
-        fprintf(stderr, "PIPE issue(): uploads+gate %.2f ms | + scoring calls %.2f ms | + downloads %.2f ms (cumulative, %llu launches)\n",
-                p->dbg_ns[0] / 1e6, p->dbg_ns[1] / 1e6, p->dbg_ns[2] / 1e6, (unsigned long long)p->launches);
-    if (dae_exp_env("DAE_DBG_PIPE") && p->dbg_log.size() > 400) {
-        uint64_t prev = 0;                                   // intervals between consecutive "got" events (launch completions seen by the caller)
-        fprintf(stderr, "PLOG got-intervals (us):");
-        for (const auto& e : p->dbg_log)
-            if (e.first / 100 == 4) { if (prev) fprintf(stderr, " %.0f", (e.second - prev) / 1e3); prev = e.second; }
-        fprintf(stderr, "\n");
-        {   // the events around the longest interval
-            size_t worst = 0; uint64_t wl = 0, pv = 0;
-            for (size_t i = 0; i < p->dbg_log.size(); ++i)
-                if (p->dbg_log[i].first / 100 == 4) { if (pv && i > 25 && p->dbg_log[i].second - pv > wl) { wl = p->dbg_log[i].second - pv; worst = i; } pv = p->dbg_log[i].second; }
-            const size_t a0 = worst > 14 ? worst - 14 : 0;
-            const uint64_t t0 = p->dbg_log[a0].second;
-            for (size_t i = a0; i < worst + 6 && i < p->dbg_log.size(); ++i)
-                fprintf(stderr, "PLOG %s slot %d  t=%.0f us\n", (const char*[]){"?", "staged", "issue>", "issue<", "got", "wait>", "freed"}[p->dbg_log[i].first / 100],
-                        p->dbg_log[i].first % 100, (p->dbg_log[i].second - t0) / 1e3);
-        }
-    }
-    if (dae_exp_env("DAE_DBG_PIPE") && p->dbg_dev_n)
-        fprintf(stderr, "PIPE device time per launch (event pair on the lane's stream): %.3f ms over %llu launches\n",
-                p->dbg_dev_ms / (double)p->dbg_dev_n, (unsigned long long)p->dbg_dev_n);
-#endif
     for (Lane& L : p->lanes) {
         if (L.stream) (void)hipStreamSynchronize(L.stream);
         if (L.tctx) (void)dae_destroy(L.tctx);                  // (borrows lane 0's images: never frees them)
@@ -582,7 +489,6 @@ int dae_pipeline_destroy(dae_pipeline* p)
         if (S.ev_prep) (void)hipEventDestroy(S.ev_prep);
         void* outs[] = {S.d_idx, S.d_score, S.d_flags, S.d_rp, S.d_col, S.d_srp, S.d_scol, S.d_status, S.d_cval, S.t_h, S.t_feat, S.t_wt, S.t_wp};
         for (void* q : outs) if (q) (void)hipFree(q);
-        if (S.ev_fetch) (void)hipEventDestroy(S.ev_fetch);
         if (S.ev_h2d) (void)hipEventDestroy(S.ev_h2d);
         if (S.ev_gate) (void)hipEventDestroy(S.ev_gate);
         if (S.d_pos) (void)hipFree(S.d_pos);
@@ -676,8 +582,7 @@ static int pipeline_create(int device, const float* W_enc, const float* b_enc, c
         if (rc_t) return bail(rc_t, dae_last_error(p->prep_tctx));
     }
     for (Slot& S : p->slots) {
-        bool ok = hipEventCreateWithFlags(&S.ev_fetch, hipEventDisableTiming) == hipSuccess &&
-                  hipEventCreateWithFlags(&S.ev_scored, hipEventDisableTiming) == hipSuccess &&
+        bool ok = hipEventCreateWithFlags(&S.ev_scored, hipEventDisableTiming) == hipSuccess &&
                   hipMalloc(reinterpret_cast<void**>(&S.d_idx), (rows * kk * sizeof(int32_t) + 15) / 16 * 16) == hipSuccess &&
                   (!want_scores || hipMalloc(reinterpret_cast<void**>(&S.d_score), (rows * kk * sizeof(float) + 15) / 16 * 16) == hipSuccess) &&
                   hipMalloc(reinterpret_cast<void**>(&S.d_flags), 4 * sizeof(int32_t)) == hipSuccess &&
@@ -713,8 +618,7 @@ static int pipeline_create(int device, const float* W_enc, const float* b_enc, c
         if (!ok) return bail(DAE_ERR_NOMEM, "dae_pipeline_create: pinned allocation failed");
     }
     for (Lane& L : p->lanes) if (hipStreamSynchronize(L.stream) != hipSuccess) return bail(DAE_ERR_HIP, "setup failed");
-    if (const char* om = dae_exp_env("DAE_PIPE_OUT")) p->out_mode = atoi(om) == 0 ? 0 : 2;       // A/B (experiments build)
-    if (p->out_mode == 2) p->out_worker = std::thread(out_worker_main, p);
+    p->out_worker = std::thread(out_worker_main, p);
     p->worker = std::thread(worker_main, p);
     *out = p;
     return DAE_OK;
@@ -880,13 +784,9 @@ int dae_pipeline_poll(dae_pipeline* p, int wait, uint64_t* ticket, const int32_t
                 return DAE_OK;
             }
             __atomic_thread_fence(__ATOMIC_ACQUIRE);
-            const hipError_t q = S.sync_fetch ? hipEventSynchronize(S.ev_fetch) : hipSuccess;
-            if (q != hipSuccess) { lk.lock(); return pfatal(p, DAE_ERR_HIP, hipGetErrorString(q)); }
         } else {
             const auto t_w = std::chrono::steady_clock::now();
-            PLOG(p, 5, p->poll_slot);
             const hipError_t e = wait_launch(S);
-            PLOG(p, 4, p->poll_slot);
             p->wait_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_w).count();
             if (e != hipSuccess) { lk.lock(); return pfatal(p, DAE_ERR_HIP, hipGetErrorString(e)); }
         }
@@ -953,7 +853,6 @@ int dae_pipeline_poll(dae_pipeline* p, int wait, uint64_t* ticket, const int32_t
     ++ob.refs;                                               // the caller's reference to the block (dae_pipeline_release)
     if (++S.next_feed == S.feeds.size()) {                   // last feed of the launch: the slot is free again
         --ob.refs;                                           // (the launch's own reference)
-        PLOG(p, 6, p->poll_slot);
         S.state = 0; S.block = -1;
         p->poll_slot = (p->poll_slot + 1) % (int)p->slots.size();
     }

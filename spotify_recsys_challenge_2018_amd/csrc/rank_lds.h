@@ -101,21 +101,14 @@ __device__ __forceinline__ void dae_rank_find_bin(const unsigned* hist, unsigned
 // barriers here (stage stamps: 3.5 k of the ordering's 9.2 k cycles at 16 waves).
 template <int NTH>
 __device__ __forceinline__ void dae_rank_emit(dae_u64* keys, unsigned c, dae_u64* sorted, unsigned* hist, unsigned* above,
-                                              int tid, int row, const dae_rank_out& o, const unsigned* range = nullptr,
-                                              long long* dbg = nullptr)
+                                              int tid, int row, const dae_rank_out& o, const unsigned* range = nullptr)
 {
-#ifdef DAE_EXPERIMENTS         // stage stamps of workgroup 0 (the caller's debug switch hands the buffer in)
-#define RKSTAMP(i) if (dbg && blockIdx.x == 0 && tid == 0) dbg[i] = __builtin_readcyclecounter();
-#else
-#define RKSTAMP(i)
-#endif
     constexpr int PER = DAE_RANK_MAX / NTH, BPT = DAE_RANK_BINS / NTH, NW = NTH / 64;
     __shared__ dae_u64 rk_mm[2];
     __shared__ unsigned rk_wave_tot[NW];
     __shared__ unsigned rk_total;
     const int lane = tid & 63;
     __syncthreads();                                             // keys complete; the scratch regions' last readers are done
-    RKSTAMP(0)
     dae_u64 mine[PER];
     dae_u64 mn = ~0ull, mx = 0ull;
 #pragma unroll
@@ -137,7 +130,6 @@ __device__ __forceinline__ void dae_rank_emit(dae_u64* keys, unsigned c, dae_u64
         __syncthreads();
         rlo = rk_mm[0]; rhi = rk_mm[1];
     }
-    RKSTAMP(1)
     if (rhi == 0ull) { dae_rank_pad<NTH>(tid, row, 0u, o); return; }       // nothing present (block-uniform)
     // bins linear in the SCORE, not in its bit pattern (topk.hip step 5a has the measurement behind this); when the scores'
     // range is degenerate -- every key shares its float -- the bit pattern of the whole key (the column breaks the ties)
@@ -163,7 +155,6 @@ __device__ __forceinline__ void dae_rank_emit(dae_u64* keys, unsigned c, dae_u64
         mpos[e] = mine[e] != 0ull ? atomicAdd(&hist[bn], 1u) : 0u;
     }
     __syncthreads();
-    RKSTAMP(2)
     {   // above[b] = keys in bins > b
         const int top = DAE_RANK_BINS - 1 - BPT * tid;
         unsigned cb[BPT], own = 0;
@@ -184,14 +175,12 @@ __device__ __forceinline__ void dae_rank_emit(dae_u64* keys, unsigned c, dae_u64
         if (tid == NTH - 1) rk_total = run;
     }
     __syncthreads();
-    RKSTAMP(3)
     const unsigned present = rk_total;
     const unsigned k_eff = present < (unsigned)o.k ? present : (unsigned)o.k;
 #pragma unroll
     for (int e = 0; e < PER; ++e)
         if (mine[e] != 0ull) sorted[above[mbin[e]] + mpos[e]] = mine[e];
     __syncthreads();
-    RKSTAMP(4)
     unsigned rk[PER];
 #pragma unroll
     for (int e = 0; e < PER; ++e) {
@@ -203,13 +192,11 @@ __device__ __forceinline__ void dae_rank_emit(dae_u64* keys, unsigned c, dae_u64
         rk[e] = rank;
     }
     // the winners in rank order through LDS, then out in rank order: thread i writes position i (whole lines per wave)
-    RKSTAMP(5)
     dae_u64* fin = keys;                                         // (every thread took its keys into registers above)
 #pragma unroll
     for (int e = 0; e < PER; ++e)
         if (rk[e] < k_eff) fin[rk[e]] = mine[e];
     __syncthreads();
-    RKSTAMP(6)
     for (unsigned i = (unsigned)tid; i < k_eff; i += NTH) {
         const dae_u64 key = fin[i];
         const float z = dae_okey_inv((unsigned)(key >> 32));
@@ -218,8 +205,6 @@ __device__ __forceinline__ void dae_rank_emit(dae_u64* keys, unsigned c, dae_u64
         if (o.out_score) o.out_score[at] = o.out_kind == DAE_OUT_SCORE ? dae_sigmoidf(z) : z;
     }
     dae_rank_pad<NTH>(tid, row, k_eff, o);
-    RKSTAMP(7)
-#undef RKSTAMP
 }
 
 // The general case: the row's candidates sit in global memory, possibly more than DAE_RANK_MAX of them.  for_keys(f) calls

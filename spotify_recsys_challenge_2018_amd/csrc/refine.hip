@@ -49,7 +49,6 @@ struct RefineP {
     const int32_t* seed_col; int bitmap_base, bitmap_n;     // the row's seeds -> an LDS bitmap over the ranked columns
     const float* row_min;                         // nullable: an exchanged threshold (dae_score_topk_finish)
     int bm_off;                                   // byte offset of the seed bitmap in the dynamic LDS (behind the staging area)
-    long long* stamps;                            // experiments build: stage stamps of workgroup 0 (DAE_DBG_R)
     // SHARED RECOMPUTATION (round 5, launches of many rows): exact_rescore_shared_kernel ran before this launch and left the
     // fp32 logit in place of the bound u for every candidate of the rows that are recomputed WITHOUT narrowing (`staged` false
     // below: the same predicate there) -- such rows only read their pairs back and order them
@@ -57,11 +56,6 @@ struct RefineP {
     int B;
 };
 
-#ifdef DAE_EXPERIMENTS
-#define RSTAMP(i) if (p.stamps && blockIdx.x == 0 && threadIdx.x == 0) p.stamps[i] = __builtin_readcyclecounter();
-#else
-#define RSTAMP(i)
-#endif
 
 // HT > 0: hidden = 16 HT known at compile time.  A trip of the recomputation's block loop then has no branch around a load, and
 // hipcc counts the waits inside it: with the run-time bounds EVERY wait of the loop was vmcnt(0) -- a block waited for the ring's
@@ -85,7 +79,6 @@ __device__ __forceinline__ void refine_body(const RefineP& p)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int row = blockIdx.x;
     const int nseg = p.nseg;
-    RSTAMP(0)
     const bool bad = p.x.row_bad && p.x.row_bad[row] != 0;          // precondition of the bound violated: nothing survives
     for (int s = tid; s < nseg; s += RF_THREADS) seg_prefix[s + 1] = p.cnt[(size_t)s * p.cnt_seg_stride + row];
     if (tid == 0) { seg_prefix[0] = 0; s_n = 0; f_range[0] = 0xFFFFFFFFu; f_range[1] = 0u; }
@@ -119,7 +112,6 @@ __device__ __forceinline__ void refine_body(const RefineP& p)
         }
     }
     __syncthreads();
-    RSTAMP(1)                                                    // counts + hidden row in LDS, prefix done
     const int total = seg_prefix[nseg];
     if (total == 0) {
         if (tid == 0 && p.out_cnt) p.out_cnt[row] = 0;
@@ -189,7 +181,6 @@ __device__ __forceinline__ void refine_body(const RefineP& p)
         unsigned* hist = reinterpret_cast<unsigned*>(surv_off);
         for (int i = tid; i < RF_BINS; i += RF_THREADS) hist[i] = 0u;
         __syncthreads();
-        RSTAMP(2)                                                // bounds staged
         // P = a staged key with count(key >= P) >= need, as large as a 2048-bin histogram over [min, max] of the row's keys
         // resolves (bins linear in the KEY: any monotone map keeps the argument): one pass of LDS atomics, one scan from
         // the top for the bin B holding the need-th largest key, one pass for the smallest key of that bin.  Everything in
@@ -248,7 +239,6 @@ __device__ __forceinline__ void refine_body(const RefineP& p)
             taup = dae_okey_inv(P) - 2.0f * p.x.eps_max[0] * 1.000001f;
             taup = dae_okey_inv(dae_okey(taup) - 2u);          // two floats further down: the subtraction rounded
         }
-        RSTAMP(3)                                                // selection done
         // an upper bound of how many pass (whole bins down to tau''s): decides where the results go
         ktau = dae_okey(taup);
         const int Bt = ktau > kmin ? bin_of(ktau < kmax ? ktau : kmax) : 0;
@@ -259,7 +249,6 @@ __device__ __forceinline__ void refine_body(const RefineP& p)
         }
         __syncthreads();
         n_kept = (int)cnts[4];
-        RSTAMP(4)
     }
     // COMPACT: the survivors' (fp32 logit, column) pairs go to this row's own list p.out[row][0 .. n_kept) and the
     // filter launch's per-workgroup lists of the row are emptied (their counts zeroed): the selection kernel then reads one
@@ -313,7 +302,7 @@ __device__ __forceinline__ void refine_body(const RefineP& p)
         float acc = 0.0f;
         // hidden activations: the same for every lane.  Lane l holds h[64 c + l] of the current 64-k chunk c in ONE register and
         // every product takes its factor by v_readlane (an SGPR operand of the v_fma) -- as four broadcast ds_read_b128 per
-        // 16 k they were a third of the LDS instructions of this loop, which is LDS-bound (stage stamps, DAE_DBG_R)
+        // 16 k they were a third of the LDS instructions of this loop, which is LDS-bound (stage stamps)
         constexpr int RF_U = RF_DEPTH < 4 ? 4 : RF_DEPTH;         // blocks per trip: whole 64-k chunks, so a block's lanes are constants
         auto trip = [&](const int j0) {
             float hq[RF_U / 4];
@@ -427,8 +416,7 @@ __device__ __forceinline__ void refine_body(const RefineP& p)
         unsigned* fhist = reinterpret_cast<unsigned*>(surv_off);
         if (fast) {
             for (int b = tid; b < RF_BINS; b += RF_THREADS) fhist[b] = 0u;
-            dae_rank_emit<RF_THREADS>(fkey, (unsigned)n_list, sorted, fhist, above, tid, row, p.fo, f_range,
-                                      p.stamps ? p.stamps + 16 : nullptr);
+            dae_rank_emit<RF_THREADS>(fkey, (unsigned)n_list, sorted, fhist, above, tid, row, p.fo, f_range);
             return;
         }
         // more survivors than the ordering stage takes (logits packed within 2 eps of the cut), or a list refined in place:
@@ -461,10 +449,8 @@ __device__ __forceinline__ void refine_body(const RefineP& p)
             const bool in = e < total;
             const int off = offset_of(in ? e : g0);
             const uint2 pr = p.base[off];
-            if (g0 == 0) { RSTAMP(5) }
             // (p.pre: recomputed and guarded by exact_rescore_shared_kernel, a decoder row fetched once for 32 playlists)
             const float z = p.pre ? __uint_as_float(pr.x) : rescore_group((int)pr.y, in);
-            if (g0 == 0) { RSTAMP(9) }
             if (!p.pre) guard(z, __uint_as_float(pr.x), (int)pr.y, in);
             if (fast) fkey_put(e, z, (int)pr.y, in);
             else if (in) {
@@ -472,10 +458,8 @@ __device__ __forceinline__ void refine_body(const RefineP& p)
                 else p.base[off].x = __float_as_uint(z);
             }
         }
-        RSTAMP(6)
         if (compact) finish_compact(total);
         if (p.fuse) final_select(total);
-        RSTAMP(8)
         return;
     }
 
@@ -505,7 +489,6 @@ __device__ __forceinline__ void refine_body(const RefineP& p)
         __syncthreads();
         const int n = s_n;
         const bool last = c0 + RND >= total;
-        if (last) { RSTAMP(5) }                                   // listed
         if (n + RND > RF_SURV || last) {                          // the list could overflow next round, or this was the last
             // (the recomputation's buffers take the head of the staging area: rounds not yet visited are re-staged after it)
             const int gstep = RF_WAVES * 64;
@@ -541,12 +524,9 @@ __device__ __forceinline__ void refine_body(const RefineP& p)
             __syncthreads();
         }
     }
-    RSTAMP(6)                                                    // recomputed
     if (tid == 0 && p.stat) p.stat[2 * row + 1] = n_out;
     if (compact) finish_compact(n_out);
-    RSTAMP(7)
     if (p.fuse) final_select(compact ? n_out : total);
-    RSTAMP(8)
 }
 
 // ---- shared recomputation: one decoder row for 32 playlists ------------------------------------------------------------------
@@ -583,13 +563,7 @@ struct SharedP {
     dae_exact_src x;
     const int32_t* seed_row_ptr; int k, B, stage_cap;
     int segb, nblk;                    // segments per workgroup, workgroups per group of 32 playlists
-    long long* stamps;                 // experiments build: stage stamps of workgroup 0 (DAE_DBG_S)
 };
-#ifdef DAE_EXPERIMENTS
-#define SSTAMP(i) if (p.stamps && blockIdx.x == 0 && threadIdx.x == 0) p.stamps[i] = __builtin_readcyclecounter();
-#else
-#define SSTAMP(i)
-#endif
 
 // grid = nblk x groups of 32 playlists, ~one workgroup per CU: the launch is a chain of memory round trips (counts -> pairs ->
 // decoder rows), so a workgroup takes as many segments as give its four waves a tile each.  (Half the tables and two workgroups
@@ -616,7 +590,6 @@ __global__ __launch_bounds__(256, 1) void exact_rescore_shared_kernel(const Shar
     const int H = GT > 0 ? 8 * GT : p.x.H, G8 = GT > 0 ? GT : (H >> 3);
 
     // ---- which rows take part, and how many candidates the workgroup's segments hold for them --------------------------------
-    SSTAMP(0)
     if (tid < RS_ROWS) r_tot[tid] = 0;
     if (tid == 0) s_maxc = 0;
     {
@@ -681,7 +654,6 @@ __global__ __launch_bounds__(256, 1) void exact_rescore_shared_kernel(const Shar
     }
     __syncthreads();
     const int maxc = s_maxc;
-    SSTAMP(1)
     if (maxc == 0) return;
     for (int r0 = 0; r0 < maxc; r0 += RS_PR) {
         // ---- the round's pairs -> the union of their columns ------------------------------------------------------------------
@@ -736,7 +708,6 @@ __global__ __launch_bounds__(256, 1) void exact_rescore_shared_kernel(const Shar
             }
         }
         __syncthreads();
-        if (r0 == 0) { SSTAMP(2) }
         // dense ranks: thread t owns RS_HASH / 256 consecutive slots
         constexpr int SPT = RS_HASH / 256;
         unsigned kv_[SPT];
@@ -767,7 +738,6 @@ __global__ __launch_bounds__(256, 1) void exact_rescore_shared_kernel(const Shar
             }
         }
         __syncthreads();
-        if (r0 == 0) { SSTAMP(3) if (p.stamps && blockIdx.x == 0 && tid == 0) p.stamps[8] = U; }
 
         for (int u0 = 0; u0 < U; u0 += RS_UPASS) {
             // ---- one tile of 32 union columns per wave: the canonical chains of 32 x 32 (column, playlist) pairs -------------
@@ -812,9 +782,7 @@ __global__ __launch_bounds__(256, 1) void exact_rescore_shared_kernel(const Shar
                 for (int r = 0; r < 16; ++r)
                     zt[(32 * wave + (r & 3) + 8 * (r >> 2) + 4 * hi) * RS_ZLD + j] = acc[r];
             }
-            if (r0 == 0 && u0 == 0) { SSTAMP(4) }
             __syncthreads();
-            if (r0 == 0 && u0 == 0) { SSTAMP(5) }
             // ---- every pair of the round whose column sits in this pass takes its logit ---------------------------------------
 #pragma unroll
             for (int n = 0; n < NPT; ++n) {
@@ -845,9 +813,7 @@ __global__ __launch_bounds__(256, 1) void exact_rescore_shared_kernel(const Shar
             for (int i = 0; i < RS_HASH / 4 / 256; ++i) hk4[tid + 256 * i] = make_uint4(0u, 0u, 0u, 0u);
             __syncthreads();
         }
-        if (r0 == 0) { SSTAMP(6) }
     }
-    SSTAMP(7)
 }
 
 template <int HT>
@@ -902,44 +868,19 @@ int dae_launch_exact_refine(dae_ctx* ctx, const dae_pair_group& g1, const dae_ex
     p.out = (out && out_cnt && out_cap > 0) ? out : nullptr; p.out_cnt = p.out ? out_cnt : nullptr; p.out_cap = p.out ? out_cap : 0;
     if ((int64_t)g1.nseg * g1.seg_stride >= ((int64_t)1 << 31))
         return dae_fail(ctx, DAE_ERR_ARG, "exact refine: candidate lists too large for 32-bit offsets");
-    p.stamps = nullptr;
-#ifdef DAE_EXPERIMENTS
-    static const bool dbgR = dae_exp_env("DAE_DBG_R") != nullptr;
-    static long long* rbuf = nullptr;
-    static int rcalls = 0;
-    if (dbgR) {
-        if (!rbuf) { (void)hipMalloc(&rbuf, 32 * 8); (void)hipMemset(rbuf, 0, 32 * 8); }
-        p.stamps = rbuf;
-        if ((++rcalls % 100) == 0) {
-            long long h[32];
-            (void)hipStreamSynchronize(ctx->stream);
-            (void)hipMemcpy(h, rbuf, sizeof(h), hipMemcpyDeviceToHost);
-            fprintf(stderr, "REFINE wg0:");
-            for (int i = 1; i < 10; ++i) if (h[i]) fprintf(stderr, " [%d]%lld", i, h[i] - h[0]);
-            for (int i = 16; i < 24; ++i) if (h[i]) fprintf(stderr, " rk%d:%lld", i - 16, h[i] - h[0]);
-            fprintf(stderr, "\n");
-        }
-    }
-#endif
     // Many rows per CU (>= 3 at 768 rows): the 256-thread shape with HALF the staging area -- 57 KB of LDS and ~100 registers,
     // so two or three rows share a CU and one's memory round trips (counts, pairs, decoder rows) hide under another's
     // arithmetic; a row is latency-bound on its own (batch 1024: 60 -> see profiles/r04_notes.md).  Rows with more candidates
     // than the smaller area holds are recomputed without narrowing (slower, same bits).
     const bool many = B >= 768;
-    bool slim = ctx->overlap_hint || many;
-    int shape = slim ? 0 : 1;                                                                  // 0 slim (256), 1 (512), 2 wide (1024)
+    int shape = ctx->overlap_hint || many ? 0 : 1;                                           // 0 slim (256), 1 (512), 2 wide (1024)
     // fused selection, one row per CU: the wide shape, whatever the overlap hint says -- measured (profiles/r05_notes.md), four
     // batches in flight: slim + fused 46.1 us per step, 512 threads + fused 41.9, slim + a selection launch 42.2
     if (p.fuse && !many) shape = 2;
-    static const char* shape_env = dae_exp_env("DAE_RF_SHAPE");                               // A/B (experiments build)
-    if (shape_env) shape = atoi(shape_env);
-    slim = shape == 0;
     p.stage_cap = many ? RF_STAGE / 2 : RF_STAGE;
     // launches of many rows: the rows that are recomputed without narrowing get their logits from the shared recomputation
     // (exact_rescore_shared_kernel: a decoder row fetched once per 32 playlists, the chains on the matrix pipe) first
-    bool shared = many && (x.H & 7) == 0 && x.H <= RS_MAXH;
-    static const char* shared_env = dae_exp_env("DAE_RF_SHARED");                             // A/B (experiments build)
-    if (shared_env) shared = atoi(shared_env) != 0 && (x.H & 7) == 0 && x.H <= RS_MAXH;
+    const bool shared = many && (x.H & 7) == 0 && x.H <= RS_MAXH;
     p.pre = shared ? 1 : 0; p.B = B;
     if (shared) {
         SharedP sp;
@@ -954,24 +895,6 @@ int dae_launch_exact_refine(dae_ctx* ctx, const dae_pair_group& g1, const dae_ex
         if (segb > RS_MAXSEG) segb = RS_MAXSEG;
         nblk = (p.nseg + segb - 1) / segb;
         sp.segb = segb; sp.nblk = nblk;
-        sp.stamps = nullptr;
-#ifdef DAE_EXPERIMENTS
-        static const bool dbgS = dae_exp_env("DAE_DBG_S") != nullptr;
-        static long long* sbuf = nullptr;
-        static int scalls = 0;
-        if (dbgS) {
-            if (!sbuf) { (void)hipMalloc(&sbuf, 16 * 8); (void)hipMemset(sbuf, 0, 16 * 8); }
-            sp.stamps = sbuf;
-            if ((++scalls % 100) == 0) {
-                long long h[16];
-                (void)hipStreamSynchronize(ctx->stream);
-                (void)hipMemcpy(h, sbuf, sizeof(h), hipMemcpyDeviceToHost);
-                fprintf(stderr, "SHARED wg0 (grid %d x %d, segb %d):", ngrp, nblk, segb);
-                for (int i = 1; i < 8; ++i) fprintf(stderr, " [%d]%lld", i, h[i] - h[0]);
-                fprintf(stderr, " U=%lld\n", h[8]);
-            }
-        }
-#endif
         if (x.H == 256) hipLaunchKernelGGL(exact_rescore_shared_kernel<32>, dim3((unsigned)(ngrp * nblk)), dim3(256), 0, ctx->stream, sp);
         else hipLaunchKernelGGL(exact_rescore_shared_kernel<0>, dim3((unsigned)(ngrp * nblk)), dim3(256), 0, ctx->stream, sp);
         DAE_CHECK_LAUNCH(ctx, "exact_rescore_shared_kernel");
@@ -985,7 +908,6 @@ int dae_launch_exact_refine(dae_ctx* ctx, const dae_pair_group& g1, const dae_ex
         return d < tb ? tb : d;
     };
     if (p.fuse && shape == 2 && dyn_of(2) + fuse_bitmap_bytes(p.bitmap_n) > RF_DYN_MAX) shape = 1;
-    slim = shape == 0;
     size_t dyn = dyn_of(shape);
     p.bm_off = (int)dyn;
     if (p.fuse) dyn += fuse_bitmap_bytes(p.bitmap_n);
@@ -1000,8 +922,7 @@ int dae_launch_exact_refine(dae_ctx* ctx, const dae_pair_group& g1, const dae_ex
                             reinterpret_cast<const void*>(&exact_refine_wide_kernel<0>), reinterpret_cast<const void*>(&exact_refine_wide_kernel<16>)};
         for (const void* kf : ks) DAE_HIP_CHECK(ctx, hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
     }
-    static const bool no_ht = dae_exp_env("DAE_RF_NO_HT") != nullptr;                         // A/B (experiments build)
-    const bool h256 = x.H == 256 && !no_ht;                                                    // the compile-time block loop
+    const bool h256 = x.H == 256;                                                              // the compile-time block loop
     if (shape == 0) {
         // (the slim shape keeps the run-time loop: 91 registers against 137 -- it exists to fit next to another batch's filter waves)
         hipLaunchKernelGGL(exact_refine_slim_kernel<0>, dim3(B), dim3(256), dyn, ctx->stream, p);

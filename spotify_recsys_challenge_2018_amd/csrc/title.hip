@@ -673,10 +673,8 @@ int dae_launch_title_features(dae_ctx* ctx, const int32_t* titles, int B, int L,
     const int p_max = L - fs_min + 1;                 // most window positions of any size
     // inference on a context that holds the table of exactly these variables (dae_title_prepack_features): fs additions per
     // (position, filter) instead of fs x E multiply-adds
-    static const bool no_table = dae_exp_env("DAE_TITLE_NO_TABLE") != nullptr;                // A/B (experiments build)
     if (ctx->title_tab.p && ctx->ttab_emb == emb && ctx->ttab_w == conv_w && ctx->ttab_nchar == n_char && ctx->ttab_E == E &&
-        ctx->ttab_F == F && ctx->ttab_nsizes == n_sizes && kp == 1.0f && !argmax && !feat_raw && p_max >= 1 && p_max <= TT_PMAX &&
-        !no_table) {
+        ctx->ttab_F == F && ctx->ttab_nsizes == n_sizes && kp == 1.0f && !argmax && !feat_raw && p_max >= 1 && p_max <= TT_PMAX) {
         bool same = true;
         for (int i = 0; i < n_sizes; ++i) same = same && ctx->ttab_fs[i] == p.fs[i];
         if (same) {
@@ -686,11 +684,9 @@ int dae_launch_title_features(dae_ctx* ctx, const int32_t* titles, int B, int L,
             return DAE_OK;
         }
     }
-    static const bool generic = dae_exp_env("DAE_TITLE_GENERIC") != nullptr;          // A/B against the first kernel
     bool even_k = true;
     for (int i = 0; i < n_sizes; ++i) even_k = even_k && ((p.fs[i] * E) % 2 == 0);
-    static const bool no_mfma = dae_exp_env("DAE_TITLE_WAVE") != nullptr;              // A/B against the fmaf-chain kernel
-    if (p_max >= 1 && p_max <= 32 && fs_max <= L && even_k && !generic && !no_mfma) {
+    if (p_max >= 1 && p_max <= 32 && fs_max <= L && even_k) {
         // positions 0 .. 31 are computed for every size: rows up to 31 + fs_max - 1 of the LDS image are read
         const int lpad = 32 + fs_max;
         const size_t lds = (size_t)lpad * E * sizeof(float);
@@ -698,7 +694,7 @@ int dae_launch_title_features(dae_ctx* ctx, const int32_t* titles, int B, int L,
         DAE_CHECK_LAUNCH(ctx, "title_features_mfma_kernel");
         return DAE_OK;
     }
-    if (p_max >= 1 && p_max <= 32 && fs_max <= L && !generic) {
+    if (p_max >= 1 && p_max <= 32 && fs_max <= L) {
         // positions up to PMAX - 1 + fs_max - 1 are read: pad the LDS image with zero rows
         const int pm = p_max <= 24 ? 24 : 32;
         const int lpad = pm + fs_max;

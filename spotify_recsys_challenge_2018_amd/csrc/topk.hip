@@ -226,7 +226,7 @@ __device__ __forceinline__ void find_bin(const unsigned* hist, unsigned* wave_to
 // quarter, and up to 8 such workgroups share a CU.  Same stages, same results.
 template <typename Src, int NTH>
 __global__ __launch_bounds__(NTH) void topk_kernel(const Src src, const dae_topk_args a,
-                                                   const int key_cap, const int dbg_stop)
+                                                   const int key_cap)
 {
     constexpr int TK_THREADS = NTH, TK_WAVES = NTH / 64;       // shadow the file-level constants
     constexpr int MAXES = 1024 / NTH;                            // per-thread maxima kept for the 3a cut (1024 in all)
@@ -272,7 +272,6 @@ __global__ __launch_bounds__(NTH) void topk_kernel(const Src src, const dae_topk
     }
     src.template prepare<NTH>(row, tid, seg_prefix);
     __syncthreads();
-    if (DAE_EXP_ON(dbg_stop == 1)) return;
 
     int sort_n = 1;
     while (sort_n < k) sort_n <<= 1;
@@ -381,7 +380,6 @@ __global__ __launch_bounds__(NTH) void topk_kernel(const Src src, const dae_topk
         if (lane == 0) { atomicMin(&s_min, mn); atomicMax(&s_max, mx); }
     }
     __syncthreads();
-    if (DAE_EXP_ON(dbg_stop == 2)) return;
     const unsigned m = s_cnt;                                   // valid elements
     const unsigned n_cached = s_slots ? s_slots : m;            // cache slots in use (fixed slots: the source size)
     const bool in_lds = key_cap > 0 && n_cached <= (unsigned)key_cap;   // all of them were kept in LDS
@@ -504,7 +502,6 @@ __global__ __launch_bounds__(NTH) void topk_kernel(const Src src, const dae_topk
         }
     }
 
-    if (DAE_EXP_ON(dbg_stop == 3)) return;
     // ---- 4. collect keys >= lo, sort descending, emit -------------------------------------------------
     for (int i = tid; i < sort_n; i += TK_THREADS) skey[i] = 0ull;
     if (tid == 0) s_cnt = 0;
@@ -572,14 +569,12 @@ __global__ __launch_bounds__(NTH) void topk_kernel(const Src src, const dae_topk
         k_eff = s_cnt < (unsigned)k ? s_cnt : (unsigned)k;
     }
 
-    if (DAE_EXP_ON(dbg_stop == 4)) return;
     // ---- 5a. k <= 512 (at most 1024 keys were collected): order by HISTOGRAM RANK.  The output position of a key is
     // the number of keys above it = (keys in higher bins) + (keys of its own bin above it): a 2048-bin histogram over
     // the live key range, a suffix scan over the bins, the keys dropped bin by bin into a second buffer, and a count
     // over the (few) keys that share the bin.  ~6 barriers and one LDS atomic per key; it takes whatever was
     // collected, so no separate "refine to <= 512 keys" stage exists (that stage + a 512-key network cost 3.9 + 13.9 us
     // of the final launch, rank-by-counting over 512 keys 3.9 + 5.7 us; profiles/r02_notes.md).
-    if (DAE_EXP_ON(dbg_stop == 5)) return;
     if (sort_n == 1024) {
         constexpr int PER = 1024 / NTH;                          // collected keys per thread (slot e * NTH + tid)
         constexpr int BPT = TK_BINS / NTH;
@@ -617,7 +612,6 @@ __global__ __launch_bounds__(NTH) void topk_kernel(const Src src, const dae_topk
             mpos[e] = mine[e] != 0ull ? atomicAdd(&hist[bn], 1u) : 0u;
         }
         __syncthreads();
-        if (DAE_EXP_ON(dbg_stop == 8)) { if (mpos[0] == 12345u) a.out_idx[0] = 1; return; }
         // above[b] = keys in bins > b.  Thread t owns the BPT bins from 2047 - BPT t downwards.
         unsigned* above = reinterpret_cast<unsigned*>(skey);     // 2048 x 4 B = the sort buffer's 1024 x 8 B
         u64* sorted = keys;                                      // key cache region: >= 1024 keys (launch_topk)
@@ -644,7 +638,6 @@ __global__ __launch_bounds__(NTH) void topk_kernel(const Src src, const dae_topk
         for (int e = 0; e < PER; ++e)
             if (mine[e] != 0ull) sorted[above[mbin[e]] + mpos[e]] = mine[e];
         __syncthreads();
-        if (DAE_EXP_ON(dbg_stop == 6)) return;
         unsigned rk[PER];
 #pragma unroll
         for (int e = 0; e < PER; ++e) {
@@ -658,7 +651,6 @@ __global__ __launch_bounds__(NTH) void topk_kernel(const Src src, const dae_topk
         // the winners in rank order through LDS (the `above` table is dead now), then out in rank order: thread i writes
         // position i, a wave 256 contiguous bytes.  Storing from the rank loop put every 4-byte value into a line of its
         // own -- ~1000 partial-line writes per row, the larger half of this launch at 1024 rows.
-        if (DAE_EXP_ON(dbg_stop == 7)) { if (rk[0] == 12345u) a.out_idx[0] = 1; return; }
         __syncthreads();
         u64* fin = skey;
 #pragma unroll
@@ -768,7 +760,6 @@ struct TauP {
     const int* samp_list; int col_lo;                            // column of sample element q = col_lo + list[q >> 5] * 32 + (q & 31)
     const int32_t* seed_row_ptr; int k;
     float* tau; uint2* out_pairs; int64_t pairs_stride; int* out_cnt;
-    long long* dbg;
 };
 // HAS_S = false: no dense sample to scan (n_s == 0: the bf16 / exact filter launch decodes every tile itself) -- tau only,
 // a third of the registers, so that the workgroup fits on a CU NEXT to a filter workgroup of another batch.
@@ -779,12 +770,6 @@ __global__ __launch_bounds__(256) void tau_select_kernel(const TauP p)
     __shared__ unsigned wsum[4];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int row = blockIdx.x;
-#ifdef DAE_EXPERIMENTS         // stage stamps of rows 0 and 100 (DAE_DBG_TAU=1 prints them every 50 launches)
-#define TSTAMP(i) if (p.dbg && tid == 0 && (row == 0 || row == 100)) p.dbg[(row ? 8 : 0) + (i)] = __builtin_readcyclecounter();
-#else
-#define TSTAMP(i)
-#endif
-    TSTAMP(0)
     const float* g = p.gmax + (size_t)row * p.ld_g;
     const int n = p.n_g;
     const unsigned ns = p.seed_row_ptr ? (unsigned)(p.seed_row_ptr[row + 1] - p.seed_row_ptr[row]) : 0u;
@@ -864,8 +849,6 @@ __global__ __launch_bounds__(256) void tau_select_kernel(const TauP p)
     unsigned lo = p_min - 1u, hi = 0xFFFFu;                      // the answer lies in [lo, hi]
     int it = 0;
     unsigned c[3];
-    TSTAMP(1)
-    TSTAMP(2)
     while (lo < hi) {                                            // invariant: count(lo) >= need, count(hi + 1) < need
         const unsigned span = hi - lo;                           // >= 1; three probes cut [lo + 1, hi] into four parts
         const unsigned m1 = lo + (span + 3u) / 4u, m2 = lo + (2u * span + 3u) / 4u, m3 = lo + (3u * span + 3u) / 4u;
@@ -876,7 +859,6 @@ __global__ __launch_bounds__(256) void tau_select_kernel(const TauP p)
         else hi = m1 - 1u;
     }
     const bool found = lo >= p_min;
-    TSTAMP(3)
     // No dense sample (n_s == 0: the bf16 filter launch decodes the sample tiles AGAIN and every candidate comes from it):
     // the element tau was taken from has to pass a compare in ANOTHER kernel.  Both kernels run the same MFMA sequence on
     // the same operands, so the values agree bit for bit (tests/test_gpu_bf16.py); 4 ulp of slack make the row's k
@@ -907,7 +889,6 @@ __global__ __launch_bounds__(256) void tau_select_kernel(const TauP p)
         const float4 z = srow[f];
         mine += (passes(z.x) ? 1u : 0u) + (passes(z.y) ? 1u : 0u) + (passes(z.z) ? 1u : 0u) + (passes(z.w) ? 1u : 0u);
     }
-    TSTAMP(4)
     unsigned incl = mine;                                        // block-wide exclusive scan of the counts
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
@@ -920,7 +901,6 @@ __global__ __launch_bounds__(256) void tau_select_kernel(const TauP p)
     unsigned at = incl - mine;
     for (int w = 0; w < wv; ++w) at += wsum[w];
     if (tid == 255) p.out_cnt[row] = (int)(at + mine);
-    TSTAMP(5)
     uint2* dst = p.out_pairs + (size_t)row * p.pairs_stride;
     auto emit4 = [&](const float4 z, int f, int tile) {
         const unsigned cb = (unsigned)(p.col_lo + tile * 32 + ((4 * f) & 31));
@@ -933,10 +913,6 @@ __global__ __launch_bounds__(256) void tau_select_kernel(const TauP p)
     for (int u = 0; u < NPRE; ++u)
         if (((live >> u) & 1u) && u * 256 + tid < n4) emit4(zpre[u], u * 256 + tid, ltile[(u * 256 + tid) >> 3]);
     for (int f = TAU_PRE * 256 + tid; f < n4; f += 256) emit4(srow[f], f, p.samp_list[f >> 3]);
-    TSTAMP(6)
-#ifdef DAE_EXPERIMENTS
-    if (p.dbg && tid == 0 && row == 0) p.dbg[7] = it;
-#endif
 }
 
 // The same for launches of MANY SHORT rows (vocabulary shards, where every rank scores the whole global batch over its
@@ -1043,45 +1019,25 @@ __global__ __launch_bounds__(256) void tau_select_wave_kernel(const TauP p, cons
 int launch_tau_select(dae_ctx* ctx, const TauP& p, int B)
 {
     if (B <= 0) return DAE_OK;
-    TauP q = p;
-#ifdef DAE_EXPERIMENTS
-    static const bool dbg = dae_exp_env("DAE_DBG_TAU") != nullptr;
-    static long long* dbuf = nullptr;
-    static int calls = 0;
-    if (dbg) { if (!dbuf) (void)hipMalloc(&dbuf, 16 * 8); q.dbg = dbuf; }
-#endif
     // many short rows (>= 4 per CU, <= 2048 maxima and sample logits each: the 8-rank shard of the global batch): a wave
     // per row, everything in registers, no barriers -- 30.1 -> 22.3 us for 2048 rows.  Longer rows lose (4096 maxima per
     // wave = 64 key registers and 128 mask SGPRs per probe: 37 vs 18.6 us at 4 ranks) and keep the workgroup kernel.
-    static const bool no_wave = dae_exp_env("DAE_TAU_NO_WAVE") != nullptr;            // A/B against the workgroup-per-row kernel
-    if (B >= 1024 && p.n_g <= 64 * 32 && (p.n_s >> 2) <= 64 * 8 && !no_wave) {
-        hipLaunchKernelGGL((tau_select_wave_kernel<32, 8>), dim3((B + 3) / 4), dim3(256), 0, ctx->stream, q, B);
+    if (B >= 1024 && p.n_g <= 64 * 32 && (p.n_s >> 2) <= 64 * 8) {
+        hipLaunchKernelGGL((tau_select_wave_kernel<32, 8>), dim3((B + 3) / 4), dim3(256), 0, ctx->stream, p, B);
         DAE_CHECK_LAUNCH(ctx, "tau_select_wave_kernel");
         return DAE_OK;
     }
     if (p.n_g <= 256 * 16 && p.n_s == 0)
-        hipLaunchKernelGGL((tau_select_kernel<16, false>), dim3(B), dim3(256), 0, ctx->stream, q);
+        hipLaunchKernelGGL((tau_select_kernel<16, false>), dim3(B), dim3(256), 0, ctx->stream, p);
     else if (p.n_g <= 256 * 32 && p.n_s == 0)
-        hipLaunchKernelGGL((tau_select_kernel<32, false>), dim3(B), dim3(256), 0, ctx->stream, q);
+        hipLaunchKernelGGL((tau_select_kernel<32, false>), dim3(B), dim3(256), 0, ctx->stream, p);
     else if (p.n_g <= 256 * 16)
-        hipLaunchKernelGGL(tau_select_kernel<16>, dim3(B), dim3(256), 0, ctx->stream, q);
+        hipLaunchKernelGGL(tau_select_kernel<16>, dim3(B), dim3(256), 0, ctx->stream, p);
     else if (p.n_g <= 256 * 32)        // batch 1024 on one GPU: 5 120 maxima per row -- half the compares of the 64-key shape
-        hipLaunchKernelGGL(tau_select_kernel<32>, dim3(B), dim3(256), 0, ctx->stream, q);
+        hipLaunchKernelGGL(tau_select_kernel<32>, dim3(B), dim3(256), 0, ctx->stream, p);
     else
-        hipLaunchKernelGGL(tau_select_kernel<64>, dim3(B), dim3(256), 0, ctx->stream, q);
+        hipLaunchKernelGGL(tau_select_kernel<64>, dim3(B), dim3(256), 0, ctx->stream, p);
     DAE_CHECK_LAUNCH(ctx, "tau_select_kernel");
-#ifdef DAE_EXPERIMENTS
-    if (dbg && (++calls % 50) == 0) {
-        long long h[16];
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipMemcpy(h, dbuf, sizeof(h), hipMemcpyDeviceToHost);
-        fprintf(stderr, "TAU row0:");
-        for (int i = 1; i < 7; ++i) fprintf(stderr, " %lld", h[i] - h[0]);
-        fprintf(stderr, " steps %lld | row100:", h[7]);
-        for (int i = 1; i < 7; ++i) fprintf(stderr, " %lld", h[8 + i] - h[8]);
-        fprintf(stderr, "\n");
-    }
-#endif
     return DAE_OK;
 }
 
@@ -1097,15 +1053,13 @@ int launch_topk(dae_ctx* ctx, const Src& src, const dae_topk_args& a)
     aa.sort_cap = sort_n;
     // Two LDS modes, both covered by the parity tests:
     //   bitmap (default): per-row seed bitmap + a key cache filling the CU's LDS -- fastest alone.
-    //   lean (DAE_TOPK_LEAN=1): no bitmap (seed-blind narrowing at rank k + n_seeds, seeds removed once
+    //   lean: no bitmap (seed-blind narrowing at rank k + n_seeds, seeds removed once
     //     from the collected keys), sort buffer + small cache only: <= 30 KiB and <= 56 registers per
     //     thread, so a workgroup fits on a CU NEXT to a decode workgroup of another batch.  Measured
     //     (profiles/r01_notes.md): the co-resident decode launch slows down by about what the overlap
     //     gains, and the kernel alone is slower (re-reads its source), so it is not the default.
-    static const bool want_lean = dae_exp_env("DAE_TOPK_LEAN") != nullptr;
-    aa.lean = want_lean ? 1 : 0;
     // a ranked range too wide for the LDS bitmap (> ~1 M columns) takes the bitmap-free mode instead of failing
-    if ((((size_t)((a.bitmap_n + 31) / 32) * 4) + 15) + (size_t)sort_n * 8 + 22 * 1024 > (size_t)160 * 1024) aa.lean = 1;
+    aa.lean = (((size_t)((a.bitmap_n + 31) / 32) * 4) + 15) + (size_t)sort_n * 8 + 22 * 1024 > (size_t)160 * 1024 ? 1 : 0;
     const size_t lds_total = 160 * 1024, lds_static = 14 * 1024;    // hist 8K + seg_prefix 4K + scalars
     size_t dyn;
     int key_cap;
@@ -1138,24 +1092,19 @@ int launch_topk(dae_ctx* ctx, const Src& src, const dae_topk_args& a)
                                                (int)(lds_total - lds_static)));
 
     }
-    // debug: DAE_TOPK_STOP=n stops the phase-A (tau-producing) kernel after stage n,
-    // DAE_TOPK_STOP=-n the other launches (bisecting stage costs under rocprofv3)
-    static const int dbg_env = dae_exp_env("DAE_TOPK_STOP") ? atoi(dae_exp_env("DAE_TOPK_STOP")) : 0;
-    const int dbg_stop = dbg_env > 0 ? (a.out_tau ? dbg_env : 0) : (a.out_tau ? 0 : -dbg_env);
     // threads per row: 256 for rows known to be short (see topk_kernel): dense rows of <= 4096 columns (the
     // sample of a small vocabulary shard) and gathered shard lists.  Candidate lists (PairSrc) keep 1024: their
     // cost is walking the per-workgroup segments (one wave per segment), which 4 waves do slower than 16
-    // (measured: 407 vs 354 us per step at --sim-world 8).  DAE_TOPK_THREADS=1024|256 forces one shape (A/B).
-    static const int nth_env = dae_exp_env("DAE_TOPK_THREADS") ? atoi(dae_exp_env("DAE_TOPK_THREADS")) : 0;
+    // (measured: 407 vs 354 us per step at --sim-world 8).
     const int bound = Src::kSegs ? 0 : src.max_keys();
     // ... and candidate lists when the launch has many rows (>= 4 per CU: large batches, vocabulary shards): a row then
     // holds few candidates, four 256-thread workgroups share a CU, and the per-row fixed cost is what counts
     // (--sim-world 8, 2048 rows: step 322 -> 284 us; at 256 rows 256 threads lose: 22 vs 14 us)
-    const bool small = nth_env ? nth_env == 256 : ((!Src::kSegs && bound <= 4096) || (Src::kSegs && (a.B >= 1024 || a.prefer_small)));
+    const bool small = (!Src::kSegs && bound <= 4096) || (Src::kSegs && (a.B >= 1024 || a.prefer_small));
     if (small)
-        hipLaunchKernelGGL((topk_kernel<Src, 256>), dim3(a.B), dim3(256), dyn, ctx->stream, src, aa, key_cap, dbg_stop);
+        hipLaunchKernelGGL((topk_kernel<Src, 256>), dim3(a.B), dim3(256), dyn, ctx->stream, src, aa, key_cap);
     else
-        hipLaunchKernelGGL((topk_kernel<Src, 1024>), dim3(a.B), dim3(1024), dyn, ctx->stream, src, aa, key_cap, dbg_stop);
+        hipLaunchKernelGGL((topk_kernel<Src, 1024>), dim3(a.B), dim3(1024), dyn, ctx->stream, src, aa, key_cap);
     DAE_CHECK_LAUNCH(ctx, "topk_kernel");
     return DAE_OK;
 }
@@ -1168,7 +1117,7 @@ int dae_launch_tau_select(dae_ctx* ctx, const float* gmax, int64_t ld_g, int n_g
 {
     if ((n_s & 31) || (ld_s & 3) || (reinterpret_cast<uintptr_t>(samp) & 15))
         return dae_fail(ctx, DAE_ERR_ARG, "sample rows must be whole tiles, 16-byte aligned");
-    TauP p{gmax, ld_g, n_g, samp, ld_s, n_s, samp_list, col_lo, seed_row_ptr, k, tau, out_pairs, pairs_stride, out_cnt, nullptr};
+    TauP p{gmax, ld_g, n_g, samp, ld_s, n_s, samp_list, col_lo, seed_row_ptr, k, tau, out_pairs, pairs_stride, out_cnt};
     return launch_tau_select(ctx, p, B);
 }
 

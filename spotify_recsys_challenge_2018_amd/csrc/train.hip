@@ -232,22 +232,18 @@ struct GwP {
     float* gW;                        // [V, H]
     float* gb;                        // [V] (written by the hc0 == 0 blocks) or null
     int accumulate;                   // gW += instead of =
-    int dbg;                          // experiments: 1 = no stores, 2 = no dz^T loads
     int n_half, nb_half;              // H / 128 hidden halves, blocks per half
     // dense TF1-Adam of the [V, H] tensor `ad_p` applied in the epilogue instead of writing gW (dae_arm_decoder_adam)
     float* ad_p; float* ad_m; float* ad_v; float ad_alpha, ad_b1, ad_b2, ad_eps;
 };
 
+// fp32 operands (the bf16 training step's K6 is grad_wdec_t_kernel / grad_wdec_t32_kernel below).
 // NA = hidden tiles per wave (4, 2 or 1): a "half" is 32*NA hidden units, hidden = hc0 + NA*i + a
-// BF16 (dae_set_train_dtype, NA = 4 only): the 8 k-steps of a GW_MMA group (16 playlists) become ONE
-// v_mfma_f32_32x32x16_bf16 per accumulator -- k-slot x of lane half hi is playlist R0 + 2x + hi in both
-// operands, which is exactly what the fp32 steps consume one at a time -- on operands rounded to bf16 in
-// registers; loads, LDS image, accumulators and stores are the fp32 kernel's.
-// TR (fp32, NA = 4): the two MFMA operands swapped -- D[i = vocabulary row of the lane pair][j = hidden lane] instead of
+// TR (NA = 4): the two MFMA operands swapped -- D[i = vocabulary row of the lane pair][j = hidden lane] instead of
 // D[i = hidden][j = vocabulary row].  Loads, LDS image and column sums are unchanged; what changes is that a lane of the
 // accumulators is a hidden unit (hc0 + 4 j + a), so the epilogue writes 512 contiguous bytes of one gW row per half-wave
 // instead of 16-byte pieces of 32 rows -- the same shape the transposed bf16 kernel (grad_wdec_t_kernel) has.
-template <int NA, int NW = 4, bool BF16 = false, bool DZ16 = false, bool TR = false>
+template <int NA, int NW = 4, bool TR = false>
 __global__ __launch_bounds__(NW * 64, 1) void grad_wdec_kernel(const GwP p)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];     // [Bp][32*NA] floats
@@ -347,27 +343,6 @@ __global__ __launch_bounds__(NW * 64, 1) void grad_wdec_kernel(const GwP p)
 // optimizer turns that into a dynamically indexed vector extract, which lives in scratch memory.
 #define GW_SEL(A, Bv) __uint_as_float((__float_as_uint(Bv) & himask) | (__float_as_uint(A) & ~himask))
 #define GW_MMA(T0, T1, R0)                                                                     \
-        if (BF16) {                                                                            \
-            float avs[8][NA];                                                                  \
-            _Pragma("unroll") for (int x_ = 0; x_ < 8; ++x_) {                                 \
-                const float4 t4 = *reinterpret_cast<const float4*>(lds + (size_t)((R0) + 2 * x_ + hi) * HW + NA * j); \
-                avs[x_][0] = t4.x; avs[x_][1 % NA] = t4.y; avs[x_][2 % NA] = t4.z; avs[x_][3 % NA] = t4.w; \
-            }                                                                                  \
-            float dx[8], dy[8];                                                                \
-            _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) {                                 \
-                dx[2 * q_] = GW_SEL(T0[q_].x, T0[q_].y); dx[2 * q_ + 1] = GW_SEL(T0[q_].z, T0[q_].w); \
-                dy[2 * q_] = GW_SEL(T1[q_].x, T1[q_].y); dy[2 * q_ + 1] = GW_SEL(T1[q_].z, T1[q_].w); \
-            }                                                                                  \
-            _Pragma("unroll") for (int x_ = 0; x_ < 8; ++x_) { cs0 += dx[x_]; cs1 += dy[x_]; } \
-            const bf16x8_t bx = pk_bf16x8(dx[0], dx[1], dx[2], dx[3], dx[4], dx[5], dx[6], dx[7]); \
-            const bf16x8_t by = pk_bf16x8(dy[0], dy[1], dy[2], dy[3], dy[4], dy[5], dy[6], dy[7]); \
-            _Pragma("unroll") for (int a = 0; a < NA; ++a) {                                   \
-                const bf16x8_t af = pk_bf16x8(avs[0][a], avs[1][a], avs[2][a], avs[3][a], avs[4][a], avs[5][a], \
-                                              avs[6][a], avs[7][a]);                           \
-                acc[a][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bx, acc[a][0], 0, 0, 0); \
-                acc[a][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, by, acc[a][1], 0, 0, 0); \
-            }                                                                                  \
-        } else                                                                                 \
         _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) {                                     \
             const int r4 = (R0) + 4 * q_;                                                      \
             GW_STEP(GW_SEL(T0[q_].x, T0[q_].y), GW_SEL(T1[q_].x, T1[q_].y), r4)                \
@@ -375,58 +350,6 @@ __global__ __launch_bounds__(NW * 64, 1) void grad_wdec_kernel(const GwP p)
         }
         const int Bp4 = Bp;                          // dz^T rows are zero padded to a multiple of 64
         const unsigned himask = hi ? 0xFFFFFFFFu : 0u;
-        if (DZ16) {
-            // dz^T stored as bf16: 16 playlists of a row = two 16-byte loads; the dword x of a row holds playlists
-            // (R0 + 2x, R0 + 2x + 1) and the lane half hi wants R0 + 2x + hi: one v_perm per operand dword
-            const unsigned short* z0 = reinterpret_cast<const unsigned short*>(p.dzT) + (size_t)(ok0 ? vcol : 0) * p.ldT;
-            const unsigned short* z1 = reinterpret_cast<const unsigned short*>(p.dzT) + (size_t)(ok1 ? vcol + 1 : 0) * p.ldT;
-            const unsigned sel = hi ? 0x07060302u : 0x05040100u;
-#define GW_LOAD16(U0, U1, R0)                                                                  \
-            _Pragma("unroll") for (int q_ = 0; q_ < 2; ++q_) {                                 \
-                const int r8 = min((R0) + 8 * q_, Bp4 - 8);                                    \
-                U0[q_] = *reinterpret_cast<const uint4*>(z0 + r8);                             \
-                U1[q_] = *reinterpret_cast<const uint4*>(z1 + r8);                             \
-            }
-#define GW_HALF(D) __uint_as_float(hi ? ((D) & 0xFFFF0000u) : ((D) << 16))
-#define GW_MMA16(U0, U1, R0)                                                                   \
-            {                                                                                  \
-                float avs[8][NA];                                                              \
-                _Pragma("unroll") for (int x_ = 0; x_ < 8; ++x_) {                             \
-                    const float4 t4 = *reinterpret_cast<const float4*>(lds + (size_t)((R0) + 2 * x_ + hi) * HW + NA * j); \
-                    avs[x_][0] = t4.x; avs[x_][1 % NA] = t4.y; avs[x_][2 % NA] = t4.z; avs[x_][3 % NA] = t4.w; \
-                }                                                                              \
-                const unsigned d0[8] = {U0[0].x, U0[0].y, U0[0].z, U0[0].w, U0[1].x, U0[1].y, U0[1].z, U0[1].w}; \
-                const unsigned d1[8] = {U1[0].x, U1[0].y, U1[0].z, U1[0].w, U1[1].x, U1[1].y, U1[1].z, U1[1].w}; \
-                _Pragma("unroll") for (int x_ = 0; x_ < 8; ++x_) { cs0 += GW_HALF(d0[x_]); cs1 += GW_HALF(d1[x_]); } \
-                const bf16x8_t bx = __builtin_bit_cast(bf16x8_t, make_uint4(                   \
-                    __builtin_amdgcn_perm(d0[1], d0[0], sel), __builtin_amdgcn_perm(d0[3], d0[2], sel), \
-                    __builtin_amdgcn_perm(d0[5], d0[4], sel), __builtin_amdgcn_perm(d0[7], d0[6], sel))); \
-                const bf16x8_t by = __builtin_bit_cast(bf16x8_t, make_uint4(                   \
-                    __builtin_amdgcn_perm(d1[1], d1[0], sel), __builtin_amdgcn_perm(d1[3], d1[2], sel), \
-                    __builtin_amdgcn_perm(d1[5], d1[4], sel), __builtin_amdgcn_perm(d1[7], d1[6], sel))); \
-                _Pragma("unroll") for (int a = 0; a < NA; ++a) {                               \
-                    const bf16x8_t af = pk_bf16x8(avs[0][a], avs[1][a], avs[2][a], avs[3][a], avs[4][a], avs[5][a], \
-                                                  avs[6][a], avs[7][a]);                       \
-                    acc[a][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bx, acc[a][0], 0, 0, 0); \
-                    acc[a][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, by, acc[a][1], 0, 0, 0); \
-                }                                                                              \
-            }
-            uint4 ua0[2], ua1[2], ub0[2], ub1[2];
-            GW_LOAD16(ua0, ua1, 0)
-            for (int r0 = 0; r0 < Bp; r0 += 32) {
-                GW_LOAD16(ub0, ub1, r0 + 16)
-                __builtin_amdgcn_sched_barrier(0);
-                GW_MMA16(ua0, ua1, r0)
-                __builtin_amdgcn_sched_barrier(0);
-                GW_LOAD16(ua0, ua1, r0 + 32)
-                __builtin_amdgcn_sched_barrier(0);
-                GW_MMA16(ub0, ub1, r0 + 16)
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#undef GW_LOAD16
-#undef GW_HALF
-#undef GW_MMA16
-        } else {
         float4 ta0[4], ta1[4], tb0[4], tb1[4];
         GW_LOAD(ta0, ta1, 0)
         for (int r0 = 0; r0 < Bp; r0 += 32) {        // straight-line 16 k-steps per iteration
@@ -439,22 +362,12 @@ __global__ __launch_bounds__(NW * 64, 1) void grad_wdec_kernel(const GwP p)
             GW_MMA(tb0, tb1, r0 + 16)
             __builtin_amdgcn_sched_barrier(0);
         }
-        }
 #undef GW_LOAD
 #undef GW_STEP
 #undef GW_SEL
 #undef GW_MMA
         // D[i][j]: hidden unit hc0 + NA * i_idx + a, i_idx = (reg & 3) + 8 (reg >> 2) + 4 hi; column
         // v0 + 2 j + b.  The NA `a` accumulators of one reg are NA consecutive hidden units.
-        if (DAE_EXP_ON(p.dbg & 1)) {
-            float keep = cs0 + cs1;
-#pragma unroll
-            for (int a = 0; a < NA; ++a)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) keep += acc[a][0][e] + acc[a][1][e];
-            if (keep == 12345.678f) p.gW[0] = keep;
-            continue;
-        }
         if (TR && NA == 4) {
             // register reg of accumulator (a, b) is row v0 + 2 i_idx + b, i_idx = (reg & 3) + 8 (reg >> 2) + 4 hi; lane j
             // holds hidden units hc0 + 4 j + a: one float4 per (b, reg)
@@ -866,7 +779,7 @@ __global__ __launch_bounds__(NW * 64, 1) void grad_wdec_t32_kernel(const GwP p)
 // playlists = two k-steps, the lane half hi taking the even / odd one), B = h^T from LDS (one float4 per lane and k-step: the four
 // accumulators' hidden units), 512 MFMAs per tile, the row sums (gb) on the VALU; then the Adam pass of section 12 -- the first
 // group of p / m / v rows requested before the MFMAs, group g + 1 before group g is computed.  The generic kernel it replaces
-// for this case (grad_wdec_kernel<4, 8, false, false, true>) ran its two phases back to back at 12 KB in flight per wave: 349 us
+// for this case (grad_wdec_kernel<4, 8, true>) ran its two phases back to back at 12 KB in flight per wave: 349 us
 // for 180 us of matrix work and 1.22 GB.
 template <int NW, bool FULL>
 __global__ __launch_bounds__(NW * 64, 1) void grad_wdec_t32_f32_kernel(const GwP p)
@@ -991,10 +904,10 @@ struct DhP {
     int fast32;                        // W and dz^T both end below 4 GB: whole chunks take 32-bit byte offsets from the matrix base
 };
 
-// BF16 (dae_set_train_dtype, NA = 4 only): the 8 k-steps of a block (16 vocabulary rows) become ONE
-// v_mfma_f32_32x32x16_bf16 per accumulator: k-slot x of lane half hi is row V0 + 2x + hi in both operands.
-// DZ16: dz^T is stored as bf16; a lane's two playlists (r0 + 2j, r0 + 2j + 1) of a row are one dword.
-template <int NA, bool BF16 = false, bool DZ16 = false>
+// BF16 (dae_set_train_dtype, NA = 4 only; dz^T is then stored as bf16, TrainPlan::dz16): the 8 k-steps of a block (16
+// vocabulary rows) become ONE v_mfma_f32_32x32x16_bf16 per accumulator: k-slot x of lane half hi is row V0 + 2x + hi in both
+// operands; a lane's two playlists (r0 + 2j, r0 + 2j + 1) of a dz^T row are one dword.
+template <int NA, bool BF16 = false>
 __global__ __launch_bounds__(256, 1) void grad_hidden_kernel(const DhP p)
 {
     constexpr int HW = 32 * NA;
@@ -1024,9 +937,9 @@ __global__ __launch_bounds__(256, 1) void grad_hidden_kernel(const DhP p)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.0f;
         // (byte offsets, 32 bits: the launcher takes the fast form only when both matrices lie below 4 GB)
-        const unsigned w_row = (unsigned)p.H * 4u, d_row = (unsigned)p.ldT * (DZ16 ? 2u : 4u);
+        const unsigned w_row = (unsigned)p.H * 4u, d_row = (unsigned)p.ldT * (BF16 ? 2u : 4u);
         const unsigned lane_w = (unsigned)(hc0 + NA * j) * 4u + (unsigned)hi * w_row;
-        const unsigned lane_d = (unsigned)(r0 + 2 * j) * (DZ16 ? 2u : 4u) + (unsigned)hi * d_row;
+        const unsigned lane_d = (unsigned)(r0 + 2 * j) * (BF16 ? 2u : 4u) + (unsigned)hi * d_row;
         const float* Wl = p.W + hc0 + NA * j;
         const float* Dl = p.dzT + r0 + 2 * j;
         const unsigned short* Dl16 = reinterpret_cast<const unsigned short*>(p.dzT) + r0 + 2 * j;
@@ -1054,7 +967,7 @@ __global__ __launch_bounds__(256, 1) void grad_hidden_kernel(const DhP p)
                 AV[s][0] = wr[0];                                                              \
             }                                                                                  \
             const char* dfast = reinterpret_cast<const char*>(p.dzT) + ((unsigned)((V0) + 2 * s) * d_row + lane_d); \
-            if (DZ16) D[s].x = __uint_as_float(*reinterpret_cast<const unsigned*>(             \
+            if (BF16) D[s].x = __uint_as_float(*reinterpret_cast<const unsigned*>(             \
                 FASTV ? dfast : reinterpret_cast<const char*>(Dl16 + (size_t)vc * p.ldT)));    \
             else D[s] = *reinterpret_cast<const float2*>(                                      \
                 FASTV ? dfast : reinterpret_cast<const char*>(Dl + (size_t)vc * p.ldT));       \
@@ -1063,26 +976,15 @@ __global__ __launch_bounds__(256, 1) void grad_hidden_kernel(const DhP p)
 // stage makes the compiler wait for that load before the sched_barrier, i.e. before the MFMAs it should hide under
 #define DH_MMA(AV, D, V0)                                                                      \
         if (BF16) {                                                                            \
-            bf16x8_t bx, by;                                                                   \
-            if (DZ16) {                                                                        \
-                unsigned dd[8];                                                                \
-                _Pragma("unroll") for (int s = 0; s < 8; ++s)                                  \
-                    dd[s] = (FASTV || (V0) + 2 * s + hi < v_end) ? __float_as_uint(D[s].x) : 0u; \
-                bx = __builtin_bit_cast(bf16x8_t, make_uint4(                                  \
-                    __builtin_amdgcn_perm(dd[1], dd[0], 0x05040100u), __builtin_amdgcn_perm(dd[3], dd[2], 0x05040100u), \
-                    __builtin_amdgcn_perm(dd[5], dd[4], 0x05040100u), __builtin_amdgcn_perm(dd[7], dd[6], 0x05040100u))); \
-                by = __builtin_bit_cast(bf16x8_t, make_uint4(                                  \
-                    __builtin_amdgcn_perm(dd[1], dd[0], 0x07060302u), __builtin_amdgcn_perm(dd[3], dd[2], 0x07060302u), \
-                    __builtin_amdgcn_perm(dd[5], dd[4], 0x07060302u), __builtin_amdgcn_perm(dd[7], dd[6], 0x07060302u))); \
-            } else {                                                                           \
-            float dx[8], dy[8];                                                                \
-            _Pragma("unroll") for (int s = 0; s < 8; ++s) {                                    \
-                const bool in = FASTV || (V0) + 2 * s + hi < v_end;                            \
-                dx[s] = in ? D[s].x : 0.f; dy[s] = in ? D[s].y : 0.f;                          \
-            }                                                                                  \
-            bx = pk_bf16x8(dx[0], dx[1], dx[2], dx[3], dx[4], dx[5], dx[6], dx[7]);            \
-            by = pk_bf16x8(dy[0], dy[1], dy[2], dy[3], dy[4], dy[5], dy[6], dy[7]);            \
-            }                                                                                  \
+            unsigned dd[8];                                                                    \
+            _Pragma("unroll") for (int s = 0; s < 8; ++s)                                      \
+                dd[s] = (FASTV || (V0) + 2 * s + hi < v_end) ? __float_as_uint(D[s].x) : 0u;   \
+            const bf16x8_t bx = __builtin_bit_cast(bf16x8_t, make_uint4(                       \
+                __builtin_amdgcn_perm(dd[1], dd[0], 0x05040100u), __builtin_amdgcn_perm(dd[3], dd[2], 0x05040100u), \
+                __builtin_amdgcn_perm(dd[5], dd[4], 0x05040100u), __builtin_amdgcn_perm(dd[7], dd[6], 0x05040100u))); \
+            const bf16x8_t by = __builtin_bit_cast(bf16x8_t, make_uint4(                       \
+                __builtin_amdgcn_perm(dd[1], dd[0], 0x07060302u), __builtin_amdgcn_perm(dd[3], dd[2], 0x07060302u), \
+                __builtin_amdgcn_perm(dd[5], dd[4], 0x07060302u), __builtin_amdgcn_perm(dd[7], dd[6], 0x07060302u))); \
             _Pragma("unroll") for (int a = 0; a < NA; ++a) {                                   \
                 const bf16x8_t af = pk_bf16x8(AV[0][a], AV[1][a], AV[2][a], AV[3][a], AV[4][a], AV[5][a], \
                                               AV[6][a], AV[7][a]);                             \
@@ -1629,17 +1531,13 @@ int train_plan(dae_ctx* ctx, int Vl, int H, int B, TrainPlan& t)
     t.NA = (H % 128) == 0 ? 4 : ((H % 64) == 0 ? 2 : 1);
     const int Hp = dae_round_up(H, DAE_HPAD);
     t.dtype = ctx->train_dtype;
-    {   // bf16 GEMMs with the 4-tile backward kernels: dL/dz itself is stored as bf16 (DAE_BWD_F32 / DAE_DZ_F32: A/B)
-        static const bool dz_f32 = dae_exp_env("DAE_BWD_F32") != nullptr || dae_exp_env("DAE_DZ_F32") != nullptr;
-        t.dz16 = (t.dtype == DAE_DTYPE_BF16 && (H % 128) == 0 && !dz_f32) ? 1 : 0;
-    }
+    // bf16 GEMMs with the 4-tile backward kernels: dL/dz itself is stored as bf16
+    t.dz16 = (t.dtype == DAE_DTYPE_BF16 && (H % 128) == 0) ? 1 : 0;
     t.g = t.dtype == DAE_DTYPE_BF16 ? dae_row_geometry_bf16(B, Hp) : dae_row_geometry(B, Hp);
     t.G = Hp / DAE_KG; t.RB = t.g.R_TILE / 32;
-    {   // hidden 256: K5 reads the row-major decoder and hidden activations directly (fp32, or rounded to bf16 in
-        // registers) -- no per-step prepack
-        static const bool k5_packed = dae_exp_env("DAE_K5_PACKED") != nullptr;                 // A/B
-        t.rm = (H == 256 && t.g.R_TILE == 128 && t.g.waves == 4 && !k5_packed) ? 1 : 0;
-    }
+    // hidden 256: K5 reads the row-major decoder and hidden activations directly (fp32, or rounded to bf16 in registers) -- no
+    // per-step prepack
+    t.rm = (H == 256 && t.g.R_TILE == 128 && t.g.waves == 4) ? 1 : 0;
     t.Bpad64 = (B + 63) / 64 * 64;
     t.hp_bytes = (size_t)t.g.n_rg * t.G * t.RB * 64 * sizeof(float4);
     if ((rc = dae_reserve(ctx, ctx->h_packed, t.hp_bytes))) return rc;
@@ -1652,8 +1550,7 @@ int train_plan(dae_ctx* ctx, int Vl, int H, int B, TrainPlan& t)
     if (t.chunk < 16) t.chunk = 16;
     t.n_chunk = (Vl + t.chunk - 1) / t.chunk;
     {   // bf16 GEMMs with dz^T as bf16 at hidden 256: dh comes out of the forward launch, one partial per workgroup + the positives'
-        static const bool no_fuse = dae_exp_env("DAE_K5_NOFUSE") != nullptr;                   // A/B: K5, then K7
-        t.fuse_dh = (t.rm && t.dtype == DAE_DTYPE_BF16 && t.dz16 && !no_fuse) ? 1 : 0;
+        t.fuse_dh = (t.rm && t.dtype == DAE_DTYPE_BF16 && t.dz16) ? 1 : 0;
         if (t.fuse_dh) t.n_chunk = t.g.grid + 1;
     }
     t.bh = (size_t)B * H;
@@ -1691,7 +1588,7 @@ int train_decode_backward(dae_ctx* ctx, const TrainPlan& t, int Vl, int H, int B
         if (t.Bpad64 != B) DAE_HIP_CHECK(ctx, hipMemsetAsync(corr_part, 0, (size_t)t.Bpad64 * H * sizeof(float), st));
     } else if (t.rm)
         rc = dae_launch_decode_loss_rowmajor(ctx, t.g, B, Vl, H, Wd, b_dec, t.hbuf, 1.0f / (float)n_batch, t.dzT, t.Bpad64,
-                                             t.loss_part, t.dtype, t.dz16);
+                                             t.loss_part);      // (fp32: a bf16 step at hidden 256 takes the fused launch above)
     else
         rc = dae_launch_decode_loss_f32(ctx, t.g, B, 1.0f / (float)n_batch, t.dzT, t.Bpad64, t.loss_part, t.dtype, t.dz16);
     if (rc) return rc;
@@ -1723,73 +1620,42 @@ int train_decode_backward(dae_ctx* ctx, const TrainPlan& t, int Vl, int H, int B
         }
         p.dzT = t.dzT; p.ldT = t.Bpad64; p.h = t.hbuf; p.H = H; p.B = B; p.V = Vl; p.gW = gWd; p.gb = gb_dec;
         p.accumulate = 0;
-        static const int k6dbg = dae_exp_env("DAE_DBG_K6") ? atoi(dae_exp_env("DAE_DBG_K6")) : 0;
-        p.dbg = k6dbg;
         p.n_half = H / (32 * NA);
         int nb = (DAE_NUM_CU / p.n_half) / DAE_NUM_XCD * DAE_NUM_XCD;
         if (nb < DAE_NUM_XCD) nb = DAE_NUM_XCD;
         p.nb_half = nb;
         const size_t lds = (size_t)((B + 31) & ~31) * 32 * NA * sizeof(float);
-        static const char attr_key = 0;
-        if (dae_first_use(ctx, &attr_key)) {
-            DAE_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&grad_wdec_kernel<4>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        }
         const dim3 grid(p.n_half * nb), blk(256);
         // two waves per SIMD on the shared h image: 241 us against 257 us with one (V = 170 000, B = H = 256); the
-        // second wave covers the dz^T load latency and the gW stores of the first (DAE_K6_WAVES=4 for the A/B)
-        static const bool k6w8 = !(dae_exp_env("DAE_K6_WAVES") && atoi(dae_exp_env("DAE_K6_WAVES")) == 4);
-        static const bool bwd_f32 = dae_exp_env("DAE_BWD_F32") != nullptr;      // A/B: bf16 forward only
-        if (NA == 4 && t.dtype == DAE_DTYPE_BF16 && !bwd_f32) {
-            static const char attr16_key = 0;
-            if (dae_first_use(ctx, &attr16_key)) {
-                DAE_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&grad_wdec_kernel<4, 8, true>),
+        // second wave covers the dz^T load latency and the gW stores of the first
+        if (NA == 4 && t.dtype == DAE_DTYPE_BF16) {          // (NA == 4 is H % 128 == 0: dz^T is bf16, t.dz16)
+            const size_t lds_t = (size_t)(((B + 31) & ~31) >> 4) * 4 * 64 * sizeof(uint4);
+            static const char k6t_key = 0;
+            if (dae_first_use(ctx, &k6t_key))
+                DAE_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&grad_wdec_t_kernel<8>),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            }
-            static const char attr16z_key = 0;
-            if (dae_first_use(ctx, &attr16z_key)) {
-                DAE_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&grad_wdec_kernel<4, 8, true, true>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            }
-            static const bool k6_old = dae_exp_env("DAE_K6_ORIENT") && !strcmp(dae_exp_env("DAE_K6_ORIENT"), "hidden");   // A/B
-            if (t.dz16 && !k6_old) {
-                const size_t lds_t = (size_t)(((B + 31) & ~31) >> 4) * 4 * 64 * sizeof(uint4);
-                static const char k6t_key = 0;
-                if (dae_first_use(ctx, &k6t_key))
-                    DAE_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&grad_wdec_t_kernel<8>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                static const bool k6_t64 = dae_exp_env("DAE_K6_T64") != nullptr;                       // A/B: the 64-row tile form
-                if (p.ad_m && !k6_t64) {
-                    static const char attr_t32_key = 0;
-                    if (dae_first_use(ctx, &attr_t32_key)) {
-                        DAE_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&grad_wdec_t32_kernel<8, true>),
-                                                               hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-                        DAE_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&grad_wdec_t32_kernel<8, false>),
-                                                               hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-                    }
-                    if (((B + 31) & ~31) == 256) hipLaunchKernelGGL((grad_wdec_t32_kernel<8, true>), grid, dim3(512), lds_t, st, p);
-                    else hipLaunchKernelGGL((grad_wdec_t32_kernel<8, false>), grid, dim3(512), lds_t, st, p);
-                } else
-                if (((B + 31) & ~31) == 256) {
-                    static const char attr_tf_key = 0;
-                    if (dae_first_use(ctx, &attr_tf_key))
-                        DAE_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&grad_wdec_t_kernel<8, true>),
-                                                               hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-                    hipLaunchKernelGGL((grad_wdec_t_kernel<8, true>), grid, dim3(512), lds_t, st, p);
-                } else
-                hipLaunchKernelGGL((grad_wdec_t_kernel<8>), grid, dim3(512), lds_t, st, p);
-            } else if (t.dz16) hipLaunchKernelGGL((grad_wdec_kernel<4, 8, true, true>), grid, dim3(512), lds, st, p);
-            else hipLaunchKernelGGL((grad_wdec_kernel<4, 8, true>), grid, dim3(512), lds, st, p);
-        } else if (NA == 4 && k6w8) {
-            static const char attr8_key = 0;
-            if (dae_first_use(ctx, &attr8_key)) {
-                DAE_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&grad_wdec_kernel<4, 8>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            }
-            static const bool k6_old32 = dae_exp_env("DAE_K6_ORIENT") && !strcmp(dae_exp_env("DAE_K6_ORIENT"), "hidden");   // A/B
-            static const bool k6_generic = dae_exp_env("DAE_K6_GENERIC") != nullptr;                // A/B: the generic kernel below
+            if (p.ad_m) {
+                static const char attr_t32_key = 0;
+                if (dae_first_use(ctx, &attr_t32_key)) {
+                    DAE_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&grad_wdec_t32_kernel<8, true>),
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+                    DAE_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&grad_wdec_t32_kernel<8, false>),
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+                }
+                if (((B + 31) & ~31) == 256) hipLaunchKernelGGL((grad_wdec_t32_kernel<8, true>), grid, dim3(512), lds_t, st, p);
+                else hipLaunchKernelGGL((grad_wdec_t32_kernel<8, false>), grid, dim3(512), lds_t, st, p);
+            } else
+            if (((B + 31) & ~31) == 256) {
+                static const char attr_tf_key = 0;
+                if (dae_first_use(ctx, &attr_tf_key))
+                    DAE_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&grad_wdec_t_kernel<8, true>),
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+                hipLaunchKernelGGL((grad_wdec_t_kernel<8, true>), grid, dim3(512), lds_t, st, p);
+            } else
+            hipLaunchKernelGGL((grad_wdec_t_kernel<8>), grid, dim3(512), lds_t, st, p);
+        } else if (NA == 4) {
             const int Bp32 = (B + 31) & ~31;
-            if (p.ad_m && H == 256 && !k6_old32 && !k6_generic && (Bp32 & 15) == 0) {
+            if (p.ad_m && H == 256 && (Bp32 & 15) == 0) {
                 // (the ring walks the dz^T row four float4 at a time: whole groups of 16 playlists)
                 const size_t lds_f = (size_t)(Bp32 >> 1) * 64 * sizeof(float4);
                 static const char attr_tf32_key = 0;
@@ -1801,16 +1667,14 @@ int train_decode_backward(dae_ctx* ctx, const TrainPlan& t, int Vl, int H, int B
                 }
                 if (Bp32 == 256) hipLaunchKernelGGL((grad_wdec_t32_f32_kernel<8, true>), grid, dim3(512), lds_f, st, p);
                 else hipLaunchKernelGGL((grad_wdec_t32_f32_kernel<8, false>), grid, dim3(512), lds_f, st, p);
-            } else
-            if (!k6_old32) {
+            } else {
                 static const char attr8t_key = 0;
                 if (dae_first_use(ctx, &attr8t_key))
-                    DAE_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&grad_wdec_kernel<4, 8, false, false, true>),
+                    DAE_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&grad_wdec_kernel<4, 8, true>),
                                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                hipLaunchKernelGGL((grad_wdec_kernel<4, 8, false, false, true>), grid, dim3(512), lds, st, p);
-            } else hipLaunchKernelGGL((grad_wdec_kernel<4, 8>), grid, dim3(512), lds, st, p);
-        } else if (NA == 4) hipLaunchKernelGGL(grad_wdec_kernel<4>, grid, blk, lds, st, p);
-        else if (NA == 2) hipLaunchKernelGGL(grad_wdec_kernel<2>, grid, blk, lds, st, p);
+                hipLaunchKernelGGL((grad_wdec_kernel<4, 8, true>), grid, dim3(512), lds, st, p);
+            }
+        } else if (NA == 2) hipLaunchKernelGGL(grad_wdec_kernel<2>, grid, blk, lds, st, p);
         else hipLaunchKernelGGL(grad_wdec_kernel<1>, grid, blk, lds, st, p);
         DAE_CHECK_LAUNCH(ctx, "grad_wdec_kernel");
         return DAE_OK;
@@ -1826,10 +1690,7 @@ int train_decode_backward(dae_ctx* ctx, const TrainPlan& t, int Vl, int H, int B
         const int total = p.n_half * p.n_rblk * t.n_chunk;
         int blocks = (total + 3) / 4;
         if (blocks > DAE_NUM_CU) blocks = DAE_NUM_CU;
-        static const bool bwd_f32_7 = dae_exp_env("DAE_BWD_F32") != nullptr;
-        if (NA == 4 && t.dtype == DAE_DTYPE_BF16 && !bwd_f32_7 && t.dz16)
-            hipLaunchKernelGGL((grad_hidden_kernel<4, true, true>), dim3(blocks), dim3(256), 0, st, p);
-        else if (NA == 4 && t.dtype == DAE_DTYPE_BF16 && !bwd_f32_7)
+        if (NA == 4 && t.dtype == DAE_DTYPE_BF16)          // (dz^T is bf16: t.dz16)
             hipLaunchKernelGGL((grad_hidden_kernel<4, true>), dim3(blocks), dim3(256), 0, st, p);
         else if (NA == 4) hipLaunchKernelGGL(grad_hidden_kernel<4>, dim3(blocks), dim3(256), 0, st, p);
         else if (NA == 2) hipLaunchKernelGGL(grad_hidden_kernel<2>, dim3(blocks), dim3(256), 0, st, p);
@@ -1919,7 +1780,7 @@ int dae_launch_grad_w(dae_ctx* ctx, const float* dzT, int64_t ldT, const float* 
     GwP p;
     p.ad_p = nullptr; p.ad_m = nullptr; p.ad_v = nullptr; p.ad_alpha = p.ad_b1 = p.ad_b2 = p.ad_eps = 0.0f;
     p.dzT = dzT; p.ldT = ldT; p.h = h; p.H = H; p.B = B; p.V = V; p.gW = gW; p.gb = gb;
-    p.accumulate = 0; p.dbg = 0;
+    p.accumulate = 0;
     p.n_half = H / (32 * NA);
     int nb = (DAE_NUM_CU / p.n_half) / DAE_NUM_XCD * DAE_NUM_XCD;
     if (nb < DAE_NUM_XCD) nb = DAE_NUM_XCD;

@@ -1,7 +1,8 @@
 """GPU (-m gpu): a short run of the randomised parity sweep scripts/fuzz_gpu.py (random vocabulary / hidden /
 batch / k / bias / seed patterns; fused vs oracle, unfused, shard + merge, bf16 fused vs unfused, exact bf16 vs
-oracle -- all bit for bit).  The long sweeps (1000+ shapes, also under DAE_TOPK_LEAN / DAE_SAMPLE=strided / DAE_TOPK_THREADS=256) are
-run by hand; this keeps a slice of them in every test run."""
+oracle -- all bit for bit).  The long sweeps (1000+ shapes) are run by hand; this keeps a slice of them in every test
+run.  The lean top-k mode and the strided tile order, which the planner takes for very wide ranked ranges / decoders,
+are tested at such shapes in test_gpu_parity.py."""
 import os
 import subprocess
 import sys

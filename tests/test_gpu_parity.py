@@ -215,6 +215,44 @@ def test_decode_topk_equals_unfused(ctx):
     assert torch.equal(i1, i2) and torch.equal(s1, s2)
 
 
+def test_wide_decoder_strided_order_bit_exact(ctx):
+    """A prepacked decoder of more than ORDER_MAX_TILES = 8192 tiles (262 144 columns) orders its sample with
+    tile_order_strided_kernel instead of the bias sort: the fused path must still equal the oracle bit for bit."""
+    import torch
+    V, nt, H, B, k = 300000, 290000, 32, 6, 100
+    p = _problem(V, nt, H, B, seed=5, bias="zipf")
+    h = _gpu_encode(ctx, p)
+    ctx.prepack_decoder(_dev(p["W_dec"]), _dev(p["b_dec"]))
+    score = torch.empty((B, k), dtype=torch.float32, device="cuda")
+    idx = torch.empty((B, k), dtype=torch.int32, device="cuda")
+    ctx.decode_topk(h, nt, _dev(p["srp"]), _dev(p["sc"]), k, score, idx)
+    torch.cuda.synchronize()
+    plan = ctx.last_plan()
+    assert plan["fused"] == 1 and plan["n_tiles"] > 8192, plan
+    z_ref = oracle.decode(h.cpu().numpy(), p["W_dec"], p["b_dec"], 0, nt)
+    sc_r, idx_r = oracle.topk(z_ref, k, p["srp"], p["sc"])
+    _check_topk(idx.cpu().numpy(), score.cpu().numpy(), idx_r, sc_r)
+
+
+def test_topk_dense_lean_wide_range_bit_exact(ctx):
+    """A ranked range too wide for the LDS seed bitmap takes the lean top-k mode.  At 2 M columns the bitmap alone is 250 KB,
+    more than a CU's 160 KB of LDS: the bitmap mode cannot take this launch (it would fail with DAE_ERR_ARG), so a pass here is
+    a lean pass."""
+    import torch
+    n, k, B = 2_000_000, 500, 3
+    rng = np.random.default_rng(17)
+    z = rng.standard_normal((B, n)).astype(np.float32)
+    for r in range(B):                          # 100 ties at the value of rank 480: they straddle the cut (k + the seeds)
+        z[r, 7::20011] = np.partition(z[r], n - 480)[n - 480]
+    seeds = [list(rng.integers(0, n, size=150)) + list(np.argsort(-z[r])[:40]) for r in range(B)]   # (some of the best)
+    srp, sc = seeds_to_csr(seeds, B, n)
+    score = torch.empty((B, k), dtype=torch.float32, device="cuda")
+    idx = torch.empty((B, k), dtype=torch.int32, device="cuda")
+    ctx.topk_dense(_dev(z), n, 0, _dev(srp), _dev(sc), k, score, idx)
+    sc_r, idx_r = oracle.topk(z, k, srp, sc)
+    _check_topk(idx.cpu().numpy(), score.cpu().numpy(), idx_r, sc_r)
+
+
 def test_shard_merge_bit_exact(ctx):
     """Column-sharded decode + K4 merge == unsharded, run on one GPU."""
     import torch
