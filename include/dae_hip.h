@@ -367,6 +367,52 @@ int dae_pipeline_times(dae_pipeline* p, uint64_t out4[4]);
 int dae_pipeline_exact_margin(dae_pipeline* p, float scale);
 const char* dae_pipeline_last_error(const dae_pipeline* p);
 
+/* ---- ranking metrics on the device (the reference's utils/metrics.py: get_r_precision, get_ndcg, get_rsc) ------------------
+ *
+ * The RecSys Challenge 2018 is judged on R-precision, NDCG and recommended-songs clicks.  An evaluation needs three numbers
+ * per playlist, not its k indices: dae_rank_metrics reads the top-k lists where the rankers wrote them and leaves one
+ * 24-byte record per row.  The definitions, per row:
+ *
+ *   cand   = the entries >= 0 of the row's list idx[row * ld .. + k), in order (the rankers pad the tail with -1);
+ *   answer = ans_col[ans_row_ptr[row] .. ans_row_ptr[row + 1]): int ids, unsorted, -1 (a track outside the vocabulary: it
+ *            hits nothing and counts in n) and duplicates allowed, any length n;  hit(p) = cand[p] is one of them.
+ *   hits_r   = number of p < min(n, len(cand)) with hit(p)                      -> r-precision = hits_r / n
+ *   first    = the smallest p with hit(p), -1 when there is none                -> clicks = first / 10 (integer), 51 for -1
+ *   m        = number of p >= 1 with hit(p)
+ *   dcg      = (hit(0) ? 1.0 : 0.0), then += disc[p] for every hit p >= 1 in ASCENDING p, in float64
+ *              -> NDCG = dcg / (1.0 + disc[1] + ... + disc[m]), the reference's ideal DCG: it grows with the number of hits,
+ *                 not with n (metrics.py:29-42, kept as is)
+ *   n_answer = n; 0 marks the record INVALID (an empty answer row: the reference divides by zero there, nothing is divided here)
+ *
+ * disc [k] float64 is the CALLER's table, disc[p] = 1 / log2(p + 1) as the caller's own logarithm gives it (disc[0] is never
+ * read): with Python's 1 / math.log(p + 1, 2) the records reproduce utils/metrics.py bit for bit -- the kernel only adds, one
+ * lane order, never reassociated, and the divisions are the host's.  An EMPTY cand (a list of -1 only), which get_ndcg cannot
+ * answer (IndexError), is defined as dcg = 0, m = 0, first = -1: NDCG 0.0, clicks 51.
+ * 1 <= k <= 1024, ld >= k; device pointers; asynchronous on the context's stream. */
+typedef struct dae_metric_rec {
+    int32_t hits_r, first, m, n_answer;
+    double dcg;
+} dae_metric_rec;
+int dae_rank_metrics(dae_ctx* ctx, const int32_t* idx, int64_t ld, int B, int k, const int32_t* ans_row_ptr,
+                     const int32_t* ans_col, const double* disc, dae_metric_rec* out);
+
+/* The pipeline's EVALUATION mode (main_train.py:48-100 for every test split): the feeds come with their answers and what
+ * leaves the device is each row's dae_metric_rec -- the lists never cross the link.
+ *   enable_eval : once, before the first submit (DAE_ERR_STATE after it).  disc_host [k] float64 (HOST; see dae_rank_metrics);
+ *                 max_answers = answer ids one launch may hold (a launch closes when the next feed's would not fit).
+ *   submit_eval : dae_pipeline_submit / _submit_titled (titles, titles_use NULL: a plain feed) plus the feed's answers as a
+ *                 HOST CSR: ans_row_ptr [n_rows + 1] (any base), ans_col int32.  Staged and uploaded with the feed.
+ *   poll_eval   : dae_pipeline_poll with *rec -> the feed's [n_rows] records inside pinned result block *block.
+ * dae_rank_metrics runs on the lane's stream behind the scoring call; coalescing, lanes, ordering, DAE_PIPE_BUSY and release
+ * are the pipeline's as above, and so is the exact mode's guard: a launch that is re-scored in fp32 has its metrics
+ * recomputed from the fp32 lists before they go out.  An eval pipeline takes only submit_eval / poll_eval, every other
+ * pipeline only submit / submit_titled / poll: the wrong call returns DAE_ERR_STATE. */
+int dae_pipeline_enable_eval(dae_pipeline* p, const double* disc_host, int64_t max_answers);
+int dae_pipeline_submit_eval(dae_pipeline* p, const int64_t* positions, const float* values, int values_broadcast, int64_t nnz,
+                             int n_rows, const int32_t* titles, const float* titles_use, const int32_t* ans_row_ptr,
+                             const int32_t* ans_col, uint64_t* ticket_out);
+int dae_pipeline_poll_eval(dae_pipeline* p, int wait, uint64_t* ticket, const dae_metric_rec** rec, int* n_rows, int* block);
+
 /* ---- training step (DAEs.py:98-102) ------------------------------------------------------ */
 
 /* Arithmetic of the three GEMMs of the training step of this context (forward hidden x W_dec^T, gW_dec = dz^T h,

@@ -24,6 +24,7 @@ EXPORTS = [
     "dae_arm_decoder_adam", "dae_set_decode_gate", "dae_set_overlap_hint",
     "dae_pipeline_create", "dae_pipeline_create_titled", "dae_pipeline_destroy", "dae_pipeline_submit", "dae_pipeline_submit_titled", "dae_pipeline_flush", "dae_pipeline_poll",
     "dae_pipeline_release", "dae_pipeline_stats", "dae_pipeline_exact_margin", "dae_pipeline_times", "dae_pipeline_last_error",
+    "dae_rank_metrics", "dae_pipeline_enable_eval", "dae_pipeline_submit_eval", "dae_pipeline_poll_eval",
 ]
 DAE_PIPE_BUSY = 1
 
@@ -141,6 +142,10 @@ def load():
     lib.dae_pipeline_exact_margin.argtypes = [vp, c_f]
     lib.dae_pipeline_times.argtypes = [vp, u64p]
     lib.dae_pipeline_last_error.argtypes = [vp]
+    lib.dae_rank_metrics.argtypes = [vp, vp, c_i64, c_int, c_int, vp, vp, vp, vp]
+    lib.dae_pipeline_enable_eval.argtypes = [vp, vp, c_i64]
+    lib.dae_pipeline_submit_eval.argtypes = [vp, vp, vp, c_int, c_i64, c_int, vp, vp, vp, vp, u64p]
+    lib.dae_pipeline_poll_eval.argtypes = [vp, c_int, u64p, ctypes.POINTER(vp), ip, ip]
     lib.dae_pipeline_last_error.restype = ctypes.c_char_p
     for name in EXPORTS:
         if name not in ("dae_last_error", "dae_scratch_bytes", "dae_profile_kernel", "dae_pipeline_last_error"):
@@ -418,6 +423,21 @@ class Context:
         self.check(self.lib.dae_topk_merge(self.h, G, B, k, _ptr(cand_logit), _ptr(cand_idx),
                                            int(out_kind), _ptr(out_score), _ptr(out_idx)))
 
+    def rank_metrics(self, idx, k, ans_row_ptr, ans_col, out=None, disc=None):
+        """dae_rank_metrics: idx int32 [B, ld >= k], the answers as a CSR (int32 CUDA tensors) -> a uint8 CUDA tensor [B, 24]
+        holding one dae_metric_rec per row (`.cpu().numpy().view(metrics.RECORD_DTYPE)`).  disc: float64 [k] CUDA tensor,
+        by default Python's own 1 / math.log(p + 1, 2) (utils/metrics.py discount_table)."""
+        import torch
+        B, ld = int(idx.shape[0]), int(idx.stride(0)) if idx.dim() == 2 else int(k)
+        if disc is None:
+            from .utils.metrics import discount_table
+            disc = torch.from_numpy(discount_table(k)).to(idx.device)
+        if out is None:
+            out = torch.empty((B, 24), dtype=torch.uint8, device=idx.device)
+        self.check(self.lib.dae_rank_metrics(self.h, _ptr(idx), ld, B, int(k), _ptr(ans_row_ptr), _ptr(ans_col), _ptr(disc),
+                                             _ptr(out)))
+        return out
+
     def profile_enable(self, on=True):
         self.check(self.lib.dae_profile_enable(self.h, 1 if on else 0))
 
@@ -519,6 +539,7 @@ class Pipeline:
         if rc != 0:
             raise DaeError("dae_pipeline_create failed (%d): %s" % (rc, self.lib.dae_pipeline_last_error(None).decode()))
         self.h = h
+        self.eval = False
         self.pending = 0                     # feeds submitted and not yet yielded
         # the foreign calls' out-parameters, made once (a feed is ~25 us of this thread: five ctypes objects and their byref()
         # per poll were 3 us of it)
@@ -527,6 +548,8 @@ class Pipeline:
         self._poll_args = (ctypes.byref(self._t), ctypes.byref(self._ip), ctypes.byref(self._sp) if self.want_scores else None,
                            ctypes.byref(self._n), ctypes.byref(self._b))
         self._t_ref = ctypes.byref(self._t)
+        self._rp = ctypes.c_void_p()
+        self._poll_eval_args = (ctypes.byref(self._t), ctypes.byref(self._rp), ctypes.byref(self._n), ctypes.byref(self._b))
         # a pipeline owns a library thread and streams: it must be gone before the runtime is (a destructor running HIP calls
         # during interpreter teardown is undefined -- ADVICE r4)
         global _live_pipelines
@@ -542,10 +565,16 @@ class Pipeline:
             raise DaeError("dae_pipeline error %d: %s" % (rc, self.lib.dae_pipeline_last_error(self.h).decode()))
         return rc
 
-    def submit(self, positions, values, n_rows, titles=None, titles_use=None):
-        """positions: int64 [nnz, 2] (C-contiguous numpy), values: float32 [nnz] or one value.  -> True, or False when every
-        lane holds lists that were not fetched yet (take `results()` first).  titles [n_rows, L] int32 + titles_use [n_rows]
-        (a titled pipeline): the launch ranks the title-mixed score."""
+    def enable_eval(self, max_answers=1 << 20):
+        """The evaluation mode (dae_pipeline_enable_eval), before the first submit: every `submit` then carries `answers=`, and
+        `poll_eval` hands out the rows' metric records instead of their lists.  The discount table is Python's own
+        1 / math.log(p + 1, 2)."""
+        from .utils.metrics import discount_table
+        disc = discount_table(self.k)
+        self._check(self.lib.dae_pipeline_enable_eval(self.h, disc.ctypes.data_as(ctypes.c_void_p), int(max_answers)))
+        self.eval, self.max_answers = True, int(max_answers)
+
+    def _feed_arrays(self, positions, values):
         import numpy as np
         if self._closing:
             raise DaeError("dae_pipeline: closed")
@@ -556,6 +585,17 @@ class Pipeline:
         nnz = pos.size >> 1
         if val.size != nnz and val.size != 1:
             raise ValueError("positions (%d) and values (%d) differ in length" % (nnz, val.size))
+        return pos, val, nnz
+
+    def submit(self, positions, values, n_rows, titles=None, titles_use=None, answers=None):
+        """positions: int64 [nnz, 2] (C-contiguous numpy), values: float32 [nnz] or one value.  -> True, or False when every
+        lane holds lists that were not fetched yet (take `results()` first).  titles [n_rows, L] int32 + titles_use [n_rows]
+        (a titled pipeline): the launch ranks the title-mixed score.  answers=: `submit_eval` (a pipeline in evaluation mode,
+        and only there)."""
+        import numpy as np
+        if answers is not None:
+            return self.submit_eval(positions, values, n_rows, answers, titles, titles_use)
+        pos, val, nnz = self._feed_arrays(positions, values)
         if titles is not None:
             tt = np.ascontiguousarray(titles, np.int32).reshape(-1)
             uu = np.ascontiguousarray(titles_use, np.float32).reshape(-1)
@@ -571,6 +611,31 @@ class Pipeline:
                                               1 if (val.size == 1 and nnz != 1) else 0, nnz, int(n_rows), self._t_ref)
             if rc < 0:
                 self._check(rc)
+        if rc == DAE_PIPE_BUSY:
+            return False
+        self.pending += 1
+        return True
+
+    def submit_eval(self, positions, values, n_rows, answers, titles=None, titles_use=None):
+        """`submit` on a pipeline in evaluation mode (`enable_eval`): the feed with its answers = (row_ptr int32 [n_rows + 1],
+        col int32), a CSR over the feed's rows (-1 and duplicates allowed); `poll_eval` hands the rows' records out."""
+        import numpy as np
+        pos, val, nnz = self._feed_arrays(positions, values)
+        arp = np.ascontiguousarray(answers[0], np.int32)
+        acol = np.ascontiguousarray(answers[1], np.int32)
+        if arp.size != int(n_rows) + 1 or arp[-1] > acol.size or arp[0] < 0:
+            raise ValueError("answers: (row_ptr [n_rows + 1], col) with row_ptr[-1] <= len(col)")
+        tt = uu = None
+        if titles is not None:
+            tt = np.ascontiguousarray(titles, np.int32).reshape(-1)
+            uu = np.ascontiguousarray(titles_use, np.float32).reshape(-1)
+            if tt.size != int(n_rows) * (self.title_len or 0) or uu.size != int(n_rows):
+                raise ValueError("titles must be [n_rows, %s] and titles_use [n_rows]" % self.title_len)
+        vp_ = ctypes.c_void_p
+        rc = self._check(self.lib.dae_pipeline_submit_eval(
+            self.h, pos.ctypes.data_as(vp_), val.ctypes.data_as(vp_), 1 if (val.size == 1 and nnz != 1) else 0, nnz, int(n_rows),
+            None if tt is None else tt.ctypes.data_as(vp_), None if uu is None else uu.ctypes.data_as(vp_),
+            arp.ctypes.data_as(vp_), acol.ctypes.data_as(vp_), self._t_ref))
         if rc == DAE_PIPE_BUSY:
             return False
         self.pending += 1
@@ -611,6 +676,24 @@ class Pipeline:
         if copy:
             idx, score = idx.copy(), (None if score is None else score.copy())
         return idx, score
+
+    def poll_eval(self, wait=True):
+        """The next feed in submission order -> its rows' records (a numpy array of utils/metrics.py RECORD_DTYPE, a private
+        copy: 24 bytes a row), or None when it is not ready (wait=False) or nothing is pending."""
+        import numpy as np
+        from .utils.metrics import RECORD_DTYPE
+        if self.pending == 0:
+            return None
+        rc = self.lib.dae_pipeline_poll_eval(self.h, 1 if wait else 0, *self._poll_eval_args)
+        if rc < 0:
+            self._check(rc)
+        n = self._n.value
+        if n == 0:
+            return None
+        self.pending -= 1
+        rec = np.frombuffer((ctypes.c_char * (n * RECORD_DTYPE.itemsize)).from_address(self._rp.value), dtype=RECORD_DTYPE).copy()
+        self._check(self.lib.dae_pipeline_release(self.h, self._b.value))
+        return rec
 
     def exact_margin(self, scale):
         self._check(self.lib.dae_pipeline_exact_margin(self.h, float(scale)))

@@ -23,6 +23,7 @@ struct Feed { uint64_t ticket; int row0, n_rows; };
 
 struct OutBlock {                 // pinned result block of one launch: idx [rows][k] (+ score), handed out by pointer
     int32_t* idx = nullptr; float* score = nullptr;
+    dae_metric_rec* rec = nullptr;                    // evaluation mode: the launch's [rows] records (idx is not kept then)
     int refs = 0;                 // feeds handed out and not yet released (+1 while its launch is pending)
 };
 
@@ -59,6 +60,11 @@ struct Slot {                     // one launch from staging to its last polled 
     hipEvent_t ev_scored = nullptr;                        // the scoring call's last kernel (the out stream waits for it)
     int32_t* h_titles = nullptr; float* h_use = nullptr;   // titled pipelines: [group_rows][L] characters, [group_rows] titles_use
     int32_t* d_titles = nullptr; float* d_use = nullptr;
+    // evaluation mode (dae_pipeline_enable_eval): the launch's answers as a CSR over its rows, staged and uploaded with the
+    // feed, and the records dae_rank_metrics leaves (the out thread moves THEM, d_idx stays on the device)
+    int32_t *h_arp = nullptr, *h_acol = nullptr, *d_arp = nullptr, *d_acol = nullptr;
+    dae_metric_rec* d_rec = nullptr;
+    int64_t n_ans = 0;
     int titled = 0;               // this launch ranks the title-mixed score (its feeds came through dae_pipeline_submit_titled)
     unsigned polls = 0;           // non-waiting polls of this issue that found its word missing (every 256th asks the runtime)
     int32_t seq = 0;              // the sequence word this launch's last kernel writes into h_flags[3] (the caller's wait watches it)
@@ -119,6 +125,9 @@ struct dae_pipeline {
     bool has_title = false;       // dae_pipeline_create_titled
     TitleW tw;
     int exact_pause = 0, overflow_streak = 0;      // titled + exact: launches left on the fp32 kernels / overflow events in a row
+    bool eval = false;            // dae_pipeline_enable_eval: feeds carry answers, records go out instead of lists
+    int64_t max_answers = 0;
+    double* d_disc = nullptr;     // the caller's discount table [k]
     uint64_t issue_ns = 0, idle_ns = 0, submit_ns = 0, wait_ns = 0;      // where the host side of the loop spends its time (dae_pipeline_times)
 };
 
@@ -238,6 +247,11 @@ int issue(dae_pipeline* p, Slot& S, int dtype)
         PIPE_HIP(p, hipMemcpyAsync(S.d_titles, S.h_titles, (size_t)S.rows * p->tw.L * sizeof(int32_t), hipMemcpyHostToDevice, p->copy_stream));
         PIPE_HIP(p, hipMemcpyAsync(S.d_use, S.h_use, (size_t)S.rows * sizeof(float), hipMemcpyHostToDevice, p->copy_stream));
     }
+    if (p->eval) {
+        PIPE_HIP(p, hipMemcpyAsync(S.d_arp, S.h_arp, (size_t)(S.rows + 1) * sizeof(int32_t), hipMemcpyHostToDevice, p->copy_stream));
+        if (S.n_ans > 0)
+            PIPE_HIP(p, hipMemcpyAsync(S.d_acol, S.h_acol, (size_t)S.n_ans * sizeof(int32_t), hipMemcpyHostToDevice, p->copy_stream));
+    }
     PIPE_HIP(p, hipEventRecord(S.ev_h2d, p->copy_stream));
     if (p->dtype == DAE_DTYPE_F32 && p->lanes.size() > 1) {
         // the fp32 filter launch takes every CU, two of them in flight only queue behind each other: this launch's waits for
@@ -284,6 +298,12 @@ int issue(dae_pipeline* p, Slot& S, int dtype)
         PIPE_HIP(p, hipStreamWaitEvent(L.stream, S.ev_prep, 0));
         rc = dae_score_topk(L.ctx, S.d_rp, S.d_col, S.d_cval, p->W_enc, p->b_enc, p->V, p->H, S.rows, dtype, p->n_tracks,
                             S.d_srp, S.d_scol, p->k, DAE_OUT_SCORE, out_score, out_idx);
+        if (rc) return pfatal(p, rc, dae_last_error(L.ctx));
+    }
+    if (p->eval) {
+        // the rows' metrics from the lists where they are (the answers came up with the feed: ev_h2d -> ev_prep -> this stream).
+        // A guard re-run comes through here again, so its records are the fp32 lists'.
+        rc = dae_rank_metrics(L.ctx, out_idx, p->k, S.rows, p->k, S.d_arp, S.d_acol, p->d_disc, S.d_rec);
         if (rc) return pfatal(p, rc, dae_last_error(L.ctx));
     }
     // The small words first pass through one device block (flags: status, guard words), so the out thread's copies of a
@@ -342,8 +362,15 @@ void out_worker_main(dae_pipeline* p)
         }
         const OutBlock& ob = p->blocks[S.block];
         const size_t nb = (size_t)S.rows * p->k;
-        if (e == hipSuccess) e = hipMemcpyAsync(ob.idx, S.d_idx, nb * sizeof(int32_t), hipMemcpyDeviceToHost, p->out_stream);
-        if (e == hipSuccess && p->want_scores) e = hipMemcpyAsync(ob.score, S.d_score, nb * sizeof(float), hipMemcpyDeviceToHost, p->out_stream);
+        if (p->eval) {
+            // the records instead of the lists; the out stream is ordered behind the launch by its event (already complete when
+            // the word is seen, so the wait costs nothing and the copies do not rest on the kernel-end write-back alone)
+            if (e == hipSuccess) e = hipStreamWaitEvent(p->out_stream, S.ev_scored, 0);
+            if (e == hipSuccess) e = hipMemcpyAsync(ob.rec, S.d_rec, (size_t)S.rows * sizeof(dae_metric_rec), hipMemcpyDeviceToHost, p->out_stream);
+        } else {
+            if (e == hipSuccess) e = hipMemcpyAsync(ob.idx, S.d_idx, nb * sizeof(int32_t), hipMemcpyDeviceToHost, p->out_stream);
+            if (e == hipSuccess && p->want_scores) e = hipMemcpyAsync(ob.score, S.d_score, nb * sizeof(float), hipMemcpyDeviceToHost, p->out_stream);
+        }
         if (e == hipSuccess) e = hipMemcpyAsync(S.h_flags, S.d_flags, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, p->out_stream);
         if (e == hipSuccess) e = hipStreamSynchronize(p->out_stream);
         if (e != hipSuccess) {
@@ -487,7 +514,8 @@ int dae_pipeline_destroy(dae_pipeline* p)
     for (Slot& S : p->slots) {
         if (S.ev_scored) (void)hipEventDestroy(S.ev_scored);
         if (S.ev_prep) (void)hipEventDestroy(S.ev_prep);
-        void* outs[] = {S.d_idx, S.d_score, S.d_flags, S.d_rp, S.d_col, S.d_srp, S.d_scol, S.d_status, S.d_cval, S.t_h, S.t_feat, S.t_wt, S.t_wp};
+        void* outs[] = {S.d_idx, S.d_score, S.d_flags, S.d_rp, S.d_col, S.d_srp, S.d_scol, S.d_status, S.d_cval, S.t_h, S.t_feat, S.t_wt, S.t_wp,
+                        S.d_arp, S.d_acol, S.d_rec};
         for (void* q : outs) if (q) (void)hipFree(q);
         if (S.ev_h2d) (void)hipEventDestroy(S.ev_h2d);
         if (S.ev_gate) (void)hipEventDestroy(S.ev_gate);
@@ -495,13 +523,15 @@ int dae_pipeline_destroy(dae_pipeline* p)
         if (S.d_val) (void)hipFree(S.d_val);
         if (S.d_titles) (void)hipFree(S.d_titles);
         if (S.d_use) (void)hipFree(S.d_use);
-        void* host[] = {S.h_pos, S.h_val, S.h_flags, S.h_titles, S.h_use};
+        void* host[] = {S.h_pos, S.h_val, S.h_flags, S.h_titles, S.h_use, S.h_arp, S.h_acol};
         for (void* q : host) if (q) (void)hipHostFree(q);
     }
     for (OutBlock& b : p->blocks) {
         if (b.idx) (void)hipHostFree(b.idx);
         if (b.score) (void)hipHostFree(b.score);
+        if (b.rec) (void)hipHostFree(b.rec);
     }
+    if (p->d_disc) (void)hipFree(p->d_disc);
     delete p;
     return DAE_OK;
 }
@@ -658,10 +688,23 @@ int dae_pipeline_flush(dae_pipeline* p)
 }
 
 static int submit_impl(dae_pipeline* p, const int64_t* positions, const float* values, int values_broadcast, int64_t nnz,
-                       int n_rows, const int32_t* titles, const float* titles_use, uint64_t* ticket_out)
+                       int n_rows, const int32_t* titles, const float* titles_use, const int32_t* ans_rp, const int32_t* ans_col,
+                       uint64_t* ticket_out)
 {
     if (!p) return DAE_ERR_ARG;
     const int titled = titles != nullptr ? 1 : 0;
+    // (p->eval is set once, before the first submit, by the caller's own thread)
+    if (p->eval != (ans_rp != nullptr))
+        return pfail(p, DAE_ERR_STATE, p->eval ? "dae_pipeline: an evaluation pipeline takes dae_pipeline_submit_eval only"
+                                               : "dae_pipeline_submit_eval: dae_pipeline_enable_eval was not called");
+    int64_t n_ans = 0;
+    if (ans_rp && n_rows >= 1) {
+        for (int r = 0; r < n_rows; ++r)
+            if (ans_rp[r + 1] < ans_rp[r]) return pfail(p, DAE_ERR_ARG, "dae_pipeline_submit_eval: ans_row_ptr decreases");
+        n_ans = (int64_t)ans_rp[n_rows] - ans_rp[0];
+        if (n_ans > p->max_answers || (n_ans > 0 && !ans_col))
+            return pfail(p, DAE_ERR_ARG, "dae_pipeline_submit_eval: a feed's answers must fit one launch (max_answers)");
+    }
     if (n_rows < 1 || n_rows > p->group_rows || nnz < 0 || nnz > p->max_nnz || (nnz > 0 && (!positions || !values)))
         return pfail(p, DAE_ERR_ARG, "dae_pipeline_submit: a feed must fit one launch (rows <= group_rows, nnz <= max_nnz)");
     const auto t_sub = std::chrono::steady_clock::now();
@@ -677,7 +720,7 @@ static int submit_impl(dae_pipeline* p, const int64_t* positions, const float* v
     if (p->open_slot >= 0) {
         Slot& O = p->slots[p->open_slot];
         // (a launch ranks EITHER the plain logits or the title-mixed score: feeds of the other kind start a new one)
-        if (O.rows + n_rows > p->group_rows || O.nnz + nnz > p->max_nnz || O.titled != titled) {
+        if (O.rows + n_rows > p->group_rows || O.nnz + nnz > p->max_nnz || O.titled != titled || O.n_ans + n_ans > p->max_answers) {
             const int rc = close_open(p);
             if (rc) return rc;
         }
@@ -689,14 +732,14 @@ static int submit_impl(dae_pipeline* p, const int64_t* positions, const float* v
                                                            "yet (poll before submitting more)");
         p->open_slot = p->next_slot;
         p->next_slot = (p->next_slot + 1) % (int)p->slots.size();
-        N.state = 1; N.rows = 0; N.nnz = 0; N.feeds.clear(); N.next_feed = 0; N.titled = titled;
+        N.state = 1; N.rows = 0; N.nnz = 0; N.n_ans = 0; N.feeds.clear(); N.next_feed = 0; N.titled = titled;
     }
     Slot& S = p->slots[p->open_slot];
     const int row0 = S.rows;
-    const int64_t off = S.nnz;
+    const int64_t off = S.nnz, aoff = S.n_ans;
     const uint64_t ticket = p->next_ticket++;
     S.feeds.push_back(Feed{ticket, row0, n_rows});
-    S.rows += n_rows; S.nnz += nnz;
+    S.rows += n_rows; S.nnz += nnz; S.n_ans += n_ans;
     lk.unlock();                                            // the copy runs outside the lock (the worker never touches an open slot)
     if (titled) {
         int64_t* dp = S.h_pos + 2 * off;
@@ -719,7 +762,7 @@ static int submit_impl(dae_pipeline* p, const int64_t* positions, const float* v
         }
         if (bad) {                                           // nothing of this feed stays: the slot is as it was before the call
             lk.lock();
-            S.feeds.pop_back(); S.rows -= n_rows; S.nnz -= nnz; --p->next_ticket;
+            S.feeds.pop_back(); S.rows -= n_rows; S.nnz -= nnz; S.n_ans -= n_ans; --p->next_ticket;
             if (S.feeds.empty()) { S.state = 0; p->next_slot = p->open_slot; p->open_slot = -1; }      // (it had opened the slot)
             return pfail(p, DAE_ERR_ARG, "dae_pipeline_submit: a row index of the feed is outside [0, n_rows)");
         }
@@ -731,6 +774,12 @@ static int submit_impl(dae_pipeline* p, const int64_t* positions, const float* v
         memcpy(S.h_titles + (size_t)row0 * p->tw.L, titles, (size_t)n_rows * p->tw.L * sizeof(int32_t));
         memcpy(S.h_use + row0, titles_use, (size_t)n_rows * sizeof(float));
     }
+    if (ans_rp) {                                            // the feed's answers behind the launch's, offsets in the launch's CSR
+        const int32_t base = ans_rp[0];
+        if (row0 == 0) S.h_arp[0] = 0;
+        for (int r = 0; r < n_rows; ++r) S.h_arp[row0 + r + 1] = (int32_t)(aoff + (ans_rp[r + 1] - base));
+        if (n_ans > 0) memcpy(S.h_acol + aoff, ans_col + base, (size_t)n_ans * sizeof(int32_t));
+    }
     if (ticket_out) *ticket_out = ticket;
     lk.lock();
     if (S.rows + n_rows > p->group_rows) (void)close_open(p);   // the next feed of this size would not fit: off it goes
@@ -741,7 +790,7 @@ static int submit_impl(dae_pipeline* p, const int64_t* positions, const float* v
 int dae_pipeline_submit(dae_pipeline* p, const int64_t* positions, const float* values, int values_broadcast, int64_t nnz,
                         int n_rows, uint64_t* ticket_out)
 {
-    return submit_impl(p, positions, values, values_broadcast, nnz, n_rows, nullptr, nullptr, ticket_out);
+    return submit_impl(p, positions, values, values_broadcast, nnz, n_rows, nullptr, nullptr, nullptr, nullptr, ticket_out);
 }
 
 int dae_pipeline_submit_titled(dae_pipeline* p, const int64_t* positions, const float* values, int values_broadcast, int64_t nnz,
@@ -750,16 +799,63 @@ int dae_pipeline_submit_titled(dae_pipeline* p, const int64_t* positions, const 
     if (!p) return DAE_ERR_ARG;
     if (!p->has_title) return pfail(p, DAE_ERR_STATE, "dae_pipeline_submit_titled: not a titled pipeline (dae_pipeline_create_titled)");
     if (!titles || !titles_use) return pfail(p, DAE_ERR_ARG, "null pointer");
-    return submit_impl(p, positions, values, values_broadcast, nnz, n_rows, titles, titles_use, ticket_out);
+    return submit_impl(p, positions, values, values_broadcast, nnz, n_rows, titles, titles_use, nullptr, nullptr, ticket_out);
 }
 
-int dae_pipeline_poll(dae_pipeline* p, int wait, uint64_t* ticket, const int32_t** idx, const float** score, int* n_rows,
-                      int* block)
+int dae_pipeline_submit_eval(dae_pipeline* p, const int64_t* positions, const float* values, int values_broadcast, int64_t nnz,
+                             int n_rows, const int32_t* titles, const float* titles_use, const int32_t* ans_row_ptr,
+                             const int32_t* ans_col, uint64_t* ticket_out)
 {
     if (!p) return DAE_ERR_ARG;
-    if (!idx || !n_rows || !block) return pfail(p, DAE_ERR_ARG, "null pointer");
+    if (!ans_row_ptr) return pfail(p, DAE_ERR_ARG, "null pointer");
+    if ((titles != nullptr) != (titles_use != nullptr)) return pfail(p, DAE_ERR_ARG, "titles and titles_use come together");
+    if (titles && !p->has_title) return pfail(p, DAE_ERR_STATE, "dae_pipeline_submit_eval: not a titled pipeline (dae_pipeline_create_titled)");
+    return submit_impl(p, positions, values, values_broadcast, nnz, n_rows, titles, titles_use, ans_row_ptr, ans_col, ticket_out);
+}
+
+// Before the first submit: the discount table on the device, the answers' staging and the records' blocks; the lists' pinned
+// blocks go back (nothing will be copied into them).
+int dae_pipeline_enable_eval(dae_pipeline* p, const double* disc_host, int64_t max_answers)
+{
+    if (!p) return DAE_ERR_ARG;
+    if (!disc_host || max_answers < 1 || max_answers >= ((int64_t)1 << 31))
+        return pfail(p, DAE_ERR_ARG, "dae_pipeline_enable_eval: needs a discount table and 1 <= max_answers < 2^31");
     std::unique_lock<std::mutex> lk(p->mu);
-    *n_rows = 0; *idx = nullptr; *block = -1;
+    if (p->err_code) return p->err_code;
+    if (p->eval || p->next_ticket != 1) return pfail(p, DAE_ERR_STATE, "dae_pipeline_enable_eval: once, before the first submit");
+    DeviceGuard dev_guard(p->device);
+    const size_t rows = (size_t)p->group_rows, na = (size_t)max_answers;
+    bool ok = hipMalloc(reinterpret_cast<void**>(&p->d_disc), (size_t)p->k * sizeof(double)) == hipSuccess &&
+              hipMemcpy(p->d_disc, disc_host, (size_t)p->k * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+    for (Slot& S : p->slots)
+        ok = ok && hipHostMalloc(reinterpret_cast<void**>(&S.h_arp), (rows + 1) * sizeof(int32_t)) == hipSuccess &&
+             hipHostMalloc(reinterpret_cast<void**>(&S.h_acol), na * sizeof(int32_t)) == hipSuccess &&
+             hipMalloc(reinterpret_cast<void**>(&S.d_arp), (rows + 1) * sizeof(int32_t)) == hipSuccess &&
+             hipMalloc(reinterpret_cast<void**>(&S.d_acol), na * sizeof(int32_t)) == hipSuccess &&
+             hipMalloc(reinterpret_cast<void**>(&S.d_rec), rows * sizeof(dae_metric_rec)) == hipSuccess;
+    for (OutBlock& b : p->blocks) {
+        ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b.rec), rows * sizeof(dae_metric_rec)) == hipSuccess;
+        if (b.idx) { (void)hipHostFree(b.idx); b.idx = nullptr; }
+        if (b.score) { (void)hipHostFree(b.score); b.score = nullptr; }
+    }
+    if (!ok) return pfatal(p, DAE_ERR_NOMEM, "dae_pipeline_enable_eval: allocation failed");
+    p->max_answers = max_answers;
+    p->eval = true;
+    return DAE_OK;
+}
+
+static int poll_impl(dae_pipeline* p, int wait, uint64_t* ticket, const int32_t** idx, const float** score,
+                     const dae_metric_rec** rec, int* n_rows, int* block)
+{
+    if (!p) return DAE_ERR_ARG;
+    if ((!idx && !rec) || !n_rows || !block) return pfail(p, DAE_ERR_ARG, "null pointer");
+    if (p->eval != (rec != nullptr))
+        return pfail(p, DAE_ERR_STATE, p->eval ? "dae_pipeline: an evaluation pipeline hands out records (dae_pipeline_poll_eval)"
+                                               : "dae_pipeline_poll_eval: dae_pipeline_enable_eval was not called");
+    std::unique_lock<std::mutex> lk(p->mu);
+    *n_rows = 0; *block = -1;
+    if (idx) *idx = nullptr;
+    if (rec) *rec = nullptr;
     if (score) *score = nullptr;
     Slot& S = p->slots[p->poll_slot];
     if (S.state == 0) return p->err_code;                    // nothing pending (0 rows), or the worker's error
@@ -846,8 +942,12 @@ int dae_pipeline_poll(dae_pipeline* p, int wait, uint64_t* ticket, const int32_t
     const Feed& f = S.feeds[S.next_feed];
     OutBlock& ob = p->blocks[S.block];
     if (ticket) *ticket = f.ticket;
-    *idx = ob.idx + (size_t)f.row0 * p->k;
-    if (score) *score = p->want_scores ? ob.score + (size_t)f.row0 * p->k : nullptr;
+    if (rec) {
+        *rec = ob.rec + f.row0;
+    } else {
+        *idx = ob.idx + (size_t)f.row0 * p->k;
+        if (score) *score = p->want_scores ? ob.score + (size_t)f.row0 * p->k : nullptr;
+    }
     *n_rows = f.n_rows;
     *block = S.block;
     ++ob.refs;                                               // the caller's reference to the block (dae_pipeline_release)
@@ -857,6 +957,19 @@ int dae_pipeline_poll(dae_pipeline* p, int wait, uint64_t* ticket, const int32_t
         p->poll_slot = (p->poll_slot + 1) % (int)p->slots.size();
     }
     return DAE_OK;
+}
+
+int dae_pipeline_poll(dae_pipeline* p, int wait, uint64_t* ticket, const int32_t** idx, const float** score, int* n_rows,
+                      int* block)
+{
+    if (p && !idx) return pfail(p, DAE_ERR_ARG, "null pointer");
+    return poll_impl(p, wait, ticket, idx, score, nullptr, n_rows, block);
+}
+
+int dae_pipeline_poll_eval(dae_pipeline* p, int wait, uint64_t* ticket, const dae_metric_rec** rec, int* n_rows, int* block)
+{
+    if (p && !rec) return pfail(p, DAE_ERR_ARG, "null pointer");
+    return poll_impl(p, wait, ticket, nullptr, nullptr, rec, n_rows, block);
 }
 
 int dae_pipeline_release(dae_pipeline* p, int block)

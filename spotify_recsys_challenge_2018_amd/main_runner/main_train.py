@@ -28,10 +28,12 @@ def log_write(conf, log):
         print(log)
 
 
-def eval(reader_test, conf, model):
+def eval(reader_test, conf, model, extra=None):
     """Mean r-precision over one test split (main_train.py:48-100): seed tracks only, both
-    keep-probs 1.0, rank the track columns, drop the seeds, top 500."""
+    keep-probs 1.0, rank the track columns, drop the seeds, top 500.  `extra`: a dict that receives the split's mean
+    'ndcg' and 'clicks' (utils/metrics.py get_ndcg / get_rsc) as well -- [BASE] eval_metrics = all."""
     total, count = 0.0, len(reader_test.playlists)
+    ndcg, clicks = 0.0, 0
     answers = []
 
     def feeds():
@@ -41,6 +43,31 @@ def eval(reader_test, conf, model):
             yield x_positions, x_ones, test_seed, titles
             if reader_test.test_idx == 0:
                 break
+
+    if hasattr(model, 'evaluate_iter'):
+        # the rows' metrics on the device (models/DAEs.py evaluate_iter): 24 bytes a row come back instead of 500 indices, and
+        # what this thread adds up, row by row in the reader's order, are the same Python floats eval_topk returns
+        from ..models.DAEs import SEEDS_FROM_INPUT
+        pad = [-1] * conf.strmaxlen if conf.mode == 'title' else None
+
+        def pairs():
+            for x_positions, x_ones, test_seed, titles in feeds():
+                if conf.mode == 'title':                           # (titles_use as in results() below)
+                    use = np.array([0.0 if t is None else 1.0 for t in titles], np.float32)
+                    feed = (x_positions, x_ones, SEEDS_FROM_INPUT, len(test_seed), [t if t is not None else pad for t in titles], use)
+                else:
+                    feed = (x_positions, x_ones, SEEDS_FROM_INPUT, len(test_seed))
+                yield feed, answers.pop()
+        for rec in model.evaluate_iter(pairs(), k=500):
+            for r in met.finish_r_precision_rows(rec):
+                total += r
+            if extra is not None:
+                for r in met.finish_ndcg_rows(rec):
+                    ndcg += r
+                clicks += sum(met.finish_rsc_rows(rec))
+        if extra is not None:
+            extra['ndcg'], extra['clicks'] = ndcg / max(count, 1), clicks / max(count, 1)
+        return total / max(count, 1)
 
     def results():
         if conf.mode == 'title':                                   # main_train.py:69-79: titles_use = 1 everywhere
@@ -71,22 +98,46 @@ def eval(reader_test, conf, model):
     for b_no, idx in enumerate(results()):
         for i in range(len(idx)):
             total += met.eval_topk(idx[i], answers[b_no][i])
+        if extra is not None:
+            for rec in met.rank_records(idx, answers[b_no]):
+                ndcg += met.finish_ndcg(rec)
+                clicks += met.finish_rsc(rec)
+    if extra is not None:
+        extra['ndcg'], extra['clicks'] = ndcg / max(count, 1), clicks / max(count, 1)
     return total / max(count, 1)
 
 
-def _eval_splits(readers_test, conf, model, rank, world):
-    """r-precision of every test split.  Under torch.distributed.run the splits are dealt round-robin to the ranks
+def _eval_splits(readers_test, conf, model, rank, world, extras=None):
+    """r-precision of every test split (`extras`: a dict that receives split -> (ndcg, clicks) as well).  Under torch.distributed.run the splits are dealt round-robin to the ranks
     (every rank holds a full, freshly synchronised replica for inference) and the values meet in one all-reduce, so
     the evaluation of an epoch costs 1/world of what every-rank-evaluates-everything did."""
     names = list(readers_test)
-    vals = [eval(readers_test[n], conf, model) if i % world == rank else 0.0 for i, n in enumerate(names)]
+    if extras is None:
+        vals = [eval(readers_test[n], conf, model) if i % world == rank else 0.0 for i, n in enumerate(names)]
+    else:                                                            # three values per split
+        vals = []
+        for i, n in enumerate(names):
+            ex = {'ndcg': 0.0, 'clicks': 0.0}
+            vals.append([eval(readers_test[n], conf, model, ex) if i % world == rank else 0.0, ex['ndcg'], ex['clicks']])
     if world > 1 and names:
         import torch
         import torch.distributed as dist
         t = torch.tensor(vals, dtype=torch.float64, device=torch.device("cuda", conf.device_index))
         dist.all_reduce(t)
         vals = t.tolist()
+    if extras is not None:
+        extras.update((n, (v[1], v[2])) for n, v in zip(names, vals))
+        vals = [v[0] for v in vals]
     return dict(zip(names, vals))
+
+
+def _log_splits(conf, readers_test, rprecs, extras):
+    """The reference's line per split; with [BASE] eval_metrics = all two more (NDCG, recommended-songs clicks)."""
+    for seed_num in readers_test:
+        log_write(conf, "seed num: %s rprecision: %f" % (seed_num, rprecs[seed_num]))
+        if extras is not None:
+            log_write(conf, "seed num: %s ndcg: %f" % (seed_num, extras[seed_num][0]))
+            log_write(conf, "seed num: %s clicks: %f" % (seed_num, extras[seed_num][1]))
 
 
 def _init_distributed(conf):
@@ -153,9 +204,9 @@ def run(conf, only_testmode):
 
     if only_testmode:                                               # main_train.py:181-191
         log_write(conf, '<<only test mode>>')
-        out = _eval_splits(readers_test, conf, model, rank, world)
-        for seed_num in readers_test:
-            log_write(conf, "seed num: %s rprecision: %f" % (seed_num, out[seed_num]))
+        extras = {} if getattr(conf, 'eval_metrics', 'rprecision') == 'all' else None
+        out = _eval_splits(readers_test, conf, model, rank, world, extras)
+        _log_splits(conf, readers_test, out, extras)
         return out
 
     epoch, it, loss, max_eval = 0, 0, 0.0, 0.0
@@ -190,9 +241,10 @@ def run(conf, only_testmode):
             log_write(conf, "training loss: " + str(loss / it))
             cur_eval = 0.0
             model.sync_params()            # collective when sharded: every rank refreshes its replica first
-            rprecs = _eval_splits(readers_test, conf, model, rank, world)
+            extras = {} if getattr(conf, 'eval_metrics', 'rprecision') == 'all' else None
+            rprecs = _eval_splits(readers_test, conf, model, rank, world, extras)
+            _log_splits(conf, readers_test, rprecs, extras)
             for seed_num in readers_test:
-                log_write(conf, "seed num: %s rprecision: %f" % (seed_num, rprecs[seed_num]))
                 if seed_num in conf.update_seed:
                     cur_eval += rprecs[seed_num]
             history.append((epoch, loss / it, cur_eval))

@@ -577,6 +577,29 @@ class DAE_tied:
             idx, score = self.recommend(x_positions, x_ones, seeds, k=k, n_rows=n_rows, dtype=dtype, **self._feed_title_kw(f))
             yield idx, (score if want_scores else None)
 
+    def evaluate_iter(self, feeds, k=500, dtype=None):
+        """The evaluation loop (main_train.py:48-100) with the metrics computed on the device: `feeds` yields
+        (feed, answers) -- `feed` what `recommend_iter` takes, `answers` one id list per row of the feed (the reader's
+        `test_answer`: ints, -1 and duplicates allowed) -- and the generator yields, per feed and in order, the rows' records
+        (a numpy array of utils/metrics.py RECORD_DTYPE: hits_r, first, m, n_answer, dcg; `finish_*` there turn a record into
+        r-precision, NDCG and clicks, bit for bit what get_r_precision / get_ndcg / get_rsc return for the row's list).
+        Where `recommend_iter` runs on the library's pipeline, this does too, in its evaluation mode: the
+        answers go up with the feed, dae_rank_metrics runs behind the scoring call and 24 bytes a row come back instead of
+        the row's k indices.  Every other case (a vocabulary-sharded model, device_csr = False, explicit seed lists, a feed
+        or its answers larger than a launch slot) goes feed by feed through `recommend` and `metrics.rank_records`."""
+        titled_native = (getattr(self, "title_model", None) is not None and getattr(self.title_model, "ctx", None) is not None
+                         and type(self)._submit is DAE_title._submit)
+        if self._score_shard is None and self.device_csr and (type(self)._submit is DAE._submit or titled_native):
+            dtype = self._dtype_of(dtype)
+            yield from self._recommend_iter_native(feeds, k, _title_dtype(dtype, self) if titled_native else dtype, False,
+                                                   eval_mode=True)
+            return
+        from ..utils.metrics import rank_records
+        for f, answers in feeds:
+            x_positions, x_ones, seeds, n_rows = f[:4]
+            idx, _score = self.recommend(x_positions, x_ones, seeds, k=k, n_rows=n_rows, dtype=dtype, **self._feed_title_kw(f))
+            yield rank_records(idx, answers)
+
     def _feed_title_kw(self, f):
         """The title arguments of a 5- or 6-item feed, for `recommend`: only a DAE_title takes them; a plain DAE scores the
         feed's first four items and ignores the rest."""
@@ -584,12 +607,16 @@ class DAE_tied:
             return {}
         return {"titles": f[4], "titles_use": f[5] if len(f) > 5 else None}
 
-    def _native_pipe(self, dtype, k, want_scores):
-        """The model's dae_pipeline for (dtype, k, scores wanted): created on first use, again after the weights changed."""
+    def _pipe_key(self, dtype, k, want_scores, eval_mode=False):
+        return (int(dtype), int(k), bool(want_scores), self.n_batch) + (("eval",) if eval_mode else ())
+
+    def _native_pipe(self, dtype, k, want_scores, eval_mode=False):
+        """The model's dae_pipeline for (dtype, k, scores wanted, evaluation mode): created on first use, again after the
+        weights changed."""
         tm = getattr(self, "title_model", None)
         if tm is not None and getattr(tm, "ctx", None) is None:
             tm = None
-        key = (int(dtype), int(k), bool(want_scores), self.n_batch)
+        key = self._pipe_key(dtype, k, want_scores, eval_mode)
         # (dae_set_exact_margin on the model's contexts -- the guard's test hook -- reaches the pipeline's own images as well)
         margins = [getattr(c, "_exact_margin", 1.0) for c in ([self.ctx] + ([] if tm is None else [tm.ctx]))]
         margin = next((m_ for m_ in margins if m_ != 1.0), 1.0)
@@ -626,12 +653,21 @@ class DAE_tied:
                                  device_index=self.device_index, title=tm)
             if margin != 1.0 and dtype == _lib.DAE_DTYPE_BF16_EXACT:
                 pipe.exact_margin(margin)
+            if eval_mode:            # (the challenge's playlists hold at most 250 tracks; a feed with more answers than a launch
+                pipe.enable_eval(max_answers=max(1 << 16, group * 256))      # slot takes goes through `recommend`)
             ent = cache[key] = (gen, pipe)
         return ent[1]
 
-    def _recommend_iter_native(self, feeds, k, dtype, want_scores):
-        pipe = self._native_pipe(dtype, k, want_scores)
-        key = (int(dtype), int(k), bool(want_scores), self.n_batch)
+    def _recommend_iter_native(self, feeds, k, dtype, want_scores, eval_mode=False):
+        """`recommend_iter` on the library's pipeline; eval_mode: `evaluate_iter` on the same loop -- feeds are (feed, answers)
+        pairs and what comes out per feed are the rows' metric records."""
+        pipe = self._native_pipe(dtype, k, want_scores, eval_mode)
+        key = self._pipe_key(dtype, k, want_scores, eval_mode)
+        poll = pipe.poll
+        if eval_mode:
+            from itertools import chain
+            from ..utils.metrics import rank_records
+            poll = pipe.poll_eval
 
         from collections import deque
         rows_out = deque()           # rows each pending feed asked for (a feed is fed as the graph's n_batch rows, DAEs.py:34)
@@ -643,6 +679,8 @@ class DAE_tied:
 
         def out(r):
             n = rows_out.popleft()
+            if eval_mode:
+                return r if n == nb_full else r[:n]
             if n == nb_full:
                 return r[0], (r[1] if want_scores else None)
             return r[0][:n], (r[1][:n] if want_scores else None)
@@ -651,6 +689,8 @@ class DAE_tied:
         pipe._users = getattr(pipe, "_users", 0) + 1             # (_native_pipe never closes a pipeline a loop is running on)
         try:
             for f in feeds:
+                if eval_mode:
+                    f, answers = f
                 x_positions, x_ones, seeds, n_rows = f[:4]
                 n = self.n_batch if n_rows is None else int(n_rows)
                 titles = use = None
@@ -671,27 +711,39 @@ class DAE_tied:
                 if not unfit:                                    # a feed larger than a launch slot: through recommend(), not a DaeError
                     nnz_f = int(np.shape(x_positions)[0]) if np.ndim(x_positions) == 2 else len(x_positions)
                     unfit = nnz_f > pipe.max_nnz
+                if eval_mode:                                    # the answers as a CSR over the launch's n_batch rows
+                    if len(answers) != n:
+                        raise ValueError("evaluate_iter: %d answer lists for a feed of %d rows" % (len(answers), n))
+                    if n <= self.n_batch and not unfit:
+                        arp = np.zeros(self.n_batch + 1, np.int32)
+                        np.cumsum(np.fromiter(map(len, answers), np.int64, n), out=arp[1:n + 1])
+                        arp[n + 1:] = arp[n]
+                        unfit = int(arp[-1]) > pipe.max_answers
                 if not (isinstance(seeds, str) and seeds == SEEDS_FROM_INPUT) or unfit or n > self.n_batch:
                     pipe.flush()                                 # a feed the pipeline does not take: in order, through recommend()
                     while pipe.pending:
-                        yield out(pipe.poll(True))
+                        yield out(poll(True))
                     idx, score = self.recommend(x_positions, x_ones, seeds, k=k, n_rows=n_rows, dtype=dtype,
                                                 **self._feed_title_kw(f))
-                    yield idx, (score if want_scores else None)
+                    yield rank_records(idx, answers) if eval_mode else (idx, (score if want_scores else None))
                     continue
-                while not pipe.submit(x_positions, x_ones, self.n_batch, titles, use):      # every lane full: hand the oldest lists out first
-                    yield out(pipe.poll(True))
+                if eval_mode:
+                    ans = (arp, np.fromiter(chain.from_iterable(answers), np.int32, int(arp[-1])))
+                # (every lane full: hand the oldest lists out first)
+                while not (pipe.submit_eval(x_positions, x_ones, self.n_batch, ans, titles, use) if eval_mode
+                           else pipe.submit(x_positions, x_ones, self.n_batch, titles, use)):
+                    yield out(poll(True))
                 rows_out.append(n)
                 n_fed += 1
                 if n_fed % per_launch == 0 or titles is not None:
                     while True:                                  # ... and whatever else is ready, without waiting
-                        r = pipe.poll(False)
+                        r = poll(False)
                         if r is None:
                             break
                         yield out(r)
             pipe.flush()
             while pipe.pending:
-                yield out(pipe.poll(True))
+                yield out(poll(True))
             clean = True
         except _lib.DaeError as e:
             if "out of range" in str(e) or "outside" in str(e):

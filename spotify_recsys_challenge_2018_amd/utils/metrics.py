@@ -86,3 +86,81 @@ def eval_topk(cand_idx, answer):
     """r-precision of an already ranked candidate row (output of model.recommend)."""
     cand = [int(i) for i in cand_idx if i >= 0]
     return get_r_precision(answer, cand)
+
+
+# ---- the three metrics as a per-row RECORD (what dae_rank_metrics leaves on the device, include/dae_hip.h) ----------------
+#
+# {hits_r, first, m, n_answer, dcg}: counts and one float64 sum of additions; the divisions are done here, in Python, so the
+# floats are the functions' above bit for bit (tests/test_metrics_cpu.py, tests/test_gpu_metrics.py).
+
+RECORD_DTYPE = np.dtype([("hits_r", np.int32), ("first", np.int32), ("m", np.int32), ("n_answer", np.int32),
+                         ("dcg", np.float64)])
+_disc, _idcg = [0.0], [1.0]          # disc[p] = 1 / math.log(p + 1, 2) (disc[0] is never used); idcg[m] = 1 + disc[1] + ... + disc[m]
+
+
+def discount_table(k):
+    """The first k discounts of get_ndcg, from Python's own math.log (the table the device kernel adds from)."""
+    while len(_disc) < max(int(k), 1):
+        p = len(_disc)
+        _disc.append(1.0 / math.log(p + 1, 2))
+        _idcg.append(_idcg[-1] + _disc[-1])
+    return np.array(_disc[:int(k)], np.float64)
+
+
+def rank_records(idx, answers):
+    """The records of the rows of `idx` [n, k] (ids, -1 = no candidate) against `answers` (n id lists) on the host: the
+    restatement of csrc/metrics.hip that `evaluate_iter` uses for the feeds the native loop does not take."""
+    idx = np.asarray(idx)
+    out = np.zeros(len(answers), RECORD_DTYPE)
+    discount_table(idx.shape[1] if idx.ndim == 2 and idx.shape[1] else 1)
+    for r, answer in enumerate(answers):
+        row = idx[r]
+        cand = row[row >= 0]
+        n = len(answer)
+        pos = np.flatnonzero(np.isin(cand, np.asarray(answer, np.int64))) if n else np.zeros(0, np.int64)
+        dcg = 0.0
+        for p in pos.tolist():                   # (float64 additions in ascending position, as get_ndcg adds them)
+            dcg = 1.0 if p == 0 else dcg + _disc[p]
+        out[r] = (int(np.count_nonzero(pos < n)), int(pos[0]) if pos.size else -1, int(np.count_nonzero(pos >= 1)), n, dcg)
+    return out
+
+
+def finish_r_precision(rec):
+    """get_r_precision of one record (an empty answer list raises, as it does there)."""
+    n = int(rec["n_answer"])
+    if n == 0:
+        raise ZeroDivisionError("empty answer list")
+    return int(rec["hits_r"]) / n
+
+
+def finish_ndcg(rec):
+    """get_ndcg of one record; 0.0 for a row without candidates (get_ndcg raises IndexError there)."""
+    m = int(rec["m"])
+    discount_table(m + 1)
+    return float(rec["dcg"]) / _idcg[m]
+
+
+def finish_rsc(rec):
+    """get_rsc of one record."""
+    first = int(rec["first"])
+    return first // 10 if first >= 0 else 51
+
+
+def finish_record(rec):
+    """-> (r-precision, NDCG, clicks) of one record."""
+    return finish_r_precision(rec), finish_ndcg(rec), finish_rsc(rec)
+
+
+def finish_r_precision_rows(rec):
+    """finish_r_precision of every record of an array, as a list of Python floats (the same int / int divisions)."""
+    return [h / n for h, n in zip(rec["hits_r"].tolist(), rec["n_answer"].tolist())]      # (n = 0: ZeroDivisionError)
+
+
+def finish_ndcg_rows(rec):
+    ms = rec["m"].tolist()
+    discount_table(max(ms, default=0) + 1)
+    return [d / _idcg[m] for d, m in zip(rec["dcg"].tolist(), ms)]
+
+
+def finish_rsc_rows(rec):
+    return [f // 10 if f >= 0 else 51 for f in rec["first"].tolist()]
