@@ -243,6 +243,50 @@ def grads(titles, params, filter_sizes, dae_score, y, w_title, w_playlist, n_bat
     return cost, g, dict(features=f0, argmax=arg, z=z, title_score=st, y_pred=yp, _aux=aux)
 
 
+def fp32_loss_head(z, dae, y, w_title, w_playlist, n_batch):
+    """title_loss_kernel's loss head as fp32 evaluates it, per element, as INTERVALS (the DAE head's treatment,
+    oracle/dae_numpy.py fp32_head, same window): where the mixed score yp = st w_t + dae w_p reaches 1 in fp32, 1 - yp is a
+    small integer multiple of 2^-24 (0 included), and st (1 - st) cancels the same way; grads()' float64 sees neither, and
+    title_grad_bounds' relative terms dyp / a0 grow past 1 there.
+        st  in dae_numpy's admissible fp32 sigmoid of z (p and 1 - p as intervals);
+        yp  = fl(fl(st w_t) + fl(dae w_p)), within 2 u of the exact mix of an admissible st (three roundings of
+              non-negative terms); for yp >= 0.5 it lies on the grid of spacing 2^-24, so q = fl(1 - yp) = m 2^-24 for the
+              integers m from floor((1 - yp_hi) / 2^-24) to ceil((1 - yp_lo) / 2^-24), m >= 0 (w_t + w_p <= 1 and both
+              scores <= 1 keep yp <= 1); below 0.5, q is within 2^-25 of 1 - yp;
+        L   = -[ y ln(yp + 1e-10) + 0.55 (1 - y) ln(q + 1e-10) ]
+        dz  = -( y / (yp + 1e-10) - 0.55 (1 - y) / (q + 1e-10) ) w_t st (1 - st) / n_batch
+    each factor monotone in its argument, so the ends of the arguments' intervals bound it; the hardware's log / division and
+    the remaining fp32 products get 2^-18 relative (as the DAE head) and L 2^-22 (|y| + 0.55 |1 - y|) absolute.  dae, w_t,
+    w_p: the fp32 values the kernel reads (no error of their own).  y in [0, 1].
+    Returns dict(L_lo, L_hi, dz_lo, dz_hi, zero): allowances included; zero = the mask of elements where q = 0 is admissible."""
+    from . import dae_numpy as dn
+    u, eps = U32, 1e-10
+    z = np.asarray(z, np.float64)
+    dae = np.asarray(dae, np.float64)
+    y = np.asarray(y, np.float64)
+    wt = np.asarray(w_title, np.float64).reshape(-1, 1)
+    wp = np.asarray(w_playlist, np.float64).reshape(-1, 1)
+    assert ((y >= 0) & (y <= 1)).all() and (wt + wp <= 1.0).all() and (dae <= 1.0).all()
+    s_lo, s_hi, c_lo, c_hi, _, _, _ = dn._head_pq(z)                       # st and 1 - st
+    yp_lo = (s_lo * wt + dae * wp) * (1 - 2 * u)
+    yp_hi = np.minimum((s_hi * wt + dae * wp) * (1 + 2 * u), 1.0)
+    grid = yp_lo >= 0.5
+    q_lo = np.where(grid, np.maximum(0.0, np.floor((1 - yp_hi) / u)) * u, np.maximum(1 - yp_hi - u / 2, 0.0))
+    q_hi = np.where(grid, np.ceil((1 - yp_lo) / u) * u, 1 - yp_lo + u / 2)
+    wy = np.abs(y) + 0.55 * np.abs(1 - y)
+    L_lo = -(y * np.log(yp_hi + eps) + 0.55 * (1 - y) * np.log(q_hi + eps))
+    L_hi = -(y * np.log(yp_lo + eps) + 0.55 * (1 - y) * np.log(q_lo + eps))
+    aL = 2.0 ** -18 * np.maximum(np.abs(L_lo), np.abs(L_hi)) + 2.0 ** -22 * wy
+    g1_lo, g1_hi = y / (yp_hi + eps), y / (yp_lo + eps)
+    g0_lo, g0_hi = 0.55 * (1 - y) / (q_hi + eps), 0.55 * (1 - y) / (q_lo + eps)
+    d_lo, d_hi = g1_lo - g0_hi, g1_hi - g0_lo                            # dL/dyp = -(d), d in [d_lo, d_hi]
+    S_lo, S_hi = s_lo * c_lo * wt / n_batch, s_hi * c_hi * wt / n_batch       # >= 0
+    cands = np.stack([d_lo * S_lo, d_lo * S_hi, d_hi * S_lo, d_hi * S_hi])
+    dz_lo, dz_hi = -cands.max(axis=0), -cands.min(axis=0)
+    adz = 2.0 ** -18 * np.maximum(np.abs(dz_lo), np.abs(dz_hi)) + 2.0 ** -126   # (below fp32's normal range: denormal or 0)
+    return dict(L_lo=L_lo - aL, L_hi=L_hi + aL, dz_lo=dz_lo - adz, dz_hi=dz_hi + adz, zero=grid & (q_lo == 0), yp_lo=yp_lo, yp_hi=yp_hi)
+
+
 def dae_logit_bounds(h, W_dec, b_dec):
     """Bound on |fp32 DAE logit - exact| for fp32 hidden activations h [B, H] known exactly (the encode kernel equals
     oracle.encode bit for bit): an fp32 sum of H products and the bias, (H + 2) u (sum_k |h W| + |b|)."""

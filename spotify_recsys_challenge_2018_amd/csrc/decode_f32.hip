@@ -748,11 +748,12 @@ __global__ __launch_bounds__(512, 1) void decode_loss_dh_bf16_kernel(const LossR
                 const bool live = row_in && tcol0 + 8 * qd + e < p.V;
                 loss_acc -= live ? (0.69314718f * 0.55f) * __builtin_amdgcn_logf(q + 1e-10f) : 0.0f;
                 q_min = fminf(q_min, live ? q : 1.0f);
-                // dL/dz = 0.55 y (1 - y) / (1 - y + 1e-10) (DAEs.py:98-99's negatives): the quotient is 1 to 2^-13 unless 1 - y < 1e-6
+                // dL/dz = 0.55 y (1 - y) / (1 - y + 1e-10) (DAEs.py:98-99's negatives): the quotient is 1 to 1e-10 / (1 - y), inside
+                // the 2^-18 the reference allows the hardware rcp and products, unless 1 - y < 2.7e-5
                 dzv[4 * qd + e] = live ? k1 * pr : 0.0f;
             }
         }
-        if (__builtin_expect(__ballot(q_min < 1e-6f) != 0ull, 0)) {   // (a logit above 13.8 somewhere in the wave: the exact form)
+        if (__builtin_expect(__ballot(q_min < 2.7e-5f) != 0ull, 0)) {   // (a logit above 10.5 somewhere in the wave: the exact form)
 #pragma unroll
             for (int qd = 0; qd < 4; ++qd)
 #pragma unroll
@@ -761,7 +762,7 @@ __global__ __launch_bounds__(512, 1) void decode_loss_dh_bf16_kernel(const LossR
                     const float pr = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * zz));
                     const float q = 1.0f - pr;
                     const bool live = row_in && tcol0 + 8 * qd + e < p.V;
-                    if (live && q < 1e-6f) dzv[4 * qd + e] = k1 * __builtin_amdgcn_rcpf(q + 1e-10f) * pr * q;
+                    if (live && q < 2.7e-5f) dzv[4 * qd + e] = k1 * __builtin_amdgcn_rcpf(q + 1e-10f) * pr * q;
                 }
         }
         unsigned pk[8];

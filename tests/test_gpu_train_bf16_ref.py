@@ -38,9 +38,38 @@ def _uniform(stream, rows, cols):
     return np.array([[l.orc_uniform(SEED, stream, int(r), int(c)) for c in cols] for r in rows], np.float32)
 
 
-def make_case(V, nt, H, B, tied=False, lam=0.0, ikp=1.0, kp=1.0, n_batch=None, yvals=False, long_rows=(), seed=6):
+def make_case(V, nt, H, B, tied=False, lam=0.0, ikp=1.0, kp=1.0, n_batch=None, yvals=False, long_rows=(), seed=6,
+              planted=(), spread=None, enc_scale=None, weights=None, feed=None):
+    """planted: (column, logit, kind) triples -- the decoder row of the column is zeroed (the encoder's too when tied) and
+    its bias set to the logit, so z = logit exactly in every row; kind "neg": no row has it as a target, "pos": y = 1 in
+    every third row, "mix": y = 0.5 / 2.0 in every fourth row and the next.  spread = (scale, n_pop): decoder rows times
+    scale * exp(N(0, 0.6)) per row and a positive bias on n_pop popular columns (a trained-like spread of logits);
+    enc_scale: W_enc and b_enc times it (hidden pre-activations far into the sigmoid's tails).  weights / feed: given
+    (W_enc, b_enc, W_dec, b_dec) and dense (x, y) instead of the synthetic ones."""
     W_enc, b_enc, W_dec, b_dec = make_weights(V, H, seed=4, bias="zipf", n_tracks=nt, tied=tied)
     b_enc = (np.random.default_rng(2).standard_normal(H) * 0.1).astype(np.float32)
+    if weights is not None:
+        W_enc, b_enc, W_dec, b_dec = (np.ascontiguousarray(w, np.float32) for w in weights)
+    if enc_scale is not None:
+        W_enc = (W_enc * np.float32(enc_scale)).astype(np.float32)
+        b_enc = (b_enc * np.float32(enc_scale)).astype(np.float32)
+        if tied:
+            W_dec = W_enc
+    if spread is not None:
+        assert not tied
+        rs = np.random.default_rng(seed + 7)
+        W_dec = (W_dec * (spread[0] * np.exp(rs.normal(0.0, 0.6, size=(V, 1))))).astype(np.float32)
+        b_dec = b_dec.copy()
+        pop = rs.choice(min(V, 200), spread[1], replace=False)
+        b_dec[pop] = rs.uniform(0.5, 4.0, size=spread[1]).astype(np.float32)
+    if planted:
+        W_dec = W_dec.copy()
+        b_dec = b_dec.copy()
+        if tied:
+            W_enc = W_dec
+        for col, logit, _ in planted:
+            W_dec[col] = 0.0
+            b_dec[col] = np.float32(logit)
     pos, ones, _ = make_playlists(B, nt, V - nt, seed=seed, seed_counts=(3, 9, 20))
     x = dn.sparse_to_dense(pos[pos[:, 1] < nt], ones[pos[:, 1] < nt], B, V)
     y = dn.sparse_to_dense(pos, np.ones(len(pos), np.float32), B, V)
@@ -55,7 +84,16 @@ def make_case(V, nt, H, B, tied=False, lam=0.0, ikp=1.0, kp=1.0, n_batch=None, y
         nz = np.argwhere(y[:, :V] != 0)
         y[nz[::3, 0], nz[::3, 1]] = 0.5
         y[nz[1::3, 0], nz[1::3, 1]] = 2.0
-    if B >= 6 and not long_rows:                           # the padded last batch: trailing rows empty in x, in y, in both
+    if feed is not None:
+        x, y = (np.array(a, np.float32) for a in feed)
+    for col, _, kind in planted:
+        y[:, col] = 0.0
+        if kind == "pos":
+            y[::3, col] = 1.0
+        elif kind == "mix":
+            y[::4, col] = 0.5
+            y[1::4, col] = 2.0
+    if B >= 6 and not long_rows and feed is None:          # the padded last batch: trailing rows empty in x, in y, in both
         x[B - 3] = 0.0
         y[B - 2] = 0.0
         x[B - 1] = 0.0
@@ -100,11 +138,32 @@ def reference(c, **kw):
                          hidden_keep_mask=c["hm"], kp=c["kp"], h=c["h"], **kw)
 
 
-def check_bf16(got, c, cost_rtol=1e-5, h_rel=0.0, witness=False):
-    ref = reference(c)
-    r = dn.bf16_check(got, ref, dn.bf16_bounds(ref, h_rel=h_rel))
+def saturation(bounds):
+    """How many elements of the case the reference puts in the saturated band (q = 1 - p of the float64 logit)."""
+    q = bounds["q64"]
+    return dict(n=int(q.size), q_lt_1e_4=int((q < 1e-4).sum()), q_lt_2p7e_5=int((q < 2.7e-5).sum()),
+                q_lt_1e_6=int((q < 1e-6).sum()), m0=int(bounds["zero"].sum()), wide=int(bounds["wide"].sum()))
+
+
+def check_cost(got, ref, bounds):
+    lo, hi = dn.cost_interval(ref, bounds)
+    print("cost %.9g in [%.9g, %.9g] (width %.3g of it)" % (got["cost"], lo, hi, (hi - lo) / abs(ref["cost"])))
+    assert np.isfinite(got["cost"]) and lo <= got["cost"] <= hi, (got["cost"], lo, hi)
+
+
+def check_bf16(got, c, cost_rtol=1e-5, h_rel=0.0, witness=False, head="f64"):
+    """head="fp32": the reference evaluates the loss head as fp32 does (dn.fp32_head), the bounds fold its intervals in and
+    the cost is checked against its interval; for cases whose logits saturate.  Returns the ratios (and ref, bounds)."""
+    ref = reference(c, head=head)
+    bounds = dn.bf16_bounds(ref, h_rel=h_rel)
+    r = dn.bf16_check(got, ref, bounds)
     print("bf16 error / bound:", {k: round(v, 4) for k, v in r.items()})
     assert all(np.isfinite(got[k]).all() for k in KEYS if ref[k] is not None)
+    if head == "fp32":
+        print("bf16 saturated band:", saturation(bounds))
+        assert max(r.values()) <= 1.0, r
+        check_cost(got, ref, bounds)
+        return r, ref, bounds
     assert max(r.values()) <= 1.0, r
     assert abs(got["cost"] - ref["cost"]) <= cost_rtol * abs(ref["cost"]), (got["cost"], ref["cost"])
     if witness:
@@ -118,8 +177,32 @@ def check_bf16(got, c, cost_rtol=1e-5, h_rel=0.0, witness=False):
     return r
 
 
-def check_f32(got, c):
+def check_f32(got, c, head="f64"):
+    """head="fp32": against dn.grads_f32 under dn.f32_bounds, element by element; an element no wide interval reaches
+    (a decoder column without one; any element when the case has none) may instead meet the fp32 tolerance below."""
     W_enc, b_enc, W_dec, b_dec = c["W"]
+    if head == "fp32":
+        ref = dn.grads_f32(c["x"], c["y"], W_enc, b_enc, W_enc if c["tied"] else W_dec, b_dec, n_batch=c["n_batch"],
+                           tied=c["tied"], h=c["h"], reg_lambda=c["lam"], input_keep_mask=c["im"], ikp=c["ikp"],
+                           hidden_keep_mask=c["hm"], kp=c["kp"])
+        bounds = dn.f32_bounds(ref)
+        r = dn.bf16_check(got, ref, bounds)
+        print("fp32 error / bound:", {k: round(v, 4) for k, v in r.items()})
+        print("fp32 saturated band:", saturation(bounds))
+        col_wide = bounds["wide"].any(axis=0)
+        for k in KEYS:
+            if ref[k] is None:
+                continue
+            assert np.isfinite(got[k]).all(), k
+            err = np.abs(got[k] - ref[k])
+            if k in ("gW_dec", "gb_dec") or (k == "gW_enc" and c["tied"]):
+                free = ~col_wide if k == "gb_dec" else np.broadcast_to(~col_wide[:, None], err.shape)
+            else:
+                free = np.full(err.shape, not col_wide.any())
+            ok = (err <= bounds[k]) | (free & (err <= 2e-7 + 2e-4 * np.abs(ref[k])))
+            assert ok.all(), (k, int((~ok).sum()), float((err / np.maximum(bounds[k], 1e-300))[~ok].max()))
+        check_cost(got, ref, bounds)
+        return r, ref, bounds
     ref = dn.grads(c["x"], c["y"], W_enc, b_enc, W_enc if c["tied"] else W_dec, b_dec, n_batch=c["n_batch"],
                    tied=c["tied"], reg_lambda=c["lam"], input_keep_mask=c["im"], ikp=c["ikp"],
                    hidden_keep_mask=c["hm"], kp=c["kp"])
@@ -176,14 +259,13 @@ def test_long_target_rows(H, B):
     check_f32(f32, c)
 
 
-@pytest.mark.parametrize("world", [2, 3])
-def test_long_target_rows_through_the_sharded_stages(world):
-    """The same rows through HipTrainStages (the shard boundaries cut every long row): concatenated gradients within the
-    bound; h comes from an all-reduced pre-activation there (not bit-exact), so h may round either way near a midpoint."""
+def run_sharded(c, world, check_rows=None):
+    """The bf16 step of case c (untied, no dropout, lambda 0) through HipTrainStages over `world` vocabulary shards on one
+    device: the concatenated gradients and the summed cost, as run_step returns them."""
     import torch
-    V, nt, H, B = 6000, 5000, 256, 80
-    c = make_case(V, nt, H, B, long_rows=LONG)
+    V, H, B = c["V"], c["H"], c["B"]
     W_enc, b_enc, W_dec, b_dec = c["W"]
+    nb = c["n_batch"]
     ctx = _lib.Context(0)
     ctx.set_train_dtype(_lib.DAE_DTYPE_BF16)
     st = HipTrainStages(ctx)
@@ -192,7 +274,8 @@ def test_long_target_rows_through_the_sharded_stages(world):
     be = _dev(b_enc)
     sh = []
     bounds = all_shard_bounds(V, world)
-    assert all(any(lo < col < hi for col in c["csr"][4][c["csr"][3][0]:c["csr"][3][1]]) for lo, hi in bounds)
+    if check_rows is not None:
+        check_rows(bounds)
     for lo, hi in bounds:
         d = dict(lo=lo, hi=hi, We=_dev(W_enc[lo:hi]), bd=_dev(b_dec[lo:hi]), Wd=_dev(W_dec[lo:hi]))
         d.update(gWe=torch.zeros((hi - lo, H), device="cuda"), gbd=torch.zeros(hi - lo, device="cuda"),
@@ -204,12 +287,12 @@ def test_long_target_rows_through_the_sharded_stages(world):
         st.encode(x, d["We"], d["lo"], d["hi"], 1.0, SEED, d["pre"])
     pre = sum(d["pre"] for d in sh)
     for d in sh:
-        st.decode(pre, be, y, d["We"], d["Wd"], d["bd"], d["lo"], d["hi"], B, False, 1.0, SEED, 0.0,
+        st.decode(pre, be, y, d["We"], d["Wd"], d["bd"], d["lo"], d["hi"], nb, False, 1.0, SEED, 0.0,
                   d["gWd"], d["gbd"], d["dh"], d["cost"])
     dh = sum(d["dh"] for d in sh)
     cost = float(sum(d["cost"] for d in sh).item())
     for d in sh:
-        st.decode(pre, be, y, d["We"], d["Wd"], d["bd"], d["lo"], d["hi"], B, False, 1.0, SEED, 0.0,
+        st.decode(pre, be, y, d["We"], d["Wd"], d["bd"], d["lo"], d["hi"], nb, False, 1.0, SEED, 0.0,
                   d["gWd"], d["gbd"], d["dh"], d["cost"])      # re-establish this shard's scratch
         st.finish(dh, x, d["We"], be, d["Wd"], d["bd"], d["lo"], d["hi"], False, 1.0, 1.0, SEED, 0.0,
                   d["gWe"], d["gbe"], d["gWd"], d["gbd"])
@@ -218,6 +301,19 @@ def test_long_target_rows_through_the_sharded_stages(world):
                gW_dec=torch.cat([d["gWd"] for d in sh]).cpu().numpy(), gb_dec=torch.cat([d["gbd"] for d in sh]).cpu().numpy(),
                cost=cost)
     ctx.close()
+    return got
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_long_target_rows_through_the_sharded_stages(world):
+    """The same rows through HipTrainStages (the shard boundaries cut every long row): concatenated gradients within the
+    bound; h comes from an all-reduced pre-activation there (not bit-exact), so h may round either way near a midpoint."""
+    V, nt, H, B = 6000, 5000, 256, 80
+    c = make_case(V, nt, H, B, long_rows=LONG)
+
+    def every_shard_cuts_row_0(bounds):
+        assert all(any(lo < col < hi for col in c["csr"][4][c["csr"][3][0]:c["csr"][3][1]]) for lo, hi in bounds)
+    got = run_sharded(c, world, check_rows=every_shard_cuts_row_0)
     check_bf16(got, c, h_rel=2.0 ** -20)
 
 
