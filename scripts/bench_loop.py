@@ -47,7 +47,7 @@ def main():
         for mode in modes:
             for nl in lanes:
                 m.n_lanes = nl or None
-                m.__dict__.pop("_pipes", None)
+                m.close_pipelines()
                 for _ in m.recommend_iter(feeds(40 if mode == "f32" else 120), k=500, want_scores=False, dtype=mode):
                     pass                                          # (~0.3 s: the device at its sustained state, as bench.py's prime phase)
                 torch.cuda.synchronize()

@@ -302,10 +302,6 @@ class Context:
             self._guard_seen = 0             # (the read reset the cumulative words: snapshots compare against zero again)
         return int(n.value), int(c.value)
 
-    def exact_guard_snapshot(self, words_out):
-        """The cumulative guard words after everything enqueued so far -> words_out (CUDA int32[2]), in stream order."""
-        self.check(self.lib.dae_exact_guard_snapshot(self.h, _ptr(words_out)))
-
     def guard_moved(self, n_bad):
         """A launch's snapshot against the previous one taken on this context: True when the count changed under it."""
         seen = getattr(self, "_guard_seen", 0)
@@ -318,12 +314,6 @@ class Context:
         self.check(self.lib.dae_exact_stats_read(self.h, a))
         rows = max(int(a[0]), 1)
         return {"rows": int(a[0]), "candidates_per_row": round(int(a[1]) / rows, 1), "recomputed_per_row": round(int(a[2]) / rows, 1)}
-
-    def exact_guard_words(self):
-        """Device address of the guard's two int32 words (for a fetch alongside the results)."""
-        p = ctypes.c_void_p()
-        self.check(self.lib.dae_exact_guard_words(self.h, ctypes.byref(p)))
-        return int(p.value)
 
     def decode_dense(self, h, out, apply_sigmoid=True, dtype=DAE_DTYPE_F32):
         B, H = h.shape
@@ -398,17 +388,6 @@ class Context:
         self.check(self.lib.dae_set_score_mix(self.h, _ptr(mixT), int(mixT.stride(0)) if mixT is not None else 0,
                                               int(mixT.shape[0]) if mixT is not None else 0, _ptr(w_title)))
 
-    def title_score_exact(self, dae_ctx, d_pos, d_val, n_rows, V, W_enc, b_enc, d_titles, tm, d_use, n_tracks, k, out_score, out_idx,
-                          guard_out, status):
-        """One titled launch of the streamed loop in one call (dae_title_score_exact); `tm`: the Char_CNN model object."""
-        nnz = int(d_pos.shape[0])
-        bcast = 1 if (d_val.numel() == 1 and nnz != 1) else 0
-        self.check(self.lib.dae_title_score_exact(
-            self.h, dae_ctx.h, _ptr(d_pos), _ptr(d_val), bcast, nnz, int(n_rows), int(V), _ptr(W_enc), _ptr(b_enc),
-            int(W_enc.shape[1]), _ptr(d_titles), tm.input_len, _ptr(tm.p["char_embedding"]), tm.char_size, tm.embedding,
-            _ptr(tm.p["conv_w"]), _ptr(tm.p["conv_b"]), tm._fs, len(tm.filter_sizes), tm.filter_num, tm.ld, _ptr(d_use),
-            int(n_tracks), int(k), _ptr(out_score), _ptr(out_idx), _ptr(guard_out), _ptr(status)))
-
     def mix_topk_exact(self, dae_ctx, feat, h, w_title, w_playlist, n_tracks, seed_row_ptr, seed_col, k, out_score, out_idx,
                        guard_out=None):
         """On the title scorer's context: top-k of the title mix, bit-identical to the fp32 path, both GEMMs on bf16
@@ -465,9 +444,6 @@ class Context:
         keys = ["R_TILE", "n_rg", "nb_rg", "S", "n_sample_tiles", "n_filter_tiles", "fused",
                 "n_tiles"]
         return dict(zip(keys, list(arr)))
-
-    def scratch_bytes(self):
-        return int(self.lib.dae_scratch_bytes(self.h))
 
 
 class _Block:
@@ -541,6 +517,7 @@ class Pipeline:
         self.h = h
         self.eval = False
         self.pending = 0                     # feeds submitted and not yet yielded
+        self.users = 0                       # streamed loops running on this pipeline (models/stream_loop.py)
         # the foreign calls' out-parameters, made once (a feed is ~25 us of this thread: five ctypes objects and their byref()
         # per poll were 3 us of it)
         self._t, self._n, self._b = ctypes.c_uint64(), ctypes.c_int(), ctypes.c_int()

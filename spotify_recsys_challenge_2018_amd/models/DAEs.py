@@ -22,25 +22,27 @@ import pickle
 import numpy as np
 
 from .. import _lib
+from . import stream_loop
+from .stream_loop import SEEDS_FROM_INPUT      # recommend(seeds=SEEDS_FROM_INPUT): the seeds are the input's track columns
 
 
 # [BASE] decode_dtype values -> the C ABI's decode arithmetic (include/dae_hip.h)
 _DECODE_DTYPES = {"f32": _lib.DAE_DTYPE_F32, "bf16": _lib.DAE_DTYPE_BF16, "exact_bf16": _lib.DAE_DTYPE_BF16_EXACT}
 
 
-def _title_dtype(dtype, model=None):
+def _title_dtype(dtype, model):
     """Arithmetic of a title-mixed launch.  exact_bf16 has its own two-GEMM path (dae_mix_topk_exact, csrc/mixexact.hip)
     built for the shipped shapes -- DAE hidden 256, title feature rows of 448; any other model runs its titled launches
     on the fp32 kernels (the lists exact_bf16 promises are the fp32 lists either way)."""
     if dtype != _lib.DAE_DTYPE_BF16_EXACT:
         return dtype
-    tm = getattr(model, "title_model", None)
-    if (tm is not None and model.n_hidden == 256 and tm.ld == 448 and not getattr(model, "title_exact_off", False)):
+    tm = model.title_model
+    if tm is not None and model.n_hidden == 256 and tm.ld == 448 and not model.title_exact_off:
         return dtype
-    if tm is not None and not getattr(model, "title_exact_off", False) and not model.__dict__.get("_title_fp32_said"):
+    if tm is not None and not model.title_exact_off and not model._title_fp32_said:
         # [DAE] hidden, [TITLE] filter_num / filter_size are free keys of the schema (main.py:46, :73-75): say ONCE that this
         # model's titled launches cost the fp32 kernels' time (about 6 x), instead of silently
-        model.__dict__["_title_fp32_said"] = True
+        model._title_fp32_said = True
         import sys
         print("[dae] decode_dtype = exact_bf16: the exact title mix is built for hidden = 256 and 448-wide title feature rows; "
               "this model has hidden = %d, %d-wide rows -- its titled launches run on the fp32 kernels (same lists, slower)"
@@ -64,9 +66,6 @@ class _Fetch:
 
     def __repr__(self):
         return "<fetch %s>" % self.name
-
-
-SEEDS_FROM_INPUT = "input"      # recommend(seeds=SEEDS_FROM_INPUT): the seeds are the track columns of the input feed
 
 
 def coo_to_csr(positions, values, n_rows, n_cols=None):
@@ -190,6 +189,12 @@ class DAE_tied:
         self._sharded = None          # sharding.ShardedTrainer when training is row-sharded over ranks
         self._params_stale = False
         self._score_shard = None      # shard_scoring(): this rank's vocabulary columns + the ShardedRanker
+        self._copy_stream = None      # _to_dev(side_stream=True): the training loop's upload stream
+        self._weights_gen = 0         # bumps with every change of the weights (a cached pipeline holds images of the old ones)
+        self._pipes = {}              # the streamed loop's pipelines (stream_loop.py): key -> (generation, _lib.Pipeline)
+        self.coalesce = self.n_lanes = None      # set from outside: feeds per launch, lanes (None: `_coalesce_count` / three)
+        self.keep_pipelines, self._old_pipes = False, []      # ... and (diagnosis) retired pipelines kept alive, here
+        self._guard_fallbacks = 0     # batches / launches re-scored in fp32 because the exact mode's bound guard fired
 
     # -- parameters ---------------------------------------------------------------------------------
     def _xavier(self, rng, shape):
@@ -246,7 +251,7 @@ class DAE_tied:
         dev = torch.device("cuda", self.device_index)
         if not side_stream:                  # calls that fetch their result anyway (recommend, predict, ...)
             return src.to(dev, dtype=dtype, non_blocking=False)
-        cs = self.__dict__.get("_copy_stream")
+        cs = self._copy_stream
         if cs is None:
             cs = self._copy_stream = torch.cuda.Stream(device=dev)
         cur = torch.cuda.current_stream(self.device_index)
@@ -265,7 +270,7 @@ class DAE_tied:
             raise ValueError("positions (%d) and values (%d) differ in length" % (pos.shape[0], vals.size))
         return pos, vals
 
-    def _upload_csr(self, positions, values, side_stream=False, ctx=None, n_rows=None):
+    def _upload_csr(self, positions, values, side_stream=False, n_rows=None):
         """The feed (COO in feed order, duplicates allowed) -> device CSR.  Default: upload the raw feed
         and build the CSR on the GPU (dae_coo_to_csr, csrc/csr.hip); `device_csr = False` keeps the numpy
         restatement `coo_to_csr` (same result entry for entry; it also range-checks eagerly)."""
@@ -274,7 +279,7 @@ class DAE_tied:
             pos, vals = self._feed_arrays(positions, values)
             d_pos = self._to_dev(pos if pos.shape[0] else np.zeros((1, 2), np.int64), torch.int64, side_stream)[:pos.shape[0]]
             d_val = self._to_dev(vals if vals.size else np.zeros(1, np.float32), torch.float32, side_stream)
-            rp, c, v, status = (ctx or self.ctx).coo_to_csr(d_pos, d_val, n_rows or self.n_batch, self.n_input)
+            rp, c, v, status = self.ctx.coo_to_csr(d_pos, d_val, n_rows or self.n_batch, self.n_input)
             # checked lazily (no sync on the scoring path).  A flag is written on the stream that is current NOW -- the
             # main stream or the second scoring lane's -- so it travels with an event recorded behind its writer: whoever
             # reads it later, on whichever stream, waits for exactly that
@@ -314,7 +319,7 @@ class DAE_tied:
         """The packed decoder images of the context(s) no longer hold the current weights."""
         self._packed_dirty = {_lib.DAE_DTYPE_F32: True, _lib.DAE_DTYPE_BF16: True, _lib.DAE_DTYPE_BF16_EXACT: True}
         self._packed_cols = {}
-        self._weights_gen = self.__dict__.get("_weights_gen", 0) + 1
+        self._weights_gen += 1
 
     # -- multi-GPU scoring (SURVEY.md 8e; BASELINE.json configs[2]): vocabulary columns sharded over the ranks ----
     def shard_scoring(self, rank, world, group=None, exchange="allgather", tau_exchange=True):
@@ -418,9 +423,6 @@ class DAE_tied:
                 self.ctx.prepack_decoder(self.weights["decoder_h"], self.biases["decoder_b"], cols[0], cols[1], dtype)
             self._packed_dirty[dtype] = False
             self._packed_cols[dtype] = cols
-            pg = self.__dict__.setdefault("_pack_gen", {})               # bumps whenever a slot of the context is re-tiled
-            slot = "f32" if dtype == _lib.DAE_DTYPE_F32 else "bf16"
-            pg[slot] = pg.get(slot, 0) + 1
             # "bf16" and "exact_bf16" share the context's bf16 image: the exact prepack serves both, a plain bf16
             # prepack drops the bounds the exact mode needs
             if dtype == _lib.DAE_DTYPE_BF16_EXACT:
@@ -461,7 +463,7 @@ class DAE_tied:
             return int(dtype)
         raise ValueError("decode dtype %r: one of %s" % (dtype, sorted(_DECODE_DTYPES)))
 
-    def _seed_csr_dev(self, seeds, csr, side_stream=False, ctx=None, n_rows=None):
+    def _seed_csr_dev(self, seeds, csr, n_rows=None):
         """Seed lists -> device CSR.  `seeds` is a list of per-row track-id lists (main_challenge.py:31-35), or
         SEEDS_FROM_INPUT: the seeds are the playlist's own tracks -- what both reference drivers pass -- and are cut
         out of the input CSR on the device (dae_seeds_from_csr): no per-row list handling, no uploads."""
@@ -469,29 +471,36 @@ class DAE_tied:
         if isinstance(seeds, str):
             if seeds != SEEDS_FROM_INPUT:
                 raise ValueError("seeds: a list of per-row id lists, or SEEDS_FROM_INPUT")
-            return (ctx or self.ctx).seeds_from_csr(csr[0], csr[1], self.n_tracks)
+            return self.ctx.seeds_from_csr(csr[0], csr[1], self.n_tracks)
         srp, sc = seeds_to_csr(seeds, n_rows or self.n_batch, self.n_tracks)
         if sc.size == 0:
             sc = np.zeros(1, np.int32)
-        return self._to_dev(srp, torch.int32, side_stream), self._to_dev(sc, torch.int32, side_stream)
+        return self._to_dev(srp, torch.int32), self._to_dev(sc, torch.int32)
 
-    def _submit(self, x_positions, x_ones, seeds, k, dtype, side_stream, titles=None, titles_use=None, ctx=None,
-                n_rows=None):
+    def _submit(self, x_positions, x_ones, seeds, k, dtype, n_rows=None):
         """Enqueue one batch of the fused scoring path on the current stream; nothing is fetched.
-        -> (score, idx, done event).  `ctx`: the library context to run on (default: the model's); `n_rows`: rows of
-        this launch when it is not the model's batch."""
+        -> (score, idx).  `n_rows`: rows of this launch when it is not the model's batch."""
         import torch
-        ctx = ctx or self.ctx
         nb = n_rows or self.n_batch
         dev = self.weights["encoder_h"].device
-        csr = self._upload_csr(x_positions, x_ones, side_stream=side_stream, ctx=ctx, n_rows=nb)
-        d_srp, d_sc = self._seed_csr_dev(seeds, csr, side_stream, ctx=ctx, n_rows=nb)
+        csr = self._upload_csr(x_positions, x_ones, n_rows=nb)
+        d_srp, d_sc = self._seed_csr_dev(seeds, csr, n_rows=nb)
         score = torch.empty((nb, k), dtype=torch.float32, device=dev)
         idx = torch.empty((nb, k), dtype=torch.int32, device=dev)
-        ctx.score_topk(csr[0], csr[1], csr[2], self.weights["encoder_h"], self.biases["encoder_b"],
-                       self.n_tracks, d_srp, d_sc, k, score, idx, dtype=dtype)
-        ev = torch.cuda.current_stream(self.device_index).record_event()
-        return score, idx, ev
+        self.ctx.score_topk(csr[0], csr[1], csr[2], self.weights["encoder_h"], self.biases["encoder_b"],
+                            self.n_tracks, d_srp, d_sc, k, score, idx, dtype=dtype)
+        return score, idx
+
+    def _title_scorer(self):
+        """The title scorer the launches of this model's pipeline mix in, or None.  (The pipeline computes what `_submit` does:
+        nothing in this repository overrides `_submit` without being a DAE_title, so every model may stream.)"""
+        return None
+
+    def _guard_fell_back(self, what, n=1):
+        """The bound guard fired and the caller (or the pipeline) re-scores in fp32: counted, and said once per event."""
+        import warnings
+        self._guard_fallbacks += n
+        warnings.warn(what, stacklevel=2)
 
     def recommend(self, x_positions, x_ones, seeds, k=500, n_rows=None, dtype=None):
         """Fused scoring path: encode -> decode -> top-k (track columns, seeds removed).
@@ -512,7 +521,6 @@ class DAE_tied:
                 # the exact mode's BOUND GUARD on a shard: a violation on ANY rank leaves the merged lists unproven (a column the
                 # bf16 filter wrongly dropped may have been that rank's contribution) -> the ranks agree on the flag (one 4-byte
                 # all-reduce per batch) and re-score the batch with the fp32 kernels together
-                import torch
                 import torch.distributed as dist
                 n_bad, col = self.ctx.exact_guard_read()
                 flag = torch.tensor([1 if n_bad else 0], dtype=torch.int32)
@@ -521,10 +529,9 @@ class DAE_tied:
                         flag = flag.to(idx.device)
                     dist.all_reduce(flag, op=dist.ReduceOp.MAX, group=sh["group"])
                 if int(flag.item()):
-                    import warnings
-                    warnings.warn("exact_bf16 (vocabulary shard): the bound guard fired on %s: this batch is re-scored with the fp32 "
-                                  "kernels on every rank" % ("this rank, e.g. column %d" % col if n_bad else "another rank"))
-                    self._guard_fallbacks = self.__dict__.get("_guard_fallbacks", 0) + 1
+                    self._guard_fell_back("exact_bf16 (vocabulary shard): the bound guard fired on %s: this batch is re-scored with "
+                                          "the fp32 kernels on every rank"
+                                          % ("this rank, e.g. column %d" % col if n_bad else "another rank"))
                     self._ensure_packed(_lib.DAE_DTYPE_F32, sh["cols"])
                     score, idx = self._shard_ranker(_lib.DAE_DTYPE_F32).rank_batch((csr[0], csr[1], csr[2], d_srp, d_sc), k)
             r0, r1 = self.owned_rows()
@@ -532,18 +539,16 @@ class DAE_tied:
             res = idx[:n_own].cpu().numpy(), score[:n_own].cpu().numpy()
             self._check_feed()
             return res
-        score, idx, _ev = self._submit(x_positions, x_ones, seeds, k, dtype, side_stream=False)
+        score, idx = self._submit(x_positions, x_ones, seeds, k, dtype)
         res = idx[:n_rows].cpu().numpy(), score[:n_rows].cpu().numpy()
         self._check_feed()
-        if dtype == _lib.DAE_DTYPE_BF16_EXACT and type(self)._submit is DAE._submit:
+        if dtype == _lib.DAE_DTYPE_BF16_EXACT:
             # the exact mode's BOUND GUARD (include/dae_hip.h dae_exact_guard_read): a recomputed survivor outside the interval
             # the bf16 filter promised means the lists of this call are unproven -- the same call again on the fp32 kernels
             n_bad, col = self.ctx.exact_guard_read()
             if n_bad:
-                import warnings
-                warnings.warn("exact_bf16: the bound guard fired (%d survivors, e.g. column %d): this batch is re-scored with "
-                              "the fp32 kernels" % (n_bad, col))
-                self._guard_fallbacks = self.__dict__.get("_guard_fallbacks", 0) + 1
+                self._guard_fell_back("exact_bf16: the bound guard fired (%d survivors, e.g. column %d): this batch is re-scored "
+                                      "with the fp32 kernels" % (n_bad, col))
                 return self.recommend(x_positions, x_ones, seeds, k=k, n_rows=n_rows, dtype=_lib.DAE_DTYPE_F32)
         return res
 
@@ -562,19 +567,13 @@ class DAE_tied:
                 idx, score = self.recommend(x_positions, x_ones, seeds, k=k, n_rows=n_rows, dtype=dtype)
                 yield idx, (score if want_scores else None)
             return
-        dtype = self._dtype_of(dtype)
-        # THE LOOP LIVES IN THE LIBRARY (include/dae_hip.h dae_pipeline_*): this generator copies feeds in and hands views of
-        # pinned result blocks out; a library-owned thread issues the launches.  (Rounds 2 - 5 kept an interpreter loop beside it
-        # -- staging rings, lane contexts, fetch streams, 270 lines of closures; round 6 retired it: the pipeline takes plain and
-        # titled feeds, and what it does not take goes through `recommend` feed by feed, in order.)
-        titled_native = (getattr(self, "title_model", None) is not None and getattr(self.title_model, "ctx", None) is not None
-                         and type(self)._submit is DAE_title._submit)
-        if self.device_csr and (type(self)._submit is DAE._submit or titled_native):
-            yield from self._recommend_iter_native(feeds, k, _title_dtype(dtype, self) if titled_native else dtype, want_scores)
+        # THE LOOP LIVES IN THE LIBRARY (include/dae_hip.h dae_pipeline_*): stream_loop.py copies feeds in and hands views of
+        # pinned result blocks out; what the pipeline does not take goes through `recommend` feed by feed, in order.
+        if self.device_csr:
+            yield from self._stream(feeds, k, self._dtype_of(dtype), want_scores)
             return
         for f in feeds:                  # (device_csr = False: host-built CSRs -- the per-batch call)
-            x_positions, x_ones, seeds, n_rows = f[:4]
-            idx, score = self.recommend(x_positions, x_ones, seeds, k=k, n_rows=n_rows, dtype=dtype, **self._feed_title_kw(f))
+            idx, score = self._recommend_feed(f, k, dtype)
             yield idx, (score if want_scores else None)
 
     def evaluate_iter(self, feeds, k=500, dtype=None):
@@ -587,185 +586,38 @@ class DAE_tied:
         answers go up with the feed, dae_rank_metrics runs behind the scoring call and 24 bytes a row come back instead of
         the row's k indices.  Every other case (a vocabulary-sharded model, device_csr = False, explicit seed lists, a feed
         or its answers larger than a launch slot) goes feed by feed through `recommend` and `metrics.rank_records`."""
-        titled_native = (getattr(self, "title_model", None) is not None and getattr(self.title_model, "ctx", None) is not None
-                         and type(self)._submit is DAE_title._submit)
-        if self._score_shard is None and self.device_csr and (type(self)._submit is DAE._submit or titled_native):
-            dtype = self._dtype_of(dtype)
-            yield from self._recommend_iter_native(feeds, k, _title_dtype(dtype, self) if titled_native else dtype, False,
-                                                   eval_mode=True)
+        if self._score_shard is None and self.device_csr:
+            yield from self._stream(feeds, k, self._dtype_of(dtype), False, eval_mode=True)
             return
         from ..utils.metrics import rank_records
         for f, answers in feeds:
-            x_positions, x_ones, seeds, n_rows = f[:4]
-            idx, _score = self.recommend(x_positions, x_ones, seeds, k=k, n_rows=n_rows, dtype=dtype, **self._feed_title_kw(f))
-            yield rank_records(idx, answers)
+            yield rank_records(self._recommend_feed(f, k, dtype)[0], answers)
 
-    def _feed_title_kw(self, f):
-        """The title arguments of a 5- or 6-item feed, for `recommend`: only a DAE_title takes them; a plain DAE scores the
-        feed's first four items and ignores the rest."""
-        if len(f) <= 4 or not isinstance(self, DAE_title):
-            return {}
-        return {"titles": f[4], "titles_use": f[5] if len(f) > 5 else None}
+    def _recommend_feed(self, f, k, dtype):
+        """`recommend` of one feed of a loop.  Only a DAE_title takes the title items of a 5- or 6-item feed; a plain DAE scores
+        the feed's first four items and ignores the rest."""
+        kw = {"titles": f[4], "titles_use": f[5] if len(f) > 5 else None} if len(f) > 4 and isinstance(self, DAE_title) else {}
+        return self.recommend(f[0], f[1], f[2], k=k, n_rows=f[3], dtype=dtype, **kw)
 
-    def _pipe_key(self, dtype, k, want_scores, eval_mode=False):
-        return (int(dtype), int(k), bool(want_scores), self.n_batch) + (("eval",) if eval_mode else ())
+    def _stream(self, feeds, k, dtype, want_scores, eval_mode=False):
+        """`stream_loop.stream` over this model's cached pipeline."""
+        scorer = self._title_scorer()
+        if scorer is not None:
+            dtype = _title_dtype(dtype, self)
+        key, pipe = stream_loop.pipeline_for(self, scorer, dtype, k, want_scores, eval_mode)
 
-    def _native_pipe(self, dtype, k, want_scores, eval_mode=False):
-        """The model's dae_pipeline for (dtype, k, scores wanted, evaluation mode): created on first use, again after the
-        weights changed."""
-        tm = getattr(self, "title_model", None)
-        if tm is not None and getattr(tm, "ctx", None) is None:
-            tm = None
-        key = self._pipe_key(dtype, k, want_scores, eval_mode)
-        # (dae_set_exact_margin on the model's contexts -- the guard's test hook -- reaches the pipeline's own images as well)
-        margins = [getattr(c, "_exact_margin", 1.0) for c in ([self.ctx] + ([] if tm is None else [tm.ctx]))]
-        margin = next((m_ for m_ in margins if m_ != 1.0), 1.0)
-        gen = (self.__dict__.get("_weights_gen", 0), None if tm is None else tm.__dict__.get("_params_gen", 0), margin)
-        cache = self.__dict__.setdefault("_pipes", {})
-        ent = cache.get(key)
-        if ent is not None and (ent[0] != gen or ent[1].h is None):
-            ent[1].close()
-            ent = None
-        if ent is None:
-            import torch
-            # one pipeline at a time per model: each holds (2 lanes + 2) staging slots of pinned + device memory and a dozen
-            # result blocks -- a caller that alternates dtypes pays a re-creation, not half a gigabyte of pinned memory
-            for key_, (_g, old) in list(cache.items()):
-                if getattr(old, "_users", 0) > 0:            # a recommend_iter generator of another (dtype, k, scores) key is still
-                    continue                                 # running on it (two loops interleaved): it closes with that loop
-                if self.__dict__.get("keep_pipelines"):      # (diagnosis: scripts/probe/row_diag.py)
-                    self.__dict__.setdefault("_old_pipes", []).append(old)
-                else:
-                    old.close()
-                cache.pop(key_, None)
-            self._flush_rows_adam()
-            torch.cuda.current_stream(self.device_index).synchronize()      # the weights are final before another thread reads them
-            # (titled launches: the fp32 rule -- 5 feeds of 150 = 750 rows of the 96- / 128-row groups, as the Python loop ran them)
-            group = self._coalesce_count(dtype if tm is None else None) * self.n_batch
-            if tm is not None:
-                group = min(group, 4096)
-            # three lanes: measured best in every mode (batch 256, playlists/s through the loop, 2 / 3 / 4 lanes: fp32 0.98 /
-            # 1.29 / 1.06 M, exact_bf16 4.1 / 4.8 / 4.2 M, bf16 5.3 / 6.3 / 5.6 M -- profiles/r04_notes.md)
-            lanes = int(self.__dict__.get("n_lanes") or 3)
-            pipe = _lib.Pipeline(self.weights["encoder_h"], self.biases["encoder_b"], self.weights["decoder_h"],
-                                 self.biases["decoder_b"], self.n_tracks, dtype=dtype, k=k, group_rows=group,
-                                 max_nnz=max(1 << 18, group * 1024), lanes=lanes, want_scores=want_scores,
-                                 device_index=self.device_index, title=tm)
-            if margin != 1.0 and dtype == _lib.DAE_DTYPE_BF16_EXACT:
-                pipe.exact_margin(margin)
-            if eval_mode:            # (the challenge's playlists hold at most 250 tracks; a feed with more answers than a launch
-                pipe.enable_eval(max_answers=max(1 << 16, group * 256))      # slot takes goes through `recommend`)
-            ent = cache[key] = (gen, pipe)
-        return ent[1]
+        def on_guard(n_fb):
+            self._guard_fell_back("exact_bf16: the bound guard fired in %d launch(es) of the streamed loop: they were re-scored "
+                                  "with the fp32 kernels" % n_fb, n_fb)
+        return stream_loop.stream(pipe, feeds, lambda f: self._recommend_feed(f, k, dtype), self.n_batch, want_scores, eval_mode,
+                                  isinstance(self, DAE_title), on_guard if dtype == _lib.DAE_DTYPE_BF16_EXACT else None,
+                                  self._pipes, key)
 
-    def _recommend_iter_native(self, feeds, k, dtype, want_scores, eval_mode=False):
-        """`recommend_iter` on the library's pipeline; eval_mode: `evaluate_iter` on the same loop -- feeds are (feed, answers)
-        pairs and what comes out per feed are the rows' metric records."""
-        pipe = self._native_pipe(dtype, k, want_scores, eval_mode)
-        key = self._pipe_key(dtype, k, want_scores, eval_mode)
-        poll = pipe.poll
-        if eval_mode:
-            from itertools import chain
-            from ..utils.metrics import rank_records
-            poll = pipe.poll_eval
-
-        from collections import deque
-        rows_out = deque()           # rows each pending feed asked for (a feed is fed as the graph's n_batch rows, DAEs.py:34)
-        nb_full = self.n_batch
-        # results arrive a LAUNCH at a time: asking the pipeline after every feed whether something is ready is a foreign call
-        # per feed for an answer that changes once per launch (the caller's thread is what bounds the bf16 loops: round 6)
-        per_launch = max(1, pipe.group_rows // max(1, self.n_batch))
-        n_fed = 0
-
-        def out(r):
-            n = rows_out.popleft()
-            if eval_mode:
-                return r if n == nb_full else r[:n]
-            if n == nb_full:
-                return r[0], (r[1] if want_scores else None)
-            return r[0][:n], (r[1][:n] if want_scores else None)
-        clean = False
-        fallbacks0 = pipe.stats()["guard_fallbacks"] if dtype == _lib.DAE_DTYPE_BF16_EXACT else 0
-        pipe._users = getattr(pipe, "_users", 0) + 1             # (_native_pipe never closes a pipeline a loop is running on)
-        try:
-            for f in feeds:
-                if eval_mode:
-                    f, answers = f
-                x_positions, x_ones, seeds, n_rows = f[:4]
-                n = self.n_batch if n_rows is None else int(n_rows)
-                titles = use = None
-                if len(f) > 5 and f[4] is not None and f[5] is not None and pipe.title_len is not None:
-                    u = np.asarray(f[5], np.float32).reshape(-1)[:self.n_batch]
-                    if u.size and np.any(u):                     # (titles_use all zero: the plain DAE, as DAE_title.recommend decides)
-                        L_ = pipe.title_len
-                        titles = np.full((self.n_batch, L_), -1, np.int32)
-                        t = f[4]
-                        nt = min(len(t), self.n_batch)
-                        if nt:
-                            if not isinstance(t, np.ndarray):
-                                t = [([-1] * L_) if x is None else x for x in t[:nt]]
-                            titles[:nt] = np.asarray(t, np.int64).reshape(-1, L_)[:nt]
-                        use = np.zeros(self.n_batch, np.float32)
-                        use[:min(u.size, nt)] = u[:nt]                                # (no title, no use)
-                unfit = len(f) > 4 and pipe.title_len is None and isinstance(self, DAE_title)     # (a plain DAE ignores titles)
-                if not unfit:                                    # a feed larger than a launch slot: through recommend(), not a DaeError
-                    nnz_f = int(np.shape(x_positions)[0]) if np.ndim(x_positions) == 2 else len(x_positions)
-                    unfit = nnz_f > pipe.max_nnz
-                if eval_mode:                                    # the answers as a CSR over the launch's n_batch rows
-                    if len(answers) != n:
-                        raise ValueError("evaluate_iter: %d answer lists for a feed of %d rows" % (len(answers), n))
-                    if n <= self.n_batch and not unfit:
-                        arp = np.zeros(self.n_batch + 1, np.int32)
-                        np.cumsum(np.fromiter(map(len, answers), np.int64, n), out=arp[1:n + 1])
-                        arp[n + 1:] = arp[n]
-                        unfit = int(arp[-1]) > pipe.max_answers
-                if not (isinstance(seeds, str) and seeds == SEEDS_FROM_INPUT) or unfit or n > self.n_batch:
-                    pipe.flush()                                 # a feed the pipeline does not take: in order, through recommend()
-                    while pipe.pending:
-                        yield out(poll(True))
-                    idx, score = self.recommend(x_positions, x_ones, seeds, k=k, n_rows=n_rows, dtype=dtype,
-                                                **self._feed_title_kw(f))
-                    yield rank_records(idx, answers) if eval_mode else (idx, (score if want_scores else None))
-                    continue
-                if eval_mode:
-                    ans = (arp, np.fromiter(chain.from_iterable(answers), np.int32, int(arp[-1])))
-                # (every lane full: hand the oldest lists out first)
-                while not (pipe.submit_eval(x_positions, x_ones, self.n_batch, ans, titles, use) if eval_mode
-                           else pipe.submit(x_positions, x_ones, self.n_batch, titles, use)):
-                    yield out(poll(True))
-                rows_out.append(n)
-                n_fed += 1
-                if n_fed % per_launch == 0 or titles is not None:
-                    while True:                                  # ... and whatever else is ready, without waiting
-                        r = poll(False)
-                        if r is None:
-                            break
-                        yield out(r)
-            pipe.flush()
-            while pipe.pending:
-                yield out(poll(True))
-            clean = True
-        except _lib.DaeError as e:
-            if "out of range" in str(e) or "outside" in str(e):
-                raise ValueError(str(e))
-            raise
-        finally:
-            pipe._users -= 1
-            if dtype == _lib.DAE_DTYPE_BF16_EXACT and pipe.h is not None:
-                n_fb = pipe.stats()["guard_fallbacks"] - fallbacks0
-                if n_fb > 0:         # (the lists that went out are the fp32 kernels': the pipeline re-scored those launches itself)
-                    import warnings
-                    self._guard_fallbacks = self.__dict__.get("_guard_fallbacks", 0) + n_fb
-                    warnings.warn("exact_bf16: the bound guard fired in %d launch(es) of the streamed loop: they were re-scored with "
-                                  "the fp32 kernels" % n_fb)
-            cache = self.__dict__.get("_pipes", {})
-            if not clean:        # an error, or a consumer that stopped early: feeds may be queued -- this pipeline is not reused
-                if cache.get(key, (None, None))[1] is pipe:
-                    cache.pop(key, None)
-                pipe.close()
-            elif pipe._users == 0 and len(cache) > 1 and cache.get(key, (None, None))[1] is pipe:
-                cache.pop(key, None)                             # another key's pipeline was created while this loop ran: one stays
-                pipe.close()
+    def close_pipelines(self):
+        """Close and forget the cached pipelines: the next streamed loop creates its own (e.g. after `n_lanes` changed)."""
+        for _gen, pipe in self._pipes.values():
+            pipe.close()
+        self._pipes.clear()
 
     def _coalesce_count(self, dtype=None):
         """Feeds per launch of the streamed loop.  fp32 decode (the device is the limit): the count (<= 8, <= 1024 rows)
@@ -773,9 +625,8 @@ class DAE_tied:
         (750 of 768 rows), 250 -> 4 (1000 of 1024), 256 -> 4, batches of >= 512 rows stay alone.  bf16 / exact_bf16
         (the host is the limit: ~0.3 ms of Python per launch against 0.2 ms of kernels for 1 024 rows): as many feeds
         as fit 2 048 rows, at most 8 (150 -> 8: 2.4 -> 3.3 M playlists/s).  `model.coalesce = n` overrides."""
-        forced = self.__dict__.get("coalesce")
-        if forced:
-            return max(1, int(forced))
+        if self.coalesce:
+            return max(1, int(self.coalesce))
         nb = self.n_batch
         if dtype is not None and dtype != _lib.DAE_DTYPE_F32:
             return max(1, min(8, 2048 // nb))
@@ -948,21 +799,32 @@ class DAE_title(DAE):
         x_count = row_sum(x) * input_keep_prob;  w_title = u / (u + x_count + 1e-10);  w_playlist = x_count / (same)
 
     with u = titles_use in {0, 1} per row (:156-162).  u = 0 gives w_playlist = 1.0f exactly, i.e. the plain
-    DAE -- those batches take the fused scoring path.  With titles the two vocabulary-wide
-    score matrices are materialised and mixed (`dae_mix_scores`), then ranked by `dae_topk_dense`: correct but
-    unfused (fusing the second GEMM into the threshold path is the follow-up)."""
+    DAE -- those batches take the fused scoring path.  With titles, `recommend` ranks the mixed score
+    without either vocabulary-wide matrix (`_submit`; exact_bf16: both GEMMs in one launch per pass, csrc/mixexact.hip) and
+    the streamed loops run their titled launches on the library's pipeline; only the dense fetch of
+    the protocol, `mixed_scores`, materialises the two matrices (`dae_mix_scores`)."""
 
     def __init__(self, conf, title_model):
         DAE.__init__(self, conf)
         self.initval_dir = conf.DAEval                    # DAEs.py:157: the frozen weights
         self.title_model = title_model
+        self.title_exact_off = False      # set from outside: titled exact_bf16 launches on the fp32 kernels
+        self._title_fp32_said = False     # `_title_dtype` said that this model's shapes have no exact title mix
+        self._tcost = None                # train_step's cost word on the device
+        # `_mix_guard_fired`: rows it re-scored alone; launches in a row whose rows overflowed the refine launch (two pause the
+        # exact mix); titled launches left of that pause, which run on the fp32 kernels
+        self._guard_row_fallbacks = self._mix_overflow_streak = self._mix_exact_pause = 0
+
+    def _title_scorer(self):
+        tm = self.title_model
+        return tm if tm is not None and tm.ctx is not None else None
 
     def _row_sums(self, x_positions, x_ones):
         rp, _c, v = coo_to_csr(x_positions, x_ones, self.n_batch, self.n_input)
         rows = np.repeat(np.arange(self.n_batch), np.diff(rp))
         return np.bincount(rows, weights=v.astype(np.float64), minlength=self.n_batch).astype(np.float32)
 
-    def _mix_weights(self, csr, titles_use, input_keep_prob=1.0, seed=0, side_stream=False, n_rows=None, u_dev=None):
+    def _mix_weights(self, csr, titles_use, input_keep_prob=1.0, seed=0, n_rows=None):
         """DAEs.py:159-162 on the device: x_count = row_sum(x) * input_keep_prob; w_title = u / (u + x_count + 1e-10),
         w_playlist = x_count / (same) -- fp32 operations in the reference's order.  -> (w_title, w_playlist) [n_batch]."""
         import torch
@@ -970,13 +832,10 @@ class DAE_title(DAE):
         dev = rp.device
         nb = n_rows or self.n_batch
         P = _lib._ptr
-        if u_dev is None:
-            u = np.zeros(nb, np.float32)
-            tu = np.asarray(titles_use, np.float32).reshape(-1)
-            u[:len(tu)] = tu[:nb]
-            u = self._to_dev(u, torch.float32, side_stream)
-        else:
-            u = u_dev                                         # (already on the device)
+        u = np.zeros(nb, np.float32)
+        tu = np.asarray(titles_use, np.float32).reshape(-1)
+        u[:len(tu)] = tu[:nb]
+        u = self._to_dev(u, torch.float32)
         w_t = torch.empty(nb, dtype=torch.float32, device=dev)
         w_p = torch.empty(nb, dtype=torch.float32, device=dev)
         # one launch (dae_mix_weights: the row sums of dae_row_sums and the four elementwise operations behind them)
@@ -1043,7 +902,7 @@ class DAE_title(DAE):
         feat, d_titles, arg, raw = tm.features(titles, self.n_batch, title_keep_prob, seed, keep_for_backward=True)
         zt = torch.empty((self.n_batch, self.n_input), dtype=torch.float32, device=dev)
         tm.ctx.decode_dense(feat, zt, apply_sigmoid=False)
-        if getattr(self, "_tcost", None) is None:
+        if self._tcost is None:
             self._tcost = torch.zeros(1, dtype=torch.float32, device=dev)
         tm.backward_and_step(feat, d_titles, arg, raw, zt, dae, (yr, yc, yv), w_t, w_p, self.n_batch,
                              title_keep_prob, seed, self._tcost)
@@ -1051,19 +910,19 @@ class DAE_title(DAE):
         self._check_feed()
         return cost
 
-    def _submit(self, x_positions, x_ones, seeds, k, dtype, side_stream, titles=None, titles_use=None, ctx=None,
-                n_rows=None):
-        """One batch enqueued, nothing fetched (`n_rows`: rows of a launch that coalesces several feeds).  Without titles in use the mix reduces to the plain DAE (w_playlist is
-        exactly 1.0f, App. B.6): the fused path of the base class.  With titles: the DAE term of the track columns
-        goes to a transposed scratch (dae_decode_mix_term) and the title scorer's context runs the fused threshold
-        path on sigmoid(z_title) * w_title + that term (dae_set_score_mix) -- no [batch, n_input] matrix of either."""
+    def _submit(self, x_positions, x_ones, seeds, k, dtype, titles=None, titles_use=None, n_rows=None):
+        """One batch enqueued, nothing fetched (`n_rows`: rows of this launch when it is not the model's batch).  Without
+        titles in use the mix reduces to the plain DAE (w_playlist is exactly 1.0f, App. B.6): the fused path of the base
+        class.  With titles: the DAE term of the track columns goes to a transposed scratch (dae_decode_mix_term) and the
+        title scorer's context runs the fused threshold path on sigmoid(z_title) * w_title + that term
+        (dae_set_score_mix) -- no [batch, n_input] matrix of either."""
         if titles is None or titles_use is None or not np.any(np.asarray(titles_use)):
-            return DAE._submit(self, x_positions, x_ones, seeds, k, dtype, side_stream, ctx=ctx, n_rows=n_rows)
+            return DAE._submit(self, x_positions, x_ones, seeds, k, dtype, n_rows=n_rows)
         import torch
         tm = self.title_model
         tm.ctx.bind_stream()
         dtype = _title_dtype(dtype, self)
-        if dtype == _lib.DAE_DTYPE_BF16_EXACT and self.__dict__.get("_mix_exact_pause", 0) > 0:
+        if dtype == _lib.DAE_DTYPE_BF16_EXACT and self._mix_exact_pause > 0:
             # rows of this model keep overflowing the refine launch's candidate buffers (a flat DAE bias: no prior for the
             # threshold sample): the exact launches are paused for a while instead of being run and re-scored every time
             self._mix_exact_pause -= 1
@@ -1072,44 +931,35 @@ class DAE_title(DAE):
             dtype = _lib.DAE_DTYPE_F32
         nb = n_rows or self.n_batch
         dev = self.weights["encoder_h"].device
-        d_titles = d_use = None
         # (Measured and not kept: the launch's two independent preambles -- CSR build / encode / seeds / mixing weights, and the
         # title features -- on streams of their own, joined before dae_mix_topk_exact: 1.12 - 1.17 M playlists/s against
         # 1.22 M without.  The loop is bound by the host's ~0.6 ms per launch, and the fork adds events and stream switches.)
-        feat = None
-        csr = self._upload_csr(x_positions, x_ones, side_stream=side_stream, n_rows=nb)
+        csr = self._upload_csr(x_positions, x_ones, n_rows=nb)
         h = torch.empty((nb, self.n_hidden), dtype=torch.float32, device=dev)
         self.ctx.encode(csr[0], csr[1], csr[2], self.weights["encoder_h"], self.biases["encoder_b"], h)
-        w_t, w_p = self._mix_weights(csr, titles_use, side_stream=side_stream, n_rows=nb, u_dev=d_use)
+        w_t, w_p = self._mix_weights(csr, titles_use, n_rows=nb)
+        feat = tm.features(titles, nb)
+        d_srp, d_sc = self._seed_csr_dev(seeds, csr, n_rows=nb)
+        score = torch.empty((nb, k), dtype=torch.float32, device=dev)
+        idx = torch.empty((nb, k), dtype=torch.int32, device=dev)
         if dtype == _lib.DAE_DTYPE_BF16_EXACT:
             # both GEMMs on bf16 operands in one launch per pass, the survivors recomputed in fp32 (csrc/mixexact.hip)
-            if feat is None:
-                feat = tm.features(titles, nb, side_stream_of=self if side_stream else None, d_titles=d_titles)
-            d_srp, d_sc = self._seed_csr_dev(seeds, csr, side_stream, n_rows=nb)
-            score = torch.empty((nb, k), dtype=torch.float32, device=dev)
-            idx = torch.empty((nb, k), dtype=torch.int32, device=dev)
             gw = torch.empty(2, dtype=torch.int32, device=dev)
             tm.ctx.mix_topk_exact(self.ctx, feat, h, w_t, w_p, self.n_tracks, d_srp, d_sc, k, score, idx, guard_out=gw)
-            ev = torch.cuda.current_stream(self.device_index).record_event()
             # the guard words travel with the lists; what a re-scoring in fp32 needs, should they have moved
             idx._mix_guard = (gw, (x_positions, x_ones, seeds, titles, titles_use, n_rows))
-            return score, idx, ev
+            return score, idx
         nt32 = min((self.n_tracks + 31) // 32 * 32, self.n_input)
         y1T = torch.empty((nt32, nb), dtype=torch.float32, device=dev)
         self.ctx.decode_mix_term(h, w_p, self.n_tracks, y1T, dtype=dtype)
-        feat = tm.features(titles, nb, side_stream_of=self if side_stream else None, d_titles=d_titles)
-        d_srp, d_sc = self._seed_csr_dev(seeds, csr, side_stream, n_rows=nb)
-        score = torch.empty((nb, k), dtype=torch.float32, device=dev)
-        idx = torch.empty((nb, k), dtype=torch.int32, device=dev)
         tm.ctx.set_score_mix(y1T, w_t)
         try:
             tm.ctx.decode_topk(feat, self.n_tracks, d_srp, d_sc, k, score, idx, out_kind=_lib.DAE_OUT_LOGIT, dtype=dtype)
         finally:
             tm.ctx.set_score_mix()
-        ev = torch.cuda.current_stream(self.device_index).record_event()
-        return score, idx, ev
+        return score, idx
 
-    def _mix_guard_fired(self, idx, k, words=None, score=None):
+    def _mix_guard_fired(self, idx, k, score):
         """A launch of the exact title mix whose guard words moved is not trusted (a recomputed logit left the interval
         the bf16 launch promised for it, or a row overflowed its candidate list): -> (score, idx) of the same feed through
         the fp32 kernels, or None when the launch stands."""
@@ -1117,7 +967,7 @@ class DAE_title(DAE):
         if tag is None:
             return None
         gw, (x_positions, x_ones, seeds, titles, titles_use, n_rows) = tag
-        n_bad, col = (int(v) for v in (gw.cpu() if words is None else words))
+        n_bad, col = (int(v) for v in gw.cpu())
         # (the shadow of the cumulative words lives on the context and is resynchronised by every dae_exact_guard_read on it:
         # ADVICE r4 -- a read elsewhere used to leave this comparison one reset behind)
         seen = getattr(self.title_model.ctx, "_guard_seen", 0)
@@ -1148,8 +998,8 @@ class DAE_title(DAE):
                 T2 = np.asarray(titles, np.int64).reshape(-1, self.title_model.input_len)[rows]
                 warnings.warn("exact_bf16 title mix: the bound guard fired (%d row(s) overflow the refine launch): those rows are "
                               "re-scored with the fp32 kernels" % len(rows))
-                self._guard_row_fallbacks = self.__dict__.get("_guard_row_fallbacks", 0) + len(rows)
-                score2, idx2, _ev = self._submit(P2, O2, seeds2, k, _lib.DAE_DTYPE_F32, False, T2, use[rows], n_rows=len(rows))
+                self._guard_row_fallbacks += len(rows)
+                score2, idx2 = self._submit(P2, O2, seeds2, k, _lib.DAE_DTYPE_F32, T2, use[rows], n_rows=len(rows))
                 rt = torch.from_numpy(rows).to(idx.device)
                 idx_n, score_n = idx.clone(), score.clone()
                 idx_n[rt] = idx2[:len(rows)]
@@ -1157,16 +1007,13 @@ class DAE_title(DAE):
                 self._mix_overflow_streak = 0
                 return score_n, idx_n
         if col in (-2, -3):                     # not a broken bound, but many rows the refine launch cannot hold: after two such
-            self._mix_overflow_streak = self.__dict__.get("_mix_overflow_streak", 0) + 1      # launches in a row the mode pauses
+            self._mix_overflow_streak += 1                                                    # launches in a row the mode pauses
             if self._mix_overflow_streak >= 2:
                 self._mix_exact_pause = 64      # launches on the fp32 kernels before it is tried again
                 self._mix_overflow_streak = 0
-        warnings.warn("exact_bf16 title mix: the bound guard fired (%s): this launch is re-scored with the fp32 kernels"
-                      % ("rows overflow the refine launch" if col in (-2, -3) else "column %d" % col))
-        self._guard_fallbacks = self.__dict__.get("_guard_fallbacks", 0) + 1
-        score, idx2, _ev = self._submit(x_positions, x_ones, seeds, k, _lib.DAE_DTYPE_F32, False, titles, titles_use,
-                                        n_rows=n_rows)
-        return score, idx2
+        self._guard_fell_back("exact_bf16 title mix: the bound guard fired (%s): this launch is re-scored with the fp32 kernels"
+                              % ("rows overflow the refine launch" if col in (-2, -3) else "column %d" % col))
+        return self._submit(x_positions, x_ones, seeds, k, _lib.DAE_DTYPE_F32, titles, titles_use, n_rows=n_rows)
 
     def recommend(self, x_positions, x_ones, seeds, k=500, n_rows=None, dtype=None, titles=None, titles_use=None):
         """Top-k of the MIXED score (DAEs.py:176-181 + main_challenge.py:26-41) without either [batch, n_input] matrix
@@ -1183,9 +1030,9 @@ class DAE_title(DAE):
         self._ensure_packed(dtype)
         self.title_model._ensure_packed(dtype)
         self.ctx.bind_stream()
-        score, idx, _ev = self._submit(x_positions, x_ones, seeds, k, dtype, False, titles, titles_use)
+        score, idx = self._submit(x_positions, x_ones, seeds, k, dtype, titles, titles_use)
         n_rows = self.n_batch if n_rows is None else n_rows
-        redo = self._mix_guard_fired(idx, k, None, score)
+        redo = self._mix_guard_fired(idx, k, score)
         if redo is not None:
             score, idx = redo
         res = idx[:n_rows].cpu().numpy(), score[:n_rows].cpu().numpy()

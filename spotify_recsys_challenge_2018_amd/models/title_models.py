@@ -14,8 +14,6 @@ scorer, never selected by the shipped configs) is not implemented.
 import ctypes
 import pickle
 
-import os
-
 import numpy as np
 
 from .. import _lib
@@ -72,6 +70,9 @@ class Char_CNN:
         self.ctx = None
         self.p = {}
         self._packed_dirty = True
+        self._packed = set()             # dtypes the context holds a prepacked Output_W^T of
+        self._params_gen = 0             # bumps with every change of the variables (a cached dae_pipeline holds images of the old ones)
+        self._ftab_gen = self._adam = None       # the _params_gen of the context's feature table; the training state (first step)
         self._rng = np.random.RandomState(int(getattr(conf, "dropout_seed", 1234)) + 1)
         self._fs = (ctypes.c_int32 * len(self.filter_sizes))(*self.filter_sizes)
 
@@ -107,7 +108,6 @@ class Char_CNN:
 
     def fit(self, params=None):
         """Create the context and put the variables on the device (host dict in TF layout, or fresh)."""
-        import torch
         self.ctx = _lib.Context(self.device_index)
         self.set_params(params if params is not None else self._host_init())
 
@@ -137,7 +137,7 @@ class Char_CNN:
         self.p["Output_WT"] = dev_t(wt)
         self.p["Output_b"] = dev_t(host["Output_b"])
         self._packed_dirty = True
-        self._params_gen = self.__dict__.get("_params_gen", 0) + 1      # (a cached dae_pipeline holds images of the old variables)
+        self._params_gen += 1
         self._drop_features_table()
 
     def get_params(self):
@@ -164,19 +164,10 @@ class Char_CNN:
             self.set_params(pickle.load(f))
 
     # -- forward ----------------------------------------------------------------------------------------
-    def _titles_dev(self, titles, n_rows, side_stream_of=None):
-        import torch
-        t = np.full((n_rows, self.input_len), -1, np.int32)
-        src = np.asarray(titles, np.int64).reshape(-1, self.input_len) if len(titles) else np.zeros((0, self.input_len))
-        t[:len(src)] = src[:n_rows]
-        if side_stream_of is not None:                 # streamed scoring: upload on the model's copy stream
-            return side_stream_of._to_dev(t, torch.int32, side_stream=True)
-        return torch.from_numpy(t).to(torch.device("cuda", self.device_index))
-
     def _ensure_features_table(self):
         """Inference with the variables as they are NOW: the convolutions as a table over (filter size, offset, character)
         (dae_title_prepack_features) -- rebuilt whenever the variables changed since it was made."""
-        if self.__dict__.get("_ftab_gen") != self._params_gen:
+        if self._ftab_gen != self._params_gen:
             P = _lib._ptr
             self.ctx.bind_stream()
             self.ctx.check(self.ctx.lib.dae_title_prepack_features(
@@ -186,18 +177,21 @@ class Char_CNN:
 
     def _drop_features_table(self):
         """The variables are about to change (a training step, set_params): no call may read the old table."""
-        if self.__dict__.get("_ftab_gen") is not None and getattr(self, "ctx", None) is not None and self.ctx.h:
+        if self._ftab_gen is not None and self.ctx is not None and self.ctx.h:
             self.ctx.check(self.ctx.lib.dae_title_prepack_features(self.ctx.h, None, 0, 0, None, None, 0, 0))
         self._ftab_gen = None
 
-    def features(self, titles, n_rows, keep_prob=1.0, seed=0, keep_for_backward=False, side_stream_of=None, d_titles=None):
+    def features(self, titles, n_rows, keep_prob=1.0, seed=0, keep_for_backward=False):
         """Char_CNN.py:23-63 -> feat [n_rows, ld] (CUDA); with keep_for_backward also (argmax, raw)."""
         import torch
         self.ctx.bind_stream()
         if keep_prob == 1.0 and not keep_for_backward:
             self._ensure_features_table()
         dev = self.p["conv_w"].device
-        d_t = self._titles_dev(titles, n_rows, side_stream_of) if d_titles is None else d_titles    # (staged with the feed)
+        t = np.full((n_rows, self.input_len), -1, np.int32)                   # -1: no character (rows without a title, padding)
+        src = np.asarray(titles, np.int64).reshape(-1, self.input_len) if len(titles) else np.zeros((0, self.input_len))
+        t[:len(src)] = src[:n_rows]
+        d_t = torch.from_numpy(t).to(dev)
         feat = torch.empty((n_rows, self.ld), dtype=torch.float32, device=dev)
         arg = torch.empty((n_rows, self.n_feat), dtype=torch.int32, device=dev) if keep_for_backward else None
         raw = torch.empty((n_rows, self.n_feat), dtype=torch.float32, device=dev) if keep_for_backward else None
@@ -228,7 +222,7 @@ class Char_CNN:
         if self._packed_dirty:
             self._packed = set()
             self._packed_dirty = False
-        if dtype not in self.__dict__.setdefault("_packed", set()):
+        if dtype not in self._packed:
             self.ctx.bind_stream()
             self.ctx.prepack_decoder(self.p["Output_WT"], self.p["Output_b"], 0, self.output_dim, dtype)
             self._packed.add(dtype)
@@ -250,7 +244,7 @@ class Char_CNN:
     # -- training (the DAE is frozen: only these variables move, DAEs.py:165-171, :198) -----------------
     def _train_state(self):
         import torch
-        if getattr(self, "_adam", None) is None:
+        if self._adam is None:
             self._step = 0
             self._tvars = ["char_embedding", "conv_w", "conv_b", "Output_WT", "Output_b"]
             self._grads = {n: torch.zeros_like(self.p[n]) for n in self._tvars}
@@ -280,7 +274,7 @@ class Char_CNN:
             ctx.check(lib.dae_adam_step(ctx.h, P(self.p[n]), P(m), P(v), P(g[n]), self.p[n].numel(),
                                         self.learning_rate, 0.9, 0.999, 1e-8, self._step))
         self._packed_dirty = True
-        self._params_gen = self.__dict__.get("_params_gen", 0) + 1
+        self._params_gen += 1
         self._drop_features_table()
 
     def __str__(self):

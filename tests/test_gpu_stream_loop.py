@@ -49,7 +49,7 @@ def test_recommend_iter_equals_recommend(tmp_path, dtype, B):
     assert np.array_equal(got2[0][0], want2[0]) and not np.array_equal(got2[0][0], want[0][0])
     for nl in (1, 2):
         m.n_lanes = nl
-        m.__dict__.pop("_pipes", None)
+        m.close_pipelines()
         got1 = list(m.recommend_iter(feeds[:3], k=k, dtype=dtype))
         assert all(np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) for a, b in zip(got1, got2))
     m.n_lanes = None

@@ -192,9 +192,8 @@ def test_challenge_driver_with_titles_under_exact_bf16_at_hidden_256(tmp_path, m
     open(work / "config.ini", "w").write(ini)
     shutil.copytree(os.path.join(G, "data"), tmp_path / "data")
     calls = []
-    real, real1 = L.Context.mix_topk_exact, L.Context.title_score_exact        # (the latter: the whole launch in one call)
+    real = L.Context.mix_topk_exact
     monkeypatch.setattr(L.Context, "mix_topk_exact", lambda self, *a, **kw: (calls.append(1), real(self, *a, **kw))[1])
-    monkeypatch.setattr(L.Context, "title_score_exact", lambda self, *a, **kw: (calls.append(1), real1(self, *a, **kw))[1])
     # ... or, since round 5, inside the library's titled pipeline (dae_pipeline_create_titled with DAE_DTYPE_BF16_EXACT,
     # feeds through dae_pipeline_submit_titled -> dae_title_score): recorded at the ctypes wrapper
     real_init, real_submit = L.Pipeline.__init__, L.Pipeline.submit
