@@ -406,18 +406,20 @@ def grads_bf16(x, y, W_enc, b_enc, W_dec, b_dec, n_batch, tied, reg_lambda=0.0,
                input_keep_mask=None, ikp=1.0, hidden_keep_mask=None, kp=1.0,
                h=None, round_dz=None, round_ops=True, head="f64"):
     """Gradient of the training step under dae_set_train_dtype(BF16), as the kernels round it: float64 everywhere except
-    where the kernels round an operand to bf16 (spotify_recsys_challenge_2018_amd/csrc, line numbers of this revision):
+    where the kernels round an operand to bf16 (spotify_recsys_challenge_2018_amd/csrc):
 
-      forward logits   z = bf16(h) . bf16(W_dec)^T + b_dec, for the negatives (K5: the prepack / pack_h kernels, the
-                       row-major K5's staged rows decode_f32.hip ~L679 and decode_loss_dh_bf16_kernel ~L891 round both
-                       operands with v_cvt_pk_bf16_f32, RNE) and for the positives alike (train.hip loss_fixup_kernel<BF16>:
-                       bf16_value on h ~L97 and on W ~L130-151, an fmaf chain from +0, then + bias).
-      H % 128 == 0     dz is stored as bf16 (loss_fixup_kernel<.., DZ16> ~L164; the K5 epilogues with p.dz16,
-                       decode_f32.hip ~L521 / ~L735 / ~L805), and gW_dec = dz^T h (grad_wdec_t_kernel: pk_bf16 of h ~L619,
-                       the bf16 dz^T read as is), dh = dz W_dec (grad_hidden_kernel<4, true, true>, or the fused K5 + K7
-                       plus the fix-up's correction sum (bf16(dz) - bf16(dz as a negative)) bf16(W), train.hip ~L187-194)
-                       run on bf16(dz), bf16(h), bf16(W_dec).  gb_dec sums the bf16 dz: grad_wdec_t_kernel forms it as an
-                       MFMA of the bf16 dz^T with a ones operand (~L623, stored ~L683).
+      forward logits   z = bf16(h) . bf16(W_dec)^T + b_dec, for the negatives (K5: prepack.hip's prepack / pack_h kernels
+                       for decode_generic.hip's EPI_LOSS; decode_f32.hip decode_loss_dh_bf16_kernel's K5D_FRAG and
+                       K5D_STAGE round both operands with dae_bf16_rne / v_cvt_pk_bf16_f32, RNE) and for the positives
+                       alike (train.hip loss_fixup_kernel<BF16>: dae_bf16_value on h and on W, an fmaf chain from +0,
+                       then + bias).
+      H % 128 == 0     dz is stored as bf16 (loss_fixup_kernel<.., DZ16>: pk_bf16(dzv, 0); the K5 epilogues: p.dz16 in
+                       decode_generic.hip's EPI_LOSS, the packed pairs pk[] of decode_loss_dh_bf16_kernel), and
+                       gW_dec = dz^T h (grad_wdec_t_kernel: pk_bf16x8 of h, the bf16 dz^T read as is), dh = dz W_dec
+                       (grad_hidden_kernel<4, true, true>, or the fused K5 + K7 plus the fix-up's correction sum
+                       (bf16(dz) - bf16(dz as a negative)) bf16(W), loss_fixup_kernel<.., CORR>) run on bf16(dz), bf16(h),
+                       bf16(W_dec).  gb_dec sums the bf16 dz: grad_wdec_t_kernel forms it as an MFMA of the bf16 dz^T
+                       with a ones operand.
       H % 128 != 0     only the forward GEMM is bf16: the backward GEMMs (grad_wdec_kernel<2|1>, grad_hidden_kernel<2|1>)
                        are fp32 on the unrounded dz, h and W_dec, and so is gb_dec.
       everything else  loss, dpre, the encoder gradient and l2 are fp32 in the kernels, float64 here.

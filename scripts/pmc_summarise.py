@@ -53,7 +53,7 @@ def src_sha(name):
         return None
 
 
-sha = {n: src_sha(n) for n in ("decode_f32.hip", "refine.hip", "encode.hip", "train.hip", "dae_internal.h")}
+sha = {n: src_sha(n) for n in ("decode_f32.hip", "decode_common.h", "refine.hip", "encode.hip", "train.hip", "dae_internal.h")}
 dec = {"source": "rocprofv3 --kernel-trace --pmc <set>, one pass per counter set (scripts/gpu_pmc_round6.sh): bench.py "
                  "--streams 1 --steps 6, default workload (B=256, V=170000, H=256); raw CSVs profiles/%s_pmc_*.csv" % PFX,
        "fetch_correction": "hbm_bytes_per_launch = FETCH_SIZE x 2 (gfx950: wide coalesced reads are tallied at half) + "

@@ -525,7 +525,7 @@ static int topk_phase_a(dae_ctx* ctx, const dae_packed* pk, const dae_rowgeom& g
         if (rc) return rc;
         order = static_cast<const int*>(pkm.order.p);
         // bf16 launches whose sample takes several rounds of the phase-A workgroups (many rows: few workgroups per row group): the
-        // sample re-dealt so that a workgroup's tiles of a round come from different popularity bands (decode_f32.hip
+        // sample re-dealt so that a workgroup's tiles of a round come from different popularity bands (prepack.hip
         // tile_band_kernel); the list is this context's, rebuilt when the order or the geometry changes
         const int n_ws_s = gA.nb_rg * gA.waves;
         // (not when the launch takes per-WAVE groups -- see wave_groups below: there the plain order IS band-dealt)

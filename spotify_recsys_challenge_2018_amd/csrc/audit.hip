@@ -13,7 +13,7 @@
 //   * counts every element outside [u - 2 eps_c, u] in the context's GUARD WORDS -- the words the refine launch's guard counts
 //     in, so DAE.recommend / dae_pipeline_poll re-score such a launch with the fp32 kernels exactly as for a survivor.
 // What this does and does not establish: the bound is PROVEN given an error model of v_mfma_f32_32x32x16_bf16's accumulation
-// (decode_f32.hip exact_bounds_kernel); survivors are CHECKED always; dropped columns are checked on a SAMPLE (all rows x
+// (prepack.hip exact_bounds_kernel); survivors are CHECKED always; dropped columns are checked on a SAMPLE (all rows x
 // n_tiles x 32 columns every N-th launch; over a loop every tile comes up); nothing else is assumed.
 #include "dae_internal.h"
 

@@ -37,9 +37,9 @@ struct dae_packed {            // one prepacked decoder image
     int V = 0, H = 0, Hp = 0;   // Hp = H padded to DAE_HPAD
     int col_lo = 0, col_hi = 0;
     int ntiles = 0;            // ceil((col_hi-col_lo)/32)
-    dae_buf W;                 // fp32: [ntiles][Hp/8][64 lanes][4]   bf16: see decode_bf16.hip
+    dae_buf W;                 // fp32: [ntiles][Hp/8][64 lanes][4]   bf16: [ntiles][Hp/16][64 lanes] uint4 (prepack.hip)
     dae_buf bias;              // [ntiles*32] fp32, zero padded
-    dae_buf bias16;            // bf16 image: [ntiles][64] uint4 bias fragments (decode_f32.hip)
+    dae_buf bias16;            // bf16 image: [ntiles][64] uint4 bias fragments (prepack.hip)
     // tiles ordered by the largest bias among their rankable columns, descending (the threshold
     // sample of the fused path takes the head of this list); rebuilt when the image or the number
     // of rankable columns changes
@@ -48,7 +48,7 @@ struct dae_packed {            // one prepacked decoder image
     int order_nrank = -1;      // rankable columns the order was built for (-1: none)
     int order_nsamp = -1;
     long long order_gen = 0;   // process-wide stamp of the last rebuild of `order` (what a context's band list was cut from)
-    // DAE_DTYPE_BF16_EXACT (bf16 image only; decode_f32.hip exact_bounds_kernel): per column c a rigorous bound
+    // DAE_DTYPE_BF16_EXACT (bf16 image only; prepack.hip exact_bounds_kernel): per column c a rigorous bound
     // eps_c >= |z32(r, c) - z16(r, c)| for every hidden row with entries in [0, 1], the bias fragments of
     // b - eps (phase A: lower bounds of the fp32 logits) and b + eps (filter: upper bounds), and a row-major fp32
     // copy of the image's decoder rows for the exact re-scoring of the survivors (topk.hip ExactSrc)
@@ -173,6 +173,25 @@ int dae_reserve(dae_ctx* ctx, dae_buf& b, size_t bytes);
 
 static inline int dae_round_up(int x, int m) { return (x + m - 1) / m * m; }
 
+inline bool dae_first_use(dae_ctx* ctx, const void* key) { return ctx->first_use_done.insert(key).second; }
+// before the first launch of `kernel` on this context: raise its dynamic-LDS limit (the kernel is its own first-use key)
+template <class K>
+inline hipError_t dae_lds_limit_once(dae_ctx* ctx, K* kernel, size_t bytes)
+{
+    const void* f = reinterpret_cast<const void*>(kernel);
+    return dae_first_use(ctx, f) ? hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) : hipSuccess;
+}
+// a launch that can be the profiled one: when a pair of profile events is armed (dae_profile_*, api.hip) it takes the pair --
+// e0 / e1 are left alone otherwise -- and notes the kernel's name
+inline void dae_take_profile_events(dae_ctx* ctx, const char* kernel, hipEvent_t& e0, hipEvent_t& e1)
+{
+    if (!ctx->prof_armed) return;
+    e0 = ctx->prof_ev[ctx->prof_used]; e1 = ctx->prof_ev[ctx->prof_used + 1];
+    ctx->prof_armed = false;
+    ctx->prof_used += 2;
+    ctx->prof_kernel = kernel;
+}
+
 // The library reads no environment variable: an A/B of two kernel variants is two source trees, each built with build()
 // (DESIGN.md section 8).
 
@@ -243,13 +262,6 @@ constexpr uint32_t DAE_KEY_NEG_INF = 0x007FFFFFU;   // dae_okey(-inf): "absent" 
 // ---------------------------------------------------------------------------------------------
 // launchers (each defined next to its kernels)
 // ---------------------------------------------------------------------------------------------
-dae_rowgeom dae_row_geometry(int B, int Hp);
-dae_rowgeom dae_row_geometry_bf16(int B, int Hp);
-int dae_launch_prepack_bf16(dae_ctx* ctx, const float* W, const float* b, int V, int H,
-                            int col_lo, int col_hi, int exact = 0);
-// row_bad (nullable): [g.Bpad] int32, 1 where a row of h has an entry outside [0, 1] (the exact mode's precondition)
-int dae_launch_pack_h_bf16(dae_ctx* ctx, const float* h, int B, int H, const dae_rowgeom& g, int* row_bad = nullptr);
-
 // encode.hip
 int dae_launch_encode(dae_ctx* ctx, const int32_t* row_ptr, const int32_t* col, const float* val,
                       const float* W_enc, const float* b_enc, int V, int H, int B,
@@ -257,17 +269,25 @@ int dae_launch_encode(dae_ctx* ctx, const int32_t* row_ptr, const int32_t* col, 
                       float* h_packed, int G, int RB, float* sg_out = nullptr,
                       float* xhat_out = nullptr, unsigned short* h_packed16 = nullptr, int NS = 0);
 
-// decode_f32.hip
+// prepack.hip
 int dae_launch_prepack_f32(dae_ctx* ctx, const float* W, const float* b, int V, int H,
                            int col_lo, int col_hi);
+int dae_launch_prepack_bf16(dae_ctx* ctx, const float* W, const float* b, int V, int H,
+                            int col_lo, int col_hi, int exact = 0);
 int dae_launch_pack_h(dae_ctx* ctx, const float* h, int B, int H, const dae_rowgeom& g);
+// row_bad (nullable): [g.Bpad] int32, 1 where a row of h has an entry outside [0, 1] (the exact mode's precondition)
+int dae_launch_pack_h_bf16(dae_ctx* ctx, const float* h, int B, int H, const dae_rowgeom& g, int* row_bad = nullptr);
 int dae_launch_tile_iota(dae_ctx* ctx, int* dst, int ntiles);      // dst[i] = i
 // (re)build pk.order for `nrank` rankable columns; the first n_samp entries are the threshold sample
-int dae_filter_block_tiles(const dae_rowgeom& g, int n_items, int dtype, int Hp, bool mixed = false);
 int dae_launch_tile_order(dae_ctx* ctx, dae_packed& pk, int nrank, int n_samp, int S);
 // band[0 .. n_samp): the sample of `order` dealt to the phase-A launch's slots so that the tiles ONE workgroup decodes in a round
 // (item = round * nb_rg * waves + wave * nb_rg + bir) come from `waves` different popularity bands; band[n_samp ..) = order
 int dae_launch_tile_band(dae_ctx* ctx, const int* order, int ntiles, int n_samp, int nb_rg, int waves, int* band);
+
+// decode_f32.hip: the host planners, and the launchers that choose between a hidden-256 kernel and the generic one
+dae_rowgeom dae_row_geometry(int B, int Hp);
+dae_rowgeom dae_row_geometry_bf16(int B, int Hp);
+int dae_filter_block_tiles(const dae_rowgeom& g, int n_items, int dtype, int Hp, bool mixed = false);
 bool dae_sample_wave_groups(const dae_rowgeom& g, int Hp, int n_samp);
 
 struct dae_tileset {        // which wave tiles a decode launch walks
@@ -309,6 +329,11 @@ int dae_launch_decode_loss_rowmajor(dae_ctx* ctx, const dae_rowgeom& g, int B, i
 int dae_launch_decode_loss_dh(dae_ctx* ctx, const dae_rowgeom& g, int B, int V, int H, const float* W, const float* bias,
                               const float* h, float inv_n_batch, float* dzT, int64_t ldT, float* loss_part, float* part, int Bpad64);
 
+// decode_generic.hip: decode_f32_kernel for (epilogue EPI_*, operand type DT_*, row-group height) -- decode_common.h
+struct dae_decp;
+int dae_launch_decode_generic(dae_ctx* ctx, int epi, int dt, const dae_rowgeom& g, const dae_decp& p);
+int dae_launch_decode_gmax_half(dae_ctx* ctx, const dae_rowgeom& g, const dae_decp& p);
+
 // train.hip
 int dae_train_step_f32(dae_ctx* ctx,
         const int32_t* x_row_ptr, const int32_t* x_col, const float* x_val,
@@ -335,7 +360,6 @@ int dae_train_shard_finish_f32(dae_ctx* ctx, const float* dh, const int32_t* x_r
 int dae_launch_grad_w(dae_ctx* ctx, const float* dzT, int64_t ldT, const float* h, int H, int B, int V,
                       float* gW, float* gb);
 int dae_launch_grad_h(dae_ctx* ctx, const float* dzT, int64_t ldT, const float* W, int H, int V, int B, float* dh);
-inline bool dae_first_use(dae_ctx* ctx, const void* key) { return ctx->first_use_done.insert(key).second; }
 
 int dae_launch_adam_rows(dae_ctx* ctx, int mode, float* param, float* m, float* v, float* grad, int32_t* last,
                          int32_t* mark, float* lr_tab, int n_rows, int row_len, const int32_t* rows,

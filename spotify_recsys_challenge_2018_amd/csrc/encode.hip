@@ -11,7 +11,7 @@
 // to 32 independent 1 KiB row reads (32 KiB) are in flight per wave, which is what hides HBM /
 // Infinity-Cache latency at batch 256 where only 256 waves exist.
 //
-// Optionally the hidden row is also written in the MFMA B-operand order of decode_f32.hip
+// Optionally the hidden row is also written in the MFMA B-operand order of prepack.hip's pack_h kernels
 // (the fused dae_score_topk path), which removes the separate re-pack pass.
 #include "dae_internal.h"
 
@@ -51,7 +51,7 @@ struct EncP {
     float* h_out;        // [B,H] row-major or null
     float* hp;           // packed [n_rg][G][RB][2][32][4] or null
     int G, RB;           // packed geometry (G = Hp/8, RB = R_TILE/32)
-    unsigned short* hp16;   // bf16 image [n_rg][NS][RB][64][8] (decode_f32.hip pack_h_bf16_kernel's layout) or null:
+    unsigned short* hp16;   // bf16 image [n_rg][NS][RB][64][8] (prepack.hip pack_h_bf16_kernel's layout) or null:
     int NS;                 // the bf16 decode reads the hidden rows rounded (RNE) straight from the encode; NS = Hp/16
     float* sg_out;       // [B,H] sigmoid BEFORE hidden dropout (training backward) or null
     float* xhat_out;     // [nnz] normalised, dropped-out input weights (training backward) or null

@@ -28,7 +28,7 @@
 //          their order -- the value the fp32 path ranks -- tested against the promise (bound guard, as refine.hip) and left
 //          as one compact (y, column) list per row for the selection kernel.  Rows with both weights 0 (no input, no title)
 //          have y = +0 everywhere: they list nothing and get the first k + n_seeds columns directly.
-// BOUNDS.  DAE side: hidden rows lie in [0, 1], eps_c of exact_bounds_kernel (decode_f32.hip) as in the plain exact mode.
+// BOUNDS.  DAE side: hidden rows lie in [0, 1], eps_c of exact_bounds_kernel (prepack.hip) as in the plain exact mode.
 // Title side: the features are ReLU maxima, not confined to [0, 1]; with F_r = max_k |feat[r][k]| every term of that
 // derivation that is linear in the hidden row scales by F_r:
 //     |z16_t - z32_t| <= F_r alpha_c + beta_c,
@@ -41,21 +41,17 @@
 // results lie within 6e-6 of the canonical ones) before they are compared; the guard compares LOGITS, which need none.
 #include <climits>
 
-#include "dae_internal.h"
+#include "decode_common.h"
 #include "rank_lds.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ bf16x8 as_bf16x8(const uint4 u) { return __builtin_bit_cast(bf16x8, u); }
 
 constexpr int MX_RB = 3;            // row blocks of 32 playlists per row group: 96 rows x 704 k x 2 B = 132 KiB of LDS
 constexpr int MX_NW = 8;            // waves per workgroup (two per SIMD: one's epilogue under the other's MFMAs)
 constexpr int MX_QR = 8;            // W ring depth (steps)
 constexpr int MX_REF_CAP = 8192;    // survivors per row the refine launch's compact lists hold
 
-// the mixed score with the operations of mix_scores_kernel (title.hip) / the fp32 mix epilogue (decode_f32.hip), in their order
+// the mixed score with the operations of mix_scores_kernel (title.hip) / the fp32 mix epilogue (decode_generic.hip), in their order
 __device__ __forceinline__ float mixf(float zt, float zd, float wt, float wp)
 {
     const float ts = dae_sigmoidf(zt) * wt;

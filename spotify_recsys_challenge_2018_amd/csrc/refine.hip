@@ -19,7 +19,7 @@
 //      memory, was the limit (14 us per launch) -- and re-distributed through 5 KiB of LDS per wave (80-byte row
 //      stride: conflict-free b128 accesses both ways); 8 blocks of 16 k (32 x 16 bytes per lane) are in flight.
 // The selection kernel (topk.hip, PairSrc) then ranks the lists as it does for the other modes.
-#include "dae_internal.h"
+#include "decode_common.h"
 #include "rank_lds.h"
 
 namespace {
@@ -377,7 +377,7 @@ __device__ __forceinline__ void refine_body(const RefineP& p)
 
     // BOUND GUARD.  The filter launch promised u - 2 eps_c <= z32 <= u for the stored upper bound u of column c; the
     // term of eps_c that covers the accumulation inside v_mfma_f32_32x32x16_bf16 rests on an error MODEL of that
-    // instruction (decode_f32.hip exact_bounds_kernel), so every recomputed survivor is tested against the promise --
+    // instruction (prepack.hip exact_bounds_kernel), so every recomputed survivor is tested against the promise --
     // both numbers are in registers -- and a violation is COUNTED in the context's guard words (dae_exact_guard_read):
     // a column whose bound fails may have a sibling that was wrongly filtered out, and the caller must know.
     // (The lower end is taken two floats down: the subtraction rounds.)
@@ -536,7 +536,7 @@ __device__ __forceinline__ void refine_body(const RefineP& p)
 // launch that decodes the whole vocabulary.  But the rows of a launch mostly want the SAME decoder rows (the popular head of
 // the vocabulary: on the bench model every playlist has the same 534 candidates, on a trained one most of them), and the
 // canonical chain acc = fmaf(h[k], W[c][k], acc), k ascending, is what v_mfma_f32_32x32x2_f32 performs for 32 columns x 32
-// playlists at a time (the fp32 kernels of decode_f32.hip: A = W, B = h, MFMA (g, e) takes k = 8 g + 2 e + hi).  So, for
+// playlists at a time (the fp32 kernels of decode_f32.hip and decode_generic.hip: A = W, B = h, MFMA (g, e) takes k = 8 g + 2 e + hi).  So, for
 // launches of many rows, BEFORE the per-row launch:
 //   workgroup (segment s, group of 32 playlists): the candidates the filter workgroup s listed for those rows -> the UNION of
 //   their columns (an LDS hash table, dense ranks by a scan) -> per tile of 32 union columns the 128 MFMAs over the group's
@@ -547,7 +547,6 @@ __device__ __forceinline__ void refine_body(const RefineP& p)
 // A decoder row is fetched once per (segment, 32 playlists) instead of once per playlist; columns of the union that a
 // playlist did not list are computed for it and ignored (the matrix pipe is idle in this launch anyway).  Bits: identical --
 // the same instruction, operand order and k order as the fp32 path's logits, which the lane-owned fmaf chain reproduces.
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int RS_ROWS = 32;            // playlists per workgroup (one MFMA row block)
 constexpr int RS_PR = 128;             // candidates per playlist and round
 constexpr int RS_PMAX = RS_ROWS * RS_PR;

@@ -7,11 +7,10 @@
 // dae_decode_dense on the features this file produces.  What is here is small per playlist (25 characters,
 // 2.3 MFLOP): one workgroup per playlist, the embedded title in LDS, one thread per (size, filter).
 // Padding characters (-1, spotify_reader.py:36) embed to zero (tf.nn.embedding_lookup's GPU behaviour).
-#include "dae_internal.h"
+#include "decode_common.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int T_MAX_SIZES = DAE_TITLE_MAX_SIZES;
 constexpr int T_MAX_LEN = 64;
 constexpr int T_MAX_EMB = 128;
@@ -428,9 +427,7 @@ __global__ __launch_bounds__(256) void title_loss_kernel(const float* __restrict
             const float a = wt[r];
             const float yp = st * a + dae[(size_t)r * ld_d + v] * wp[r];
             const float t = y[(size_t)r * V + v];
-            const float a1 = yp + 1e-10f, a0 = 1.0f - yp + 1e-10f;
-            loss -= t * __logf(a1) + 0.55f * (1.0f - t) * __logf(a0);
-            dz = -(t / a1 - 0.55f * (1.0f - t) / a0) * inv_nb * a * st * (1.0f - st);
+            dz = dae_loss_head_mixed(yp, t, inv_nb, loss) * a * st * (1.0f - st);
         }
         tile[ty + 8 * i][tx] = dz;                                    // [r local][v local]
     }

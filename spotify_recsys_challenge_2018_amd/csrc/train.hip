@@ -4,7 +4,7 @@
 //
 //   forward   K1 encode with dropout (encode.hip) -> K5 decode GEMM whose epilogue turns logits
 //             into the weighted-BCE loss and dL/dz, every element taken as a negative
-//             (decode_f32.hip EPI_LOSS), writing dz^T [V,B]; loss_fixup_kernel redoes the positives
+//             (decode_f32.hip; decode_generic.hip EPI_LOSS), writing dz^T [V,B]; loss_fixup_kernel redoes the positives
 //             of the target CSR (no dense target matrix)
 //   K6        gW_dec[v,:] = sum_r dz[r,v] h[r,:]   (+ gb_dec = column sums)      contraction B
 //   K7        dh[r,:]     = sum_v dz[r,v] W_dec[v,:]  split over V, partials reduced   contraction V
@@ -16,7 +16,7 @@
 // both, and the 4 (2) tiles a wave owns along i (j) are interleaved (hidden = hc0 + 4 i + a) so
 // that one float4 (float2) per lane feeds 4 (2) MFMAs.  Summation orders differ from the oracle's
 // float64 reference: parity is by tolerance (tests/test_gpu_train.py), not bitwise.
-#include "dae_internal.h"
+#include "decode_common.h"
 
 namespace {
 
@@ -34,18 +34,8 @@ __device__ __forceinline__ void nt_st4(float* a, const float4 x)
 }
 
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-template <int N> struct IntC { static constexpr int value = N; };
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+typedef bf16x8 bf16x8_t;
 
-// two floats -> packed bf16 pair, round to nearest even (v_cvt_pk_bf16_f32 on gfx950)
-__device__ __forceinline__ unsigned pk_bf16(float a, float b)
-{
-    const f32x2_t v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-}
 // eight floats -> the 8 k-slots a lane holds of one 32x32x16 bf16 MFMA operand
 __device__ __forceinline__ bf16x8_t pk_bf16x8(float a0, float a1, float a2, float a3, float a4, float a5, float a6,
                                               float a7)
@@ -54,7 +44,7 @@ __device__ __forceinline__ bf16x8_t pk_bf16x8(float a0, float a1, float a2, floa
 }
 
 // ---- the positives of the loss -----------------------------------------------------------------------
-// K5 (decode_f32.hip, EPI_LOSS) treats all B x V elements as negatives.  A batch holds ~100 positives per row
+// K5 (decode_f32.hip; decode_generic.hip EPI_LOSS) treats all B x V elements as negatives.  A batch holds ~100 positives per row
 // out of 170 000 columns, so instead of a dense [B, V] target matrix (174 MB zeroed, scattered into and read
 // back per step) each target entry (row, col, y) is redone here: the same logit -- the fmaf chain over
 // k = 0..H-1 from +0, then + bias, which is what the fp32 MFMA computes -- then the full loss term and
@@ -62,13 +52,6 @@ __device__ __forceinline__ bf16x8_t pk_bf16x8(float a0, float a1, float a2, floa
 // One workgroup per row (h row in LDS), one thread per target entry.  The target CSR holds one entry per
 // (row, col) (include/dae_hip.h: the CSR contract), so no two threads own the same element.
 constexpr int FIX_MAXH = 1024;
-// value of the bf16 nearest (ties to even) to f, as the prepack / pack_h kernels round the MFMA operands
-__device__ __forceinline__ float bf16_value(float f)
-{
-    unsigned u = __float_as_uint(f);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return __uint_as_float(u & 0xFFFF0000u);
-}
 // BF16: the forward GEMM ran on bf16 operands (dae_set_train_dtype): W and h are rounded the same way here
 // DZ16: dL/dz is kept as bf16 (the bf16 backward GEMMs read it as such)
 // CORR (with BF16 and DZ16: the forward launch has already folded dh = dz W_dec into itself with every element a negative):
@@ -94,7 +77,7 @@ __global__ __launch_bounds__(256) void loss_fixup_kernel(const int32_t* __restri
     const int H4 = H >> 2;
     for (int i = tid; i < H4; i += 256) {
         float4 v = reinterpret_cast<const float4*>(h + (size_t)row * H)[i];
-        if (BF16) v = make_float4(bf16_value(v.x), bf16_value(v.y), bf16_value(v.z), bf16_value(v.w));
+        if (BF16) v = make_float4(dae_bf16_value(v.x), dae_bf16_value(v.y), dae_bf16_value(v.z), dae_bf16_value(v.w));
         sh[i] = v;
     }
     __syncthreads();
@@ -127,7 +110,7 @@ __global__ __launch_bounds__(256) void loss_fixup_kernel(const int32_t* __restri
                 for (int u = 0; u < 16; ++u) wv[u] = w[k + u];
 #pragma unroll
                 for (int u = 0; u < 16; ++u) {
-                    if (BF16) wv[u] = make_float4(bf16_value(wv[u].x), bf16_value(wv[u].y), bf16_value(wv[u].z), bf16_value(wv[u].w));
+                    if (BF16) wv[u] = make_float4(dae_bf16_value(wv[u].x), dae_bf16_value(wv[u].y), dae_bf16_value(wv[u].z), dae_bf16_value(wv[u].w));
                     const float4 hv = sh[k + u];
                     z = fmaf(wv[u].x, hv.x, z); z = fmaf(wv[u].y, hv.y, z);
                     z = fmaf(wv[u].z, hv.z, z); z = fmaf(wv[u].w, hv.w, z);
@@ -139,7 +122,7 @@ __global__ __launch_bounds__(256) void loss_fixup_kernel(const int32_t* __restri
                 for (int u = 0; u < 8; ++u) wv[u] = w[k + u];
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
-                    if (BF16) wv[u] = make_float4(bf16_value(wv[u].x), bf16_value(wv[u].y), bf16_value(wv[u].z), bf16_value(wv[u].w));
+                    if (BF16) wv[u] = make_float4(dae_bf16_value(wv[u].x), dae_bf16_value(wv[u].y), dae_bf16_value(wv[u].z), dae_bf16_value(wv[u].w));
                     const float4 hv = sh[k + u];
                     z = fmaf(wv[u].x, hv.x, z); z = fmaf(wv[u].y, hv.y, z);
                     z = fmaf(wv[u].z, hv.z, z); z = fmaf(wv[u].w, hv.w, z);
@@ -148,17 +131,11 @@ __global__ __launch_bounds__(256) void loss_fixup_kernel(const int32_t* __restri
             for (; k < H4; ++k) {
                 float4 wv = w[k];
                 const float4 hv = sh[k];
-                if (BF16) wv = make_float4(bf16_value(wv.x), bf16_value(wv.y), bf16_value(wv.z), bf16_value(wv.w));
+                if (BF16) wv = make_float4(dae_bf16_value(wv.x), dae_bf16_value(wv.y), dae_bf16_value(wv.z), dae_bf16_value(wv.w));
                 z = fmaf(wv.x, hv.x, z); z = fmaf(wv.y, hv.y, z); z = fmaf(wv.z, hv.z, z); z = fmaf(wv.w, hv.w, z);
             }
             z += bias[lc];
-            const float pr = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * z));
-            const float a1 = pr + 1e-10f, a0 = 1.0f - pr + 1e-10f;
-            const float l1 = __builtin_amdgcn_logf(a1), l0 = __builtin_amdgcn_logf(a0);
-            // L(y) - L(0) = -ln2 * y * (log2 a1 - 0.55 log2 a0)
-            corr -= 0.69314718f * y * (l1 - 0.55f * l0);
-            const float dzv = -(y * __builtin_amdgcn_rcpf(a1) - 0.55f * (1.0f - y) * __builtin_amdgcn_rcpf(a0)) *
-                              pr * (1.0f - pr) * inv_nb;
+            const float dzv = dae_loss_head(dae_train_sigmoid(z), y, inv_nb, corr);
             if (DZ16) {
                 unsigned short* dst = reinterpret_cast<unsigned short*>(dzT) + (size_t)lc * ldT + row;
                 const unsigned short nw = (unsigned short)(pk_bf16(dzv, 0.0f) & 0xFFFFu);
@@ -184,15 +161,15 @@ __global__ __launch_bounds__(256) void loss_fixup_kernel(const int32_t* __restri
 #pragma unroll
                     for (int u = 0; u < 8; ++u) {
                         const float d = cdel[e + 4 * u];
-                        a.x = fmaf(d, bf16_value(wv[u].x), a.x); a.y = fmaf(d, bf16_value(wv[u].y), a.y);
-                        a.z = fmaf(d, bf16_value(wv[u].z), a.z); a.w = fmaf(d, bf16_value(wv[u].w), a.w);
+                        a.x = fmaf(d, dae_bf16_value(wv[u].x), a.x); a.y = fmaf(d, dae_bf16_value(wv[u].y), a.y);
+                        a.z = fmaf(d, dae_bf16_value(wv[u].z), a.z); a.w = fmaf(d, dae_bf16_value(wv[u].w), a.w);
                     }
                 }
                 for (; e < n; e += 4) {
                     const float4 w1 = reinterpret_cast<const float4*>(Wd + (size_t)ccol[e] * H)[k4];
                     const float d = cdel[e];
-                    a.x = fmaf(d, bf16_value(w1.x), a.x); a.y = fmaf(d, bf16_value(w1.y), a.y);
-                    a.z = fmaf(d, bf16_value(w1.z), a.z); a.w = fmaf(d, bf16_value(w1.w), a.w);
+                    a.x = fmaf(d, dae_bf16_value(w1.x), a.x); a.y = fmaf(d, dae_bf16_value(w1.y), a.y);
+                    a.z = fmaf(d, dae_bf16_value(w1.z), a.z); a.w = fmaf(d, dae_bf16_value(w1.w), a.w);
                 }
                 cacc_r[j] = a;
             }
@@ -1630,26 +1607,15 @@ int train_decode_backward(dae_ctx* ctx, const TrainPlan& t, int Vl, int H, int B
         // second wave covers the dz^T load latency and the gW stores of the first
         if (NA == 4 && t.dtype == DAE_DTYPE_BF16) {          // (NA == 4 is H % 128 == 0: dz^T is bf16, t.dz16)
             const size_t lds_t = (size_t)(((B + 31) & ~31) >> 4) * 4 * 64 * sizeof(uint4);
-            static const char k6t_key = 0;
-            if (dae_first_use(ctx, &k6t_key))
-                DAE_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&grad_wdec_t_kernel<8>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &grad_wdec_t_kernel<8>, 160 * 1024));
             if (p.ad_m) {
-                static const char attr_t32_key = 0;
-                if (dae_first_use(ctx, &attr_t32_key)) {
-                    DAE_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&grad_wdec_t32_kernel<8, true>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-                    DAE_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&grad_wdec_t32_kernel<8, false>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-                }
+                DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &grad_wdec_t32_kernel<8, true>, 64 * 1024));
+                DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &grad_wdec_t32_kernel<8, false>, 64 * 1024));
                 if (((B + 31) & ~31) == 256) hipLaunchKernelGGL((grad_wdec_t32_kernel<8, true>), grid, dim3(512), lds_t, st, p);
                 else hipLaunchKernelGGL((grad_wdec_t32_kernel<8, false>), grid, dim3(512), lds_t, st, p);
             } else
             if (((B + 31) & ~31) == 256) {
-                static const char attr_tf_key = 0;
-                if (dae_first_use(ctx, &attr_tf_key))
-                    DAE_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&grad_wdec_t_kernel<8, true>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+                DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &grad_wdec_t_kernel<8, true>, 64 * 1024));
                 hipLaunchKernelGGL((grad_wdec_t_kernel<8, true>), grid, dim3(512), lds_t, st, p);
             } else
             hipLaunchKernelGGL((grad_wdec_t_kernel<8>), grid, dim3(512), lds_t, st, p);
@@ -1658,20 +1624,12 @@ int train_decode_backward(dae_ctx* ctx, const TrainPlan& t, int Vl, int H, int B
             if (p.ad_m && H == 256 && (Bp32 & 15) == 0) {
                 // (the ring walks the dz^T row four float4 at a time: whole groups of 16 playlists)
                 const size_t lds_f = (size_t)(Bp32 >> 1) * 64 * sizeof(float4);
-                static const char attr_tf32_key = 0;
-                if (dae_first_use(ctx, &attr_tf32_key)) {
-                    DAE_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&grad_wdec_t32_f32_kernel<8, true>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-                    DAE_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&grad_wdec_t32_f32_kernel<8, false>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-                }
+                DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &grad_wdec_t32_f32_kernel<8, true>, 128 * 1024));
+                DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &grad_wdec_t32_f32_kernel<8, false>, 128 * 1024));
                 if (Bp32 == 256) hipLaunchKernelGGL((grad_wdec_t32_f32_kernel<8, true>), grid, dim3(512), lds_f, st, p);
                 else hipLaunchKernelGGL((grad_wdec_t32_f32_kernel<8, false>), grid, dim3(512), lds_f, st, p);
             } else {
-                static const char attr8t_key = 0;
-                if (dae_first_use(ctx, &attr8t_key))
-                    DAE_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&grad_wdec_kernel<4, 8, true>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &grad_wdec_kernel<4, 8, true>, 160 * 1024));
                 hipLaunchKernelGGL((grad_wdec_kernel<4, 8, true>), grid, dim3(512), lds, st, p);
             }
         } else if (NA == 2) hipLaunchKernelGGL(grad_wdec_kernel<2>, grid, blk, lds, st, p);
@@ -1786,11 +1744,7 @@ int dae_launch_grad_w(dae_ctx* ctx, const float* dzT, int64_t ldT, const float* 
     if (nb < DAE_NUM_XCD) nb = DAE_NUM_XCD;
     p.nb_half = nb;
     const size_t lds = (size_t)((B + 31) & ~31) * 32 * NA * sizeof(float);
-    static const char attr_key = 0;
-    if (dae_first_use(ctx, &attr_key)) {
-        DAE_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&grad_wdec_kernel<4>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
+    DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &grad_wdec_kernel<4>, 160 * 1024));
     const dim3 grid(p.n_half * nb), blk(256);
     if (NA == 4) hipLaunchKernelGGL(grad_wdec_kernel<4>, grid, blk, lds, ctx->stream, p);
     else if (NA == 2) hipLaunchKernelGGL(grad_wdec_kernel<2>, grid, blk, lds, ctx->stream, p);
