@@ -357,10 +357,16 @@ int dae_train_shard_finish_f32(dae_ctx* ctx, const float* dh, const int32_t* x_r
                                const float* b_dec_loc, int col_lo, int col_hi, int H, int B, int tied,
                                float ikp, float kp, uint32_t seed, float reg_lambda,
                                float* gW_enc_loc, float* gb_enc, float* gW_dec_loc, float* gb_dec_loc);
-int dae_launch_grad_w(dae_ctx* ctx, const float* dzT, int64_t ldT, const float* h, int H, int B, int V,
-                      float* gW, float* gb);
 int dae_launch_grad_h(dae_ctx* ctx, const float* dzT, int64_t ldT, const float* W, int H, int V, int B, float* dh);
 
+// grad_wdec.hip (K6).  dae_armed_adam: the dense TF1-Adam of the [V, H] tensor p that an armed K6 applies in its epilogue
+struct dae_armed_adam { float* p; float* m; float* v; float alpha, b1, b2, eps; };
+int dae_launch_k6(dae_ctx* ctx, const float* dzT, int64_t ldT, int dz16, const float* h, int H, int B, int V, float* gW,
+                  float* gb, const dae_armed_adam* arm, int small_v);
+int dae_launch_grad_w(dae_ctx* ctx, const float* dzT, int64_t ldT, const float* h, int H, int B, int V,
+                      float* gW, float* gb);
+
+// adam.hip
 int dae_launch_adam_rows(dae_ctx* ctx, int mode, float* param, float* m, float* v, float* grad, int32_t* last,
                          int32_t* mark, float* lr_tab, int n_rows, int row_len, const int32_t* rows,
                          const int32_t* n_listed_dev, int n_listed_max, float lr_t, float beta1, float beta2,

@@ -6,35 +6,21 @@
 //             into the weighted-BCE loss and dL/dz, every element taken as a negative
 //             (decode_f32.hip; decode_generic.hip EPI_LOSS), writing dz^T [V,B]; loss_fixup_kernel redoes the positives
 //             of the target CSR (no dense target matrix)
-//   K6        gW_dec[v,:] = sum_r dz[r,v] h[r,:]   (+ gb_dec = column sums)      contraction B
+//   K6        gW_dec[v,:] = sum_r dz[r,v] h[r,:]   (+ gb_dec = column sums)      contraction B   (grad_wdec.hip)
 //   K7        dh[r,:]     = sum_v dz[r,v] W_dec[v,:]  split over V, partials reduced   contraction V
 //   K8        dpre = dh * dropout-mask/kp * s(1-s); gb_enc; gW_enc[c,:] += xhat[r,c] dpre[r,:]
-//   K9        TF1 Adam, dense (moments decay on zero-gradient rows too)
+//   K9        TF1 Adam, dense (moments decay on zero-gradient rows too)                            (adam.hip)
 //
-// Both backward GEMMs use v_mfma_f32_32x32x2_f32 with D[i = hidden unit][j = v or r]; operands are
-// read in their natural row-major layouts because the contraction index is the slow dimension of
-// both, and the 4 (2) tiles a wave owns along i (j) are interleaved (hidden = hc0 + 4 i + a) so
-// that one float4 (float2) per lane feeds 4 (2) MFMAs.  Summation orders differ from the oracle's
-// float64 reference: parity is by tolerance (tests/test_gpu_train.py), not bitwise.
-#include "decode_common.h"
+// This file: the three step entry points and their planning (TrainPlan), loss_fixup_kernel, K7, K8 and the small kernels.
+// K7 (grad_hidden_kernel) uses v_mfma_f32_32x32x2_f32 (one 32x32x16 bf16 MFMA per 8 k-steps under dae_set_train_dtype) with
+// operands read in their natural row-major layouts because the contraction index is the slow dimension of both; the 4 (2)
+// tiles a wave owns along the hidden dimension are interleaved (hidden = hc0 + 4 i + a) so that one float4 (float2) per lane
+// feeds 4 (2) MFMAs.  Which MFMA operand the hidden unit is differs by instance (NA = 4 and the transposed K6 forms put it
+// on the lane, the others on the register).  Summation orders differ from the oracle's float64 reference: parity is by
+// tolerance (tests/test_gpu_train.py), not bitwise.
+#include "train_common.h"
 
 namespace {
-
-// streamed-once 16-byte accesses (Adam state: every byte is read and written exactly once per step)
-typedef float nt4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 nt_ld4(const float* a)
-{
-    const nt4_t t = __builtin_nontemporal_load(reinterpret_cast<const nt4_t*>(a));
-    return make_float4(t.x, t.y, t.z, t.w);
-}
-__device__ __forceinline__ void nt_st4(float* a, const float4 x)
-{
-    const nt4_t t = {x.x, x.y, x.z, x.w};
-    __builtin_nontemporal_store(t, reinterpret_cast<nt4_t*>(a));
-}
-
-
-typedef bf16x8 bf16x8_t;
 
 // eight floats -> the 8 k-slots a lane holds of one 32x32x16 bf16 MFMA operand
 __device__ __forceinline__ bf16x8_t pk_bf16x8(float a0, float a1, float a2, float a3, float a4, float a5, float a6,
@@ -200,676 +186,6 @@ __global__ __launch_bounds__(256) void loss_fixup_kernel(const int32_t* __restri
     }
 }
 
-// ---- K6: gW[v, hc] (+)= sum_r dz[r, v] * h[r, hc];  gb[v] = sum_r dz[r, v] ----------------------
-// block = 4 waves sharing the LDS image of h[:, hc0 : hc0+128] (K = B <= 256 rows); a wave owns
-// tiles of 64 vocabulary columns (2 MFMA tiles, v = v0 + 2 j + b) x 128 hidden units (4 tiles).
-struct GwP {
-    const float* dzT; int64_t ldT;    // [V, ldT] (dz transposed, rows zero padded to ldT)
-    const float* h; int H, B, V;
-    float* gW;                        // [V, H]
-    float* gb;                        // [V] (written by the hc0 == 0 blocks) or null
-    int accumulate;                   // gW += instead of =
-    int n_half, nb_half;              // H / 128 hidden halves, blocks per half
-    // dense TF1-Adam of the [V, H] tensor `ad_p` applied in the epilogue instead of writing gW (dae_arm_decoder_adam)
-    float* ad_p; float* ad_m; float* ad_v; float ad_alpha, ad_b1, ad_b2, ad_eps;
-};
-
-// fp32 operands (the bf16 training step's K6 is grad_wdec_t_kernel / grad_wdec_t32_kernel below).
-// NA = hidden tiles per wave (4, 2 or 1): a "half" is 32*NA hidden units, hidden = hc0 + NA*i + a
-// TR (NA = 4): the two MFMA operands swapped -- D[i = vocabulary row of the lane pair][j = hidden lane] instead of
-// D[i = hidden][j = vocabulary row].  Loads, LDS image and column sums are unchanged; what changes is that a lane of the
-// accumulators is a hidden unit (hc0 + 4 j + a), so the epilogue writes 512 contiguous bytes of one gW row per half-wave
-// instead of 16-byte pieces of 32 rows -- the same shape the transposed bf16 kernel (grad_wdec_t_kernel) has.
-template <int NA, int NW = 4, bool TR = false>
-__global__ __launch_bounds__(NW * 64, 1) void grad_wdec_kernel(const GwP p)
-{
-    extern __shared__ __attribute__((aligned(16))) float lds[];     // [Bp][32*NA] floats
-    constexpr int HW = 32 * NA;
-    const int tid = threadIdx.x, lane = tid & 63, hi = lane >> 5, j = lane & 31;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int gs = DAE_NUM_XCD * p.n_half;
-    const int q = blockIdx.x / gs, rem = blockIdx.x % gs;
-    const int half = rem / DAE_NUM_XCD;
-    const int bir = q * DAE_NUM_XCD + (rem % DAE_NUM_XCD);
-    const int hc0 = half * HW;
-    const int Bp = (p.B + 31) & ~31;           // rows padded to whole 32-row groups (zero rows)
-
-    // LDS image of h[:, hc0 : hc0 + HW]: 8 independent 16-byte loads in flight per thread.  (One 4-byte load ->
-    // wait -> ds_write per iteration, 128 iterations per thread, was ~80 us of this kernel's 280: every iteration
-    // pays an L2 round trip.)
-    if ((reinterpret_cast<uintptr_t>(p.h) & 15) == 0 && (p.H & 3) == 0) {
-        constexpr int HW4 = HW / 4, NT = NW * 64;
-        const int n4 = Bp * HW4;
-        float4* lds4 = reinterpret_cast<float4*>(lds);
-        for (int i0 = tid; i0 < n4; i0 += 8 * NT) {
-            float4 v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int i = min(i0 + u * NT, n4 - 1);
-                const int r = i / HW4, c4 = i - r * HW4;
-                v[u] = *reinterpret_cast<const float4*>(p.h + (size_t)min(r, p.B - 1) * p.H + hc0 + 4 * c4);
-                if (r >= p.B) v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int i = i0 + u * NT;
-                if (i < n4) lds4[i] = v[u];
-            }
-        }
-    } else {
-        for (int i = tid; i < Bp * HW; i += NW * 64) {
-            const int r = i / HW, c = i - r * HW;
-            lds[i] = r < p.B ? p.h[(size_t)r * p.H + hc0 + c] : 0.0f;
-        }
-    }
-    __syncthreads();
-
-    const int n_tiles = (p.V + 63) / 64;
-    const int n_ws = p.nb_half * NW;
-    for (int t = bir * NW + wave; t < n_tiles; t += n_ws) {
-        const int v0 = t * 64;
-        const int vcol = v0 + 2 * j;                                 // this lane's 2 columns
-        const bool ok0 = vcol < p.V, ok1 = vcol + 1 < p.V;
-        f32x16 acc[NA][2];
-#pragma unroll
-        for (int a = 0; a < NA; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.0f;
-        float cs0 = 0.f, cs1 = 0.f;
-
-        // B operand from dz^T [V][ldT]: the tile's 64 columns x B rows are ONE contiguous 64 KiB
-        // block there (a strip of row-major dz is 256-byte pieces at a 4*V-byte stride: every piece
-        // another DRAM page and TLB entry -- 584 us measured).  A lane owns columns vcol, vcol+1 =
-        // two rows of dz^T; one float4 per row carries 4 consecutive playlists = 2 k-steps
-        // (playlist 4q + 2*step + hi).
-        const float* t0p = p.dzT + (size_t)(ok0 ? vcol : 0) * p.ldT;
-        const float* t1p = p.dzT + (size_t)(ok1 ? vcol + 1 : 0) * p.ldT;
-// unconditional loads (conditional writes to these arrays sent them to scratch memory): columns
-// past V read row 0 and accumulate values that are never stored; the prefetch issued in the last
-// iteration re-reads the last group
-#define GW_LOAD(T0, T1, R0)                                                                    \
-        _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) {                                     \
-            const int r4 = min((R0) + 4 * q_, Bp4 - 4);                                        \
-            T0[q_] = *reinterpret_cast<const float4*>(t0p + r4);                               \
-            T1[q_] = *reinterpret_cast<const float4*>(t1p + r4);                               \
-        }
-#define GW_STEP(DX, DY, R)                                                                     \
-        {                                                                                      \
-            const float* ap = lds + (size_t)((R) + hi) * HW + NA * j;                          \
-            float av[NA];                                                                      \
-            if (NA == 4) {                                                                     \
-                const float4 t4 = *reinterpret_cast<const float4*>(ap);                        \
-                av[0] = t4.x; av[1 % NA] = t4.y; av[2 % NA] = t4.z; av[3 % NA] = t4.w;         \
-            } else if (NA == 2) {                                                              \
-                const float2 t2 = *reinterpret_cast<const float2*>(ap);                        \
-                av[0] = t2.x; av[1 % NA] = t2.y;                                               \
-            } else {                                                                           \
-                av[0] = ap[0];                                                                 \
-            }                                                                                  \
-            cs0 += (DX); cs1 += (DY);                                                          \
-            _Pragma("unroll") for (int a = 0; a < NA; ++a)                                     \
-                acc[a][0] = TR ? __builtin_amdgcn_mfma_f32_32x32x2f32((DX), av[a], acc[a][0], 0, 0, 0) \
-                               : __builtin_amdgcn_mfma_f32_32x32x2f32(av[a], (DX), acc[a][0], 0, 0, 0); \
-            _Pragma("unroll") for (int a = 0; a < NA; ++a)                                     \
-                acc[a][1] = TR ? __builtin_amdgcn_mfma_f32_32x32x2f32((DY), av[a], acc[a][1], 0, 0, 0) \
-                               : __builtin_amdgcn_mfma_f32_32x32x2f32(av[a], (DY), acc[a][1], 0, 0, 0); \
-        }
-// the upper half-wave takes the odd playlist.  A bit blend (v_bfi), NOT `hi ? t.y : t.x`: the
-// optimizer turns that into a dynamically indexed vector extract, which lives in scratch memory.
-#define GW_SEL(A, Bv) __uint_as_float((__float_as_uint(Bv) & himask) | (__float_as_uint(A) & ~himask))
-#define GW_MMA(T0, T1, R0)                                                                     \
-        _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) {                                     \
-            const int r4 = (R0) + 4 * q_;                                                      \
-            GW_STEP(GW_SEL(T0[q_].x, T0[q_].y), GW_SEL(T1[q_].x, T1[q_].y), r4)                \
-            GW_STEP(GW_SEL(T0[q_].z, T0[q_].w), GW_SEL(T1[q_].z, T1[q_].w), r4 + 2)            \
-        }
-        const int Bp4 = Bp;                          // dz^T rows are zero padded to a multiple of 64
-        const unsigned himask = hi ? 0xFFFFFFFFu : 0u;
-        float4 ta0[4], ta1[4], tb0[4], tb1[4];
-        GW_LOAD(ta0, ta1, 0)
-        for (int r0 = 0; r0 < Bp; r0 += 32) {        // straight-line 16 k-steps per iteration
-            GW_LOAD(tb0, tb1, r0 + 16)
-            __builtin_amdgcn_sched_barrier(0);       // keep the prefetch AHEAD of the 64 MFMAs below
-            GW_MMA(ta0, ta1, r0)                     // (hipcc sinks loads next to their first use)
-            __builtin_amdgcn_sched_barrier(0);
-            GW_LOAD(ta0, ta1, r0 + 32)               // past the end: re-reads the last group
-            __builtin_amdgcn_sched_barrier(0);
-            GW_MMA(tb0, tb1, r0 + 16)
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#undef GW_LOAD
-#undef GW_STEP
-#undef GW_SEL
-#undef GW_MMA
-        // D[i][j]: hidden unit hc0 + NA * i_idx + a, i_idx = (reg & 3) + 8 (reg >> 2) + 4 hi; column
-        // v0 + 2 j + b.  The NA `a` accumulators of one reg are NA consecutive hidden units.
-        if (TR && NA == 4) {
-            // register reg of accumulator (a, b) is row v0 + 2 i_idx + b, i_idx = (reg & 3) + 8 (reg >> 2) + 4 hi; lane j
-            // holds hidden units hc0 + 4 j + a: one float4 per (b, reg)
-            const float b1 = p.ad_b1, b2 = p.ad_b2, eps = p.ad_eps, al = p.ad_alpha;
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-#pragma unroll
-                for (int r4 = 0; r4 < 16; r4 += 4) {
-                    if (p.ad_m) {
-                        float4 pp[4], mm[4], vv[4];
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            const int reg = r4 + u;
-                            const int v = v0 + 2 * ((reg & 3) + 8 * (reg >> 2) + 4 * hi) + b;
-                            const size_t o = (size_t)(v < p.V ? v : 0) * p.H + hc0 + 4 * j;
-                            pp[u] = nt_ld4(p.ad_p + o);
-                            mm[u] = nt_ld4(p.ad_m + o);
-                            vv[u] = nt_ld4(p.ad_v + o);
-                        }
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            const int reg = r4 + u;
-                            const int v = v0 + 2 * ((reg & 3) + 8 * (reg >> 2) + 4 * hi) + b;
-                            const size_t o = (size_t)(v < p.V ? v : 0) * p.H + hc0 + 4 * j;
-                            const float g0 = acc[0][b][reg], g1 = acc[1 % NA][b][reg], g2 = acc[2 % NA][b][reg],
-                                        g3 = acc[3 % NA][b][reg];
-#define K6_ADAM(P, M, V, G)                                              \
-                            M = M + (G - M) * (1.0f - b1);               \
-                            V = V + (G * G - V) * (1.0f - b2);           \
-                            P = P - (M * al) / (sqrtf(V) + eps);
-                            K6_ADAM(pp[u].x, mm[u].x, vv[u].x, g0) K6_ADAM(pp[u].y, mm[u].y, vv[u].y, g1)
-                            K6_ADAM(pp[u].z, mm[u].z, vv[u].z, g2) K6_ADAM(pp[u].w, mm[u].w, vv[u].w, g3)
-#undef K6_ADAM
-                            if (v < p.V) {
-                                nt_st4(p.ad_p + o, pp[u]);
-                                nt_st4(p.ad_m + o, mm[u]);
-                                nt_st4(p.ad_v + o, vv[u]);
-                            }
-                        }
-                    } else {
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            const int reg = r4 + u;
-                            const int v = v0 + 2 * ((reg & 3) + 8 * (reg >> 2) + 4 * hi) + b;
-                            if (v >= p.V) continue;
-                            float4* dst = reinterpret_cast<float4*>(p.gW + (size_t)v * p.H + hc0 + 4 * j);
-                            float4 o4 = make_float4(acc[0][b][reg], acc[1 % NA][b][reg], acc[2 % NA][b][reg], acc[3 % NA][b][reg]);
-                            if (p.accumulate) { const float4 old = *dst; o4.x += old.x; o4.y += old.y; o4.z += old.z; o4.w += old.w; }
-                            *dst = o4;
-                        }
-                    }
-                }
-            }
-        } else
-        if (NA == 4 && p.ad_m) {
-            // the gradient tile goes straight into the Adam update of its parameters: W / m / v are read and written
-            // in place, gW never reaches memory (7 passes over the tensor + 1 of the gradient become 6).  Same
-            // per-element operations as adam_kernel, so the parameters are the bits dae_adam_step would produce.
-            const float b1 = p.ad_b1, b2 = p.ad_b2, eps = p.ad_eps, al = p.ad_alpha;
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                const int v = vcol + b;
-                if (v >= p.V) continue;
-                const size_t rbase = (size_t)v * p.H + hc0;
-#pragma unroll
-                for (int r4 = 0; r4 < 16; r4 += 4) {
-                    float4 pp[4], mm[4], vv[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int reg = r4 + u;
-                        const size_t o = rbase + 4 * ((reg & 3) + 8 * (reg >> 2) + 4 * hi);
-                        pp[u] = nt_ld4(p.ad_p + o);
-                        mm[u] = nt_ld4(p.ad_m + o);
-                        vv[u] = nt_ld4(p.ad_v + o);
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int reg = r4 + u;
-                        const size_t o = rbase + 4 * ((reg & 3) + 8 * (reg >> 2) + 4 * hi);
-                        const float g0 = acc[0][b][reg], g1 = acc[1 % NA][b][reg], g2 = acc[2 % NA][b][reg],
-                                    g3 = acc[3 % NA][b][reg];
-#define K6_ADAM(P, M, V, G)                                              \
-                        M = M + (G - M) * (1.0f - b1);                   \
-                        V = V + (G * G - V) * (1.0f - b2);               \
-                        P = P - (M * al) / (sqrtf(V) + eps);
-                        K6_ADAM(pp[u].x, mm[u].x, vv[u].x, g0) K6_ADAM(pp[u].y, mm[u].y, vv[u].y, g1)
-                        K6_ADAM(pp[u].z, mm[u].z, vv[u].z, g2) K6_ADAM(pp[u].w, mm[u].w, vv[u].w, g3)
-#undef K6_ADAM
-                        nt_st4(p.ad_p + o, pp[u]);
-                        nt_st4(p.ad_m + o, mm[u]);
-                        nt_st4(p.ad_v + o, vv[u]);
-                    }
-                }
-            }
-        } else
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int v = vcol + b;
-            if (v >= p.V) continue;
-            float* orow = p.gW + (size_t)v * p.H + hc0;
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const int i_idx = (reg & 3) + 8 * (reg >> 2) + 4 * hi;
-                if (NA == 4) {
-                    float4* dst = reinterpret_cast<float4*>(orow + 4 * i_idx);
-                    float4 o = make_float4(acc[0][b][reg], acc[1 % NA][b][reg], acc[2 % NA][b][reg], acc[3 % NA][b][reg]);
-                    if (p.accumulate) { const float4 old = *dst; o.x += old.x; o.y += old.y; o.z += old.z; o.w += old.w; }
-                    *dst = o;
-                } else {
-#pragma unroll
-                    for (int a = 0; a < NA; ++a) {
-                        float* dst = orow + NA * i_idx + a;
-                        *dst = p.accumulate ? *dst + acc[a][b][reg] : acc[a][b][reg];
-                    }
-                }
-            }
-        }
-        if (p.gb && half == 0) {
-            cs0 += __shfl_xor(cs0, 32);
-            cs1 += __shfl_xor(cs1, 32);
-            if (hi == 0) {
-                if (ok0) p.gb[vcol] = cs0;
-                if (ok1) p.gb[vcol + 1] = cs1;
-            }
-        }
-    }
-}
-
-// ---- K6, transposed orientation (bf16 operands, dz^T stored as bf16, hidden a multiple of 128) --------------------
-// Same product gW[v, hc] = sum_r dz[r, v] h[r, hc] with the operand roles swapped: A = dz^T (M = vocabulary rows),
-// B = h^T (N = hidden units), so that an accumulator lane is a hidden unit and its registers are vocabulary rows.
-// What that buys is memory shape on both sides:
-//   * A fragments are plain 16-byte loads from the bf16 dz^T row of the lane (8 consecutive playlists): no selects,
-//     no permutes, no conversions;
-//   * a store instruction writes, per half-wave, 32 lanes x float4 = 512 contiguous bytes of ONE gW row (hidden =
-//     hc0 + 4 n + a), where the other orientation writes 16-byte pieces of 32 rows (57 of its 113 us were the store);
-//     the armed Adam update (dae_arm_decoder_adam) reads and writes W / m / v with the same shape.
-// LDS holds h^T for the workgroup's 128 hidden units as bf16 B fragments in operand order: 4 KB per k-step of 16
-// playlists, 64 KB at B = 256.  gb = dz^T 1 comes out of the matrix pipe as well (a ones fragment as B operand).
-template <int NW, bool FULL = false>
-__global__ __launch_bounds__(NW * 64, 1) void grad_wdec_t_kernel(const GwP p)
-{
-    extern __shared__ __attribute__((aligned(16))) uint4 ldsq[];      // [S][4][64] B fragments
-    const int tid = threadIdx.x, lane = tid & 63, hi = lane >> 5, n = lane & 31;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int gs = DAE_NUM_XCD * p.n_half;
-    const int q = blockIdx.x / gs, rem = blockIdx.x % gs;
-    const int half = rem / DAE_NUM_XCD;
-    const int bir = q * DAE_NUM_XCD + (rem % DAE_NUM_XCD);
-    const int hc0 = half * 128;
-    const int Bp = (p.B + 31) & ~31;
-    const int S = Bp >> 4;                                             // k-steps of 16 playlists (2..16)
-
-    // B fragments: (s, a, lane (n, hi)) = bf16 of h[16 s + 8 hi + x][hc0 + 4 n + a], x = 0..7; rows past B are zero
-    for (int f = tid; f < S * 4 * 64; f += NW * 64) {
-        const int fl = f & 63, fa = (f >> 6) & 3, fs = f >> 8;
-        const int r0 = 16 * fs + 8 * (fl >> 5);
-        const float* src = p.h + hc0 + 4 * (fl & 31) + fa;
-        float x[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) x[e] = r0 + e < p.B ? src[(size_t)(r0 + e) * p.H] : 0.0f;
-        ldsq[f] = make_uint4(pk_bf16(x[0], x[1]), pk_bf16(x[2], x[3]), pk_bf16(x[4], x[5]), pk_bf16(x[6], x[7]));
-    }
-    __syncthreads();
-
-    const bf16x8_t ones = __builtin_bit_cast(bf16x8_t, make_uint4(0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u));
-    const unsigned short* dz = reinterpret_cast<const unsigned short*>(p.dzT);
-    const int n_tiles = (p.V + 63) / 64;
-    const int n_ws = p.nb_half * NW;
-    constexpr int RING = 4;                                            // k-steps of A fragments in flight per wave (8: spills)
-    for (int t = bir * NW + wave; t < n_tiles; t += n_ws) {
-        const int v0 = t * 64;
-        const int va = v0 + n, vb = v0 + 32 + n;                       // this lane's two A rows
-        const unsigned short* ra = dz + (size_t)(va < p.V ? va : 0) * p.ldT + 8 * hi;
-        const unsigned short* rb = dz + (size_t)(vb < p.V ? vb : 0) * p.ldT + 8 * hi;
-        f32x16 acc[2][4], accg[2];
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) accg[m][e] = 0.0f;
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[m][a][e] = 0.0f;
-        }
-        uint4 qa[RING], qb[RING];
-#pragma unroll
-        for (int u = 0; u < RING; ++u) {
-            const int su = (FULL || u < S) ? u : S - 1;
-            qa[u] = *reinterpret_cast<const uint4*>(ra + 16 * su);
-            qb[u] = *reinterpret_cast<const uint4*>(rb + 16 * su);
-        }
-#pragma unroll
-        for (int s_ = 0; s_ < 16; ++s_) {
-            // (FULL: S == 16, a batch of 241 .. 256, known at compile time -- with the wave-uniform tests in the loop hipcc ends
-            // every step on s_waitcnt vmcnt(0), i.e. on the ring slot it has just requested)
-            if (FULL || s_ < S) {                                      // wave-uniform
-                const bf16x8_t fa = __builtin_bit_cast(bf16x8_t, qa[s_ % RING]);
-                const bf16x8_t fb = __builtin_bit_cast(bf16x8_t, qb[s_ % RING]);
-                if (s_ + RING < 16) {                                  // refill the slot (clamped: values unused past S)
-                    const int sn = (FULL || s_ + RING < S) ? s_ + RING : S - 1;
-                    qa[s_ % RING] = *reinterpret_cast<const uint4*>(ra + 16 * sn);
-                    qb[s_ % RING] = *reinterpret_cast<const uint4*>(rb + 16 * sn);
-                }
-                uint4 bq[4];
-#pragma unroll
-                for (int a = 0; a < 4; ++a) bq[a] = ldsq[(s_ * 4 + a) * 64 + lane];
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int a = 0; a < 4; ++a) {
-                    const bf16x8_t bf = __builtin_bit_cast(bf16x8_t, bq[a]);
-                    acc[0][a] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, bf, acc[0][a], 0, 0, 0);
-                    acc[1][a] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb, bf, acc[1][a], 0, 0, 0);
-                }
-                accg[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, ones, accg[0], 0, 0, 0);
-                accg[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb, ones, accg[1], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        if (p.gb && half == 0 && n == 0) {                             // every lane holds the row sums; lanes 0 and 32 store
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg) {
-                    const int v = v0 + 32 * m + (reg & 3) + 8 * (reg >> 2) + 4 * hi;
-                    if (v < p.V) p.gb[v] = accg[m][reg];
-                }
-        }
-        // lane n holds hidden units hc0 + 4 n + a (a = the 4 accumulators of a register), register reg the row
-        // v0 + 32 m + (reg & 3) + 8 (reg >> 2) + 4 hi: one float4 per (m, reg), 512 contiguous bytes per half-wave
-        if (p.ad_m) {
-            const float b1 = p.ad_b1, b2 = p.ad_b2, eps = p.ad_eps, al = p.ad_alpha;
-#pragma unroll
-            for (int m = 0; m < 2; ++m) {
-#pragma unroll
-                for (int r4 = 0; r4 < 16; r4 += 4) {
-                    float4 pp[4], mm[4], vv[4];
-                    size_t o[4];
-                    bool ok[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int reg = r4 + u;
-                        const int v = v0 + 32 * m + (reg & 3) + 8 * (reg >> 2) + 4 * hi;
-                        ok[u] = v < p.V;
-                        o[u] = (size_t)(ok[u] ? v : 0) * p.H + hc0 + 4 * n;
-                        pp[u] = nt_ld4(p.ad_p + o[u]);
-                        mm[u] = nt_ld4(p.ad_m + o[u]);
-                        vv[u] = nt_ld4(p.ad_v + o[u]);
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int reg = r4 + u;
-                        const float g0 = acc[m][0][reg], g1 = acc[m][1][reg], g2 = acc[m][2][reg], g3 = acc[m][3][reg];
-#define K6_ADAM(P, M, V, G)                                              \
-                        M = M + (G - M) * (1.0f - b1);                   \
-                        V = V + (G * G - V) * (1.0f - b2);               \
-                        P = P - (M * al) / (sqrtf(V) + eps);
-                        K6_ADAM(pp[u].x, mm[u].x, vv[u].x, g0) K6_ADAM(pp[u].y, mm[u].y, vv[u].y, g1)
-                        K6_ADAM(pp[u].z, mm[u].z, vv[u].z, g2) K6_ADAM(pp[u].w, mm[u].w, vv[u].w, g3)
-#undef K6_ADAM
-                        if (ok[u]) {
-                            nt_st4(p.ad_p + o[u], pp[u]);
-                            nt_st4(p.ad_m + o[u], mm[u]);
-                            nt_st4(p.ad_v + o[u], vv[u]);
-                        }
-                    }
-                }
-            }
-        } else {
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg) {
-                    const int v = v0 + 32 * m + (reg & 3) + 8 * (reg >> 2) + 4 * hi;
-                    if (v < p.V)
-                        *reinterpret_cast<float4*>(p.gW + (size_t)v * p.H + hc0 + 4 * n) =
-                            make_float4(acc[m][0][reg], acc[m][1][reg], acc[m][2][reg], acc[m][3][reg]);
-                }
-        }
-    }
-}
-
-// ---- K6, transposed orientation, the armed-Adam form with its state streams kept in flight (round 6) ---------------------------
-// grad_wdec_t_kernel above runs a tile in two phases -- 160 MFMAs with 4 KB of dz^T requests in flight per wave, then the Adam
-// pass in groups of 12 x 1 KB loads, compute, 12 stores -- and sits at 5.3 TB/s for 1.14 GB with its waves parked 59 % of the time
-// (SQ counters, r06 notes 8): too few bytes in flight, not too many instructions.  At 248 registers it has no room for more.
-// This form halves the tile (32 decoder rows: 64 accumulator registers instead of 128 + 32) and spends the registers on the
-// streams: the first group of p / m / v rows of a tile is requested BEFORE its MFMAs (under which it arrives), and inside the Adam
-// pass group g + 1 is requested before group g is computed and stored (two buffers).  Same operands, same k order per
-// element, same update operations as above: the parameters stay bit-identical to dense Adam.
-template <int NW, bool FULL>
-__global__ __launch_bounds__(NW * 64, 1) void grad_wdec_t32_kernel(const GwP p)
-{
-    extern __shared__ __attribute__((aligned(16))) uint4 ldsq[];      // [S][4][64] B fragments
-    const int tid = threadIdx.x, lane = tid & 63, hi = lane >> 5, n = lane & 31;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int gs = DAE_NUM_XCD * p.n_half;
-    const int q = blockIdx.x / gs, rem = blockIdx.x % gs;
-    const int half = rem / DAE_NUM_XCD;
-    const int bir = q * DAE_NUM_XCD + (rem % DAE_NUM_XCD);
-    const int hc0 = half * 128;
-    const int Bp = (p.B + 31) & ~31;
-    const int S = Bp >> 4;
-
-    for (int f = tid; f < S * 4 * 64; f += NW * 64) {
-        const int fl = f & 63, fa = (f >> 6) & 3, fs = f >> 8;
-        const int r0 = 16 * fs + 8 * (fl >> 5);
-        const float* src = p.h + hc0 + 4 * (fl & 31) + fa;
-        float x[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) x[e] = r0 + e < p.B ? src[(size_t)(r0 + e) * p.H] : 0.0f;
-        ldsq[f] = make_uint4(pk_bf16(x[0], x[1]), pk_bf16(x[2], x[3]), pk_bf16(x[4], x[5]), pk_bf16(x[6], x[7]));
-    }
-    __syncthreads();
-
-    const bf16x8_t ones = __builtin_bit_cast(bf16x8_t, make_uint4(0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u));
-    const unsigned short* dz = reinterpret_cast<const unsigned short*>(p.dzT);
-    const int n_tiles = (p.V + 31) / 32;
-    const int n_ws = p.nb_half * NW;
-    constexpr int RING = 4;
-    const float b1 = p.ad_b1, b2 = p.ad_b2, eps = p.ad_eps, al = p.ad_alpha;
-    for (int t = bir * NW + wave; t < n_tiles; t += n_ws) {
-        const int v0 = t * 32;
-        const int va = v0 + n;
-        const unsigned short* ra = dz + (size_t)(va < p.V ? va : 0) * p.ldT + 8 * hi;
-        f32x16 acc[4], accg;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) accg[e] = 0.0f;
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[a][e] = 0.0f;
-        uint4 qa[RING];
-#pragma unroll
-        for (int u = 0; u < RING; ++u) qa[u] = *reinterpret_cast<const uint4*>(ra + 16 * ((FULL || u < S) ? u : S - 1));
-        // the Adam pass's rows: register reg of lane (n, hi) is decoder row v0 + (reg & 3) + 8 (reg >> 2) + 4 hi, hidden hc0 + 4 n + a
-        float4 P[2][4], M[2][4], Vv[2][4];
-        size_t off[2][4];
-        bool ok[2][4];
-        auto issue = [&](int buf, int r4) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int reg = r4 + u;
-                const int v = v0 + (reg & 3) + 8 * (reg >> 2) + 4 * hi;
-                ok[buf][u] = v < p.V;
-                off[buf][u] = (size_t)(ok[buf][u] ? v : 0) * p.H + hc0 + 4 * n;
-                P[buf][u] = nt_ld4(p.ad_p + off[buf][u]);
-                M[buf][u] = nt_ld4(p.ad_m + off[buf][u]);
-                Vv[buf][u] = nt_ld4(p.ad_v + off[buf][u]);
-            }
-        };
-        issue(0, 0);                                                   // arrives under the MFMAs
-        // (S == 16 -- a batch of 241 .. 256 -- is a template case: with the wave-uniform `s_ < S` tests in the loop hipcc ends every
-        // step on s_waitcnt vmcnt(0), i.e. on the ring slot it has just requested: 16 memory round trips per tile instead of a ring)
-#pragma unroll
-        for (int s_ = 0; s_ < 16; ++s_) {
-            if (FULL || s_ < S) {                                      // wave-uniform
-                const bf16x8_t fa = __builtin_bit_cast(bf16x8_t, qa[s_ % RING]);
-                if (s_ + RING < 16) {
-                    const int sn = (FULL || s_ + RING < S) ? s_ + RING : S - 1;
-                    qa[s_ % RING] = *reinterpret_cast<const uint4*>(ra + 16 * sn);
-                }
-                uint4 bq[4];
-#pragma unroll
-                for (int a = 0; a < 4; ++a) bq[a] = ldsq[(s_ * 4 + a) * 64 + lane];
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int a = 0; a < 4; ++a)
-                    acc[a] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, __builtin_bit_cast(bf16x8_t, bq[a]), acc[a], 0, 0, 0);
-                accg = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, ones, accg, 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        if (p.gb && half == 0 && n == 0) {
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const int v = v0 + (reg & 3) + 8 * (reg >> 2) + 4 * hi;
-                if (v < p.V) p.gb[v] = accg[reg];
-            }
-        }
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int cb = g & 1;
-            if (g + 1 < 4) issue(cb ^ 1, 4 * (g + 1));
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int reg = 4 * g + u;
-                float4 pp = P[cb][u], mm = M[cb][u], vv = Vv[cb][u];
-                const float g0 = acc[0][reg], g1 = acc[1][reg], g2 = acc[2][reg], g3 = acc[3][reg];
-#define K6_ADAM(Pq, Mq, Vq, G)                                           \
-                Mq = Mq + (G - Mq) * (1.0f - b1);                        \
-                Vq = Vq + (G * G - Vq) * (1.0f - b2);                    \
-                Pq = Pq - (Mq * al) / (sqrtf(Vq) + eps);
-                K6_ADAM(pp.x, mm.x, vv.x, g0) K6_ADAM(pp.y, mm.y, vv.y, g1)
-                K6_ADAM(pp.z, mm.z, vv.z, g2) K6_ADAM(pp.w, mm.w, vv.w, g3)
-#undef K6_ADAM
-                if (ok[cb][u]) {
-                    nt_st4(p.ad_p + off[cb][u], pp);
-                    nt_st4(p.ad_m + off[cb][u], mm);
-                    nt_st4(p.ad_v + off[cb][u], vv);
-                }
-            }
-        }
-    }
-}
-
-// ---- K6 with fp32 operands (train_dtype = f32), the armed-Adam form with its state streams kept in flight (round 6) -------------
-// grad_wdec_t32_kernel's plan on v_mfma_f32_32x32x2_f32: a tile of 32 decoder rows, A = dz^T (fp32 rows; a float4 = 4
-// playlists = two k-steps, the lane half hi taking the even / odd one), B = h^T from LDS (one float4 per lane and k-step: the four
-// accumulators' hidden units), 512 MFMAs per tile, the row sums (gb) on the VALU; then the Adam pass of section 12 -- the first
-// group of p / m / v rows requested before the MFMAs, group g + 1 before group g is computed.  The generic kernel it replaces
-// for this case (grad_wdec_kernel<4, 8, true>) ran its two phases back to back at 12 KB in flight per wave: 349 us
-// for 180 us of matrix work and 1.22 GB.
-template <int NW, bool FULL>
-__global__ __launch_bounds__(NW * 64, 1) void grad_wdec_t32_f32_kernel(const GwP p)
-{
-    extern __shared__ __attribute__((aligned(16))) float4 ldsf[];     // [Bp / 2 k-steps][64 lanes]: h[2 g + hi][hc0 + 4 n .. + 3]
-    const int tid = threadIdx.x, lane = tid & 63, hi = lane >> 5, n = lane & 31;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int gs = DAE_NUM_XCD * p.n_half;
-    const int q_ = blockIdx.x / gs, rem = blockIdx.x % gs;
-    const int half = rem / DAE_NUM_XCD;
-    const int bir = q_ * DAE_NUM_XCD + (rem % DAE_NUM_XCD);
-    const int hc0 = half * 128;
-    const int Bp = (p.B + 31) & ~31;
-    const int Q = Bp >> 2;                                             // float4 of a dz^T row (4 playlists each)
-
-    for (int f = tid; f < (Bp >> 1) * 64; f += NW * 64) {
-        const int fl = f & 63, g = f >> 6;
-        const int r = 2 * g + (fl >> 5);
-        ldsf[f] = r < p.B ? *reinterpret_cast<const float4*>(p.h + (size_t)r * p.H + hc0 + 4 * (fl & 31)) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    __syncthreads();
-
-    const int n_tiles = (p.V + 31) / 32;
-    const int n_ws = p.nb_half * NW;
-    constexpr int RING = 4;
-    const unsigned himask = hi ? 0xFFFFFFFFu : 0u;
-    // (Tried: the second wave of each SIMD starting 2 .. 16 x 8 k cycles late, so that one wave's MFMAs run under the other's state
-    // streams -- 345 - 352 us at every setting: phases that coincide are not what this launch loses its time to.)
-#define K6F_SEL(A, Bv) __uint_as_float((__float_as_uint(Bv) & himask) | (__float_as_uint(A) & ~himask))
-    const float b1 = p.ad_b1, b2 = p.ad_b2, eps = p.ad_eps, al = p.ad_alpha;
-    for (int t = bir * NW + wave; t < n_tiles; t += n_ws) {
-        const int v0 = t * 32;
-        const int va = v0 + n;
-        const float4* ra = reinterpret_cast<const float4*>(p.dzT + (size_t)(va < p.V ? va : 0) * p.ldT);
-        f32x16 acc[4];
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[a][e] = 0.0f;
-        float cs = 0.0f;
-        float4 qa[RING];
-#pragma unroll
-        for (int u = 0; u < RING; ++u) qa[u] = ra[(FULL || u < Q) ? u : Q - 1];
-        float4 P[2][4], M[2][4], Vv[2][4];
-        size_t off[2][4];
-        bool ok[2][4];
-        auto issue = [&](int buf, int r4) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int reg = r4 + u;
-                const int v = v0 + (reg & 3) + 8 * (reg >> 2) + 4 * hi;
-                ok[buf][u] = v < p.V;
-                off[buf][u] = (size_t)(ok[buf][u] ? v : 0) * p.H + hc0 + 4 * n;
-                P[buf][u] = nt_ld4(p.ad_p + off[buf][u]);
-                M[buf][u] = nt_ld4(p.ad_m + off[buf][u]);
-                Vv[buf][u] = nt_ld4(p.ad_v + off[buf][u]);
-            }
-        };
-        issue(0, 0);                                                   // arrives under the 512 MFMAs
-        const int q_end = FULL ? 64 : Q;
-        for (int q0 = 0; q0 < q_end; q0 += RING) {
-#pragma unroll
-            for (int u = 0; u < RING; ++u) {
-                const int qq = q0 + u;
-                const float4 d4 = qa[u];
-                {
-                    const int qn = qq + RING;
-                    qa[u] = ra[(FULL ? qn < 64 : qn < Q) ? qn : q_end - 1];
-                }
-                const float4 bA = ldsf[(2 * qq) * 64 + lane], bB = ldsf[(2 * qq + 1) * 64 + lane];
-                const float dA = K6F_SEL(d4.x, d4.y), dB = K6F_SEL(d4.z, d4.w);
-                __builtin_amdgcn_sched_barrier(0);
-                cs += dA; cs += dB;
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(dA, bA.x, acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(dA, bA.y, acc[1], 0, 0, 0);
-                acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(dA, bA.z, acc[2], 0, 0, 0);
-                acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(dA, bA.w, acc[3], 0, 0, 0);
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(dB, bB.x, acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(dB, bB.y, acc[1], 0, 0, 0);
-                acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(dB, bB.z, acc[2], 0, 0, 0);
-                acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(dB, bB.w, acc[3], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        cs += __shfl_xor(cs, 32);                                      // the two lane halves hold the even / odd playlists of the row
-        if (p.gb && half == 0 && hi == 0 && va < p.V) p.gb[va] = cs;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int cb = g & 1;
-            if (g + 1 < 4) issue(cb ^ 1, 4 * (g + 1));
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int reg = 4 * g + u;
-                float4 pp = P[cb][u], mm = M[cb][u], vv = Vv[cb][u];
-                const float g0 = acc[0][reg], g1 = acc[1][reg], g2 = acc[2][reg], g3 = acc[3][reg];
-#define K6_ADAM(Pq, Mq, Vq, G)                                           \
-                Mq = Mq + (G - Mq) * (1.0f - b1);                        \
-                Vq = Vq + (G * G - Vq) * (1.0f - b2);                    \
-                Pq = Pq - (Mq * al) / (sqrtf(Vq) + eps);
-                K6_ADAM(pp.x, mm.x, vv.x, g0) K6_ADAM(pp.y, mm.y, vv.y, g1)
-                K6_ADAM(pp.z, mm.z, vv.z, g2) K6_ADAM(pp.w, mm.w, vv.w, g3)
-#undef K6_ADAM
-                if (ok[cb][u]) {
-                    nt_st4(p.ad_p + off[cb][u], pp);
-                    nt_st4(p.ad_m + off[cb][u], mm);
-                    nt_st4(p.ad_v + off[cb][u], vv);
-                }
-            }
-        }
-    }
-#undef K6F_SEL
-}
-
 // ---- K7: dh partial [chunk][r][hc] = sum_{v in chunk} dzT[v, r] * W[v, hc] -----------------------
 // a wave owns one (hidden half of 128, 64 playlists) output tile for one chunk of V: 8 accumulators;
 // A = W rows (float4 per lane: hc0 + 4 i + a), B = dz^T rows (float2 per lane: r0 + 2 j + b); no LDS.
@@ -1009,7 +325,7 @@ __global__ __launch_bounds__(256, 1) void grad_hidden_kernel(const DhP p)
             const int r = r0 + 2 * j + b;
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
-                const int i_idx = (reg & 3) + 8 * (reg >> 2) + 4 * hi;
+                const int i_idx = acc_row32(reg, hi);
                 if (NA == 4) {
                     // operands swapped (NA = 4): the lane is the hidden unit hc0 + 4 j + a, the register the playlist
                     // r0 + 2 i_idx + b -- 512 contiguous bytes of one partial row per half-wave
@@ -1253,245 +569,46 @@ __global__ __launch_bounds__(64) void finish_cost_kernel(const float* __restrict
     if (lane == 0) *cost = (float)(s + (double)lambda * l2);
 }
 
-// ---- K9: TF1 AdamOptimizer, dense ------------------------------------------------
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float* __restrict__ m,
-                                                   float* __restrict__ v,
-                                                   const float* __restrict__ g, size_t n,
-                                                   float lr_t, float b1, float b2, float eps)
+// split of K7's V contraction: about one (output tile of NA * 32 hidden units x 64 playlists, chunk) work item per wave slot
+struct K7Plan { int NA, chunk, n_chunk; };
+K7Plan k7_plan(int V, int H, int Bpad64)
 {
-    const size_t n4 = n / 4;
-    float4* p4 = reinterpret_cast<float4*>(p); float4* m4 = reinterpret_cast<float4*>(m);
-    float4* v4 = reinterpret_cast<float4*>(v); const float4* g4 = reinterpret_cast<const float4*>(g);
-// TF1 ApplyAdam functor: m += (g - m)(1 - b1); v += (g^2 - v)(1 - b2); var -= (m alpha)/(sqrt(v)+eps)
-#define ADAM1(P, M, V, G, c)                                         \
-        M.c = M.c + (G.c - M.c) * (1.0f - b1);                       \
-        V.c = V.c + (G.c * G.c - V.c) * (1.0f - b2);                 \
-        P.c = P.c - (M.c * lr_t) / (sqrtf(V.c) + eps);
-    // two float4 groups per iteration: 8 independent 16-byte loads in flight per thread (HBM-bound: 7 passes
-    // over the tensor).  Every byte is touched once: nontemporal loads and stores keep the 7 streams out of each
-    // other's way in L2.
-    typedef float nt4 __attribute__((ext_vector_type(4)));
-    auto ld = [](const float4* a) {
-        const nt4 t = __builtin_nontemporal_load(reinterpret_cast<const nt4*>(a));
-        return make_float4(t.x, t.y, t.z, t.w);
-    };
-    auto st = [](float4* a, const float4 x) {
-        const nt4 t = {x.x, x.y, x.z, x.w};
-        __builtin_nontemporal_store(t, reinterpret_cast<nt4*>(a));
-    };
-    const size_t stride = (size_t)gridDim.x * 256;
-    size_t o = (size_t)blockIdx.x * 256 + threadIdx.x;
-    for (; o + stride < n4; o += 2 * stride) {
-        const size_t o2 = o + stride;
-        float4 pa = ld(p4 + o), ma = ld(m4 + o), va = ld(v4 + o);
-        const float4 ga = ld(g4 + o);
-        float4 pb = ld(p4 + o2), mb = ld(m4 + o2), vb = ld(v4 + o2);
-        const float4 gb = ld(g4 + o2);
-        ADAM1(pa, ma, va, ga, x) ADAM1(pa, ma, va, ga, y) ADAM1(pa, ma, va, ga, z) ADAM1(pa, ma, va, ga, w)
-        ADAM1(pb, mb, vb, gb, x) ADAM1(pb, mb, vb, gb, y) ADAM1(pb, mb, vb, gb, z) ADAM1(pb, mb, vb, gb, w)
-        st(p4 + o, pa); st(m4 + o, ma); st(v4 + o, va);
-        st(p4 + o2, pb); st(m4 + o2, mb); st(v4 + o2, vb);
-    }
-    for (; o < n4; o += stride) {
-        float4 pp = p4[o], mm = m4[o], vv = v4[o];
-        const float4 gg = g4[o];
-        ADAM1(pp, mm, vv, gg, x) ADAM1(pp, mm, vv, gg, y) ADAM1(pp, mm, vv, gg, z) ADAM1(pp, mm, vv, gg, w)
-        p4[o] = pp; m4[o] = mm; v4[o] = vv;
-    }
-#undef ADAM1
-    for (size_t o = n4 * 4 + (size_t)blockIdx.x * 256 + threadIdx.x; o < n;
-         o += (size_t)gridDim.x * 256) {
-        const float gg = g[o];
-        const float mm = m[o] + (gg - m[o]) * (1.0f - b1);
-        const float vv = v[o] + (gg * gg - v[o]) * (1.0f - b2);
-        m[o] = mm; v[o] = vv;
-        p[o] = p[o] - (mm * lr_t) / (sqrtf(vv) + eps);
-    }
+    K7Plan k;
+    k.NA = (H % 128) == 0 ? 4 : ((H % 64) == 0 ? 2 : 1);
+    const int n_out_tiles = (H / (32 * k.NA)) * (Bpad64 / 64);
+    int want_chunks = (DAE_NUM_CU * 4) / n_out_tiles;
+    if (want_chunks < 1) want_chunks = 1;
+    k.chunk = ((V + want_chunks - 1) / want_chunks + 15) / 16 * 16;
+    if (k.chunk < 16) k.chunk = 16;
+    k.n_chunk = (V + k.chunk - 1) / k.chunk;
+    return k;
 }
 
-// ---- K9 on a ROW-SPARSE gradient: the same dense TF1 Adam, without the HBM passes over rows that have none ------
-// The untied encoder's gradient is non-zero on the few thousand rows the batch's input names (4 % of 170 000).
-// Dense Adam still moves every row (m and v decay, p follows m), which costs 7 passes over 174 MB per step.  A row
-// without gradient, however, evolves by a recurrence nobody else reads: its state can stay at the step it was last
-// current for (`last[row]`) and be brought up to date -- by running the SAME per-element update with g = 0 once per
-// missed step, with the alpha each of those steps used (lr_tab[s]) -- when the row is next needed: before a step
-// whose input names it (dae_adam_rows_begin), or for everyone at a sync point (dae_adam_rows_flush).  Every element
-// sees exactly the operation sequence dense Adam would have applied, so the parameters are bit-identical
-// (tests/test_gpu_train.py); only the memory traffic of untouched rows is gone.
-// One wave per listed row; a row listed several times (a track in many playlists) is claimed once per launch through
-// mark[row] (atomicExch with a per-launch stamp).
-#define ADAM_EL(P, M, V, G, A)                                           \
-        M = M + (G - M) * (1.0f - b1);                                   \
-        V = V + (G * G - V) * (1.0f - b2);                               \
-        P = P - (M * A) / (sqrtf(V) + eps);
-
-// MODE 0: begin  (listed rows -> current at step - 1)
-// MODE 1: apply  (listed rows -> current at step - 1, then the update of `step` with their gradient row, which is
-//                 zeroed again so that the dense gradient buffer stays all-zero between steps)
-template <int MODE>
-__global__ __launch_bounds__(256) void adam_rows_kernel(float* __restrict__ p, float* __restrict__ m,
-                                                        float* __restrict__ v, float* __restrict__ g,
-                                                        int* __restrict__ last, int* __restrict__ mark,
-                                                        float* __restrict__ lr_tab, int n_rows, int row_len,
-                                                        const int32_t* __restrict__ rows,
-                                                        const int32_t* __restrict__ n_listed_dev, int n_listed_max,
-                                                        float lr_t, float b1, float b2, float eps, int step)
+// K7: the k.n_chunk partials [n_chunk][Bpad64][H] of dh = dz W at `part`.  dz16: dz^T holds bf16 (k.NA == 4)
+int launch_k7(dae_ctx* ctx, const float* dzT, int64_t ldT, int dz16, const float* W, int H, int V, int Bpad64, const K7Plan& k,
+              float* part)
 {
-    const int lane = threadIdx.x & 63;
-    const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (MODE == 1 && blockIdx.x == 0 && threadIdx.x == 0) lr_tab[step] = lr_t;
-    const int n_listed = n_listed_dev ? min(*n_listed_dev, n_listed_max) : n_listed_max;
-    if (w >= n_listed) return;
-    const int row = rows[w];
-    if (row < 0 || row >= n_rows) return;
-    const int stamp = 2 * step + MODE;
-    // (round 6) Everything that depends on `row` alone is requested TOGETHER: the claim, the row's step and the first 64 float4 of
-    // its state (the whole row at hidden 256) -- the wave was four dependent trips to memory (row, claim, step, state) for one
-    // update, and a launch is ~100 such waves per CU: 27 + 30 us for 95 MB.  A wave that loses the claim has read lines the
-    // winner reads anyway.
-    const bool vec = (row_len & 3) == 0;
-    const bool first_in = vec && lane < (row_len >> 2);
-    const size_t o_first = ((size_t)row * row_len >> 2) + lane;
-    float4 pp0 = make_float4(0.f, 0.f, 0.f, 0.f), mm0 = pp0, vv0 = pp0, gg0 = pp0;
-    if (first_in) {
-        pp0 = reinterpret_cast<float4*>(p)[o_first]; mm0 = reinterpret_cast<float4*>(m)[o_first];
-        vv0 = reinterpret_cast<float4*>(v)[o_first];
-        if (MODE == 1) gg0 = reinterpret_cast<float4*>(g)[o_first];
-    }
-    const int from = last[row];
-    int claimed = 0;
-    if (lane == 0) claimed = atomicExch(&mark[row], stamp) != stamp;
-    claimed = __shfl(claimed, 0);
-    if (!claimed) return;
-    const int upto = step - 1;
-    // four elements per lane at a time: the replay is a sequential recurrence per element (sqrt -> divide -> subtract),
-    // so independent chains are the only instruction-level parallelism there is
-    if (vec) {
-        for (int c4 = lane; c4 < (row_len >> 2); c4 += 64) {
-            const size_t o = ((size_t)row * row_len >> 2) + c4;
-            const bool pre = c4 == lane;                           // the first round was requested above
-            float4 pp = pre ? pp0 : reinterpret_cast<float4*>(p)[o], mm = pre ? mm0 : reinterpret_cast<float4*>(m)[o],
-                   vv = pre ? vv0 : reinterpret_cast<float4*>(v)[o];
-            for (int s_ = from + 1; s_ <= upto; ++s_) {
-                const float a = lr_tab[s_];
-                const float z = 0.0f;
-                ADAM_EL(pp.x, mm.x, vv.x, z, a) ADAM_EL(pp.y, mm.y, vv.y, z, a)
-                ADAM_EL(pp.z, mm.z, vv.z, z, a) ADAM_EL(pp.w, mm.w, vv.w, z, a)
-            }
-            if (MODE == 1) {
-                const float4 gg = pre ? gg0 : reinterpret_cast<float4*>(g)[o];
-                ADAM_EL(pp.x, mm.x, vv.x, gg.x, lr_t) ADAM_EL(pp.y, mm.y, vv.y, gg.y, lr_t)
-                ADAM_EL(pp.z, mm.z, vv.z, gg.z, lr_t) ADAM_EL(pp.w, mm.w, vv.w, gg.w, lr_t)
-                reinterpret_cast<float4*>(g)[o] = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-            reinterpret_cast<float4*>(p)[o] = pp; reinterpret_cast<float4*>(m)[o] = mm;
-            reinterpret_cast<float4*>(v)[o] = vv;
-        }
-    } else
-    for (int c = lane; c < row_len; c += 64) {
-        const size_t o = (size_t)row * row_len + c;
-        float pp = p[o], mm = m[o], vv = v[o];
-        for (int s_ = from + 1; s_ <= upto; ++s_) {
-            const float a = lr_tab[s_];
-            const float z = 0.0f;
-            ADAM_EL(pp, mm, vv, z, a)
-        }
-        if (MODE == 1) {
-            const float gg = g[o];
-            ADAM_EL(pp, mm, vv, gg, lr_t)
-            g[o] = 0.0f;
-        }
-        p[o] = pp; m[o] = mm; v[o] = vv;
-    }
-    if (lane == 0) last[row] = MODE == 1 ? step : upto;
-}
-
-// every row -> current at `step` (sync points: evaluation, saving, sharding, ...); one wave per row
-__global__ __launch_bounds__(256) void adam_rows_flush_kernel(float* __restrict__ p, float* __restrict__ m,
-                                                              float* __restrict__ v, int* __restrict__ last,
-                                                              const float* __restrict__ lr_tab, int n_rows,
-                                                              int row_len, float b1, float b2, float eps, int step)
-{
-    const int lane = threadIdx.x & 63;
-    for (int row = blockIdx.x * 4 + (threadIdx.x >> 6); row < n_rows; row += gridDim.x * 4) {
-        const int from = last[row];
-        if (from >= step) continue;
-        if ((row_len & 3) == 0) {
-            for (int c4 = lane; c4 < (row_len >> 2); c4 += 64) {
-                const size_t o = ((size_t)row * row_len >> 2) + c4;
-                float4 pp = reinterpret_cast<float4*>(p)[o], mm = reinterpret_cast<float4*>(m)[o],
-                       vv = reinterpret_cast<float4*>(v)[o];
-                for (int s_ = from + 1; s_ <= step; ++s_) {
-                    const float a = lr_tab[s_];
-                    const float z = 0.0f;
-                    ADAM_EL(pp.x, mm.x, vv.x, z, a) ADAM_EL(pp.y, mm.y, vv.y, z, a)
-                    ADAM_EL(pp.z, mm.z, vv.z, z, a) ADAM_EL(pp.w, mm.w, vv.w, z, a)
-                }
-                reinterpret_cast<float4*>(p)[o] = pp; reinterpret_cast<float4*>(m)[o] = mm;
-                reinterpret_cast<float4*>(v)[o] = vv;
-            }
-        } else
-        for (int c = lane; c < row_len; c += 64) {
-            const size_t o = (size_t)row * row_len + c;
-            float pp = p[o], mm = m[o], vv = v[o];
-            for (int s_ = from + 1; s_ <= step; ++s_) {
-                const float a = lr_tab[s_];
-                const float z = 0.0f;
-                ADAM_EL(pp, mm, vv, z, a)
-            }
-            p[o] = pp; m[o] = mm; v[o] = vv;
-        }
-        if (lane == 0) last[row] = step;
-    }
-}
-#undef ADAM_EL
-
-int grid_for(size_t n) { size_t b = (n + 255) / 256; return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b)); }
-
-}  // namespace
-
-int dae_launch_adam(dae_ctx* ctx, float* param, float* m, float* v, const float* grad, int64_t n,
-                    float lr_t, float beta1, float beta2, float eps)
-{
-    if (n <= 0) return DAE_OK;
-    size_t work = (size_t)n / 4;
-    hipLaunchKernelGGL(adam_kernel, dim3(grid_for(work ? work : 1)), dim3(256), 0, ctx->stream, param, m, v,
-                       grad, (size_t)n, lr_t, beta1, beta2, eps);
-    DAE_CHECK_LAUNCH(ctx, "adam_kernel");
+    DhP p;
+    p.dzT = dzT; p.ldT = ldT; p.W = W; p.H = H; p.V = V; p.part = part;
+    p.n_chunk = k.n_chunk; p.chunk = k.chunk; p.Bpad64 = Bpad64; p.n_half = H / (32 * k.NA);
+    p.n_rblk = Bpad64 / 64;
+    p.fast32 = ((uint64_t)(V + 32) * (uint64_t)H * 4 < (1ull << 32) && (uint64_t)(V + 32) * (uint64_t)ldT * 4 < (1ull << 32)) ? 1 : 0;
+    const int total = p.n_half * p.n_rblk * k.n_chunk;
+    int blocks = (total + 3) / 4;
+    if (blocks > DAE_NUM_CU) blocks = DAE_NUM_CU;
+    if (k.NA == 4 && dz16) hipLaunchKernelGGL((grad_hidden_kernel<4, true>), dim3(blocks), dim3(256), 0, ctx->stream, p);
+    else if (k.NA == 4) hipLaunchKernelGGL(grad_hidden_kernel<4>, dim3(blocks), dim3(256), 0, ctx->stream, p);
+    else if (k.NA == 2) hipLaunchKernelGGL(grad_hidden_kernel<2>, dim3(blocks), dim3(256), 0, ctx->stream, p);
+    else hipLaunchKernelGGL(grad_hidden_kernel<1>, dim3(blocks), dim3(256), 0, ctx->stream, p);
+    DAE_CHECK_LAUNCH(ctx, "grad_hidden_kernel");
     return DAE_OK;
 }
-
-int dae_launch_adam_rows(dae_ctx* ctx, int mode, float* param, float* m, float* v, float* grad, int32_t* last,
-                         int32_t* mark, float* lr_tab, int n_rows, int row_len, const int32_t* rows,
-                         const int32_t* n_listed_dev, int n_listed_max, float lr_t, float beta1, float beta2,
-                         float eps, int step)
-{
-    if (mode == 2) {
-        int blocks = (n_rows + 3) / 4;
-        if (blocks > 16 * DAE_NUM_CU) blocks = 16 * DAE_NUM_CU;
-        hipLaunchKernelGGL(adam_rows_flush_kernel, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, ctx->stream, param, m, v,
-                           last, lr_tab, n_rows, row_len, beta1, beta2, eps, step);
-        DAE_CHECK_LAUNCH(ctx, "adam_rows_flush_kernel");
-        return DAE_OK;
-    }
-    // mode 1 always launches: its first thread records this step's alpha even when no row is listed
-    const int blocks = (n_listed_max + 3) / 4 > 0 ? (n_listed_max + 3) / 4 : 1;
-    if (mode == 0)
-        hipLaunchKernelGGL(adam_rows_kernel<0>, dim3(blocks), dim3(256), 0, ctx->stream, param, m, v, grad, last, mark,
-                           lr_tab, n_rows, row_len, rows, n_listed_dev, n_listed_max, lr_t, beta1, beta2, eps, step);
-    else
-        hipLaunchKernelGGL(adam_rows_kernel<1>, dim3(blocks), dim3(256), 0, ctx->stream, param, m, v, grad, last, mark,
-                           lr_tab, n_rows, row_len, rows, n_listed_dev, n_listed_max, lr_t, beta1, beta2, eps, step);
-    DAE_CHECK_LAUNCH(ctx, "adam_rows_kernel");
-    return DAE_OK;
-}
-
-namespace {
 
 // scratch carved for one training step over a [Vl, H] weight (shard) and B rows; stable for a given
 // (Vl, H, B), so the stages of a sharded step find h / sg where the earlier stage left them
 struct TrainPlan {
-    int NA, G, RB, Bpad64, n_chunk, chunk, n_fix, dtype, dz16, rm;
+    int G, RB, Bpad64, n_chunk, n_fix, dtype, dz16, rm;
+    K7Plan k7;          // (k7.n_chunk: K7's own launch; n_chunk: the partials of dh the step leaves, whoever wrote them)
     int fuse_dh;        // K5 leaves dh's partials itself (decode_f32.hip decode_loss_dh_bf16_kernel): no K7; n_chunk = g.grid + 1
     dae_rowgeom g;
     size_t bh, hp_bytes;
@@ -1505,7 +622,6 @@ int train_plan(dae_ctx* ctx, int Vl, int H, int B, TrainPlan& t)
     if (B < 1 || B > 256) return dae_fail(ctx, DAE_ERR_ARG, "training batch %d outside [1, 256]", B);
     if (Vl < 1) return dae_fail(ctx, DAE_ERR_ARG, "empty vocabulary shard");
     int rc;
-    t.NA = (H % 128) == 0 ? 4 : ((H % 64) == 0 ? 2 : 1);
     const int Hp = dae_round_up(H, DAE_HPAD);
     t.dtype = ctx->train_dtype;
     // bf16 GEMMs with the 4-tile backward kernels: dL/dz itself is stored as bf16
@@ -1519,13 +635,8 @@ int train_plan(dae_ctx* ctx, int Vl, int H, int B, TrainPlan& t)
     t.hp_bytes = (size_t)t.g.n_rg * t.G * t.RB * 64 * sizeof(float4);
     if ((rc = dae_reserve(ctx, ctx->h_packed, t.hp_bytes))) return rc;
     if ((rc = dae_reserve(ctx, ctx->train_b, (size_t)Vl * t.Bpad64 * sizeof(float)))) return rc;
-    // split of the V contraction of K7: about one (output tile, chunk) work item per wave slot
-    const int n_out_tiles = (H / (32 * t.NA)) * (t.Bpad64 / 64);
-    int want_chunks = (DAE_NUM_CU * 4) / n_out_tiles;
-    if (want_chunks < 1) want_chunks = 1;
-    t.chunk = ((Vl + want_chunks - 1) / want_chunks + 15) / 16 * 16;
-    if (t.chunk < 16) t.chunk = 16;
-    t.n_chunk = (Vl + t.chunk - 1) / t.chunk;
+    t.k7 = k7_plan(Vl, H, t.Bpad64);
+    t.n_chunk = t.k7.n_chunk;
     {   // bf16 GEMMs with dz^T as bf16 at hidden 256: dh comes out of the forward launch, one partial per workgroup + the positives'
         t.fuse_dh = (t.rm && t.dtype == DAE_DTYPE_BF16 && t.dz16) ? 1 : 0;
         if (t.fuse_dh) t.n_chunk = t.g.grid + 1;
@@ -1552,7 +663,6 @@ int train_decode_backward(dae_ctx* ctx, const TrainPlan& t, int Vl, int H, int B
                           int col_lo, int col_hi, const float* Wd, const float* b_dec, float* gWd, float* gb_dec)
 {
     hipStream_t st = ctx->stream;
-    const int NA = t.NA;
     int rc;
     if (H > FIX_MAXH) return dae_fail(ctx, DAE_ERR_ARG, "training kernels need H <= %d (H=%d)", FIX_MAXH, H);
     if (t.Bpad64 != B)
@@ -1569,103 +679,31 @@ int train_decode_backward(dae_ctx* ctx, const TrainPlan& t, int Vl, int H, int B
     else
         rc = dae_launch_decode_loss_f32(ctx, t.g, B, 1.0f / (float)n_batch, t.dzT, t.Bpad64, t.loss_part, t.dtype, t.dz16);
     if (rc) return rc;
-    if (t.fuse_dh)
-        hipLaunchKernelGGL((loss_fixup_kernel<true, true, true>), dim3(B), dim3(256), 0, st, y_row_ptr, y_col, y_val, B, H, col_lo,
-                           col_hi, t.hbuf, Wd, b_dec, 1.0f / (float)n_batch, t.dzT, (int64_t)t.Bpad64,
-                           t.loss_part + t.g.grid, corr_part);
-    else if (t.dtype == DAE_DTYPE_BF16 && t.dz16)
-        hipLaunchKernelGGL((loss_fixup_kernel<true, true>), dim3(B), dim3(256), 0, st, y_row_ptr, y_col, y_val, B, H, col_lo,
-                           col_hi, t.hbuf, Wd, b_dec, 1.0f / (float)n_batch, t.dzT, (int64_t)t.Bpad64,
-                           t.loss_part + t.g.grid);
-    else if (t.dtype == DAE_DTYPE_BF16)
-        hipLaunchKernelGGL(loss_fixup_kernel<true>, dim3(B), dim3(256), 0, st, y_row_ptr, y_col, y_val, B, H, col_lo,
-                           col_hi, t.hbuf, Wd, b_dec, 1.0f / (float)n_batch, t.dzT, (int64_t)t.Bpad64,
-                           t.loss_part + t.g.grid);
-    else
-        hipLaunchKernelGGL(loss_fixup_kernel<false>, dim3(B), dim3(256), 0, st, y_row_ptr, y_col, y_val, B, H, col_lo,
-                           col_hi, t.hbuf, Wd, b_dec, 1.0f / (float)n_batch, t.dzT, (int64_t)t.Bpad64,
-                           t.loss_part + t.g.grid);
+    auto fixup = [&](auto kernel, float* corr_out) {
+        hipLaunchKernelGGL(kernel, dim3(B), dim3(256), 0, st, y_row_ptr, y_col, y_val, B, H, col_lo, col_hi, t.hbuf, Wd, b_dec,
+                           1.0f / (float)n_batch, t.dzT, (int64_t)t.Bpad64, t.loss_part + t.g.grid, corr_out);
+    };
+    if (t.fuse_dh) fixup(&loss_fixup_kernel<true, true, true>, corr_part);
+    else if (t.dz16) fixup(&loss_fixup_kernel<true, true>, nullptr);
+    else if (t.dtype == DAE_DTYPE_BF16) fixup(&loss_fixup_kernel<true>, nullptr);
+    else fixup(&loss_fixup_kernel<false>, nullptr);
     DAE_CHECK_LAUNCH(ctx, "loss_fixup_kernel");
 
-    // ---- K6: decoder gradient ------------------------------------------------------------------------
-    auto run_k6 = [&]() -> int {
-        GwP p;
-        p.ad_p = nullptr; p.ad_m = nullptr; p.ad_v = nullptr; p.ad_alpha = p.ad_b1 = p.ad_b2 = p.ad_eps = 0.0f;
-        if (ctx->arm_m) {           // dae_arm_decoder_adam: update Wd in place instead of writing gWd
-            p.ad_p = const_cast<float*>(Wd); p.ad_m = ctx->arm_m; p.ad_v = ctx->arm_v; p.ad_alpha = ctx->arm_alpha;
-            p.ad_b1 = ctx->arm_b1; p.ad_b2 = ctx->arm_b2; p.ad_eps = ctx->arm_eps;
-        }
-        p.dzT = t.dzT; p.ldT = t.Bpad64; p.h = t.hbuf; p.H = H; p.B = B; p.V = Vl; p.gW = gWd; p.gb = gb_dec;
-        p.accumulate = 0;
-        p.n_half = H / (32 * NA);
-        int nb = (DAE_NUM_CU / p.n_half) / DAE_NUM_XCD * DAE_NUM_XCD;
-        if (nb < DAE_NUM_XCD) nb = DAE_NUM_XCD;
-        p.nb_half = nb;
-        const size_t lds = (size_t)((B + 31) & ~31) * 32 * NA * sizeof(float);
-        const dim3 grid(p.n_half * nb), blk(256);
-        // two waves per SIMD on the shared h image: 241 us against 257 us with one (V = 170 000, B = H = 256); the
-        // second wave covers the dz^T load latency and the gW stores of the first
-        if (NA == 4 && t.dtype == DAE_DTYPE_BF16) {          // (NA == 4 is H % 128 == 0: dz^T is bf16, t.dz16)
-            const size_t lds_t = (size_t)(((B + 31) & ~31) >> 4) * 4 * 64 * sizeof(uint4);
-            DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &grad_wdec_t_kernel<8>, 160 * 1024));
-            if (p.ad_m) {
-                DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &grad_wdec_t32_kernel<8, true>, 64 * 1024));
-                DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &grad_wdec_t32_kernel<8, false>, 64 * 1024));
-                if (((B + 31) & ~31) == 256) hipLaunchKernelGGL((grad_wdec_t32_kernel<8, true>), grid, dim3(512), lds_t, st, p);
-                else hipLaunchKernelGGL((grad_wdec_t32_kernel<8, false>), grid, dim3(512), lds_t, st, p);
-            } else
-            if (((B + 31) & ~31) == 256) {
-                DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &grad_wdec_t_kernel<8, true>, 64 * 1024));
-                hipLaunchKernelGGL((grad_wdec_t_kernel<8, true>), grid, dim3(512), lds_t, st, p);
-            } else
-            hipLaunchKernelGGL((grad_wdec_t_kernel<8>), grid, dim3(512), lds_t, st, p);
-        } else if (NA == 4) {
-            const int Bp32 = (B + 31) & ~31;
-            if (p.ad_m && H == 256 && (Bp32 & 15) == 0) {
-                // (the ring walks the dz^T row four float4 at a time: whole groups of 16 playlists)
-                const size_t lds_f = (size_t)(Bp32 >> 1) * 64 * sizeof(float4);
-                DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &grad_wdec_t32_f32_kernel<8, true>, 128 * 1024));
-                DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &grad_wdec_t32_f32_kernel<8, false>, 128 * 1024));
-                if (Bp32 == 256) hipLaunchKernelGGL((grad_wdec_t32_f32_kernel<8, true>), grid, dim3(512), lds_f, st, p);
-                else hipLaunchKernelGGL((grad_wdec_t32_f32_kernel<8, false>), grid, dim3(512), lds_f, st, p);
-            } else {
-                DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &grad_wdec_kernel<4, 8, true>, 160 * 1024));
-                hipLaunchKernelGGL((grad_wdec_kernel<4, 8, true>), grid, dim3(512), lds, st, p);
-            }
-        } else if (NA == 2) hipLaunchKernelGGL(grad_wdec_kernel<2>, grid, blk, lds, st, p);
-        else hipLaunchKernelGGL(grad_wdec_kernel<1>, grid, blk, lds, st, p);
-        DAE_CHECK_LAUNCH(ctx, "grad_wdec_kernel");
-        return DAE_OK;
+    auto run_k6 = [&](const dae_armed_adam* arm) {
+        return dae_launch_k6(ctx, t.dzT, t.Bpad64, t.dz16, t.hbuf, H, B, Vl, gWd, gb_dec, arm, 0);
     };
-
-    // ---- K7: dh, split over V ------------------------------------------------------------------------
-    auto run_k7 = [&]() -> int {
-        DhP p;
-        p.dzT = t.dzT; p.ldT = t.Bpad64; p.W = Wd; p.H = H; p.V = Vl; p.part = t.part;
-        p.n_chunk = t.n_chunk; p.chunk = t.chunk; p.Bpad64 = t.Bpad64; p.n_half = H / (32 * NA);
-        p.n_rblk = t.Bpad64 / 64;
-        p.fast32 = ((uint64_t)(Vl + 32) * (uint64_t)H * 4 < (1ull << 32) && (uint64_t)(Vl + 32) * (uint64_t)t.Bpad64 * 4 < (1ull << 32)) ? 1 : 0;
-        const int total = p.n_half * p.n_rblk * t.n_chunk;
-        int blocks = (total + 3) / 4;
-        if (blocks > DAE_NUM_CU) blocks = DAE_NUM_CU;
-        if (NA == 4 && t.dtype == DAE_DTYPE_BF16)          // (dz^T is bf16: t.dz16)
-            hipLaunchKernelGGL((grad_hidden_kernel<4, true>), dim3(blocks), dim3(256), 0, st, p);
-        else if (NA == 4) hipLaunchKernelGGL(grad_hidden_kernel<4>, dim3(blocks), dim3(256), 0, st, p);
-        else if (NA == 2) hipLaunchKernelGGL(grad_hidden_kernel<2>, dim3(blocks), dim3(256), 0, st, p);
-        else hipLaunchKernelGGL(grad_hidden_kernel<1>, dim3(blocks), dim3(256), 0, st, p);
-        DAE_CHECK_LAUNCH(ctx, "grad_hidden_kernel");
-        return DAE_OK;
-    };
+    auto run_k7 = [&]() { return launch_k7(ctx, t.dzT, t.Bpad64, t.dz16, Wd, H, Vl, t.Bpad64, t.k7, t.part); };
     // K6 and K7 are independent (both read dz^T).  With the armed Adam K6 rewrites Wd in place, and K7 multiplies by
     // the weights the forward pass used: K7 first.
-    if (ctx->arm_m) {
-        if (NA != 4) { ctx->arm_m = nullptr; return dae_fail(ctx, DAE_ERR_ARG, "the armed decoder Adam needs H %% 128 == 0 (H=%d)", H); }
-        if (!t.fuse_dh) { rc = run_k7(); if (rc) return rc; }
-        rc = run_k6();
+    if (ctx->arm_m) {           // dae_arm_decoder_adam: update Wd in place instead of writing gWd
+        const dae_armed_adam arm = {const_cast<float*>(Wd), ctx->arm_m, ctx->arm_v, ctx->arm_alpha, ctx->arm_b1, ctx->arm_b2,
+                                    ctx->arm_eps};
         ctx->arm_m = nullptr; ctx->arm_v = nullptr;         // one step only
-        return rc;
+        if ((H % 128) != 0) return dae_fail(ctx, DAE_ERR_ARG, "the armed decoder Adam needs H %% 128 == 0 (H=%d)", H);
+        if (!t.fuse_dh) { rc = run_k7(); if (rc) return rc; }
+        return run_k6(&arm);
     }
-    rc = run_k6(); if (rc) return rc;
+    rc = run_k6(nullptr); if (rc) return rc;
     return t.fuse_dh ? DAE_OK : run_k7();
 }
 
@@ -1728,59 +766,19 @@ int train_encoder_backward(dae_ctx* ctx, const TrainPlan& t, const float* part, 
 
 }  // namespace
 
-// ---- the two backward GEMMs on caller-provided buffers (also used by the title scorer's output layer) ---
-// gW[v, :] = sum_r dzT[v, r] h[r, :]  and  gb[v] = sum_r dzT[v, r]   (H % 32 == 0, B <= 256)
-int dae_launch_grad_w(dae_ctx* ctx, const float* dzT, int64_t ldT, const float* h, int H, int B, int V,
-                      float* gW, float* gb)
-{
-    if ((H % 32) != 0 || B < 1 || B > 256) return dae_fail(ctx, DAE_ERR_ARG, "grad_w: H=%d B=%d unsupported", H, B);
-    const int NA = (H % 128) == 0 ? 4 : ((H % 64) == 0 ? 2 : 1);
-    GwP p;
-    p.ad_p = nullptr; p.ad_m = nullptr; p.ad_v = nullptr; p.ad_alpha = p.ad_b1 = p.ad_b2 = p.ad_eps = 0.0f;
-    p.dzT = dzT; p.ldT = ldT; p.h = h; p.H = H; p.B = B; p.V = V; p.gW = gW; p.gb = gb;
-    p.accumulate = 0;
-    p.n_half = H / (32 * NA);
-    int nb = (DAE_NUM_CU / p.n_half) / DAE_NUM_XCD * DAE_NUM_XCD;
-    if (nb < DAE_NUM_XCD) nb = DAE_NUM_XCD;
-    p.nb_half = nb;
-    const size_t lds = (size_t)((B + 31) & ~31) * 32 * NA * sizeof(float);
-    DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &grad_wdec_kernel<4>, 160 * 1024));
-    const dim3 grid(p.n_half * nb), blk(256);
-    if (NA == 4) hipLaunchKernelGGL(grad_wdec_kernel<4>, grid, blk, lds, ctx->stream, p);
-    else if (NA == 2) hipLaunchKernelGGL(grad_wdec_kernel<2>, grid, blk, lds, ctx->stream, p);
-    else hipLaunchKernelGGL(grad_wdec_kernel<1>, grid, blk, lds, ctx->stream, p);
-    DAE_CHECK_LAUNCH(ctx, "grad_wdec_kernel");
-    return DAE_OK;
-}
-
+// ---- K7 on caller-provided buffers (the title scorer's output layer; its K6 is grad_wdec.hip dae_launch_grad_w) ---
 // dh[r, :] = sum_v dzT[v, r] W[v, :]  (split over V into ctx scratch, reduced in fixed order)
 int dae_launch_grad_h(dae_ctx* ctx, const float* dzT, int64_t ldT, const float* W, int H, int V, int B, float* dh)
 {
     if ((H % 32) != 0 || B < 1 || B > 256) return dae_fail(ctx, DAE_ERR_ARG, "grad_h: H=%d B=%d unsupported", H, B);
-    const int NA = (H % 128) == 0 ? 4 : ((H % 64) == 0 ? 2 : 1);
     const int Bpad64 = (B + 63) / 64 * 64;
     if (ldT < Bpad64) return dae_fail(ctx, DAE_ERR_ARG, "grad_h: ldT=%lld < %d", (long long)ldT, Bpad64);
-    const int n_out_tiles = (H / (32 * NA)) * (Bpad64 / 64);
-    int want_chunks = (DAE_NUM_CU * 4) / n_out_tiles;
-    if (want_chunks < 1) want_chunks = 1;
-    int chunk = ((V + want_chunks - 1) / want_chunks + 15) / 16 * 16;
-    if (chunk < 16) chunk = 16;
-    const int n_chunk = (V + chunk - 1) / chunk;
+    const K7Plan k = k7_plan(V, H, Bpad64);
+    const int n_chunk = k.n_chunk;
     int rc = dae_reserve(ctx, ctx->train_d, (size_t)n_chunk * Bpad64 * H * sizeof(float));
     if (rc) return rc;
     float* part = static_cast<float*>(ctx->train_d.p);
-    DhP p;
-    p.dzT = dzT; p.ldT = ldT; p.W = W; p.H = H; p.V = V; p.part = part;
-    p.n_chunk = n_chunk; p.chunk = chunk; p.Bpad64 = Bpad64; p.n_half = H / (32 * NA);
-    p.n_rblk = Bpad64 / 64;
-    p.fast32 = ((uint64_t)(V + 32) * (uint64_t)H * 4 < (1ull << 32) && (uint64_t)(V + 32) * (uint64_t)ldT * 4 < (1ull << 32)) ? 1 : 0;
-    const int total = p.n_half * p.n_rblk * n_chunk;
-    int blocks = (total + 3) / 4;
-    if (blocks > DAE_NUM_CU) blocks = DAE_NUM_CU;
-    if (NA == 4) hipLaunchKernelGGL(grad_hidden_kernel<4>, dim3(blocks), dim3(256), 0, ctx->stream, p);
-    else if (NA == 2) hipLaunchKernelGGL(grad_hidden_kernel<2>, dim3(blocks), dim3(256), 0, ctx->stream, p);
-    else hipLaunchKernelGGL(grad_hidden_kernel<1>, dim3(blocks), dim3(256), 0, ctx->stream, p);
-    DAE_CHECK_LAUNCH(ctx, "grad_hidden_kernel");
+    if ((rc = launch_k7(ctx, dzT, ldT, 0, W, H, V, Bpad64, k, part))) return rc;
     const size_t bh = (size_t)B * H;
     hipLaunchKernelGGL(sum_chunks_kernel, dim3(grid_for(bh)), dim3(256), 0, ctx->stream, part, n_chunk,
                        (size_t)Bpad64 * H, bh, dh);

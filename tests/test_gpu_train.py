@@ -367,13 +367,27 @@ def test_model_rows_adam_follows_dense_adam():
         assert np.allclose(pa, pb, rtol=1e-3, atol=2e-6)
 
 
-@pytest.mark.parametrize("bf16", [False, True])
-def test_armed_decoder_adam_is_bit_identical(bf16):
+# (V, nt, H, B) -> the armed decoder-gradient kernel the fp32 / the bf16 step runs (grad_wdec.hip, the launcher's decision list)
+ARMED_SHAPES = [
+    (3000, 2400, 128, 100),      # grad_wdec_kernel<4,8,true> / grad_wdec_t32_kernel<8,false>, one hidden half
+    (3000, 2400, 256, 256),      # the FULL instances: grad_wdec_t32_f32_kernel<8,true> / grad_wdec_t32_kernel<8,true>
+    (3000, 2400, 256, 250),      # FULL with zero-padded rows (256 padded rows, 250 real ones)
+    (3000, 2400, 256, 100),      # the non-FULL t32 instances at hidden 256: two hidden halves
+    (3000, 2400, 256, 5),        # 2 k-steps of 16 rows (8 float4 in fp32) under a ring of 4: the clamped refill
+    (40, 30, 256, 37),           # two tiles of 32 decoder rows, the second with 8; almost every wave idle
+    (33000, 26000, 256, 256),    # 1 032 tiles for 1 024 wave slots: eight waves take a second tile, the last tile has 8 rows
+    (3000, 2400, 384, 100),      # three hidden halves: grad_wdec_kernel<4,8,true> armed / grad_wdec_t32_kernel<8,false>
+]
+
+
+@pytest.mark.parametrize("bf16", [False, True], ids=["f32", "bf16"])
+@pytest.mark.parametrize("V,nt,H,B", ARMED_SHAPES, ids=["V%d-H%d-B%d" % (s[0], s[2], s[3]) for s in ARMED_SHAPES])
+def test_armed_decoder_adam_is_bit_identical(V, nt, H, B, bf16):
     """dae_arm_decoder_adam: the step applies the dense Adam update of W_dec inside the decoder-gradient kernel.
     Same inputs, same draws: W_dec / m / v must be the bits of `write gW_dec, then dae_adam_step`, and every other
-    output of the step (cost, gW_enc, gb_enc, gb_dec) must be unchanged -- K7 still multiplies by the old W_dec."""
+    output of the step (cost, gW_enc, gb_enc, gb_dec) must be unchanged -- K7 still multiplies by the old W_dec.
+    The shapes reach every armed instance, every clamp of their dz^T rings and a wave's second tile."""
     import torch
-    V, nt, H, B = 3000, 2400, 128, 100
     W_enc, b_enc, W_dec, b_dec = make_weights(V, H, seed=4, bias="zipf", n_tracks=nt)
     pos, ones, _ = make_playlists(B, nt, V - nt, seed=6, seed_counts=(3, 9, 20))
     xr, xc, xv = coo_to_csr(pos[pos[:, 1] < nt], ones[pos[:, 1] < nt], B, V)
