@@ -71,6 +71,15 @@ def encode(row_ptr, col, val, W_enc, b_enc, ikp=1.0, kp=1.0, seed=0):
     return h
 
 
+def row_sums(row_ptr, col, val, ikp=1.0, seed=0):
+    """The reduce_sum (DAEs.py:41) of every row after input dropout: what orc_encode adds 1e-10 to and divides by."""
+    row_ptr, col, val = _i32(row_ptr), _i32(col), _f32(val)
+    B = row_ptr.size - 1
+    out = np.empty(B, dtype=np.float32)
+    lib().orc_row_sums(_p(row_ptr), _p(col), _p(val), ctypes.c_int(B), ctypes.c_float(ikp), ctypes.c_uint32(seed), _p(out))
+    return out
+
+
 def decode(h, W_dec, b_dec, col_lo=0, col_hi=None, apply_sigmoid=False, bf16=False):
     h, W_dec, b_dec = _f32(h), _f32(W_dec), _f32(b_dec)
     B, H = h.shape

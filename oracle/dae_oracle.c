@@ -85,6 +85,32 @@ uint32_t orc_okey(float f)
  * :66-68 encoder matmul + bias + sigmoid + hidden dropout.
  * Canonical order: non-zeros in ascending column order, one fmaf per non-zero per hidden unit.
  * ---------------------------------------------------------------------------------------------- */
+/* One row's input dropout and reduce_sum (DAEs.py:40-41): xd[i] = the dropped-out value of entry i (xd may be NULL),
+ * returns s = their sum, added one after the other in entry order.  orc_encode divides by this s + 1e-10f. */
+static float row_dropout_sum(const int32_t* col, const float* val, int beg, int nnz,
+                             float ikp, uint32_t seed, int r, float* xd)
+{
+    float s = 0.0f;
+    for (int i = 0; i < nnz; ++i) {
+        float x = val[beg + i];
+        if (ikp < 1.0f) {                                       /* tf.nn.dropout: x/kp*floor(kp+u) */
+            float u = orc_uniform(seed, 0U, (uint32_t)r, (uint32_t)col[beg + i]);
+            x = (x / ikp) * floorf(ikp + u);
+        }
+        if (xd) xd[i] = x;
+        s += x;                                                 /* reduce_sum, DAEs.py:41 */
+    }
+    return s;
+}
+
+/* out[r] = the reduce_sum of row r (DAEs.py:41) that orc_encode normalises by: the reference of dae_row_sums. */
+void orc_row_sums(const int32_t* row_ptr, const int32_t* col, const float* val, int B,
+                  float ikp, uint32_t seed, float* out)
+{
+    for (int r = 0; r < B; ++r)
+        out[r] = row_dropout_sum(col, val, row_ptr[r], row_ptr[r + 1] - row_ptr[r], ikp, seed, r, NULL);
+}
+
 void orc_encode(const int32_t* row_ptr, const int32_t* col, const float* val,
                 const float* W_enc, const float* b_enc, int V, int H, int B,
                 float ikp, float kp, uint32_t seed, float* h_out)
@@ -95,16 +121,7 @@ void orc_encode(const int32_t* row_ptr, const int32_t* col, const float* val,
         const int beg = row_ptr[r], end = row_ptr[r + 1];
         const int nnz = end - beg;
         float* xd = (float*)malloc(sizeof(float) * (size_t)(nnz > 0 ? nnz : 1));
-        float s = 0.0f;
-        for (int i = 0; i < nnz; ++i) {
-            float x = val[beg + i];
-            if (ikp < 1.0f) {                                   /* tf.nn.dropout: x/kp*floor(kp+u) */
-                float u = orc_uniform(seed, 0U, (uint32_t)r, (uint32_t)col[beg + i]);
-                x = (x / ikp) * floorf(ikp + u);
-            }
-            xd[i] = x;
-            s += x;                                             /* reduce_sum, DAEs.py:41 */
-        }
+        const float s = row_dropout_sum(col, val, beg, nnz, ikp, seed, r, xd);
         const float denom = s + 1e-10f;                         /* DAEs.py:42 */
         for (int j = 0; j < H; ++j) acc[j] = 0.0f;
         for (int i = 0; i < nnz; ++i) {

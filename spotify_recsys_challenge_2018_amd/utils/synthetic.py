@@ -53,6 +53,43 @@ def make_playlists(B, n_tracks, n_artists, seed=1, dist="zipf", seed_counts=(1, 
     return x_positions, x_ones, seeds
 
 
+# Row lengths on and around every boundary of the kernels that walk an input row: the encode kernels' groups of 16 entries
+# inside a 64-entry chunk, the 256 entries encode_split_kernel keeps in registers and the groups of 16 / 32 of its tail
+# chunks (256 + 16, + 32, + 64), 512 entries, and the 1 024 entries scatter_gwenc_kernel stages in LDS at a time.
+ROW_LENGTHS = (0, 1, 15, 16, 17, 31, 32, 33, 47, 48, 49, 63, 64, 65, 127, 128, 129, 255, 256, 257, 271, 272, 273, 287, 288,
+               289, 319, 320, 321, 500, 513, 1023, 1024, 1025, 2100)
+
+
+def rows_of_lengths(lengths, V, seed, values="reader", B=None, n_tracks=None):
+    """A CSR batch (row_ptr int32 [B + 1], col int32, val float32) whose row r holds exactly lengths[r % len(lengths)]
+    entries: columns drawn without replacement from [0, V), ascending and unique per row (the CSR contract of
+    include/dae_hip.h).  B defaults to len(lengths).  values:
+      "reader"  what the readers feed (data_reader.py:317): 1.0 for a track column (< n_tracks, default 0.8 V), 0.5 for
+                an artist column;
+      "any"     positive fp32 values of any size: exp(N(0, 1)), every seventh entry one of 0.15 / 1e-3 / 3.0."""
+    lengths = [int(n) for n in lengths]
+    B = len(lengths) if B is None else int(B)
+    n_tracks = int(0.8 * V) if n_tracks is None else int(n_tracks)
+    if max(lengths, default=0) > V or min(lengths, default=0) < 0:
+        raise ValueError("row lengths must lie in [0, V = %d]" % V)
+    if values not in ("reader", "any"):
+        raise ValueError("values %r: 'reader' or 'any'" % (values,))
+    rng = np.random.default_rng(seed)
+    row_ptr = np.zeros(B + 1, np.int64)
+    cols = []
+    for r in range(B):
+        n = lengths[r % len(lengths)]
+        cols.append(np.sort(rng.permutation(V)[:n]))
+        row_ptr[r + 1] = row_ptr[r] + n
+    col = np.concatenate(cols) if cols else np.zeros(0, np.int64)
+    if values == "reader":
+        val = np.where(col < n_tracks, np.float32(1.0), np.float32(0.5)).astype(np.float32)
+    else:
+        val = np.exp(rng.standard_normal(col.size)).astype(np.float32)
+        val[::7] = np.array([0.15, 1e-3, 3.0], np.float32)[np.arange(val[::7].size) % 3]
+    return row_ptr.astype(np.int32), col.astype(np.int32), val
+
+
 # ---- a TRAINED model without MPD data: clustered playlists ------------------------------------------------------------
 # The Xavier + Zipf-bias model above is popularity-dominated: every playlist of a batch ranks nearly the same tracks first.
 # A model trained on playlists with structure ranks them differently per playlist, its decoder rows have very

@@ -259,15 +259,16 @@ def test_long_target_rows(H, B):
     check_f32(f32, c)
 
 
-def run_sharded(c, world, check_rows=None):
-    """The bf16 step of case c (untied, no dropout, lambda 0) through HipTrainStages over `world` vocabulary shards on one
-    device: the concatenated gradients and the summed cost, as run_step returns them."""
+def run_sharded(c, world, check_rows=None, dtype=_lib.DAE_DTYPE_BF16):
+    """The step of case c (bf16 unless dtype says fp32; tied or untied, keep probabilities and lambda as the case has them)
+    through HipTrainStages over `world` vocabulary shards on one device: the concatenated gradients and the summed cost,
+    as run_step returns them."""
     import torch
-    V, H, B = c["V"], c["H"], c["B"]
+    V, H, B, tied = c["V"], c["H"], c["B"], c["tied"]
     W_enc, b_enc, W_dec, b_dec = c["W"]
-    nb = c["n_batch"]
+    nb, ikp, kp, lam = c["n_batch"], c["ikp"], c["kp"], c["lam"]
     ctx = _lib.Context(0)
-    ctx.set_train_dtype(_lib.DAE_DTYPE_BF16)
+    ctx.set_train_dtype(dtype)
     st = HipTrainStages(ctx)
     x = tuple(_dev(a) for a in c["csr"][:3])
     y = tuple(_dev(a) for a in c["csr"][3:])
@@ -277,29 +278,32 @@ def run_sharded(c, world, check_rows=None):
     if check_rows is not None:
         check_rows(bounds)
     for lo, hi in bounds:
-        d = dict(lo=lo, hi=hi, We=_dev(W_enc[lo:hi]), bd=_dev(b_dec[lo:hi]), Wd=_dev(W_dec[lo:hi]))
+        d = dict(lo=lo, hi=hi, We=_dev(W_enc[lo:hi]), bd=_dev(b_dec[lo:hi]), Wd=None if tied else _dev(W_dec[lo:hi]))
         d.update(gWe=torch.zeros((hi - lo, H), device="cuda"), gbd=torch.zeros(hi - lo, device="cuda"),
-                 gWd=torch.zeros((hi - lo, H), device="cuda"), gbe=torch.zeros(H, device="cuda"),
+                 gWd=None if tied else torch.zeros((hi - lo, H), device="cuda"), gbe=torch.zeros(H, device="cuda"),
                  pre=torch.zeros((B, H), device="cuda"), dh=torch.zeros((B, H), device="cuda"),
                  cost=torch.zeros(1, device="cuda"))
         sh.append(d)
+
+    def decode(d):
+        st.decode(pre, be, y, d["We"], d["Wd"], d["bd"], d["lo"], d["hi"], nb, tied, kp, SEED, lam,
+                  d["gWe"] if tied else d["gWd"], d["gbd"], d["dh"], d["cost"])
     for d in sh:
-        st.encode(x, d["We"], d["lo"], d["hi"], 1.0, SEED, d["pre"])
+        st.encode(x, d["We"], d["lo"], d["hi"], ikp, SEED, d["pre"])
     pre = sum(d["pre"] for d in sh)
     for d in sh:
-        st.decode(pre, be, y, d["We"], d["Wd"], d["bd"], d["lo"], d["hi"], nb, False, 1.0, SEED, 0.0,
-                  d["gWd"], d["gbd"], d["dh"], d["cost"])
+        decode(d)
     dh = sum(d["dh"] for d in sh)
     cost = float(sum(d["cost"] for d in sh).item())
     for d in sh:
-        st.decode(pre, be, y, d["We"], d["Wd"], d["bd"], d["lo"], d["hi"], nb, False, 1.0, SEED, 0.0,
-                  d["gWd"], d["gbd"], d["dh"], d["cost"])      # re-establish this shard's scratch
-        st.finish(dh, x, d["We"], be, d["Wd"], d["bd"], d["lo"], d["hi"], False, 1.0, 1.0, SEED, 0.0,
+        decode(d)                                                  # re-establish this shard's scratch
+        st.finish(dh, x, d["We"], be, d["Wd"], d["bd"], d["lo"], d["hi"], tied, ikp, kp, SEED, lam,
                   d["gWe"], d["gbe"], d["gWd"], d["gbd"])
     torch.cuda.synchronize()
     got = dict(gW_enc=torch.cat([d["gWe"] for d in sh]).cpu().numpy(), gb_enc=sh[0]["gbe"].cpu().numpy(),
-               gW_dec=torch.cat([d["gWd"] for d in sh]).cpu().numpy(), gb_dec=torch.cat([d["gbd"] for d in sh]).cpu().numpy(),
-               cost=cost)
+               gb_dec=torch.cat([d["gbd"] for d in sh]).cpu().numpy(), cost=cost)
+    if not tied:
+        got["gW_dec"] = torch.cat([d["gWd"] for d in sh]).cpu().numpy()
     ctx.close()
     return got
 
