@@ -92,9 +92,10 @@ const char* dae_profile_kernel(const dae_ctx* ctx);
  * wall clock's rate (hipDeviceAttributeWallClockRate).  GHz = cycles / ticks * wall_khz / 1e6. */
 int dae_clock_probe(dae_ctx* ctx, void* hip_stream, int window_us, uint64_t* out2_dev, int* wall_khz_out);
 
-/* Geometry of the last dae_decode_topk issued from the calling thread, for roofline accounting:
+/* Geometry of the last dae_decode_topk or dae_mix_topk_exact issued from the calling thread, for roofline accounting:
  * {R_TILE, n_row_groups, blocks_per_row_group, sample_stride S, n_sample_tiles (phase A),
- *  n_filter_tiles (phase B), fused(0/1), n_tiles}.  A tile is 32 vocabulary columns. */
+ *  n_filter_tiles (phase B), fused(0/1), n_tiles}.  A tile is 32 vocabulary columns.  (dae_mix_topk_exact: S = 1,
+ * fused = 0; its filter launch gives every workgroup of blocks_per_row_group 8 waves that claim tiles.) */
 int dae_last_plan(int32_t out[8]);
 
 /* ---- input: COO -> CSR (DAEs.py:33-38 SparseTensor + sparse_tensor_to_dense) --------------- */
@@ -534,8 +535,12 @@ int dae_set_score_mix(dae_ctx* ctx, const float* mixT, int64_t ld, int n_cols, c
  * on bounds of the two logits (sample: lower bounds -> threshold; filter: upper bounds -> candidates), and the candidates'
  * logits are recomputed with the canonical fp32 chains and mixed with dae_mix_scores' operations before they are ranked.
  * No [B, V] matrix and no transposed term.  Called on the TITLE scorer's context; `dae` is the DAE's.  Both must hold
- * their weights prepacked with DAE_DTYPE_BF16_EXACT over the same columns [0, V) (DAE: hidden 256; title: Output_W^T in
- * rows of 448), and be bound to the same stream.  feat [B][ld_feat]: title features (dae_title_features; any finite
+ * their weights prepacked with DAE_DTYPE_BF16_EXACT over the same columns [0, V), and be bound to the same stream.
+ * SHAPES: dae_mix_exact_shape_ok(hidden, ld_feat) -- DAE hidden 128 .. 512 and title rows (Output_W^T, the feature row
+ * length) 64 .. 512, both in steps of 64.  The launch was built for hidden 256 and rows of 448, which keep a kernel unrolled
+ * for them; the other shapes share one kernel that takes the two step counts at run time (row groups of 96 playlists while
+ * both scorers' rows fit the CU's LDS, of 64 beyond hidden + row length 832).  Any other shape: DAE_ERR_ARG -- rank it
+ * with DAE_DTYPE_F32, which returns the same lists.  feat [B][ld_feat]: title features (dae_title_features; any finite
  * values -- the bound scales with the row's largest |feature|), h [B][ld_h]: the DAE's fp32 hidden rows (dae_encode),
  * w_title / w_playlist [B] in [0, 1] (DAEs.py:159-162).  Rows that violate a precondition return no recommendations
  * (idx -1).  The bound guard of the plain exact mode covers both GEMMs: dae_exact_guard_read / _words on the title
@@ -568,6 +573,9 @@ int dae_title_score_exact(dae_ctx* title_ctx, dae_ctx* dae, const int64_t* posit
 int dae_mix_topk_exact(dae_ctx* title_ctx, dae_ctx* dae, const float* feat, int64_t ld_feat, const float* h, int64_t ld_h,
                        int B, const float* w_title, const float* w_playlist, int n_tracks, const int32_t* seed_row_ptr,
                        const int32_t* seed_col, int k, float* out_score, int32_t* out_idx, int32_t* guard_out);
+/* 1 when dae_mix_topk_exact (and dae_title_score under DAE_DTYPE_BF16_EXACT) takes a DAE of this hidden size with title
+ * feature rows of this length, 0 otherwise.  Needs no context and no device. */
+int dae_mix_exact_shape_ok(int hidden, int ld_feat);
 
 /* Training of the title variables (main_train.py:214-221 feeds the playlist as x AND y, titles_use = 1; the DAE
  * arrays are constants, DAEs.py:165-171).  The caller runs the forward pieces -- dae_encode (dropout on) +

@@ -1,6 +1,8 @@
 #!/usr/bin/env python
-"""The titled drivers' loop alone, one mode per call (for rocprofv3): python scripts/time_title.py <f32|bf16|exact_bf16> [n_feeds]
-Shapes of scripts/bench_title.py ([TITLE] batch = 150, filters 3/5/7/9 x 100, 170 000 columns)."""
+"""The titled drivers' loop alone, one mode per call (for rocprofv3):
+python scripts/time_title.py <f32|bf16|exact_bf16> [n_feeds] [hidden] [filter_num]
+Shapes of scripts/bench_title.py ([TITLE] batch = 150, filters 3/5/7/9 x 100, 170 000 columns) unless [DAE] hidden and [TITLE]
+filter_num are given (feature rows of 4 x filter_num, padded to 64)."""
 import os
 import pickle
 import sys
@@ -17,7 +19,7 @@ from spotify_recsys_challenge_2018_amd.models.title_models import get_model   # 
 from spotify_recsys_challenge_2018_amd.utils.synthetic import make_playlists, make_weights   # noqa: E402
 
 
-def build(B=150, nt=140000, na=30000, H=256):
+def build(B=150, nt=140000, na=30000, H=256, n_filters=100):
     V = nt + na
     W_enc, b_enc, W_dec, b_dec = make_weights(V, H, seed=0, bias=os.environ.get("BIAS", "zipf"), n_tracks=nt)
     W_dec = (W_dec * np.float32(float(os.environ.get("SCALE", "1")))).astype(np.float32)
@@ -27,7 +29,7 @@ def build(B=150, nt=140000, na=30000, H=256):
 
     class C:
         batch = B; n_input = V; n_output = V; n_tracks = nt; hidden = H; lr = 0.001; reg_lambda = 0.0
-        char_emb = 50; strmaxlen = 25; charsize = 41; char_model = 'Char_CNN'; filter_num = 100
+        char_emb = 50; strmaxlen = 25; charsize = 41; char_model = 'Char_CNN'; filter_num = n_filters
         filter_size = [3, 5, 7, 9]; save = "/tmp/_t_unused"; initval = "NULL"; DAEval = path; title_lr = 0.001
     mt = get_model(C()); mt.fit()
     m = DAE_title(C(), mt); m.fit()
@@ -42,7 +44,7 @@ def main():
     import torch
     mode = sys.argv[1] if len(sys.argv) > 1 else "f32"
     n = int(sys.argv[2]) if len(sys.argv) > 2 else 40
-    m, feed = build()
+    m, feed = build(H=int(sys.argv[3]) if len(sys.argv) > 3 else 256, n_filters=int(sys.argv[4]) if len(sys.argv) > 4 else 100)
     if os.environ.get('TITLE_COALESCE'):
         m.coalesce = int(os.environ['TITLE_COALESCE'])
     if os.environ.get('TITLE_LANES'):
@@ -76,7 +78,8 @@ def main():
     torch.cuda.synchronize()
     print("  device-wide synchronize after the loop: %.2f ms (not part of the rate)" % ((time.perf_counter() - t_end) * 1e3))
     ds = (t_end - t0) / n
-    print("titled recommend_iter %s: %.3f ms per batch of 150 = %.0f playlists/s (first lists after %.2f ms)" % (mode, ds * 1e3, 150 / ds, first * 1e3))
+    print("titled recommend_iter %s hidden %d rows %d: %.3f ms per batch of 150 = %.0f playlists/s (first lists after %.2f ms)"
+          % (mode, m.n_hidden, m.title_model.ld, ds * 1e3, 150 / ds, first * 1e3))
     for _g, pipe in m.__dict__.get("_pipes", {}).values():
         print("  pipeline:", pipe.stats(), pipe.times())
     if mode == "exact_bf16":

@@ -19,7 +19,7 @@ EXPORTS = [
     "dae_exact_guard_read", "dae_exact_guard_words", "dae_exact_guard_snapshot", "dae_exact_stats_read", "dae_set_exact_margin", "dae_set_exact_margin_range", "dae_set_exact_audit", "dae_exact_audit_read", "dae_decode_dense", "dae_decode_topk",
     "dae_score_topk", "dae_score_topk_begin", "dae_score_topk_finish", "dae_topk_dense", "dae_topk_merge", "dae_set_train_dtype", "dae_train_forward_backward",
     "dae_train_shard_encode", "dae_train_shard_decode", "dae_train_shard_finish", "dae_title_features", "dae_title_prepack_features",
-    "dae_mix_scores", "dae_decode_mix_term", "dae_set_score_mix", "dae_mix_topk_exact", "dae_title_score_exact", "dae_title_score", "dae_row_sums", "dae_mix_weights", "dae_title_loss_backward", "dae_title_conv_backward", "dae_adam_step",
+    "dae_mix_scores", "dae_decode_mix_term", "dae_set_score_mix", "dae_mix_topk_exact", "dae_mix_exact_shape_ok", "dae_title_score_exact", "dae_title_score", "dae_row_sums", "dae_mix_weights", "dae_title_loss_backward", "dae_title_conv_backward", "dae_adam_step",
     "dae_adam_rows_begin", "dae_adam_rows_apply", "dae_adam_rows_flush", "dae_set_enc_grad_prezeroed",
     "dae_arm_decoder_adam", "dae_set_decode_gate", "dae_set_overlap_hint",
     "dae_pipeline_create", "dae_pipeline_create_titled", "dae_pipeline_destroy", "dae_pipeline_submit", "dae_pipeline_submit_titled", "dae_pipeline_flush", "dae_pipeline_poll",
@@ -104,6 +104,7 @@ def load():
     lib.dae_decode_mix_term.argtypes = [vp, vp, c_int, c_int, c_int, vp, c_int, vp, c_i64]
     lib.dae_set_score_mix.argtypes = [vp, vp, c_i64, c_int, vp]
     lib.dae_mix_topk_exact.argtypes = [vp, vp, vp, c_i64, vp, c_i64, c_int, vp, vp, c_int, vp, vp, c_int, vp, vp, vp]
+    lib.dae_mix_exact_shape_ok.argtypes = [c_int, c_int]
     lib.dae_row_sums.argtypes = [vp, vp, vp, vp, c_int, c_f, c_u32, vp]
     lib.dae_title_score_exact.argtypes = [vp, vp, vp, vp, c_int, c_i64, c_int, c_int, vp, vp, c_int, vp, c_int, vp, c_int, c_int, vp, vp,
                                           ctypes.POINTER(ctypes.c_int32), c_int, c_int, c_int, vp, c_int, c_int, vp, vp, vp, vp]
@@ -152,6 +153,12 @@ def load():
             getattr(lib, name).restype = c_int
     _lib = lib
     return lib
+
+
+def mix_exact_shape_ok(hidden, ld_feat):
+    """Does the exact title mix (dae_mix_topk_exact) take a DAE of this hidden size with title feature rows of this length?
+    The library's own rule (dae_mix_exact_shape_ok): no context, no device."""
+    return bool(load().dae_mix_exact_shape_ok(int(hidden), int(ld_feat)))
 
 
 def _ptr(t):

@@ -111,6 +111,12 @@ const dae_packed* packed_for(dae_ctx* ctx, int dtype, int H)
 
 }  // namespace
 
+// dae_mix_topk_exact leaves its geometry in the same words (mixexact.hip): S = 1, fused = 0
+void dae_note_plan(int R_TILE, int n_rg, int nb_rg, int n_samp, int n_filter, int ntiles)
+{
+    g_plan = Plan{R_TILE, n_rg, nb_rg, 1, n_samp, n_filter, 0, ntiles};
+}
+
 extern "C" {
 
 int dae_version(void) { return 1000; }
@@ -237,7 +243,7 @@ int dae_clock_probe(dae_ctx* ctx, void* hip_stream, int window_us, uint64_t* out
     return DAE_OK;
 }
 
-/* geometry of the last dae_decode_topk on this thread:
+/* geometry of the last dae_decode_topk / dae_mix_topk_exact on this thread:
  * {R_TILE, n_rg, nb_rg, S, n_sample_tiles, n_filter_tiles, fused(0/1), ntiles} */
 int dae_last_plan(int32_t out[8])
 {

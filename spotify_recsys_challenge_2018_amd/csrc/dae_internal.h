@@ -425,6 +425,7 @@ int dae_launch_mix_scores(dae_ctx* ctx, const float* title_score, int64_t ld_t, 
 // mixexact.hip (DAE_DTYPE_BF16_EXACT under the title mix)
 int dae_launch_mix_title_bounds(dae_ctx* ctx, const float* W, const float* b, int H, int Hp, int col_lo, int col_hi,
                                 int ntiles, dae_packed& pk);
+void dae_note_plan(int R_TILE, int n_rg, int nb_rg, int n_samp, int n_filter, int ntiles);      // api.hip: what dae_last_plan reports
 int dae_mix_topk_exact_impl(dae_ctx* tc, dae_ctx* dc, const float* feat, int64_t ld_feat, const float* h, int64_t ld_h, int B,
                             const float* w_title, const float* w_playlist, int n_tracks, const int32_t* seed_row_ptr,
                             const int32_t* seed_col, int k, float* out_score, int32_t* out_idx);

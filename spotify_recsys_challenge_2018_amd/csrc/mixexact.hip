@@ -50,6 +50,8 @@ constexpr int MX_RB = 3;            // row blocks of 32 playlists per row group:
 constexpr int MX_NW = 8;            // waves per workgroup (two per SIMD: one's epilogue under the other's MFMAs)
 constexpr int MX_QR = 8;            // W ring depth (steps)
 constexpr int MX_REF_CAP = 8192;    // survivors per row the refine launch's compact lists hold
+constexpr int MX_MAX_STEPS = 32;    // MFMA steps of one image at the largest supported shape (hidden / row length 512)
+constexpr size_t MX_LDS_BYTES = 160 * 1024;      // LDS of a CU: what one workgroup can be given
 
 // the mixed score with the operations of mix_scores_kernel (title.hip) / the fp32 mix epilogue (decode_generic.hip), in their order
 __device__ __forceinline__ float mixf(float zt, float zd, float wt, float wp)
@@ -124,7 +126,81 @@ struct MixP {
     int B, n_rg, nb_rg, Bpad;
     uint4* cand; int* cand_cnt; int cap;         // filter: [bir][Bpad][cap] entries (u_t, u_d, column, 0) + [bir][Bpad] counts
     float* samp; int64_t ld_s;                   // sample: [B][ld_s] maxima of 4-column groups, element item * 8 + 4 hi + qd
+    int nsD, nsT;                                // mix_bf16_steps_kernel: MFMA steps of the two images (H / 16, both multiples of 4)
 };
+
+// ---- the two epilogues of a decoded tile: lane = playlist j of row block rb; register reg is column
+// 32 t + 4 hi + (reg & 3) + 8 (reg >> 2)
+// filter (MODE 0): the columns whose pair of upper logits can reach the row's threshold go to the row's candidate segment
+template <int RB>
+__device__ __forceinline__ void mix_filter_epilogue(const MixP& p, const f32x16 (&accD)[RB], const f32x16 (&accT)[RB],
+                                                    const float (&tau_r)[RB], const float (&wt_r)[RB], const float (&wp_r)[RB],
+                                                    int* lcnt, int t, int rg, int bir, int hi, int j)
+{
+    constexpr int R_TILE = RB * 32;
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb) {
+        const float tv = tau_r[rb], wt = wt_r[rb], wp = wp_r[rb];
+        float mT = accT[rb][0], mD = accD[rb][0];
+#pragma unroll
+        for (int reg = 1; reg < 16; ++reg) { mT = fmaxf(mT, accT[rb][reg]); mD = fmaxf(mD, accD[rb][reg]); }
+        // (the pair of maxima bounds every pair of the lane's 16 columns)
+        if (mix_can_reach(mT, mD, wt, wp, tv)) {
+            // one compare pair per element first (mix_thresholds); the exact test only for the registers in which SOME lane
+            // of the wave still has a column in play (wave-uniform: __ballot)
+            float th_t, th_d;
+            mix_thresholds(mT, mD, wt, wp, tv, th_t, th_d);
+            unsigned pm = 0;
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg)
+                if (accT[rb][reg] >= th_t && accD[rb][reg] >= th_d) pm |= 1u << reg;
+            unsigned m = 0;
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                if (__ballot((pm >> reg) & 1u)) {
+                    const int lc = t * 32 + 4 * hi + (reg & 3) + 8 * (reg >> 2);
+                    if (((pm >> reg) & 1u) && mix_can_reach(accT[rb][reg], accD[rb][reg], wt, wp, tv) && lc < p.n_valid_col)
+                        m |= 1u << reg;
+                }
+            }
+            if (m) {
+                int at = atomicAdd(&lcnt[rb * 32 + j], __popc(m));
+                uint4* dst = p.cand + ((size_t)bir * p.Bpad + rg * R_TILE + rb * 32 + j) * (size_t)p.cap;
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg) {
+                    if (m & (1u << reg))
+                        dst[at++] = make_uint4(__float_as_uint(accT[rb][reg]), __float_as_uint(accD[rb][reg]),
+                                               (unsigned)(t * 32 + 4 * hi + (reg & 3) + 8 * (reg >> 2)), 0u);
+                }
+            }
+        }
+    }
+}
+// sample (MODE 1): the maxima of the lower bounds of y over groups of 4 columns, stored per list item `it`
+template <int RB>
+__device__ __forceinline__ void mix_sample_epilogue(const MixP& p, const f32x16 (&accD)[RB], const f32x16 (&accT)[RB],
+                                                    const float (&wt_r)[RB], const float (&wp_r)[RB], int t, int it, int rg, int hi, int j)
+{
+    constexpr int R_TILE = RB * 32;
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb) {
+        const int row = rg * R_TILE + rb * 32 + j;
+        float o[4];
+#pragma unroll
+        for (int qd = 0; qd < 4; ++qd) {
+            float mx = -__builtin_inff();
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int lc = t * 32 + 4 * hi + e + 8 * qd;
+                const float y = mix_fast_dn(accT[rb][4 * qd + e], accD[rb][4 * qd + e], wt_r[rb], wp_r[rb]);
+                if (lc < p.n_valid_col) mx = fmaxf(mx, y);
+            }
+            o[qd] = mx;
+        }
+        if (row < p.B)
+            *reinterpret_cast<float4*>(p.samp + (size_t)row * p.ld_s + (size_t)it * 8 + 4 * hi) = make_float4(o[0], o[1], o[2], o[3]);
+    }
+}
 
 template <int NSD, int NST, int RB, int QR, int NW, int MODE>
 __global__ __launch_bounds__(NW * 64, 1) void mix_bf16_kernel(const MixP p)
@@ -275,65 +351,186 @@ __global__ __launch_bounds__(NW * 64, 1) void mix_bf16_kernel(const MixP p)
             __builtin_amdgcn_sched_barrier(0);
         }
 
-        // ---- epilogue: lane = playlist j of row block rb; register reg is column 32 t + 4 hi + (reg & 3) + 8 (reg >> 2)
-        if (MODE == 0) {
+        // ---- epilogue
+        if (MODE == 0) mix_filter_epilogue<RB>(p, accD, accT, tau_r, wt_r, wp_r, lcnt, t, rg, bir, hi, j);
+        else mix_sample_epilogue<RB>(p, accD, accT, wt_r, wp_r, t, it, rg, hi, j);
+        t = u; u = __builtin_amdgcn_readfirstlane(wv);
+        it = g_nxt; g_nxt = g_nn;
+    }
+    if (MODE == 0) {
+        __syncthreads();
+        for (int i = tid; i < R_TILE; i += NTH) p.cand_cnt[(size_t)bir * p.Bpad + rg * R_TILE + i] = lcnt[i];
+    }
+}
+
+// ---- the same launch at the other supported shapes (dae_mix_exact_shape_ok): step counts at run time --------------------
+// mix_bf16_kernel is unrolled over its 44 steps; an instance per shape (7 hidden sizes x 8 row lengths x 2 modes) is not an
+// option.  Here a tile is two run-time loops -- the DAE image's steps into accD, then the title image's into accT -- over
+// CHUNKS of 8 steps, unrolled inside the chunk.  The W ring is one chunk: slot i, once step i has been issued, takes step i
+// of the NEXT chunk -- of the same image, of the other image, or of the next tile -- 8 steps ahead as in mix_bf16_kernel,
+// with no assumption on the title image's step count but "at least 4, a multiple of 4" (row lengths are multiples of 64).
+// REQUIRES nsD >= 8 and a multiple of 4 (hidden >= 128, a multiple of 64: dae_mix_exact_shape_ok): the prologue and the refill
+// across the tile boundary load the DAE image's first EIGHT steps of a tile -- with nsD = 4 (hidden 64) they would read past
+// the tile's DAE steps; whoever widens the predicate gives those two places the half-chunk addresses first.  An image of 8 m + 4 steps ends on a HALF chunk: steps 4 .. 7 of it multiply nothing, and their slots are loaded
+// all the same (slots 4 .. 7 of a half chunk repeat the addresses of slots 0 .. 3) -- EVERY chunk issues its 8 loads, so
+// the count of loads in flight is the same on every path and the s_waitcnt vmcnt(n) before a step waits for that step's
+// slot only (a skipped load would make it wait for the youngest one: a ring one step deep).  Everything else -- the bias
+// and bound fragments through the matrix pipe, tile claiming, both epilogues -- is mix_bf16_kernel's.
+template <int RB, int NW, int MODE>
+__global__ __launch_bounds__(NW * 64, 1) void mix_bf16_steps_kernel(const MixP p)
+{
+    constexpr int R_TILE = RB * 32, NTH = NW * 64;
+    extern __shared__ __attribute__((aligned(16))) float4 lds4[];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int hi = lane >> 5;
+    const int j = lane & 31;
+    const int NSD = p.nsD, NST = p.nsT, NS = NSD + NST;
+
+    const int gs = DAE_NUM_XCD * p.n_rg;
+    const int q = blockIdx.x / gs, rem = blockIdx.x % gs;
+    const int rg = rem / DAE_NUM_XCD;
+    const int bir = q * DAE_NUM_XCD + (rem % DAE_NUM_XCD);
+
+    const int n_h4 = RB * 64 * NS;
+    const int n_items = p.n_items;
+    const int n_ws = p.nb_rg * NW;
+    const int it0 = wave * p.nb_rg + bir;
+    const uint4* ldsq = reinterpret_cast<const uint4*>(lds4);
+
+    const bool has = it0 < n_items;
+    const int tv0 = p.list[has ? it0 : 0];
+    const int tv1 = p.list[has ? (it0 + n_ws < n_items ? it0 + n_ws : it0) : 0];
+    static_assert(R_TILE <= NTH, "one thread per row");
+    float tau_g = __builtin_inff();
+    if (MODE == 0) {
+        const int rr = rg * R_TILE + (tid < R_TILE ? tid : 0);
+        const int rc = rr < p.B ? rr : p.B - 1;
+        const float tau = p.tau[rc];
+        const float a_t = p.w_t[rc], a_p = p.w_p[rc];
+        if (tid < R_TILE && rr < p.B) {
+            tau_g = tau > 0.0f ? tau * (1.0f - 0x1p-17f) : 0.0f;
+            if (a_t == 0.0f && a_p == 0.0f) tau_g = __builtin_inff();
+        }
+    }
+    int* lcnt = reinterpret_cast<int*>(lds4 + n_h4);
+    float* ltau = reinterpret_cast<float*>(lcnt + R_TILE);
+    int* claim = reinterpret_cast<int*>(ltau + R_TILE);
+    if (tid == 0) *claim = 2 * NW;
+    {
+        // the row group's hidden rows of both scorers, 4 loads in flight per thread and round.  Loads AND stores on the clamped
+        // index: no branch (hipcc sinks a load into the branch that guards its store and waits for each there); the threads
+        // past the end store the last element a second time
+        const uint4* hsrc = p.hp + (size_t)rg * n_h4;
+        uint4* l4 = reinterpret_cast<uint4*>(lds4);
+        for (int e0 = 0; e0 < n_h4; e0 += 4 * NTH) {
+            uint4 hv[4];
+            int ic[4];
 #pragma unroll
-            for (int rb = 0; rb < RB; ++rb) {
-                const float tv = tau_r[rb], wt = wt_r[rb], wp = wp_r[rb];
-                float mT = accT[rb][0], mD = accD[rb][0];
-#pragma unroll
-                for (int reg = 1; reg < 16; ++reg) { mT = fmaxf(mT, accT[rb][reg]); mD = fmaxf(mD, accD[rb][reg]); }
-                // (the pair of maxima bounds every pair of the lane's 16 columns)
-                if (mix_can_reach(mT, mD, wt, wp, tv)) {
-                    // one compare pair per element first (mix_thresholds); the exact test only for the registers in which SOME lane
-                    // of the wave still has a column in play (wave-uniform: __ballot)
-                    float th_t, th_d;
-                    mix_thresholds(mT, mD, wt, wp, tv, th_t, th_d);
-                    unsigned pm = 0;
-#pragma unroll
-                    for (int reg = 0; reg < 16; ++reg)
-                        if (accT[rb][reg] >= th_t && accD[rb][reg] >= th_d) pm |= 1u << reg;
-                    unsigned m = 0;
-#pragma unroll
-                    for (int reg = 0; reg < 16; ++reg) {
-                        if (__ballot((pm >> reg) & 1u)) {
-                            const int lc = t * 32 + 4 * hi + (reg & 3) + 8 * (reg >> 2);
-                            if (((pm >> reg) & 1u) && mix_can_reach(accT[rb][reg], accD[rb][reg], wt, wp, tv) && lc < p.n_valid_col)
-                                m |= 1u << reg;
-                        }
-                    }
-                    if (m) {
-                        int at = atomicAdd(&lcnt[rb * 32 + j], __popc(m));
-                        uint4* dst = p.cand + ((size_t)bir * p.Bpad + rg * R_TILE + rb * 32 + j) * (size_t)p.cap;
-#pragma unroll
-                        for (int reg = 0; reg < 16; ++reg) {
-                            if (m & (1u << reg))
-                                dst[at++] = make_uint4(__float_as_uint(accT[rb][reg]), __float_as_uint(accD[rb][reg]),
-                                                       (unsigned)(t * 32 + 4 * hi + (reg & 3) + 8 * (reg >> 2)), 0u);
-                        }
-                    }
-                }
+            for (int e = 0; e < 4; ++e) {
+                const int i = e0 + e * NTH + tid;
+                ic[e] = i < n_h4 ? i : n_h4 - 1;
+                hv[e] = hsrc[ic[e]];
             }
-        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) l4[ic[e]] = hv[e];
+        }
+    }
+    if (tid < R_TILE) { lcnt[tid] = 0; ltau[tid] = tau_g; }
+    float wt_r[RB], wp_r[RB];
+    unsigned oy[RB];
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb) {
+        const int row = rg * R_TILE + rb * 32 + j;
+        const bool in = row < p.B;
+        const int rc = in ? row : p.B - 1;
+        const float a_t = p.w_t[rc], a_p = p.w_p[rc];
+        const unsigned fh = p.fhat[rc];
+        wt_r[rb] = in ? a_t : 0.0f;
+        wp_r[rb] = in ? a_p : 0.0f;
+        oy[rb] = hi == 0 ? (0x3F80u | ((in ? fh : 0u) << 16)) : 0u;
+    }
+    int t = __builtin_amdgcn_readfirstlane(tv0), u = __builtin_amdgcn_readfirstlane(tv1);
+    // this lane's uint4 of step sg of an image, tile x; the following steps of the tile at [64], [128], ...
+    auto wD = [&](int x, int sg) -> const uint4* { return p.WqD + ((size_t)x * NSD + sg) * 64 + lane; };
+    auto wT = [&](int x, int sg) -> const uint4* { return p.WqT + ((size_t)x * NST + sg) * 64 + lane; };
+    uint4 wq[8];
+    uint4 cb[2][RB];
+    uint4 bfD = p.biasD[(size_t)t * 64 + lane], bfT = p.biasT[(size_t)t * 64 + lane];
+    {
+        const uint4* a = wD(t, 0);                                // (nsD >= 8)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) wq[i] = a[i * 64];
+    }
+    __syncthreads();
+
+    float tau_r[RB];
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb) tau_r[rb] = ltau[rb * 32 + j];
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb) cb[0][rb] = ldsq[rb * 64 + lane];
+    const uint4 onesD = hi == 0 ? make_uint4(0x3F803F80u, 0x00003F80u, 0u, 0u) : make_uint4(0u, 0u, 0u, 0u);
+
+    int g_nxt = it0 + n_ws;
+    for (int it = it0; it < n_items;) {
+        int g_nn;
+        {
+            int n2 = 0;
+            if (lane == 0) n2 = atomicAdd(claim, 1);
+            g_nn = __builtin_amdgcn_readfirstlane(n2) * p.nb_rg + bir;
+        }
+        const int wv = p.list[g_nn < n_items ? g_nn : it];       // consumed at the end of this tile
+
+        f32x16 accD[RB], accT[RB];
+        {
+            f32x16 zero;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) zero[e] = 0.0f;
+            const uint4 bd = bfD, bt = bfT;
+            bfD = p.biasD[(size_t)u * 64 + lane];
+            bfT = p.biasT[(size_t)u * 64 + lane];
 #pragma unroll
             for (int rb = 0; rb < RB; ++rb) {
-                const int row = rg * R_TILE + rb * 32 + j;
-                float o[4];
-#pragma unroll
-                for (int qd = 0; qd < 4; ++qd) {
-                    float mx = -__builtin_inff();
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int lc = t * 32 + 4 * hi + e + 8 * qd;
-                        const float y = mix_fast_dn(accT[rb][4 * qd + e], accD[rb][4 * qd + e], wt_r[rb], wp_r[rb]);
-                        if (lc < p.n_valid_col) mx = fmaxf(mx, y);
-                    }
-                    o[qd] = mx;
-                }
-                if (row < p.B)
-                    *reinterpret_cast<float4*>(p.samp + (size_t)row * p.ld_s + (size_t)it * 8 + 4 * hi) = make_float4(o[0], o[1], o[2], o[3]);
+                accD[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(bd), as_bf16x8(onesD), zero, 0, 0, 0);
+                const uint4 ot = hi == 0 ? make_uint4(0x3F803F80u, oy[rb], 0u, 0u) : make_uint4(0u, 0u, 0u, 0u);
+                accT[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(bt), as_bf16x8(ot), zero, 0, 0, 0);
             }
         }
+        // a chunk of n (8, or 4: the image's last 4 steps) steps, the first one step s0 of the tile (the order of the rows in
+        // LDS); the ring then holds the chunk at `next`, of n_next steps.  Only the multiplications of steps 4 .. 7 depend on n:
+        // the loads are straight-line code
+        auto chunk = [&](f32x16 (&acc)[RB], int s0, int n, const uint4* next, int n_next) __attribute__((always_inline)) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                if (i < 4 || n == 8) {
+                    const int s = s0 + i;
+                    const uint4* bn = ldsq + (size_t)(s + 1 == NS ? 0 : s + 1) * (RB * 64) + lane;      // the B operands of the step after
+#pragma unroll
+                    for (int rb = 0; rb < RB; ++rb) {
+                        acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(wq[i]), as_bf16x8(cb[i & 1][rb]), acc[rb], 0, 0, 0);
+                        __builtin_amdgcn_sched_barrier(0);
+                        cb[(i + 1) & 1][rb] = bn[rb * 64];
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+                wq[i] = next[(i < 4 || n_next == 8 ? i : i - 4) * 64];
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        };
+        for (int s0 = 0; s0 < NSD; s0 += 8) {                     // the DAE image; after its last chunk: the title image's first
+            const int sn = s0 + 8;
+            const bool more = sn < NSD;
+            chunk(accD, s0, NSD - s0 < 8 ? 4 : 8, more ? wD(t, sn) : wT(t, 0), (more ? NSD - sn : NST) < 8 ? 4 : 8);
+        }
+        for (int s0 = 0; s0 < NST; s0 += 8) {                     // the title image; after its last chunk: the next tile
+            const int sn = s0 + 8;
+            const bool more = sn < NST;
+            chunk(accT, NSD + s0, NST - s0 < 8 ? 4 : 8, more ? wT(t, sn) : wD(u, 0), (more ? NST - sn : NSD) < 8 ? 4 : 8);
+        }
+
+        if (MODE == 0) mix_filter_epilogue<RB>(p, accD, accT, tau_r, wt_r, wp_r, lcnt, t, rg, bir, hi, j);
+        else mix_sample_epilogue<RB>(p, accD, accT, wt_r, wp_r, t, it, rg, hi, j);
         t = u; u = __builtin_amdgcn_readfirstlane(wv);
         it = g_nxt; g_nxt = g_nn;
     }
@@ -1008,6 +1205,14 @@ static int mix_audit(dae_ctx* tc, dae_ctx* dc, const float* feat, int64_t ld_fea
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
+// THE rule for "does this model have an exact title mix" (models/DAEs.py asks it through the ABI): multiples of 64, so that both
+// images are whole chunks of 4 steps (mix_bf16_steps_kernel); hidden 64 is left to the fp32 kernels -- a DAE GEMM of 4 steps
+extern "C" int dae_mix_exact_shape_ok(int hidden, int ld_feat)
+{
+    return hidden >= 128 && hidden <= 16 * MX_MAX_STEPS && hidden % 64 == 0 &&
+           ld_feat >= 64 && ld_feat <= 16 * MX_MAX_STEPS && ld_feat % 64 == 0;
+}
+
 int dae_launch_mix_title_bounds(dae_ctx* ctx, const float* W, const float* b, int H, int Hp, int col_lo, int col_hi,
                                 int ntiles, dae_packed& pk)
 {
@@ -1032,14 +1237,22 @@ int dae_mix_topk_exact_impl(dae_ctx* tc, dae_ctx* dc, const float* feat, int64_t
                             const float* w_title, const float* w_playlist, int n_tracks, const int32_t* seed_row_ptr,
                             const int32_t* seed_col, int k, float* out_score, int32_t* out_idx)
 {
-    constexpr int NSD = 16, NST = 28, RB = MX_RB, NW = MX_NW, QR = MX_QR, NS = NSD + NST, R_TILE = RB * 32;
+    constexpr int NW = MX_NW, QR = MX_QR;
     dae_packed& pt = tc->pk_bf16;
     dae_packed& pd = dc->pk_bf16;
     if (!pt.valid || !pt.exact || !pd.valid || !pd.exact)
         return dae_fail(tc, DAE_ERR_STATE, "both contexts need their weights prepacked with DAE_DTYPE_BF16_EXACT");
-    if (pd.Hp != NSD * 16 || pt.Hp != NST * 16 || pd.H != pd.Hp || (pt.H & 15))
-        return dae_fail(tc, DAE_ERR_ARG, "the exact title mix is built for hidden 256 (DAE) and 448-wide feature rows "
-                        "(got %d and %d): use DAE_DTYPE_F32", pd.H, pt.H);
+    // the shipped shape (hidden 256, rows of 448) keeps its unrolled instance; every other shape of dae_mix_exact_shape_ok runs
+    // mix_bf16_steps_kernel
+    const bool shipped = pd.Hp == 16 * 16 && pt.Hp == 28 * 16 && pd.H == pd.Hp && !(pt.H & 15);
+    if (!shipped && !dae_mix_exact_shape_ok(pd.H, pt.H))
+        return dae_fail(tc, DAE_ERR_ARG, "the exact title mix is built for hidden 256 (DAE) and 448-wide feature rows; it also takes "
+                        "hidden 128..512 and rows of 64..512 in steps of 64 (got %d and %d): use DAE_DTYPE_F32", pd.H, pt.H);
+    const int NSD = pd.Hp / 16, NST = pt.Hp / 16, NS = NSD + NST;
+    // row groups of 96 playlists while their hidden rows (RB x NS KiB) and the kernel's tail fit the CU's 160 KiB of LDS -- up to
+    // 52 steps (hidden 384 + rows of 448) -- and of 64 beyond (at most 128 KiB at hidden 512 + rows of 512)
+    const int RB = shipped || (size_t)MX_RB * 64 * NS * sizeof(uint4) + MX_RB * 32 * 8 + 16 <= MX_LDS_BYTES ? MX_RB : 2;
+    const int R_TILE = RB * 32;
     if (pt.col_lo != 0 || pd.col_lo != 0 || pt.col_hi != pd.col_hi)
         return dae_fail(tc, DAE_ERR_ARG, "both images must hold the same columns, starting at 0");
     if (B <= 0) return DAE_OK;
@@ -1050,7 +1263,7 @@ int dae_mix_topk_exact_impl(dae_ctx* tc, dae_ctx* dc, const float* feat, int64_t
     const int ntr = (n_valid_col + 31) / 32;                      // tiles with rankable columns
     if (ntr <= 0) return dae_fail(tc, DAE_ERR_ARG, "no rankable column");
 
-    // geometry: 96-row groups; the workgroups of a row group in multiples of the XCD count
+    // geometry: row groups of R_TILE playlists; the workgroups of a row group in multiples of the XCD count
     const int n_rg = (B + R_TILE - 1) / R_TILE;
     const int Bpad = n_rg * R_TILE;
     int nb = (DAE_NUM_CU / n_rg) / DAE_NUM_XCD * DAE_NUM_XCD;
@@ -1094,13 +1307,29 @@ int dae_mix_topk_exact_impl(dae_ctx* tc, dae_ctx* dc, const float* feat, int64_t
     p.w_t = w_title; p.w_p = w_playlist;
     p.n_valid_col = n_valid_col;
     p.B = B; p.n_rg = n_rg; p.nb_rg = nb; p.Bpad = Bpad;
+    p.nsD = NSD; p.nsT = NST;
     const size_t lds = (size_t)RB * 64 * NS * sizeof(uint4) + (size_t)R_TILE * 8 + 16;
-    auto kf = mix_bf16_kernel<NSD, NST, RB, QR, NW, 0>;
-    auto ks = mix_bf16_kernel<NSD, NST, RB, QR, NW, 1>;
-    static const char attr_key = 0;
-    if (dae_first_use(tc, &attr_key)) {
-        DAE_HIP_CHECK(tc, hipFuncSetAttribute(reinterpret_cast<const void*>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        DAE_HIP_CHECK(tc, hipFuncSetAttribute(reinterpret_cast<const void*>(ks), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    void (*kf)(MixP);
+    void (*ks)(MixP);
+    if (shipped) {
+        kf = mix_bf16_kernel<16, 28, MX_RB, QR, NW, 0>;
+        ks = mix_bf16_kernel<16, 28, MX_RB, QR, NW, 1>;
+        static const char attr_key = 0;
+        if (dae_first_use(tc, &attr_key)) {
+            DAE_HIP_CHECK(tc, hipFuncSetAttribute(reinterpret_cast<const void*>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            DAE_HIP_CHECK(tc, hipFuncSetAttribute(reinterpret_cast<const void*>(ks), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        }
+    } else {
+        // one instance per row-group height and mode; its LDS limit is raised once, to the largest row group it can be given
+        static const char attr3_key = 0, attr2_key = 0;
+        if (RB == MX_RB) { kf = mix_bf16_steps_kernel<MX_RB, NW, 0>; ks = mix_bf16_steps_kernel<MX_RB, NW, 1>; }
+        else { kf = mix_bf16_steps_kernel<2, NW, 0>; ks = mix_bf16_steps_kernel<2, NW, 1>; }
+        // (RB = 3 was chosen because its row group fits MX_LDS_BYTES; RB = 2 holds at most 2 x 64 steps: 128 KiB)
+        const size_t lds_max = RB == MX_RB ? MX_LDS_BYTES : (size_t)2 * 64 * (2 * MX_MAX_STEPS) * sizeof(uint4) + 2 * 32 * 8 + 16;
+        if (dae_first_use(tc, RB == MX_RB ? &attr3_key : &attr2_key)) {
+            DAE_HIP_CHECK(tc, hipFuncSetAttribute(reinterpret_cast<const void*>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+            DAE_HIP_CHECK(tc, hipFuncSetAttribute(reinterpret_cast<const void*>(ks), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+        }
     }
 
     // ---- sample: lower bounds over the head of the list -> tau
@@ -1124,7 +1353,7 @@ int dae_mix_topk_exact_impl(dae_ctx* tc, dae_ctx* dc, const float* feat, int64_t
         ps.nb_rg = nb_s;
         hipLaunchKernelGGL(ks, dim3(n_rg * nb_s), dim3(NW * 64), lds, st, ps);
     }
-    DAE_CHECK_LAUNCH(tc, "mix_bf16_kernel<sample>");
+    DAE_CHECK_LAUNCH(tc, shipped ? "mix_bf16_kernel<sample>" : "mix_bf16_steps_kernel<sample>");
     rc = dae_reserve(tc, tc->sample_top, (size_t)Bpad * (sizeof(uint2) + sizeof(int))); if (rc) return rc;
     rc = dae_launch_tau_select(tc, p.samp, ld_s, (int)ld_s, p.samp, 0, 0, order, 0, B, k, seed_row_ptr,
                                static_cast<float*>(tc->tau.p), static_cast<uint2*>(tc->sample_top.p), 1,
@@ -1140,8 +1369,9 @@ int dae_mix_topk_exact_impl(dae_ctx* tc, dae_ctx* dc, const float* feat, int64_t
     p.tau = static_cast<const float*>(tc->tau.p);
     p.cand = static_cast<uint4*>(tc->cand.p); p.cand_cnt = static_cast<int*>(tc->cand_cnt.p); p.cap = cap;
     p.samp = nullptr; p.ld_s = 0;
+    dae_note_plan(R_TILE, n_rg, nb, n_samp, ntr, pt.ntiles);
     hipLaunchKernelGGL(kf, dim3(grid), dim3(NW * 64), lds, st, p);
-    DAE_CHECK_LAUNCH(tc, "mix_bf16_kernel<filter>");
+    DAE_CHECK_LAUNCH(tc, shipped ? "mix_bf16_kernel<filter>" : "mix_bf16_steps_kernel<filter>");
 
     // ---- refine + selection
     if (!tc->guard.p) {

@@ -32,21 +32,22 @@ _DECODE_DTYPES = {"f32": _lib.DAE_DTYPE_F32, "bf16": _lib.DAE_DTYPE_BF16, "exact
 
 def _title_dtype(dtype, model):
     """Arithmetic of a title-mixed launch.  exact_bf16 has its own two-GEMM path (dae_mix_topk_exact, csrc/mixexact.hip)
-    built for the shipped shapes -- DAE hidden 256, title feature rows of 448; any other model runs its titled launches
-    on the fp32 kernels (the lists exact_bf16 promises are the fp32 lists either way)."""
+    for the shapes the library says it takes (dae_mix_exact_shape_ok: DAE hidden 128 .. 512, title feature rows of 64 .. 512,
+    both in steps of 64); any other model runs its titled launches on the fp32 kernels (the lists exact_bf16 promises are
+    the fp32 lists either way)."""
     if dtype != _lib.DAE_DTYPE_BF16_EXACT:
         return dtype
     tm = model.title_model
-    if tm is not None and model.n_hidden == 256 and tm.ld == 448 and not model.title_exact_off:
+    if tm is not None and not model.title_exact_off and _lib.mix_exact_shape_ok(model.n_hidden, tm.ld):
         return dtype
     if tm is not None and not model.title_exact_off and not model._title_fp32_said:
         # [DAE] hidden, [TITLE] filter_num / filter_size are free keys of the schema (main.py:46, :73-75): say ONCE that this
-        # model's titled launches cost the fp32 kernels' time (about 6 x), instead of silently
+        # model's titled launches cost the fp32 kernels' time, instead of silently
         model._title_fp32_said = True
         import sys
-        print("[dae] decode_dtype = exact_bf16: the exact title mix is built for hidden = 256 and 448-wide title feature rows; "
-              "this model has hidden = %d, %d-wide rows -- its titled launches run on the fp32 kernels (same lists, slower)"
-              % (model.n_hidden, tm.ld), file=sys.stderr)
+        print("[dae] decode_dtype = exact_bf16: the exact title mix takes hidden = 128 .. 512 and title feature rows of 64 .. 512, "
+              "both in steps of 64; this model has hidden = %d, %d-wide rows -- its titled launches run on the fp32 kernels "
+              "(same lists, slower)" % (model.n_hidden, tm.ld), file=sys.stderr)
     return _lib.DAE_DTYPE_F32
 
 
