@@ -94,8 +94,10 @@ int dae_clock_probe(dae_ctx* ctx, void* hip_stream, int window_us, uint64_t* out
 
 /* Geometry of the last dae_decode_topk or dae_mix_topk_exact issued from the calling thread, for roofline accounting:
  * {R_TILE, n_row_groups, blocks_per_row_group, sample_stride S, n_sample_tiles (phase A),
- *  n_filter_tiles (phase B), fused(0/1), n_tiles}.  A tile is 32 vocabulary columns.  (dae_mix_topk_exact: S = 1,
- * fused = 0; its filter launch gives every workgroup of blocks_per_row_group 8 waves that claim tiles.) */
+ *  n_filter_tiles (phase B), fused(0/1), n_tiles}.  A tile is 32 vocabulary columns.  n_tiles counts the tiles the call
+ * WALKS: those of the image that hold a ranked column, ceil((min(n_tracks, col_hi) - col_lo) / 32) -- not the image's
+ * (0 when n_tracks <= col_lo: no launch).  (dae_mix_topk_exact: S = 1, fused = 0; its filter launch gives every workgroup of
+ * blocks_per_row_group 8 waves that claim tiles.) */
 int dae_last_plan(int32_t out[8]);
 
 /* ---- input: COO -> CSR (DAEs.py:33-38 SparseTensor + sparse_tensor_to_dense) --------------- */
@@ -239,7 +241,11 @@ int dae_decode_dense(dae_ctx* ctx, const float* h, int B, int H, int dtype,
  * (seed_row_ptr[B+1], seed_col sorted ascending & unique per row; may be NULL = no seeds).
  * Order: logit descending, then column index ascending.  Writes k entries per row:
  * out_idx[r, i] = GLOBAL column id (or -1 when fewer than k candidates exist, as the reference's
- * cand[:500] of a short list), out_score per `out_kind`.  1 <= k <= 1024. */
+ * cand[:500] of a short list), out_score per `out_kind`.  1 <= k <= 1024.
+ * The ranked columns are a prefix of the image, and the call decodes the 32-column tiles that hold one and no other: the
+ * columns behind them (the artist columns of the reference's vocabulary, which its graph computes before slicing them away,
+ * main_challenge.py:87) can return nothing and are not read.  dae_decode_dense is the call that needs their logits.  An image
+ * with no ranked column (n_tracks <= col_lo) launches no GEMM: every slot is (-1, -inf). */
 int dae_decode_topk(dae_ctx* ctx, const float* h, int B, int H, int dtype,
                     int n_tracks,
                     const int32_t* seed_row_ptr, const int32_t* seed_col,
@@ -249,7 +255,8 @@ int dae_decode_topk(dae_ctx* ctx, const float* h, int B, int H, int dtype,
 /* The whole scoring path in one call: dae_encode (inference keep-probs) -> dae_decode_topk,
  * with the hidden activations kept inside the ctx in the decode kernels' operand order (no
  * [B,H] round trip, no re-pack pass).  Results are identical to calling the two separately.
- * This is what main_challenge.py:80-90 / main_train.py:66-89 do per batch. */
+ * This is what main_challenge.py:80-90 / main_train.py:66-89 do per batch.  As dae_decode_topk, it decodes the tiles with a
+ * ranked column only. */
 int dae_score_topk(dae_ctx* ctx,
                    const int32_t* row_ptr, const int32_t* col, const float* val,
                    const float* W_enc, const float* b_enc, int V, int H, int B, int dtype,
@@ -260,10 +267,11 @@ int dae_score_topk(dae_ctx* ctx,
 
 /* dae_score_topk in two halves, for vocabulary-sharded scoring with a THRESHOLD EXCHANGE between them:
  *   begin:  encode + the threshold sample of this image's columns -> tau_out[B] (device): per row a valid lower bound
- *           of the k-th largest rankable non-seed logit among THIS image's columns (-inf when the image is small enough
- *           to be ranked densely).  The k-th largest logit over ALL shards is at least every shard's bound, so the
- *           element-wise MAXIMUM of the shards' tau_out (one all-gather of 4 B per row and rank) is a valid -- and far
- *           tighter -- threshold for every shard.
+ *           of the k-th largest rankable non-seed logit among THIS image's columns (-inf when the ranked part of the image
+ *           is small enough to be ranked densely, or empty).  The sample is drawn from the tiles with a ranked column, which
+ *           are also all the filter launch of `finish` walks: the artist slice of a shard image is not read.  The k-th
+ *           largest logit over ALL shards is at least every shard's bound, so the element-wise MAXIMUM of the shards'
+ *           tau_out (one all-gather of 4 B per row and rank) is a valid -- and far tighter -- threshold for every shard.
  *   finish: the filter launch with `tau` (tau_out, or that maximum), the selection: out_score / out_idx hold the image's
  *           columns with logit >= tau in rank order, at most k, padded with (-inf, -1): merged over the shards
  *           (dae_topk_merge) they give exactly what the unsharded call returns.

@@ -446,6 +446,9 @@ class Context:
         return khz.value
 
     def last_plan(self):
+        """Geometry of the last decode_topk / score_topk* / mix_topk_exact on this thread (dae_last_plan).  n_tiles: the 32-column
+        tiles the call WALKED -- those with a ranked column, ceil((min(n_tracks, col_hi) - col_lo) / 32), not the image's; a
+        fused fp32 call splits them into n_sample_tiles + n_filter_tiles, a bf16 filter launch walks all of them again."""
         arr = (ctypes.c_int32 * 8)()
         self.lib.dae_last_plan(arr)
         keys = ["R_TILE", "n_rg", "nb_rg", "S", "n_sample_tiles", "n_filter_tiles", "fused",

@@ -111,7 +111,7 @@ const dae_packed* packed_for(dae_ctx* ctx, int dtype, int H)
 
 }  // namespace
 
-// dae_mix_topk_exact leaves its geometry in the same words (mixexact.hip): S = 1, fused = 0
+// dae_mix_topk_exact leaves its geometry in the same words (mixexact.hip): S = 1, fused = 0; ntiles = the ranked tiles it walks
 void dae_note_plan(int R_TILE, int n_rg, int nb_rg, int n_samp, int n_filter, int ntiles)
 {
     g_plan = Plan{R_TILE, n_rg, nb_rg, 1, n_samp, n_filter, 0, ntiles};
@@ -212,6 +212,13 @@ __global__ __launch_bounds__(256) void fill_f32_kernel(float* dst, int n, float 
     if (i < n) dst[i] = v;
 }
 
+// what the selection kernels leave in the slots of a list with no entry: score -inf, index -1
+__global__ __launch_bounds__(256) void fill_pad_kernel(float* score, int32_t* idx, int n)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) { score[i] = -__builtin_inff(); idx[i] = -1; }
+}
+
 __global__ __launch_bounds__(64) void clock_probe_kernel(unsigned long long* out, unsigned long long ticks)
 {
     if (threadIdx.x != 0) return;
@@ -244,7 +251,8 @@ int dae_clock_probe(dae_ctx* ctx, void* hip_stream, int window_us, uint64_t* out
 }
 
 /* geometry of the last dae_decode_topk / dae_mix_topk_exact on this thread:
- * {R_TILE, n_rg, nb_rg, S, n_sample_tiles, n_filter_tiles, fused(0/1), ntiles} */
+ * {R_TILE, n_rg, nb_rg, S, n_sample_tiles, n_filter_tiles, fused(0/1), ntiles}; ntiles = the tiles the call walks, i.e. those
+ * with a ranked column (topk_phase_a), not the image's */
 int dae_last_plan(int32_t out[8])
 {
     if (!out) return DAE_ERR_ARG;
@@ -469,10 +477,13 @@ static int topk_phase_a(dae_ctx* ctx, const dae_packed* pk, const dae_rowgeom& g
     tk.valid = false;
     const bool exact = dtype_in == DAE_DTYPE_BF16_EXACT;
     const int dtype = exact ? DAE_DTYPE_BF16 : dtype_in;          // the arithmetic of the GEMM launches
-    const int ntiles = pk->ntiles;
     const int n_valid_col = n_tracks < pk->col_hi ? n_tracks : pk->col_hi;       // global bound
     int nrank = n_valid_col - pk->col_lo;                                         // ranked columns
     if (nrank < 0) nrank = 0;
+    // the ranked columns are a prefix of the image: a ranking call walks the tiles that hold one and no other (the tiles behind
+    // them -- the artist columns of the shipped vocabulary -- can return nothing; only dae_decode_dense needs their logits).
+    // Offsets laid out by the image (eps_max behind pk->ntiles * 32 bounds) keep pk->ntiles.
+    const int ntiles = (nrank + 31) / 32;
 
     // ---- plan: how many tiles form the threshold sample (phase A) ---------------------------------
     // phase A decodes one tile per SIMD of the row group's workgroups (a full, short round on the
@@ -481,6 +492,15 @@ static int topk_phase_a(dae_ctx* ctx, const dae_packed* pk, const dae_rowgeom& g
     int rounds = (int)(((double)ntiles / 8.0) / n_simd + 0.5);
     if (rounds < 1) rounds = 1;
     int S = (ntiles + rounds * n_simd - 1) / (rounds * n_simd);
+    // WHICH shapes take the threshold path stays what it was when the calls walked the whole image: an image of more tiles than a
+    // round of SIMD slots is scored through sample + filter (callers and tests count on `fused` for such shapes).  Where its ranked
+    // tiles alone fit one round, the sample is every second one of them: the same decode work as the dense launch, and a
+    // selection over the survivors instead of over every ranked column.
+    if (S < 2 && ntiles >= 2) {
+        int rounds_img = (int)(((double)pk->ntiles / 8.0) / n_simd + 0.5);
+        if (rounds_img < 1) rounds_img = 1;
+        if ((pk->ntiles + rounds_img * n_simd - 1) / (rounds_img * n_simd) >= 2) S = 2;
+    }
     // exact mode: the same launches whatever the size (a small problem's "sample" is every tile: S = 1)
     if (exact && S < 2) S = 1;
     const bool fused = (S >= 2 || exact) && nrank > 0;
@@ -497,6 +517,19 @@ static int topk_phase_a(dae_ctx* ctx, const dae_packed* pk, const dae_rowgeom& g
     // Same sample tiles, same logits; the groups (the tiles one wave decodes, n_ws places apart in the bias order) change, i.e.
     // only how tight tau is.  Only where that kernel applies (bf16 image of hidden 256, 128-row groups, no title mix).
     const bool mixed = ctx->mixT != nullptr;               // dae_set_score_mix: the launches rank the MIXED score
+    if (mixed && exact) return dae_fail(ctx, DAE_ERR_ARG, "DAE_DTYPE_BF16_EXACT is not available with dae_set_score_mix");
+    if (ntiles == 0) {
+        // no ranked column in this image (n_tracks <= col_lo): no GEMM launch; tau = -inf, and phase B pads every slot
+        tk.pk = pk; tk.g = g; tk.B = B; tk.k = k; tk.dtype = dtype; tk.exact = exact; tk.fused = false; tk.mixed = mixed;
+        tk.whole_b = false; tk.S = 1; tk.n_samp = 0; tk.n_other = 0; tk.n_valid_col = n_valid_col; tk.nrank = 0;
+        tk.n_rank_tiles = 0; tk.ld_s = 0; tk.order = nullptr; tk.sample_cnt = nullptr;
+        if (tau_dst) {
+            hipLaunchKernelGGL(fill_f32_kernel, dim3((B + 255) / 256), dim3(256), 0, ctx->stream, tau_dst, B, -__builtin_inff());
+            DAE_CHECK_LAUNCH(ctx, "fill_f32_kernel");
+        }
+        tk.valid = true;
+        return DAE_OK;
+    }
     // does a launch of geometry gg take per-WAVE groups?  (the one predicate behind `wave_groups` below)
     auto takes_wave_groups = [&](const dae_rowgeom& gg) {
         const int n_ws = gg.nb_rg * gg.waves;
@@ -559,7 +592,6 @@ static int topk_phase_a(dae_ctx* ctx, const dae_packed* pk, const dae_rowgeom& g
     // large batches -- keep one value per wave slot and position, i.e. every sample element
     int gmax_per_wave = ld_g < 4 * (int64_t)k ? 1 : 0;
     if (gmax_per_wave) ld_g *= gA.waves;
-    if (mixed && exact) return dae_fail(ctx, DAE_ERR_ARG, "DAE_DTYPE_BF16_EXACT is not available with dae_set_score_mix");
     // the groups are the tiles ONE wave of the filter kernel's shape decodes (decode_bf16_h256_wavemax_kernel: no exchange
     // through LDS, two waves per SIMD) -- 8 nb_rg x 32 maxima per row
     const bool wave_groups = takes_wave_groups(gA);        // (== !gmax_per_wave && ...: the same `enough`)
@@ -594,7 +626,7 @@ static int topk_phase_a(dae_ctx* ctx, const dae_packed* pk, const dae_rowgeom& g
 
     tk.pk = pk; tk.g = g; tk.B = B; tk.k = k; tk.dtype = dtype; tk.exact = exact; tk.fused = fused; tk.mixed = mixed;
     tk.whole_b = whole_b; tk.S = S; tk.n_samp = n_samp; tk.n_other = n_other; tk.n_valid_col = n_valid_col; tk.nrank = nrank;
-    tk.ld_s = ld_s; tk.order = order; tk.sample_cnt = nullptr;
+    tk.n_rank_tiles = ntiles; tk.ld_s = ld_s; tk.order = order; tk.sample_cnt = nullptr;
     if (!fused) {                                          // phase B ranks the dense rows; no threshold exists
         if (tau_dst) {
             // (-inf: 0xFF800000 is not a byte pattern hipMemset can write)
@@ -648,13 +680,19 @@ static int topk_phase_b(dae_ctx* ctx, const float* tau_src, const int32_t* seed_
     // per SIMD lane and 94 KB of LDS on every CU -- the 256-thread selection fits there and runs UNDER the other batch's
     // launch (alone it is slower: 14 vs 11 us); the fp32 launches fill the LDS, nothing fits next to them
     ta.prefer_small = (ctx->overlap_hint && dtype == DAE_DTYPE_BF16) ? 1 : 0;
+    if (tk.n_rank_tiles == 0) {                            // nothing to rank: the padding of a short list in every slot
+        const int n = B * k;                               // (B <= DAE_ROW_SLAB, k <= DAE_MAX_K)
+        hipLaunchKernelGGL(fill_pad_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, out_score, out_idx, n);
+        DAE_CHECK_LAUNCH(ctx, "fill_pad_kernel");
+        return DAE_OK;
+    }
     if (!tk.fused) {
         dae_dense_src ds{static_cast<const float*>(ctx->sample.p), tk.ld_s, (int)tk.ld_s, pk->col_lo, 1, nullptr};
         return dae_launch_topk_dense(ctx, ds, ta);
     }
 
     // phase B: everything else through the threshold filter
-    const int n_filter = tk.whole_b ? pk->ntiles : tk.n_other;
+    const int n_filter = tk.whole_b ? tk.n_rank_tiles : tk.n_other;
     const int cap = dae_filter_block_tiles(g, n_filter, dtype, pk->Hp, tk.mixed) * 32;    // worst case: everything passes
     rc = dae_reserve(ctx, ctx->cand, (size_t)g.nb_rg * g.Bpad * cap * sizeof(uint2));
     if (rc) return rc;

@@ -43,7 +43,7 @@ struct dae_packed {            // one prepacked decoder image
     // tiles ordered by the largest bias among their rankable columns, descending (the threshold
     // sample of the fused path takes the head of this list); rebuilt when the image or the number
     // of rankable columns changes
-    dae_buf order;             // [ntiles] int32
+    dae_buf order;             // [ceil(order_nrank / 32)] int32: the tiles with a rankable column only
     dae_buf ident;             // [ntiles] int32: 0, 1, 2, ... (the tile list of "all tiles")
     int order_nrank = -1;      // rankable columns the order was built for (-1: none)
     int order_nsamp = -1;
@@ -76,6 +76,7 @@ struct dae_topk_state {     // what the second half of a fused scoring call need
     const dae_packed* pk = nullptr;
     dae_rowgeom g{};
     int B = 0, k = 0, dtype = 0, S = 0, n_samp = 0, n_other = 0, n_valid_col = 0, nrank = 0;
+    int n_rank_tiles = 0;   // ceil(nrank / 32): the tiles the call walks (a prefix of the image's); 0 = nothing to rank
     bool exact = false, fused = false, mixed = false, whole_b = false;
     int64_t ld_s = 0;
     const int* order = nullptr;
@@ -280,6 +281,7 @@ int dae_launch_pack_h_bf16(dae_ctx* ctx, const float* h, int B, int H, const dae
 int dae_launch_tile_iota(dae_ctx* ctx, int* dst, int ntiles);      // dst[i] = i
 // (re)build pk.order for `nrank` rankable columns; the first n_samp entries are the threshold sample
 int dae_launch_tile_order(dae_ctx* ctx, dae_packed& pk, int nrank, int n_samp, int S);
+bool dae_tile_order_sorted(int n_rank_tiles);    // the bias sort (true) or the strided list, by the number of ranked tiles
 // band[0 .. n_samp): the sample of `order` dealt to the phase-A launch's slots so that the tiles ONE workgroup decodes in a round
 // (item = round * nb_rg * waves + wave * nb_rg + bir) come from `waves` different popularity bands; band[n_samp ..) = order
 int dae_launch_tile_band(dae_ctx* ctx, const int* order, int ntiles, int n_samp, int nb_rg, int waves, int* band);

@@ -1277,7 +1277,7 @@ int dae_mix_topk_exact_impl(dae_ctx* tc, dae_ctx* dc, const float* feat, int64_t
     if (n_samp < 256) n_samp = 256;
     if (n_samp > ntr) n_samp = ntr;
     if (dc->stream != st) return dae_fail(tc, DAE_ERR_STATE, "both contexts must be bound to the same stream");
-    if (!(pd.order.p && pd.order_nrank == n_valid_col && pd.ntiles <= 8192)) {      // (the bias order does not depend on the sample size)
+    if (!(pd.order.p && pd.order_nrank == n_valid_col && dae_tile_order_sorted(ntr))) {      // (the bias order does not depend on the sample size)
         rc = dae_launch_tile_order(dc, pd, n_valid_col, n_samp, 1);
         if (rc) return dae_fail(tc, rc, "%s", dc->err.c_str());
     }
@@ -1369,7 +1369,7 @@ int dae_mix_topk_exact_impl(dae_ctx* tc, dae_ctx* dc, const float* feat, int64_t
     p.tau = static_cast<const float*>(tc->tau.p);
     p.cand = static_cast<uint4*>(tc->cand.p); p.cand_cnt = static_cast<int*>(tc->cand_cnt.p); p.cap = cap;
     p.samp = nullptr; p.ld_s = 0;
-    dae_note_plan(R_TILE, n_rg, nb, n_samp, ntr, pt.ntiles);
+    dae_note_plan(R_TILE, n_rg, nb, n_samp, ntr, ntr);
     hipLaunchKernelGGL(kf, dim3(grid), dim3(NW * 64), lds, st, p);
     DAE_CHECK_LAUNCH(tc, shipped ? "mix_bf16_kernel<filter>" : "mix_bf16_steps_kernel<filter>");
 

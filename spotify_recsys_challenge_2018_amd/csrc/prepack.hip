@@ -242,7 +242,7 @@ __global__ __launch_bounds__(256) void tile_band_kernel(const int* __restrict__ 
     }
 }
 
-// fallback for images of more than ORDER_MAX_TILES tiles: every S-th tile first, then the others
+// fallback for more than ORDER_MAX_TILES ranked tiles: every S-th tile first, then the others (n_samp = ceil(ntiles / S))
 __global__ __launch_bounds__(256) void tile_order_strided_kernel(int ntiles, int n_samp, int S,
                                                                  int* __restrict__ order)
 {
@@ -430,14 +430,20 @@ int dae_launch_tile_iota(dae_ctx* ctx, int* dst, int ntiles)
 int dae_launch_tile_order(dae_ctx* ctx, dae_packed& pk, int nrank, int n_samp, int S)
 {
     if (pk.order_nrank == nrank && pk.order_nsamp == n_samp && pk.order.p) return DAE_OK;
-    int rc = dae_reserve(ctx, pk.order, (size_t)pk.ntiles * sizeof(int));
+    // the list holds the tiles with a rankable column -- a prefix of the image's -- and its length picks the kernel: a wide
+    // image whose ranked part fits the sort still gets the bias order
+    int n_rt = (nrank + 31) / 32;
+    if (n_rt > pk.ntiles) n_rt = pk.ntiles;
+    int rc = dae_reserve(ctx, pk.order, (size_t)(n_rt > 0 ? n_rt : 1) * sizeof(int));
     if (rc) return rc;
-    if (pk.ntiles > ORDER_MAX_TILES) {
-        hipLaunchKernelGGL(tile_order_strided_kernel, dim3((pk.ntiles + 255) / 256), dim3(256), 0, ctx->stream,
-                           pk.ntiles, n_samp, S, static_cast<int*>(pk.order.p));
+    if (n_rt <= 0) {
+        // (no list to build)
+    } else if (!dae_tile_order_sorted(n_rt)) {
+        hipLaunchKernelGGL(tile_order_strided_kernel, dim3((n_rt + 255) / 256), dim3(256), 0, ctx->stream,
+                           n_rt, n_samp, S, static_cast<int*>(pk.order.p));
     } else {
         hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(1024), 0, ctx->stream,
-                           static_cast<const float*>(pk.bias.p), pk.ntiles, nrank, static_cast<int*>(pk.order.p));
+                           static_cast<const float*>(pk.bias.p), n_rt, nrank, static_cast<int*>(pk.order.p));
     }
     DAE_CHECK_LAUNCH(ctx, "tile_order_kernel");
     pk.order_nrank = nrank; pk.order_nsamp = n_samp;
@@ -445,6 +451,9 @@ int dae_launch_tile_order(dae_ctx* ctx, dae_packed& pk, int nrank, int n_samp, i
     pk.order_gen = ++gen;
     return DAE_OK;
 }
+
+// does a list of n_rank_tiles take the bias sort (whose order does not depend on the sample size)?
+bool dae_tile_order_sorted(int n_rank_tiles) { return n_rank_tiles <= ORDER_MAX_TILES; }
 
 int dae_launch_tile_band(dae_ctx* ctx, const int* order, int ntiles, int n_samp, int nb_rg, int waves, int* band)
 {

@@ -31,11 +31,12 @@ def all_shard_bounds(n_cols, world, align=TILE):
 
 
 def scoring_shard(n_tracks, n_input, world, rank):
-    """The columns rank `rank` of a vocabulary-sharded SCORING job decodes: an equal, tile-aligned slice of the TRACK
-    columns (the only ones that are ranked, main_challenge.py:87) and an equal slice of the artist columns (decoded
-    because the reference decodes every column, DAEs.py:143; never ranked) -> ((t_lo, t_hi), (a_lo, a_hi)).
-    Splitting [0, n_input) as one range (round 2) left the last ranks with artist columns only: same GEMM work, but
-    empty candidate lists there and all of the selection work on the first ranks."""
+    """The columns rank `rank` of a vocabulary-sharded SCORING job holds: an equal, tile-aligned slice of the TRACK
+    columns (the only ones that are ranked, main_challenge.py:87) and an equal slice of the artist columns (the
+    reference decodes every column, DAEs.py:143; here only the dense fetch does -- a scoring call walks the tiles
+    with a ranked column and never reads the artist slice) -> ((t_lo, t_hi), (a_lo, a_hi)).
+    Splitting [0, n_input) as one range (round 2) left the last ranks with artist columns only: empty candidate
+    lists there and all of the decode and selection work on the first ranks."""
     t_lo, t_hi = shard_bounds(n_tracks, world, rank)
     a_lo, a_hi = shard_bounds(n_input - n_tracks, world, rank)
     return (t_lo, t_hi), (n_tracks + a_lo, n_tracks + a_hi)
@@ -46,7 +47,10 @@ def prepack_scoring_shard(ctx, W_dec, b_dec, shard, dtype=0):
     copy [track rows | artist rows] of its part of the decoder (a shard owner holds 1/G of the matrix).  The image's
     global columns are [t_lo, t_lo + n): the track part under its real ids, the artist part under ids that are never
     emitted because the rank bound the scoring calls pass is t_hi (the returned value: use it as `n_tracks` in
-    dae_score_topk / HipRankStages).  Seed lists and results stay in GLOBAL track ids.  Returns (rank_bound, keepalive)."""
+    dae_score_topk / HipRankStages).  The scoring calls decode the tiles below that bound only, so the artist part
+    of the image is not read by them (dae_decode_dense on the context still returns it); leaving it out of a scoring
+    shard's image altogether is a follow-up.  Seed lists and results stay in GLOBAL track ids.
+    Returns (rank_bound, keepalive)."""
     import torch
     (t_lo, t_hi), (a_lo, a_hi) = shard
     W_loc = torch.cat([W_dec[t_lo:t_hi], W_dec[a_lo:a_hi]]).contiguous()
