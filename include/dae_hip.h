@@ -195,6 +195,26 @@ int dae_exact_guard_snapshot(dae_ctx* ctx, int32_t* words_out_dev);
  * recomputed in fp32 after the narrowing step (sum)}.  Synchronises the ctx stream. */
 int dae_exact_stats_read(dae_ctx* ctx, uint64_t out3[3]);
 
+/* ---- skipped filter tiles (DAE_DTYPE_F32, hidden 225..256, batches that score in 128-row groups, no dae_set_score_mix) ----
+ * dae_prepack_decoder(DAE_DTYPE_F32) keeps two floats per 32-column tile t of the image, A_t and M_t, with
+ *   fp32 logit(r, c) <= A_t + d * M_t   for every column c of the tile and every hidden row r with |h[r][k] - 0.5| <= d, all k
+ * (the rounding of the canonical chain is inside).  A ranking call knows each row's threshold tau before
+ * its filter launch: per row group it takes d over the group's rows and tau_rg = the smallest of their thresholds, and the
+ * filter launch walks only the tiles with !(A_t + d M_t < tau_rg).  A tile left out holds no logit the launch would have kept:
+ * lists and scores are bit for bit those of the full walk.  The bounds belong to the image and travel with dae_share_decoder.
+ *   dae_set_filter_skip : on (default) / off = the launch over every planned filter tile.
+ *   dae_filter_skip_read: out3 = {filter launches that built live lists, planned filter tiles x row groups (sum), tiles they
+ *                         walked (sum)} since the last read; resets the counters; synchronises the ctx stream.  dae_last_plan
+ *                         keeps reporting the PLANNED tiles: the work really done is this.
+ *   dae_filter_skip_last: the live tiles per row group of the context's last ranking call (live_out[0 .. min(cap, n_rg)), host);
+ *                         *n_rg_out = 0 when that call's filter launch built no live lists.  Synchronises.
+ *   dae_tile_bounds_read: the fp32 image's {A_t, M_t} pairs to ub_out (HOST, 2 floats per tile, at most cap_tiles tiles);
+ *                         *ntiles_out = tiles of the image.  Synchronises. */
+int dae_set_filter_skip(dae_ctx* ctx, int on);
+int dae_filter_skip_read(dae_ctx* ctx, uint64_t out3[3]);
+int dae_filter_skip_last(dae_ctx* ctx, int32_t* live_out, int cap, int* n_rg_out);
+int dae_tile_bounds_read(dae_ctx* ctx, float* ub_out, int cap_tiles, int* ntiles_out);
+
 /* Factor on every eps_c computed by the NEXT dae_prepack_decoder(DAE_DTYPE_BF16_EXACT) of this context (default 1).
  * > 1 widens the bounds: a safety margin for a caller who distrusts the error model (more survivors to recompute, same
  * results).  < 1 VOIDS the guarantee and exists so that the guard can be exercised: results may then differ from the

@@ -16,7 +16,8 @@ EXPORTS = [
     "dae_version", "dae_create", "dae_destroy", "dae_set_stream", "dae_last_error",
     "dae_scratch_bytes", "dae_profile_enable", "dae_profile_read", "dae_profile_kernel", "dae_clock_probe", "dae_last_plan",
     "dae_coo_to_csr", "dae_seeds_from_csr", "dae_encode", "dae_prepack_decoder", "dae_prepack_decoder_rows", "dae_share_decoder", "dae_exact_bounds",
-    "dae_exact_guard_read", "dae_exact_guard_words", "dae_exact_guard_snapshot", "dae_exact_stats_read", "dae_set_exact_margin", "dae_set_exact_margin_range", "dae_set_exact_audit", "dae_exact_audit_read", "dae_decode_dense", "dae_decode_topk",
+    "dae_exact_guard_read", "dae_exact_guard_words", "dae_exact_guard_snapshot", "dae_exact_stats_read", "dae_set_exact_margin", "dae_set_exact_margin_range", "dae_set_exact_audit", "dae_exact_audit_read",
+    "dae_set_filter_skip", "dae_filter_skip_read", "dae_filter_skip_last", "dae_tile_bounds_read", "dae_decode_dense", "dae_decode_topk",
     "dae_score_topk", "dae_score_topk_begin", "dae_score_topk_finish", "dae_topk_dense", "dae_topk_merge", "dae_set_train_dtype", "dae_train_forward_backward",
     "dae_train_shard_encode", "dae_train_shard_decode", "dae_train_shard_finish", "dae_title_features", "dae_title_prepack_features",
     "dae_mix_scores", "dae_decode_mix_term", "dae_set_score_mix", "dae_mix_topk_exact", "dae_mix_exact_shape_ok", "dae_title_score_exact", "dae_title_score", "dae_row_sums", "dae_mix_weights", "dae_title_loss_backward", "dae_title_conv_backward", "dae_adam_step",
@@ -80,6 +81,10 @@ def load():
     lib.dae_set_exact_margin_range.argtypes = [vp, c_int, c_int, c_f]
     lib.dae_set_exact_audit.argtypes = [vp, c_int, c_int]
     lib.dae_exact_audit_read.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
+    lib.dae_set_filter_skip.argtypes = [vp, c_int]
+    lib.dae_filter_skip_read.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
+    lib.dae_filter_skip_last.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), c_int, ctypes.POINTER(c_int)]
+    lib.dae_tile_bounds_read.argtypes = [vp, vp, c_int, ctypes.POINTER(c_int)]
     lib.dae_decode_dense.argtypes = [vp, vp, c_int, c_int, c_int, c_int, vp, c_i64]
     lib.dae_decode_topk.argtypes = [vp, vp, c_int, c_int, c_int, c_int, vp, vp, c_int, c_int, vp, vp]
     lib.dae_score_topk.argtypes = [vp, vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, vp, vp,
@@ -321,6 +326,32 @@ class Context:
         self.check(self.lib.dae_exact_stats_read(self.h, a))
         rows = max(int(a[0]), 1)
         return {"rows": int(a[0]), "candidates_per_row": round(int(a[1]) / rows, 1), "recomputed_per_row": round(int(a[2]) / rows, 1)}
+
+    def set_filter_skip(self, on=True):
+        """The fp32 hidden-256 filter launch walks only the tiles whose logit bound reaches the threshold (default on;
+        include/dae_hip.h).  Off: every planned tile -- the same lists and scores."""
+        self.check(self.lib.dae_set_filter_skip(self.h, 1 if on else 0))
+
+    def filter_skip_read(self):
+        """{launches, planned, live} filter tiles (summed over row groups) since the last read; resets; synchronises."""
+        a = (ctypes.c_uint64 * 3)()
+        self.check(self.lib.dae_filter_skip_read(self.h, a))
+        return {"launches": int(a[0]), "planned": int(a[1]), "live": int(a[2])}
+
+    def filter_skip_last(self):
+        """Live filter tiles per row group of the context's last ranking call ([] when it built no live lists); synchronises."""
+        a, n = (ctypes.c_int32 * 64)(), ctypes.c_int()
+        self.check(self.lib.dae_filter_skip_last(self.h, a, 64, ctypes.byref(n)))
+        return [int(a[i]) for i in range(min(n.value, 64))]
+
+    def tile_bounds(self):
+        """The fp32 image's per-tile logit bounds as a float32 array [ntiles, 2] = (A_t, M_t) (include/dae_hip.h); synchronises."""
+        import numpy as np
+        n = ctypes.c_int()
+        self.check(self.lib.dae_tile_bounds_read(self.h, None, 0, ctypes.byref(n)))
+        out = np.empty((max(n.value, 1), 2), np.float32)
+        self.check(self.lib.dae_tile_bounds_read(self.h, out.ctypes.data_as(ctypes.c_void_p), n.value, ctypes.byref(n)))
+        return out[:n.value]
 
     def decode_dense(self, h, out, apply_sigmoid=True, dtype=DAE_DTYPE_F32):
         B, H = h.shape

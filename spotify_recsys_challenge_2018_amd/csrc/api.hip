@@ -150,13 +150,14 @@ int dae_destroy(dae_ctx* ctx)
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     for (dae_packed* pk : {&ctx->pk_f32, &ctx->pk_bf16})
-        if (pk->borrowed) pk->W = pk->bias = pk->bias16 = pk->bias16_lo = pk->bias16_hi = pk->eps = pk->W32 = pk->mix_alpha = pk->mix_beta = pk->mix16_lo = pk->mix16_hi = dae_buf{};
+        if (pk->borrowed) pk->W = pk->bias = pk->tile_ub = pk->bias16 = pk->bias16_lo = pk->bias16_hi = pk->eps = pk->W32 = pk->mix_alpha = pk->mix_beta = pk->mix16_lo = pk->mix16_hi = dae_buf{};
     dae_buf* bufs[] = {&ctx->pk_f32.W, &ctx->pk_f32.bias, &ctx->pk_bf16.W, &ctx->pk_bf16.bias, &ctx->pk_f32.order, &ctx->pk_bf16.order, &ctx->pk_bf16.bias16, &ctx->pk_f32.ident, &ctx->pk_bf16.ident,
                        &ctx->h_packed, &ctx->sample, &ctx->tau, &ctx->sample_top, &ctx->cand,
                        &ctx->cand_cnt, &ctx->gmax, &ctx->dense_tmp, &ctx->h_packed16, &ctx->h_scratch, &ctx->train_a, &ctx->train_b,
                        &ctx->train_c, &ctx->train_d, &ctx->csr_tmp, &ctx->row_bad, &ctx->guard, &ctx->refined, &ctx->refstat, &ctx->pk_bf16.eps, &ctx->pk_bf16.bias16_lo,
                        &ctx->pk_bf16.bias16_hi, &ctx->pk_bf16.W32, &ctx->pk_bf16.mix_alpha, &ctx->pk_bf16.mix_beta, &ctx->pk_bf16.mix16_lo,
-                       &ctx->pk_bf16.mix16_hi, &ctx->mix_fhat, &ctx->title_scratch, &ctx->tile_band, &ctx->title_tab, &ctx->audit, &ctx->audit_stat, &ctx->title_y1};
+                       &ctx->pk_bf16.mix16_hi, &ctx->mix_fhat, &ctx->title_scratch, &ctx->tile_band, &ctx->title_tab, &ctx->audit, &ctx->audit_stat, &ctx->title_y1,
+                       &ctx->pk_f32.tile_ub, &ctx->live, &ctx->skip_stat};
     for (dae_buf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (hipEvent_t ev : ctx->prof_ev) (void)hipEventDestroy(ev);
@@ -304,7 +305,7 @@ int dae_encode(dae_ctx* ctx, const int32_t* row_ptr, const int32_t* col, const f
 static void unborrow(dae_packed& pk)
 {
     if (!pk.borrowed) return;
-    pk.W = pk.bias = pk.bias16 = pk.bias16_lo = pk.bias16_hi = pk.eps = pk.W32 = pk.mix_alpha = pk.mix_beta = pk.mix16_lo = pk.mix16_hi = dae_buf{};
+    pk.W = pk.bias = pk.tile_ub = pk.bias16 = pk.bias16_lo = pk.bias16_hi = pk.eps = pk.W32 = pk.mix_alpha = pk.mix_beta = pk.mix16_lo = pk.mix16_hi = dae_buf{};
     pk.borrowed = false; pk.valid = false; pk.exact = false; pk.order_nrank = -1;
 }
 
@@ -322,7 +323,7 @@ int dae_share_decoder(dae_ctx* dst, const dae_ctx* src, int dtype)
     if (!dp.borrowed) {                                    // drop the own image of this slot (after its last use)
         hipError_t e = hipStreamSynchronize(dst->stream);
         if (e != hipSuccess) return dae_fail(dst, DAE_ERR_HIP, "sync: %s", hipGetErrorString(e));
-        for (dae_buf* b : {&dp.W, &dp.bias, &dp.bias16, &dp.bias16_lo, &dp.bias16_hi, &dp.eps, &dp.W32, &dp.mix_alpha, &dp.mix_beta, &dp.mix16_lo, &dp.mix16_hi})
+        for (dae_buf* b : {&dp.W, &dp.bias, &dp.tile_ub, &dp.bias16, &dp.bias16_lo, &dp.bias16_hi, &dp.eps, &dp.W32, &dp.mix_alpha, &dp.mix_beta, &dp.mix16_lo, &dp.mix16_hi})
             if (b->p) { (void)hipFree(b->p); dst->scratch_total -= b->bytes; *b = dae_buf{}; }
     }
     const dae_buf order = dp.order, ident = dp.ident;      // the tile lists stay this context's own (small, built lazily)
@@ -386,6 +387,53 @@ int dae_exact_stats_read(dae_ctx* ctx, uint64_t out3[3])
     DAE_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     out3[0] = (uint64_t)n;
     for (int r = 0; r < n; ++r) { out3[1] += (uint64_t)h[2 * r]; out3[2] += (uint64_t)h[2 * r + 1]; }
+    return DAE_OK;
+}
+
+int dae_set_filter_skip(dae_ctx* ctx, int on)
+{
+    if (!ctx) return DAE_ERR_ARG;
+    ctx->filter_skip = on ? 1 : 0;
+    return DAE_OK;
+}
+
+int dae_filter_skip_read(dae_ctx* ctx, uint64_t out3[3])
+{
+    if (!ctx) return DAE_ERR_ARG;
+    if (!out3) return dae_fail(ctx, DAE_ERR_ARG, "null pointer");
+    out3[0] = out3[1] = out3[2] = 0;
+    if (!ctx->skip_stat.p) return DAE_OK;
+    unsigned long long h[3] = {0, 0, 0};
+    DAE_HIP_CHECK(ctx, hipMemcpyAsync(h, ctx->skip_stat.p, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    DAE_HIP_CHECK(ctx, hipMemsetAsync(ctx->skip_stat.p, 0, sizeof(h), ctx->stream));
+    DAE_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < 3; ++i) out3[i] = (uint64_t)h[i];
+    return DAE_OK;
+}
+
+int dae_filter_skip_last(dae_ctx* ctx, int32_t* live_out, int cap, int* n_rg_out)
+{
+    if (!ctx) return DAE_ERR_ARG;
+    if (!n_rg_out || (cap > 0 && !live_out)) return dae_fail(ctx, DAE_ERR_ARG, "null pointer");
+    *n_rg_out = ctx->live_n_rg;
+    const int n = ctx->live_n_rg < cap ? ctx->live_n_rg : cap;
+    if (n <= 0) return DAE_OK;
+    DAE_HIP_CHECK(ctx, hipMemcpyAsync(live_out, ctx->live.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    DAE_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return DAE_OK;
+}
+
+int dae_tile_bounds_read(dae_ctx* ctx, float* ub_out, int cap_tiles, int* ntiles_out)
+{
+    if (!ctx) return DAE_ERR_ARG;
+    if (!ntiles_out || (cap_tiles > 0 && !ub_out)) return dae_fail(ctx, DAE_ERR_ARG, "null pointer");
+    const dae_packed& pk = ctx->pk_f32;
+    if (!pk.valid || !pk.ub_valid || !pk.tile_ub.p) return dae_fail(ctx, DAE_ERR_STATE, "no fp32 decoder image with tile bounds");
+    *ntiles_out = pk.ntiles;
+    const int n = pk.ntiles < cap_tiles ? pk.ntiles : cap_tiles;
+    if (n <= 0) return DAE_OK;
+    DAE_HIP_CHECK(ctx, hipMemcpyAsync(ub_out, pk.tile_ub.p, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    DAE_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return DAE_OK;
 }
 
@@ -662,6 +710,7 @@ static int topk_phase_b(dae_ctx* ctx, const float* tau_src, const int32_t* seed_
     dae_topk_state& tk = ctx->tk;
     if (!tk.valid) return dae_fail(ctx, DAE_ERR_STATE, "no scoring call in progress on this context");
     tk.valid = false;
+    ctx->live_n_rg = 0;                                    // (dae_filter_skip_last: no live lists unless the launch below builds them)
     const dae_packed* pk = tk.pk;
     const dae_rowgeom& g = tk.g;
     const int B = tk.B, k = tk.k, dtype = tk.dtype;
@@ -699,12 +748,34 @@ static int topk_phase_b(dae_ctx* ctx, const float* tau_src, const int32_t* seed_
     rc = dae_reserve(ctx, ctx->cand_cnt, (size_t)g.nb_rg * g.Bpad * sizeof(int));
     if (rc) return rc;
     dae_tileset tsB{n_filter, tk.S, 3, tk.whole_b ? tk.order : tk.order + tk.n_samp};
+    // SKIPPED TILES (fp32, hidden 256, 128-row groups, no score mix: decode_f32_h256_filter_kernel): the thresholds are known
+    // here, and so is a bound of every tile's logits for the hidden rows of a row group (pk->tile_ub, prepack.hip) -- one small
+    // launch compacts, per row group, the tiles of tsB that can hold a logit >= tau for one of its rows, and the filter launch
+    // walks those.  What it leaves out the filter epilogue would have dropped element by element: the lists cannot change
+    // (DESIGN.md section 2).  Issued before the gate: it runs while the other batch's filter launch holds the matrix cores.
+    // Every other filter launch (generic fp32, bf16, exact bf16, the mixed score) walks all of tsB; the plan stays host-planned.
+    const int* live_cnt = nullptr; const int* live_list = nullptr;
+    if (ctx->filter_skip && n_filter > 0 && !tk.whole_b && pk->ub_valid && pk->tile_ub.p && dae_filter_takes_live(g, dtype, pk->Hp, tk.mixed)) {
+        const size_t cnt_ints = (size_t)dae_round_up(g.n_rg, 64);
+        rc = dae_reserve(ctx, ctx->live, (cnt_ints + (size_t)g.n_rg * n_filter) * sizeof(int));
+        if (rc) return rc;
+        if (!ctx->skip_stat.p) {
+            rc = dae_reserve(ctx, ctx->skip_stat, 3 * sizeof(unsigned long long));
+            if (rc) return rc;
+            DAE_HIP_CHECK(ctx, hipMemsetAsync(ctx->skip_stat.p, 0, 3 * sizeof(unsigned long long), ctx->stream));
+        }
+        int* lc = static_cast<int*>(ctx->live.p);
+        rc = dae_launch_live_tiles(ctx, *pk, g, B, tsB.list, n_filter, tau_src, tk.nrank, lc, lc + cnt_ints,
+                                   static_cast<unsigned long long*>(ctx->skip_stat.p));
+        if (rc) return rc;
+        live_cnt = lc; live_list = lc + cnt_ints; ctx->live_n_rg = g.n_rg;
+    }
     // dae_set_decode_gate: the dominant launch takes every CU, so two of them in flight on two streams only queue
     // behind each other; the gate makes this one wait for the other context's and announces its own end
     if (ctx->gate_wait) DAE_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, ctx->gate_wait, 0));
     rc = prof_begin(ctx); if (rc) return rc;
     rc = dae_launch_decode_filter_f32(ctx, g, B, tsB, tau_src, tk.n_valid_col, static_cast<uint2*>(ctx->cand.p),
-                                      static_cast<int*>(ctx->cand_cnt.p), cap, dtype, tk.exact ? 2 : 0);
+                                      static_cast<int*>(ctx->cand_cnt.p), cap, dtype, tk.exact ? 2 : 0, live_cnt, live_list);
     if (rc) return rc;
     rc = prof_end(ctx); if (rc) return rc;
     if (ctx->gate_record) DAE_HIP_CHECK(ctx, hipEventRecord(ctx->gate_record, ctx->stream));

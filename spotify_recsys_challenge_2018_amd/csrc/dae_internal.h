@@ -33,12 +33,20 @@ struct dae_buf {
 
 struct dae_packed {            // one prepacked decoder image
     bool valid = false;
-    bool borrowed = false;      // W / bias / bias16* / eps / W32 belong to ANOTHER context (dae_share_decoder): never freed here
+    bool borrowed = false;      // W / bias / bias16* / eps / W32 / tile_ub belong to ANOTHER context (dae_share_decoder): never freed here
     int V = 0, H = 0, Hp = 0;   // Hp = H padded to DAE_HPAD
     int col_lo = 0, col_hi = 0;
     int ntiles = 0;            // ceil((col_hi-col_lo)/32)
     dae_buf W;                 // fp32: [ntiles][Hp/8][64 lanes][4]   bf16: [ntiles][Hp/16][64 lanes] uint4 (prepack.hip)
     dae_buf bias;              // [ntiles*32] fp32, zero padded
+    // fp32 image only (prepack.hip prepack_tile_kernel): per tile t two floats {A_t, M_t} with z32(r, c) <= A_t + d M_t for every
+    // column c of the tile and every hidden row r whose entries lie within d of 0.5 -- what the filter launch of hidden 256
+    // skips dead tiles by (api.hip topk_phase_b)
+    // Layout: [ntiles][2] fp32 {A_t, M_t} (the two floats per tile the skip needs), then -- MORE than the per-tile pair -- the
+    // columns' own {a_c, m_c}, [ntiles * 32][2]: the tile that holds a call's last ranked column is bounded over its ranked
+    // columns alone (its other columns are the first artists, whose biases are the image's largest).  ub_valid: the bounds
+    // belong to the current image (the training step's re-tiling leaves them out: such an image skips nothing)
+    dae_buf tile_ub; bool ub_valid = false;
     dae_buf bias16;            // bf16 image: [ntiles][64] uint4 bias fragments (prepack.hip)
     // tiles ordered by the largest bias among their rankable columns, descending (the threshold
     // sample of the fused path takes the head of this list); rebuilt when the image or the number
@@ -142,6 +150,11 @@ struct dae_ctx {
         ttab_nsizes = 0; int ttab_fs[DAE_TITLE_MAX_SIZES] = {0};
     // the bias-ordered tile list with its sample RE-DEALT for a launch geometry (dae_launch_tile_band): which order it was cut from
     dae_buf tile_band; long long band_gen = -1; int band_nsamp = 0, band_nbrg = 0, band_waves = 0;
+    // the fp32 hidden-256 filter launch walks, per row group, only the tiles whose logit bound reaches the group's threshold
+    // (prepack.hip live_tiles_kernel): [n_rg] counts (16 ints reserved at least) | [n_rg][n_filter] tile ids, in tsB's order
+    int filter_skip = 1;       // dae_set_filter_skip
+    dae_buf live; int live_n_rg = 0;       // live_n_rg: row groups of the last launch that built the lists (0: none yet)
+    dae_buf skip_stat;         // 3 x uint64 {launches, planned tiles x row groups, live tiles} since the last dae_filter_skip_read
 
     // profiling of the dominant kernel
     bool prof_on = false;
@@ -271,8 +284,9 @@ int dae_launch_encode(dae_ctx* ctx, const int32_t* row_ptr, const int32_t* col, 
                       float* xhat_out = nullptr, unsigned short* h_packed16 = nullptr, int NS = 0);
 
 // prepack.hip
+// bounds: also the per-tile logit bounds (dae_packed::tile_ub) -- the scoring images; the training step's re-tiling passes false
 int dae_launch_prepack_f32(dae_ctx* ctx, const float* W, const float* b, int V, int H,
-                           int col_lo, int col_hi);
+                           int col_lo, int col_hi, bool bounds = true);
 int dae_launch_prepack_bf16(dae_ctx* ctx, const float* W, const float* b, int V, int H,
                             int col_lo, int col_hi, int exact = 0);
 int dae_launch_pack_h(dae_ctx* ctx, const float* h, int B, int H, const dae_rowgeom& g);
@@ -285,6 +299,10 @@ bool dae_tile_order_sorted(int n_rank_tiles);    // the bias sort (true) or the 
 // band[0 .. n_samp): the sample of `order` dealt to the phase-A launch's slots so that the tiles ONE workgroup decodes in a round
 // (item = round * nb_rg * waves + wave * nb_rg + bir) come from `waves` different popularity bands; band[n_samp ..) = order
 int dae_launch_tile_band(dae_ctx* ctx, const int* order, int ntiles, int n_samp, int nb_rg, int waves, int* band);
+// the live lists of an fp32 filter launch over `list[0 .. n_items)` (128-row groups, hidden tile packed in ctx->h_packed):
+// live_cnt[rg] tiles of the list, in its order, at live_list[rg * n_items ..), can hold a logit >= min over the group's rows of tau
+int dae_launch_live_tiles(dae_ctx* ctx, const dae_packed& pk, const dae_rowgeom& g, int B, const int* list, int n_items,
+                          const float* tau, int nrank, int* live_cnt, int* live_list, unsigned long long* stat);
 
 // decode_f32.hip: the host planners, and the launchers that choose between a hidden-256 kernel and the generic one
 dae_rowgeom dae_row_geometry(int B, int Hp);
@@ -309,9 +327,13 @@ int dae_launch_decode_dense_f32(dae_ctx* ctx, const dae_rowgeom& g, int B, const
 // samples); 3 = per-WAVE groups over all of a wave's tiles, 8 wave slots per workgroup (dae_sample_wave_groups: ld_gmax = 8 nb_rg 32);
 // 4 = the same with waves w and w + 4 sharing a group (ld_gmax = 4 nb_rg 32)
 // filter epilogue: append (logit, global col) with logit >= tau[row] and col < n_valid_col
+// live_cnt / live_list (nullable; the fp32 hidden-256 kernel only -- dae_filter_takes_live): row group rg walks the live_cnt[rg]
+// tiles at live_list[rg * ts.n_items ..) instead of ts.list (dae_launch_live_tiles)
 int dae_launch_decode_filter_f32(dae_ctx* ctx, const dae_rowgeom& g, int B, const dae_tileset& ts,
                                  const float* tau, int n_valid_col, uint2* cand, int* cand_cnt,
-                                 int cap, int dtype = DAE_DTYPE_F32, int bias_sel = 0);
+                                 int cap, int dtype = DAE_DTYPE_F32, int bias_sel = 0, const int* live_cnt = nullptr,
+                                 const int* live_list = nullptr);
+bool dae_filter_takes_live(const dae_rowgeom& g, int dtype, int Hp, bool mixed);    // does the filter launch run that kernel?
 // bias_sel (bf16 image prepacked with DAE_DTYPE_BF16_EXACT): 0 = b, 1 = b - eps (lower bounds), 2 = b + eps (upper bounds)
 
 int dae_launch_decode_scaled_T(dae_ctx* ctx, const dae_rowgeom& g, int B, const dae_tileset& ts, const float* row_scale,

@@ -422,9 +422,19 @@ __global__ __launch_bounds__(256, 1) void decode_f32_h256_filter_kernel(const da
     const int bir = q * DAE_NUM_XCD + (rem_b % DAE_NUM_XCD);
 
     constexpr int n_h4 = RB * 64 * G;
+    // SKIPPED TILES (api.hip topk_phase_b, prepack.hip live_tiles_kernel): with live lists the row group walks the tiles of
+    // p.ts whose logit bound reaches the smallest threshold of its rows -- live_cnt[rg] of them, in p.ts's order -- and R, rem,
+    // split and item_at below follow that count.  A tile left out holds no logit >= tau[row] for any row of the group: the
+    // epilogue would have dropped every element of it.  No live tile: the workgroup's candidate counts are zero, nothing else
+    // is read.
+    const int* const tlist = p.live_cnt ? p.live_list + (size_t)rg * p.ts.n_items : p.ts.list;
+    const int n_items = p.live_cnt ? __builtin_amdgcn_readfirstlane(p.live_cnt[rg]) : p.ts.n_items;
+    if (n_items <= 0) {
+        if (tid < R_TILE) p.cand_cnt[(size_t)bir * p.Bpad + rg * R_TILE + tid] = 0;
+        return;
+    }
     // this wave's work: whole tiles ws + r * n_ws (r < R), then possibly one tile -- or half of one -- of
     // the last round
-    const int n_items = p.ts.n_items;
     const int n_ws = p.nb_rg * NW;
     const int ws = wave * p.nb_rg + bir;
     const int R = n_items / n_ws, rem = n_items - R * n_ws;
@@ -438,7 +448,7 @@ __global__ __launch_bounds__(256, 1) void decode_f32_h256_filter_kernel(const da
     };
     // the first two tile ids go out ahead of the hidden tile's loads, so that the W ring can start before the workgroup
     // meets (tile, barrier, ids, W was one more dependent trip to memory in front of the first MFMA)
-    const int tv_cur = tile_of_item(p.ts, item_at(0)), tv_nxt = tile_of_item(p.ts, item_at(1));
+    const int tv_cur = tlist[item_at(0)], tv_nxt = tlist[item_at(1)];
     {
         const float4* src = p.hp + (size_t)rg * n_h4;
         constexpr int NT = NW * 64;
@@ -476,7 +486,7 @@ __global__ __launch_bounds__(256, 1) void decode_f32_h256_filter_kernel(const da
         const int t = t_cur;
         const float4* wp = p.Wp + (size_t)t * G * 64 + lane;
         const float4* wn = p.Wp + (size_t)t_nxt * G * 64 + lane;
-        const int t_nn_v = tile_of_item(p.ts, item_at(r + 2));        // two tiles ahead (see decode_f32_kernel)
+        const int t_nn_v = tlist[item_at(r + 2)];                     // two tiles ahead (see decode_f32_kernel)
         const float* bp = p.bias + (size_t)t * 32 + 4 * hi;
         float4 bq[4];
 #pragma unroll
@@ -1168,15 +1178,24 @@ int dae_launch_decode_loss_f32(dae_ctx* ctx, const dae_rowgeom& g, int B, float 
     return dae_launch_decode_generic(ctx, EPI_LOSS, dtype == DAE_DTYPE_BF16 ? DT_BF16 : DT_F32, g, p);
 }
 
+// the launch below runs decode_f32_h256_filter_kernel<0>, the one kernel that can walk live lists
+bool dae_filter_takes_live(const dae_rowgeom& g, int dtype, int Hp, bool mixed)
+{
+    return dtype == DAE_DTYPE_F32 && g.R_TILE == 128 && Hp / DAE_KG == 32 && g.waves == 4 && !mixed;
+}
+
 int dae_launch_decode_filter_f32(dae_ctx* ctx, const dae_rowgeom& g, int B, const dae_tileset& ts,
                                  const float* tau, int n_valid_col, uint2* cand, int* cand_cnt,
-                                 int cap, int dtype, int bias_sel)
+                                 int cap, int dtype, int bias_sel, const int* live_cnt, const int* live_list)
 {
     dae_decp p;
     int rc = fill_common(ctx, g, B, ts, p, dtype, bias_sel);
     if (rc) return rc;
     p.tau = tau; p.n_valid_col = n_valid_col; p.cand = cand; p.cand_cnt = cand_cnt; p.cap = cap;
-    if (dtype == DAE_DTYPE_F32 && g.R_TILE == 128 && p.G == 32 && g.waves == 4 && !p.mixT) {
+    if (live_cnt && !dae_filter_takes_live(g, dtype, p.G * DAE_KG, p.mixT != nullptr))
+        return dae_fail(ctx, DAE_ERR_ARG, "live tile lists: the fp32 hidden-256 filter launch only");
+    p.live_cnt = live_cnt; p.live_list = live_list;
+    if (dae_filter_takes_live(g, dtype, p.G * DAE_KG, p.mixT != nullptr)) {
         const size_t lds = (size_t)4 * 64 * 32 * sizeof(float4) + 128 * sizeof(int) + 128 * sizeof(float);
         DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &decode_f32_h256_filter_kernel<0>, 160 * 1024));
         hipEvent_t e0 = nullptr, e1 = nullptr;

@@ -19,17 +19,23 @@ namespace {
 // (zero outside the matrix)
 constexpr int PP_PAD = 4;          // LDS row stride Hp + 4 floats: rows stay 16-byte aligned
 
+// the larger of two values, a NaN if either is one (fmax would drop it)
+template <class T>
+__device__ __forceinline__ T dae_max_nan(T a, T b) { return (a != a) ? a : ((b > a || b != b) ? b : a); }
+
 template <int DT>
 __global__ __launch_bounds__(256) void prepack_tile_kernel(const float* __restrict__ W,
                                                            const float* __restrict__ b, int H, int Hp,
                                                            int col_lo, int col_hi, int ntiles,
                                                            void* __restrict__ Wp_,
                                                            float* __restrict__ bias,
-                                                           uint4* __restrict__ bias16)
+                                                           uint4* __restrict__ bias16,
+                                                           float* __restrict__ tile_ub)
 {
-    extern __shared__ __attribute__((aligned(16))) float pp_tile[];      // [32][Hp + PP_PAD]
+    extern __shared__ __attribute__((aligned(16))) float pp_tile[];      // [32][Hp + PP_PAD] | 4 x 2 floats
     const int tid = threadIdx.x;
     const int ldt = Hp + PP_PAD;
+    float (*const ub_wave)[2] = reinterpret_cast<float (*)[2]>(pp_tile + 32 * ldt);     // (fp32 image) the waves' maxima of a_c, m_c
     const int Hp4 = Hp >> 2;
     const bool vec = (H & 3) == 0 && (reinterpret_cast<uintptr_t>(W) & 15) == 0;
     for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
@@ -73,6 +79,44 @@ __global__ __launch_bounds__(256) void prepack_tile_kernel(const float* __restri
             }
         }
         if (tid < 32) bias[t * 32 + tid] = v0 + tid < col_hi ? b[v0 + tid] : 0.0f;
+        if (DT == DT_F32 && tile_ub) {
+            // ---- the tile's logit bound (the filter launch of hidden 256 skips tiles by it: live_tiles_kernel below) ----------
+            // z32(r, c) = the canonical chain acc = fmaf(h[k], W[c][k], acc) over k < H, + b[c]  (oracle orc_decode): H + 1
+            // roundings, so |z32 - z| <= rho (sum_k |h_k W_ck| + |b_c|) with z = b_c + sum_k h_k W_ck in real numbers and
+            // rho = (H + 2) 2^-24 (1 + 2^-10), the recursive-summation bound exact_bounds_kernel uses for the same chain, plus
+            // (H + 2) 2^-125 in absolute terms for results that underflow (flushed or gradual).  For a hidden row with
+            // |h_k - 0.5| <= d for all k, and s = sum_k W_ck, n = sum_k |W_ck|:
+            //     z <= b + 0.5 s + d n,     sum_k |h_k W_ck| <= (0.5 + d) n,     hence     z32(r, c) <= a_c + d m_c,
+            //     a_c = b + 0.5 s + rho (0.5 n + |b|) + (H + 2) 2^-125,     m_c = (1 + rho) n.
+            // s and n are summed in double (H terms: off by <= H 2^-53 n, covered by 2^-40 (n + |b|) and the factor 1 + 2^-40)
+            // and a_c, m_c rounded UP to float.  The tile keeps A_t = max_c a_c, M_t = max_c m_c over its columns inside the image
+            // (n_tracks is a call-time argument: a superset of the ranked columns is still a bound).  A NaN stays a NaN: the
+            // comparison that skips a tile is written so that a NaN keeps it.
+            const int c = tid >> 3, part = tid & 7;
+            const float* wrow = pp_tile + c * ldt;
+            double sw = 0.0, nw = 0.0;
+            for (int k = part; k < H; k += 8) { const double w = (double)wrow[k]; sw += w; nw += fabs(w); }
+#pragma unroll
+            for (int sh = 1; sh < 8; sh <<= 1) { sw += __shfl_xor(sw, sh); nw += __shfl_xor(nw, sh); }
+            float a_f = -__builtin_inff(), m_f = 0.0f;                   // a column past the image bounds nothing
+            if (v0 + c < col_hi) {
+                const double bv = (double)b[v0 + c], ab = fabs(bv);
+                const double rho = (double)(H + 2) * 0x1p-24 * (1.0 + 0x1p-10);
+                const double a = bv + 0.5 * sw + rho * (0.5 * nw + ab) + (double)(H + 2) * 0x1p-125 + 0x1p-40 * (nw + ab);
+                const double m = (1.0 + rho) * nw * (1.0 + 0x1p-40);
+                a_f = (float)a; if ((double)a_f < a) a_f = nextafterf(a_f, __builtin_inff());
+                m_f = (float)m; if ((double)m_f < m) m_f = nextafterf(m_f, __builtin_inff());
+            }
+            // (the columns' own pairs behind the tiles': the tile that holds the LAST ranked column of a call is bounded over its
+            // ranked columns alone -- live_tiles_kernel -- since its other columns, the first artists, carry the largest biases)
+            if (part == 0) { tile_ub[2 * (ntiles + t * 32 + c)] = a_f; tile_ub[2 * (ntiles + t * 32 + c) + 1] = m_f; }
+#pragma unroll
+            for (int sh = 8; sh < 64; sh <<= 1) {
+                a_f = dae_max_nan(a_f, __shfl_xor(a_f, sh));
+                m_f = dae_max_nan(m_f, __shfl_xor(m_f, sh));
+            }
+            if ((tid & 63) == 0) { ub_wave[tid >> 6][0] = a_f; ub_wave[tid >> 6][1] = m_f; }
+        }
         if (DT == DT_BF16 && tid < 64) {
             const int v = v0 + (tid & 31);
             uint4 f = make_uint4(0u, 0u, 0u, 0u);
@@ -88,6 +132,94 @@ __global__ __launch_bounds__(256) void prepack_tile_kernel(const float* __restri
             bias16[t * 64 + tid] = f;
         }
         __syncthreads();
+        // (the next tile's maxima are written behind the next barrier, which this thread reaches after these reads)
+        if (DT == DT_F32 && tile_ub && tid < 2)
+            tile_ub[2 * t + tid] = dae_max_nan(dae_max_nan(ub_wave[0][tid], ub_wave[1][tid]), dae_max_nan(ub_wave[2][tid], ub_wave[3][tid]));
+    }
+}
+
+// ---- the live lists of the fp32 filter launch (api.hip topk_phase_b; hidden 256 in 128-row groups) ---------------------
+// One workgroup per row group rg.  From the group's packed hidden tile: d = max |h[r][k] - 0.5| over its rows r < B and the
+// units k < H (the zero padding of the tile is NOT read: it would give 0.5); from the thresholds the filter launch is given:
+// tau_rg = min over the same rows.  Item i of `list` is live unless U = A_t + d M_t < tau_rg (prepack_tile_kernel's bound:
+// no column of tile t then reaches the threshold of any row of the group, i.e. the filter epilogue would drop all of it).
+// The live tiles go to live_list[rg * n_items ..) in the list's order, their number to live_cnt[rg].  Roundings go the safe
+// way: d, the product and the sum in double, d and U pushed up by more than their rounding errors; the test is !(U < tau_rg),
+// so a NaN anywhere (weights, hidden rows, thresholds) and tau = -inf keep the tile.
+// stat: {launches, planned tiles x row groups, live tiles} of the context (dae_filter_skip_read).
+__global__ __launch_bounds__(1024) void live_tiles_kernel(const float4* __restrict__ hp, int B, int H, int G,
+                                                          const float* __restrict__ tau, const float* __restrict__ tile_ub,
+                                                          int ntiles, int nrank, const int* __restrict__ list, int n_items,
+                                                          int* __restrict__ live_cnt, int* __restrict__ live_list,
+                                                          unsigned long long* __restrict__ stat)
+{
+    constexpr int RB = 4, R_TILE = 128, NW = 16;
+    __shared__ double sh_d[NW];
+    __shared__ float sh_t[NW];
+    __shared__ int sh_n[NW];
+    const int rg = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // hidden tile of the group: float4 index (g * RB + rb) * 64 + l holds h[rg * 128 + rb * 32 + (l & 31)][8 g + 2 e + (l >> 5)]
+    double d = 0.0;
+    const float4* src = hp + (size_t)rg * G * RB * 64;
+    for (int o = tid; o < G * RB * 64; o += 1024) {
+        const int l = o & 63, rb = (o >> 6) % RB, g = (o >> 6) / RB;
+        if ((rg * RB + rb) * 32 + (l & 31) >= B) continue;
+        const float4 v = src[o];
+        const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (8 * g + 2 * c + (l >> 5) < H) d = dae_max_nan(d, fabs((double)e[c] - 0.5));
+    }
+    // the tile that holds the last ranked column (nrank is no multiple of 32): its bound over the ranked columns only
+    __shared__ float sh_edge[2];
+    const int t_edge = (nrank & 31) ? (nrank >> 5) : -1;
+    if (wave == 0 && t_edge >= 0) {
+        float ea = -__builtin_inff(), em = 0.0f;
+        if (lane < (nrank & 31)) { ea = tile_ub[2 * (ntiles + t_edge * 32 + lane)]; em = tile_ub[2 * (ntiles + t_edge * 32 + lane) + 1]; }
+#pragma unroll
+        for (int sh = 1; sh < 64; sh <<= 1) { ea = dae_max_nan(ea, __shfl_xor(ea, sh)); em = dae_max_nan(em, __shfl_xor(em, sh)); }
+        if (lane == 0) { sh_edge[0] = ea; sh_edge[1] = em; }
+    }
+    float tm = __builtin_inff();
+    if (tid < R_TILE && rg * R_TILE + tid < B) tm = tau[rg * R_TILE + tid];
+#pragma unroll
+    for (int sh = 1; sh < 64; sh <<= 1) {
+        d = dae_max_nan(d, __shfl_xor(d, sh));
+        tm = -dae_max_nan(-tm, -__shfl_xor(tm, sh));
+    }
+    if (lane == 0) { sh_d[wave] = d; sh_t[wave] = tm; }
+    __syncthreads();
+    for (int w = 0; w < NW; ++w) { d = dae_max_nan(d, sh_d[w]); tm = -dae_max_nan(-tm, -sh_t[w]); }
+    d *= 1.0 + 0x1p-40;                                     // (|h - 0.5| in double is off by at most 2^-53 relative)
+    const double tau_rg = (double)tm;
+
+    int done = 0;
+    int* const out = live_list + (size_t)rg * n_items;
+    for (int i0 = 0; i0 < n_items; i0 += 1024) {
+        const int i = i0 + tid;
+        bool keep = false;
+        int t = 0;
+        if (i < n_items) {
+            t = list[i];
+            const double A = (double)(t == t_edge ? sh_edge[0] : tile_ub[2 * t]), M = (double)(t == t_edge ? sh_edge[1] : tile_ub[2 * t + 1]);
+            const double dm = d * M;
+            const double U = A + dm + (fabs(A) + fabs(dm)) * 0x1p-48;   // two roundings of 2^-53 (|A| + |d M|) at most
+            keep = !(U < tau_rg);
+        }
+        const unsigned long long mask = __ballot(keep);
+        if (lane == 0) sh_n[wave] = __popcll(mask);
+        __syncthreads();
+        int before = 0, all = 0;
+        for (int w = 0; w < NW; ++w) { before += w < wave ? sh_n[w] : 0; all += sh_n[w]; }
+        if (keep) out[done + before + __popcll(mask & ((1ull << lane) - 1ull))] = t;
+        done += all;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        live_cnt[rg] = done;
+        if (rg == 0) atomicAdd(&stat[0], 1ull);
+        atomicAdd(&stat[1], (unsigned long long)n_items);
+        atomicAdd(&stat[2], (unsigned long long)done);
     }
 }
 
@@ -311,14 +443,14 @@ __global__ __launch_bounds__(256) void pack_h_bf16_kernel(const float* __restric
 
 template <int DT>
 int launch_prepack_tiles(dae_ctx* ctx, const float* W, const float* b, int H, int Hp, int col_lo, int col_hi,
-                         int ntiles, void* Wp, float* bias, uint4* bias16)
+                         int ntiles, void* Wp, float* bias, uint4* bias16, float* tile_ub = nullptr)
 {
     if (ntiles <= 0) return DAE_OK;
-    const size_t lds = (size_t)32 * (Hp + PP_PAD) * sizeof(float);
+    const size_t lds = ((size_t)32 * (Hp + PP_PAD) + 8) * sizeof(float);
     DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &prepack_tile_kernel<DT>, 160 * 1024));
     const int blocks = ntiles < 8 * DAE_NUM_CU ? ntiles : 8 * DAE_NUM_CU;
     hipLaunchKernelGGL(prepack_tile_kernel<DT>, dim3(blocks), dim3(256), lds, ctx->stream, W, b, H, Hp, col_lo, col_hi,
-                       ntiles, Wp, bias, bias16);
+                       ntiles, Wp, bias, bias16, tile_ub);
     DAE_CHECK_LAUNCH(ctx, "prepack_tile_kernel");
     return DAE_OK;
 }
@@ -394,10 +526,10 @@ int dae_launch_pack_h_bf16(dae_ctx* ctx, const float* h, int B, int H, const dae
 }
 
 int dae_launch_prepack_f32(dae_ctx* ctx, const float* W, const float* b, int V, int H,
-                           int col_lo, int col_hi)
+                           int col_lo, int col_hi, bool bounds)
 {
     dae_packed& pk = ctx->pk_f32;
-    pk.valid = false; pk.order_nrank = -1;
+    pk.valid = false; pk.order_nrank = -1; pk.ub_valid = false;
     const int Hp = dae_round_up(H, DAE_HPAD);
     if ((size_t)32 * Hp * 4 > 128 * 1024)
         return dae_fail(ctx, DAE_ERR_ARG, "hidden size %d too large (max 1024)", H);
@@ -407,15 +539,19 @@ int dae_launch_prepack_f32(dae_ctx* ctx, const float* W, const float* b, int V, 
     if (rc) return rc;
     rc = dae_reserve(ctx, pk.bias, (size_t)ntiles * 32 * sizeof(float));
     if (rc) return rc;
+    if (bounds) {
+        rc = dae_reserve(ctx, pk.tile_ub, (size_t)(ntiles > 0 ? ntiles : 1) * 33 * 2 * sizeof(float));      // [ntiles][2] | [ntiles * 32][2]
+        if (rc) return rc;
+    }
     rc = launch_prepack_tiles<DT_F32>(ctx, W, b, H, Hp, col_lo, col_hi, ntiles, pk.W.p,
-                                      static_cast<float*>(pk.bias.p), nullptr);
+                                      static_cast<float*>(pk.bias.p), nullptr, bounds ? static_cast<float*>(pk.tile_ub.p) : nullptr);
     if (rc) return rc;
     pk.V = V; pk.H = H; pk.Hp = Hp; pk.col_lo = col_lo; pk.col_hi = col_hi; pk.ntiles = ntiles;
     rc = dae_reserve(ctx, pk.ident, (size_t)(ntiles > 0 ? ntiles : 1) * sizeof(int));
     if (rc) return rc;
     rc = dae_launch_tile_iota(ctx, static_cast<int*>(pk.ident.p), ntiles);
     if (rc) return rc;
-    pk.valid = true;
+    pk.valid = true; pk.ub_valid = bounds;
     return DAE_OK;
 }
 
@@ -461,6 +597,18 @@ int dae_launch_tile_band(dae_ctx* ctx, const int* order, int ntiles, int n_samp,
     hipLaunchKernelGGL(tile_band_kernel, dim3((ntiles + 255) / 256), dim3(256), 0, ctx->stream, order, ntiles, n_samp, nb_rg,
                        waves, band);
     DAE_CHECK_LAUNCH(ctx, "tile_band_kernel");
+    return DAE_OK;
+}
+
+int dae_launch_live_tiles(dae_ctx* ctx, const dae_packed& pk, const dae_rowgeom& g, int B, const int* list, int n_items,
+                          const float* tau, int nrank, int* live_cnt, int* live_list, unsigned long long* stat)
+{
+    if (g.R_TILE != 128 || !pk.ub_valid || !pk.tile_ub.p || !ctx->h_packed.p || n_items <= 0)
+        return dae_fail(ctx, DAE_ERR_STATE, "live tile lists: fp32 image with tile bounds, 128-row groups");
+    hipLaunchKernelGGL(live_tiles_kernel, dim3(g.n_rg), dim3(1024), 0, ctx->stream, static_cast<const float4*>(ctx->h_packed.p),
+                       B, pk.H, pk.Hp / DAE_KG, tau, static_cast<const float*>(pk.tile_ub.p), pk.ntiles, nrank, list, n_items, live_cnt, live_list,
+                       stat);
+    DAE_CHECK_LAUNCH(ctx, "live_tiles_kernel");
     return DAE_OK;
 }
 

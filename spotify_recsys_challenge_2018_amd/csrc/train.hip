@@ -806,7 +806,7 @@ int dae_train_step_f32(dae_ctx* ctx,
     // decoder weights change every step: re-tile them for the forward GEMM
     if (!t.rm) {
         rc = t.dtype == DAE_DTYPE_BF16 ? dae_launch_prepack_bf16(ctx, Wd, b_dec, V, H, 0, V)
-                                       : dae_launch_prepack_f32(ctx, Wd, b_dec, V, H, 0, V);
+                                       : dae_launch_prepack_f32(ctx, Wd, b_dec, V, H, 0, V, false);    // (no logit bounds: a ranking call on this image skips nothing)
         if (rc) return rc;
     }
 
@@ -878,7 +878,7 @@ int dae_train_shard_decode_f32(dae_ctx* ctx, const float* pre, const float* b_en
     const float* Wd = tied ? W_enc_loc : W_dec_loc;
     if (!t.rm) {
         rc = t.dtype == DAE_DTYPE_BF16 ? dae_launch_prepack_bf16(ctx, Wd, b_dec_loc, Vl, H, 0, Vl)
-                                       : dae_launch_prepack_f32(ctx, Wd, b_dec_loc, Vl, H, 0, Vl);
+                                       : dae_launch_prepack_f32(ctx, Wd, b_dec_loc, Vl, H, 0, Vl, false);
         if (rc) return rc;
     }
     hipLaunchKernelGGL(activate_kernel, dim3(grid_for(t.bh)), dim3(256), 0, st, pre, b_enc, B, H, kp, seed,
