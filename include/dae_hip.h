@@ -131,6 +131,34 @@ int dae_coo_to_csr(dae_ctx* ctx, const int64_t* positions, const float* values, 
 int dae_seeds_from_csr(dae_ctx* ctx, const int32_t* row_ptr, const int32_t* col, int B, int n_tracks,
                        int32_t* seed_row_ptr, int32_t* seed_col);
 
+/* ---- the training feed on the device (csrc/train_feed.hip; utils/data_reader.py) ------------ */
+
+/* The training set as the reader holds it -- per side (tracks, artists) a flat id array and n_playlists + 1 offsets --
+ * copied ONCE into device memory the set owns.  HOST arrays: trk / art int32, trk_off / art_off int64.  Refused here, on
+ * the host and before any HIP call (DAE_ERR_ARG and a message): offsets that do not start at 0 or descend, a track id
+ * outside [0, n_tracks), an artist id outside [n_tracks, n_items).  dae_train_batch relies on it and carries no per-entry
+ * range flag.  The set belongs to ctx's device; destroy it before the process ends (it waits for the device first). */
+typedef struct dae_train_set dae_train_set;
+int dae_train_set_create(dae_ctx* ctx, const int32_t* trk, const int64_t* trk_off, const int32_t* art, const int64_t* art_off,
+                         int n_playlists, int n_tracks, int n_items, dae_train_set** out);
+int dae_train_set_destroy(dae_train_set* set);
+
+/* Both CSRs of one training step from the reader's DRAWS, on ctx's stream, in two launches (no memset).
+ *   draw   DEVICE int32 [3][B]: playlist index (the file's own), given tracks, given artists.  Entry i of a side (its
+ *          position in the playlist) carries the value 1 if given < 0 || i < given, else 0; -1 feeds the whole side.
+ *   x_side 0: x = the tracks, 1: the artists, 2: both (y's entries with x's values).  y = tracks u artists, value 1.
+ * The result is what dae_coo_to_csr makes of that feed: among equal columns of a row the LAST position wins, zero values
+ * are dropped, columns ascend; row_ptr[B] entries of col / val are written.  A playlist may be drawn into several rows.
+ *   x_cap / y_cap: room of x_col, x_val / y_col, y_val in entries; nothing is written at or past it (row_ptr still holds
+ *          the offsets of the whole result).
+ *   status DEVICE int32, always written: bit 0 = a playlist index outside [0, n_playlists) (that row is empty), bit 1 =
+ *          x_cap or y_cap was too small.
+ * 1 <= B <= 4096.  Scratch: 8 bytes x B x the set's longest playlist (12 when a side of the set exceeds 512 entries:
+ * such sides are ranked over global memory instead of LDS). */
+int dae_train_batch(dae_ctx* ctx, const dae_train_set* set, const int32_t* draw, int B, int x_side,
+                    int32_t* x_row_ptr, int32_t* x_col, float* x_val, int x_cap,
+                    int32_t* y_row_ptr, int32_t* y_col, float* y_val, int y_cap, int32_t* status);
+
 /* h[r,:] = hidden_dropout( sigmoid( sum_c (x[r,c]/(s_r+1e-10)) * W_enc[c,:] + b_enc ) )
  *   x      = input_dropout(CSR row r), s_r = sum of surviving weights.
  *   ikp/kp = input / hidden keep probabilities (1.0 = identity, the inference setting);

@@ -4,7 +4,10 @@ i.e. what `main.py --dae` sustains, at BASELINE.json configs[3] shape: V = 170 0
 ranks, 20..100 tracks per playlist) is written to a temp dir, then the loop of main_runner/main_train.py is
 timed with its parts: reader.next_batch, train_step (upload + device CSR + step + cost fetch).
 
-  python scripts/bench_epoch.py [--playlists 20000] [--steps 200] [--tied]
+  python scripts/bench_epoch.py [--playlists 20000] [--steps 200] [--tied] [--firstn 0.3,0.6] [--device-feed]
+
+--device-feed: the loop of `[BASE] train_feed = device` -- reader.next_batch_draw, then train_step_draw (12 bytes a row up,
+both CSRs built on the device from the resident training set).
 """
 import argparse, json, os, random, sys, tempfile, time
 import numpy as np
@@ -39,16 +42,21 @@ def main():
     ap.add_argument("--decoder-adam", choices=["fused", "dense"], default="fused",
                     help="untied decoder: Adam inside the decoder-gradient kernel (default) or dae_adam_step")
     ap.add_argument("--host-csr", action="store_true", help="device_csr = False: feed -> CSR with numpy on the host")
+    ap.add_argument("--device-feed", action="store_true", help="train_feed = device: next_batch_draw + train_step_draw")
+    ap.add_argument("--firstn", default=None, metavar="LO,HI", help="data_reader_firstN with this firstN_range (e.g. 0.3,0.6)")
     ap.add_argument("--flush-every", type=int, default=32, help="rows-Adam: all rows brought up to date every N steps")
     args = ap.parse_args()
     import torch
     from spotify_recsys_challenge_2018_amd.models.DAEs import DAE, DAE_tied
-    from spotify_recsys_challenge_2018_amd.utils.data_reader import data_reader
+    from spotify_recsys_challenge_2018_amd.utils.data_reader import data_reader, data_reader_firstN
 
     nt, na = 140000, 30000
     tmp = tempfile.mkdtemp()
     write_train(os.path.join(tmp, "train"), args.playlists, nt, na)
-    reader = data_reader(data_dir=tmp, filename="train", batch_size=256)
+    if args.firstn:
+        reader = data_reader_firstN(data_dir=tmp, filename="train", batch_size=256, from_to=[float(t) for t in args.firstn.split(",")])
+    else:
+        reader = data_reader(data_dir=tmp, filename="train", batch_size=256)
 
     class C: pass
     conf = C()
@@ -64,16 +72,24 @@ def main():
         conf.train_dtype = "bf16"
     model = (DAE_tied if args.tied else DAE)(conf)
     model.fit()
+    if args.device_feed:
+        model.attach_train_set(reader)
     random.seed(0); np.random.seed(0)
 
     def one(fetch=True):
         t0 = time.perf_counter()
-        trk, art, y, _t, tv, av = reader.next_batch()
+        if args.device_feed:
+            draw = reader.next_batch_draw()
+        else:
+            trk, art, y, _t, tv, av = reader.next_batch()
         t1 = time.perf_counter()
         kp = random.uniform(0.5, 0.8)
-        x, xv = (trk, tv) if np.random.randint(2) == 0 else (art, av)
         kw = {} if fetch else {"fetch_cost": False}
-        l = model.train_step(x, xv, y, np.ones(len(y), np.float32), 0.8, kp, **kw)
+        if args.device_feed:
+            l = model.train_step_draw(draw, int(np.random.randint(2) != 0), 0.8, kp, **kw)
+        else:
+            x, xv = (trk, tv) if np.random.randint(2) == 0 else (art, av)
+            l = model.train_step(x, xv, y, np.ones(len(y), np.float32), 0.8, kp, **kw)
         t2 = time.perf_counter()
         return t1 - t0, t2 - t1, l
 
@@ -93,7 +109,8 @@ def main():
                       "playlists_per_s": round(256 * args.steps / wall, 1),
                       "reader_ms": round(tr / args.steps * 1e3, 3), "train_step_call_ms": round(ts / args.steps * 1e3, 3),
                       "async_cost": bool(args.async_cost), "encoder_adam": "dense" if args.tied else args.encoder_adam,
-                      "train_dtype": "bf16" if args.bf16 else "f32", "last_cost": float(l)}))
+                      "train_dtype": "bf16" if args.bf16 else "f32", "feed": "device" if args.device_feed else "host",
+                      "firstn": args.firstn, "last_cost": float(l)}))
 
 
 if __name__ == "__main__":

@@ -15,7 +15,7 @@ DAE_DTYPE_F32, DAE_DTYPE_BF16, DAE_DTYPE_BF16_EXACT = 0, 1, 2
 EXPORTS = [
     "dae_version", "dae_create", "dae_destroy", "dae_set_stream", "dae_last_error",
     "dae_scratch_bytes", "dae_profile_enable", "dae_profile_read", "dae_profile_kernel", "dae_clock_probe", "dae_last_plan",
-    "dae_coo_to_csr", "dae_seeds_from_csr", "dae_encode", "dae_prepack_decoder", "dae_prepack_decoder_rows", "dae_share_decoder", "dae_exact_bounds",
+    "dae_coo_to_csr", "dae_seeds_from_csr", "dae_train_set_create", "dae_train_set_destroy", "dae_train_batch", "dae_encode", "dae_prepack_decoder", "dae_prepack_decoder_rows", "dae_share_decoder", "dae_exact_bounds",
     "dae_exact_guard_read", "dae_exact_guard_words", "dae_exact_guard_snapshot", "dae_exact_stats_read", "dae_set_exact_margin", "dae_set_exact_margin_range", "dae_set_exact_audit", "dae_exact_audit_read",
     "dae_set_filter_skip", "dae_filter_skip_read", "dae_filter_skip_last", "dae_tile_bounds_read", "dae_decode_dense", "dae_decode_topk",
     "dae_score_topk", "dae_score_topk_begin", "dae_score_topk_finish", "dae_topk_dense", "dae_topk_merge", "dae_set_train_dtype", "dae_train_forward_backward",
@@ -68,6 +68,9 @@ def load():
     lib.dae_last_plan.argtypes = [ctypes.POINTER(ctypes.c_int32)]
     lib.dae_coo_to_csr.argtypes = [vp, vp, vp, c_int, c_i64, c_int, c_int, vp, vp, vp, vp]
     lib.dae_seeds_from_csr.argtypes = [vp, vp, vp, c_int, c_int, vp, vp]
+    lib.dae_train_set_create.argtypes = [vp, vp, vp, vp, vp, c_int, c_int, c_int, ctypes.POINTER(vp)]
+    lib.dae_train_set_destroy.argtypes = [vp]
+    lib.dae_train_batch.argtypes = [vp, vp, vp, c_int, c_int, vp, vp, vp, c_int, vp, vp, vp, c_int, vp]
     lib.dae_encode.argtypes = [vp, vp, vp, vp, vp, vp, c_int, c_int, c_int, c_f, c_f, c_u32, vp]
     lib.dae_prepack_decoder.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_int, c_int]
     lib.dae_prepack_decoder_rows.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_int]
@@ -173,6 +176,44 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+class TrainSet:
+    """Owns one dae_train_set: the training playlists on the device of `ctx` (dae_train_set_create copies the host arrays
+    once).  trk / art: the flat id arrays of the two sides, trk_off / art_off: n_playlists + 1 offsets each -- the reader's
+    `_trk / _trk_off / _art / _art_off` (utils/data_reader.py).  Ids outside their ranges raise DaeError before any launch."""
+
+    def __init__(self, ctx, trk, trk_off, art, art_off, n_tracks, n_items):
+        import numpy as np
+        self.ctx, self.h = ctx, None                         # (the context outlives the set: it names the device)
+        trk, art = (np.ascontiguousarray(a, dtype=np.int64) for a in (trk, art))
+        for a in (trk, art):                                 # narrowed for the device; what does not fit is no id
+            if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+                raise DaeError("dae_train_set_create: an id does not fit 32 bits")
+        trk, art = trk.astype(np.int32), art.astype(np.int32)
+        trk_off, art_off = (np.ascontiguousarray(a, dtype=np.int64) for a in (trk_off, art_off))
+        if trk_off.size != art_off.size or trk_off.size < 2:
+            raise DaeError("dae_train_set_create: trk_off and art_off hold n_playlists + 1 offsets each")
+        if int(trk_off[-1]) != trk.size or int(art_off[-1]) != art.size:
+            raise DaeError("dae_train_set_create: the last offset of a side is the length of its id array")
+        self.n_playlists = int(trk_off.size) - 1
+        h = ctypes.c_void_p()
+        vp = ctypes.c_void_p
+        ctx.check(ctx.lib.dae_train_set_create(ctx.h, vp(trk.ctypes.data), vp(trk_off.ctypes.data), vp(art.ctypes.data),
+                                               vp(art_off.ctypes.data), self.n_playlists, int(n_tracks), int(n_items),
+                                               ctypes.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.dae_train_set_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Context:
     """Owns one dae_ctx bound to a device + the caller's current torch stream."""
 
@@ -224,6 +265,25 @@ class Context:
         sc = torch.empty(max(int(col.numel()), 1), dtype=torch.int32, device=row_ptr.device)
         self.check(self.lib.dae_seeds_from_csr(self.h, _ptr(row_ptr), _ptr(col), B, int(n_tracks), _ptr(srp), _ptr(sc)))
         return srp, sc
+
+    def train_batch(self, train_set, draw, x_side, x_cap, y_cap):
+        """Both CSRs of a training step from the reader's draws (dae_train_batch).  draw: int32 [3, B] CUDA tensor (playlist
+        index, given tracks, given artists); x_side 0 tracks / 1 artists / 2 both; x_cap / y_cap: room of the outputs in
+        entries (an upper bound of the kept entries).  -> ((x_row_ptr, x_col, x_val), (y_row_ptr, y_col, y_val), status):
+        status bit 0 = a playlist index out of range, bit 1 = a capacity was too small."""
+        import torch
+        B = int(draw.shape[1])
+        assert draw.dtype == torch.int32 and draw.is_contiguous() and draw.shape[0] == 3
+        dev = draw.device
+        out = []
+        for cap in (x_cap, y_cap):
+            out.append((torch.empty(B + 1, dtype=torch.int32, device=dev), torch.empty(max(int(cap), 1), dtype=torch.int32, device=dev),
+                        torch.empty(max(int(cap), 1), dtype=torch.float32, device=dev)))
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        (xr, xc, xv), (yr, yc, yv) = out
+        self.check(self.lib.dae_train_batch(self.h, train_set.h, _ptr(draw), B, int(x_side), _ptr(xr), _ptr(xc), _ptr(xv),
+                                            int(x_cap), _ptr(yr), _ptr(yc), _ptr(yv), int(y_cap), _ptr(status)))
+        return out[0], out[1], status
 
     def set_train_dtype(self, dtype):
         """Arithmetic of the training forward GEMM: DAE_DTYPE_F32 (default) or DAE_DTYPE_BF16."""

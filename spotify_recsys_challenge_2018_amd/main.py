@@ -4,7 +4,7 @@ the same config.ini schema:
     python -m spotify_recsys_challenge_2018_amd.main --dir D {--pretrain|--dae|--challenge} [--testmode]
 
     [BASE] verbose data_dir result_dir testsize   (+ optional, this build only: train_dtype = f32 | bf16, decode_dtype = f32 | bf16 | exact_bf16,
-                                                  eval_metrics = rprecision | all)
+                                                  eval_metrics = rprecision | all, train_feed = host | device)
     [DAE] epochs batch lr reg_lambda hidden test_seed update_seed keep_prob input_kp firstN_range initval save
     [PRETRAIN] epochs batch lr reg_lambda save
     [TITLE] ... (parsed for compatibility; the title models are outside the scoring path)
@@ -70,7 +70,7 @@ class Conf:
         self.dir = dir
         self.ini = ini
         self._load('BASE')
-        # three OPTIONAL [BASE] keys this build adds (absent from the reference's files, which then mean fp32 / rprecision):
+        # four OPTIONAL [BASE] keys this build adds (absent from the reference's files, which then mean fp32 / rprecision):
         #   train_dtype  = f32 | bf16   arithmetic of the training step's three GEMMs (BASELINE.json configs[3])
         #   decode_dtype = f32 | bf16 | exact_bf16   arithmetic of the scoring decode: fp32 MFMA (bit-exact path), bf16
         #                  (configs[4]), or the bf16 GEMM as a filter with the survivors recomputed in fp32 (north_star:
@@ -78,9 +78,13 @@ class Conf:
         #   eval_metrics = rprecision | all   what the evaluation of a test split logs: the r-precision line alone (default,
         #                  the reference's log), or NDCG and recommended-songs clicks as well (utils/metrics.py get_ndcg /
         #                  get_rsc, which the reference defines and never calls); model selection reads r-precision either way
+        #   train_feed   = host | device      where the training batches of --pretrain / --dae are built: by the reader on the host
+        #                  (default), or on the device from a resident copy of the training set -- only the reader's draws
+        #                  go over the link (models/DAEs.py train_step_draw); same batches, same random draws
         self.eval_metrics = 'rprecision'
+        self.train_feed = 'host'
         for key, allowed in (('train_dtype', ('f32', 'bf16')), ('decode_dtype', ('f32', 'bf16', 'exact_bf16')),
-                             ('eval_metrics', ('rprecision', 'all'))):
+                             ('eval_metrics', ('rprecision', 'all')), ('train_feed', ('host', 'device'))):
             if key in self.ini['BASE']:
                 val = self.ini['BASE'][key].strip().lower()
                 if val not in allowed:

@@ -209,14 +209,27 @@ def run(conf, only_testmode):
         _log_splits(conf, readers_test, out, extras)
         return out
 
+    # [BASE] train_feed = device: the training set lives on the device and a batch goes up as the reader's draws alone
+    device_feed = getattr(conf, 'train_feed', 'host') == 'device'
+    if device_feed and conf.mode == 'title':
+        log_write(conf, "train_feed = device is ignored in title mode: the batches are built on the host")
+        device_feed = False
+    if device_feed:
+        model.attach_train_set(reader)
+
     epoch, it, loss, max_eval = 0, 0, 0.0, 0.0
     history = []
     while True:
         start_idx = reader.train_idx
-        trk_positions, art_positions, y_positions, _titles, trk_val, art_val = reader.next_batch()
+        if device_feed:
+            draw = reader.next_batch_draw()
+        else:
+            trk_positions, art_positions, y_positions, _titles, trk_val, art_val = reader.next_batch()
         end_idx = reader.train_idx
         input_kp = random.uniform(kp_range[0], kp_range[-1])        # main_train.py:199
-        if conf.mode == 'title':                                    # :214-221: the whole playlist is input and target
+        if device_feed:                                             # the same coin, after the same draws
+            l = model.train_step_draw(draw, int(np.random.randint(2) != 0), conf.kp, input_kp, fetch_cost=False)
+        elif conf.mode == 'title':                                    # :214-221: the whole playlist is input and target
             ones = np.ones(len(y_positions), np.float32)
             l = model.train_step(y_positions, ones, y_positions, ones, conf.kp, input_kp, titles=_titles,
                                  titles_use=np.ones(conf.batch, np.float32), title_keep_prob=conf.title_kp)

@@ -188,6 +188,7 @@ class DAE_tied:
         self.device_csr = bool(getattr(conf, "device_csr", True))
         self._csr_status = None
         self._sharded = None          # sharding.ShardedTrainer when training is row-sharded over ranks
+        self._train_feed = None       # attach_train_set(): the reader and its playlists on the device (_lib.TrainSet)
         self._params_stale = False
         self._score_shard = None      # shard_scoring(): this rank's vocabulary columns + the ShardedRanker
         self._copy_stream = None      # _to_dev(side_stream=True): the training loop's upload stream
@@ -655,6 +656,14 @@ class DAE_tied:
             if fetch_cost:
                 self._check_feed()
             return cost
+        x = self._upload_csr(x_positions, x_ones, side_stream=True)
+        y = self._upload_csr(y_positions, y_ones, side_stream=True)
+        return self._train_step_csr(x, y, keep_prob, input_keep_prob, fetch_cost)
+
+    def _train_step_csr(self, x, y, keep_prob, input_keep_prob, fetch_cost):
+        """One Adam step on the device CSRs x, y = (row_ptr, col, val) of a batch, whichever feed built them (`train_step`:
+        the host's COO through dae_coo_to_csr; `train_step_draw`: dae_train_batch).  -> the cost, as `train_step` returns it."""
+        import torch
         dev = self.weights["encoder_h"].device
         if self._adam is None:
             self._grads = {}
@@ -665,8 +674,7 @@ class DAE_tied:
                 self._grads[n] = torch.zeros_like(p)
                 self._adam[n] = (torch.zeros_like(p), torch.zeros_like(p))
             self._cost = torch.zeros(1, dtype=torch.float32, device=dev)
-        xr, xc, xv = self._upload_csr(x_positions, x_ones, side_stream=True)
-        yr, yc, yv = self._upload_csr(y_positions, y_ones, side_stream=True)
+        (xr, xc, xv), (yr, yc, yv) = x, y
         seed = int(self._rng.randint(0, 2 ** 31 - 1))
         g = self._grads
         lib, ctx = self.ctx.lib, self.ctx
@@ -726,6 +734,63 @@ class DAE_tied:
         cost = float(self._cost.item())
         self._check_feed()
         return cost
+
+    # -- the device feed (csrc/train_feed.hip; DESIGN.md "The training feed") ---------------------------------------
+    def attach_train_set(self, reader):
+        """Keep `reader`'s training set on the device for `train_step_draw`: its flat id arrays and offsets are copied
+        once (dae_train_set_create, which refuses ids outside their ranges).  Once per model, after fit().  A
+        vocabulary-sharded model keeps only the reader: its `train_step_draw` rebuilds the host feed."""
+        if self._train_feed is not None:
+            raise _lib.DaeError("attach_train_set: this model already holds a training set")
+        feed = {"reader": reader, "set": None,
+                "trk_len": np.diff(reader._trk_off), "art_len": np.diff(reader._art_off)}
+        if self._takes_device_feed():
+            feed["set"] = _lib.TrainSet(self.ctx, reader._trk, reader._trk_off, reader._art, reader._art_off,
+                                        reader.num_tracks, reader.num_items)
+        self._train_feed = feed
+
+    def _takes_device_feed(self):
+        return self._sharded is None
+
+    def _host_feed_step(self, draw, x_side, keep_prob, input_keep_prob, fetch_cost):
+        """`train_step` on the host feed rebuilt from the draw: same batches, same results, nothing sped up."""
+        from ..utils.data_reader import feed_from_draw
+        x_pos, x_val, y_pos = feed_from_draw(self._train_feed["reader"], draw, x_side)
+        return self.train_step(x_pos, x_val, y_pos, np.ones(len(y_pos), np.float32), keep_prob, input_keep_prob,
+                               fetch_cost=fetch_cost)
+
+    def train_step_draw(self, draw, x_side, keep_prob, input_keep_prob, fetch_cost=True):
+        """`train_step` of the batch the reader's `next_batch_draw` names: draw int32 [3, n_batch] (playlist index, given
+        tracks, given artists), x_side 0 / 1 / 2 = x is the tracks / the artists / both; y is the whole playlist.  Only the
+        draw goes over the link (12 bytes a row, on the copy stream); both CSRs are built on the device from the attached
+        set (dae_train_batch: two launches) and are, entry for entry, what `train_step` builds from `next_batch`'s COO -- so
+        is everything after them.  A vocabulary-sharded model and DAE_title do NOT take the device feed: they rebuild the
+        host feed from the draw (utils/data_reader.py feed_from_draw) and call their `train_step`."""
+        import torch
+        feed = self._train_feed
+        if feed is None:
+            raise _lib.DaeError("train_step_draw needs attach_train_set(reader) first")
+        draw = np.ascontiguousarray(draw, dtype=np.int32)
+        if draw.shape != (3, self.n_batch):
+            raise ValueError("draw has shape %s, expected (3, %d)" % (draw.shape, self.n_batch))
+        if feed["set"] is None or not self._takes_device_feed():
+            return self._host_feed_step(draw, x_side, keep_prob, input_keep_prob, fetch_cost)
+        if x_side not in (0, 1, 2):
+            raise ValueError("x_side %r: 0 tracks, 1 artists, 2 both" % (x_side,))
+        self.ctx.bind_stream()
+        # room of the outputs: the playlists' lengths bound the kept entries of a side (an index out of range is the device's
+        # to flag: its row is empty)
+        idx = np.clip(draw[0], 0, len(feed["trk_len"]) - 1)
+        n_trk, n_art = int(feed["trk_len"][idx].sum()), int(feed["art_len"][idx].sum())
+        x_cap = (n_trk, n_art, n_trk + n_art)[x_side]
+        d_draw = self._to_dev(draw, torch.int32, side_stream=True)
+        x, y, status = self.ctx.train_batch(feed["set"], d_draw, x_side, x_cap, n_trk + n_art)
+        cur = torch.cuda.current_stream(self.device_index)
+        pending = (self._csr_status or []) + [(status, cur.record_event())]
+        if len(pending) > 64:                                   # un-fetched training steps: fold on the device
+            pending = [(self._fold_status(pending), cur.record_event())]
+        self._csr_status = pending
+        return self._train_step_csr(x, y, keep_prob, input_keep_prob, fetch_cost)
 
     # -- persistence ----------------------------------------------------------------------------------
     def get_params(self):
@@ -910,6 +975,19 @@ class DAE_title(DAE):
         cost = float(self._tcost.item())
         self._check_feed()
         return cost
+
+    def _takes_device_feed(self):
+        return False                  # the device table holds no titles: `train_step_draw` rebuilds the host feed
+
+    def _host_feed_step(self, draw, x_side, keep_prob, input_keep_prob, fetch_cost, title_keep_prob=1.0):
+        """The title step of the batch a draw names (always fetches its cost, as `train_step` here does): the feed AND the
+        titles rebuilt on the host from the attached reader."""
+        from ..utils.data_reader import feed_from_draw
+        reader = self._train_feed["reader"]
+        x_pos, x_val, y_pos = feed_from_draw(reader, draw, x_side)
+        return self.train_step(x_pos, x_val, y_pos, np.ones(len(y_pos), np.float32), keep_prob, input_keep_prob,
+                               titles=[reader._title(int(i)) for i in draw[0]],
+                               titles_use=np.ones(self.n_batch, np.float32), title_keep_prob=title_keep_prob)
 
     def _submit(self, x_positions, x_ones, seeds, k, dtype, titles=None, titles_use=None, n_rows=None):
         """One batch enqueued, nothing fetched (`n_rows`: rows of this launch when it is not the model's batch).  Without

@@ -66,13 +66,24 @@ class data_reader(_TrainFile):
         self.batch_size = batch_size
         self.train_idx = 0
 
-    def _take(self):
-        """Indices of the next batch_size playlists; shuffles exactly where the reference does
-        (data_reader.py:44-46: when the cursor hits the end, reset and random.shuffle)."""
+    def _given_counts(self, orig_index):
+        """(given tracks, given artists) of one drawn playlist: -1, -1 -- the whole side is fed with value 1 -- and no RNG call."""
+        return -1, -1
+
+    def _draw(self):
+        """Everything random about the next batch: -> (order, g_trk, g_art), `order` the ORIGINAL file indices of the next
+        batch_size playlists, g_* the given counts of their sides.  The `random` module is consulted exactly where the
+        reference does: per playlist by `_given_counts` (tracks, then artists), BEFORE the wrap of that playlist's slot
+        (data_reader.py:44-46: when the cursor hits the end, reset and random.shuffle).  `next_batch` and `next_batch_draw` both
+        start here, so the two cannot drift."""
         n = len(self.playlists)
-        picked = []
+        order, g_trk, g_art = [], [], []
         for _ in range(self.batch_size):
-            picked.append(self._order[self.train_idx])
+            oi = self._order[self.train_idx]
+            gt, ga = self._given_counts(oi)
+            g_trk.append(gt)
+            g_art.append(ga)
+            order.append(oi)
             self.train_idx += 1
             if self.train_idx == n:
                 self.train_idx = 0
@@ -80,18 +91,37 @@ class data_reader(_TrainFile):
                 random.shuffle(perm)             # same RNG draw sequence as shuffling the list
                 self._order = self._order[np.asarray(perm, dtype=np.int64)]
                 self.playlists = [self.playlists[i] for i in perm]
-        return np.asarray(picked, dtype=np.int64)
+        return np.asarray(order, dtype=np.int64), np.asarray(g_trk, dtype=np.int64), np.asarray(g_art, dtype=np.int64)
 
-    def next_batch(self):
-        order = self._take()
-        trk, trk_rows, _ = _gather(self._trk, self._trk_off, order)
-        art, art_rows, _ = _gather(self._art, self._art_off, order)
+    def _batch_of(self, order, g_trk, g_art):
+        """The deterministic part of a batch: what `next_batch` returns for the draw (order, g_trk, g_art).  All positions of
+        a side are fed; entry i of a playlist's side carries 1 if its given count is negative or i < given, else 0."""
+        order = np.asarray(order, dtype=np.int64)
+        trk, trk_rows, trk_lens = _gather(self._trk, self._trk_off, order)
+        art, art_rows, art_lens = _gather(self._art, self._art_off, order)
+
+        def first_n(lens, given):
+            given = np.asarray(given, dtype=np.int64)
+            if given.size and given.max() < 0:                   # the plain reader: every side whole
+                return np.ones(int(lens.sum()), np.float32)
+            within = np.arange(int(lens.sum()), dtype=np.int64) - np.repeat(np.cumsum(lens) - lens, lens)
+            return (within < np.repeat(np.where(given < 0, lens, given), lens)).astype(np.float32)
+
         trk_positions = _positions(trk_rows, trk)
         art_positions = _positions(art_rows, art)
         y_positions = np.concatenate((trk_positions, art_positions), 0)
         titles = [self._title(i) for i in order]
         return (trk_positions, art_positions, y_positions, titles,
-                np.ones(len(trk_positions), np.float32), np.ones(len(art_positions), np.float32))
+                first_n(trk_lens, g_trk), first_n(art_lens, g_art))
+
+    def next_batch(self):
+        return self._batch_of(*self._draw())
+
+    def next_batch_draw(self):
+        """The next batch as its draw alone: int32 [3, batch_size] -- original file index, given tracks, given artists
+        (-1: the whole side) -- 12 bytes a row for a device that holds the table (models/DAEs.py train_step_draw).
+        train_idx, the permutation and the `random` state advance exactly as in `next_batch`: the two calls may be mixed."""
+        return np.stack(self._draw()).astype(np.int32)
 
     def _title(self, orig_index):
         return self._titles[orig_index]
@@ -99,6 +129,23 @@ class data_reader(_TrainFile):
     def _index(self):
         _TrainFile._index(self)
         self._titles = [p[2] for p in self.playlists]
+        # the sides' lengths as Python ints: the firstN draw asks for two of them per playlist
+        self._trk_len, self._art_len = np.diff(self._trk_off).tolist(), np.diff(self._art_off).tolist()
+
+
+def feed_from_draw(reader, draw, x_side):
+    """numpy restatement of the device feed (include/dae_hip.h dae_train_batch): the COO `reader.next_batch()` would have
+    returned for `draw` (int [3, B], what `next_batch_draw` returns), as the training loop feeds it.
+    x_side 0: x = the tracks, 1: the artists, 2: both.  -> (x_positions, x_vals, y_positions); y's values are all 1."""
+    draw = np.asarray(draw, dtype=np.int64)
+    trk_positions, art_positions, y_positions, _titles, trk_val, art_val = reader._batch_of(draw[0], draw[1], draw[2])
+    if x_side == 0:
+        return trk_positions, trk_val, y_positions
+    if x_side == 1:
+        return art_positions, art_val, y_positions
+    if x_side == 2:
+        return y_positions, np.concatenate((trk_val, art_val)), y_positions
+    raise ValueError("x_side %r: 0 tracks, 1 artists, 2 both" % (x_side,))
 
 
 class data_reader_firstN(data_reader):
@@ -118,39 +165,12 @@ class data_reader_firstN(data_reader):
             n, m = int(max(length * lo_f, 1)), int(max(length * hi_f, 1))
         return random.randrange(n, m + 1)                        # :91 / :109
 
-    def next_batch(self):
-        # the RNG is consulted playlist by playlist, tracks then artists, BEFORE the wrap
-        # shuffle of that playlist's slot -- replay that order exactly
-        n_pl = len(self.playlists)
-        order, g_trk, g_art = [], [], []
-        for _ in range(self.batch_size):
-            oi = self._order[self.train_idx]
-            lt = int(self._trk_off[oi + 1] - self._trk_off[oi])
-            la = int(self._art_off[oi + 1] - self._art_off[oi])
-            g_trk.append(self._given(lt) if lt != 0 else 0)
-            g_art.append(self._given(la) if la != 0 else 0)
-            order.append(oi)
-            self.train_idx += 1
-            if self.train_idx == n_pl:
-                self.train_idx = 0
-                perm = list(range(n_pl))
-                random.shuffle(perm)
-                self._order = self._order[np.asarray(perm, dtype=np.int64)]
-                self.playlists = [self.playlists[i] for i in perm]
-        order = np.asarray(order, dtype=np.int64)
-        trk, trk_rows, trk_lens = _gather(self._trk, self._trk_off, order)
-        art, art_rows, art_lens = _gather(self._art, self._art_off, order)
-
-        def first_n(lens, given):
-            within = np.arange(int(lens.sum()), dtype=np.int64) - np.repeat(np.cumsum(lens) - lens, lens)
-            return (within < np.repeat(np.asarray(given, dtype=np.int64), lens)).astype(np.float32)
-
-        trk_positions = _positions(trk_rows, trk)
-        art_positions = _positions(art_rows, art)
-        y_positions = np.concatenate((trk_positions, art_positions), 0)
-        titles = [self._titles[i] for i in order]
-        return (trk_positions, art_positions, y_positions, titles,
-                first_n(trk_lens, g_trk), first_n(art_lens, g_art))
+    def _given_counts(self, orig_index):
+        # the RNG is consulted playlist by playlist, tracks then artists; an empty side draws nothing
+        lt, la = self._trk_len[orig_index], self._art_len[orig_index]
+        gt = self._given(lt) if lt != 0 else 0
+        ga = self._given(la) if la != 0 else 0
+        return gt, ga
 
 
 class data_reader_test:
