@@ -12,17 +12,14 @@
 #include <vector>
 
 #include "../../include/dae_hip.h"
+#include "score_plan.h"            // dae_rowgeom, the host planners, DAE_KG / DAE_MAX_K / DAE_NUM_CU / DAE_NUM_XCD
 
 // ---------------------------------------------------------------------------------------------
 // geometry constants of the decode path (see DESIGN.md "HBM layout")
 // ---------------------------------------------------------------------------------------------
 constexpr int DAE_TITLE_MAX_SIZES = 8;   // filter sizes a title scorer may have (title.hip's kernels, the table, dae_pipeline_create_titled)
 constexpr int DAE_VT = 32;        // vocabulary columns per wave tile (MFMA M = 32)
-constexpr int DAE_KG = 8;         // k values per packed group (4 MFMA 32x32x2 steps)
 constexpr int DAE_HPAD = 32;      // hidden size is zero-padded to a multiple of this
-constexpr int DAE_MAX_K = 1024;   // largest top-k supported
-constexpr int DAE_NUM_CU = 256;   // MI355X
-constexpr int DAE_NUM_XCD = 8;
 constexpr int DAE_REFINED_CAP = 4096;   // survivors per row the exact mode's compact lists hold (more: refined in place)
 constexpr size_t DAE_GUARD_BYTES = 2 * sizeof(int);   // a context's guard words {violations, a violating column}
 
@@ -41,7 +38,7 @@ struct dae_packed {            // one prepacked decoder image
     dae_buf bias;              // [ntiles*32] fp32, zero padded
     // fp32 image only (prepack.hip prepack_tile_kernel): per tile t two floats {A_t, M_t} with z32(r, c) <= A_t + d M_t for every
     // column c of the tile and every hidden row r whose entries lie within d of 0.5 -- what the filter launch of hidden 256
-    // skips dead tiles by (api.hip topk_phase_b)
+    // skips dead tiles by (score.hip topk_phase_b)
     // Layout: [ntiles][2] fp32 {A_t, M_t} (the two floats per tile the skip needs), then -- MORE than the per-tile pair -- the
     // columns' own {a_c, m_c}, [ntiles * 32][2]: the tile that holds a call's last ranked column is bounded over its ranked
     // columns alone (its other columns are the first artists, whose biases are the image's largest).  ub_valid: the bounds
@@ -70,28 +67,24 @@ struct dae_packed {            // one prepacked decoder image
     dae_buf mix16_lo, mix16_hi;     // [ntiles][64] uint4
 };
 
-struct dae_rowgeom {        // how B rows are cut into row groups for the decode kernels
-    int R_TILE;             // rows per group: 128, 64 or 32 (LDS-resident h tile)
-    int n_rg;               // ceil(B / R_TILE)
-    int Bpad;               // n_rg * R_TILE
-    int nb_rg;              // thread blocks per row group
-    int grid;               // n_rg * nb_rg
-    int waves;              // waves per workgroup (4 or 8)
-};
+// the buffers of an image that dae_share_decoder lends to another context (`order` / `ident` stay each context's own)
+template <class F>
+inline void dae_packed_shared_bufs(dae_packed& pk, F&& f)
+{
+    for (dae_buf* b : {&pk.W, &pk.bias, &pk.tile_ub, &pk.bias16, &pk.bias16_lo, &pk.bias16_hi, &pk.eps, &pk.W32, &pk.mix_alpha,
+                       &pk.mix_beta, &pk.mix16_lo, &pk.mix16_hi})
+        f(*b);
+}
 
-struct dae_topk_state {     // what the second half of a fused scoring call needs from the first (api.hip topk_phase_a / _b)
+struct dae_topk_state {     // what the second half of a fused scoring call needs from the first (score.hip topk_phase_a / _b)
     bool valid = false;
     const dae_packed* pk = nullptr;
     dae_rowgeom g{};
-    int B = 0, k = 0, dtype = 0, S = 0, n_samp = 0, n_other = 0, n_valid_col = 0, nrank = 0;
-    int n_rank_tiles = 0;   // ceil(nrank / 32): the tiles the call walks (a prefix of the image's); 0 = nothing to rank
-    bool exact = false, fused = false, mixed = false, whole_b = false;
-    int64_t ld_s = 0;
+    int B = 0, k = 0;
+    dae_score_plan plan{};  // score_plan.h
     const int* order = nullptr;
     int* sample_cnt = nullptr;
-    // dae_score_topk_begin / _finish: arguments of the pending call
-    int pend_H = 0, pend_dtype = 0, pend_n_tracks = 0;
-    const float* pend_h32 = nullptr;
+    const float* pend_h32 = nullptr;   // dae_score_topk_begin / _finish: the fp32 hidden rows of the pending call
 };
 
 struct dae_ctx {
@@ -119,7 +112,6 @@ struct dae_ctx {
     dae_buf sample_top;        // [Bpad][k] (logit, idx) pairs
     dae_buf cand;              // [nb_rg][Bpad][cap] pairs
     dae_buf cand_cnt;          // [nb_rg][Bpad] int
-    dae_buf dense_tmp;         // unfused fallback logits
     dae_buf train_a, train_b, train_c, train_d;
     float* arm_m = nullptr; float* arm_v = nullptr; float arm_alpha = 0.f, arm_b1 = 0.f, arm_b2 = 0.f, arm_eps = 0.f;  // dae_arm_decoder_adam
     const float* mixT = nullptr; int64_t mix_ld = 0; const float* mix_w = nullptr; int mix_ncols = 0;   // dae_set_score_mix (caller-owned)
@@ -169,6 +161,7 @@ extern thread_local std::string g_dae_create_err;
 
 int dae_fail(dae_ctx* ctx, int code, const char* fmt, ...);
 int dae_reserve(dae_ctx* ctx, dae_buf& b, size_t bytes);
+int dae_ensure_guard(dae_ctx* ctx);       // ctx->guard: allocated and zeroed once (api.hip)
 
 #define DAE_HIP_CHECK(ctx, expr)                                                              \
     do {                                                                                      \
@@ -187,6 +180,7 @@ int dae_reserve(dae_ctx* ctx, dae_buf& b, size_t bytes);
     } while (0)
 
 static inline int dae_round_up(int x, int m) { return (x + m - 1) / m * m; }
+inline bool dae_known_dtype(int dtype) { return dtype == DAE_DTYPE_F32 || dtype == DAE_DTYPE_BF16 || dtype == DAE_DTYPE_BF16_EXACT; }
 
 inline bool dae_first_use(dae_ctx* ctx, const void* key) { return ctx->first_use_done.insert(key).second; }
 // before the first launch of `kernel` on this context: raise its dynamic-LDS limit (the kernel is its own first-use key)
@@ -196,7 +190,7 @@ inline hipError_t dae_lds_limit_once(dae_ctx* ctx, K* kernel, size_t bytes)
     const void* f = reinterpret_cast<const void*>(kernel);
     return dae_first_use(ctx, f) ? hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) : hipSuccess;
 }
-// a launch that can be the profiled one: when a pair of profile events is armed (dae_profile_*, api.hip) it takes the pair --
+// a launch that can be the profiled one: when a pair of profile events is armed (dae_profile_*: api.hip, score.hip) it takes the pair --
 // e0 / e1 are left alone otherwise -- and notes the kernel's name
 inline void dae_take_profile_events(dae_ctx* ctx, const char* kernel, hipEvent_t& e0, hipEvent_t& e1)
 {
@@ -305,12 +299,7 @@ int dae_launch_tile_band(dae_ctx* ctx, const int* order, int ntiles, int n_samp,
 int dae_launch_live_tiles(dae_ctx* ctx, const dae_packed& pk, const dae_rowgeom& g, int B, const int* list, int n_items,
                           const float* tau, int nrank, int* live_cnt, int* live_list, unsigned long long* stat);
 
-// decode_f32.hip: the host planners, and the launchers that choose between a hidden-256 kernel and the generic one
-dae_rowgeom dae_row_geometry(int B, int Hp);
-dae_rowgeom dae_row_geometry_bf16(int B, int Hp);
-int dae_filter_block_tiles(const dae_rowgeom& g, int n_items, int dtype, int Hp, bool mixed = false);
-bool dae_sample_wave_groups(const dae_rowgeom& g, int Hp, int n_samp);
-
+// decode_f32.hip: the launchers that choose between a hidden-256 kernel and the generic one (by the predicates of score_plan.h)
 struct dae_tileset {        // which wave tiles a decode launch walks
     int n_items;            // number of tiles in the set
     int stride;             // S
@@ -334,7 +323,6 @@ int dae_launch_decode_filter_f32(dae_ctx* ctx, const dae_rowgeom& g, int B, cons
                                  const float* tau, int n_valid_col, uint2* cand, int* cand_cnt,
                                  int cap, int dtype = DAE_DTYPE_F32, int bias_sel = 0, const int* live_cnt = nullptr,
                                  const int* live_list = nullptr);
-bool dae_filter_takes_live(const dae_rowgeom& g, int dtype, int Hp, bool mixed);    // does the filter launch run that kernel?
 // bias_sel (bf16 image prepacked with DAE_DTYPE_BF16_EXACT): 0 = b, 1 = b - eps (lower bounds), 2 = b + eps (upper bounds)
 
 int dae_launch_decode_scaled_T(dae_ctx* ctx, const dae_rowgeom& g, int B, const dae_tileset& ts, const float* row_scale,
@@ -403,7 +391,7 @@ int dae_launch_adam(dae_ctx* ctx, float* param, float* m, float* v, const float*
 int dae_launch_coo_to_csr(dae_ctx* ctx, const int64_t* positions, const float* values, int values_broadcast,
                           int64_t nnz, int n_rows, int n_cols, int32_t* row_ptr, int32_t* col, float* val,
                           int32_t* status);
-// a titled launch's intermediates (api.hip dae_title_prepare / dae_title_rank; device pointers, caller-owned)
+// a titled launch's intermediates (score.hip dae_title_prepare / dae_title_rank; device pointers, caller-owned)
 struct dae_title_bufs {
     int32_t *rp, *col, *srp, *sc;     // CSR of the feed [B + 1], [nnz]; seed lists [B + 1], [nnz]
     float *val, *h, *feat, *wt, *wp;  // values [nnz]; DAE hidden rows [B][H]; title features [B][ld_feat]; mixing weights [B]
@@ -450,7 +438,7 @@ int dae_launch_mix_scores(dae_ctx* ctx, const float* title_score, int64_t ld_t, 
 // mixexact.hip (DAE_DTYPE_BF16_EXACT under the title mix)
 int dae_launch_mix_title_bounds(dae_ctx* ctx, const float* W, const float* b, int H, int Hp, int col_lo, int col_hi,
                                 int ntiles, dae_packed& pk);
-void dae_note_plan(int R_TILE, int n_rg, int nb_rg, int n_samp, int n_filter, int ntiles);      // api.hip: what dae_last_plan reports
+void dae_note_plan(int R_TILE, int n_rg, int nb_rg, int n_samp, int n_filter, int ntiles);      // score.hip: what dae_last_plan reports
 int dae_mix_topk_exact_impl(dae_ctx* tc, dae_ctx* dc, const float* feat, int64_t ld_feat, const float* h, int64_t ld_h, int B,
                             const float* w_title, const float* w_playlist, int n_tracks, const int32_t* seed_row_ptr,
                             const int32_t* seed_col, int k, float* out_score, int32_t* out_idx);

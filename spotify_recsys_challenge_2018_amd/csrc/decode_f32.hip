@@ -3,7 +3,7 @@
 // :141-145 (untied), and on bf16 operands (v_mfma_f32_32x32x16_bf16).  Here: the kernels of the shipped shape, hidden =
 // 256 -- the two filter kernels (keep only (logit, column) pairs with logit >= tau[row]: the fused front half of the
 // top-500 ranking, main_challenge.py:28-36; nothing dense reaches HBM), the bf16 per-wave threshold sample, the two K5
-// training forwards from the row-major decoder --, the host planners, and the public launchers, which pass every other
+// training forwards from the row-major decoder -- and the public launchers (the host planners: score_plan.h), which pass every other
 // shape and the dense epilogue (the reference's y_pred, main_train.py:66) on to the generic kernel of decode_generic.hip.
 // The operand images all of them stream are built by prepack.hip.
 //
@@ -422,7 +422,7 @@ __global__ __launch_bounds__(256, 1) void decode_f32_h256_filter_kernel(const da
     const int bir = q * DAE_NUM_XCD + (rem_b % DAE_NUM_XCD);
 
     constexpr int n_h4 = RB * 64 * G;
-    // SKIPPED TILES (api.hip topk_phase_b, prepack.hip live_tiles_kernel): with live lists the row group walks the tiles of
+    // SKIPPED TILES (score.hip topk_phase_b, prepack.hip live_tiles_kernel): with live lists the row group walks the tiles of
     // p.ts whose logit bound reaches the smallest threshold of its rows -- live_cnt[rg] of them, in p.ts's order -- and R, rem,
     // split and item_at below follow that count.  A tile left out holds no logit >= tau[row] for any row of the group: the
     // epilogue would have dropped every element of it.  No live tile: the workgroup's candidate counts are zero, nothing else
@@ -1008,12 +1008,6 @@ __global__ __launch_bounds__(NW * 64, 1) void decode_bf16_h256_filter_kernel(con
 
 // (The variant with the hidden tile in REGISTERS for MFMA-bound batches measured slower and is not kept: profiles/r04_notes.md 6.)
 
-// the dedicated phase-B kernel: hidden = 256 (16 steps), 128-row groups
-bool bf16_fast_filter(const dae_rowgeom& g, int dtype, int G)
-{
-    return dtype == DAE_DTYPE_BF16 && G == 16 && g.waves == 4 && g.R_TILE == 128;
-}
-
 int fill_common(dae_ctx* ctx, const dae_rowgeom& g, int B, const dae_tileset& ts, dae_decp& p,
                 int dtype = DAE_DTYPE_F32, int bias_sel = 0)
 {
@@ -1042,48 +1036,7 @@ int fill_common(dae_ctx* ctx, const dae_rowgeom& g, int B, const dae_tileset& ts
 
 }  // namespace
 
-// most tiles one workgroup of the filter launch can walk (sizes its private candidate lists)
-int dae_filter_block_tiles(const dae_rowgeom& g, int n_items, int dtype, int Hp, bool mixed)
-{
-    const int n_ws = g.nb_rg * g.waves;
-    if (bf16_fast_filter(g, dtype, Hp / 16) && !mixed) {
-        const int n_ws8 = g.nb_rg * 8;                       // (decode_bf16_h256_filter_kernel<1, 4, 8, 8>: 8 waves, a tile each)
-        return 8 * ((n_items + n_ws8 - 1) / n_ws8);
-    }
-    return g.waves * ((n_items + n_ws - 1) / n_ws);
-}
-
-// Rows are cut into groups of R_TILE playlists whose hidden tile (R_TILE x Hp elements of `elt` bytes) stays in LDS.
-static dae_rowgeom row_geometry(int B, int Hp, int elt)
-{
-    dae_rowgeom g;
-    int rt = 128;
-    while (rt > 32 && (size_t)rt * Hp * elt > 128 * 1024) rt >>= 1;   // <= 128 KiB of LDS
-    while (rt > 32 && B <= rt / 2) rt >>= 1;                          // small batches
-    g.R_TILE = rt;
-    g.n_rg = (B + rt - 1) / rt;
-    g.Bpad = g.n_rg * rt;
-    int nb = (DAE_NUM_CU / g.n_rg) / DAE_NUM_XCD * DAE_NUM_XCD;
-    if (nb < DAE_NUM_XCD) nb = DAE_NUM_XCD;
-    g.nb_rg = nb;
-    g.grid = g.n_rg * nb;
-    g.waves = 4;
-    return g;
-}
-// fp32: one wave per SIMD -- with 4 independent accumulators it saturates the fp32 matrix pipe (two per SIMD measured
-// slower, profiles/r01_notes.md)
-dae_rowgeom dae_row_geometry(int B, int Hp) { return row_geometry(B, Hp, 4); }
-// bf16: 128-playlist tiles (64 KiB of LDS at H = 256).  256-playlist tiles fit LDS too but need 394 registers per wave,
-// which rules out the second wave per SIMD that hides the epilogue (and measured the same kernel time but a slower phase A).
-dae_rowgeom dae_row_geometry_bf16(int B, int Hp) { return row_geometry(B, Hp, 2); }
-
-// phase A with per-WAVE group maxima (decode_bf16_h256_wavemax_kernel): bf16 image of hidden 256, 128-row groups, and a sample
-// that gives each of the 8 wave slots per workgroup at least two tiles
-bool dae_sample_wave_groups(const dae_rowgeom& g, int Hp, int n_samp)
-{
-    return Hp == 256 && g.R_TILE == 128 && g.waves == 4 && n_samp >= 2 * g.nb_rg * 8;
-}
-
+// (which kernel a geometry takes: the predicates of score_plan.h, shared with the plan of a scoring call)
 int dae_launch_decode_dense_f32(dae_ctx* ctx, const dae_rowgeom& g, int B, const dae_tileset& ts,
                                 int apply_sigmoid, int mask_from_col, float* out, int64_t ld,
                                 int fill_pad, int dtype, float* gmax, int64_t ld_gmax, int gmax_per_wave, int bias_sel)
@@ -1176,12 +1129,6 @@ int dae_launch_decode_loss_f32(dae_ctx* ctx, const dae_rowgeom& g, int B, float 
     p.dz16 = (dtype == DAE_DTYPE_BF16 && dz16) ? 1 : 0;
     // (hidden 256 in 128-row groups takes the row-major K5 launches above: train.hip train_plan `rm`)
     return dae_launch_decode_generic(ctx, EPI_LOSS, dtype == DAE_DTYPE_BF16 ? DT_BF16 : DT_F32, g, p);
-}
-
-// the launch below runs decode_f32_h256_filter_kernel<0>, the one kernel that can walk live lists
-bool dae_filter_takes_live(const dae_rowgeom& g, int dtype, int Hp, bool mixed)
-{
-    return dtype == DAE_DTYPE_F32 && g.R_TILE == 128 && Hp / DAE_KG == 32 && g.waves == 4 && !mixed;
 }
 
 int dae_launch_decode_filter_f32(dae_ctx* ctx, const dae_rowgeom& g, int B, const dae_tileset& ts,

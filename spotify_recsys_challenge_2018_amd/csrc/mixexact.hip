@@ -1341,7 +1341,7 @@ int dae_mix_topk_exact_impl(dae_ctx* tc, dae_ctx* dc, const float* feat, int64_t
     p.samp = static_cast<float*>(tc->gmax.p); p.ld_s = ld_s;
     {
         // the sample pass on a grid of its own when other launches are in flight (round 6, as the plain path's sample launch:
-        // api.hip topk_phase_a): an eighth of the tiles does not need a workgroup on every CU -- ~8 items per wave slot; its
+        // score_plan.h dae_plan_topk): an eighth of the tiles does not need a workgroup on every CU -- ~8 items per wave slot; its
         // maxima are stored per ITEM, so the geometry changes nothing but where they are computed
         int nb_s = nb;
         if (tc->overlap_hint) {
@@ -1374,10 +1374,7 @@ int dae_mix_topk_exact_impl(dae_ctx* tc, dae_ctx* dc, const float* feat, int64_t
     DAE_CHECK_LAUNCH(tc, shipped ? "mix_bf16_kernel<filter>" : "mix_bf16_steps_kernel<filter>");
 
     // ---- refine + selection
-    if (!tc->guard.p) {
-        rc = dae_reserve(tc, tc->guard, DAE_GUARD_BYTES); if (rc) return rc;
-        DAE_HIP_CHECK(tc, hipMemsetAsync(tc->guard.p, 0, DAE_GUARD_BYTES, st));
-    }
+    rc = dae_ensure_guard(tc); if (rc) return rc;
     rc = dae_reserve(tc, tc->refined, (size_t)Bpad * MX_REF_CAP * sizeof(uint2) + (size_t)Bpad * sizeof(int)); if (rc) return rc;
     uint2* rf = static_cast<uint2*>(tc->refined.p);
     int* rf_cnt = reinterpret_cast<int*>(rf + (size_t)Bpad * MX_REF_CAP);

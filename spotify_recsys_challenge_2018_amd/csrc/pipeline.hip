@@ -270,11 +270,11 @@ int issue(dae_pipeline* p, Slot& S, int dtype)
     int32_t* const out_idx = S.d_idx;
     float* const out_score = p->want_scores ? S.d_score : L.d_score;     // (scores nobody fetches stay on the lane)
     if (S.titled) {
-        // main_challenge.py:80-90 with DAE_title: the whole titled launch in one library call (api.hip dae_title_score)
+        // main_challenge.py:80-90 with DAE_title: the whole titled launch in one library call (score.hip dae_title_score)
         const TitleW& t = p->tw;
         if (dtype == DAE_DTYPE_F32) { rc = ensure_f32(p, S.lane); if (rc) return rc; }
         // the half that does not depend on the lane's previous launch -- title features, CSR + seed lists, hidden rows, mixing
-        // weights -- on the prep stream (contexts of its own), the ranking on the lane (api.hip dae_title_prepare / _rank)
+        // weights -- on the prep stream (contexts of its own), the ranking on the lane (score.hip dae_title_prepare / _rank)
         dae_title_bufs tb;
         tb.rp = S.d_rp; tb.col = S.d_col; tb.srp = S.d_srp; tb.sc = S.d_scol; tb.val = S.d_cval;
         tb.h = S.t_h; tb.feat = S.t_feat; tb.wt = S.t_wt; tb.wp = S.t_wp;

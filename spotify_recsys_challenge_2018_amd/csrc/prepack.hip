@@ -138,7 +138,7 @@ __global__ __launch_bounds__(256) void prepack_tile_kernel(const float* __restri
     }
 }
 
-// ---- the live lists of the fp32 filter launch (api.hip topk_phase_b; hidden 256 in 128-row groups) ---------------------
+// ---- the live lists of the fp32 filter launch (score.hip topk_phase_b; hidden 256 in 128-row groups) ---------------------
 // One workgroup per row group rg.  From the group's packed hidden tile: d = max |h[r][k] - 0.5| over its rows r < B and the
 // units k < H (the zero padding of the tile is NOT read: it would give 0.5); from the thresholds the filter launch is given:
 // tau_rg = min over the same rows.  Item i of `list` is live unless U = A_t + d M_t < tau_rg (prepack_tile_kernel's bound:

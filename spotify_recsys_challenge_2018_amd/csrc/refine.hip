@@ -2,7 +2,7 @@
 // stored values into what the fp32 path would have computed -- or into "absent".
 //
 // The filter launch (decode_f32.hip, bias b + eps) leaves per (decode workgroup, row) lists of (u, column) where
-// u is an UPPER bound of the column's fp32 logit z32 with z32 >= u - 2 eps_c (api.hip decode_topk_core; the bound is
+// u is an UPPER bound of the column's fp32 logit z32 with z32 >= u - 2 eps_c (score.hip decode_topk_core; the bound is
 // derived next to exact_bounds_kernel).  One 512-thread workgroup per row:
 //   1. narrow: with need = k + n_seeds, the need-th largest u (to 20 key bits) minus 2 eps_max is a threshold tau'
 //      that `need` distinct columns provably reach in fp32, so a candidate with u < tau' cannot be among the k best
