@@ -486,7 +486,12 @@ int dae_set_train_dtype(dae_ctx* ctx, int dtype);
  * gradients.  Gradients are dense fp32 buffers the caller owns (overwritten).
  * cost_out: device scalar = mean_rows(L) + reg_lambda * l2 (DAEs.py:79-82/:147-150, :100).
  * A target row may hold any number of entries (one per column: the CSR contract), under every train dtype;
- * the same holds for dae_train_shard_decode. */
+ * the same holds for dae_train_shard_decode.
+ * 1 <= B <= 4096 rows, H % 32 == 0, H <= 1024.  A batch above 256 rows is walked in panels of 256 rows (and a shorter last
+ * one) by the decode side of the step -- loss, dL/dz, the decoder gradient and dh; DESIGN.md "Batches above 256 rows" --
+ * with the same meaning: cost = (1 / n_batch) sum over all B rows + lambda l2, every gradient the sum over all B rows, the
+ * dropout masks keyed by the row's index in the batch.  A batch of at most 256 rows is one panel: the launches it always
+ * made.  Scratch beyond [B, H]-sized buffers does not grow with B. */
 int dae_train_forward_backward(dae_ctx* ctx,
         const int32_t* x_row_ptr, const int32_t* x_col, const float* x_val,
         const int32_t* y_row_ptr, const int32_t* y_col, const float* y_val,
@@ -517,7 +522,9 @@ int dae_train_forward_backward(dae_ctx* ctx,
  * untied: gW_out = gW_dec_loc.  Adam is local: dae_adam_step on the owned rows.
  * The stages keep h / sigmoid in ctx scratch between calls: run them in order on one ctx.
  * With a single shard [0, V) the result equals dae_train_forward_backward up to fp32
- * re-association in the encoder sum. */
+ * re-association in the encoder sum.
+ * 1 <= B <= 4096 for all three stages, as for dae_train_forward_backward: stage "decode" walks the same 256-row panels
+ * (no exchange happens inside the stage), the other two run over all rows at once. */
 int dae_train_shard_encode(dae_ctx* ctx,
         const int32_t* x_row_ptr, const int32_t* x_col, const float* x_val,
         const float* W_enc_loc, int col_lo, int col_hi, int H, int B,
@@ -706,7 +713,10 @@ int dae_adam_rows_flush(dae_ctx* ctx, float* param, float* m, float* v, int32_t*
  * (which the call then writes through its const pointer), m and v are updated in place and gW_dec is not written
  * (it may be NULL).  The per-element operations are dae_adam_step's, so the parameters are bit-identical to writing
  * the gradient and calling dae_adam_step(W_dec, m, v, gW_dec, V*H, lr, ..., t); what disappears is one pass over the
- * gradient in each direction (1.2 GB -> 1.0 GB for Adam + the gradient at V = 170 000, H = 256).  m = NULL disarms. */
+ * gradient in each direction (1.2 GB -> 1.0 GB for Adam + the gradient at V = 170 000, H = 256).  m = NULL disarms.
+ * A batch above 256 rows applies the update in its LAST panel: the earlier panels leave their sum in a [V, H] scratch of the
+ * context, and the last one adds its tile to it in the order the unarmed step adds -- the bits stay those of "write gW_dec,
+ * then dae_adam_step" at every B. */
 int dae_arm_decoder_adam(dae_ctx* ctx, float* m, float* v, float lr, float beta1, float beta2, float eps, int t);
 
 /* on != 0: the untied gW_enc buffer handed to dae_train_forward_backward is all-zero on entry (kept so by

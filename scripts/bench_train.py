@@ -10,6 +10,8 @@ from spotify_recsys_challenge_2018_amd.models.DAEs import coo_to_csr
 from spotify_recsys_challenge_2018_amd.utils.synthetic import make_playlists, make_weights
 tied = "--tied" in sys.argv
 V, nt, H, B = 170000, 140000, 256, 256
+if "--batch" in sys.argv:              # rows per step (above 256: the step walks 256-row panels)
+    B = int(sys.argv[sys.argv.index("--batch") + 1])
 W_enc, b_enc, W_dec, b_dec = make_weights(V, H, seed=0, bias="zeros", n_tracks=nt, tied=tied)
 pos, ones, _ = make_playlists(B, nt, V - nt, seed=1, seed_counts=(20, 40, 66, 100))
 m = pos[:, 1] < nt

@@ -375,7 +375,7 @@ int dae_launch_grad_h(dae_ctx* ctx, const float* dzT, int64_t ldT, const float* 
 // grad_wdec.hip (K6).  dae_armed_adam: the dense TF1-Adam of the [V, H] tensor p that an armed K6 applies in its epilogue
 struct dae_armed_adam { float* p; float* m; float* v; float alpha, b1, b2, eps; };
 int dae_launch_k6(dae_ctx* ctx, const float* dzT, int64_t ldT, int dz16, const float* h, int H, int B, int V, float* gW,
-                  float* gb, const dae_armed_adam* arm, int small_v);
+                  float* gb, const dae_armed_adam* arm, int small_v, const float* gprev);
 int dae_launch_grad_w(dae_ctx* ctx, const float* dzT, int64_t ldT, const float* h, int H, int B, int V,
                       float* gW, float* gb);
 

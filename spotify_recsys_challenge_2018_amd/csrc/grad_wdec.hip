@@ -13,6 +13,10 @@ struct GwP {
     const float* h; int H, B, V;
     float* gW;                        // [V, H]
     float* gb;                        // [V] (written by the hc0 == 0 blocks) or null
+    // the ACC instances (a later 256-row panel of a longer batch, train.hip): the [V, H] gradient of the earlier panels, which the
+    // tile is added to (partial + tile, element by element) -- gW itself for the unarmed kernels, the context's scratch for the
+    // armed ones, which feed the sum to Adam; gb[v] then holds the earlier panels' column sums and has this panel's added
+    const float* gprev;
     int n_half, nb_half;              // H / 128 hidden halves, blocks per half
     // dense TF1-Adam of the [V, H] tensor `ad.p` applied in the epilogue instead of writing gW (dae_arm_decoder_adam); read by
     // the kernels that can be armed only: grad_wdec_kernel<4, 8, true> and the two t32 kernels
@@ -52,8 +56,11 @@ __device__ __forceinline__ void k6_fill_ht_bf16(uint4* ldsq, const GwP& p, int h
 // The armed pass of the two t32 kernels over a tile of 32 decoder rows: register reg of lane (n, hi) is decoder row
 // v0 + acc_row32(reg, hi), hidden hc0 + 4 n + a (a = the 4 accumulators).  Four groups of four rows through two buffers: group
 // g + 1 is requested before group g is updated and stored; group 0 is requested by the kernel before its MFMAs.
+// ACC: the earlier panels' gradient rows (p.gprev) travel with P / M / V -- requested a group ahead, like them.  A group's rows
+// are added into its accumulators (partial + tile) before the next group is requested, so one buffer of them is enough.
+template <bool ACC>
 struct K6AdamRows {
-    float4 P[2][4], M[2][4], V[2][4];
+    float4 P[2][4], M[2][4], V[2][4], G[ACC ? 4 : 1];
     size_t off[2][4];
     bool ok[2][4];
     __device__ __forceinline__ void issue(const GwP& p, int buf, int r4, int v0, int hi, int hcol)
@@ -66,13 +73,23 @@ struct K6AdamRows {
             P[buf][u] = nt_ld4(p.ad.p + off[buf][u]);
             M[buf][u] = nt_ld4(p.ad.m + off[buf][u]);
             V[buf][u] = nt_ld4(p.ad.v + off[buf][u]);
+            if (ACC) G[ACC ? u : 0] = nt_ld4(p.gprev + off[buf][u]);
         }
     }
-    __device__ __forceinline__ void pass(const GwP& p, const f32x16 (&acc)[4], int v0, int hi, int hcol)
+    __device__ __forceinline__ void pass(const GwP& p, f32x16 (&acc)[4], int v0, int hi, int hcol)
     {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const int cb = g & 1;
+            if (ACC) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const float4 g0 = G[ACC ? u : 0];
+                    const int reg = 4 * g + u;
+                    acc[0][reg] = g0.x + acc[0][reg]; acc[1][reg] = g0.y + acc[1][reg];
+                    acc[2][reg] = g0.z + acc[2][reg]; acc[3][reg] = g0.w + acc[3][reg];
+                }
+            }
             if (g + 1 < 4) issue(p, cb ^ 1, 4 * (g + 1), v0, hi, hcol);
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -96,8 +113,10 @@ struct K6AdamRows {
 // D[i = hidden][j = vocabulary row].  Loads, LDS image and column sums are unchanged; what changes is that a lane of the
 // accumulators is a hidden unit (hc0 + 4 j + a), so the epilogue writes 512 contiguous bytes of one gW row per half-wave
 // instead of 16-byte pieces of 32 rows -- the same shape the transposed bf16 kernel (grad_wdec_t_kernel) has.
-template <int NA, int NW = 4, bool TR = false>
-__global__ __launch_bounds__(NW * 64, 1) void grad_wdec_kernel(const GwP p)
+// ACC: the tile is added to the earlier panels' gradient at p.gprev (see GwP).  Each of the four kernels is a body with the ACC
+// switch and two entry points: the kernel a batch of at most 256 rows has always launched, and its _acc twin for a later panel.
+template <int NA, int NW, bool TR, bool ACC>
+__device__ __forceinline__ void grad_wdec_body(const GwP& p)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];     // [Bp][32*NA] floats
     constexpr int HW = 32 * NA;
@@ -228,7 +247,7 @@ __global__ __launch_bounds__(NW * 64, 1) void grad_wdec_kernel(const GwP p)
                         // the gradient tile goes straight into the Adam update of its parameters: W / m / v are read and
                         // written in place, gW never reaches memory (7 passes over the tensor + 1 of the gradient become 6).
                         // 12 loads, compute, 12 stores per group of four rows.
-                        float4 pp[4], mm[4], vv[4];
+                        float4 pp[4], mm[4], vv[4], gp[ACC ? 4 : 1];
 #pragma unroll
                         for (int u = 0; u < 4; ++u) {
                             const int v = v0 + 2 * acc_row32(r4 + u, hi) + b;
@@ -236,15 +255,19 @@ __global__ __launch_bounds__(NW * 64, 1) void grad_wdec_kernel(const GwP p)
                             pp[u] = nt_ld4(p.ad.p + o);
                             mm[u] = nt_ld4(p.ad.m + o);
                             vv[u] = nt_ld4(p.ad.v + o);
+                            if (ACC) gp[ACC ? u : 0] = nt_ld4(p.gprev + o);
                         }
 #pragma unroll
                         for (int u = 0; u < 4; ++u) {
                             const int reg = r4 + u;
                             const int v = v0 + 2 * acc_row32(reg, hi) + b;
                             const size_t o = (size_t)(v < p.V ? v : 0) * p.H + hc0 + 4 * j;
-                            dae_adam_el4(pp[u], mm[u], vv[u],
-                                         make_float4(acc[0][b][reg], acc[1 % NA][b][reg], acc[2 % NA][b][reg], acc[3 % NA][b][reg]),
-                                         p.ad.alpha, p.ad.b1, p.ad.b2, p.ad.eps);
+                            float4 gg = make_float4(acc[0][b][reg], acc[1 % NA][b][reg], acc[2 % NA][b][reg], acc[3 % NA][b][reg]);
+                            if (ACC) {
+                                const float4 g0 = gp[ACC ? u : 0];
+                                gg = make_float4(g0.x + gg.x, g0.y + gg.y, g0.z + gg.z, g0.w + gg.w);
+                            }
+                            dae_adam_el4(pp[u], mm[u], vv[u], gg, p.ad.alpha, p.ad.b1, p.ad.b2, p.ad.eps);
                             if (v < p.V) {
                                 nt_st4(p.ad.p + o, pp[u]);
                                 nt_st4(p.ad.m + o, mm[u]);
@@ -252,13 +275,25 @@ __global__ __launch_bounds__(NW * 64, 1) void grad_wdec_kernel(const GwP p)
                             }
                         }
                     } else {
+                        float4 gp[ACC ? 4 : 1];
+                        if (ACC) {                      // the four rows' earlier sums first, then the four stores
+#pragma unroll
+                            for (int u = 0; u < 4; ++u) {
+                                const int v = v0 + 2 * acc_row32(r4 + u, hi) + b;
+                                gp[ACC ? u : 0] = *reinterpret_cast<const float4*>(p.gprev + (size_t)(v < p.V ? v : 0) * p.H + hc0 + 4 * j);
+                            }
+                        }
 #pragma unroll
                         for (int u = 0; u < 4; ++u) {
                             const int reg = r4 + u;
                             const int v = v0 + 2 * acc_row32(reg, hi) + b;
                             if (v >= p.V) continue;
-                            *reinterpret_cast<float4*>(p.gW + (size_t)v * p.H + hc0 + 4 * j) =
-                                make_float4(acc[0][b][reg], acc[1 % NA][b][reg], acc[2 % NA][b][reg], acc[3 % NA][b][reg]);
+                            float4 gg = make_float4(acc[0][b][reg], acc[1 % NA][b][reg], acc[2 % NA][b][reg], acc[3 % NA][b][reg]);
+                            if (ACC) {
+                                const float4 g0 = gp[ACC ? u : 0];
+                                gg = make_float4(g0.x + gg.x, g0.y + gg.y, g0.z + gg.z, g0.w + gg.w);
+                            }
+                            *reinterpret_cast<float4*>(p.gW + (size_t)v * p.H + hc0 + 4 * j) = gg;
                         }
                     }
                 }
@@ -269,15 +304,20 @@ __global__ __launch_bounds__(NW * 64, 1) void grad_wdec_kernel(const GwP p)
             const int v = vcol + b;
             if (v >= p.V) continue;
             float* orow = p.gW + (size_t)v * p.H + hc0;
+            const float* prow = p.gprev + (size_t)v * p.H + hc0;          // (read under ACC only)
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
                 const int i_idx = acc_row32(reg, hi);
                 if (NA == 4) {
-                    *reinterpret_cast<float4*>(orow + 4 * i_idx) =
-                        make_float4(acc[0][b][reg], acc[1 % NA][b][reg], acc[2 % NA][b][reg], acc[3 % NA][b][reg]);
+                    float4 gg = make_float4(acc[0][b][reg], acc[1 % NA][b][reg], acc[2 % NA][b][reg], acc[3 % NA][b][reg]);
+                    if (ACC) {
+                        const float4 g0 = *reinterpret_cast<const float4*>(prow + 4 * i_idx);
+                        gg = make_float4(g0.x + gg.x, g0.y + gg.y, g0.z + gg.z, g0.w + gg.w);
+                    }
+                    *reinterpret_cast<float4*>(orow + 4 * i_idx) = gg;
                 } else {
 #pragma unroll
-                    for (int a = 0; a < NA; ++a) orow[NA * i_idx + a] = acc[a][b][reg];
+                    for (int a = 0; a < NA; ++a) orow[NA * i_idx + a] = ACC ? prow[NA * i_idx + a] + acc[a][b][reg] : acc[a][b][reg];
                 }
             }
         }
@@ -285,8 +325,8 @@ __global__ __launch_bounds__(NW * 64, 1) void grad_wdec_kernel(const GwP p)
             cs0 += __shfl_xor(cs0, 32);
             cs1 += __shfl_xor(cs1, 32);
             if (hi == 0) {
-                if (ok0) p.gb[vcol] = cs0;
-                if (ok1) p.gb[vcol + 1] = cs1;
+                if (ok0) p.gb[vcol] = ACC ? p.gb[vcol] + cs0 : cs0;
+                if (ok1) p.gb[vcol + 1] = ACC ? p.gb[vcol + 1] + cs1 : cs1;
             }
         }
     }
@@ -303,8 +343,8 @@ __global__ __launch_bounds__(NW * 64, 1) void grad_wdec_kernel(const GwP p)
 //     the armed Adam update (dae_arm_decoder_adam) reads and writes W / m / v with the same shape.
 // LDS holds h^T for the workgroup's 128 hidden units as bf16 B fragments in operand order: 4 KB per k-step of 16
 // playlists, 64 KB at B = 256.  gb = dz^T 1 comes out of the matrix pipe as well (a ones fragment as B operand).
-template <int NW, bool FULL = false>
-__global__ __launch_bounds__(NW * 64, 1) void grad_wdec_t_kernel(const GwP p)
+template <int NW, bool FULL, bool ACC>
+__device__ __forceinline__ void grad_wdec_t_body(const GwP& p)
 {
     extern __shared__ __attribute__((aligned(16))) uint4 ldsq[];      // [S][4][64] B fragments
     const int tid = threadIdx.x, lane = tid & 63, hi = lane >> 5, n = lane & 31;
@@ -375,11 +415,34 @@ __global__ __launch_bounds__(NW * 64, 1) void grad_wdec_t_kernel(const GwP p)
 #pragma unroll
                 for (int reg = 0; reg < 16; ++reg) {
                     const int v = v0 + 32 * m + acc_row32(reg, hi);
-                    if (v < p.V) p.gb[v] = accg[m][reg];
+                    if (v < p.V) p.gb[v] = ACC ? p.gb[v] + accg[m][reg] : accg[m][reg];
                 }
         }
         // lane n holds hidden units hc0 + 4 n + a (a = the 4 accumulators of a register), register reg the row
         // v0 + 32 m + acc_row32(reg, hi): one float4 per (m, reg), 512 contiguous bytes per half-wave
+        if (ACC) {
+            // the earlier panels' rows four at a time (the dz^T ring's registers are free by now), then their four stores
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+#pragma unroll
+                for (int r4 = 0; r4 < 16; r4 += 4) {
+                    float4 gp[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const int v = v0 + 32 * m + acc_row32(r4 + u, hi);
+                        gp[u] = *reinterpret_cast<const float4*>(p.gprev + (size_t)(v < p.V ? v : 0) * p.H + hc0 + 4 * n);
+                    }
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const int reg = r4 + u;
+                        const int v = v0 + 32 * m + acc_row32(reg, hi);
+                        if (v < p.V)
+                            *reinterpret_cast<float4*>(p.gW + (size_t)v * p.H + hc0 + 4 * n) =
+                                make_float4(gp[u].x + acc[m][0][reg], gp[u].y + acc[m][1][reg], gp[u].z + acc[m][2][reg],
+                                            gp[u].w + acc[m][3][reg]);
+                    }
+                }
+        } else
 #pragma unroll
         for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -400,8 +463,8 @@ __global__ __launch_bounds__(NW * 64, 1) void grad_wdec_t_kernel(const GwP p)
 // streams: the first group of p / m / v rows of a tile is requested BEFORE its MFMAs (under which it arrives), and inside the Adam
 // pass group g + 1 is requested before group g is computed and stored (two buffers).  Same operands, same k order per
 // element, same update operations as above: the parameters stay bit-identical to dense Adam.
-template <int NW, bool FULL>
-__global__ __launch_bounds__(NW * 64, 1) void grad_wdec_t32_kernel(const GwP p)
+template <int NW, bool FULL, bool ACC>
+__device__ __forceinline__ void grad_wdec_t32_body(const GwP& p)
 {
     extern __shared__ __attribute__((aligned(16))) uint4 ldsq[];      // [S][4][64] B fragments
     const int tid = threadIdx.x, lane = tid & 63, hi = lane >> 5, n = lane & 31;
@@ -431,7 +494,7 @@ __global__ __launch_bounds__(NW * 64, 1) void grad_wdec_t32_kernel(const GwP p)
         uint4 qa[RING];
 #pragma unroll
         for (int u = 0; u < RING; ++u) qa[u] = *reinterpret_cast<const uint4*>(ra + 16 * ((FULL || u < S) ? u : S - 1));
-        K6AdamRows ad;
+        K6AdamRows<ACC> ad;
         ad.issue(p, 0, 0, v0, hi, hc0 + 4 * n);                         // group 0 arrives under the MFMAs
         // (S == 16 -- a batch of 241 .. 256 -- is a template case: with the wave-uniform `s_ < S` tests in the loop hipcc ends every
         // step on s_waitcnt vmcnt(0), i.e. on the ring slot it has just requested: 16 memory round trips per tile instead of a ring)
@@ -458,7 +521,7 @@ __global__ __launch_bounds__(NW * 64, 1) void grad_wdec_t32_kernel(const GwP p)
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
                 const int v = v0 + acc_row32(reg, hi);
-                if (v < p.V) p.gb[v] = accg[reg];
+                if (v < p.V) p.gb[v] = ACC ? p.gb[v] + accg[reg] : accg[reg];
             }
         }
         ad.pass(p, acc, v0, hi, hc0 + 4 * n);
@@ -472,8 +535,8 @@ __global__ __launch_bounds__(NW * 64, 1) void grad_wdec_t32_kernel(const GwP p)
 // group of p / m / v rows requested before the MFMAs, group g + 1 before group g is computed.  The generic kernel it replaces
 // for this case (grad_wdec_kernel<4, 8, true>) ran its two phases back to back at 12 KB in flight per wave: 349 us
 // for 180 us of matrix work and 1.22 GB.
-template <int NW, bool FULL>
-__global__ __launch_bounds__(NW * 64, 1) void grad_wdec_t32_f32_kernel(const GwP p)
+template <int NW, bool FULL, bool ACC>
+__device__ __forceinline__ void grad_wdec_t32_f32_body(const GwP& p)
 {
     extern __shared__ __attribute__((aligned(16))) float4 ldsf[];     // [Bp / 2 k-steps][64 lanes]: h[2 g + hi][hc0 + 4 n .. + 3]
     const int tid = threadIdx.x, lane = tid & 63, hi = lane >> 5, n = lane & 31;
@@ -509,7 +572,7 @@ __global__ __launch_bounds__(NW * 64, 1) void grad_wdec_t32_f32_kernel(const GwP
         float4 qa[RING];
 #pragma unroll
         for (int u = 0; u < RING; ++u) qa[u] = ra[(FULL || u < Q) ? u : Q - 1];
-        K6AdamRows ad;
+        K6AdamRows<ACC> ad;
         ad.issue(p, 0, 0, v0, hi, hc0 + 4 * n);                         // group 0 arrives under the 512 MFMAs
         const int q_end = FULL ? 64 : Q;
         for (int q0 = 0; q0 < q_end; q0 += RING) {
@@ -537,25 +600,46 @@ __global__ __launch_bounds__(NW * 64, 1) void grad_wdec_t32_f32_kernel(const GwP
             }
         }
         cs += __shfl_xor(cs, 32);                                      // the two lane halves hold the even / odd playlists of the row
-        if (p.gb && half == 0 && hi == 0 && va < p.V) p.gb[va] = cs;
+        if (p.gb && half == 0 && hi == 0 && va < p.V) p.gb[va] = ACC ? p.gb[va] + cs : cs;
         ad.pass(p, acc, v0, hi, hc0 + 4 * n);
     }
 #undef K6F_SEL
 }
+
+// the entry points: <...>_kernel as ever, <...>_acc_kernel for a later panel
+template <int NA, int NW = 4, bool TR = false>
+__global__ __launch_bounds__(NW * 64, 1) void grad_wdec_kernel(const GwP p) { grad_wdec_body<NA, NW, TR, false>(p); }
+template <int NA, int NW = 4, bool TR = false>
+__global__ __launch_bounds__(NW * 64, 1) void grad_wdec_acc_kernel(const GwP p) { grad_wdec_body<NA, NW, TR, true>(p); }
+template <int NW, bool FULL = false>
+__global__ __launch_bounds__(NW * 64, 1) void grad_wdec_t_kernel(const GwP p) { grad_wdec_t_body<NW, FULL, false>(p); }
+template <int NW, bool FULL = false>
+__global__ __launch_bounds__(NW * 64, 1) void grad_wdec_t_acc_kernel(const GwP p) { grad_wdec_t_body<NW, FULL, true>(p); }
+template <int NW, bool FULL>
+__global__ __launch_bounds__(NW * 64, 1) void grad_wdec_t32_kernel(const GwP p) { grad_wdec_t32_body<NW, FULL, false>(p); }
+template <int NW, bool FULL>
+__global__ __launch_bounds__(NW * 64, 1) void grad_wdec_t32_acc_kernel(const GwP p) { grad_wdec_t32_body<NW, FULL, true>(p); }
+template <int NW, bool FULL>
+__global__ __launch_bounds__(NW * 64, 1) void grad_wdec_t32_f32_kernel(const GwP p) { grad_wdec_t32_f32_body<NW, FULL, false>(p); }
+template <int NW, bool FULL>
+__global__ __launch_bounds__(NW * 64, 1) void grad_wdec_t32_f32_acc_kernel(const GwP p) { grad_wdec_t32_f32_body<NW, FULL, true>(p); }
 
 }  // namespace
 
 // K6 on caller-provided buffers: gW[v, :] = sum_r dzT[v, r] h[r, :] and gb[v] = sum_r dzT[v, r] (gb nullable), or, with `arm`,
 // the Adam update of arm->p from that gradient (gW is not touched).  H % 32 == 0, B <= 256; dz16: dz^T holds bf16 (H % 128 == 0).
 // small_v: the caller's V is a few tiles (the title scorer's output layer): the 4-wave untransposed form, as it always took.
+// gprev: null, or the [V, H] gradient of the earlier panels of a batch above 256 rows (train.hip): the tile is added to it, gW
+// (or the armed update) takes the sum, and gb has this panel's column sums added to what it holds.
 int dae_launch_k6(dae_ctx* ctx, const float* dzT, int64_t ldT, int dz16, const float* h, int H, int B, int V, float* gW,
-                  float* gb, const dae_armed_adam* arm, int small_v)
+                  float* gb, const dae_armed_adam* arm, int small_v, const float* gprev)
 {
     if ((H % 32) != 0 || B < 1 || B > 256) return dae_fail(ctx, DAE_ERR_ARG, "grad_w: H=%d B=%d unsupported", H, B);
     const int NA = (H % 128) == 0 ? 4 : ((H % 64) == 0 ? 2 : 1);
     if ((arm || dz16) && NA != 4) return dae_fail(ctx, DAE_ERR_ARG, "grad_w: armed Adam / bf16 dz^T need H %% 128 == 0 (H=%d)", H);
+    if (gprev && small_v) return dae_fail(ctx, DAE_ERR_ARG, "grad_w: no accumulation in the small-V form");
     GwP p;
-    p.dzT = dzT; p.ldT = ldT; p.h = h; p.H = H; p.B = B; p.V = V; p.gW = gW; p.gb = gb;
+    p.dzT = dzT; p.ldT = ldT; p.h = h; p.H = H; p.B = B; p.V = V; p.gW = gW; p.gb = gb; p.gprev = gprev;
     p.ad = arm ? *arm : dae_armed_adam{nullptr, nullptr, nullptr, 0.0f, 0.0f, 0.0f, 0.0f};
     p.n_half = H / (32 * NA);
     int nb = (DAE_NUM_CU / p.n_half) / DAE_NUM_XCD * DAE_NUM_XCD;
@@ -577,7 +661,29 @@ int dae_launch_k6(dae_ctx* ctx, const float* dzT, int64_t ldT, int dz16, const f
     //   fp32   yes    yes       yes / no      grad_wdec_t32_f32_kernel<8, true / false>
     //   fp32   yes    no        any           grad_wdec_kernel<4, 8, true>, armed
     //   fp32   no     any       any           grad_wdec_kernel<4, 8, true> (H % 128 == 0), <2> or <1>;  small_v: <4>, <2> or <1>
-    if (dz16 && arm) {
+    //   gprev (a later panel of a batch above 256 rows): the same choice among the _acc twins; never with small_v
+    if (gprev) {
+        if (dz16 && arm) {
+            DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &grad_wdec_t32_acc_kernel<8, true>, 64 * 1024));
+            DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &grad_wdec_t32_acc_kernel<8, false>, 64 * 1024));
+            if (full) hipLaunchKernelGGL((grad_wdec_t32_acc_kernel<8, true>), grid, w8, lds_t, st, p);
+            else hipLaunchKernelGGL((grad_wdec_t32_acc_kernel<8, false>), grid, w8, lds_t, st, p);
+        } else if (dz16) {
+            DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &grad_wdec_t_acc_kernel<8, true>, 64 * 1024));
+            DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &grad_wdec_t_acc_kernel<8>, 160 * 1024));
+            if (full) hipLaunchKernelGGL((grad_wdec_t_acc_kernel<8, true>), grid, w8, lds_t, st, p);
+            else hipLaunchKernelGGL((grad_wdec_t_acc_kernel<8>), grid, w8, lds_t, st, p);
+        } else if (arm && H == 256) {
+            DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &grad_wdec_t32_f32_acc_kernel<8, true>, 128 * 1024));
+            DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &grad_wdec_t32_f32_acc_kernel<8, false>, 128 * 1024));
+            if (full) hipLaunchKernelGGL((grad_wdec_t32_f32_acc_kernel<8, true>), grid, w8, lds_f, st, p);
+            else hipLaunchKernelGGL((grad_wdec_t32_f32_acc_kernel<8, false>), grid, w8, lds_f, st, p);
+        } else if (NA == 4) {
+            DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &grad_wdec_acc_kernel<4, 8, true>, 160 * 1024));
+            hipLaunchKernelGGL((grad_wdec_acc_kernel<4, 8, true>), grid, w8, lds, st, p);
+        } else if (NA == 2) hipLaunchKernelGGL(grad_wdec_acc_kernel<2>, grid, w4, lds, st, p);
+        else hipLaunchKernelGGL(grad_wdec_acc_kernel<1>, grid, w4, lds, st, p);
+    } else if (dz16 && arm) {
         DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &grad_wdec_t32_kernel<8, true>, 64 * 1024));
         DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &grad_wdec_t32_kernel<8, false>, 64 * 1024));
         if (full) hipLaunchKernelGGL((grad_wdec_t32_kernel<8, true>), grid, w8, lds_t, st, p);
@@ -609,5 +715,5 @@ int dae_launch_k6(dae_ctx* ctx, const float* dzT, int64_t ldT, int dz16, const f
 int dae_launch_grad_w(dae_ctx* ctx, const float* dzT, int64_t ldT, const float* h, int H, int B, int V,
                       float* gW, float* gb)
 {
-    return dae_launch_k6(ctx, dzT, ldT, 0, h, H, B, V, gW, gb, nullptr, 1);
+    return dae_launch_k6(ctx, dzT, ldT, 0, h, H, B, V, gW, gb, nullptr, 1, nullptr);
 }

@@ -604,24 +604,41 @@ int launch_k7(dae_ctx* ctx, const float* dzT, int64_t ldT, int dz16, const float
     return DAE_OK;
 }
 
-// scratch carved for one training step over a [Vl, H] weight (shard) and B rows; stable for a given
-// (Vl, H, B), so the stages of a sharded step find h / sg where the earlier stage left them
-struct TrainPlan {
+// ---- batches above 256 rows: panels ----------------------------------------------------------------------------------------
+// K5, the positives' fix-up, K7 and K6 hold a batch of at most TRAIN_PANEL rows (K6's LDS image of h, the [V, 256] dz^T).  A longer
+// batch is cut into panels of TRAIN_PANEL rows and a shorter last one; each panel runs those launches as a batch of its own rows
+// would, on h + r0 H, y_row_ptr + r0 (the offsets stay absolute) and the same dz^T scratch.  What is a sum over rows crosses the
+// panels: K6 of a later panel adds its tile to the gradient the earlier ones left (grad_wdec.hip ACC), the loss partials of all
+// panels lie side by side for finish_cost_kernel, and dh's partials are reduced per panel into the panel's rows of dpre (or of
+// the shard's dh).  Encode / activate, the encoder backward, the lambda terms and the cost run once, over all rows: the dropout
+// masks are keyed by the row's index in the batch and no kernel that draws them sees a panel.
+constexpr int TRAIN_PANEL = 256;
+constexpr int TRAIN_MAX_B = 4096;
+
+// what the launches of one batch (or panel) of B <= TRAIN_PANEL rows are: which K5, dz^T's type and row pitch, K7's split
+struct TrainShape {
     int G, RB, Bpad64, n_chunk, n_fix, dtype, dz16, rm;
     K7Plan k7;          // (k7.n_chunk: K7's own launch; n_chunk: the partials of dh the step leaves, whoever wrote them)
     int fuse_dh;        // K5 leaves dh's partials itself (decode_f32.hip decode_loss_dh_bf16_kernel): no K7; n_chunk = g.grid + 1
     dae_rowgeom g;
-    size_t bh, hp_bytes;
-    float *dzT, *hbuf, *sg, *dpre, *part, *loss_part;
-    double* l2_part;
+    size_t hp_bytes;
 };
 
-int train_plan(dae_ctx* ctx, int Vl, int H, int B, TrainPlan& t)
+// scratch carved for one training step over a [Vl, H] weight (shard) and B rows; stable for a given
+// (Vl, H, B), so the stages of a sharded step find h / sg where the earlier stage left them.
+// B > TRAIN_PANEL: the TrainShape part is that of a full panel, `last` that of the last one; hbuf / sg / dpre hold all B rows,
+// part one panel's partials, loss_part every panel's (n_loss of them); train_panel() is the plan of one panel.
+struct TrainPlan : TrainShape {
+    size_t bh;
+    float *dzT, *hbuf, *sg, *dpre, *part, *loss_part;
+    double* l2_part;
+    int B, H, n_panel, n_loss;
+    TrainShape last;
+};
+
+TrainShape train_shape(dae_ctx* ctx, int Vl, int H, int B)
 {
-    if ((H % 32) != 0) return dae_fail(ctx, DAE_ERR_ARG, "training kernels need H %% 32 == 0 (H=%d)", H);
-    if (B < 1 || B > 256) return dae_fail(ctx, DAE_ERR_ARG, "training batch %d outside [1, 256]", B);
-    if (Vl < 1) return dae_fail(ctx, DAE_ERR_ARG, "empty vocabulary shard");
-    int rc;
+    TrainShape t;
     const int Hp = dae_round_up(H, DAE_HPAD);
     t.dtype = ctx->train_dtype;
     // bf16 GEMMs with the 4-tile backward kernels: dL/dz itself is stored as bf16
@@ -633,38 +650,74 @@ int train_plan(dae_ctx* ctx, int Vl, int H, int B, TrainPlan& t)
     t.rm = (H == 256 && t.g.R_TILE == 128 && t.g.waves == 4) ? 1 : 0;
     t.Bpad64 = (B + 63) / 64 * 64;
     t.hp_bytes = (size_t)t.g.n_rg * t.G * t.RB * 64 * sizeof(float4);
-    if ((rc = dae_reserve(ctx, ctx->h_packed, t.hp_bytes))) return rc;
-    if ((rc = dae_reserve(ctx, ctx->train_b, (size_t)Vl * t.Bpad64 * sizeof(float)))) return rc;
     t.k7 = k7_plan(Vl, H, t.Bpad64);
     t.n_chunk = t.k7.n_chunk;
     {   // bf16 GEMMs with dz^T as bf16 at hidden 256: dh comes out of the forward launch, one partial per workgroup + the positives'
         t.fuse_dh = (t.rm && t.dtype == DAE_DTYPE_BF16 && t.dz16) ? 1 : 0;
         if (t.fuse_dh) t.n_chunk = t.g.grid + 1;
     }
-    t.bh = (size_t)B * H;
     t.n_fix = B;                                   // loss partials of the positives: one per row
-    const size_t c_floats = 3 * t.bh + (size_t)t.n_chunk * t.Bpad64 * H + (size_t)t.g.grid + t.n_fix + 64;
+    return t;
+}
+
+int train_plan(dae_ctx* ctx, int Vl, int H, int B, TrainPlan& t)
+{
+    if ((H % 32) != 0) return dae_fail(ctx, DAE_ERR_ARG, "training kernels need H %% 32 == 0 (H=%d)", H);
+    if (B < 1 || B > TRAIN_MAX_B) return dae_fail(ctx, DAE_ERR_ARG, "training batch %d outside [1, %d]", B, TRAIN_MAX_B);
+    if (Vl < 1) return dae_fail(ctx, DAE_ERR_ARG, "empty vocabulary shard");
+    int rc;
+    t.B = B; t.H = H;
+    t.n_panel = (B + TRAIN_PANEL - 1) / TRAIN_PANEL;
+    static_cast<TrainShape&>(t) = train_shape(ctx, Vl, H, t.n_panel > 1 ? TRAIN_PANEL : B);
+    t.last = t.n_panel > 1 ? train_shape(ctx, Vl, H, B - (t.n_panel - 1) * TRAIN_PANEL) : static_cast<const TrainShape&>(t);
+    const int ld_dz = t.n_panel > 1 ? TRAIN_PANEL : t.Bpad64;
+    if ((rc = dae_reserve(ctx, ctx->h_packed, t.hp_bytes > t.last.hp_bytes ? t.hp_bytes : t.last.hp_bytes))) return rc;
+    if ((rc = dae_reserve(ctx, ctx->train_b, (size_t)Vl * ld_dz * sizeof(float)))) return rc;
+    t.bh = (size_t)B * H;
+    size_t part_floats = (size_t)t.n_chunk * t.Bpad64 * H;
+    if ((size_t)t.last.n_chunk * t.last.Bpad64 * H > part_floats) part_floats = (size_t)t.last.n_chunk * t.last.Bpad64 * H;
+    t.n_loss = (t.n_panel - 1) * (t.g.grid + t.n_fix) + t.last.g.grid + t.last.n_fix;
+    const size_t c_floats = 3 * t.bh + part_floats + (size_t)t.n_loss + 64;
     if ((rc = dae_reserve(ctx, ctx->train_c, c_floats * sizeof(float) + 4096 * sizeof(double)))) return rc;
     t.dzT = static_cast<float*>(ctx->train_b.p);
     t.hbuf = static_cast<float*>(ctx->train_c.p);
     t.sg = t.hbuf + t.bh;
     t.dpre = t.sg + t.bh;
     t.part = t.dpre + t.bh;
-    t.loss_part = t.part + (size_t)t.n_chunk * t.Bpad64 * H;
+    t.loss_part = t.part + part_floats;
     t.l2_part = reinterpret_cast<double*>(
-        (reinterpret_cast<uintptr_t>(t.loss_part + t.g.grid + t.n_fix) + 63) & ~(uintptr_t)63);
+        (reinterpret_cast<uintptr_t>(t.loss_part + t.n_loss) + 63) & ~(uintptr_t)63);
     return DAE_OK;
 }
 
-// K5 loss/dz over the prepacked decoder image + the positives' fix-up -> K6 (gW, gb) -> K7 partials of dh.
-// h (row-major in t.hbuf and tiled in ctx->h_packed) and ctx->pk_f32 must be current.
-int train_decode_backward(dae_ctx* ctx, const TrainPlan& t, int Vl, int H, int B, int n_batch,
-                          const int32_t* y_row_ptr, const int32_t* y_col, const float* y_val,
-                          int col_lo, int col_hi, const float* Wd, const float* b_dec, float* gWd, float* gb_dec)
+// the plan of panel i (rows [i TRAIN_PANEL, ...)) of a step: its own shape, its rows of hbuf / sg / dpre, its loss partials
+TrainPlan train_panel(const TrainPlan& t, int i)
+{
+    if (t.n_panel == 1) return t;
+    TrainPlan p = t;
+    const int r0 = i * TRAIN_PANEL;
+    if (i == t.n_panel - 1) static_cast<TrainShape&>(p) = t.last;
+    p.B = i == t.n_panel - 1 ? t.B - r0 : TRAIN_PANEL;
+    p.bh = (size_t)p.B * t.H;
+    p.hbuf += (size_t)r0 * t.H; p.sg += (size_t)r0 * t.H; p.dpre += (size_t)r0 * t.H;
+    p.loss_part += (size_t)i * (t.g.grid + t.n_fix);
+    p.n_loss = p.g.grid + p.n_fix;
+    p.n_panel = 1;
+    return p;
+}
+
+// One panel (a whole batch of at most TRAIN_PANEL rows is its only panel): K5 loss/dz over the prepacked decoder image + the
+// positives' fix-up -> K6 (gW, gb) -> K7 partials of dh.  t: the panel's plan; h (row-major in t.hbuf and tiled in ctx->h_packed)
+// and ctx->pk_f32 must be current.  arm: the step is armed (dae_arm_decoder_adam).  first / last: the panel's place in the step.
+// A later panel adds to the gradient of the earlier ones; the armed update belongs to the last panel, the earlier ones leave their
+// sum in gscr ([Vl, H], ctx->train_d) instead of gWd.
+int train_decode_backward_panel(dae_ctx* ctx, const TrainPlan& t, int Vl, int H, int B, int n_batch,
+                                const int32_t* y_row_ptr, const int32_t* y_col, const float* y_val,
+                                int col_lo, int col_hi, const float* Wd, const float* b_dec, float* gWd, float* gb_dec,
+                                const dae_armed_adam* arm, bool first, bool last, float* gscr)
 {
     hipStream_t st = ctx->stream;
     int rc;
-    if (H > FIX_MAXH) return dae_fail(ctx, DAE_ERR_ARG, "training kernels need H <= %d (H=%d)", FIX_MAXH, H);
     if (t.Bpad64 != B)
         DAE_HIP_CHECK(ctx, hipMemsetAsync(t.dzT, 0, (size_t)Vl * t.Bpad64 * (t.dz16 ? sizeof(unsigned short) : sizeof(float)), st));
     float* const corr_part = t.part + (size_t)(t.n_chunk - 1) * t.Bpad64 * H;         // (fuse_dh: the positives' partial, the last one)
@@ -689,22 +742,58 @@ int train_decode_backward(dae_ctx* ctx, const TrainPlan& t, int Vl, int H, int B
     else fixup(&loss_fixup_kernel<false>, nullptr);
     DAE_CHECK_LAUNCH(ctx, "loss_fixup_kernel");
 
-    auto run_k6 = [&](const dae_armed_adam* arm) {
-        return dae_launch_k6(ctx, t.dzT, t.Bpad64, t.dz16, t.hbuf, H, B, Vl, gWd, gb_dec, arm, 0);
+    // where the gradient of the panels so far lies: gWd, or gscr while an armed step has panels to come
+    float* const gsum = (arm && !(first && last)) ? gscr : gWd;
+    auto run_k6 = [&](const dae_armed_adam* a) {
+        return dae_launch_k6(ctx, t.dzT, t.Bpad64, t.dz16, t.hbuf, H, B, Vl, a ? gWd : gsum, gb_dec, a, 0, first ? nullptr : gsum);
     };
     auto run_k7 = [&]() { return launch_k7(ctx, t.dzT, t.Bpad64, t.dz16, Wd, H, Vl, t.Bpad64, t.k7, t.part); };
     // K6 and K7 are independent (both read dz^T).  With the armed Adam K6 rewrites Wd in place, and K7 multiplies by
     // the weights the forward pass used: K7 first.
-    if (ctx->arm_m) {           // dae_arm_decoder_adam: update Wd in place instead of writing gWd
-        const dae_armed_adam arm = {const_cast<float*>(Wd), ctx->arm_m, ctx->arm_v, ctx->arm_alpha, ctx->arm_b1, ctx->arm_b2,
-                                    ctx->arm_eps};
-        ctx->arm_m = nullptr; ctx->arm_v = nullptr;         // one step only
-        if ((H % 128) != 0) return dae_fail(ctx, DAE_ERR_ARG, "the armed decoder Adam needs H %% 128 == 0 (H=%d)", H);
+    if (arm && last) {          // dae_arm_decoder_adam: update Wd in place instead of writing gWd
         if (!t.fuse_dh) { rc = run_k7(); if (rc) return rc; }
-        return run_k6(&arm);
+        return run_k6(arm);
     }
     rc = run_k6(nullptr); if (rc) return rc;
     return t.fuse_dh ? DAE_OK : run_k7();
+}
+
+// The decode side of a step over all its panels.  after_panel(plan of the panel, its first row): what has to read the panel's
+// partials of dh before the next panel overwrites them; called for steps of more than one panel only (the one panel of a shorter
+// batch leaves them at t.part, as it always did).
+template <class After>
+int train_decode_backward(dae_ctx* ctx, const TrainPlan& t, int Vl, int H, int B, int n_batch,
+                          const int32_t* y_row_ptr, const int32_t* y_col, const float* y_val,
+                          int col_lo, int col_hi, const float* Wd, const float* b_dec, float* gWd, float* gb_dec, After after_panel)
+{
+    int rc;
+    if (H > FIX_MAXH) return dae_fail(ctx, DAE_ERR_ARG, "training kernels need H <= %d (H=%d)", FIX_MAXH, H);
+    dae_armed_adam arm = {const_cast<float*>(Wd), ctx->arm_m, ctx->arm_v, ctx->arm_alpha, ctx->arm_b1, ctx->arm_b2, ctx->arm_eps};
+    const bool armed = ctx->arm_m != nullptr;
+    float* gscr = nullptr;
+    if (armed) {
+        ctx->arm_m = nullptr; ctx->arm_v = nullptr;         // one step only
+        if ((H % 128) != 0) return dae_fail(ctx, DAE_ERR_ARG, "the armed decoder Adam needs H %% 128 == 0 (H=%d)", H);
+        if (t.n_panel > 1) {
+            // (train_d: otherwise the title scorer's K7 partials, dae_launch_grad_h -- nothing of either outlives its call)
+            if ((rc = dae_reserve(ctx, ctx->train_d, (size_t)Vl * H * sizeof(float)))) return rc;
+            gscr = static_cast<float*>(ctx->train_d.p);
+        }
+    }
+    for (int i = 0; i < t.n_panel; ++i) {
+        const TrainPlan pv = train_panel(t, i);
+        const int r0 = i * TRAIN_PANEL;
+        if (t.n_panel > 1 && !pv.rm) {                      // the packed K5 reads the panel's rows as a hidden tile of its own
+            rc = pv.dtype == DAE_DTYPE_BF16 ? dae_launch_pack_h_bf16(ctx, pv.hbuf, pv.B, H, pv.g) : dae_launch_pack_h(ctx, pv.hbuf, pv.B, H, pv.g);
+            if (rc) return rc;
+            ctx->h_geom_key = -1;
+        }
+        rc = train_decode_backward_panel(ctx, pv, Vl, H, pv.B, n_batch, y_row_ptr + r0, y_col, y_val, col_lo, col_hi, Wd, b_dec,
+                                         gWd, gb_dec, armed ? &arm : nullptr, i == 0, i == t.n_panel - 1, gscr);
+        if (rc) return rc;
+        if (t.n_panel > 1 && (rc = after_panel(pv, r0))) return rc;
+    }
+    return DAE_OK;
 }
 
 // cost = sum of the loss partials + lambda * (l2 of the listed tensors)
@@ -722,14 +811,23 @@ int train_cost(dae_ctx* ctx, const TrainPlan& t, float reg_lambda, const float* 
             n_l2 += nb;
         }
     }
-    hipLaunchKernelGGL(finish_cost_kernel, dim3(1), dim3(64), 0, st, t.loss_part, t.g.grid + t.n_fix, t.l2_part, n_l2,
+    hipLaunchKernelGGL(finish_cost_kernel, dim3(1), dim3(64), 0, st, t.loss_part, t.n_loss, t.l2_part, n_l2,
                        reg_lambda, cost_out);
     DAE_CHECK_LAUNCH(ctx, "finish_cost_kernel");
     return DAE_OK;
 }
 
-// dpre from dh (n_chunk partials at `part`), gb_enc, the row-sparse gW_enc of this column range,
-// and the lambda terms of the weight gradients
+// dpre of a batch's (or panel's) rows from its n_chunk partials of dh at `part`
+int train_hidden_backward(dae_ctx* ctx, const TrainPlan& t, const float* part, int n_chunk, int H, int B, float kp)
+{
+    hipLaunchKernelGGL(hidden_backward_kernel, dim3(grid_for(t.bh)), dim3(256), 0, ctx->stream, part, n_chunk,
+                       t.Bpad64, H, B, t.hbuf, t.sg, kp, t.dpre);
+    DAE_CHECK_LAUNCH(ctx, "hidden_backward_kernel");
+    return DAE_OK;
+}
+
+// dpre from dh (n_chunk partials at `part`; part == null: the panels of the step have left dpre already), gb_enc, the row-sparse
+// gW_enc of this column range, and the lambda terms of the weight gradients -- over all B rows of the step
 int train_encoder_backward(dae_ctx* ctx, const TrainPlan& t, const float* part, int n_chunk,
                            const int32_t* x_row_ptr, const int32_t* x_col, const float* x_val,
                            int col_lo, int col_hi, int H, int B, int tied, float ikp, float kp,
@@ -739,9 +837,10 @@ int train_encoder_backward(dae_ctx* ctx, const TrainPlan& t, const float* part, 
 {
     hipStream_t st = ctx->stream;
     const size_t nW = (size_t)(col_hi - col_lo) * H;
-    hipLaunchKernelGGL(hidden_backward_kernel, dim3(grid_for(t.bh)), dim3(256), 0, st, part, n_chunk,
-                       t.Bpad64, H, B, t.hbuf, t.sg, kp, t.dpre);
-    DAE_CHECK_LAUNCH(ctx, "hidden_backward_kernel");
+    if (part) {
+        const int rc = train_hidden_backward(ctx, t, part, n_chunk, H, B, kp);
+        if (rc) return rc;
+    }
     hipLaunchKernelGGL(colsum_kernel, dim3((H + 63) / 64), dim3(256), 0, st, t.dpre, B, H, reg_lambda,
                        b_enc, gb_enc);
     DAE_CHECK_LAUNCH(ctx, "colsum_kernel");
@@ -803,8 +902,10 @@ int dae_train_step_f32(dae_ctx* ctx,
         return dae_fail(ctx, DAE_ERR_ARG, "the armed decoder Adam needs the untied model and reg_lambda = 0");
     }
     const float* Wd = tied ? W_enc : W_dec;
+    const bool packed = !t.rm || !t.last.rm;                // some panel takes the packed K5
+    const bool panels = t.n_panel > 1;                      // (each panel's hidden tile is then packed from t.hbuf, panel by panel)
     // decoder weights change every step: re-tile them for the forward GEMM
-    if (!t.rm) {
+    if (packed) {
         rc = t.dtype == DAE_DTYPE_BF16 ? dae_launch_prepack_bf16(ctx, Wd, b_dec, V, H, 0, V)
                                        : dae_launch_prepack_f32(ctx, Wd, b_dec, V, H, 0, V, false);    // (no logit bounds: a ranking call on this image skips nothing)
         if (rc) return rc;
@@ -813,7 +914,7 @@ int dae_train_step_f32(dae_ctx* ctx,
     // ---- forward ----------------------------------------------------------------------------------
     // the pad rows / pad k of the fp32 image are never written by the encode kernel: zeroed once per geometry and
     // buffer (same key as the scoring path: the two share the image)
-    if (t.dtype == DAE_DTYPE_F32 && !t.rm) {
+    if (t.dtype == DAE_DTYPE_F32 && !t.rm && !panels) {
         const long long key = ((long long)B << 32) | ((long long)H << 12) | (long long)t.g.R_TILE;
         if (ctx->h_geom_key != key || ctx->h_geom_ptr != ctx->h_packed.p) {
             DAE_HIP_CHECK(ctx, hipMemsetAsync(ctx->h_packed.p, 0, t.hp_bytes, st));
@@ -821,7 +922,7 @@ int dae_train_step_f32(dae_ctx* ctx,
             ctx->h_geom_ptr = ctx->h_packed.p;
         }
     }
-    if (t.rm) {
+    if (t.rm || panels) {
         rc = dae_launch_encode(ctx, x_row_ptr, x_col, x_val, W_enc, b_enc, V, H, B, ikp, kp, seed, t.hbuf,
                                nullptr, 0, 0, t.sg, nullptr);
     } else if (t.dtype == DAE_DTYPE_BF16) {
@@ -835,7 +936,9 @@ int dae_train_step_f32(dae_ctx* ctx,
     }
     if (rc) return rc;
     rc = train_decode_backward(ctx, t, V, H, B, n_batch, y_row_ptr, y_col, y_val, 0, V, Wd, b_dec,
-                               tied ? gW_enc : gW_dec, gb_dec);
+                               tied ? gW_enc : gW_dec, gb_dec, [&](const TrainPlan& pv, int) {
+                                   return train_hidden_backward(ctx, pv, pv.part, pv.n_chunk, H, pv.B, kp);
+                               });
     if (rc) return rc;
 
     // ---- cost (+ lambda * l2) ----------------------------------------------------------------------
@@ -844,11 +947,11 @@ int dae_train_step_f32(dae_ctx* ctx,
     rc = train_cost(ctx, t, reg_lambda, ts, ns, 4, cost_out);
     if (rc) return rc;
 
-    rc = train_encoder_backward(ctx, t, t.part, t.n_chunk, x_row_ptr, x_col, x_val, 0, V, H, B, tied,
+    rc = train_encoder_backward(ctx, t, panels ? nullptr : t.part, t.n_chunk, x_row_ptr, x_col, x_val, 0, V, H, B, tied,
                                 ikp, kp, seed, reg_lambda, W_enc, b_enc, W_dec, b_dec,
                                 gW_enc, gb_enc, gW_dec, gb_dec);
     if (rc) return rc;
-    if (!t.rm) (t.dtype == DAE_DTYPE_BF16 ? ctx->pk_bf16 : ctx->pk_f32).valid = true;
+    if (packed) (t.dtype == DAE_DTYPE_BF16 ? ctx->pk_bf16 : ctx->pk_f32).valid = true;
     return DAE_OK;
 }
 
@@ -876,7 +979,8 @@ int dae_train_shard_decode_f32(dae_ctx* ctx, const float* pre, const float* b_en
     int rc = train_plan(ctx, Vl, H, B, t);
     if (rc) return rc;
     const float* Wd = tied ? W_enc_loc : W_dec_loc;
-    if (!t.rm) {
+    const bool packed = !t.rm || !t.last.rm;
+    if (packed) {
         rc = t.dtype == DAE_DTYPE_BF16 ? dae_launch_prepack_bf16(ctx, Wd, b_dec_loc, Vl, H, 0, Vl)
                                        : dae_launch_prepack_f32(ctx, Wd, b_dec_loc, Vl, H, 0, Vl, false);
         if (rc) return rc;
@@ -885,23 +989,28 @@ int dae_train_shard_decode_f32(dae_ctx* ctx, const float* pre, const float* b_en
                        t.hbuf, t.sg);
     DAE_CHECK_LAUNCH(ctx, "activate_kernel");
     ctx->h_geom_key = -1;
-    if (!t.rm) {
+    if (!t.rm && t.n_panel == 1) {
         rc = t.dtype == DAE_DTYPE_BF16 ? dae_launch_pack_h_bf16(ctx, t.hbuf, B, H, t.g)
                                        : dae_launch_pack_h(ctx, t.hbuf, B, H, t.g);
         if (rc) return rc;
     }
+    // dh of this shard: the partials summed in chunk order, a panel's rows after the panel
+    auto sum_dh = [&](const TrainPlan& pv, int r0) {
+        hipLaunchKernelGGL(sum_chunks_kernel, dim3(grid_for(pv.bh)), dim3(256), 0, st, pv.part, pv.n_chunk,
+                           (size_t)pv.Bpad64 * H, pv.bh, dh_partial + (size_t)r0 * H);
+        DAE_CHECK_LAUNCH(ctx, "sum_chunks_kernel");
+        return (int)DAE_OK;
+    };
     rc = train_decode_backward(ctx, t, Vl, H, B, n_batch, y_row_ptr, y_col, y_val, col_lo, col_hi, Wd, b_dec_loc,
-                               gW_out, gb_dec_loc);
+                               gW_out, gb_dec_loc, sum_dh);
     if (rc) return rc;
     // b_enc is replicated: its l2 term is counted once, by the shard that owns column 0
     const float* ts[4] = {W_enc_loc, b_dec_loc, col_lo == 0 ? b_enc : nullptr, tied ? nullptr : W_dec_loc};
     const size_t ns[4] = {(size_t)Vl * H, (size_t)Vl, (size_t)H, (size_t)Vl * H};
     rc = train_cost(ctx, t, reg_lambda, ts, ns, 4, cost_partial);
     if (rc) return rc;
-    hipLaunchKernelGGL(sum_chunks_kernel, dim3(grid_for(t.bh)), dim3(256), 0, st, t.part, t.n_chunk,
-                       (size_t)t.Bpad64 * H, t.bh, dh_partial);
-    DAE_CHECK_LAUNCH(ctx, "sum_chunks_kernel");
-    if (!t.rm) (t.dtype == DAE_DTYPE_BF16 ? ctx->pk_bf16 : ctx->pk_f32).valid = true;
+    if (t.n_panel == 1 && (rc = sum_dh(t, 0))) return rc;
+    if (packed) (t.dtype == DAE_DTYPE_BF16 ? ctx->pk_bf16 : ctx->pk_f32).valid = true;
     return DAE_OK;
 }
 

@@ -938,7 +938,7 @@ class DAE_title(DAE):
         if titles is None:
             raise ValueError("DAE_title trains the title scorer: titles are required")
         tm = self.title_model
-        tm.check_trainable()
+        tm.check_trainable(self.n_batch)
         seed = int(self._rng.randint(0, 2 ** 31 - 1))
         self._ensure_packed()
         self.ctx.bind_stream()

@@ -23,6 +23,7 @@ T_MAX_EMB = 128          # csrc/title.hip T_MAX_EMB
 T_MAX_LEN = 64           # csrc/title.hip T_MAX_LEN
 T_MAX_SIZES = 8          # csrc/dae_internal.h DAE_TITLE_MAX_SIZES
 T_MAX_TRAIN_FILTERS = 256    # title_wgrad_kernel: one thread per filter, one workgroup of at most 256
+T_MAX_TRAIN_BATCH = 256      # the output layer's gradients (dae_launch_grad_w / dae_launch_grad_h) and the two dense [B, V] matrices
 T_MAX_F32_FEATURES = 1024    # the fp32 decoder prepack (dae_launch_prepack_f32): hidden <= 1024
 
 
@@ -202,8 +203,11 @@ class Char_CNN:
             float(keep_prob), int(seed), P(feat), self.ld, P(arg), P(raw)))
         return (feat, d_t, arg, raw) if keep_for_backward else feat
 
-    def check_trainable(self):
+    def check_trainable(self, n_batch=None):
         """A training step's shape limits, checked before any of its kernels runs."""
+        if n_batch is not None and n_batch > T_MAX_TRAIN_BATCH:
+            raise ValueError("[TITLE] batch = %d: training the title scorer takes at most %d rows per step (the DAE's own "
+                             "training step takes up to 4096)" % (n_batch, T_MAX_TRAIN_BATCH))
         if self.filter_num > T_MAX_TRAIN_FILTERS:
             raise ValueError("[TITLE] filter_num = %d: training takes at most %d filters per size"
                              % (self.filter_num, T_MAX_TRAIN_FILTERS))
@@ -255,7 +259,7 @@ class Char_CNN:
                           seed, cost_out):
         """Gradients of the mixed-score loss w.r.t. the title variables, then one TF1-Adam step on each."""
         import torch
-        self.check_trainable()
+        self.check_trainable(n_batch)
         g = self._train_state()
         ctx, lib, P = self.ctx, self.ctx.lib, _lib._ptr
         B, V = z_title.shape
