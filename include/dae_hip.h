@@ -159,6 +159,20 @@ int dae_train_batch(dae_ctx* ctx, const dae_train_set* set, const int32_t* draw,
                     int32_t* x_row_ptr, int32_t* x_col, float* x_val, int x_cap,
                     int32_t* y_row_ptr, int32_t* y_col, float* y_val, int y_cap, int32_t* status);
 
+/* The playlists' TITLES join the set: what the reader appends per drawn playlist (data_reader.py:29 / :42, `titles`) and the
+ * title step feeds as model_title.titles (main_train.py:218), so that a title step too is named by its draw alone.
+ *   titles HOST int32 [n_playlists][L], copied once into an allocation the set owns (dae_train_set_destroy frees it):
+ *          4 L bytes a playlist.  n_playlists must be the set's, 1 <= L <= 64 (the title kernels' longest title).
+ * Refused on the host, before any HIP call (DAE_ERR_ARG): an entry that is neither -1 (no character) nor in [0, n_char).
+ * A second attach: DAE_ERR_STATE.  The call has no context: its message is dae_last_error(NULL)'s. */
+int dae_train_set_attach_titles(dae_train_set* set, const int32_t* titles, int n_playlists, int L, int n_char);
+
+/* titles_out (DEVICE int32 [B][L]) row r = the title row of playlist draw[0][r]: one launch on ctx's stream, one wave per
+ * row.  `draw` as dae_train_batch takes it (only its first B entries are read).  A playlist index outside
+ * [0, n_playlists) gives a row of -1; dae_train_batch raises its status bit 0 for that same draw, so there is no second
+ * status word here.  1 <= B <= 4096.  A set without titles: DAE_ERR_STATE. */
+int dae_train_titles(dae_ctx* ctx, const dae_train_set* set, const int32_t* draw, int B, int32_t* titles_out);
+
 /* h[r,:] = hidden_dropout( sigmoid( sum_c (x[r,c]/(s_r+1e-10)) * W_enc[c,:] + b_enc ) )
  *   x      = input_dropout(CSR row r), s_r = sum of surviving weights.
  *   ikp/kp = input / hidden keep probabilities (1.0 = identity, the inference setting);

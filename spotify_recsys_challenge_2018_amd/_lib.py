@@ -15,7 +15,7 @@ DAE_DTYPE_F32, DAE_DTYPE_BF16, DAE_DTYPE_BF16_EXACT = 0, 1, 2
 EXPORTS = [
     "dae_version", "dae_create", "dae_destroy", "dae_set_stream", "dae_last_error",
     "dae_scratch_bytes", "dae_profile_enable", "dae_profile_read", "dae_profile_kernel", "dae_clock_probe", "dae_last_plan",
-    "dae_coo_to_csr", "dae_seeds_from_csr", "dae_train_set_create", "dae_train_set_destroy", "dae_train_batch", "dae_encode", "dae_prepack_decoder", "dae_prepack_decoder_rows", "dae_share_decoder", "dae_exact_bounds",
+    "dae_coo_to_csr", "dae_seeds_from_csr", "dae_train_set_create", "dae_train_set_destroy", "dae_train_batch", "dae_train_set_attach_titles", "dae_train_titles", "dae_encode", "dae_prepack_decoder", "dae_prepack_decoder_rows", "dae_share_decoder", "dae_exact_bounds",
     "dae_exact_guard_read", "dae_exact_guard_words", "dae_exact_guard_snapshot", "dae_exact_stats_read", "dae_set_exact_margin", "dae_set_exact_margin_range", "dae_set_exact_audit", "dae_exact_audit_read",
     "dae_set_filter_skip", "dae_filter_skip_read", "dae_filter_skip_last", "dae_tile_bounds_read", "dae_decode_dense", "dae_decode_topk",
     "dae_score_topk", "dae_score_topk_begin", "dae_score_topk_finish", "dae_topk_dense", "dae_topk_merge", "dae_set_train_dtype", "dae_train_forward_backward",
@@ -71,6 +71,8 @@ def load():
     lib.dae_train_set_create.argtypes = [vp, vp, vp, vp, vp, c_int, c_int, c_int, ctypes.POINTER(vp)]
     lib.dae_train_set_destroy.argtypes = [vp]
     lib.dae_train_batch.argtypes = [vp, vp, vp, c_int, c_int, vp, vp, vp, c_int, vp, vp, vp, c_int, vp]
+    lib.dae_train_set_attach_titles.argtypes = [vp, vp, c_int, c_int, c_int]
+    lib.dae_train_titles.argtypes = [vp, vp, vp, c_int, vp]
     lib.dae_encode.argtypes = [vp, vp, vp, vp, vp, vp, c_int, c_int, c_int, c_f, c_f, c_u32, vp]
     lib.dae_prepack_decoder.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_int, c_int]
     lib.dae_prepack_decoder_rows.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_int]
@@ -201,6 +203,24 @@ class TrainSet:
                                                vp(art_off.ctypes.data), self.n_playlists, int(n_tracks), int(n_items),
                                                ctypes.byref(h)))
         self.h = h
+        self.has_titles, self.title_len = False, 0
+
+    def attach_titles(self, titles, n_char):
+        """The playlists' title rows join the set (dae_train_set_attach_titles copies them once): titles int
+        [n_playlists, L], every entry -1 (no character) or a character id in [0, n_char).  Anything else, a second attach or
+        rows for another number of playlists raise DaeError before any launch."""
+        import numpy as np
+        t = np.asarray(titles)
+        if t.ndim != 2 or t.shape[0] != self.n_playlists:
+            raise DaeError("dae_train_set_attach_titles: titles of shape %s for a set of %d playlists" % (t.shape, self.n_playlists))
+        if t.size and (t.min() < -2 ** 31 or t.max() >= 2 ** 31):
+            raise DaeError("dae_train_set_attach_titles: a character id does not fit 32 bits")
+        t = np.ascontiguousarray(t, dtype=np.int32)
+        rc = self.ctx.lib.dae_train_set_attach_titles(self.h, ctypes.c_void_p(t.ctypes.data), int(t.shape[0]), int(t.shape[1]),
+                                                      int(n_char))
+        if rc != 0:                                          # (a call without a context: its message is the global one)
+            raise DaeError("libdae_hip error %d: %s" % (rc, self.ctx.lib.dae_last_error(None).decode()))
+        self.has_titles, self.title_len = True, int(t.shape[1])
 
     def close(self):
         if getattr(self, "h", None):
@@ -284,6 +304,17 @@ class Context:
         self.check(self.lib.dae_train_batch(self.h, train_set.h, _ptr(draw), B, int(x_side), _ptr(xr), _ptr(xc), _ptr(xv),
                                             int(x_cap), _ptr(yr), _ptr(yc), _ptr(yv), int(y_cap), _ptr(status)))
         return out[0], out[1], status
+
+    def train_titles(self, train_set, draw):
+        """The title rows of a drawn batch (dae_train_titles; the set holds titles: TrainSet.attach_titles).  draw: the int32
+        [3, B] CUDA tensor `train_batch` takes.  -> int32 [B, L] CUDA tensor; a playlist index out of range gives a row of -1
+        (and `train_batch`'s status bit 0 for the same draw)."""
+        import torch
+        assert draw.dtype == torch.int32 and draw.is_contiguous() and draw.shape[0] == 3
+        B = int(draw.shape[1])
+        out = torch.empty((B, max(int(train_set.title_len), 1)), dtype=torch.int32, device=draw.device)
+        self.check(self.lib.dae_train_titles(self.h, train_set.h, _ptr(draw), B, _ptr(out)))
+        return out
 
     def set_train_dtype(self, dtype):
         """Arithmetic of the training forward GEMM: DAE_DTYPE_F32 (default) or DAE_DTYPE_BF16."""

@@ -8,6 +8,8 @@
 //   feed_compact_kernel  one workgroup per row: output offset = the kept counts of the rows before it, summed here
 //                        (csr_compact_sum_kernel's scheme: no scan launch), then a copy; the last row's workgroup writes
 //                        the status word
+//   feed_titles_kernel   dae_train_titles: one wave per row copies the drawn playlists' title rows out of the set
+//                        (dae_train_set_attach_titles: the reader's [n_playlists][L] character ids, copied once)
 // No memset, no atomics on global memory.  Integer work bound by latency and launch count, not by any rate.
 #include "dae_internal.h"
 #include "train_feed_check.h"
@@ -21,6 +23,8 @@ struct dae_train_set {
     const int32_t* art = nullptr;
     int n_playlists = 0, n_tracks = 0, n_items = 0;
     dae_train_set_shape shape;
+    int32_t* titles = nullptr;         // dae_train_set_attach_titles: [n_playlists][title_len], an allocation of its own
+    int title_len = 0;
 };
 
 namespace {
@@ -159,6 +163,18 @@ __global__ __launch_bounds__(256) void feed_compact_kernel(const int* __restrict
         if (ox + s < x_cap) { x_col[ox + s] = xk[b + s]; x_val[ox + s] = 1.0f; }
 }
 
+// One wave per batch row (four rows per workgroup): lane i copies character i of the drawn playlist's title; a playlist
+// index out of range gives a row of -1 (no character) -- feed_row_kernel raises the status bit for that same draw.
+__global__ __launch_bounds__(256) void feed_titles_kernel(const int32_t* __restrict__ titles, int n_playlists, int L,
+                                                          const int32_t* __restrict__ draw, int B, int32_t* __restrict__ out)
+{
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= B) return;
+    const int p = draw[row];
+    const bool ok = p >= 0 && p < n_playlists;
+    for (int i = lane; i < L; i += 64) out[(int64_t)row * L + i] = ok ? titles[(int64_t)p * L + i] : -1;
+}
+
 }  // namespace
 
 int dae_train_set_create(dae_ctx* ctx, const int32_t* trk, const int64_t* trk_off, const int32_t* art, const int64_t* art_off,
@@ -209,7 +225,32 @@ int dae_train_set_destroy(dae_train_set* set)
     (void)hipSetDevice(set->device);
     (void)hipDeviceSynchronize();          // a batch that reads the table may still be running
     (void)hipFree(set->block);
+    if (set->titles) (void)hipFree(set->titles);
     delete set;
+    return DAE_OK;
+}
+
+int dae_train_set_attach_titles(dae_train_set* set, const int32_t* titles, int n_playlists, int L, int n_char)
+{
+    // (no context here: the message goes where dae_create's does, dae_last_error(NULL))
+    if (!set) return dae_fail(nullptr, DAE_ERR_ARG, "dae_train_set_attach_titles: null pointer");
+    if (set->titles) return dae_fail(nullptr, DAE_ERR_STATE, "dae_train_set_attach_titles: the set already holds titles");
+    char msg[256];
+    const int rc = dae_train_titles_check(titles, n_playlists, set->n_playlists, L, n_char, msg, sizeof(msg));
+    if (rc) return dae_fail(nullptr, rc, "dae_train_set_attach_titles: %s", msg);
+    const size_t bytes = (size_t)n_playlists * (size_t)L * sizeof(int32_t);
+    hipError_t e = hipSetDevice(set->device);
+    if (e != hipSuccess) return dae_fail(nullptr, DAE_ERR_HIP, "dae_train_set_attach_titles: hipSetDevice: %s", hipGetErrorString(e));
+    int32_t* d = nullptr;
+    e = hipMalloc(reinterpret_cast<void**>(&d), bytes);
+    if (e != hipSuccess) return dae_fail(nullptr, DAE_ERR_NOMEM, "dae_train_set_attach_titles: hipMalloc failed: %s", hipGetErrorString(e));
+    e = hipMemcpy(d, titles, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return dae_fail(nullptr, DAE_ERR_HIP, "dae_train_set_attach_titles: upload failed: %s", hipGetErrorString(e));
+    }
+    set->titles = d;
+    set->title_len = L;
     return DAE_OK;
 }
 
@@ -247,5 +288,18 @@ int dae_train_batch(dae_ctx* ctx, const dae_train_set* set, const int32_t* draw,
     hipLaunchKernelGGL(feed_compact_kernel, dim3(B), dim3(256), 0, ctx->stream, ycnt, xcnt, rflag, B, stride, yk, xk,
                        x_row_ptr, x_col, x_val, x_cap, y_row_ptr, y_col, y_val, y_cap, status);
     DAE_CHECK_LAUNCH(ctx, "feed_compact_kernel");
+    return DAE_OK;
+}
+
+int dae_train_titles(dae_ctx* ctx, const dae_train_set* set, const int32_t* draw, int B, int32_t* titles_out)
+{
+    if (!ctx) return DAE_ERR_ARG;
+    if (!set || !draw || !titles_out) return dae_fail(ctx, DAE_ERR_ARG, "null pointer");
+    if (B < 1 || B > 4096) return dae_fail(ctx, DAE_ERR_ARG, "dae_train_titles: B=%d, must be in [1, 4096]", B);
+    if (set->device != ctx->device) return dae_fail(ctx, DAE_ERR_ARG, "dae_train_titles: the set lives on device %d", set->device);
+    if (!set->titles) return dae_fail(ctx, DAE_ERR_STATE, "dae_train_titles: the set holds no titles (dae_train_set_attach_titles)");
+    hipLaunchKernelGGL(feed_titles_kernel, dim3((B + 3) / 4), dim3(256), 0, ctx->stream, set->titles, set->n_playlists,
+                       set->title_len, draw, B, titles_out);
+    DAE_CHECK_LAUNCH(ctx, "feed_titles_kernel");
     return DAE_OK;
 }

@@ -1,7 +1,7 @@
 // train_feed_check.h -- the host-side validation of dae_train_set_create (train_feed.hip), free of HIP so that a plain C++
 // program can exercise it (tests/host/train_set_check_main.cpp).  The device path relies on what is checked here: offsets
 // that start at 0 and never descend, every track in [0, n_tracks), every artist in [n_tracks, n_items) -- dae_train_batch
-// carries no per-entry range flag.
+// carries no per-entry range flag.  Likewise dae_train_set_attach_titles' check of the title rows, further down.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -71,5 +71,42 @@ inline int dae_train_set_check(const int32_t* trk, const int64_t* trk_off, const
     shape->n_art = total[1];
     shape->max_side = max_side;
     shape->max_row = (int)max_row;
+    return 0;
+}
+
+constexpr int DAE_TRAIN_TITLE_MAX_LEN = 64;     // csrc/title.hip T_MAX_LEN: the longest title the title kernels take
+
+// dae_train_set_attach_titles' validation (tests/host/train_titles_check_main.cpp): titles [n_playlists][L], every entry -1
+// (no character) or a character id in [0, n_char).  `set_playlists`: the playlists of the set the titles join.
+// 0 = well formed; otherwise the DAE_ERR_* code to return, with the reason in `msg`.  dae_train_titles copies rows as they
+// are: it carries no per-entry check either.
+inline int dae_train_titles_check(const int32_t* titles, int n_playlists, int set_playlists, int L, int n_char, char* msg,
+                                  size_t msg_len)
+{
+    constexpr int ERR_ARG = -1;        // DAE_ERR_ARG (include/dae_hip.h)
+    if (!titles || !msg) {
+        if (msg) snprintf(msg, msg_len, "null pointer");
+        return ERR_ARG;
+    }
+    if (n_playlists < 1 || n_playlists != set_playlists) {
+        snprintf(msg, msg_len, "titles of %d playlists for a set of %d", n_playlists, set_playlists);
+        return ERR_ARG;
+    }
+    if (L < 1 || L > DAE_TRAIN_TITLE_MAX_LEN) {
+        snprintf(msg, msg_len, "title length %d: must be in [1, %d]", L, DAE_TRAIN_TITLE_MAX_LEN);
+        return ERR_ARG;
+    }
+    if (n_char < 1) {
+        snprintf(msg, msg_len, "n_char = %d: must be at least 1", n_char);
+        return ERR_ARG;
+    }
+    for (int p = 0; p < n_playlists; ++p)
+        for (int i = 0; i < L; ++i) {
+            const int32_t c = titles[(size_t)p * (size_t)L + i];
+            if (c < -1 || c >= n_char) {
+                snprintf(msg, msg_len, "titles[%d][%d] = %d is no character: -1 (none) or an id in [0, %d)", p, i, c, n_char);
+                return ERR_ARG;
+            }
+        }
     return 0;
 }

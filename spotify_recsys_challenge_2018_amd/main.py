@@ -78,7 +78,7 @@ class Conf:
         #   eval_metrics = rprecision | all   what the evaluation of a test split logs: the r-precision line alone (default,
         #                  the reference's log), or NDCG and recommended-songs clicks as well (utils/metrics.py get_ndcg /
         #                  get_rsc, which the reference defines and never calls); model selection reads r-precision either way
-        #   train_feed   = host | device      where the training batches of --pretrain / --dae are built: by the reader on the host
+        #   train_feed   = host | device      where the training batches of --pretrain / --dae / --title are built: by the reader on the host
         #                  (default), or on the device from a resident copy of the training set -- only the reader's draws
         #                  go over the link (models/DAEs.py train_step_draw); same batches, same random draws
         self.eval_metrics = 'rprecision'

@@ -210,10 +210,8 @@ def run(conf, only_testmode):
         return out
 
     # [BASE] train_feed = device: the training set lives on the device and a batch goes up as the reader's draws alone
+    # (title mode: its title rows too)
     device_feed = getattr(conf, 'train_feed', 'host') == 'device'
-    if device_feed and conf.mode == 'title':
-        log_write(conf, "train_feed = device is ignored in title mode: the batches are built on the host")
-        device_feed = False
     if device_feed:
         model.attach_train_set(reader)
 
@@ -227,7 +225,13 @@ def run(conf, only_testmode):
             trk_positions, art_positions, y_positions, _titles, trk_val, art_val = reader.next_batch()
         end_idx = reader.train_idx
         input_kp = random.uniform(kp_range[0], kp_range[-1])        # main_train.py:199
-        if device_feed:                                             # the same coin, after the same draws
+        if device_feed and conf.mode == 'title':
+            # :214-221 from the draw: the whole playlist is input and target with value 1, whatever the reader's given counts
+            # say, and -- like the host loop below -- no coin is drawn
+            draw[1:] = -1
+            l = model.train_step_draw(draw, 2, conf.kp, input_kp, fetch_cost=False, title_keep_prob=conf.title_kp)
+            l = l.double()      # summed on the device as the host loop sums its Python floats: the epoch's loss keeps its bits
+        elif device_feed:                                           # the same coin, after the same draws
             l = model.train_step_draw(draw, int(np.random.randint(2) != 0), conf.kp, input_kp, fetch_cost=False)
         elif conf.mode == 'title':                                    # :214-221: the whole playlist is input and target
             ones = np.ones(len(y_positions), np.float32)

@@ -739,7 +739,8 @@ class DAE_tied:
     def attach_train_set(self, reader):
         """Keep `reader`'s training set on the device for `train_step_draw`: its flat id arrays and offsets are copied
         once (dae_train_set_create, which refuses ids outside their ranges).  Once per model, after fit().  A
-        vocabulary-sharded model keeps only the reader: its `train_step_draw` rebuilds the host feed."""
+        vocabulary-sharded model holds the set on every rank: the batch is replicated, only the vocabulary rows are
+        sharded."""
         if self._train_feed is not None:
             raise _lib.DaeError("attach_train_set: this model already holds a training set")
         feed = {"reader": reader, "set": None,
@@ -750,7 +751,7 @@ class DAE_tied:
         self._train_feed = feed
 
     def _takes_device_feed(self):
-        return self._sharded is None
+        return True
 
     def _host_feed_step(self, draw, x_side, keep_prob, input_keep_prob, fetch_cost):
         """`train_step` on the host feed rebuilt from the draw: same batches, same results, nothing sped up."""
@@ -764,17 +765,33 @@ class DAE_tied:
         tracks, given artists), x_side 0 / 1 / 2 = x is the tracks / the artists / both; y is the whole playlist.  Only the
         draw goes over the link (12 bytes a row, on the copy stream); both CSRs are built on the device from the attached
         set (dae_train_batch: two launches) and are, entry for entry, what `train_step` builds from `next_batch`'s COO -- so
-        is everything after them.  A vocabulary-sharded model and DAE_title do NOT take the device feed: they rebuild the
-        host feed from the draw (utils/data_reader.py feed_from_draw) and call their `train_step`."""
-        import torch
-        feed = self._train_feed
-        if feed is None:
+        is everything after them.  A vocabulary-sharded model hands the same CSRs to its ShardedTrainer, as its `train_step`
+        does (every rank draws the same batches); DAE_title has a `train_step_draw` of its own."""
+        draw = self._checked_draw(draw)
+        if self._train_feed["set"] is None:
+            return self._host_feed_step(draw, x_side, keep_prob, input_keep_prob, fetch_cost)
+        _d_draw, x, y = self._device_feed(draw, x_side)
+        if self._sharded is not None:
+            self._params_stale = True
+            cost = self._sharded.train_step(x, y, keep_prob, input_keep_prob, fetch_cost=fetch_cost)
+            if fetch_cost:
+                self._check_feed()
+            return cost
+        return self._train_step_csr(x, y, keep_prob, input_keep_prob, fetch_cost)
+
+    def _checked_draw(self, draw):
+        if self._train_feed is None:
             raise _lib.DaeError("train_step_draw needs attach_train_set(reader) first")
         draw = np.ascontiguousarray(draw, dtype=np.int32)
         if draw.shape != (3, self.n_batch):
             raise ValueError("draw has shape %s, expected (3, %d)" % (draw.shape, self.n_batch))
-        if feed["set"] is None or not self._takes_device_feed():
-            return self._host_feed_step(draw, x_side, keep_prob, input_keep_prob, fetch_cost)
+        return draw
+
+    def _device_feed(self, draw, x_side):
+        """The draw uploaded and both CSRs of its batch built from the attached set (dae_train_batch) -> (d_draw, x, y); the
+        feed's status word joins the pending range flags (`_check_feed`)."""
+        import torch
+        feed = self._train_feed
         if x_side not in (0, 1, 2):
             raise ValueError("x_side %r: 0 tracks, 1 artists, 2 both" % (x_side,))
         self.ctx.bind_stream()
@@ -790,7 +807,7 @@ class DAE_tied:
         if len(pending) > 64:                                   # un-fetched training steps: fold on the device
             pending = [(self._fold_status(pending), cur.record_event())]
         self._csr_status = pending
-        return self._train_step_csr(x, y, keep_prob, input_keep_prob, fetch_cost)
+        return d_draw, x, y
 
     # -- persistence ----------------------------------------------------------------------------------
     def get_params(self):
@@ -877,6 +894,7 @@ class DAE_title(DAE):
         self.title_exact_off = False      # set from outside: titled exact_bf16 launches on the fp32 kernels
         self._title_fp32_said = False     # `_title_dtype` said that this model's shapes have no exact title mix
         self._tcost = None                # train_step's cost word on the device
+        self._ones_use = None             # train_step_draw's titles_use on the device
         # `_mix_guard_fired`: rows it re-scored alone; launches in a row whose rows overflowed the refine launch (two pause the
         # exact mix); titled launches left of that pause, which run on the fp32 kernels
         self._guard_row_fallbacks = self._mix_overflow_streak = self._mix_exact_pause = 0
@@ -931,22 +949,46 @@ class DAE_title(DAE):
         return y
 
     def train_step(self, x_positions, x_ones, y_positions, y_ones, keep_prob, input_keep_prob, titles=None,
-                   titles_use=None, title_keep_prob=1.0):
+                   titles_use=None, title_keep_prob=1.0, fetch_cost=True):
         """sess.run([model.optimizer, model.cost], ...) of the title graph (main_train.py:214-221): one Adam step
-        on the title variables; the DAE arrays stay as loaded.  Returns the cost."""
+        on the title variables; the DAE arrays stay as loaded.  Returns the cost; `fetch_cost=False` as in
+        `DAE_tied.train_step`: a 0-dim DEVICE tensor, no wait for the step."""
         import torch
         if titles is None:
             raise ValueError("DAE_title trains the title scorer: titles are required")
         tm = self.title_model
         tm.check_trainable(self.n_batch)
+        self.ctx.bind_stream()
+        dev = self.weights["encoder_h"].device
+        x = self._upload_csr(x_positions, x_ones)
+        y = self._upload_csr(y_positions, y_ones)
+
+        # titles_use and the title rows go up where the step first reads them, as they always did: a pageable copy blocks
+        # the host until the stream reaches it, and behind the DAE forward's launches that wait costs nothing -- in front
+        # of them the device would sit idle meanwhile (measured: profiles/title_feed_notes.md)
+        def use():
+            u = torch.zeros(self.n_batch, dtype=torch.float32, device=dev)
+            tu = np.ones(self.n_batch, np.float32) if titles_use is None else np.asarray(titles_use, np.float32).reshape(-1)
+            u[:min(len(tu), self.n_batch)] = torch.from_numpy(tu[:self.n_batch]).to(dev)
+            return u
+        return self._title_step_csr(x, y, lambda: tm.titles_to_device(titles, self.n_batch), use, keep_prob, input_keep_prob,
+                                    title_keep_prob, fetch_cost)
+
+    def _title_step_csr(self, x, y, d_titles, d_use, keep_prob, input_keep_prob, title_keep_prob, fetch_cost):
+        """One Adam step on the title variables from what already lies on the device, whichever feed put it there
+        (`train_step`: the host's COO and title lists; `train_step_draw`: dae_train_batch and dae_train_titles):
+        x, y = (row_ptr, col, val) CSRs of the batch, d_titles int32 [n_batch, strmaxlen], d_use float32 [n_batch]
+        (titles_use) -- device tensors, or (the host feed) functions that upload them, called where the step first reads
+        them.  -> the cost, as `train_step` returns it."""
+        import torch
+        tm = self.title_model                 # (its shape limits were checked by the caller, before its uploads)
         seed = int(self._rng.randint(0, 2 ** 31 - 1))
         self._ensure_packed()
         self.ctx.bind_stream()
         tm.ctx.bind_stream()
         dev = self.weights["encoder_h"].device
+        (xr, xc, xv), (yr, yc, yv) = x, y
         # frozen DAE forward with its dropouts (model.keep_prob = conf.kp, input_keep_prob; main_train.py:219-220)
-        xr, xc, xv = self._upload_csr(x_positions, x_ones)
-        yr, yc, yv = self._upload_csr(y_positions, y_ones)
         h = torch.empty((self.n_batch, self.n_hidden), dtype=torch.float32, device=dev)
         self.ctx.encode(xr, xc, xv, self.weights["encoder_h"], self.biases["encoder_b"], h,
                         ikp=input_keep_prob, kp=keep_prob, seed=seed)
@@ -957,37 +999,67 @@ class DAE_title(DAE):
         P = _lib._ptr
         self.ctx.check(self.ctx.lib.dae_row_sums(self.ctx.h, P(xr), P(xc), P(xv), self.n_batch,
                                                  float(input_keep_prob), seed, P(s)))
-        u = torch.zeros(self.n_batch, dtype=torch.float32, device=dev)
-        tu = np.ones(self.n_batch, np.float32) if titles_use is None else np.asarray(titles_use, np.float32).reshape(-1)
-        u[:min(len(tu), self.n_batch)] = torch.from_numpy(tu[:self.n_batch]).to(dev)
+        u = d_use() if callable(d_use) else d_use
         x_count = s * float(np.float32(input_keep_prob))
         deno = u + x_count + 1e-10
         w_t, w_p = (u / deno).contiguous(), (x_count / deno).contiguous()
         # title forward, keeping what the backward pass needs
         tm._ensure_packed(features_table=False)
-        feat, d_titles, arg, raw = tm.features(titles, self.n_batch, title_keep_prob, seed, keep_for_backward=True)
+        d_titles = d_titles() if callable(d_titles) else d_titles
+        feat, d_titles, arg, raw = tm.features(d_titles, self.n_batch, title_keep_prob, seed, keep_for_backward=True)
         zt = torch.empty((self.n_batch, self.n_input), dtype=torch.float32, device=dev)
         tm.ctx.decode_dense(feat, zt, apply_sigmoid=False)
         if self._tcost is None:
             self._tcost = torch.zeros(1, dtype=torch.float32, device=dev)
         tm.backward_and_step(feat, d_titles, arg, raw, zt, dae, (yr, yc, yv), w_t, w_p, self.n_batch,
                              title_keep_prob, seed, self._tcost)
+        if not fetch_cost:
+            return self._tcost[0].clone()
         cost = float(self._tcost.item())
         self._check_feed()
         return cost
 
-    def _takes_device_feed(self):
-        return False                  # the device table holds no titles: `train_step_draw` rebuilds the host feed
+    def attach_train_set(self, reader):
+        """`DAE_tied.attach_train_set`, and the reader's title rows join the set (dae_train_set_attach_titles: 4 x strmaxlen
+        bytes a playlist): a title step is then named by its draw alone."""
+        DAE.attach_train_set(self, reader)
+        ts = self._train_feed["set"]
+        try:
+            n, L = ts.n_playlists, self.title_model.input_len
+            ts.attach_titles(np.asarray(reader._titles, np.int32).reshape(n, L), self.title_model.char_size)
+        except Exception:
+            ts.close()
+            self._train_feed = None
+            raise
+        self._ones_use = None         # the device feed's titles_use: all ones, made once
+
+    def train_step_draw(self, draw, x_side, keep_prob, input_keep_prob, fetch_cost=True, title_keep_prob=1.0):
+        """The title step of the batch a draw names (`DAE_tied.train_step_draw`): the draw is uploaded, both CSRs and the
+        title rows come out of the attached set (dae_train_batch, dae_train_titles), titles_use is 1 for every row
+        (main_train.py:221), and `_title_step_csr` does what `train_step` does behind its uploads -- for any draw the step
+        `_host_feed_step` runs from the host's rebuild of the same batch."""
+        import torch
+        draw = self._checked_draw(draw)
+        ts = self._train_feed["set"]
+        if ts is None or not ts.has_titles:
+            return self._host_feed_step(draw, x_side, keep_prob, input_keep_prob, fetch_cost, title_keep_prob)
+        self.title_model.check_trainable(self.n_batch)
+        d_draw, x, y = self._device_feed(draw, x_side)
+        d_titles = self.ctx.train_titles(ts, d_draw)
+        if self._ones_use is None:
+            self._ones_use = torch.ones(self.n_batch, dtype=torch.float32, device=d_draw.device)
+        return self._title_step_csr(x, y, d_titles, self._ones_use, keep_prob, input_keep_prob, title_keep_prob, fetch_cost)
 
     def _host_feed_step(self, draw, x_side, keep_prob, input_keep_prob, fetch_cost, title_keep_prob=1.0):
-        """The title step of the batch a draw names (always fetches its cost, as `train_step` here does): the feed AND the
-        titles rebuilt on the host from the attached reader."""
+        """The title step of the batch a draw names, the feed AND the titles rebuilt on the host from the attached reader:
+        what `train_step_draw` computes, through `train_step`'s uploads (the fallback for a set without titles)."""
         from ..utils.data_reader import feed_from_draw
         reader = self._train_feed["reader"]
         x_pos, x_val, y_pos = feed_from_draw(reader, draw, x_side)
         return self.train_step(x_pos, x_val, y_pos, np.ones(len(y_pos), np.float32), keep_prob, input_keep_prob,
                                titles=[reader._title(int(i)) for i in draw[0]],
-                               titles_use=np.ones(self.n_batch, np.float32), title_keep_prob=title_keep_prob)
+                               titles_use=np.ones(self.n_batch, np.float32), title_keep_prob=title_keep_prob,
+                               fetch_cost=fetch_cost)
 
     def _submit(self, x_positions, x_ones, seeds, k, dtype, titles=None, titles_use=None, n_rows=None):
         """One batch enqueued, nothing fetched (`n_rows`: rows of this launch when it is not the model's batch).  Without

@@ -182,17 +182,31 @@ class Char_CNN:
             self.ctx.check(self.ctx.lib.dae_title_prepack_features(self.ctx.h, None, 0, 0, None, None, 0, 0))
         self._ftab_gen = None
 
+    def titles_to_device(self, titles, n_rows):
+        """Host title rows -> the int32 CUDA tensor [n_rows, strmaxlen] the kernels read (staged, then uploaded)."""
+        import torch
+        t = np.full((n_rows, self.input_len), -1, np.int32)                   # -1: no character (rows without a title, padding)
+        src = np.asarray(titles, np.int64).reshape(-1, self.input_len) if len(titles) else np.zeros((0, self.input_len))
+        t[:len(src)] = src[:n_rows]
+        return torch.from_numpy(t).to(self.p["conv_w"].device)
+
     def features(self, titles, n_rows, keep_prob=1.0, seed=0, keep_for_backward=False):
-        """Char_CNN.py:23-63 -> feat [n_rows, ld] (CUDA); with keep_for_backward also (argmax, raw)."""
+        """Char_CNN.py:23-63 -> feat [n_rows, ld] (CUDA); with keep_for_backward also (argmax, raw).  `titles`: host rows
+        (staged and uploaded here), or an int32 CUDA tensor [n_rows, strmaxlen] that is read where it lies (the device
+        training feed, dae_train_titles)."""
         import torch
         self.ctx.bind_stream()
         if keep_prob == 1.0 and not keep_for_backward:
             self._ensure_features_table()
         dev = self.p["conv_w"].device
-        t = np.full((n_rows, self.input_len), -1, np.int32)                   # -1: no character (rows without a title, padding)
-        src = np.asarray(titles, np.int64).reshape(-1, self.input_len) if len(titles) else np.zeros((0, self.input_len))
-        t[:len(src)] = src[:n_rows]
-        d_t = torch.from_numpy(t).to(dev)
+        if isinstance(titles, torch.Tensor):
+            if (titles.dtype != torch.int32 or titles.device != dev or tuple(titles.shape) != (n_rows, self.input_len)
+                    or not titles.is_contiguous()):
+                raise ValueError("device titles: a contiguous int32 tensor [%d, %d] on %s is required, got %s %s on %s"
+                                 % (n_rows, self.input_len, dev, titles.dtype, tuple(titles.shape), titles.device))
+            d_t = titles
+        else:
+            d_t = self.titles_to_device(titles, n_rows)
         feat = torch.empty((n_rows, self.ld), dtype=torch.float32, device=dev)
         arg = torch.empty((n_rows, self.n_feat), dtype=torch.int32, device=dev) if keep_for_backward else None
         raw = torch.empty((n_rows, self.n_feat), dtype=torch.float32, device=dev) if keep_for_backward else None
