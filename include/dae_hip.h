@@ -284,7 +284,7 @@ int dae_set_exact_margin_range(dae_ctx* ctx, int col_from, int col_to, float sca
  * Under the exact title mix (dae_mix_topk_exact / dae_title_score; set on the TITLE context, same defaults) the audit tests the
  * OUTCOME instead: the sampled tiles' mixed scores, recomputed with the canonical chains of both images and the fp32 path's mix
  * (DAEs.py:153-181), against the lists the launch just wrote -- an element above its row's k-th listed score that is neither
- * listed nor one of the row's seeds counts as a violation in the title context's guard words (csrc/mixexact.hip mix_audit). */
+ * listed nor one of the row's seeds counts as a violation in the title context's guard words (csrc/audit.hip dae_launch_mix_audit). */
 int dae_set_exact_audit(dae_ctx* ctx, int every_n, int n_tiles);
 int dae_exact_audit_read(dae_ctx* ctx, uint64_t out3[3]);
 
@@ -614,7 +614,7 @@ int dae_set_score_mix(dae_ctx* ctx, const float* mixT, int64_t ld, int n_cols, c
  * No [B, V] matrix and no transposed term.  Called on the TITLE scorer's context; `dae` is the DAE's.  Both must hold
  * their weights prepacked with DAE_DTYPE_BF16_EXACT over the same columns [0, V), and be bound to the same stream.
  * SHAPES: dae_mix_exact_shape_ok(hidden, ld_feat) -- DAE hidden 128 .. 512 and title rows (Output_W^T, the feature row
- * length) 64 .. 512, both in steps of 64.  The launch was built for hidden 256 and rows of 448, which keep a kernel unrolled
+ * length) 64 .. 512, both in steps of 64.  Hidden 256 and rows of 448, the shipped shape, keep a kernel unrolled
  * for them; the other shapes share one kernel that takes the two step counts at run time (row groups of 96 playlists while
  * both scorers' rows fit the CU's LDS, of 64 beyond hidden + row length 832).  Any other shape: DAE_ERR_ARG -- rank it
  * with DAE_DTYPE_F32, which returns the same lists.  feat [B][ld_feat]: title features (dae_title_features; any finite

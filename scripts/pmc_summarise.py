@@ -129,7 +129,7 @@ if len(trn) > 3:
 f = per_kernel(os.path.join(root, "%s_pmc_title_fetch.csv" % PFX))
 w = per_kernel(os.path.join(root, "%s_pmc_title_write.csv" % PFX))
 ttl = {"source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE -- python scripts/time_title.py exact_bf16 20",
-       "fetch_correction": dec["fetch_correction"], "kernel_source_sha256_16": dict(sha, **{"mixexact.hip": src_sha("mixexact.hip")})}
+       "fetch_correction": dec["fetch_correction"], "kernel_source_sha256_16": dict(sha, **{n: src_sha(n) for n in ("mix_filter.hip", "mix_refine.hip", "mix_common.h")})}
 for key, sub in (("mix_filter", "mix_bf16_kernel<16, 28, 3, 8, 8, 0>"), ("mix_sample", "mix_bf16_kernel<16, 28, 3, 8, 8, 1>"),
                  ("mix_refine", "mix_refine_kernel"), ("title_features", "title_features_mfma_kernel")):
     kn, fd = find(f, sub)

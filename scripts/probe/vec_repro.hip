@@ -1,5 +1,5 @@
 // vec_repro.hip -- reduced reproducer of round 4's "loop vectorizer miscompile" (profiles/r04_notes.md 11d, VERDICT r4 Weak #4):
-// the per-lane staging loop of mix_refine_kernel as it stood at commit d614ea5, with and without
+// the per-lane staging loop of mix_refine_kernel (csrc/mix_refine.hip) as it stood at commit d614ea5, with and without
 // `#pragma clang loop vectorize(disable) interleave(disable)`, checked against a one-thread recomputation of every staged key.
 // Build + run: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fno-fast-math scripts/probe/vec_repro.hip -o vec_repro && ./vec_repro
 #include <hip/hip_runtime.h>

@@ -16,6 +16,7 @@
 // (prepack.hip exact_bounds_kernel); survivors are CHECKED always; dropped columns are checked on a SAMPLE (all rows x
 // n_tiles x 32 columns every N-th launch; over a loop every tile comes up); nothing else is assumed.
 #include "dae_internal.h"
+#include "mix_common.h"            // mixf
 
 #include <limits.h>
 #include <string.h>
@@ -45,7 +46,7 @@ struct AuditP {
     const int* row_bad;                              // nullable: rows outside the bound's precondition
     int* guard; unsigned long long* stat;            // guard words {violations, a column}; {elements checked, violations}
     float* zout;                                     // non-null: no test here -- z32 goes out ([B][n_tiles * 32], like u) for the
-                                                     // caller's own (the exact title mix: mixexact.hip mix_audit_kernel)
+                                                     // caller's own (the exact title mix: mix_audit_kernel below)
 };
 
 // workgroup (pair of sampled tiles = 64 columns, block of AU_ROWS playlists); lane = column, a wave walks 8 playlists.
@@ -124,6 +125,56 @@ __global__ __launch_bounds__(256) void exact_audit_kernel(const AuditP p)
     }
 }
 
+// ---- the exact title mix's audit of dropped columns (round 6; the plain exact mode's is the kernel above) --------------------
+// The refine launch's guard sees survivors only; a column the filter launch dropped is never recomputed.  Every N-th launch
+// (dae_set_exact_audit on the TITLE context) a random set of ranked tiles is recomputed in fp32 for every row -- z_t and z_d
+// with the canonical chains (exact_audit_kernel's zout mode, both images), mixed as the lists' scores are -- and tested against the
+// lists THIS launch wrote: an element whose score lies above the row's k-th listed score must be in the list or among the
+// row's seeds.  Anything else is a column the filter dropped although it belongs in the list: counted in the title context's
+// guard words (DAE_title.recommend / dae_pipeline_poll re-score such a launch with the fp32 kernels, as for a survivor).
+// This tests the OUTCOME (main_challenge.py:26-36 on DAEs.py:180's y), whatever the bound's shape; ties with the k-th score
+// are not judged.
+struct MixAuditP {
+    const float* zt; const float* zd; int64_t ld_z;  // [B][n_tiles * 32] canonical logits of the sampled tiles
+    const int* tiles; int n_tiles; int B, k, n_valid_col;
+    const float* w_t; const float* w_p; const int* row_bad;
+    const float* out_score; const int32_t* out_idx;  // the launch's lists [B][k]
+    const int32_t* seed_row_ptr; const int32_t* seed_col;
+    int* guard; unsigned long long* stat;
+};
+
+__global__ __launch_bounds__(256) void mix_audit_kernel(const MixAuditP p)
+{
+    const int per_row = p.n_tiles * 32;
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int row = (int)(e / per_row), j = (int)(e % per_row);
+    bool counted = false, bad = false;
+    if (row < p.B && !p.row_bad[row]) {
+        const float wt = p.w_t[row], wp = p.w_p[row];
+        const int col = p.tiles[j >> 5] * 32 + (j & 31);
+        const float zt = p.zt[(size_t)row * p.ld_z + j], zd = p.zd[(size_t)row * p.ld_z + j];
+        if (col < p.n_valid_col && zt > -__builtin_inff() && zd > -__builtin_inff() && !(wt == 0.0f && wp == 0.0f)) {
+            counted = true;
+            const float s = mixf(zt, zd, wt, wp);
+            const size_t last = (size_t)row * p.k + (p.k - 1);
+            const float thr = p.out_idx[last] < 0 ? -__builtin_inff() : p.out_score[last];      // (a short list: every column belongs)
+            if (s > thr) {
+                bool found = false;
+                for (int i = 0; i < p.k && !found; ++i) found = p.out_idx[(size_t)row * p.k + i] == col;
+                if (!found && p.seed_row_ptr)
+                    for (int i = p.seed_row_ptr[row]; i < p.seed_row_ptr[row + 1] && !found; ++i) found = p.seed_col[i] == col;
+                bad = !found;
+                if (bad) { atomicAdd(p.guard, 1); p.guard[1] = col; }
+            }
+        }
+    }
+    const unsigned nc = (unsigned)__popcll(__ballot(counted)), nb = (unsigned)__popcll(__ballot(bad));
+    if ((threadIdx.x & 63) == 0 && nc) {
+        atomicAdd(p.stat, (unsigned long long)nc);
+        if (nb) atomicAdd(p.stat + 1, (unsigned long long)nb);
+    }
+}
+
 }  // namespace
 
 static int launch_audit_kernel(dae_ctx* ctx, const AuditP& p)
@@ -164,6 +215,42 @@ int dae_launch_audit_chains(dae_ctx* ctx, const float* h, int64_t ld_h, int H, c
     p.h = h; p.ld_h = ld_h; p.H = H; p.W32 = W32; p.bias = bias; p.ncols = ncols; p.col_bound = col_bound;
     p.tiles = tiles; p.n_tiles = n_tiles; p.B = B; p.ld_u = (int64_t)n_tiles * 32; p.zout = zout;
     return launch_audit_kernel(ctx, p);
+}
+
+// one audit of the exact title mix's launch in progress (title context tc, DAE context dc): the lists it just wrote against the
+// canonical mixed scores of n random ranked tiles (mix_audit_kernel)
+int dae_launch_mix_audit(dae_ctx* tc, dae_ctx* dc, int n_valid_col, const dae_mix_call& c)
+{
+    if (tc->audit_every <= 0 || tc->audit_tiles <= 0 || !c.out_score || !c.out_idx) return DAE_OK;
+    const int B = c.B;
+    if ((++tc->audit_seq % (uint64_t)tc->audit_every) != 0) return DAE_OK;
+    const dae_packed& pt = tc->pk_bf16;
+    const dae_packed& pd = dc->pk_bf16;
+    const int n_tiles = tc->audit_tiles > 64 ? 64 : tc->audit_tiles;
+    unsigned long long* stat; int* tiles;
+    int rc = dae_audit_pick_tiles(tc, (n_valid_col + 31) / 32, n_tiles, &stat, &tiles);
+    if (rc) return rc;
+    const size_t per = (size_t)B * n_tiles * 32;
+    rc = dae_reserve(tc, tc->audit, 2 * per * sizeof(float));
+    if (rc) return rc;
+    float* zt = static_cast<float*>(tc->audit.p);
+    float* zd = zt + per;
+    rc = dae_launch_audit_chains(tc, c.feat, c.ld_feat, pt.H, static_cast<const float*>(pt.W32.p), static_cast<const float*>(pt.bias.p),
+                                 pt.col_hi - pt.col_lo, n_valid_col, B, tiles, n_tiles, zt);
+    if (rc) return rc;
+    rc = dae_launch_audit_chains(tc, c.h, c.ld_h, pd.H, static_cast<const float*>(pd.W32.p), static_cast<const float*>(pd.bias.p),
+                                 pd.col_hi - pd.col_lo, n_valid_col, B, tiles, n_tiles, zd);
+    if (rc) return rc;
+    MixAuditP a;
+    a.zt = zt; a.zd = zd; a.ld_z = (int64_t)n_tiles * 32; a.tiles = tiles; a.n_tiles = n_tiles; a.B = B; a.k = c.k;
+    a.n_valid_col = n_valid_col; a.w_t = c.w_title; a.w_p = c.w_playlist; a.row_bad = static_cast<const int*>(tc->row_bad.p);
+    a.out_score = c.out_score; a.out_idx = c.out_idx; a.seed_row_ptr = c.seed_row_ptr; a.seed_col = c.seed_col;
+    a.guard = static_cast<int*>(tc->guard.p); a.stat = stat;
+    const int64_t total = (int64_t)per;
+    hipLaunchKernelGGL(mix_audit_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, tc->stream, a);
+    DAE_CHECK_LAUNCH(tc, "mix_audit_kernel");
+    ++tc->audits_run;
+    return DAE_OK;
 }
 
 // one audit of the scoring launch in progress on ctx (its packed bf16 hidden tile and fp32 rows are still in place)

@@ -13,6 +13,7 @@
 
 #include "../../include/dae_hip.h"
 #include "score_plan.h"            // dae_rowgeom, the host planners, DAE_KG / DAE_MAX_K / DAE_NUM_CU / DAE_NUM_XCD
+#include "mix_plan.h"              // dae_mix_plan: the same for the exact title mix
 
 // ---------------------------------------------------------------------------------------------
 // geometry constants of the decode path (see DESIGN.md "HBM layout")
@@ -61,7 +62,7 @@ struct dae_packed {            // one prepacked decoder image
     dae_buf eps;               // [ntiles*32] fp32, zero padded; then one more float: the maximum (eps_max)
     dae_buf bias16_lo, bias16_hi;   // [ntiles][64] uint4, as bias16
     dae_buf W32;               // [col_hi - col_lo][H] fp32 row-major
-    // the same image as the TITLE side of the exact title mix (mixexact.hip): hidden rows with entries in [-F_r, F_r],
+    // the same image as the TITLE side of the exact title mix (mix_common.h): hidden rows with entries in [-F_r, F_r],
     // |z32 - z16| <= F_r alpha_c + beta_c; the bias fragments carry b -+ beta in k-slots 0..2 and -+alpha (bf16) in slot 3
     dae_buf mix_alpha, mix_beta;    // [ntiles*32] fp32 (alpha: the bf16 value the fragments hold)
     dae_buf mix16_lo, mix16_hi;     // [ntiles][64] uint4
@@ -435,10 +436,25 @@ int dae_launch_title_conv_backward(dae_ctx* ctx, const int32_t* titles, int B, i
 int dae_launch_mix_scores(dae_ctx* ctx, const float* title_score, int64_t ld_t, float* dae_score, int64_t ld_d,
                           const float* w_title, const float* w_playlist, int B, int ncols);
 
-// mixexact.hip (DAE_DTYPE_BF16_EXACT under the title mix)
+// the exact title mix (DAE_DTYPE_BF16_EXACT under the title mix): mixexact.hip is the call, mix_plan.h its geometry
+// mix_prep.hip: the title image's row-scaled bounds (once per image, from prepack.hip)
 int dae_launch_mix_title_bounds(dae_ctx* ctx, const float* W, const float* b, int H, int Hp, int col_lo, int col_hi,
                                 int ntiles, dae_packed& pk);
-void dae_note_plan(int R_TILE, int n_rg, int nb_rg, int n_samp, int n_filter, int ntiles);      // score.hip: what dae_last_plan reports
+struct dae_mix_call {       // the caller's arguments of dae_mix_topk_exact that its launches read
+    const float* feat; int64_t ld_feat;           // title features [B][ld_feat]
+    const float* h; int64_t ld_h;                 // DAE hidden rows [B][ld_h]
+    int B;
+    const float* w_title; const float* w_playlist;                    // [B] mixing weights
+    const int32_t* seed_row_ptr; const int32_t* seed_col;
+    int k; float* out_score; int32_t* out_idx;
+};
+// The launches of one call, in its order; each reads and writes the title context's scratch, reserved by the caller for pl.
+int dae_launch_mix_prep_pack(dae_ctx* tc, const dae_mix_plan& pl, int HD, int HT, const dae_mix_call& c);             // mix_prep.hip
+int dae_launch_mix_pass(dae_ctx* tc, const dae_mix_plan& pl, bool sample, const dae_packed& pd, const dae_packed& pt,    // mix_filter.hip
+                        const int* order, const dae_mix_call& c);
+int dae_launch_mix_refine(dae_ctx* tc, const dae_mix_plan& pl, const dae_packed& pd, const dae_packed& pt, const dae_mix_call& c);   // mix_refine.hip
+int dae_launch_mix_audit(dae_ctx* tc, dae_ctx* dc, int n_valid_col, const dae_mix_call& c);                           // audit.hip
+void dae_note_plan(const int32_t last[8]);      // score.hip: what dae_last_plan reports
 int dae_mix_topk_exact_impl(dae_ctx* tc, dae_ctx* dc, const float* feat, int64_t ld_feat, const float* h, int64_t ld_h, int B,
                             const float* w_title, const float* w_playlist, int n_tracks, const int32_t* seed_row_ptr,
                             const int32_t* seed_col, int k, float* out_score, int32_t* out_idx);
@@ -498,7 +514,7 @@ struct dae_exact_src {
 // leaves behind are not meant to be read
 // audit.hip: one audit of the exact scoring launch in progress (n_tiles random ranked tiles x all B rows -> the guard words)
 int dae_launch_exact_audit(dae_ctx* ctx, const dae_rowgeom& g, int B, const dae_exact_src& x, int nrank, int n_tiles);
-// (pieces the exact title mix's audit shares: mixexact.hip mix_audit) this audit's tile ids + the context's totals; the canonical
+// (pieces the exact title mix's audit shares: dae_launch_mix_audit) this audit's tile ids + the context's totals; the canonical
 // logits of those tiles for rows [0, B) into zout[B][n_tiles * 32]
 int dae_audit_pick_tiles(dae_ctx* ctx, int n_rank_tiles, int n_tiles, unsigned long long** stat_out, int** tiles_out);
 int dae_launch_audit_chains(dae_ctx* ctx, const float* h, int64_t ld_h, int H, const float* W32, const float* bias, int ncols,

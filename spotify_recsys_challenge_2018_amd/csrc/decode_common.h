@@ -1,5 +1,5 @@
 // decode_common.h -- what the decode translation units (decode_f32.hip, decode_generic.hip, prepack.hip) share with each
-// other and with the kernels built on the same MFMA fragments (mixexact.hip, refine.hip, title.hip, train.hip): vector
+// other and with the kernels built on the same MFMA fragments (mix_filter.hip, refine.hip, title.hip, train.hip): vector
 // types, bf16 helpers, the decode kernels' argument block, and the loss head of the training step.
 #pragma once
 #include "dae_internal.h"

@@ -1,7 +1,7 @@
 // rank_lds.h -- the tail of the ranking (main_challenge.py:26-36: argsort descending, drop the seeds, keep k) for a row whose
 // candidates already sit in LDS as unique composite keys  (okey(score) << 32) | ~column  -- the order topk.hip defines:
 // score descending, column ascending.  Used by the kernels that end a scoring call with the row's candidates in hand
-// (refine.hip: the exact mode's recomputed survivors; mixexact.hip: the exact title mix), so that no separate selection
+// (refine.hip: the exact mode's recomputed survivors; mix_refine.hip: the exact title mix), so that no separate selection
 // launch has to read them back.  Same stages as topk_kernel's step 5a (order by histogram rank), same results.
 #pragma once
 #include "dae_internal.h"

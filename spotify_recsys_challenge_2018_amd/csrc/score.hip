@@ -1,6 +1,6 @@
 // score.hip -- the launch sequences of the scoring path behind dae_decode_dense / dae_decode_topk / dae_score_topk* and the
 // titled calls: pack or encode the hidden rows, plan the call (score_plan.h dae_plan_topk), reserve scratch, launch.  The
-// kernels are those of decode_*.hip, topk.hip, refine.hip, audit.hip and mixexact.hip; here live only the two fill kernels.
+// kernels are those of decode_*.hip, topk.hip, refine.hip, audit.hip and mix_*.hip; here live only the two fill kernels.
 #include <climits>
 
 #include "dae_internal.h"
@@ -72,11 +72,10 @@ const dae_packed* packed_for(dae_ctx* ctx, int dtype, int H)
 
 }  // namespace
 
-// dae_mix_topk_exact leaves its geometry in the same words (mixexact.hip): S = 1, fused = 0; ntiles = the ranked tiles it walks
-void dae_note_plan(int R_TILE, int n_rg, int nb_rg, int n_samp, int n_filter, int ntiles)
+// dae_mix_topk_exact leaves its geometry in the same words (mix_plan.h dae_plan_mix): S = 1, fused = 0; ntiles = the ranked tiles it walks
+void dae_note_plan(const int32_t last[8])
 {
-    const int32_t w[8] = {R_TILE, n_rg, nb_rg, 1, n_samp, n_filter, 0, ntiles};
-    memcpy(g_last_plan, w, sizeof(w));
+    memcpy(g_last_plan, last, 8 * sizeof(int32_t));
 }
 
 extern "C" {

@@ -31,7 +31,7 @@ _DECODE_DTYPES = {"f32": _lib.DAE_DTYPE_F32, "bf16": _lib.DAE_DTYPE_BF16, "exact
 
 
 def _title_dtype(dtype, model):
-    """Arithmetic of a title-mixed launch.  exact_bf16 has its own two-GEMM path (dae_mix_topk_exact, csrc/mixexact.hip)
+    """Arithmetic of a title-mixed launch.  exact_bf16 has its own two-GEMM path (dae_mix_topk_exact, csrc/mixexact.hip and mix_*.hip)
     for the shapes the library says it takes (dae_mix_exact_shape_ok: DAE hidden 128 .. 512, title feature rows of 64 .. 512,
     both in steps of 64); any other model runs its titled launches on the fp32 kernels (the lists exact_bf16 promises are
     the fp32 lists either way)."""
@@ -883,7 +883,7 @@ class DAE_title(DAE):
 
     with u = titles_use in {0, 1} per row (:156-162).  u = 0 gives w_playlist = 1.0f exactly, i.e. the plain
     DAE -- those batches take the fused scoring path.  With titles, `recommend` ranks the mixed score
-    without either vocabulary-wide matrix (`_submit`; exact_bf16: both GEMMs in one launch per pass, csrc/mixexact.hip) and
+    without either vocabulary-wide matrix (`_submit`; exact_bf16: both GEMMs in one launch per pass, csrc/mix_filter.hip) and
     the streamed loops run their titled launches on the library's pipeline; only the dense fetch of
     the protocol, `mixed_scores`, materialises the two matrices (`dae_mix_scores`)."""
 
@@ -1094,7 +1094,7 @@ class DAE_title(DAE):
         score = torch.empty((nb, k), dtype=torch.float32, device=dev)
         idx = torch.empty((nb, k), dtype=torch.int32, device=dev)
         if dtype == _lib.DAE_DTYPE_BF16_EXACT:
-            # both GEMMs on bf16 operands in one launch per pass, the survivors recomputed in fp32 (csrc/mixexact.hip)
+            # both GEMMs on bf16 operands in one launch per pass, the survivors recomputed in fp32 (csrc/mixexact.hip, mix_*.hip)
             gw = torch.empty(2, dtype=torch.int32, device=dev)
             tm.ctx.mix_topk_exact(self.ctx, feat, h, w_t, w_p, self.n_tracks, d_srp, d_sc, k, score, idx, guard_out=gw)
             # the guard words travel with the lists; what a re-scoring in fp32 needs, should they have moved

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): DAE_DTYPE_BF16_EXACT under the title mix (dae_mix_topk_exact, csrc/mixexact.hip) -- what `--challenge`
+"""GPU (-m gpu): DAE_DTYPE_BF16_EXACT under the title mix (dae_mix_topk_exact, csrc/mixexact.hip and mix_*.hip) -- what `--challenge`
 ranks for every titled batch (reference main_challenge.py:80-90, DAEs.py:153-181).  The bar is the exact mode's: the lists
 (indices AND score bits) of the fp32 title path, which tests/test_gpu_title.py pins to the oracle's ranking rule on the
 numpy restatement of the mix."""
@@ -267,7 +267,7 @@ def test_exact_title_mix_guard_and_fallback(tmp_path):
     _same(got, want)
 
 
-# ---- round 6: the audit of DROPPED columns under the title mix (csrc/mixexact.hip mix_audit) -----------------------------------
+# ---- round 6: the audit of DROPPED columns under the title mix (csrc/audit.hip dae_launch_mix_audit) -----------------------------------
 def test_title_mix_audit_is_silent_on_honest_images_and_counts_its_work(tmp_path):
     """Every launch audited (dae_set_exact_audit(1, 16) on the title context): 16 random ranked tiles x all rows recomputed in
     fp32 and held against the lists the launch wrote -- nothing above a row's k-th score is missing from its list, the lists
@@ -372,7 +372,7 @@ def test_exact_title_mix_other_shapes_run_fp32(tmp_path, capfd):
     feat = torch.zeros((4, tm.ld), device=dev); h = torch.zeros((4, 64), device=dev)
     w = torch.ones(4, device=dev)
     sc = torch.empty((4, 10), device=dev); ix = torch.empty((4, 10), dtype=torch.int32, device=dev)
-    with pytest.raises(_lib.DaeError, match="hidden 256"):
+    with pytest.raises(_lib.DaeError, match=r"hidden 128\.\.512"):
         tm.ctx.mix_topk_exact(m.ctx, feat, h, w, w, conf.n_tracks, None, None, 10, sc, ix)
 
 

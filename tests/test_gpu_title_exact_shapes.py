@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the exact title mix (dae_mix_topk_exact, csrc/mixexact.hip) at DAE hidden sizes and title feature row
+"""GPU (-m gpu): the exact title mix (dae_mix_topk_exact, csrc/mixexact.hip and mix_*.hip) at DAE hidden sizes and title feature row
 lengths other than the shipped 256 / 448 -- `[DAE] hidden`, `[TITLE] filter_num` and `filter_size` are free keys of the
 reference's schema (main.py:46, :73-75).  The supported set is dae_mix_exact_shape_ok's: hidden 128 .. 512, rows of 64 .. 512,
 both in steps of 64; those shapes run the two-GEMM bf16 launches (mix_bf16_steps_kernel: the step counts at run time, row
@@ -76,6 +76,24 @@ def test_exact_title_mix_shapes_return_the_fp32_lists(tmp_path, capfd, hidden, f
             assert plan["R_TILE"] == rows_per_group and plan["n_rg"] == -(-batch // rows_per_group), plan
         assert not getattr(m, "_guard_fallbacks", 0)
     assert FALLBACK_LINE not in capfd.readouterr().err
+
+
+@pytest.mark.parametrize("hidden,filter_num", [(256, 100), (128, 16)])
+def test_exact_title_mix_unfused_selection_above_k_512(tmp_path, hidden, filter_num):
+    """k above 512: the refine launch cannot order the row itself (mix_plan.h `fuse`), so it leaves its compact lists and the
+    selection kernel behind it ends the call.  The shipped shape and hidden 128 / rows of 64, one partial row group."""
+    conf, m = _shape_model(tmp_path, hidden, filter_num, 24)
+    tm = m.title_model
+    for trial, k in enumerate((513, 777)):
+        pos, ones, seeds, titles, use = _case(conf, trial)
+        want = m.recommend(pos, ones, seeds, k=k, titles=titles, titles_use=use, dtype="f32")
+        with warnings.catch_warnings():
+            warnings.simplefilter("error")
+            got = m.recommend(pos, ones, seeds, k=k, titles=titles, titles_use=use, dtype="exact_bf16")
+        _same(got, want)
+        assert tm.ctx.exact_stats_read()["rows"] == 24                # the two-GEMM launches ran
+        assert tm.ctx.exact_guard_read()[0] == 0
+    assert not getattr(m, "_guard_fallbacks", 0)
 
 
 # (hidden, filter_num, feature row length, playlists per row group, tracks, columns)
@@ -248,7 +266,7 @@ def test_exact_title_mix_shapes_still_outside(tmp_path, capfd, hidden, filter_nu
     _same(got, want)
     _same(got2, want)
     assert m.title_model.ctx.exact_stats_read()["rows"] == 0          # no two-GEMM launch ran
-    with pytest.raises(_lib.DaeError, match="hidden 256"):
+    with pytest.raises(_lib.DaeError, match=r"hidden 128\.\.512"):
         _c_call(m, conf, case, 10)
 
 
