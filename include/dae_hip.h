@@ -680,6 +680,21 @@ int dae_title_loss_backward(dae_ctx* ctx, const float* title_logits, int64_t ld_
                             const float* w_title, const float* w_playlist, int B, int V, int n_batch,
                             const float* feat, int ld, const float* Output_WT, float* gOutput_WT, float* gOutput_b,
                             float* dfeat, float* cost_out);
+/* dae_title_loss_backward restricted to the vocabulary columns [col_lo, col_hi) -- one rank's part of a vocabulary-sharded
+ * title step.  title_logits / dae_score are [B, col_hi - col_lo]: column j is global column col_lo + j.  The y CSR is the
+ * WHOLE batch's, with global column ids, ASCENDING AND UNIQUE within a row (what dae_coo_to_csr and dae_train_batch write):
+ * the kernel binary-searches a row for its window; targets outside the window are ignored.  Output_WT_rows / gOutput_WT_rows
+ * [col_hi - col_lo, ld] and gOutput_b_rows [col_hi - col_lo] are the rows col_lo .. col_hi of the full arrays.  dfeat_partial
+ * [B, ld] and cost_partial are this window's ADDENDS of dfeat and of the cost (1 / n_batch applied, as in the dense call):
+ * summed over a partition of the columns they give the dense call's values up to the order of the sum.  No [B, V] target
+ * matrix is built.  On the same window the outputs equal, bit for bit, those of dae_title_loss_backward called with
+ * V = col_hi - col_lo on the sliced inputs.
+ * DAE_ERR_ARG before any launch: col_lo < 0, col_hi <= col_lo, B < 1, B > 256, ld % 32 != 0. */
+int dae_title_loss_backward_cols(dae_ctx* ctx, const float* title_logits, int64_t ld_z, const float* dae_score, int64_t ld_d,
+                                 const int32_t* y_row_ptr, const int32_t* y_col, const float* y_val,
+                                 const float* w_title, const float* w_playlist, int B, int col_lo, int col_hi, int n_batch,
+                                 const float* feat, int ld, const float* Output_WT_rows, float* gOutput_WT_rows,
+                                 float* gOutput_b_rows, float* dfeat_partial, float* cost_partial);
 int dae_title_conv_backward(dae_ctx* ctx, const int32_t* titles, int B, int L, const float* emb, int n_char, int E,
                             const float* conv_w, const int32_t* filter_sizes, int n_sizes, int F,
                             const int32_t* argmax, const float* feat_raw, const float* dfeat, int64_t ld,

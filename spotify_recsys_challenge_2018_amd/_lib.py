@@ -20,7 +20,7 @@ EXPORTS = [
     "dae_set_filter_skip", "dae_filter_skip_read", "dae_filter_skip_last", "dae_tile_bounds_read", "dae_decode_dense", "dae_decode_topk",
     "dae_score_topk", "dae_score_topk_begin", "dae_score_topk_finish", "dae_topk_dense", "dae_topk_merge", "dae_set_train_dtype", "dae_train_forward_backward",
     "dae_train_shard_encode", "dae_train_shard_decode", "dae_train_shard_finish", "dae_title_features", "dae_title_prepack_features",
-    "dae_mix_scores", "dae_decode_mix_term", "dae_set_score_mix", "dae_mix_topk_exact", "dae_mix_exact_shape_ok", "dae_title_score_exact", "dae_title_score", "dae_row_sums", "dae_mix_weights", "dae_title_loss_backward", "dae_title_conv_backward", "dae_adam_step",
+    "dae_mix_scores", "dae_decode_mix_term", "dae_set_score_mix", "dae_mix_topk_exact", "dae_mix_exact_shape_ok", "dae_title_score_exact", "dae_title_score", "dae_row_sums", "dae_mix_weights", "dae_title_loss_backward", "dae_title_loss_backward_cols", "dae_title_conv_backward", "dae_adam_step",
     "dae_adam_rows_begin", "dae_adam_rows_apply", "dae_adam_rows_flush", "dae_set_enc_grad_prezeroed",
     "dae_arm_decoder_adam", "dae_set_decode_gate", "dae_set_overlap_hint",
     "dae_pipeline_create", "dae_pipeline_create_titled", "dae_pipeline_destroy", "dae_pipeline_submit", "dae_pipeline_submit_titled", "dae_pipeline_flush", "dae_pipeline_poll",
@@ -121,6 +121,8 @@ def load():
     lib.dae_mix_weights.argtypes = [vp, vp, vp, vp, c_int, c_f, c_u32, vp, vp, vp]
     lib.dae_title_loss_backward.argtypes = [vp, vp, c_i64, vp, c_i64, vp, vp, vp, vp, vp, c_int, c_int, c_int,
                                             vp, c_int, vp, vp, vp, vp, vp]
+    lib.dae_title_loss_backward_cols.argtypes = [vp, vp, c_i64, vp, c_i64, vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int,
+                                                 vp, c_int, vp, vp, vp, vp, vp]
     lib.dae_title_conv_backward.argtypes = [vp, vp, c_int, c_int, vp, c_int, c_int, vp, ctypes.POINTER(ctypes.c_int32),
                                             c_int, c_int, vp, vp, vp, c_i64, c_f, c_u32, vp, vp, vp]
     lib.dae_adam_step.argtypes = [vp, vp, vp, vp, vp, c_i64, c_f, c_f, c_f, c_f, c_int]
@@ -362,6 +364,19 @@ class Context:
         assert W_rows.is_contiguous() and b_rows.is_contiguous() and b_rows.numel() == n
         self.check(self.lib.dae_prepack_decoder_rows(self.h, _ptr(W_rows), _ptr(b_rows), int(n), H, int(col_lo), int(dtype)))
         self._drop_share(dtype)
+
+    def title_loss_backward_cols(self, z_title, dae_score, y_csr, w_title, w_playlist, col_lo, col_hi, n_batch, feat,
+                                 Output_WT_rows, gOutput_WT_rows, gOutput_b_rows, dfeat_partial, cost_partial):
+        """The title loss head and the output layer's gradients on the vocabulary columns [col_lo, col_hi)
+        (dae_title_loss_backward_cols): z_title / dae_score [B, col_hi - col_lo], y_csr the WHOLE batch's (row_ptr, col,
+        val) with global ids, the *_rows tensors the rows col_lo .. col_hi of their arrays; dfeat_partial [B, ld] and
+        cost_partial [1] receive this window's addends."""
+        B, ld = feat.shape
+        self.check(self.lib.dae_title_loss_backward_cols(
+            self.h, _ptr(z_title), int(z_title.stride(0)), _ptr(dae_score), int(dae_score.stride(0)),
+            _ptr(y_csr[0]), _ptr(y_csr[1]), _ptr(y_csr[2]), _ptr(w_title), _ptr(w_playlist), int(B), int(col_lo), int(col_hi),
+            int(n_batch), _ptr(feat), int(ld), _ptr(Output_WT_rows), _ptr(gOutput_WT_rows), _ptr(gOutput_b_rows),
+            _ptr(dfeat_partial), _ptr(cost_partial)))
 
     def set_overlap_hint(self, batches_in_flight):
         """Other batches are in flight on other streams: kernel shapes that share CUs (include/dae_hip.h)."""

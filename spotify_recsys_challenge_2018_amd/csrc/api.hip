@@ -579,6 +579,26 @@ int dae_title_loss_backward(dae_ctx* ctx, const float* title_logits, int64_t ld_
                                           dfeat, cost_out);
 }
 
+int dae_title_loss_backward_cols(dae_ctx* ctx, const float* title_logits, int64_t ld_z, const float* dae_score, int64_t ld_d,
+                                 const int32_t* y_row_ptr, const int32_t* y_col, const float* y_val,
+                                 const float* w_title, const float* w_playlist, int B, int col_lo, int col_hi, int n_batch,
+                                 const float* feat, int ld, const float* Output_WT_rows, float* gOutput_WT_rows,
+                                 float* gOutput_b_rows, float* dfeat_partial, float* cost_partial)
+{
+    if (!ctx) return DAE_ERR_ARG;
+    if (!title_logits || !dae_score || !y_row_ptr || !w_title || !w_playlist || !feat || !Output_WT_rows || !gOutput_WT_rows ||
+        !gOutput_b_rows || !dfeat_partial || !cost_partial)
+        return dae_fail(ctx, DAE_ERR_ARG, "null pointer");
+    if (col_lo < 0 || col_hi <= col_lo) return dae_fail(ctx, DAE_ERR_ARG, "column window [%d, %d) is empty or negative", col_lo, col_hi);
+    if (B < 1 || B > 256) return dae_fail(ctx, DAE_ERR_ARG, "B=%d outside [1, 256]", B);
+    if (ld < 32 || (ld % 32) != 0) return dae_fail(ctx, DAE_ERR_ARG, "ld=%d is no multiple of 32", ld);
+    const int V = col_hi - col_lo;
+    if (n_batch <= 0 || ld_z < V || ld_d < V) return dae_fail(ctx, DAE_ERR_ARG, "bad shape");
+    return dae_launch_title_loss_backward_cols(ctx, title_logits, ld_z, dae_score, ld_d, y_row_ptr, y_col, y_val, w_title,
+                                               w_playlist, B, col_lo, col_hi, n_batch, feat, ld, Output_WT_rows,
+                                               gOutput_WT_rows, gOutput_b_rows, dfeat_partial, cost_partial);
+}
+
 int dae_title_conv_backward(dae_ctx* ctx, const int32_t* titles, int B, int L, const float* emb, int n_char, int E,
                             const float* conv_w, const int32_t* filter_sizes, int n_sizes, int F,
                             const int32_t* argmax, const float* feat_raw, const float* dfeat, int64_t ld,

@@ -429,6 +429,12 @@ int dae_launch_title_loss_backward(dae_ctx* ctx, const float* zt, int64_t ld_z, 
                                    const float* w_title, const float* w_playlist, int B, int V, int n_batch,
                                    const float* feat, int ld, const float* Output_WT, float* gOutput_WT,
                                    float* gOutput_b, float* dfeat, float* cost_out);
+int dae_launch_title_loss_backward_cols(dae_ctx* ctx, const float* zt, int64_t ld_z, const float* dae_score, int64_t ld_d,
+                                        const int32_t* y_row_ptr, const int32_t* y_col, const float* y_val,
+                                        const float* w_title, const float* w_playlist, int B, int col_lo, int col_hi,
+                                        int n_batch, const float* feat, int ld, const float* Output_WT_rows,
+                                        float* gOutput_WT_rows, float* gOutput_b_rows, float* dfeat_partial,
+                                        float* cost_partial);
 int dae_launch_title_conv_backward(dae_ctx* ctx, const int32_t* titles, int B, int L, const float* emb, int n_char,
                                    int E, const float* conv_w, const int32_t* filter_sizes, int n_sizes, int F,
                                    const int32_t* argmax, const float* feat_raw, const float* dfeat, int64_t ld,

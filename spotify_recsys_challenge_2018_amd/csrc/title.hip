@@ -445,6 +445,105 @@ __global__ __launch_bounds__(256) void title_loss_kernel(const float* __restrict
         loss_part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = ((wsum[0] + wsum[1]) + (wsum[2] + wsum[3])) * inv_nb;
 }
 
+// title_loss_kernel on the column window [col_lo, col_hi) of a vocabulary-sharded step: zt / dae hold the window's columns
+// (column j = global column col_lo + j, V = col_hi - col_lo of them), the targets come straight from the WHOLE batch's CSR
+// (global ids, ascending and unique within a row) -- no [B, V] target matrix.  The tile's targets are built in the LDS tile
+// the gradients leave through: zeroed, then lane r of the first 32 writes the (at most 32) entries of row r0 + r that lie in
+// [the tile's first global column, min(that + 32, col_hi)).  Every element is then read and overwritten by the same thread,
+// so one tile serves both.  A workgroup walks TLC_TILES consecutive column tiles: the lane binary-searches its row once,
+// for the first entry >= the first tile's first column, and its cursor moves on with the tiles (the entries ascend) -- a
+// search per tile is a chain of ~9 dependent reads in front of every tile's arithmetic (measured at V = 170 000, B = 150:
+// 127 us with a search per tile, 90 us with four tiles per walk; the dense kernel with its memset and scatter takes 113 us;
+// profiles/title_shard_notes.md).  The arithmetic
+// per element, the transposed store, the order of a tile's partial sum and its slot in loss_part are title_loss_kernel's:
+// on the same window the two write the same bits.
+constexpr int TLC_TILES = 4;
+__global__ __launch_bounds__(256) void title_loss_cols_kernel(const float* __restrict__ zt, int64_t ld_z,
+                                                              const float* __restrict__ dae, int64_t ld_d,
+                                                              const int32_t* __restrict__ y_row_ptr,
+                                                              const int32_t* __restrict__ y_col,
+                                                              const float* __restrict__ y_val, const float* __restrict__ wt,
+                                                              const float* __restrict__ wp, int B, int col_lo, int col_hi,
+                                                              float inv_nb, float* __restrict__ dzT, int64_t ldT,
+                                                              float* __restrict__ loss_part)
+{
+    __shared__ float tile[32][33];
+    __shared__ float wsum[4];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;          // 32 x 8
+    const int r0 = blockIdx.y * 32;
+    const int V = col_hi - col_lo;
+    const int n_tiles = (V + 31) >> 5;
+    const int t0 = blockIdx.x * TLC_TILES, t1 = min(t0 + TLC_TILES, n_tiles);
+    const bool walker = threadIdx.x < 32 && r0 + (int)threadIdx.x < B;    // this lane owns the targets of row r0 + threadIdx.x
+    int cur = 0, end = 0;                                             // its cursor into the row, and the row's end
+    for (int t = t0; t < t1; ++t) {
+        const int v0 = t * 32;
+        // the element loads go out first, all of them at once: the walker's reads below are a dependent chain of their own.
+        // Rows and columns past the end load the last one's values (unused) -- a load under a condition becomes a branch with
+        // a wait behind it, one memory round trip after the other (measured here: 4 of them in front of every tile)
+        float zs[4], ds[4], as[4], ws[4];
+        const int vc = min(v0 + tx, V - 1);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int rc = min(r0 + ty + 8 * i, B - 1);
+            zs[i] = zt[(size_t)rc * ld_z + vc];
+            ds[i] = dae[(size_t)rc * ld_d + vc];
+            as[i] = wt[rc];
+            ws[i] = wp[rc];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) tile[ty + 8 * i][tx] = 0.0f;
+        __syncthreads();
+        if (walker) {
+            const int g0 = col_lo + v0;                               // the tile's first global column
+            const int g1 = min(g0 + 32, col_hi);
+            if (t == t0) {                                            // first entry >= g0
+                cur = y_row_ptr[r0 + threadIdx.x];
+                end = y_row_ptr[r0 + threadIdx.x + 1];
+                int hi = end;
+                while (cur < hi) {
+                    const int mid = cur + ((hi - cur) >> 1);
+                    if (y_col[mid] < g0) cur = mid + 1; else hi = mid;
+                }
+            }
+            for (int n = 0; n < 32 && cur < end; ++n, ++cur) {
+                const int c = y_col[cur];
+                const float val = y_val[cur];                         // (with the column: one round trip per entry, not two)
+                if (c >= g1) break;
+                if (c >= g0) tile[threadIdx.x][c - g0] = val;         // (c < g0: only in a row that is not ascending)
+            }
+        }
+        __syncthreads();
+        float loss = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int r = r0 + ty + 8 * i, v = v0 + tx;
+            float dz = 0.0f;
+            if (r < B && v < V) {
+                const float z = zs[i];
+                const float st = 1.0f / (1.0f + __expf(-z));
+                const float a = as[i];
+                const float yp = st * a + ds[i] * ws[i];
+                const float tg = tile[ty + 8 * i][tx];
+                dz = dae_loss_head_mixed(yp, tg, inv_nb, loss) * a * st * (1.0f - st);
+            }
+            tile[ty + 8 * i][tx] = dz;                                // [r local][v local]
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int v = v0 + ty + 8 * i, r = r0 + tx;
+            if (v < V && r < ldT) dzT[(size_t)v * ldT + r] = tile[tx][ty + 8 * i];
+        }
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) loss += __shfl_xor(loss, d);
+        if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = loss;
+        __syncthreads();                                              // (also: the tile is read out before the next round zeroes it)
+        if (threadIdx.x == 0)
+            loss_part[(size_t)blockIdx.y * n_tiles + t] = ((wsum[0] + wsum[1]) + (wsum[2] + wsum[3])) * inv_nb;
+    }
+}
+
 __global__ void title_cost_kernel(const float* __restrict__ part, int n, float* __restrict__ cost)
 {
     __shared__ double ws[256];
@@ -597,6 +696,35 @@ int dae_launch_title_loss_backward(dae_ctx* ctx, const float* zt, int64_t ld_z, 
     DAE_CHECK_LAUNCH(ctx, "title_cost_kernel");
     if ((rc = dae_launch_grad_w(ctx, dzT, Bpad64, feat, ld, B, V, gOutput_WT, gOutput_b))) return rc;
     return dae_launch_grad_h(ctx, dzT, Bpad64, Output_WT, ld, V, B, dfeat);
+}
+
+// The same on the columns [col_lo, col_hi) alone (a vocabulary shard): every launch after the loss head sees V = col_hi -
+// col_lo, as the dense launcher called on the sliced problem does; train_a is not touched.
+int dae_launch_title_loss_backward_cols(dae_ctx* ctx, const float* zt, int64_t ld_z, const float* dae_score, int64_t ld_d,
+                                        const int32_t* y_row_ptr, const int32_t* y_col, const float* y_val,
+                                        const float* w_title, const float* w_playlist, int B, int col_lo, int col_hi,
+                                        int n_batch, const float* feat, int ld, const float* Output_WT_rows,
+                                        float* gOutput_WT_rows, float* gOutput_b_rows, float* dfeat_partial,
+                                        float* cost_partial)
+{
+    hipStream_t st = ctx->stream;
+    int rc;
+    const int V = col_hi - col_lo;
+    const int Bpad64 = (B + 63) / 64 * 64;
+    if ((rc = dae_reserve(ctx, ctx->train_b, (size_t)V * Bpad64 * sizeof(float)))) return rc;   // dz^T
+    const dim3 grid((V + 31) / 32, Bpad64 / 32);
+    const size_t n_part = (size_t)grid.x * grid.y;
+    if ((rc = dae_reserve(ctx, ctx->train_c, n_part * sizeof(float)))) return rc;
+    float* dzT = static_cast<float*>(ctx->train_b.p);
+    float* part = static_cast<float*>(ctx->train_c.p);
+    const dim3 grid_walk((grid.x + TLC_TILES - 1) / TLC_TILES, grid.y);      // a workgroup walks TLC_TILES column tiles
+    hipLaunchKernelGGL(title_loss_cols_kernel, grid_walk, dim3(256), 0, st, zt, ld_z, dae_score, ld_d, y_row_ptr, y_col, y_val,
+                       w_title, w_playlist, B, col_lo, col_hi, 1.0f / (float)n_batch, dzT, (int64_t)Bpad64, part);
+    DAE_CHECK_LAUNCH(ctx, "title_loss_cols_kernel");
+    hipLaunchKernelGGL(title_cost_kernel, dim3(1), dim3(256), 0, st, part, (int)n_part, cost_partial);
+    DAE_CHECK_LAUNCH(ctx, "title_cost_kernel");
+    if ((rc = dae_launch_grad_w(ctx, dzT, Bpad64, feat, ld, B, V, gOutput_WT_rows, gOutput_b_rows))) return rc;
+    return dae_launch_grad_h(ctx, dzT, Bpad64, Output_WT_rows, ld, V, B, dfeat_partial);
 }
 
 int dae_launch_title_conv_backward(dae_ctx* ctx, const int32_t* titles, int B, int L, const float* emb, int n_char,

@@ -122,7 +122,9 @@ def _eval_splits(readers_test, conf, model, rank, world, extras=None):
     if world > 1 and names:
         import torch
         import torch.distributed as dist
-        t = torch.tensor(vals, dtype=torch.float64, device=torch.device("cuda", conf.device_index))
+        # (gloo, the one-device rehearsal of the flow, reduces on the host)
+        t = torch.tensor(vals, dtype=torch.float64,
+                         device="cpu" if dist.get_backend() == "gloo" else torch.device("cuda", conf.device_index))
         dist.all_reduce(t)
         vals = t.tolist()
     if extras is not None:
@@ -154,7 +156,8 @@ def _init_distributed(conf):
     conf.device_index = int(os.environ.get("LOCAL_RANK", rank))
     torch.cuda.set_device(conf.device_index)
     if not dist.is_initialized():
-        dist.init_process_group("nccl", rank=rank, world_size=world)
+        # DAE_DIST_BACKEND=gloo: the N > 1 flow on one device (main_challenge reads the same variable)
+        dist.init_process_group(os.environ.get("DAE_DIST_BACKEND", "nccl"), rank=rank, world_size=world)
     random.seed(int(getattr(conf, "seed", 0)))
     np.random.seed(int(getattr(conf, "seed", 0)))
     conf.verbose = getattr(conf, "verbose", True) and rank == 0
@@ -199,8 +202,12 @@ def run(conf, only_testmode):
     log_write(conf, '*' * 10)
     log_write(conf, info + ' start at ' + str(datetime.datetime.now()))
     model.fit()
-    if world > 1 and not only_testmode and conf.mode != 'title':
-        model.shard_training(rank, world)
+    if world > 1 and not only_testmode:
+        if conf.mode == 'title':              # the output layer's columns over the ranks; the DAE is frozen
+            model.shard_title_training(rank, world)
+            log_write(conf, "title training sharded over %d ranks" % world)
+        else:
+            model.shard_training(rank, world)
 
     if only_testmode:                                               # main_train.py:181-191
         log_write(conf, '<<only test mode>>')

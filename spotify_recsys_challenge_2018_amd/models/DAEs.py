@@ -895,6 +895,8 @@ class DAE_title(DAE):
         self._title_fp32_said = False     # `_title_dtype` said that this model's shapes have no exact title mix
         self._tcost = None                # train_step's cost word on the device
         self._ones_use = None             # train_step_draw's titles_use on the device
+        self._title_sharded = None        # shard_title_training: the sharding.ShardedTitleTrainer the title steps go through
+        self._title_stale = False         # ... and whether it has stepped since the title model's variables were refreshed
         # `_mix_guard_fired`: rows it re-scored alone; launches in a row whose rows overflowed the refine launch (two pause the
         # exact mix); titled launches left of that pause, which run on the fp32 kernels
         self._guard_row_fallbacks = self._mix_overflow_streak = self._mix_exact_pause = 0
@@ -902,6 +904,52 @@ class DAE_title(DAE):
     def _title_scorer(self):
         tm = self.title_model
         return tm if tm is not None and tm.ctx is not None else None
+
+    # -- multi-GPU title training: the output layer's columns sharded over the ranks ----
+    def shard_title_training(self, rank, world, group=None):
+        """Train the title scorer through sharding.ShardedTitleTrainer: this rank owns the rows
+        `sharding.shard_bounds(n_input, world, rank)` of Output_W^T and Output_b (with their Adam moments), decodes only
+        those columns of the frozen DAE, and exchanges one [batch, features] all-reduce, the scalar cost and the embedding
+        gradient per step; the small variables in front of the output layer are replicated.  `train_step` and
+        `train_step_draw` then run that step; the title model's own variables are refreshed from the shards by
+        `sync_params` (collective), which scoring and the end of an epoch call.  The trainer draws its dropout seeds from
+        this model's own stream, so a sharded run draws what an unsharded one draws."""
+        from ..sharding import HipTitleStages, ShardedTitleTrainer
+        tm = self.title_model
+        tm.check_trainable()
+        self.sync_params()
+        shape = dict(L=tm.input_len, n_char=tm.char_size, E=tm.embedding, filter_sizes=tm.filter_sizes, F=tm.filter_num, ld=tm.ld)
+        stages = HipTitleStages(self.ctx, tm.ctx, self.weights["encoder_h"], self.biases["encoder_b"],
+                                self._pack_frozen_dae, shape)
+        self._title_sharded = ShardedTitleTrainer(tm.p, self.n_batch, tm.learning_rate, stages,
+                                                  device=self.weights["encoder_h"].device, rank=rank, world=world,
+                                                  group=group, seed=self._rng)
+        self._title_stale = False
+
+    def _pack_frozen_dae(self, lo, hi):
+        """The DAE context's fp32 image holds the decoder columns [lo, hi): `_ensure_packed(cols=(lo, hi))` for the sharded
+        title step, without the refresh of the title variables `sync_params` does on this class -- the DAE is frozen, and
+        a step must not gather what the step before it left on the shards."""
+        DAE.sync_params(self)
+        dtype, cols = _lib.DAE_DTYPE_F32, (int(lo), int(hi))
+        if self._packed_dirty[dtype] or self._packed_cols.get(dtype) != cols:
+            self.ctx.bind_stream()
+            self.ctx.prepack_decoder(self.weights["decoder_h"], self.biases["decoder_b"], cols[0], cols[1], dtype)
+            self._packed_dirty[dtype] = False
+            self._packed_cols[dtype] = cols
+
+    def sync_params(self):
+        """`DAE.sync_params`, and -- collective when the title training is sharded -- the title model's variables
+        refreshed from the shards when a step has run since the last refresh."""
+        DAE.sync_params(self)
+        if self._title_sharded is not None and self._title_stale:
+            self._title_stale = False
+            self.title_model.ctx.bind_stream()
+            self._title_sharded.sync_title_params(self.title_model)
+
+    def _stream(self, feeds, k, dtype, want_scores, eval_mode=False):
+        self.sync_params()            # (the pipeline copies the title variables: current ones)
+        return DAE._stream(self, feeds, k, dtype, want_scores, eval_mode)
 
     def _row_sums(self, x_positions, x_ones):
         rp, _c, v = coo_to_csr(x_positions, x_ones, self.n_batch, self.n_input)
@@ -982,6 +1030,16 @@ class DAE_title(DAE):
         them.  -> the cost, as `train_step` returns it."""
         import torch
         tm = self.title_model                 # (its shape limits were checked by the caller, before its uploads)
+        if self._title_sharded is not None:
+            # the same step on this rank's columns (sharding.ShardedTitleTrainer); the title model's own variables go stale
+            u = d_use() if callable(d_use) else d_use
+            d_titles = d_titles() if callable(d_titles) else d_titles
+            cost = self._title_sharded.train_step(x, y, d_titles, u, keep_prob, input_keep_prob, title_keep_prob,
+                                                  fetch_cost=fetch_cost)
+            self._title_stale = True
+            if fetch_cost:
+                self._check_feed()
+            return cost
         seed = int(self._rng.randint(0, 2 ** 31 - 1))
         self._ensure_packed()
         self.ctx.bind_stream()

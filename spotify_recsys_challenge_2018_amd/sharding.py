@@ -427,3 +427,204 @@ class ShardedTrainer:
         W_enc = full["W_enc"].cpu().numpy()
         W_dec = W_enc if self.tied else full["W_dec"].cpu().numpy()
         return [W_enc, W_dec, full["b_enc"].cpu().numpy(), full["b_dec"].cpu().numpy()]
+
+
+# ---- title training: the output layer's columns sharded, three small collectives per step ------
+
+class HipTitleStages:
+    """The device stages of a vocabulary-sharded title step through the C ABI (include/dae_hip.h), on the two contexts
+    of a DAE_title model: `dae_ctx` (the frozen DAE: encode, the decoder image of the rank's columns) and `title_ctx`
+    (the title scorer: features, the image of the rank's Output_W^T rows, the loss head on the column window, the
+    convolution backward, Adam).
+
+    W_enc / b_enc: the frozen encoder (replicated).  pack_dae(lo, hi): makes dae_ctx's fp32 image hold the decoder
+    columns [lo, hi) (DAE._ensure_packed(cols=...)).  shape: dict(L, n_char, E, filter_sizes, F, ld) of the title model."""
+
+    def __init__(self, dae_ctx, title_ctx, W_enc, b_enc, pack_dae, shape):
+        import ctypes
+        self.dae_ctx, self.ctx = dae_ctx, title_ctx
+        self.W_enc, self.b_enc, self.pack_dae = W_enc, b_enc, pack_dae
+        self.L, self.n_char, self.E, self.F, self.ld = (int(shape[k]) for k in ("L", "n_char", "E", "F", "ld"))
+        fs = [int(f) for f in shape["filter_sizes"]]
+        self.n_sizes, self.n_feat = len(fs), len(fs) * self.F
+        self._fs = (ctypes.c_int32 * len(fs))(*fs)
+
+    def dae_forward(self, x, use, lo, hi, keep_prob, input_keep_prob, seed):
+        """The frozen DAE's forward with its dropouts on the columns [lo, hi), and the mixing weights of DAEs.py:159-162
+        from the dropped-out row sums -- what DAE_title._title_step_csr computes.  -> (w_title, w_playlist, dae [B, hi - lo])."""
+        import torch
+        from ._lib import _ptr as P
+        c = self.dae_ctx
+        self.pack_dae(lo, hi)
+        c.bind_stream()
+        xr, xc, xv = x
+        B, dev = xr.numel() - 1, self.W_enc.device
+        h = torch.empty((B, self.W_enc.shape[1]), dtype=torch.float32, device=dev)
+        c.encode(xr, xc, xv, self.W_enc, self.b_enc, h, ikp=input_keep_prob, kp=keep_prob, seed=seed)
+        dae = torch.empty((B, hi - lo), dtype=torch.float32, device=dev)
+        c.decode_dense(h, dae, apply_sigmoid=True)
+        s = torch.empty(B, dtype=torch.float32, device=dev)
+        c.check(c.lib.dae_row_sums(c.h, P(xr), P(xc), P(xv), B, float(input_keep_prob), seed, P(s)))
+        x_count = s * float(np.float32(input_keep_prob))
+        deno = use + x_count + 1e-10
+        return (use / deno).contiguous(), (x_count / deno).contiguous(), dae
+
+    def features(self, titles, emb, conv_w, conv_b, keep_prob, seed):
+        """dae_title_features with argmax and feat_raw -> (feat [B, ld], argmax, feat_raw)."""
+        import torch
+        from ._lib import _ptr as P
+        c = self.ctx
+        c.bind_stream()
+        B, dev = titles.shape[0], emb.device
+        feat = torch.empty((B, self.ld), dtype=torch.float32, device=dev)
+        arg = torch.empty((B, self.n_feat), dtype=torch.int32, device=dev)
+        raw = torch.empty((B, self.n_feat), dtype=torch.float32, device=dev)
+        c.check(c.lib.dae_title_features(c.h, P(titles), B, self.L, P(emb), self.n_char, self.E, P(conv_w), P(conv_b),
+                                         self._fs, self.n_sizes, self.F, float(keep_prob), int(seed), P(feat), self.ld,
+                                         P(arg), P(raw)))
+        return feat, arg, raw
+
+    def logits(self, feat, WT_rows, b_rows, lo, hi):
+        """The rank's image from its own rows (dae_prepack_decoder_rows), then the title logits [B, hi - lo]."""
+        import torch
+        c = self.ctx
+        c.prepack_decoder_rows(WT_rows, b_rows, lo)
+        zt = torch.empty((feat.shape[0], hi - lo), dtype=torch.float32, device=feat.device)
+        c.decode_dense(feat, zt, apply_sigmoid=False)
+        return zt
+
+    def loss_backward(self, zt, dae, y, w_t, w_p, lo, hi, n_batch, feat, WT_rows, gWT_rows, gb_rows, dfeat, cost):
+        self.ctx.title_loss_backward_cols(zt, dae, y, w_t, w_p, lo, hi, n_batch, feat, WT_rows, gWT_rows, gb_rows, dfeat, cost)
+
+    def conv_backward(self, titles, emb, conv_w, arg, raw, dfeat, keep_prob, seed, g_emb, g_conv_w, g_conv_b):
+        from ._lib import _ptr as P
+        c = self.ctx
+        c.check(c.lib.dae_title_conv_backward(c.h, P(titles), titles.shape[0], self.L, P(emb), self.n_char, self.E, P(conv_w),
+                                              self._fs, self.n_sizes, self.F, P(arg), P(raw), P(dfeat), self.ld,
+                                              float(keep_prob), int(seed), P(g_emb), P(g_conv_w), P(g_conv_b)))
+
+    def adam(self, p, m, v, g, lr, t):
+        from ._lib import _ptr as P
+        c = self.ctx
+        c.check(c.lib.dae_adam_step(c.h, P(p), P(m), P(v), P(g), p.numel(), float(lr), 0.9, 0.999, 1e-8, int(t)))
+
+
+class ShardedTitleTrainer:
+    """One training step of the title scorer (reference models/DAEs.py:183-198: the DAE arrays are constants) with the
+    output layer's columns sharded over the ranks of `group`.
+
+    Rank g owns rows [lo_g, hi_g) = shard_bounds(V, world, g) of Output_W^T [V, ld] and of Output_b with their Adam
+    moments and gradients, and decodes only those columns of the frozen DAE.  char_embedding, conv_w and conv_b -- the
+    small variables in front of the output layer -- are replicated with their moments and updated identically on every
+    rank.  Per step the ranks exchange three things: all-reduce(sum) of dfeat [B, ld] and of the scalar cost, and a
+    broadcast from rank 0 of the embedding gradient [n_char, E]: the convolution backward runs on every rank from the
+    same reduced dfeat and its filter gradients have a fixed summation order, but the embedding gradient is summed with
+    float atomics (title_egrad_kernel), so its last bit may differ between ranks -- with rank 0's copy everywhere the
+    replicas stay in lock-step.  `stages` carries the device work (HipTitleStages); it is injected so that the
+    bookkeeping runs under gloo on CPU in the tests.
+
+    full_params: {"char_embedding", "conv_w", "conv_b", "Output_WT", "Output_b"} -- host arrays or tensors, the title
+    model's own layout (models/title_models.py) -- that every rank slices identically."""
+
+    OWNED = ("Output_WT", "Output_b")
+    REPLICATED = ("char_embedding", "conv_w", "conv_b")
+
+    def __init__(self, full_params, n_batch, lr, stages, device="cpu", rank=0, world=1, group=None, seed=0):
+        import torch
+        self.V, self.ld = (int(d) for d in full_params["Output_WT"].shape)
+        self.n_batch, self.lr = int(n_batch), float(lr)
+        self.rank, self.world, self.group, self.stages = rank, world, group, stages
+        self.lo, self.hi = shard_bounds(self.V, world, rank)
+        if self.hi <= self.lo:
+            raise ValueError("rank %d of %d owns no column of %d" % (rank, world, self.V))
+        self.device = device
+
+        def dev(a):                                   # own copy
+            if isinstance(a, torch.Tensor):
+                return a.detach().to(device=device, dtype=torch.float32, copy=True).contiguous()
+            return torch.from_numpy(np.array(a, dtype=np.float32, order="C", copy=True)).to(device)
+        self.params = {n: dev(full_params[n][self.lo:self.hi]) for n in self.OWNED}
+        self.params.update((n, dev(full_params[n])) for n in self.REPLICATED)
+        self.grads = {n: torch.zeros_like(p) for n, p in self.params.items()}
+        self.moments = {n: (torch.zeros_like(p), torch.zeros_like(p)) for n, p in self.params.items()}
+        self.dfeat = torch.zeros((self.n_batch, self.ld), dtype=torch.float32, device=device)
+        self.cost = torch.zeros(1, dtype=torch.float32, device=device)
+        self.step = 0
+        # same stream on every rank: same dropout draws (seed: an int, or the RandomState to draw from)
+        self._rng = seed if isinstance(seed, np.random.RandomState) else np.random.RandomState(seed)
+
+    def _allreduce(self, t):
+        if self.world > 1:
+            import torch.distributed as dist
+            if t.is_cuda and dist.get_backend(self.group) == "gloo":      # (the one-device rehearsal: through the host)
+                h = t.cpu()
+                dist.all_reduce(h, group=self.group)
+                t.copy_(h)
+            else:
+                dist.all_reduce(t, group=self.group)
+
+    def _broadcast0(self, t):
+        if self.world > 1:
+            import torch.distributed as dist
+            src = dist.get_global_rank(self.group, 0) if self.group is not None else 0
+            if t.is_cuda and dist.get_backend(self.group) == "gloo":
+                h = t.cpu()
+                dist.broadcast(h, src, group=self.group)
+                t.copy_(h)
+            else:
+                dist.broadcast(t, src, group=self.group)
+
+    def train_step(self, x_csr, y_csr, titles, titles_use, keep_prob, input_keep_prob, title_keep_prob, fetch_cost=True):
+        """x_csr / y_csr: (row_ptr, col, val) of the WHOLE batch with global column ids; titles int32 [B, L]; titles_use
+        float32 [B] -- tensors on the trainer's device.  Returns the global cost: a float, or with fetch_cost=False a
+        0-dim tensor on the trainer's device."""
+        st, p, g = self.stages, self.params, self.grads
+        lo, hi = self.lo, self.hi
+        seed = int(self._rng.randint(0, 2 ** 31 - 1))
+        w_t, w_p, dae = st.dae_forward(x_csr, titles_use, lo, hi, keep_prob, input_keep_prob, seed)
+        feat, arg, raw = st.features(titles, p["char_embedding"], p["conv_w"], p["conv_b"], title_keep_prob, seed)
+        zt = st.logits(feat, p["Output_WT"], p["Output_b"], lo, hi)
+        st.loss_backward(zt, dae, y_csr, w_t, w_p, lo, hi, self.n_batch, feat, p["Output_WT"], g["Output_WT"],
+                         g["Output_b"], self.dfeat, self.cost)
+        self._allreduce(self.dfeat)
+        self._allreduce(self.cost)
+        st.conv_backward(titles, p["char_embedding"], p["conv_w"], arg, raw, self.dfeat, title_keep_prob, seed,
+                         g["char_embedding"], g["conv_w"], g["conv_b"])
+        self._broadcast0(g["char_embedding"])
+        self.step += 1
+        for n in self.REPLICATED + self.OWNED:
+            m, v = self.moments[n]
+            st.adam(p[n], m, v, g[n], self.lr, self.step)
+        return float(self.cost.item()) if fetch_cost else self.cost[0].clone()
+
+    def gather_params(self):
+        """The five full arrays on every rank, on the trainer's device: the replicated ones as they are, the row shards
+        all-gathered (padded to the largest shard, then trimmed)."""
+        import torch
+        full = {n: self.params[n] for n in self.REPLICATED}
+        if self.world == 1:
+            full.update((n, self.params[n]) for n in self.OWNED)
+            return full
+        import torch.distributed as dist
+        bounds = all_shard_bounds(self.V, self.world)
+        rows = max(hi - lo for lo, hi in bounds)
+        for n in self.OWNED:
+            p = self.params[n]
+            pad = torch.zeros((rows,) + tuple(p.shape[1:]), dtype=p.dtype, device=p.device)
+            pad[:p.shape[0]] = p
+            out = torch.empty((self.world * rows,) + tuple(p.shape[1:]), dtype=p.dtype, device=p.device)
+            _collective(dist.all_gather_into_tensor, out, pad, self.group)
+            out = out.view((self.world, rows) + tuple(p.shape[1:]))
+            full[n] = torch.cat([out[r, :hi - lo] for r, (lo, hi) in enumerate(bounds)], dim=0)
+        return full
+
+    def sync_title_params(self, title_model):
+        """Collective: the title model's five full variables (`title_model.p`, models/title_models.py) refreshed from the
+        shards and the replicas; its packed images are marked dirty, its parameter generation bumps and its features table
+        is dropped, so that scoring, evaluation and saving read the current weights."""
+        full = self.gather_params()
+        for n in self.REPLICATED + self.OWNED:
+            title_model.p[n].copy_(full[n])
+        title_model._packed_dirty = True
+        title_model._params_gen += 1
+        title_model._drop_features_table()
