@@ -86,6 +86,7 @@ struct dae_topk_state {     // what the second half of a fused scoring call need
     const int* order = nullptr;
     int* sample_cnt = nullptr;
     const float* pend_h32 = nullptr;   // dae_score_topk_begin / _finish: the fp32 hidden rows of the pending call
+    bool live_built = false;           // the threshold launch built the live lists in ctx->live (dae_score_plan::live_in_tau)
 };
 
 struct dae_ctx {
@@ -145,9 +146,14 @@ struct dae_ctx {
     // the bias-ordered tile list with its sample RE-DEALT for a launch geometry (dae_launch_tile_band): which order it was cut from
     dae_buf tile_band; long long band_gen = -1; int band_nsamp = 0, band_nbrg = 0, band_waves = 0;
     // the fp32 hidden-256 filter launch walks, per row group, only the tiles whose logit bound reaches the group's threshold
-    // (prepack.hip live_tiles_kernel): [n_rg] counts (16 ints reserved at least) | [n_rg][n_filter] tile ids, in tsB's order
+    // (built by the threshold launch itself -- topk.hip tau_select_kernel -- or, on foreign thresholds, by prepack.hip
+    // live_tiles_kernel): [n_rg] counts (16 ints reserved at least) | [n_rg][n_filter] tile ids, in tsB's order
     int filter_skip = 1;       // dae_set_filter_skip
     dae_buf live; int live_n_rg = 0;       // live_n_rg: row groups of the last launch that built the lists (0: none yet)
+    // the threshold launch's own words for that: 64 arrival counters (one per row group; zeroed when the buffer is (re)allocated,
+    // left at zero by every launch) | [Bpad] doubles, the rows' max |h - 0.5|.  Nothing else re-zeroes the counters: a threshold
+    // launch that never completes (a device fault) leaves them standing for the life of the context, like the rest of its state
+    dae_buf live_sync; void* live_sync_zeroed = nullptr; size_t live_sync_zeroed_bytes = 0;   // (which allocation was zeroed)
     dae_buf skip_stat;         // 3 x uint64 {launches, planned tiles x row groups, live tiles} since the last dae_filter_skip_read
 
     // profiling of the dominant kernel
@@ -494,9 +500,20 @@ int dae_launch_topk_dense(dae_ctx* ctx, const dae_dense_src& src, const dae_topk
 //   largest of gmax[row][0..n_g) (-inf = absent) to 16 key bits; -inf when the row holds fewer finite maxima;
 //   out_pairs[row * pairs_stride + i], i < out_cnt[row]: the (logit, column) of every dense sample logit
 //   samp[row][0..n_s) >= tau (column of element q = col_lo + samp_list[q >> 5] * 32 + (q & 31)), unordered
+//   live (nullable; the workgroup-per-row kernel of an fp32 launch with a dense sample only -- dae_score_plan::live_in_tau):
+//   the launch also builds the live lists of the filter launch that takes these thresholds, as dae_launch_live_tiles would
+//   from them: the last workgroup of each 128-row group to finish does it, so nothing waits and no launch is added
+struct dae_tau_live {
+    const float4* hp; int B, H, G;                               // the packed fp32 hidden image in 128-row groups; G = Hp / 8 = 32
+    const float* tile_ub; int ntiles, nrank;                     // dae_packed::tile_ub of the image's ntiles tiles; ranked columns
+    const int* list; int n_items;                                // the filter launch's tile list
+    unsigned long long* d_row;                                   // [Bpad] scratch: the bits of each row's max |h - 0.5| (double)
+    unsigned* arrive;                                            // [n_rg] rows of the group that have published; ZERO between launches
+    int* live_cnt; int* live_list; unsigned long long* stat;     // as dae_launch_live_tiles
+};
 int dae_launch_tau_select(dae_ctx* ctx, const float* gmax, int64_t ld_g, int n_g, const float* samp, int64_t ld_s,
                           int n_s, const int* samp_list, int col_lo, int B, int k, const int32_t* seed_row_ptr,
-                          float* tau, uint2* out_pairs, int64_t pairs_stride, int* out_cnt);
+                          float* tau, uint2* out_pairs, int64_t pairs_stride, int* out_cnt, const dae_tau_live* live);
 int dae_launch_topk_pairs(dae_ctx* ctx, const dae_pair_group& g0, const dae_pair_group& g1,
                           const dae_topk_args& a);
 int dae_launch_topk_soa(dae_ctx* ctx, int G, const float* logit, const int32_t* idx,

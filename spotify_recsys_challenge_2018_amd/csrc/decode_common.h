@@ -77,6 +77,40 @@ struct dae_decp {          // argument block of the decode kernels on the prepac
     int dz16;                      // dzT holds bf16 (the bf16 backward GEMMs read it as such)
 };
 
+// ---------------------------------------------------------------------------------------------
+// The live lists of the fp32 filter launch: ONE test, shared by the two kernels that build them (topk.hip tau_select_kernel's
+// tail, prepack.hip live_tiles_kernel).  For a row group: d_max = dae_max_nan over its rows r < B and the units k < H of
+// |(double)h[r][k] - 0.5| (the zero padding of the packed tile is NOT read: it would give 0.5), tau_min = dae_min_nan over
+// the same rows of their thresholds.  A tile with the bound {A_t, M_t} (prepack_tile_kernel) is live unless
+// U = A_t + d M_t < tau_min.  Roundings go the safe way: d_max, the product and the sum in double, d and U pushed up by more
+// than their rounding errors; the test is !(U < tau_min), so a NaN anywhere (weights, hidden rows, thresholds) and
+// tau = -inf keep the tile.
+// ---------------------------------------------------------------------------------------------
+// the larger of two values, a NaN if either is one (fmax would drop it)
+template <class T>
+__device__ __forceinline__ T dae_max_nan(T a, T b) { return (a != a) ? a : ((b > a || b != b) ? b : a); }
+template <class T>
+__device__ __forceinline__ T dae_min_nan(T a, T b) { return -dae_max_nan(-a, -b); }
+
+__device__ __forceinline__ bool dae_tile_is_live(float A_t, float M_t, double d_max, float tau_min)
+{
+    const double d = d_max * (1.0 + 0x1p-40);               // (|h - 0.5| in double is off by at most 2^-53 relative)
+    const double A = (double)A_t, dm = d * (double)M_t;
+    const double U = A + dm + (fabs(A) + fabs(dm)) * 0x1p-48;   // two roundings of 2^-53 (|A| + |d M|) at most
+    return !(U < (double)tau_min);
+}
+
+// The tile that holds the last ranked column (nrank is no multiple of 32) is bounded over its ranked columns only, from the
+// columns' own pairs behind the tiles' in tile_ub.  One whole wave calls this; every lane returns the pair.  t_edge < 0: none.
+__device__ __forceinline__ void dae_edge_tile_bound(const float* tile_ub, int ntiles, int nrank, int lane, float& ea, float& em)
+{
+    const int t_edge = nrank >> 5;
+    ea = -__builtin_inff(); em = 0.0f;
+    if (lane < (nrank & 31)) { ea = tile_ub[2 * (ntiles + t_edge * 32 + lane)]; em = tile_ub[2 * (ntiles + t_edge * 32 + lane) + 1]; }
+#pragma unroll
+    for (int sh = 1; sh < 64; sh <<= 1) { ea = dae_max_nan(ea, __shfl_xor(ea, sh)); em = dae_max_nan(em, __shfl_xor(em, sh)); }
+}
+
 __device__ __forceinline__ int tile_of_item(const dae_tileset& ts, int i)
 {
     return ts.list[i];          // always a list (the identity for "all tiles"): no branch around a load

@@ -92,7 +92,7 @@ int dae_mix_topk_exact_impl(dae_ctx* tc, dae_ctx* dc, const float* feat, int64_t
     float* samp = static_cast<float*>(tc->gmax.p);
     uint2* top = static_cast<uint2*>(tc->sample_top.p);
     rc = dae_launch_tau_select(tc, samp, pl.ld_s, (int)pl.ld_s, samp, 0, 0, order, 0, B, k, seed_row_ptr, static_cast<float*>(tc->tau.p),
-                               top, 1, reinterpret_cast<int*>(top + Bpad));                  // (no sample list: count 0)
+                               top, 1, reinterpret_cast<int*>(top + Bpad), nullptr);         // (no sample list: count 0; no live lists)
     if (rc) return rc;
     // ---- filter: upper bounds over every rankable tile
     dae_note_plan(pl.last);

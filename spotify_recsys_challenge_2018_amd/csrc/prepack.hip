@@ -19,10 +19,6 @@ namespace {
 // (zero outside the matrix)
 constexpr int PP_PAD = 4;          // LDS row stride Hp + 4 floats: rows stay 16-byte aligned
 
-// the larger of two values, a NaN if either is one (fmax would drop it)
-template <class T>
-__device__ __forceinline__ T dae_max_nan(T a, T b) { return (a != a) ? a : ((b > a || b != b) ? b : a); }
-
 template <int DT>
 __global__ __launch_bounds__(256) void prepack_tile_kernel(const float* __restrict__ W,
                                                            const float* __restrict__ b, int H, int Hp,
@@ -139,13 +135,16 @@ __global__ __launch_bounds__(256) void prepack_tile_kernel(const float* __restri
 }
 
 // ---- the live lists of the fp32 filter launch (score.hip topk_phase_b; hidden 256 in 128-row groups) ---------------------
-// One workgroup per row group rg.  From the group's packed hidden tile: d = max |h[r][k] - 0.5| over its rows r < B and the
+// The STANDALONE builder.  A call whose filter launch takes the thresholds its own threshold launch computed gets the lists
+// from that launch (topk.hip tau_select_kernel<.., LIVE>: dae_score_plan::live_in_tau) and never runs this kernel; it runs
+// where the thresholds come from elsewhere (dae_score_topk_finish: exchanged, possibly raised) or the threshold launch is the
+// wave-per-row kernel.  Both builders apply ONE test, dae_tile_is_live (decode_common.h), to the same d_max and tau_min, so the
+// lists of the two are the same for the same thresholds.
+// One workgroup per row group rg.  From the group's packed hidden tile: d_max = max |h[r][k] - 0.5| over its rows r < B and the
 // units k < H (the zero padding of the tile is NOT read: it would give 0.5); from the thresholds the filter launch is given:
-// tau_rg = min over the same rows.  Item i of `list` is live unless U = A_t + d M_t < tau_rg (prepack_tile_kernel's bound:
+// tau_min = min over the same rows.  Item i of `list` is live unless U = A_t + d M_t < tau_min (prepack_tile_kernel's bound:
 // no column of tile t then reaches the threshold of any row of the group, i.e. the filter epilogue would drop all of it).
-// The live tiles go to live_list[rg * n_items ..) in the list's order, their number to live_cnt[rg].  Roundings go the safe
-// way: d, the product and the sum in double, d and U pushed up by more than their rounding errors; the test is !(U < tau_rg),
-// so a NaN anywhere (weights, hidden rows, thresholds) and tau = -inf keep the tile.
+// The live tiles go to live_list[rg * n_items ..) in the list's order, their number to live_cnt[rg].
 // stat: {launches, planned tiles x row groups, live tiles} of the context (dae_filter_skip_read).
 __global__ __launch_bounds__(1024) void live_tiles_kernel(const float4* __restrict__ hp, int B, int H, int G,
                                                           const float* __restrict__ tau, const float* __restrict__ tile_ub,
@@ -174,10 +173,8 @@ __global__ __launch_bounds__(1024) void live_tiles_kernel(const float4* __restri
     __shared__ float sh_edge[2];
     const int t_edge = (nrank & 31) ? (nrank >> 5) : -1;
     if (wave == 0 && t_edge >= 0) {
-        float ea = -__builtin_inff(), em = 0.0f;
-        if (lane < (nrank & 31)) { ea = tile_ub[2 * (ntiles + t_edge * 32 + lane)]; em = tile_ub[2 * (ntiles + t_edge * 32 + lane) + 1]; }
-#pragma unroll
-        for (int sh = 1; sh < 64; sh <<= 1) { ea = dae_max_nan(ea, __shfl_xor(ea, sh)); em = dae_max_nan(em, __shfl_xor(em, sh)); }
+        float ea, em;
+        dae_edge_tile_bound(tile_ub, ntiles, nrank, lane, ea, em);
         if (lane == 0) { sh_edge[0] = ea; sh_edge[1] = em; }
     }
     float tm = __builtin_inff();
@@ -185,13 +182,11 @@ __global__ __launch_bounds__(1024) void live_tiles_kernel(const float4* __restri
 #pragma unroll
     for (int sh = 1; sh < 64; sh <<= 1) {
         d = dae_max_nan(d, __shfl_xor(d, sh));
-        tm = -dae_max_nan(-tm, -__shfl_xor(tm, sh));
+        tm = dae_min_nan(tm, __shfl_xor(tm, sh));
     }
     if (lane == 0) { sh_d[wave] = d; sh_t[wave] = tm; }
     __syncthreads();
-    for (int w = 0; w < NW; ++w) { d = dae_max_nan(d, sh_d[w]); tm = -dae_max_nan(-tm, -sh_t[w]); }
-    d *= 1.0 + 0x1p-40;                                     // (|h - 0.5| in double is off by at most 2^-53 relative)
-    const double tau_rg = (double)tm;
+    for (int w = 0; w < NW; ++w) { d = dae_max_nan(d, sh_d[w]); tm = dae_min_nan(tm, sh_t[w]); }
 
     int done = 0;
     int* const out = live_list + (size_t)rg * n_items;
@@ -201,10 +196,7 @@ __global__ __launch_bounds__(1024) void live_tiles_kernel(const float4* __restri
         int t = 0;
         if (i < n_items) {
             t = list[i];
-            const double A = (double)(t == t_edge ? sh_edge[0] : tile_ub[2 * t]), M = (double)(t == t_edge ? sh_edge[1] : tile_ub[2 * t + 1]);
-            const double dm = d * M;
-            const double U = A + dm + (fabs(A) + fabs(dm)) * 0x1p-48;   // two roundings of 2^-53 (|A| + |d M|) at most
-            keep = !(U < tau_rg);
+            keep = dae_tile_is_live(t == t_edge ? sh_edge[0] : tile_ub[2 * t], t == t_edge ? sh_edge[1] : tile_ub[2 * t + 1], d, tm);
         }
         const unsigned long long mask = __ballot(keep);
         if (lane == 0) sh_n[wave] = __popcll(mask);

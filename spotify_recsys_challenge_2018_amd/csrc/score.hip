@@ -138,26 +138,46 @@ static int fill_tau_neg_inf(dae_ctx* ctx, float* tau_dst, int B)
     return DAE_OK;
 }
 
+// the live lists of a filter launch of n_filter tiles (dae_score_plan::build_live): ctx->live = [n_rg] counts, padded | [n_rg]
+// [n_filter] tile ids, and the context's skip counters (zeroed when first reserved)
+static int reserve_live(dae_ctx* ctx, const dae_rowgeom& g, int n_filter, int** live_cnt, int** live_list)
+{
+    const size_t cnt_ints = (size_t)dae_round_up(g.n_rg, 64);
+    int rc = dae_reserve(ctx, ctx->live, (cnt_ints + (size_t)g.n_rg * n_filter) * sizeof(int));
+    if (rc) return rc;
+    if (!ctx->skip_stat.p) {
+        rc = dae_reserve(ctx, ctx->skip_stat, 3 * sizeof(unsigned long long));
+        if (rc) return rc;
+        DAE_HIP_CHECK(ctx, hipMemsetAsync(ctx->skip_stat.p, 0, 3 * sizeof(unsigned long long), ctx->stream));
+    }
+    *live_cnt = static_cast<int*>(ctx->live.p);
+    *live_list = *live_cnt + cnt_ints;
+    return DAE_OK;
+}
+
 // ---- decode + rank with the hidden tile already packed in the context for geometry g, in two halves -----------------
 // topk_phase_a: the plan, the threshold sample (phase A) and tau_select -> tau_dst[B] (a valid lower bound, per row, of
 //   the k-th largest rankable non-seed logit among THIS image's columns); small problems: the dense logits, tau = -inf.
+//   own_tau: phase B will be given exactly these thresholds (decode_topk_core; not dae_score_topk_begin, whose caller may
+//   pass exchanged, raised ones to dae_score_topk_finish) -- the threshold launch may then build the filter launch's live
+//   lists itself (dae_score_plan::live_in_tau).
 // topk_phase_b: the filter launch with tau_src[B] (the same values, or larger ones that are still lower bounds of the
 //   row's k-th largest logit over ALL shards: dae_score_topk_finish), the exact mode's refine step, the final selection.
 // What phase B needs from phase A travels in ctx->tk.
 // dtype_in == DAE_DTYPE_BF16_EXACT: h32 = the fp32 hidden rows [B][H] the packed bf16 image was rounded from,
 // row_bad (nullable) = rows of h32 outside [0, 1]
 static int topk_phase_a(dae_ctx* ctx, const dae_packed* pk, const dae_rowgeom& g, int B, int n_tracks,
-                        const int32_t* seed_row_ptr, int k, int dtype_in, float* tau_dst)
+                        const int32_t* seed_row_ptr, int k, int dtype_in, float* tau_dst, bool own_tau)
 {
     int rc;
     dae_topk_state& tk = ctx->tk;
     tk.valid = false;
     const dae_plan_in in{pk->ntiles, pk->col_lo, pk->col_hi, pk->Hp, pk->ub_valid && pk->tile_ub.p, g, n_tracks, k, dtype_in,
-                         ctx->mixT != nullptr, ctx->overlap_hint, ctx->filter_skip};
+                         ctx->mixT != nullptr, ctx->overlap_hint, ctx->filter_skip, own_tau, B};
     const dae_score_plan pl = dae_plan_topk(in);
     memcpy(g_last_plan, pl.last, sizeof(pl.last));
     if (pl.bad_mix) return dae_fail(ctx, DAE_ERR_ARG, "DAE_DTYPE_BF16_EXACT is not available with dae_set_score_mix");
-    tk.pk = pk; tk.g = g; tk.B = B; tk.k = k; tk.plan = pl; tk.order = nullptr; tk.sample_cnt = nullptr;
+    tk.pk = pk; tk.g = g; tk.B = B; tk.k = k; tk.plan = pl; tk.order = nullptr; tk.sample_cnt = nullptr; tk.live_built = false;
     if (pl.ntiles == 0) {                                  // no GEMM launch; tau = -inf, and phase B pads every slot
         rc = fill_tau_neg_inf(ctx, tau_dst, B);
         tk.valid = rc == DAE_OK;
@@ -216,11 +236,35 @@ static int topk_phase_a(dae_ctx* ctx, const dae_packed* pk, const dae_rowgeom& g
     rc = dae_reserve(ctx, ctx->sample_top, ((size_t)g.Bpad * pstride) * sizeof(uint2) + (size_t)g.Bpad * sizeof(int));
     if (rc) return rc;
     tk.sample_cnt = reinterpret_cast<int*>(static_cast<uint2*>(ctx->sample_top.p) + (size_t)g.Bpad * pstride);
+    // SKIPPED TILES, the thresholds being phase B's own (dae_score_plan::live_in_tau): the threshold launch compacts, per row
+    // group, the filter launch's tiles that can hold a logit >= tau for one of its rows -- in the workgroup of the group's
+    // last row to finish, so the step's chain of launches carries no launch for it
+    dae_tau_live lv{};
+    if (pl.live_in_tau) {
+        constexpr size_t n_arrive = 64;                        // (a slab is at most DAE_ROW_SLAB = 4096 rows: 32 groups of 128)
+        if ((size_t)g.n_rg > n_arrive) return dae_fail(ctx, DAE_ERR_STATE, "%d row groups in one threshold launch", g.n_rg);
+        int* lc; int* ll;
+        rc = reserve_live(ctx, g, pl.n_filter, &lc, &ll);
+        if (rc) return rc;
+        rc = dae_reserve(ctx, ctx->live_sync, n_arrive * sizeof(unsigned) + (size_t)g.Bpad * sizeof(double));
+        if (rc) return rc;
+        if (ctx->live_sync_zeroed != ctx->live_sync.p || ctx->live_sync_zeroed_bytes != ctx->live_sync.bytes) {
+            DAE_HIP_CHECK(ctx, hipMemsetAsync(ctx->live_sync.p, 0, n_arrive * sizeof(unsigned), ctx->stream));
+            ctx->live_sync_zeroed = ctx->live_sync.p; ctx->live_sync_zeroed_bytes = ctx->live_sync.bytes;
+        }
+        unsigned* arrive = static_cast<unsigned*>(ctx->live_sync.p);
+        lv = dae_tau_live{static_cast<const float4*>(ctx->h_packed.p), B, pk->H, pk->Hp / DAE_KG,
+                          static_cast<const float*>(pk->tile_ub.p), pk->ntiles, pl.nrank, order + pl.n_samp, pl.n_filter,
+                          reinterpret_cast<unsigned long long*>(arrive + n_arrive), arrive, lc, ll,
+                          static_cast<unsigned long long*>(ctx->skip_stat.p)};
+    }
     rc = dae_launch_tau_select(ctx, gmax, pl.ld_g, (int)pl.ld_g, pl.whole_b ? gmax : sample, pl.whole_b ? 0 : pl.ld_s,
                                pl.whole_b ? 0 : (int)pl.ld_s, order, pk->col_lo, B, k,
                                seed_row_ptr, tau_dst, static_cast<uint2*>(ctx->sample_top.p),
-                               pstride, tk.sample_cnt);
+                               pstride, tk.sample_cnt, pl.live_in_tau ? &lv : nullptr);
     if (rc) return rc;
+    tk.live_built = pl.live_in_tau;
+    if (pl.live_in_tau) ctx->live_n_rg = g.n_rg;
     tk.valid = true;
     return DAE_OK;
 }
@@ -233,7 +277,7 @@ static int topk_phase_b(dae_ctx* ctx, const float* tau_src, const int32_t* seed_
     dae_topk_state& tk = ctx->tk;
     if (!tk.valid) return dae_fail(ctx, DAE_ERR_STATE, "no scoring call in progress on this context");
     tk.valid = false;
-    ctx->live_n_rg = 0;                                    // (dae_filter_skip_last: no live lists unless the launch below builds them)
+    if (!tk.live_built) ctx->live_n_rg = 0;                // (dae_filter_skip_last: no live lists unless phase A's launch or the one below builds them)
     const dae_packed* pk = tk.pk;
     const dae_rowgeom& g = tk.g;
     const dae_score_plan& pl = tk.plan;
@@ -271,24 +315,22 @@ static int topk_phase_b(dae_ctx* ctx, const float* tau_src, const int32_t* seed_
     rc = dae_reserve(ctx, ctx->cand_cnt, (size_t)g.nb_rg * g.Bpad * sizeof(int));
     if (rc) return rc;
     dae_tileset tsB{n_filter, pl.S, 3, pl.whole_b ? tk.order : tk.order + pl.n_samp};
-    // SKIPPED TILES (dae_score_plan::build_live): the thresholds are known here -- one small launch compacts, per row group, the
-    // tiles of tsB that can hold a logit >= tau for one of its rows, and the filter launch walks those.  Issued before the gate:
-    // it runs while the other batch's filter launch holds the matrix cores.
+    // SKIPPED TILES (dae_score_plan::build_live): the filter launch walks, per row group, the tiles of tsB that can hold a logit
+    // >= tau for one of its rows.  Where the thresholds are the ones phase A computed for this very launch (live_in_tau), its
+    // threshold launch has built the lists already and they are only handed on.  Otherwise -- thresholds from elsewhere
+    // (dae_score_topk_finish), or the wave-per-row threshold kernel -- they are known here and one small launch compacts the
+    // lists from them.  Issued before the gate: it runs while the other batch's filter launch holds the matrix cores.
     const int* live_cnt = nullptr; const int* live_list = nullptr;
     if (pl.build_live) {
-        const size_t cnt_ints = (size_t)dae_round_up(g.n_rg, 64);
-        rc = dae_reserve(ctx, ctx->live, (cnt_ints + (size_t)g.n_rg * n_filter) * sizeof(int));
+        int* lc; int* ll;
+        rc = reserve_live(ctx, g, n_filter, &lc, &ll);     // (live_built: the same pointers phase A gave its launch)
         if (rc) return rc;
-        if (!ctx->skip_stat.p) {
-            rc = dae_reserve(ctx, ctx->skip_stat, 3 * sizeof(unsigned long long));
+        if (!tk.live_built) {
+            rc = dae_launch_live_tiles(ctx, *pk, g, B, tsB.list, n_filter, tau_src, pl.nrank, lc, ll,
+                                       static_cast<unsigned long long*>(ctx->skip_stat.p));
             if (rc) return rc;
-            DAE_HIP_CHECK(ctx, hipMemsetAsync(ctx->skip_stat.p, 0, 3 * sizeof(unsigned long long), ctx->stream));
         }
-        int* lc = static_cast<int*>(ctx->live.p);
-        rc = dae_launch_live_tiles(ctx, *pk, g, B, tsB.list, n_filter, tau_src, pl.nrank, lc, lc + cnt_ints,
-                                   static_cast<unsigned long long*>(ctx->skip_stat.p));
-        if (rc) return rc;
-        live_cnt = lc; live_list = lc + cnt_ints; ctx->live_n_rg = g.n_rg;
+        live_cnt = lc; live_list = ll; ctx->live_n_rg = g.n_rg;
     }
     // dae_set_decode_gate: the dominant launch takes every CU, so two of them in flight on two streams only queue
     // behind each other; the gate makes this one wait for the other context's and announces its own end
@@ -344,7 +386,7 @@ static int decode_topk_core(dae_ctx* ctx, const dae_packed* pk, const dae_rowgeo
 {
     int rc = dae_reserve(ctx, ctx->tau, (size_t)g.Bpad * sizeof(float));
     if (rc) return rc;
-    rc = topk_phase_a(ctx, pk, g, B, n_tracks, seed_row_ptr, k, dtype_in, static_cast<float*>(ctx->tau.p));
+    rc = topk_phase_a(ctx, pk, g, B, n_tracks, seed_row_ptr, k, dtype_in, static_cast<float*>(ctx->tau.p), true);
     if (rc) return rc;
     return topk_phase_b(ctx, static_cast<const float*>(ctx->tau.p), seed_row_ptr, seed_col, out_kind, out_score, out_idx,
                         h32, row_bad);
@@ -481,7 +523,7 @@ int dae_score_topk_begin(dae_ctx* ctx, const int32_t* row_ptr, const int32_t* co
     const dae_packed* pk; dae_rowgeom g; const float* h32;
     int rc = score_encode(ctx, row_ptr, col, val, W_enc, b_enc, V, H, B, dtype, &pk, &g, &h32);
     if (rc) return rc;
-    rc = topk_phase_a(ctx, pk, g, B, n_tracks, seed_row_ptr, k, dtype, tau_out);
+    rc = topk_phase_a(ctx, pk, g, B, n_tracks, seed_row_ptr, k, dtype, tau_out, false);
     if (rc) return rc;
     ctx->tk.pend_h32 = h32;
     return DAE_OK;

@@ -83,7 +83,16 @@ struct dae_plan_in {
     int n_tracks, k, dtype_in;
     bool mixed;                       // dae_set_score_mix: the launches rank the MIXED score
     int overlap_hint, filter_skip;    // dae_set_overlap_hint, dae_set_filter_skip
+    bool own_tau = false;             // the thresholds this call computes are the ones its filter launch takes (no exchange between)
+    int B = 0;                        // rows of the call (which threshold kernel runs: dae_tau_wave_per_row)
 };
+
+// does the threshold launch take tau_select_wave_kernel (topk.hip: a WAVE per row, for launches of many short rows) instead of
+// the workgroup-per-row kernel?  n_g maxima and n_s dense sample logits per row
+inline bool dae_tau_wave_per_row(int B, int64_t n_g, int64_t n_s)
+{
+    return B >= 1024 && n_g <= 64 * 32 && (n_s >> 2) <= 64 * 8;
+}
 
 struct dae_score_plan {
     bool bad_mix;           // DAE_DTYPE_BF16_EXACT under dae_set_score_mix: no launch sequence exists (only `last` is filled)
@@ -102,6 +111,8 @@ struct dae_score_plan {
     int n_filter, cap;      // tiles of the filter launch; candidates one of its workgroups can emit per row
     bool build_live;        // the filter launch walks per-row-group live lists (dae_launch_live_tiles: tiles skipped by their bound)
     int32_t last[8];        // what dae_last_plan reports
+    bool live_in_tau;       // build_live, and the threshold launch builds the lists itself (tau_select_kernel's tail, topk.hip): no
+                            // launch of live_tiles_kernel
 };
 
 inline dae_score_plan dae_plan_topk(const dae_plan_in& in)
@@ -220,5 +231,9 @@ inline dae_score_plan dae_plan_topk(const dae_plan_in& in)
     // logit >= tau.  What that leaves out the filter epilogue would have dropped element by element: the lists cannot change
     // (DESIGN.md section 2).  Every other filter launch (generic fp32, bf16, exact bf16, the mixed score) walks all its tiles.
     p.build_live = in.filter_skip && p.n_filter > 0 && !whole_b && in.ub_valid && dae_filter_takes_live(g, dtype, in.Hp, mixed);
+    // WHO builds them: the threshold launch itself, where the thresholds it computes are the filter launch's (no exchange between
+    // the two halves) and it is the workgroup-per-row kernel, whose workgroups count themselves per row group; else a launch of
+    // live_tiles_kernel on the thresholds the filter launch is given
+    p.live_in_tau = p.build_live && in.own_tau && !dae_tau_wave_per_row(in.B, ld_g, whole_b ? 0 : ld_s);
     return p;
 }

@@ -24,7 +24,9 @@
 //   dense : a row of logits (dae_topk_dense; small problems of the fused path)
 //   pairs : segments of (logit, column) pairs (the sample's survivors from tau_select_kernel + phase-B candidate lists)
 //   soa   : [G, B, k] shard lists gathered by RCCL (K4 merge)
-#include "dae_internal.h"
+#include <type_traits>
+
+#include "decode_common.h"      // dae_tile_is_live: the live lists tau_select_kernel builds
 
 namespace {
 
@@ -761,11 +763,29 @@ struct TauP {
     const int32_t* seed_row_ptr; int k;
     float* tau; uint2* out_pairs; int64_t pairs_stride; int* out_cnt;
 };
+// LIVE: the launch also builds the live lists of the fp32 filter launch that takes its thresholds (dae_score_plan::live_in_tau;
+// the test and its conventions: decode_common.h dae_tile_is_live, shared with prepack.hip live_tiles_kernel).
+//   - the row's own 256 hidden values are requested from the packed image with the dense row's requests (64 float4 per wave,
+//     the same in all four) and wave 0 takes d_row = max |h - 0.5| over the units k < H from them behind the search;
+//   - behind step 3, one lane publishes {d_row, tau} and counts the row in at arrive[row / 128].  The hand-off between
+//     workgroups: payload stored with agent-scope atomic (write-through) stores, drained (s_waitcnt vmcnt(0)) by the storing
+//     lane, which then adds to the counter with an agent-scope atomic; the workgroup whose add returns rows_in_group - 1 knows
+//     that every row of its group has published, runs ONE agent-scope acquire, and only then -- behind a barrier -- do its
+//     waves load the group's payload (with agent-scope atomic loads: vector loads that bypass this CU's L1).  Nobody waits for
+//     anybody: a workgroup that is not last ends;
+//   - that last workgroup is the group's reducer: d_max and tau_min over the group's rows, the edge tile's bound, the test on
+//     every item of the filter launch's list -- a contiguous run of LIVE_PER items per thread, all its list[] loads, then all
+//     its bound loads, one block scan of the counts per 256 * LIVE_PER items -- and the kept tiles in the list's order.  It
+//     leaves arrive[rg] at zero for the next launch on the stream.
+using TauLive = dae_tau_live;      // (dae_internal.h: filled by score.hip topk_phase_a)
+struct TauNoLive {};
+constexpr int LIVE_PER = 16;       // items per thread and chunk of the reducer
 // HAS_S = false: no dense sample to scan (n_s == 0: the bf16 / exact filter launch decodes every tile itself) -- tau only,
 // a third of the registers, so that the workgroup fits on a CU NEXT to a filter workgroup of another batch.
-template <int TAU_PER, bool HAS_S = true>   // TAU_PER: maxima per thread held in registers (rows of <= 256 * TAU_PER maxima in one sweep)
-__global__ __launch_bounds__(256) void tau_select_kernel(const TauP p)
+template <int TAU_PER, bool HAS_S = true, bool LIVE = false>   // TAU_PER: maxima per thread held in registers (rows of <= 256 * TAU_PER maxima in one sweep)
+__global__ __launch_bounds__(256) void tau_select_kernel(const TauP p, const std::conditional_t<LIVE, TauLive, TauNoLive> lv)
 {
+    static_assert(!LIVE || HAS_S, "the live lists belong to a filter launch that does not decode the sample again");
     __shared__ unsigned wcnt[2][4][3];
     __shared__ unsigned wsum[4];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -804,6 +824,19 @@ __global__ __launch_bounds__(256) void tau_select_kernel(const TauP p)
         }
         for (int i = tid; i < TAU_PRE * 256 / 8; i += 256) ltile[i] = p.samp_list[i < (n4 + 7) / 8 ? i : 0];
     }
+    // LIVE: the row's hidden values.  float4 index (g * 4 + rb) * 64 + l of row group rg holds h[rg * 128 + rb * 32 + (l & 31)]
+    // [8 g + 2 e + (l >> 5)], e = component (prepack.hip pack_h / the encode kernel): lane j takes g = j >> 1, l >> 5 = j & 1
+    // (the 64-key shape has no four registers to spare across the search -- they would cost it a wave per SIMD: it asks behind
+    // the search and the latency hides under step 3)
+    constexpr bool HV_EARLY = TAU_PER < 64;
+    float4 hv = make_float4(0.5f, 0.5f, 0.5f, 0.5f);
+    auto load_hv = [&]() {
+        // (every wave asks for the same 64 float4, wave 0 uses them: a branch around the request ends in a wait for it -- and
+        // for the dense row in front of it -- before the search, which is the latency the early request is there to hide)
+        if constexpr (LIVE)
+            hv = lv.hp[((size_t)(row >> 7) * lv.G * 4 + (size_t)((lane >> 1) * 4 + ((row >> 5) & 3))) * 64 + (lane & 1) * 32 + (row & 31)];
+    };
+    if constexpr (LIVE && HV_EARLY) load_hv();
     __builtin_amdgcn_sched_barrier(0);                           // keep every request above ahead of the search
     // ---- 2. tau -------------------------------------------------------------------------------------------------
     // counts of keys >= each of 3 probes over the row (block-uniform results); absent / -inf keys never count
@@ -866,7 +899,25 @@ __global__ __launch_bounds__(256) void tau_select_kernel(const TauP p)
     // leave the row one candidate short: -1 padding instead of an error).
     const unsigned tkey = (p.n_s == 0 && (lo << 16) > DAE_KEY_NEG_INF + 8u) ? (lo << 16) - 4u : (lo << 16);
     const float tv = found ? dae_okey_inv(tkey) : -__builtin_inff();
-    if (tid == 0) p.tau[row] = tv;
+    if (!LIVE && tid == 0) p.tau[row] = tv;                      // (LIVE: published at the end, with d_row)
+    double d_row = 0.0;                                          // LIVE, wave 0: max |h - 0.5| over the row's units k < H (the zero pad would read 0.5)
+    auto take_d_row = [&]() {
+        if constexpr (LIVE) {
+            if (wv == 0) {
+                // (an opaque use HERE: without it the compiler converts the four values to double right behind their request,
+                // i.e. waits for them before the search)
+                asm volatile("" : "+v"(hv.x), "+v"(hv.y), "+v"(hv.z), "+v"(hv.w));
+                const float e[4] = {hv.x, hv.y, hv.z, hv.w};
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    if (8 * (lane >> 1) + 2 * c + (lane & 1) < lv.H) d_row = dae_max_nan(d_row, fabs((double)e[c] - 0.5));
+#pragma unroll
+                for (int sh = 1; sh < 64; sh <<= 1) d_row = dae_max_nan(d_row, __shfl_xor(d_row, sh));
+            }
+        }
+    };
+    if constexpr (LIVE && HV_EARLY) take_d_row();
+    if constexpr (LIVE && !HV_EARLY) load_hv();
     if (!HAS_S) {                                                // no sample to scan: the (empty) survivor list
         if (tid == 0) p.out_cnt[row] = 0;
         return;
@@ -913,6 +964,91 @@ __global__ __launch_bounds__(256) void tau_select_kernel(const TauP p)
     for (int u = 0; u < NPRE; ++u)
         if (((live >> u) & 1u) && u * 256 + tid < n4) emit4(zpre[u], u * 256 + tid, ltile[(u * 256 + tid) >> 3]);
     for (int f = TAU_PRE * 256 + tid; f < n4; f += 256) emit4(srow[f], f, p.samp_list[f >> 3]);
+    if constexpr (LIVE) {
+        // ---- 4. publish {d_row, tau}, arrive; the group's last workgroup builds its live list ----------------------------
+        __shared__ int sh_last;
+        __shared__ double sh_d[4];
+        __shared__ float sh_t[4], sh_edge[2];
+        const int rg = row >> 7, r0 = rg << 7;
+        const int nrows = lv.B - r0 < 128 ? lv.B - r0 : 128;
+        unsigned* const tau_bits = reinterpret_cast<unsigned*>(p.tau);
+        if constexpr (!HV_EARLY) take_d_row();
+        if (tid == 0) {
+            __hip_atomic_store(lv.d_row + row, (unsigned long long)__double_as_longlong(d_row), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(tau_bits + row, __float_as_uint(tv), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // both stores have left before the counter moves
+            const unsigned before = __hip_atomic_fetch_add(lv.arrive + rg, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const int last = before == (unsigned)(nrows - 1) ? 1 : 0;
+            if (last) {
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // ... and the invalidate has completed before the barrier lets the others load
+            }
+            sh_last = last;
+        }
+        __syncthreads();
+        if (!sh_last) return;
+        double d = 0.0;
+        float tm = __builtin_inff();
+        if (tid < nrows) {
+            d = __longlong_as_double((long long)__hip_atomic_load(lv.d_row + r0 + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+            tm = __uint_as_float(__hip_atomic_load(tau_bits + r0 + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        }
+#pragma unroll
+        for (int sh = 1; sh < 64; sh <<= 1) {
+            d = dae_max_nan(d, __shfl_xor(d, sh));
+            tm = dae_min_nan(tm, __shfl_xor(tm, sh));
+        }
+        if (lane == 0) { sh_d[wv] = d; sh_t[wv] = tm; }
+        const int t_edge = (lv.nrank & 31) ? (lv.nrank >> 5) : -1;
+        if (wv == 3 && t_edge >= 0) {                            // (rows sit in waves 0 and 1: this one has nothing in flight)
+            float ea, em;
+            dae_edge_tile_bound(lv.tile_ub, lv.ntiles, lv.nrank, lane, ea, em);
+            if (lane == 0) { sh_edge[0] = ea; sh_edge[1] = em; }
+        }
+        __syncthreads();
+        for (int w = 0; w < 4; ++w) { d = dae_max_nan(d, sh_d[w]); tm = dae_min_nan(tm, sh_t[w]); }
+        const float2* const ub2 = reinterpret_cast<const float2*>(lv.tile_ub);
+        int* const out = lv.live_list + (size_t)rg * lv.n_items;
+        int done = 0;
+        for (int c0 = 0; c0 < lv.n_items; c0 += 256 * LIVE_PER) {
+            const int i0 = c0 + tid * LIVE_PER;
+            int t[LIVE_PER];
+            float2 ub[LIVE_PER];
+#pragma unroll
+            for (int u = 0; u < LIVE_PER; ++u) t[u] = lv.list[i0 + u < lv.n_items ? i0 + u : lv.n_items - 1];
+#pragma unroll
+            for (int u = 0; u < LIVE_PER; ++u) ub[u] = ub2[t[u]];
+            unsigned keep = 0;
+#pragma unroll
+            for (int u = 0; u < LIVE_PER; ++u) {
+                const bool edge = t[u] == t_edge;
+                if (i0 + u < lv.n_items && dae_tile_is_live(edge ? sh_edge[0] : ub[u].x, edge ? sh_edge[1] : ub[u].y, d, tm)) keep |= 1u << u;
+            }
+            const unsigned cnt = (unsigned)__popc(keep);
+            unsigned incl2 = cnt;                                // block-wide exclusive scan of the counts
+#pragma unroll
+            for (int sh = 1; sh < 64; sh <<= 1) {
+                const unsigned o = __shfl_up(incl2, sh);
+                if (lane >= sh) incl2 += o;
+            }
+            if (lane == 63) wsum[wv] = incl2;
+            __syncthreads();
+            int slot = done + (int)(incl2 - cnt);
+            for (int w = 0; w < wv; ++w) slot += (int)wsum[w];
+            done += (int)(wsum[0] + wsum[1] + wsum[2] + wsum[3]);
+#pragma unroll
+            for (int u = 0; u < LIVE_PER; ++u)
+                if ((keep >> u) & 1u) out[slot++] = t[u];
+            __syncthreads();                                     // (wsum is written again by the next chunk)
+        }
+        if (tid == 0) {
+            lv.live_cnt[rg] = done;
+            if (rg == 0) atomicAdd(&lv.stat[0], 1ull);
+            atomicAdd(&lv.stat[1], (unsigned long long)lv.n_items);
+            atomicAdd(&lv.stat[2], (unsigned long long)done);
+            __hip_atomic_store(lv.arrive + rg, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // the next launch on the stream counts from zero
+        }
+    }
 }
 
 // The same for launches of MANY SHORT rows (vocabulary shards, where every rank scores the whole global batch over its
@@ -1016,27 +1152,42 @@ __global__ __launch_bounds__(256) void tau_select_wave_kernel(const TauP p, cons
     }
 }
 
-int launch_tau_select(dae_ctx* ctx, const TauP& p, int B)
+int launch_tau_select(dae_ctx* ctx, const TauP& p, int B, const TauLive* lv)
 {
     if (B <= 0) return DAE_OK;
     // many short rows (>= 4 per CU, <= 2048 maxima and sample logits each: the 8-rank shard of the global batch): a wave
     // per row, everything in registers, no barriers -- 30.1 -> 22.3 us for 2048 rows.  Longer rows lose (4096 maxima per
     // wave = 64 key registers and 128 mask SGPRs per probe: 37 vs 18.6 us at 4 ranks) and keep the workgroup kernel.
-    if (B >= 1024 && p.n_g <= 64 * 32 && (p.n_s >> 2) <= 64 * 8) {
+    // (score_plan.h dae_tau_wave_per_row: the plan asks the same question before it gives this launch the live lists to build)
+    if (dae_tau_wave_per_row(B, p.n_g, p.n_s)) {
+        if (lv) return dae_fail(ctx, DAE_ERR_STATE, "the wave-per-row threshold kernel builds no live lists");
         hipLaunchKernelGGL((tau_select_wave_kernel<32, 8>), dim3((B + 3) / 4), dim3(256), 0, ctx->stream, p, B);
         DAE_CHECK_LAUNCH(ctx, "tau_select_wave_kernel");
         return DAE_OK;
     }
+    if (lv) {
+        if (p.n_s == 0 || lv->G != 32 || lv->n_items <= 0)
+            return dae_fail(ctx, DAE_ERR_STATE, "live lists from the threshold launch: fp32 image of hidden 256 with a dense sample only");
+        if (p.n_g <= 256 * 16)
+            hipLaunchKernelGGL((tau_select_kernel<16, true, true>), dim3(B), dim3(256), 0, ctx->stream, p, *lv);
+        else if (p.n_g <= 256 * 32)
+            hipLaunchKernelGGL((tau_select_kernel<32, true, true>), dim3(B), dim3(256), 0, ctx->stream, p, *lv);
+        else
+            hipLaunchKernelGGL((tau_select_kernel<64, true, true>), dim3(B), dim3(256), 0, ctx->stream, p, *lv);
+        DAE_CHECK_LAUNCH(ctx, "tau_select_kernel");
+        return DAE_OK;
+    }
+    const TauNoLive nl{};
     if (p.n_g <= 256 * 16 && p.n_s == 0)
-        hipLaunchKernelGGL((tau_select_kernel<16, false>), dim3(B), dim3(256), 0, ctx->stream, p);
+        hipLaunchKernelGGL((tau_select_kernel<16, false>), dim3(B), dim3(256), 0, ctx->stream, p, nl);
     else if (p.n_g <= 256 * 32 && p.n_s == 0)
-        hipLaunchKernelGGL((tau_select_kernel<32, false>), dim3(B), dim3(256), 0, ctx->stream, p);
+        hipLaunchKernelGGL((tau_select_kernel<32, false>), dim3(B), dim3(256), 0, ctx->stream, p, nl);
     else if (p.n_g <= 256 * 16)
-        hipLaunchKernelGGL(tau_select_kernel<16>, dim3(B), dim3(256), 0, ctx->stream, p);
+        hipLaunchKernelGGL(tau_select_kernel<16>, dim3(B), dim3(256), 0, ctx->stream, p, nl);
     else if (p.n_g <= 256 * 32)        // batch 1024 on one GPU: 5 120 maxima per row -- half the compares of the 64-key shape
-        hipLaunchKernelGGL(tau_select_kernel<32>, dim3(B), dim3(256), 0, ctx->stream, p);
+        hipLaunchKernelGGL(tau_select_kernel<32>, dim3(B), dim3(256), 0, ctx->stream, p, nl);
     else
-        hipLaunchKernelGGL(tau_select_kernel<64>, dim3(B), dim3(256), 0, ctx->stream, p);
+        hipLaunchKernelGGL(tau_select_kernel<64>, dim3(B), dim3(256), 0, ctx->stream, p, nl);
     DAE_CHECK_LAUNCH(ctx, "tau_select_kernel");
     return DAE_OK;
 }
@@ -1113,12 +1264,12 @@ int launch_topk(dae_ctx* ctx, const Src& src, const dae_topk_args& a)
 
 int dae_launch_tau_select(dae_ctx* ctx, const float* gmax, int64_t ld_g, int n_g, const float* samp, int64_t ld_s,
                           int n_s, const int* samp_list, int col_lo, int B, int k, const int32_t* seed_row_ptr,
-                          float* tau, uint2* out_pairs, int64_t pairs_stride, int* out_cnt)
+                          float* tau, uint2* out_pairs, int64_t pairs_stride, int* out_cnt, const dae_tau_live* live)
 {
     if ((n_s & 31) || (ld_s & 3) || (reinterpret_cast<uintptr_t>(samp) & 15))
         return dae_fail(ctx, DAE_ERR_ARG, "sample rows must be whole tiles, 16-byte aligned");
     TauP p{gmax, ld_g, n_g, samp, ld_s, n_s, samp_list, col_lo, seed_row_ptr, k, tau, out_pairs, pairs_stride, out_cnt};
-    return launch_tau_select(ctx, p, B);
+    return launch_tau_select(ctx, p, B, live);
 }
 
 int dae_launch_topk_dense(dae_ctx* ctx, const dae_dense_src& s, const dae_topk_args& a)
