@@ -484,6 +484,53 @@ int dae_pipeline_submit_eval(dae_pipeline* p, const int64_t* positions, const fl
                              const int32_t* ans_col, uint64_t* ticket_out);
 int dae_pipeline_poll_eval(dae_pipeline* p, int wait, uint64_t* ticket, const dae_metric_rec** rec, int* n_rows, int* block);
 
+/* ---- caller-given candidate columns (csrc/candidates.hip) -----------------------------------------------------------------
+ *
+ * What the reference answers with a slice of the dense matrix: main_train.py:66 / main_challenge.py:80 `sess.run(model.y_pred)`
+ * followed by y_pred[r][cols] -- the scores of a FEW columns per playlist (a second-stage reranker's candidates, held-out
+ * answers among sampled negatives, a market's catalogue) -- here without the [B, V] matrix: per listed (row, column) the
+ * canonical fp32 chain of dae_decode_dense (fmaf over k = 0 .. H-1 from +0, then + b[c]) against the model's own row-major
+ * tensors, bit for bit the dense value at [r, c].  No prepacked image is needed.
+ *
+ * The candidates are a CSR on the device: cand_row_ptr [B + 1] (starting at 0), cand_col [n_cand] int32 GLOBAL column ids,
+ * tracks and artists in any order, duplicates allowed; n_cand = cand_row_ptr[B], passed by the caller (it sizes the launch:
+ * nothing is read back; nothing at or past n_cand is touched).  An id of -1 is padding: its slot receives -inf.  Any other id
+ * outside [0, V) receives a quiet NaN, is never dereferenced and ORs bit 0 into *status (DEVICE int32, nullable; the caller
+ * zeroes it).  1 <= B <= 4096, H % 4 == 0, H <= 1024; the tensors 16-byte aligned.  Asynchronous on the context's stream;
+ * only dae_score_candidates (hidden rows) and dae_rank_candidates (the pair lists) use the context's scratch.
+ *
+ * dae_decode_candidates: out[i] = (out_kind == DAE_OUT_SCORE ? sigmoid : id)(h[r,:] . W_dec[c,:] + b_dec[c]) for c = cand_col[i]
+ *   of row r, in the order of cand_col (DAEs.py:73-77 tied -- pass the encoder matrix -- / :141-145 untied).
+ * dae_score_candidates: the same behind dae_encode with the inference keep-probabilities on the batch CSR (DAEs.py:64-70); the
+ *   hidden rows stay in the context's scratch, as dae_score_topk keeps them.
+ * dae_mix_candidates (on the title scorer's context; `dae` the DAE's, same stream): the TITLED score of the same pairs,
+ *   out[i] = sigmoid(feat[r,:] . OutW_T[c,:] + Out_b[c]) * w_title[r] + sigmoid(h[r,:] . W_dec[c,:] + b_dec[c]) * w_playlist[r]
+ *   (DAEs.py:176-181) with dae_mix_scores' operations in its order: dae_decode_dense x 2 + dae_mix_scores at [r, c], bit for
+ *   bit.  OutW_T [V][ld_feat] = Output_W^T zero padded, feat [B][ld_feat]; ld_feat % 4 == 0, ld_feat <= 1024.
+ * dae_rank_candidates: the k best candidates of every row by `key` [n_cand] (the logits of dae_decode_candidates /
+ *   dae_score_candidates with DAE_OUT_LOGIT, or the mixed scores of dae_mix_candidates), what main_challenge.py:26-36 does to
+ *   a whole row: key descending, then column ascending; the row's seeds removed; out_idx / out_score [B, k], slots beyond the
+ *   list (-1, -inf).  out_score follows out_kind for logits; for mixed keys pass DAE_OUT_LOGIT: it then holds y, as under
+ *   dae_set_score_mix.  The existing selection kernel ranks the lists (no kernel of its own): they are written at a fixed row
+ *   stride, so the call takes row_cap >= the longest row (entries of a row beyond row_cap are not ranked) and V (ids outside
+ *   [0, V), -1 included, are absent; the seed bitmap covers [0, V)).  A column listed twice is ranked twice: de-duplicate
+ *   before the call (models/DAEs.py does).  1 <= k <= 1024.  Scratch: 8 bytes x B x row_cap. */
+#define DAE_CAND_CHUNK 256    /* candidates of one row a workgroup of the candidate kernels takes (a lane each) */
+int dae_decode_candidates(dae_ctx* ctx, const float* h, int64_t ld_h, int B, int H, const float* W_dec, const float* b_dec, int V,
+                          const int32_t* cand_row_ptr, const int32_t* cand_col, int n_cand, int out_kind, float* out,
+                          int32_t* status);
+int dae_score_candidates(dae_ctx* ctx, const int32_t* row_ptr, const int32_t* col, const float* val, const float* W_enc,
+                         const float* b_enc, int V, int H, int B, const float* W_dec, const float* b_dec,
+                         const int32_t* cand_row_ptr, const int32_t* cand_col, int n_cand, int out_kind, float* out,
+                         int32_t* status);
+int dae_mix_candidates(dae_ctx* title_ctx, dae_ctx* dae, const float* h, int64_t ld_h, int H, const float* W_dec,
+                       const float* b_dec, const float* feat, int64_t ld_feat, const float* OutW_T, const float* Out_b,
+                       const float* w_title, const float* w_playlist, int B, int V, const int32_t* cand_row_ptr,
+                       const int32_t* cand_col, int n_cand, float* out, int32_t* status);
+int dae_rank_candidates(dae_ctx* ctx, int B, int V, const int32_t* cand_row_ptr, const int32_t* cand_col, const float* key,
+                        int row_cap, const int32_t* seed_row_ptr, const int32_t* seed_col, int k, int out_kind,
+                        float* out_score, int32_t* out_idx);
+
 /* ---- training step (DAEs.py:98-102) ------------------------------------------------------ */
 
 /* Arithmetic of the three GEMMs of the training step of this context (forward hidden x W_dec^T, gW_dec = dz^T h,

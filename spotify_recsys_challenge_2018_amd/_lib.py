@@ -10,6 +10,7 @@ LIB_PATH = os.path.join(_HERE, "libdae_hip.so")
 
 DAE_OUT_SCORE, DAE_OUT_LOGIT = 0, 1
 DAE_DTYPE_F32, DAE_DTYPE_BF16, DAE_DTYPE_BF16_EXACT = 0, 1, 2
+DAE_CAND_CHUNK = 256            # candidates of one row a workgroup of the candidate kernels takes (include/dae_hip.h)
 
 # every symbol include/dae_hip.h declares (tests/test_abi_cpu.py checks the .so exports all of them)
 EXPORTS = [
@@ -26,6 +27,7 @@ EXPORTS = [
     "dae_pipeline_create", "dae_pipeline_create_titled", "dae_pipeline_destroy", "dae_pipeline_submit", "dae_pipeline_submit_titled", "dae_pipeline_flush", "dae_pipeline_poll",
     "dae_pipeline_release", "dae_pipeline_stats", "dae_pipeline_exact_margin", "dae_pipeline_times", "dae_pipeline_last_error",
     "dae_rank_metrics", "dae_pipeline_enable_eval", "dae_pipeline_submit_eval", "dae_pipeline_poll_eval",
+    "dae_decode_candidates", "dae_score_candidates", "dae_mix_candidates", "dae_rank_candidates",
 ]
 DAE_PIPE_BUSY = 1
 
@@ -160,6 +162,11 @@ def load():
     lib.dae_pipeline_submit_eval.argtypes = [vp, vp, vp, c_int, c_i64, c_int, vp, vp, vp, vp, u64p]
     lib.dae_pipeline_poll_eval.argtypes = [vp, c_int, u64p, ctypes.POINTER(vp), ip, ip]
     lib.dae_pipeline_last_error.restype = ctypes.c_char_p
+    lib.dae_decode_candidates.argtypes = [vp, vp, c_i64, c_int, c_int, vp, vp, c_int, vp, vp, c_int, c_int, vp, vp]
+    lib.dae_score_candidates.argtypes = [vp, vp, vp, vp, vp, vp, c_int, c_int, c_int, vp, vp, vp, vp, c_int, c_int, vp, vp]
+    lib.dae_mix_candidates.argtypes = [vp, vp, vp, c_i64, c_int, vp, vp, vp, c_i64, vp, vp, vp, vp, c_int, c_int, vp, vp,
+                                       c_int, vp, vp]
+    lib.dae_rank_candidates.argtypes = [vp, c_int, c_int, vp, vp, vp, c_int, vp, vp, c_int, c_int, vp, vp]
     for name in EXPORTS:
         if name not in ("dae_last_error", "dae_scratch_bytes", "dae_profile_kernel", "dae_pipeline_last_error"):
             getattr(lib, name).restype = c_int
@@ -540,6 +547,38 @@ class Context:
         self.check(self.lib.dae_mix_topk_exact(self.h, dae_ctx.h, _ptr(feat), int(feat.stride(0)), _ptr(h), int(h.stride(0)),
                                                int(B), _ptr(w_title), _ptr(w_playlist), int(n_tracks), _ptr(seed_row_ptr),
                                                _ptr(seed_col), int(k), _ptr(out_score), _ptr(out_idx), _ptr(guard_out)))
+
+    # ---- caller-given candidate columns (csrc/candidates.hip): cand = (row_ptr int32 [B + 1], col int32 [>= n_cand]) ----------
+    def decode_candidates(self, h, W_dec, b_dec, cand, n_cand, out, out_kind=DAE_OUT_SCORE, status=None):
+        """out[i] = score or logit of column cand_col[i] for its row's hidden row (dae_decode_candidates)."""
+        B, H = h.shape
+        self.check(self.lib.dae_decode_candidates(self.h, _ptr(h), int(h.stride(0)), B, H, _ptr(W_dec), _ptr(b_dec),
+                                                  int(W_dec.shape[0]), _ptr(cand[0]), _ptr(cand[1]), int(n_cand), int(out_kind),
+                                                  _ptr(out), _ptr(status)))
+
+    def score_candidates(self, row_ptr, col, val, W_enc, b_enc, W_dec, b_dec, cand, n_cand, out, out_kind=DAE_OUT_SCORE,
+                         status=None):
+        """dae_encode (inference) + decode_candidates in one call; the hidden rows stay in the context."""
+        V, H = W_enc.shape
+        B = row_ptr.numel() - 1
+        self.check(self.lib.dae_score_candidates(self.h, _ptr(row_ptr), _ptr(col), _ptr(val), _ptr(W_enc), _ptr(b_enc), V, H, B,
+                                                 _ptr(W_dec), _ptr(b_dec), _ptr(cand[0]), _ptr(cand[1]), int(n_cand),
+                                                 int(out_kind), _ptr(out), _ptr(status)))
+
+    def mix_candidates(self, dae_ctx, h, W_dec, b_dec, feat, OutW_T, Out_b, w_title, w_playlist, cand, n_cand, out, status=None):
+        """On the title scorer's context: the title-mixed score of the listed (row, column) pairs (dae_mix_candidates)."""
+        B, H = h.shape
+        self.check(self.lib.dae_mix_candidates(self.h, dae_ctx.h, _ptr(h), int(h.stride(0)), H, _ptr(W_dec), _ptr(b_dec), _ptr(feat),
+                                               int(feat.stride(0)), _ptr(OutW_T), _ptr(Out_b), _ptr(w_title), _ptr(w_playlist),
+                                               B, int(W_dec.shape[0]), _ptr(cand[0]), _ptr(cand[1]), int(n_cand), _ptr(out),
+                                               _ptr(status)))
+
+    def rank_candidates(self, n_cols, cand, key, row_cap, seed_row_ptr, seed_col, k, out_score, out_idx, out_kind=DAE_OUT_SCORE):
+        """The k best candidates of every row by `key` (dae_rank_candidates); row_cap >= the longest row."""
+        B = cand[0].numel() - 1
+        self.check(self.lib.dae_rank_candidates(self.h, B, int(n_cols), _ptr(cand[0]), _ptr(cand[1]), _ptr(key), int(row_cap),
+                                                _ptr(seed_row_ptr), _ptr(seed_col), int(k), int(out_kind), _ptr(out_score),
+                                                _ptr(out_idx)))
 
     def topk_merge(self, cand_logit, cand_idx, out_score, out_idx, out_kind=DAE_OUT_SCORE):
         G, B, k = cand_logit.shape

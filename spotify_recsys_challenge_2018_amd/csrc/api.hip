@@ -92,7 +92,8 @@ int dae_destroy(dae_ctx* ctx)
     for (dae_buf* b : {&ctx->h_packed, &ctx->sample, &ctx->tau, &ctx->sample_top, &ctx->cand, &ctx->cand_cnt, &ctx->gmax,
                        &ctx->h_packed16, &ctx->h_scratch, &ctx->train_a, &ctx->train_b, &ctx->train_c, &ctx->train_d, &ctx->csr_tmp,
                        &ctx->feed_tmp, &ctx->row_bad, &ctx->guard, &ctx->refined, &ctx->refstat, &ctx->mix_fhat, &ctx->title_scratch,
-                       &ctx->tile_band, &ctx->title_tab, &ctx->audit, &ctx->audit_stat, &ctx->title_y1, &ctx->live, &ctx->skip_stat, &ctx->live_sync})
+                       &ctx->tile_band, &ctx->title_tab, &ctx->audit, &ctx->audit_stat, &ctx->title_y1, &ctx->live, &ctx->skip_stat, &ctx->live_sync,
+                       &ctx->cand_list})
         release(*b);
     for (hipEvent_t ev : ctx->prof_ev) (void)hipEventDestroy(ev);
     delete ctx;

@@ -154,6 +154,7 @@ struct dae_ctx {
     // left at zero by every launch) | [Bpad] doubles, the rows' max |h - 0.5|.  Nothing else re-zeroes the counters: a threshold
     // launch that never completes (a device fault) leaves them standing for the life of the context, like the rest of its state
     dae_buf live_sync; void* live_sync_zeroed = nullptr; size_t live_sync_zeroed_bytes = 0;   // (which allocation was zeroed)
+    dae_buf cand_list;         // dae_rank_candidates: [B][row_cap] (key, column) pairs | [B] counts (candidates.hip)
     dae_buf skip_stat;         // 3 x uint64 {launches, planned tiles x row groups, live tiles} since the last dae_filter_skip_read
 
     // profiling of the dominant kernel

@@ -102,6 +102,49 @@ def coo_to_csr(positions, values, n_rows, n_cols=None):
     return row_ptr.astype(np.int32), c.astype(np.int32), v.astype(np.float32)
 
 
+def candidates_to_csr(candidates, n_rows, n_cols, unique=False):
+    """Caller-given candidate columns -> the CSR the candidate kernels take (csrc/candidates.hip): (row_ptr int32
+    [n_rows + 1], col int32 [n_cand]).  `candidates`: a list of per-row id sequences (ragged, possibly empty; fewer than
+    n_rows lists leave the last rows empty), or a 2-D int array [n_rows, C].  Ids are GLOBAL columns, tracks and artists in any
+    order; -1 is padding (it keeps its slot, so results stay aligned with the input).  unique: per row, padding dropped and
+    every column listed once, ascending (what a ranking needs: a column listed twice would be ranked twice).  Any other id
+    outside [0, n_cols) raises ValueError.  Pure numpy: needs no device."""
+    import itertools
+    if isinstance(candidates, np.ndarray) and candidates.ndim == 2:
+        if candidates.dtype.kind not in "iu":
+            raise ValueError("candidates: an integer array is required, got %s" % candidates.dtype)
+        if candidates.shape[0] > n_rows:
+            raise ValueError("candidates: %d rows for a feed of %d" % (candidates.shape[0], n_rows))
+        lens = np.zeros(n_rows, dtype=np.int64)
+        lens[:candidates.shape[0]] = candidates.shape[1]
+        flat = candidates.astype(np.int64).reshape(-1)
+    else:
+        if len(candidates) > n_rows:
+            raise ValueError("candidates: %d rows for a feed of %d" % (len(candidates), n_rows))
+        lens = np.zeros(n_rows, dtype=np.int64)
+        lens[:len(candidates)] = np.fromiter(map(len, candidates), dtype=np.int64, count=len(candidates))
+        total = int(lens.sum())
+        flat = np.fromiter(itertools.chain.from_iterable(candidates), dtype=np.int64, count=total)
+    if flat.size and (flat.min() < -1 or flat.max() >= n_cols):
+        bad = flat[(flat < -1) | (flat >= n_cols)][0]
+        raise ValueError("candidate id %d out of range: -1 (padding) or [0, %d)" % (bad, n_cols))
+    if flat.size >= 2 ** 31:
+        raise ValueError("candidates: %d entries do not fit the int32 offsets of the CSR" % flat.size)
+    if unique:
+        rows = np.repeat(np.arange(n_rows, dtype=np.int64), lens)
+        ok = flat >= 0
+        flat, rows = flat[ok], rows[ok]
+        order = np.lexsort((flat, rows))
+        flat, rows = flat[order], rows[order]
+        first = np.ones(flat.size, dtype=bool)
+        first[1:] = (rows[1:] != rows[:-1]) | (flat[1:] != flat[:-1])
+        flat, rows = flat[first], rows[first]
+        lens = np.bincount(rows, minlength=n_rows).astype(np.int64)
+    row_ptr = np.zeros(n_rows + 1, dtype=np.int64)
+    row_ptr[1:] = np.cumsum(lens)
+    return row_ptr.astype(np.int32), flat.astype(np.int32)
+
+
 def seeds_to_csr(seeds, n_rows, n_tracks):
     """Per-row seed track lists (main_challenge.py:31-35 `cand.remove(i)`) -> CSR of sorted unique
     in-range track ids.  One lexsort over all rows (the per-row np.unique loop was the largest host cost
@@ -552,6 +595,91 @@ class DAE_tied:
                 self._guard_fell_back("exact_bf16: the bound guard fired (%d survivors, e.g. column %d): this batch is re-scored "
                                       "with the fp32 kernels" % (n_bad, col))
                 return self.recommend(x_positions, x_ones, seeds, k=k, n_rows=n_rows, dtype=_lib.DAE_DTYPE_F32)
+        return res
+
+    # -- caller-given candidate columns (csrc/candidates.hip) ---------------------------------------------------------------------
+    _CAND_KINDS = {"sigmoid": _lib.DAE_OUT_SCORE, "logit": _lib.DAE_OUT_LOGIT}
+
+    def _cand_begin(self, candidates, n_rows, unique):
+        """The prologue of the candidate calls.  On the host, before anything is launched: the refusal of a scoring shard and
+        the range-checked CSR of the first n_rows rows' lists.  Then that CSR on the device over the launch's n_batch rows (the
+        rows behind it are empty) and a zeroed status word.  -> (n_rows, host row_ptr, host col, (row_ptr, col) CUDA, status)."""
+        import torch
+        if self._score_shard is not None:
+            raise _lib.DaeError("candidate scoring is not vocabulary-sharded: this model has a scoring shard (shard_scoring); "
+                                "score candidates on a model that holds the whole decoder")
+        n_rows = self.n_batch if n_rows is None else n_rows
+        if n_rows > self.n_batch:
+            raise ValueError("n_rows = %d exceeds the model's batch of %d" % (n_rows, self.n_batch))
+        rp, col = candidates_to_csr(candidates, n_rows, self.n_input, unique=unique)
+        self.sync_params()
+        self.ctx.bind_stream()
+        rp_b = np.full(self.n_batch + 1, rp[-1], np.int32)
+        rp_b[:len(rp)] = rp
+        d_rp = self._to_dev(rp_b, torch.int32)
+        d_col = self._to_dev(col if col.size else np.zeros(1, np.int32), torch.int32)
+        return n_rows, rp, col, (d_rp, d_col), torch.zeros(1, dtype=torch.int32, device=d_rp.device)
+
+    def _cand_status(self, status):
+        """The candidate kernels' range flag joins the feed's: checked lazily by `check_feed`, like the CSR builder's."""
+        import torch
+        cur = torch.cuda.current_stream(self.device_index)
+        self._csr_status = (self._csr_status or []) + [(status, cur.record_event())]
+
+    def _cand_scores(self, x_positions, x_ones, cand, n_cand, out_kind, status):
+        """Enqueue encode + the candidates' chains on the current stream -> the values, a CUDA tensor in the order of the CSR."""
+        import torch
+        csr = self._upload_csr(x_positions, x_ones)
+        out = torch.empty(max(n_cand, 1), dtype=torch.float32, device=csr[0].device)
+        self.ctx.score_candidates(csr[0], csr[1], csr[2], self.weights["encoder_h"], self.biases["encoder_b"],
+                                  self.weights["decoder_h"], self.biases["decoder_b"], cand, n_cand, out, out_kind=out_kind,
+                                  status=status)
+        self._cand_status(status)
+        return out, csr
+
+    @staticmethod
+    def _cand_result(values, candidates, rp):
+        """The fetched values in the caller's form: [n_rows, C] for the 2-D form, else one float32 array per row."""
+        if isinstance(candidates, np.ndarray) and candidates.ndim == 2:
+            out = np.full((len(rp) - 1, candidates.shape[1]), -np.inf, np.float32)
+            out[:candidates.shape[0]] = values.reshape(candidates.shape)
+            return out
+        return [values[rp[r]:rp[r + 1]] for r in range(len(rp) - 1)]
+
+    def score_candidates(self, x_positions, x_ones, candidates, n_rows=None, kind="sigmoid"):
+        """What the model thinks of THESE columns for each playlist: `predict(...)[r][candidates[r]]` without the
+        [n_batch, n_input] matrix -- per listed (row, column) the canonical fp32 chain of the dense decode, the same bits.
+        candidates: a list of per-row id sequences (tracks and artists, any order, repeats allowed; ragged, possibly empty)
+        -> a list of float32 arrays aligned with them; or a 2-D int array [n_rows, C] with -1 padding -> float32 [n_rows, C]
+        (-inf beside a -1), so `score_candidates(feed, recommend(feed)[0])` equals `recommend(feed)[1]`.
+        kind: "sigmoid" (the scores) or "logit".  An id outside -1 / [0, n_input) raises ValueError before any launch.
+        Always fp32: the call is bound by the gathered decoder rows, not by the matrix units."""
+        if kind not in self._CAND_KINDS:
+            raise ValueError("kind %r: one of %s" % (kind, sorted(self._CAND_KINDS)))
+        n_rows, rp, col, cand, status = self._cand_begin(candidates, n_rows, unique=False)
+        out, _csr = self._cand_scores(x_positions, x_ones, cand, int(col.size), self._CAND_KINDS[kind], status)
+        values = out.cpu().numpy()[:col.size]
+        self._check_feed()
+        return self._cand_result(values, candidates, rp)
+
+    def rank_candidates(self, x_positions, x_ones, candidates, seeds, k=500, n_rows=None):
+        """`recommend` restricted to the caller's candidates: per row the k best of its candidate columns (each once, however
+        often it is listed; seeds removed), logit descending then column ascending -> (idx [n_rows, k] int32 with -1 padding,
+        score [n_rows, k] float32, -inf beside a -1).  seeds: as `recommend` takes them, SEEDS_FROM_INPUT included.  With
+        candidates = range(n_tracks) this is `recommend`."""
+        n_rows, rp, col, cand, status = self._cand_begin(candidates, n_rows, unique=True)
+        key, csr = self._cand_scores(x_positions, x_ones, cand, int(col.size), _lib.DAE_OUT_LOGIT, status)
+        return self._cand_rank(cand, rp, key, seeds, csr, k, n_rows, _lib.DAE_OUT_SCORE)
+
+    def _cand_rank(self, cand, rp, key, seeds, csr, k, n_rows, out_kind):
+        import torch
+        d_srp, d_sc = self._seed_csr_dev(seeds, csr)
+        score = torch.empty((self.n_batch, k), dtype=torch.float32, device=key.device)
+        idx = torch.empty((self.n_batch, k), dtype=torch.int32, device=key.device)
+        self.ctx.rank_candidates(self.n_input, cand, key, int(np.diff(rp).max()) if len(rp) > 1 else 0, d_srp, d_sc, k, score, idx,
+                                 out_kind=out_kind)
+        res = idx[:n_rows].cpu().numpy(), score[:n_rows].cpu().numpy()
+        self._check_feed()
         return res
 
     def recommend_iter(self, feeds, k=500, dtype=None, want_scores=True):
@@ -1167,6 +1295,45 @@ class DAE_title(DAE):
         finally:
             tm.ctx.set_score_mix()
         return score, idx
+
+    def _cand_mixed(self, x_positions, x_ones, titles, titles_use, cand, n_cand, status):
+        """Enqueue the titled score of the listed pairs: encode, mixing weights, title features, then both chains per pair and
+        `mixed_scores`' mix (dae_mix_candidates) -- no [n_batch, n_input] matrix of either scorer."""
+        import torch
+        tm = self.title_model
+        tm.ctx.bind_stream()
+        csr = self._upload_csr(x_positions, x_ones)
+        h = torch.empty((self.n_batch, self.n_hidden), dtype=torch.float32, device=csr[0].device)
+        self.ctx.encode(csr[0], csr[1], csr[2], self.weights["encoder_h"], self.biases["encoder_b"], h)
+        w_t, w_p = self._mix_weights(csr, titles_use)
+        feat = tm.features(titles, self.n_batch)
+        out = torch.empty(max(n_cand, 1), dtype=torch.float32, device=h.device)
+        tm.ctx.mix_candidates(self.ctx, h, self.weights["decoder_h"], self.biases["decoder_b"], feat, tm.p["Output_WT"],
+                              tm.p["Output_b"], w_t, w_p, cand, n_cand, out, status=status)
+        self._cand_status(status)
+        return out, csr
+
+    def score_candidates(self, x_positions, x_ones, candidates, n_rows=None, kind="sigmoid", titles=None, titles_use=None):
+        """`DAE.score_candidates`; with titles in use the MIXED score of the listed pairs, `mixed_scores(...)[r][candidates[r]]`
+        bit for bit (kind "sigmoid" only: the mix has no logit).  Without titles in use: the base class's call."""
+        if titles is None or titles_use is None or not np.any(np.asarray(titles_use)):
+            return DAE.score_candidates(self, x_positions, x_ones, candidates, n_rows=n_rows, kind=kind)
+        if kind != "sigmoid":
+            raise ValueError("kind %r: the title-mixed score has no logit; use kind = \"sigmoid\"" % (kind,))
+        n_rows, rp, col, cand, status = self._cand_begin(candidates, n_rows, unique=False)
+        out, _csr = self._cand_mixed(x_positions, x_ones, titles, titles_use, cand, int(col.size), status)
+        values = out.cpu().numpy()[:col.size]
+        self._check_feed()
+        return self._cand_result(values, candidates, rp)
+
+    def rank_candidates(self, x_positions, x_ones, candidates, seeds, k=500, n_rows=None, titles=None, titles_use=None):
+        """`DAE.rank_candidates`; with titles in use the candidates are ranked by the mixed score (score = y), as the titled
+        `recommend` ranks the whole track range."""
+        if titles is None or titles_use is None or not np.any(np.asarray(titles_use)):
+            return DAE.rank_candidates(self, x_positions, x_ones, candidates, seeds, k=k, n_rows=n_rows)
+        n_rows, rp, col, cand, status = self._cand_begin(candidates, n_rows, unique=True)
+        key, csr = self._cand_mixed(x_positions, x_ones, titles, titles_use, cand, int(col.size), status)
+        return self._cand_rank(cand, rp, key, seeds, csr, k, n_rows, _lib.DAE_OUT_LOGIT)     # (out_score holds y)
 
     def _mix_guard_fired(self, idx, k, score):
         """A launch of the exact title mix whose guard words moved is not trusted (a recomputed logit left the interval
