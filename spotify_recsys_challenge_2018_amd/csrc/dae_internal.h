@@ -14,6 +14,7 @@
 #include "../../include/dae_hip.h"
 #include "score_plan.h"            // dae_rowgeom, the host planners, DAE_KG / DAE_MAX_K / DAE_NUM_CU / DAE_NUM_XCD
 #include "mix_plan.h"              // dae_mix_plan: the same for the exact title mix
+#include "tau_search.h"            // DAE_KEY_NEG_INF, the threshold search (host and device)
 
 // ---------------------------------------------------------------------------------------------
 // geometry constants of the decode path (see DESIGN.md "HBM layout")
@@ -146,7 +147,7 @@ struct dae_ctx {
     // the bias-ordered tile list with its sample RE-DEALT for a launch geometry (dae_launch_tile_band): which order it was cut from
     dae_buf tile_band; long long band_gen = -1; int band_nsamp = 0, band_nbrg = 0, band_waves = 0;
     // the fp32 hidden-256 filter launch walks, per row group, only the tiles whose logit bound reaches the group's threshold
-    // (built by the threshold launch itself -- topk.hip tau_select_kernel -- or, on foreign thresholds, by prepack.hip
+    // (built by the threshold launch itself -- tau_select.hip tau_select_kernel -- or, on foreign thresholds, by prepack.hip
     // live_tiles_kernel): [n_rg] counts (16 ints reserved at least) | [n_rg][n_filter] tile ids, in tsB's order
     int filter_skip = 1;       // dae_set_filter_skip
     dae_buf live; int live_n_rg = 0;       // live_n_rg: row groups of the last launch that built the lists (0: none yet)
@@ -274,7 +275,19 @@ __device__ __forceinline__ float dae_okey_inv(uint32_t k)
     uint32_t u = (k & 0x80000000U) ? (k & 0x7FFFFFFFU) : ~k;
     return __uint_as_float(u);
 }
-constexpr uint32_t DAE_KEY_NEG_INF = 0x007FFFFFU;   // dae_okey(-inf): "absent" marker
+// (DAE_KEY_NEG_INF = dae_okey(-inf), the "absent" marker: tau_search.h)
+
+// inclusive scan over the 64 lanes of a wave (every lane active)
+__device__ __forceinline__ unsigned dae_wave_scan_incl(unsigned v, int lane)
+{
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned o = __shfl_up(v, d);
+        if (lane >= d) v += o;
+    }
+    return v;
+}
+__device__ __forceinline__ int dae_wave_scan_incl(int v, int lane) { return (int)dae_wave_scan_incl((unsigned)v, lane); }
 
 // ---------------------------------------------------------------------------------------------
 // launchers (each defined next to its kernels)
@@ -496,7 +509,8 @@ struct dae_topk_args {
     const float* row_min;         // nullable: [B] elements with logit < row_min[row] are absent (an exchanged threshold)
 };
 int dae_launch_topk_dense(dae_ctx* ctx, const dae_dense_src& src, const dae_topk_args& a);
-// Threshold of the fused path + the sample's survivors (topk.hip tau_select_kernel):
+// tau_select.hip
+// Threshold of the fused path + the sample's survivors (tau_select_kernel):
 //   tau[row] = a valid lower bound of the row's k-th largest rankable non-seed logit: the (k + n_seeds(row))-th
 //   largest of gmax[row][0..n_g) (-inf = absent) to 16 key bits; -inf when the row holds fewer finite maxima;
 //   out_pairs[row * pairs_stride + i], i < out_cnt[row]: the (logit, column) of every dense sample logit

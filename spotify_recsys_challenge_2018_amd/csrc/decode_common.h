@@ -56,7 +56,7 @@ struct dae_decp {          // argument block of the decode kernels on the prepac
     // tiles a workgroup decodes in one round of every (row, position in the tile):
     //   gmax[row * ld_gmax + (round * nb_rg + bir) * 32 + c]  = max over waves of z[row][tile(wave)][c]
     // The groups are disjoint sets of columns, so the maxima are distinct elements of the row and their k-th
-    // largest is a valid lower bound of the row's k-th largest logit (tau_select_kernel, topk.hip).  The tiles of
+    // largest is a valid lower bound of the row's k-th largest logit (tau_select_kernel, tau_select.hip).  The tiles of
     // one workgroup sit nb_rg items apart in the bias-ordered list, i.e. in different popularity bands: with ids
     // = popularity ranks the winners are packed into the first tiles, and a group then holds at most one of them
     // (maxima over neighbouring columns would lose 7 of 8: measured, 4 000 instead of 600 survivors per row).
@@ -78,7 +78,7 @@ struct dae_decp {          // argument block of the decode kernels on the prepac
 };
 
 // ---------------------------------------------------------------------------------------------
-// The live lists of the fp32 filter launch: ONE test, shared by the two kernels that build them (topk.hip tau_select_kernel's
+// The live lists of the fp32 filter launch: ONE test, shared by the two kernels that build them (tau_select.hip tau_select_kernel's
 // tail, prepack.hip live_tiles_kernel).  For a row group: d_max = dae_max_nan over its rows r < B and the units k < H of
 // |(double)h[r][k] - 0.5| (the zero padding of the packed tile is NOT read: it would give 0.5), tau_min = dae_min_nan over
 // the same rows of their thresholds.  A tile with the bound {A_t, M_t} (prepack_tile_kernel) is live unless

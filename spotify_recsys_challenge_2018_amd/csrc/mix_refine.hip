@@ -146,12 +146,7 @@ __global__ __launch_bounds__(MR_THREADS, 1) void mix_refine_kernel(const MixRefP
         int carry = 0;
         for (int b0 = 0; b0 < nseg; b0 += 64) {
             const int i = b0 + tid;
-            int v = i < nseg ? seg_prefix[i + 1] : 0;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const int o = __shfl_up(v, d);
-                if (tid >= d) v += o;
-            }
+            const int v = dae_wave_scan_incl(i < nseg ? seg_prefix[i + 1] : 0, tid);
             if (i < nseg) seg_prefix[i + 1] = v + carry;
             carry += __shfl(v, 63);
         }
@@ -284,12 +279,7 @@ __global__ __launch_bounds__(MR_THREADS, 1) void mix_refine_kernel(const MixRefP
         unsigned hc[BPT], own = 0;
 #pragma unroll
         for (int e = 0; e < BPT; ++e) { hc[e] = hist[top - e]; own += hc[e]; }
-        unsigned incl = own;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned o = __shfl_up(incl, d);
-            if (lane >= d) incl += o;
-        }
+        unsigned incl = dae_wave_scan_incl(own, lane);
         if (lane == 63) cnts[8 + wave] = incl;
         __syncthreads();
         unsigned pre = 0;

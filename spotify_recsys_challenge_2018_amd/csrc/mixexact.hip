@@ -10,7 +10,7 @@
 // hidden rows of both scorers (704 k values, two accumulator sets) -- on BOUNDS of the two logits, and only the survivors are
 // recomputed in fp32:
 //   sample launch (mix_filter.hip, MODE 1): biases shifted DOWN by the bounds -> lower bounds l of y over the head of the
-//          bias-ordered tile list; their maxima over groups of 4 columns go to the threshold kernel (tau_select_kernel, topk.hip),
+//          bias-ordered tile list; their maxima over groups of 4 columns go to the threshold kernel (tau_select_kernel, tau_select.hip),
 //          whose tau is a valid lower bound of the row's k-th largest rankable non-seed y;
 //   filter launch (mix_filter.hip, MODE 0): biases shifted UP -> upper logits (u_t, u_d); a column is listed with them when
 //          its upper bound can reach tau.  The test needs no sigmoid and no division: with E = exp(-z),

@@ -136,7 +136,7 @@ __global__ __launch_bounds__(256) void prepack_tile_kernel(const float* __restri
 
 // ---- the live lists of the fp32 filter launch (score.hip topk_phase_b; hidden 256 in 128-row groups) ---------------------
 // The STANDALONE builder.  A call whose filter launch takes the thresholds its own threshold launch computed gets the lists
-// from that launch (topk.hip tau_select_kernel<.., LIVE>: dae_score_plan::live_in_tau) and never runs this kernel; it runs
+// from that launch (tau_select.hip tau_select_kernel<.., LIVE>: dae_score_plan::live_in_tau) and never runs this kernel; it runs
 // where the thresholds come from elsewhere (dae_score_topk_finish: exchanged, possibly raised) or the threshold launch is the
 // wave-per-row kernel.  Both builders apply ONE test, dae_tile_is_live (decode_common.h), to the same d_max and tau_min, so the
 // lists of the two are the same for the same thresholds.

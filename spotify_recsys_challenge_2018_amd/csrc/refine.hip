@@ -101,12 +101,7 @@ __device__ __forceinline__ void refine_body(const RefineP& p)
         int carry = 0;
         for (int b0 = 0; b0 < nseg; b0 += 64) {
             const int i = b0 + tid;
-            int v = i < nseg ? seg_prefix[i + 1] : 0;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const int o = __shfl_up(v, d);
-                if (tid >= d) v += o;
-            }
+            const int v = dae_wave_scan_incl(i < nseg ? seg_prefix[i + 1] : 0, tid);
             if (i < nseg) seg_prefix[i + 1] = v + carry;
             carry += __shfl(v, 63);
         }
@@ -201,12 +196,7 @@ __device__ __forceinline__ void refine_body(const RefineP& p)
         unsigned hc[BPT], own = 0;
 #pragma unroll
         for (int e = 0; e < BPT; ++e) { hc[e] = hist[top - e]; own += hc[e]; }
-        unsigned incl = own;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned o = __shfl_up(incl, d);
-            if (lane >= d) incl += o;
-        }
+        unsigned incl = dae_wave_scan_incl(own, lane);
         if (lane == 63) cnts[8 + wave] = incl;
         __syncthreads();
         unsigned pre = 0;
@@ -718,12 +708,7 @@ __global__ __launch_bounds__(256, 1) void exact_rescore_shared_kernel(const Shar
         int own = 0;
 #pragma unroll
         for (int e = 0; e < SPT; ++e) own += kv_[e] != 0u;
-        int incl = own;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int o = __shfl_up(incl, d);
-            if (lane >= d) incl += o;
-        }
+        const int incl = dae_wave_scan_incl(own, lane);
         if (lane == 63) s_wtot[wave] = incl;
         __syncthreads();
         int pre = incl - own;

@@ -1,6 +1,6 @@
 // score.hip -- the launch sequences of the scoring path behind dae_decode_dense / dae_decode_topk / dae_score_topk* and the
 // titled calls: pack or encode the hidden rows, plan the call (score_plan.h dae_plan_topk), reserve scratch, launch.  The
-// kernels are those of decode_*.hip, topk.hip, refine.hip, audit.hip and mix_*.hip; here live only the two fill kernels.
+// kernels are those of decode_*.hip, tau_select.hip, topk.hip, refine.hip, audit.hip and mix_*.hip; here live only the two fill kernels.
 #include <climits>
 
 #include "dae_internal.h"

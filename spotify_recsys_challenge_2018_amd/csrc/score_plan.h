@@ -87,7 +87,7 @@ struct dae_plan_in {
     int B = 0;                        // rows of the call (which threshold kernel runs: dae_tau_wave_per_row)
 };
 
-// does the threshold launch take tau_select_wave_kernel (topk.hip: a WAVE per row, for launches of many short rows) instead of
+// does the threshold launch take tau_select_wave_kernel (tau_select.hip: a WAVE per row, for launches of many short rows) instead of
 // the workgroup-per-row kernel?  n_g maxima and n_s dense sample logits per row
 inline bool dae_tau_wave_per_row(int B, int64_t n_g, int64_t n_s)
 {
@@ -111,7 +111,7 @@ struct dae_score_plan {
     int n_filter, cap;      // tiles of the filter launch; candidates one of its workgroups can emit per row
     bool build_live;        // the filter launch walks per-row-group live lists (dae_launch_live_tiles: tiles skipped by their bound)
     int32_t last[8];        // what dae_last_plan reports
-    bool live_in_tau;       // build_live, and the threshold launch builds the lists itself (tau_select_kernel's tail, topk.hip): no
+    bool live_in_tau;       // build_live, and the threshold launch builds the lists itself (tau_select_kernel's tail, tau_select.hip): no
                             // launch of live_tiles_kernel
 };
 

@@ -85,7 +85,7 @@ long long sweep()
 
 int main()
 {
-    // the predicate itself, at its three edges (topk.hip launch_tau_select: many short rows take a wave per row)
+    // the predicate itself, at its three edges (tau_select.hip launch_tau_select: many short rows take a wave per row)
     if (!dae_tau_wave_per_row(1024, 2048, 2048) || dae_tau_wave_per_row(1023, 2048, 2048) || dae_tau_wave_per_row(1024, 2049, 2048) ||
         dae_tau_wave_per_row(1024, 2048, 2052) || !dae_tau_wave_per_row(4096, 1, 0)) {
         printf("FAILED: dae_tau_wave_per_row\n");

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the threshold launch builds the live tile lists of the fp32 hidden-256 filter launch itself (topk.hip
+"""GPU (-m gpu): the threshold launch builds the live tile lists of the fp32 hidden-256 filter launch itself (tau_select.hip
 tau_select_kernel's tail: DESIGN.md section 2, "who builds the lists").
 
 Two ways lead to the lists.  dae_score_topk / dae_decode_topk compute the thresholds and hand them to their own filter launch:

@@ -253,6 +253,43 @@ def test_topk_dense_lean_wide_range_bit_exact(ctx):
     _check_topk(idx.cpu().numpy(), score.cpu().numpy(), idx_r, sc_r)
 
 
+def test_topk_dense_lean_seed_scan_bit_exact(ctx):
+    """Lean mode with more seeds than the sort buffer leaves room for (k + seeds = 1 100 > 1 024): the narrowing cannot run
+    seed-blind, so every element is tested against the row's seed list instead.  One row over a range too wide for the bitmap."""
+    import torch
+    n, k, B = 1_200_000, 500, 1
+    rng = np.random.default_rng(23)
+    z = rng.standard_normal((B, n)).astype(np.float32)
+    z[0, 11::30011] = np.partition(z[0], n - 490)[n - 490]      # ties at the value of rank 490: they straddle the cut
+    best = np.argsort(-z[0])
+    seeds = [list(best[:60]) + list(best[470:530:2]) + list(rng.choice(n, size=510, replace=False))]
+    srp, sc = seeds_to_csr(seeds, B, n)
+    assert srp[1] - srp[0] >= 600 - 90 and k + (srp[1] - srp[0]) > 1024      # (duplicates collapse: still past the sort buffer)
+    score = torch.empty((B, k), dtype=torch.float32, device="cuda")
+    idx = torch.empty((B, k), dtype=torch.int32, device="cuda")
+    ctx.topk_dense(_dev(z), n, 0, _dev(srp), _dev(sc), k, score, idx)
+    sc_r, idx_r = oracle.topk(z, k, srp, sc)
+    _check_topk(idx.cpu().numpy(), score.cpu().numpy(), idx_r, sc_r)
+
+
+def test_score_topk_many_short_rows_bit_exact(ctx):
+    """1 024 rows over 6 000 ranked columns: the fused path (188 ranked tiles > the 128 SIMD slots of a row group's workgroups),
+    whose final selection over the candidate lists runs with 256 threads per row at this many rows."""
+    import torch
+    V, nt, H, B, k = 6400, 6000, 32, 1024, 100
+    p = _problem(V, nt, H, B, bias="zipf")
+    ctx.prepack_decoder(_dev(p["W_dec"]), _dev(p["b_dec"]))
+    score = torch.empty((B, k), dtype=torch.float32, device="cuda")
+    idx = torch.empty((B, k), dtype=torch.int32, device="cuda")
+    sc = p["sc"] if p["sc"].size else np.zeros(1, np.int32)
+    ctx.score_topk(_dev(p["rp"]), _dev(p["col"]), _dev(p["val"]), _dev(p["W_enc"]), _dev(p["b_enc"]),
+                   nt, _dev(p["srp"]), _dev(sc), k, score, idx)
+    assert ctx.last_plan()["fused"] == 1, ctx.last_plan()
+    s_ref, i_ref = oracle.score_batch(p["rp"], p["col"], p["val"], p["W_enc"], p["b_enc"], p["W_dec"],
+                                      p["b_dec"], nt, nt, p["srp"], p["sc"], k)
+    _check_topk(idx.cpu().numpy(), score.cpu().numpy(), i_ref, s_ref)
+
+
 def test_shard_merge_bit_exact(ctx):
     """Column-sharded decode + K4 merge == unsharded, run on one GPU."""
     import torch
