@@ -303,7 +303,10 @@ int dae_decode_dense(dae_ctx* ctx, const float* h, int B, int H, int dtype,
  * (seed_row_ptr[B+1], seed_col sorted ascending & unique per row; may be NULL = no seeds).
  * Order: logit descending, then column index ascending.  Writes k entries per row:
  * out_idx[r, i] = GLOBAL column id (or -1 when fewer than k candidates exist, as the reference's
- * cand[:500] of a short list), out_score per `out_kind`.  1 <= k <= 1024.
+ * cand[:500] of a short list), out_score per `out_kind`.
+ * k: 1 <= k <= 4096 (DAE_MAX_K_DEEP) with DAE_DTYPE_F32 / DAE_DTYPE_BF16; 1 <= k <= 1024 (DAE_MAX_K) with
+ * DAE_DTYPE_BF16_EXACT and on a context under dae_set_score_mix.  A larger k is refused before any launch, the message
+ * naming the limit.  Lists of k > 1024 are prefix-extensions of the shorter ones: the same canonical order.
  * The ranked columns are a prefix of the image, and the call decodes the 32-column tiles that hold one and no other: the
  * columns behind them (the artist columns of the reference's vocabulary, which its graph computes before slicing them away,
  * main_challenge.py:87) can return nothing and are not read.  dae_decode_dense is the call that needs their logits.  An image
@@ -318,7 +321,7 @@ int dae_decode_topk(dae_ctx* ctx, const float* h, int B, int H, int dtype,
  * with the hidden activations kept inside the ctx in the decode kernels' operand order (no
  * [B,H] round trip, no re-pack pass).  Results are identical to calling the two separately.
  * This is what main_challenge.py:80-90 / main_train.py:66-89 do per batch.  As dae_decode_topk, it decodes the tiles with a
- * ranked column only. */
+ * ranked column only.  k: as dae_decode_topk (4096; 1024 with DAE_DTYPE_BF16_EXACT or under dae_set_score_mix). */
 int dae_score_topk(dae_ctx* ctx,
                    const int32_t* row_ptr, const int32_t* col, const float* val,
                    const float* W_enc, const float* b_enc, int V, int H, int B, int dtype,
@@ -338,7 +341,8 @@ int dae_score_topk(dae_ctx* ctx,
  *           columns with logit >= tau in rank order, at most k, padded with (-inf, -1): merged over the shards
  *           (dae_topk_merge) they give exactly what the unsharded call returns.
  * One begin / finish pair at a time per context, same stream, 1 <= B <= 4096; seed_row_ptr of finish is the one
- * begin was given.  Replaces the same graph section as dae_score_topk (main_challenge.py:80-90, one batch). */
+ * begin was given.  Replaces the same graph section as dae_score_topk (main_challenge.py:80-90, one batch).
+ * k: 1 <= k <= 4096 with DAE_DTYPE_F32 / DAE_DTYPE_BF16, 1 <= k <= 1024 with DAE_DTYPE_BF16_EXACT (checked by begin). */
 int dae_score_topk_begin(dae_ctx* ctx,
                          const int32_t* row_ptr, const int32_t* col, const float* val,
                          const float* W_enc, const float* b_enc,
@@ -350,14 +354,15 @@ int dae_score_topk_finish(dae_ctx* ctx, const float* tau,
 
 /* Unfused ranking of caller-provided dense logits/scores [B, ld] whose column 0 is global
  * column `col_base`; ranks columns [0, ncols).  Same order/seed rules as dae_decode_topk.
- * (parity path: dae_decode_dense + dae_topk_dense must equal dae_decode_topk.) */
+ * (parity path: dae_decode_dense + dae_topk_dense must equal dae_decode_topk.)  1 <= k <= 4096: rows of k > 1024 are
+ * ranked by an instantiation of the selection kernel with an 8192-key sort buffer, always one 1024-thread workgroup per row. */
 int dae_topk_dense(dae_ctx* ctx, const float* logits, int64_t ld, int B, int ncols, int col_base,
                    const int32_t* seed_row_ptr, const int32_t* seed_col,
                    int k, int out_kind, float* out_score, int32_t* out_idx);
 
 /* Merge G per-shard candidate lists (as produced with DAE_OUT_LOGIT, gathered by RCCL
  * all-gather into cand_logit/cand_idx [G, B, k]) into the global top-k.  idx == -1 entries are
- * ignored. */
+ * ignored.  1 <= k <= 4096. */
 int dae_topk_merge(dae_ctx* ctx, int G, int B, int k,
                    const float* cand_logit, const int32_t* cand_idx,
                    int out_kind, float* out_score, int32_t* out_idx);
@@ -401,6 +406,7 @@ int dae_set_decode_gate(dae_ctx* ctx, void* wait_event, void* record_event);
  *   stats  : {launches issued, feeds submitted, launches re-scored in fp32 after a bound-guard hit}. */
 typedef struct dae_pipeline dae_pipeline;
 #define DAE_PIPE_BUSY 1
+/* k: 1 <= k <= 1024 for every dtype (a larger k is refused at creation). */
 int dae_pipeline_create(int device, const float* W_enc, const float* b_enc, const float* W_dec, const float* b_dec,
                         int V, int H, int n_tracks, int dtype, int k, int group_rows, int64_t max_nnz, int lanes,
                         int want_scores, int result_blocks, dae_pipeline** out);
@@ -514,7 +520,7 @@ int dae_pipeline_poll_eval(dae_pipeline* p, int wait, uint64_t* ticket, const da
  *   dae_set_score_mix.  The existing selection kernel ranks the lists (no kernel of its own): they are written at a fixed row
  *   stride, so the call takes row_cap >= the longest row (entries of a row beyond row_cap are not ranked) and V (ids outside
  *   [0, V), -1 included, are absent; the seed bitmap covers [0, V)).  A column listed twice is ranked twice: de-duplicate
- *   before the call (models/DAEs.py does).  1 <= k <= 1024.  Scratch: 8 bytes x B x row_cap. */
+ *   before the call (models/DAEs.py does).  1 <= k <= 4096.  Scratch: 8 bytes x B x row_cap. */
 #define DAE_CAND_CHUNK 256    /* candidates of one row a workgroup of the candidate kernels takes (a lane each) */
 int dae_decode_candidates(dae_ctx* ctx, const float* h, int64_t ld_h, int B, int H, const float* W_dec, const float* b_dec, int V,
                           const int32_t* cand_row_ptr, const int32_t* cand_col, int n_cand, int out_kind, float* out,
@@ -681,7 +687,8 @@ int dae_set_score_mix(dae_ctx* ctx, const float* mixT, int64_t ld, int n_cols, c
  * launch).  filter_sizes: HOST array.  csr_status: device int32, as dae_coo_to_csr's. */
 /* dae_title_score: the same launch for any dtype -- DAE_DTYPE_BF16_EXACT as above; DAE_DTYPE_F32 / DAE_DTYPE_BF16 through the
  * fused mix (dae_decode_mix_term on the DAE's context, dae_set_score_mix + dae_decode_topk on the title context; both hold
- * their weights prepacked with that dtype), guard_out zeroed.  dae_title_score_exact = dae_title_score(DAE_DTYPE_BF16_EXACT). */
+ * their weights prepacked with that dtype), guard_out zeroed.  dae_title_score_exact = dae_title_score(DAE_DTYPE_BF16_EXACT).
+ * k: 1 <= k <= 1024 for every dtype (as dae_mix_topk_exact), refused before any launch otherwise. */
 int dae_title_score(dae_ctx* title_ctx, dae_ctx* dae, int dtype, const int64_t* positions, const float* values, int values_broadcast,
                     int64_t nnz, int n_rows, int V, const float* W_enc, const float* b_enc, int H,
                     const int32_t* titles, int L, const float* emb, int n_char, int E, const float* conv_w,

@@ -9,6 +9,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libdae_hip.so")
 
 DAE_OUT_SCORE, DAE_OUT_LOGIT = 0, 1
+# largest k (include/dae_hip.h): DAE_MAX_K for the exact mode, the title mix, the pipeline and the metrics kernel; DAE_MAX_K_DEEP for
+# the fp32 / bf16 ranking calls, dae_topk_dense / dae_topk_merge and dae_rank_candidates
+DAE_MAX_K, DAE_MAX_K_DEEP = 1024, 4096
 DAE_DTYPE_F32, DAE_DTYPE_BF16, DAE_DTYPE_BF16_EXACT = 0, 1, 2
 DAE_CAND_CHUNK = 256            # candidates of one row a workgroup of the candidate kernels takes (include/dae_hip.h)
 

@@ -318,7 +318,7 @@ int dae_rank_candidates(dae_ctx* ctx, int B, int V, const int32_t* cand_row_ptr,
     if (!cand_row_ptr || !cand_col || !key || !out_score || !out_idx) return dae_fail(ctx, DAE_ERR_ARG, "null pointer");
     if (B < 1 || B > 4096) return dae_fail(ctx, DAE_ERR_ARG, "B=%d out of [1, 4096]", B);
     if (V <= 0 || row_cap < 0) return dae_fail(ctx, DAE_ERR_ARG, "bad shape V=%d row_cap=%d", V, row_cap);
-    if (k < 1 || k > DAE_MAX_K) return dae_fail(ctx, DAE_ERR_ARG, "k=%d out of [1,%d]", k, DAE_MAX_K);
+    if (k < 1 || k > DAE_MAX_K_DEEP) return dae_fail(ctx, DAE_ERR_ARG, "k=%d out of [1,%d]", k, DAE_MAX_K_DEEP);
     if ((seed_row_ptr == nullptr) != (seed_col == nullptr))
         return dae_fail(ctx, DAE_ERR_ARG, "seed_row_ptr and seed_col must both be given or both null");
     const int cap = row_cap > 0 ? row_cap : 1;

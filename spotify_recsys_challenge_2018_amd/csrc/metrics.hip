@@ -76,7 +76,8 @@ extern "C" int dae_rank_metrics(dae_ctx* ctx, const int32_t* idx, int64_t ld, in
 {
     if (!ctx) return DAE_ERR_ARG;
     if (!idx || !ans_row_ptr || !disc || !out) return dae_fail(ctx, DAE_ERR_ARG, "null pointer");
-    if (k < 1 || k > DAE_MAX_K || ld < k || B < 0) return dae_fail(ctx, DAE_ERR_ARG, "dae_rank_metrics: bad shape B=%d k=%d ld=%lld", B, k, (long long)ld);
+    if (k > DAE_MAX_K) return dae_fail(ctx, DAE_ERR_ARG, "dae_rank_metrics: k=%d out of [1,%d]", k, DAE_MAX_K);
+    if (k < 1 || ld < k || B < 0) return dae_fail(ctx, DAE_ERR_ARG, "dae_rank_metrics: bad shape B=%d k=%d ld=%lld", B, k, (long long)ld);
     if (B == 0) return DAE_OK;
     if (k <= 512)
         hipLaunchKernelGGL(rank_metrics_kernel<8>, dim3(B), dim3(64), 0, ctx->stream, idx, ld, B, k, ans_row_ptr, ans_col, disc, out);

@@ -542,7 +542,9 @@ static int pipeline_create(int device, const float* W_enc, const float* b_enc, c
 {
     if (!out) return pfail(nullptr, DAE_ERR_ARG, "out is null");
     if (!W_enc || !b_enc || !W_dec || !b_dec) return pfail(nullptr, DAE_ERR_ARG, "null pointer");
-    if (V <= 0 || H <= 0 || n_tracks <= 0 || n_tracks > V || k < 1 || k > DAE_MAX_K || group_rows < 1 || group_rows > 16384 ||
+    if (k > DAE_MAX_K) return pfail(nullptr, DAE_ERR_ARG, "dae_pipeline_create: k out of [1,1024]");
+    static_assert(DAE_MAX_K == 1024, "the message above names the limit");
+    if (V <= 0 || H <= 0 || n_tracks <= 0 || n_tracks > V || k < 1 || group_rows < 1 || group_rows > 16384 ||
         max_nnz < 1 || max_nnz >= ((int64_t)1 << 31) || lanes < 1 || lanes > 8)
         return pfail(nullptr, DAE_ERR_ARG, "dae_pipeline_create: bad shape / sizes");
     if (dtype != DAE_DTYPE_F32 && dtype != DAE_DTYPE_BF16 && dtype != DAE_DTYPE_BF16_EXACT)

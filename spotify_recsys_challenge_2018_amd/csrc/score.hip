@@ -298,7 +298,7 @@ static int topk_phase_b(dae_ctx* ctx, const float* tau_src, const int32_t* seed_
     // launch (alone it is slower: 14 vs 11 us); the fp32 launches fill the LDS, nothing fits next to them
     ta.prefer_small = (ctx->overlap_hint && dtype == DAE_DTYPE_BF16) ? 1 : 0;
     if (pl.ntiles == 0) {                            // nothing to rank: the padding of a short list in every slot
-        const int n = B * k;                               // (B <= DAE_ROW_SLAB, k <= DAE_MAX_K)
+        const int n = B * k;                               // (B <= DAE_ROW_SLAB, k <= DAE_MAX_K_DEEP: at most 2^24)
         hipLaunchKernelGGL(fill_pad_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, out_score, out_idx, n);
         DAE_CHECK_LAUNCH(ctx, "fill_pad_kernel");
         return DAE_OK;
@@ -392,12 +392,25 @@ static int decode_topk_core(dae_ctx* ctx, const dae_packed* pk, const dae_rowgeo
                         h32, row_bad);
 }
 
+// k of a ranking call: DAE_MAX_K_DEEP for fp32 / bf16 arithmetic; the exact mode (its refine launch holds DAE_MAX_K winners) and
+// a context under dae_set_score_mix keep DAE_MAX_K
+static int check_k(dae_ctx* ctx, int dtype, int k)
+{
+    const bool keeps = dtype == DAE_DTYPE_BF16_EXACT || ctx->mixT != nullptr;
+    const int k_max = keeps ? DAE_MAX_K : DAE_MAX_K_DEEP;
+    if (k < 1 || k > k_max)
+        return dae_fail(ctx, DAE_ERR_ARG, "k=%d out of [1,%d]%s", k, k_max,
+                        !keeps ? "" : dtype == DAE_DTYPE_BF16_EXACT ? " (DAE_DTYPE_BF16_EXACT)" : " (dae_set_score_mix)");
+    return DAE_OK;
+}
+
 static int check_topk_args(dae_ctx* ctx, int dtype, int k, const int32_t* seed_row_ptr,
                            const int32_t* seed_col, const void* out_score, const void* out_idx)
 {
     if (!out_score || !out_idx) return dae_fail(ctx, DAE_ERR_ARG, "null pointer");
     if (!dae_known_dtype(dtype)) return dae_fail(ctx, DAE_ERR_ARG, "unknown dtype %d", dtype);
-    if (k < 1 || k > DAE_MAX_K) return dae_fail(ctx, DAE_ERR_ARG, "k=%d out of [1,%d]", k, DAE_MAX_K);
+    const int rc_k = check_k(ctx, dtype, k);
+    if (rc_k) return rc_k;
     if ((seed_row_ptr == nullptr) != (seed_col == nullptr))
         return dae_fail(ctx, DAE_ERR_ARG, "seed_row_ptr and seed_col must both be given or both null");
     return DAE_OK;
@@ -517,7 +530,7 @@ int dae_score_topk_begin(dae_ctx* ctx, const int32_t* row_ptr, const int32_t* co
     if (!ctx) return DAE_ERR_ARG;
     if (!tau_out) return dae_fail(ctx, DAE_ERR_ARG, "null pointer");
     if (!dae_known_dtype(dtype)) return dae_fail(ctx, DAE_ERR_ARG, "unknown dtype %d", dtype);
-    if (k < 1 || k > DAE_MAX_K) return dae_fail(ctx, DAE_ERR_ARG, "k=%d out of [1,%d]", k, DAE_MAX_K);
+    if (const int rc_k = check_k(ctx, dtype, k)) return rc_k;
     if (B < 1 || B > DAE_ROW_SLAB) return dae_fail(ctx, DAE_ERR_ARG, "dae_score_topk_begin takes 1..%d rows (B=%d)", DAE_ROW_SLAB, B);
     if (ctx->mixT) return dae_fail(ctx, DAE_ERR_ARG, "dae_score_topk_begin is not available with dae_set_score_mix");
     const dae_packed* pk; dae_rowgeom g; const float* h32;
@@ -649,6 +662,8 @@ int dae_title_score(dae_ctx* tc, dae_ctx* dc, int dtype, const int64_t* position
     if (!tc) return DAE_ERR_ARG;
     if (!dc || dc == tc) return dae_fail(tc, DAE_ERR_ARG, "dae_title_score: needs the DAE's context");
     if (!dae_known_dtype(dtype)) return dae_fail(tc, DAE_ERR_ARG, "unknown dtype %d", dtype);
+    // (every dtype: the exact mix, and the fp32 / bf16 mix under dae_set_score_mix, keep DAE_MAX_K -- refused before any launch)
+    if (k < 1 || k > DAE_MAX_K) return dae_fail(tc, DAE_ERR_ARG, "k=%d out of [1,%d] (titled scoring)", k, DAE_MAX_K);
     if (!titles || !titles_use || !W_enc || !b_enc || !csr_status || (nnz > 0 && (!positions || !values)))
         return dae_fail(tc, DAE_ERR_ARG, "null pointer");
     if (n_rows <= 0) return DAE_OK;

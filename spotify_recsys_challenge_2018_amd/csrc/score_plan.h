@@ -9,7 +9,8 @@
 #include "../../include/dae_hip.h"
 
 constexpr int DAE_KG = 8;         // k values per packed group (4 MFMA 32x32x2 steps)
-constexpr int DAE_MAX_K = 1024;   // largest top-k supported
+constexpr int DAE_MAX_K = 1024;   // largest top-k of the paths that keep one 2048-key sort buffer: the exact mode, the title mix, the pipeline, the metrics kernel
+constexpr int DAE_MAX_K_DEEP = 4096;   // largest top-k of the selection itself and of the fp32 / bf16 ranking calls (topk.hip: the 8192-key instantiation)
 constexpr int DAE_NUM_CU = 256;   // MI355X
 constexpr int DAE_NUM_XCD = 8;
 

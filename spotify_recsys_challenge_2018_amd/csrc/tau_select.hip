@@ -357,7 +357,12 @@ __global__ __launch_bounds__(256) void tau_select_wave_kernel(const TauP p, cons
 }
 
 // per = TAU_PER: 16 for rows of <= 4 096 maxima; 32 up to 8 192 (batch 1024 on one GPU: 5 120 maxima per row -- half the
-// compares of the 64-key shape); 64 beyond, which has no sample-free instance (it sees n_s == 0 at run time)
+// compares of the 64-key shape); 64 beyond, which has no sample-free instance (it sees n_s == 0 at run time).
+// Deep k (<= DAE_MAX_K_DEEP) changes no shape: the plan keeps every sample element as a maximum while a row has fewer than 4 k
+// of them, so a row can hold more than 256 * 64 slots (e.g. 4 x 8 192, most of them -inf): the 64-key shape then reads the
+// maxima from memory in every search step (one_sweep = false).  A row with fewer than k + n_seeds finite maxima leaves the
+// search at DAE_TAU_P_MIN - 1, i.e. tau = -inf (tau_search.h), in this kernel and in the wave-per-row one, which only takes rows
+// of <= 64 * 32 maxima whatever k is (dae_tau_wave_per_row).
 template <bool HAS_S, bool LIVE, typename Lv>
 void launch_tau_per(dae_ctx* ctx, const TauP& p, int B, int per, const Lv& lv)
 {

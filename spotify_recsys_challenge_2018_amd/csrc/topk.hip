@@ -16,7 +16,8 @@
 //      (keys are unique, so no tie handling exists anywhere);
 //   4. collect those keys; k <= 512: order them by HISTOGRAM RANK (position = keys in higher bins + keys of the
 //      own bin above; one LDS atomic per key, a suffix scan, a count inside the bin); k > 512: hybrid bitonic sort
-//      (wave shuffles + LDS stages); emit k.
+//      (wave shuffles + LDS stages); emit k.  k > 1024 (<= 4096): the same with a sort buffer of 4096 or 8192 keys, 4 or 8 per
+//      thread (the TK_SORT_DEEP instantiation below).
 // Rows whose elements do not fit the LDS key buffer (dae_topk_dense over a whole vocabulary row)
 // run the same steps with step 3 re-reading the source instead of LDS.
 //
@@ -32,6 +33,17 @@ constexpr int TK_BINS = DAE_RANK_BINS;
 constexpr int TK_MAX_SEG = 1024;
 constexpr int TK_SORT_MAX = 2048;
 static_assert(TK_SORT_MAX == 2 * DAE_RANK_MAX, "k <= 512 collects what dae_rank_order takes; k > 512 sorts twice as many");
+// deep rows (DAE_MAX_K < k <= DAE_MAX_K_DEEP) run an instantiation of their own with a sort buffer of TK_SORT_DEEP keys; the
+// instantiations for k <= DAE_MAX_K keep TK_SORT_MAX, and with it their code, registers and LDS (profiles/deep_k_notes.md)
+constexpr int TK_SORT_DEEP = 8192;
+constexpr size_t TK_LDS_TOTAL = 160 * 1024, TK_LDS_STATIC = 14 * 1024;   // the CU's LDS; hist 8K + seg_prefix 4K + scalars
+static_assert(TK_SORT_DEEP >= 2 * DAE_MAX_K_DEEP, "the deep sort buffer holds twice the largest k, as TK_SORT_MAX does for DAE_MAX_K");
+static_assert(TK_SORT_DEEP % 1024 == 0 && (TK_SORT_DEEP & (TK_SORT_DEEP - 1)) == 0, "a bitonic network over whole slots of 1024 threads");
+// the deep LDS budget: 64 KiB sort buffer + the seed bitmap of the shipped vocabulary (170 000 columns: ~21 KiB) + the static
+// part + at least the 8 KiB second buffer / key cache
+static_assert((size_t)TK_SORT_DEEP * 8 == 64 * 1024, "deep sort buffer: 64 KiB");
+static_assert((size_t)TK_SORT_DEEP * 8 + ((170000 + 31) / 32 * 4 + 15) / 16 * 16 + TK_LDS_STATIC + 8 * 1024 <= TK_LDS_TOTAL,
+              "deep sort buffer + seed bitmap over 170 000 columns + static LDS + the smallest key cache fit one CU");
 typedef dae_u64 u64;
 
 struct DenseSrc {
@@ -180,13 +192,17 @@ struct SoaSrc {
 // lists, small shards, gathered shard lists) -- a short row is bound by the fixed cost of every stage
 // (histogram clears, bin scans, barriers joining 16 waves), which a quarter of the threads cuts to a
 // quarter, and up to 8 such workgroups share a CU.  Same stages, same results.
-template <typename Src, int NTH>
+// CAP: the sort buffer's capacity in keys -- TK_SORT_MAX for k <= DAE_MAX_K; TK_SORT_DEEP (1024 threads only) for deeper lists:
+// the same stages with a.sort_cap (4096 or 8192) keys collected and sorted, and CAP thread maxima behind the 3a cut.
+template <typename Src, int NTH, int CAP = TK_SORT_MAX>
 __global__ __launch_bounds__(NTH) void topk_kernel(const Src src, const dae_topk_args a,
                                                    const int key_cap)
 {
+    static_assert(CAP == TK_SORT_MAX || (CAP == TK_SORT_DEEP && NTH == 1024), "deep rows always take the 1024-thread shape");
     constexpr int TK_WAVES = NTH / 64;
-    constexpr int MAXES = 1024 / NTH;                            // per-thread maxima kept for the 3a cut (1024 in all)
-    constexpr int EMAX = TK_SORT_MAX / NTH;                      // sort-buffer keys per thread, at most
+    // per-thread maxima kept for the 3a cut: 1024 in all; deep: CAP in all (the k-th largest of fewer than 2 k maxima cuts nothing)
+    constexpr int MAXES = CAP == TK_SORT_MAX ? 1024 / NTH : CAP / NTH;
+    constexpr int EMAX = CAP / NTH;                              // sort-buffer keys per thread, at most
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
     __shared__ unsigned hist[TK_BINS];
     __shared__ int seg_prefix[Src::kSegs + 2];
@@ -233,6 +249,7 @@ __global__ __launch_bounds__(NTH) void topk_kernel(const Src src, const dae_topk
     while (sort_n < k) sort_n <<= 1;
     if (sort_n < 1024) sort_n = 1024;                            // always <= TK_SORT_MAX (k <= 1024)
     if (k > 512) sort_n = TK_SORT_MAX;
+    if (CAP > TK_SORT_MAX) sort_n = a.sort_cap;                  // deep: 4096 (k <= 2048) or 8192, chosen by launch_topk
     const bool seed_blind = lean && ns > 0 && k + ns <= sort_n;  // remove the seeds after the collect
     const bool seed_scan = lean && ns > 0 && !seed_blind;         // (rare) test every element
     auto is_seed = [&](int colv) -> bool {
@@ -258,7 +275,7 @@ __global__ __launch_bounds__(NTH) void topk_kernel(const Src src, const dae_topk
 
     // ---- 2. first read: keys -> LDS (if they fit), count, min, max ---------------------------------
     // this thread's largest keys, one per class of its elements (class = visit number mod MAXES): MAXES x NTH
-    // = 1024 distinct elements of the row in all
+    // = 1024 (deep: CAP) distinct elements of the row in all
     u64 tmaxv[MAXES];
 #pragma unroll
     for (int c = 0; c < MAXES; ++c) tmaxv[c] = 0ull;
@@ -508,7 +525,7 @@ __global__ __launch_bounds__(NTH) void topk_kernel(const Src src, const dae_topk
         if (a.out_tau && i == (unsigned)k - 1) a.out_tau[row] = z;
     };
     // ---- 5a. k <= 512 (at most 1024 keys were collected): order by histogram rank (rank_lds.h dae_rank_order) ----------
-    if (sort_n == 1024) {
+    if (CAP == TK_SORT_MAX && sort_n == 1024) {
         constexpr int PER = 1024 / NTH;                          // collected keys per thread (slot e * NTH + tid)
         const unsigned c = s_cnt < 1024u ? s_cnt : 1024u;
         u64 mine[PER];
@@ -586,11 +603,13 @@ __global__ __launch_bounds__(NTH) void topk_kernel(const Src src, const dae_topk
 template <typename Src>
 int launch_topk(dae_ctx* ctx, const Src& src, const dae_topk_args& a)
 {
-    if (a.k < 1 || a.k > DAE_MAX_K)
-        return dae_fail(ctx, DAE_ERR_ARG, "k=%d out of [1,%d]", a.k, DAE_MAX_K);
+    if (a.k < 1 || a.k > DAE_MAX_K_DEEP)
+        return dae_fail(ctx, DAE_ERR_ARG, "k=%d out of [1,%d]", a.k, DAE_MAX_K_DEEP);
     if (a.B <= 0) return DAE_OK;
+    const bool deep = a.k > DAE_MAX_K;                           // topk_kernel<Src, 1024, TK_SORT_DEEP>
     int sort_n = 1024;
     if (a.k > 512) sort_n = TK_SORT_MAX;
+    if (deep) sort_n = a.k > TK_SORT_DEEP / 4 ? TK_SORT_DEEP : TK_SORT_DEEP / 2;
     dae_topk_args aa = a;
     aa.sort_cap = sort_n;
     // Two LDS modes, both covered by the parity tests:
@@ -600,9 +619,10 @@ int launch_topk(dae_ctx* ctx, const Src& src, const dae_topk_args& a)
     //     thread, so a workgroup fits on a CU NEXT to a decode workgroup of another batch.  Measured
     //     (profiles/r01_notes.md): the co-resident decode launch slows down by about what the overlap
     //     gains, and the kernel alone is slower (re-reads its source), so it is not the default.
+    //     (deep rows: the sort buffer alone is 32 / 64 KiB -- no cache beside it, nothing shares the CU.)
     // a ranked range too wide for the LDS bitmap (> ~1 M columns) takes the bitmap-free mode instead of failing
     aa.lean = (((size_t)((a.bitmap_n + 31) / 32) * 4) + 15) + (size_t)sort_n * 8 + 22 * 1024 > (size_t)160 * 1024 ? 1 : 0;
-    const size_t lds_total = 160 * 1024, lds_static = 14 * 1024;    // hist 8K + seg_prefix 4K + scalars
+    const size_t lds_total = TK_LDS_TOTAL, lds_static = TK_LDS_STATIC;
     size_t dyn;
     int key_cap;
     if (aa.lean) {
@@ -620,12 +640,17 @@ int launch_topk(dae_ctx* ctx, const Src& src, const dae_topk_args& a)
         const size_t room = lds_total - lds_static - bm_bytes - (size_t)sort_n * 8;
         size_t want = (size_t)(src.max_keys() > 0 ? src.max_keys() : 8192) * 8;
         if (want < 1024 * 8) want = 1024 * 8;                   // the ordering stage's second buffer (1024 keys)
+        if (deep) want = room;                                   // one workgroup per CU whatever the cache: a deep row keeps what fits
         if (want > room) want = room;
         key_cap = (int)(want / 8);
         dyn = bm_bytes + (size_t)sort_n * 8 + want;
     }
-    static const char attr_set_key = 0;
-    if (dae_first_use(ctx, &attr_set_key)) {
+    static const char attr_set_key = 0, attr_set_key_deep = 0;
+    if (deep && dae_first_use(ctx, &attr_set_key_deep))
+        DAE_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&topk_kernel<Src, 1024, TK_SORT_DEEP>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               (int)(lds_total - lds_static)));
+    if (!deep && dae_first_use(ctx, &attr_set_key)) {
         DAE_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&topk_kernel<Src, 1024>),
                                                hipFuncAttributeMaxDynamicSharedMemorySize,
                                                (int)(lds_total - lds_static)));
@@ -643,7 +668,9 @@ int launch_topk(dae_ctx* ctx, const Src& src, const dae_topk_args& a)
     // holds few candidates, four 256-thread workgroups share a CU, and the per-row fixed cost is what counts
     // (--sim-world 8, 2048 rows: step 322 -> 284 us; at 256 rows 256 threads lose: 22 vs 14 us)
     const bool small = (!Src::kSegs && bound <= 4096) || (Src::kSegs && (a.B >= 1024 || a.prefer_small));
-    if (small)
+    if (deep)                                                    // never the 256-thread shape: 8192 keys are 8 per thread of 1024
+        hipLaunchKernelGGL((topk_kernel<Src, 1024, TK_SORT_DEEP>), dim3(a.B), dim3(1024), dyn, ctx->stream, src, aa, key_cap);
+    else if (small)
         hipLaunchKernelGGL((topk_kernel<Src, 256>), dim3(a.B), dim3(256), dyn, ctx->stream, src, aa, key_cap);
     else
         hipLaunchKernelGGL((topk_kernel<Src, 1024>), dim3(a.B), dim3(1024), dyn, ctx->stream, src, aa, key_cap);

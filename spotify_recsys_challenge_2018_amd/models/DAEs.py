@@ -51,6 +51,25 @@ def _title_dtype(dtype, model):
     return _lib.DAE_DTYPE_F32
 
 
+def _deep_k_dtype(dtype, k, model):
+    """Arithmetic of a plain ranking call at k > DAE_MAX_K.  The exact mode's kernels keep k <= 1024; its contract is
+    the fp32 lists, so a deeper call runs the fp32 kernels and says so once, as `_title_dtype` does for its fallback."""
+    if dtype != _lib.DAE_DTYPE_BF16_EXACT or k <= _lib.DAE_MAX_K:
+        return dtype
+    if not model._deep_k_said:
+        model._deep_k_said = True
+        import sys
+        print("[dae] decode_dtype = exact_bf16: the exact mode ranks k <= %d; calls with a larger k (here %d) run on the fp32 "
+              "kernels (same lists, slower)" % (_lib.DAE_MAX_K, k), file=sys.stderr)
+    return _lib.DAE_DTYPE_F32
+
+
+def _refuse_deep_k(k, what):
+    if k > _lib.DAE_MAX_K:
+        raise ValueError("%s takes k <= %d (got %d): deeper lists come from `recommend` / `rank_candidates` without titles, "
+                         "k <= %d" % (what, _lib.DAE_MAX_K, k, _lib.DAE_MAX_K_DEEP))
+
+
 class _Placeholder:
     """Stands in for a tf.placeholder: only used as a feed_dict key."""
 
@@ -239,6 +258,7 @@ class DAE_tied:
         self._pipes = {}              # the streamed loop's pipelines (stream_loop.py): key -> (generation, _lib.Pipeline)
         self.coalesce = self.n_lanes = None      # set from outside: feeds per launch, lanes (None: `_coalesce_count` / three)
         self.keep_pipelines, self._old_pipes = False, []      # ... and (diagnosis) retired pipelines kept alive, here
+        self._deep_k_said = False     # `_deep_k_dtype` said that exact_bf16 calls with k > 1024 run on the fp32 kernels
         self._guard_fallbacks = 0     # batches / launches re-scored in fp32 because the exact mode's bound guard fired
 
     # -- parameters ---------------------------------------------------------------------------------
@@ -552,7 +572,7 @@ class DAE_tied:
         Equivalent of main_challenge.py:80-90 / main_train.py:66-89 without the dense matrix.
         Returns (idx [n_rows,k] int32 with -1 padding, score [n_rows,k] float32)."""
         import torch
-        dtype = self._dtype_of(dtype)
+        dtype = _deep_k_dtype(self._dtype_of(dtype), k, self)
         sh = self._score_shard
         self._ensure_packed(dtype, None if sh is None else sh["cols"])
         self.ctx.bind_stream()
@@ -683,6 +703,12 @@ class DAE_tied:
         return res
 
     def recommend_iter(self, feeds, k=500, dtype=None, want_scores=True):
+        """`recommend` over a stream of batches (`_recommend_iter`).  k <= 1024: the pipeline behind the loop keeps that limit, and a
+        larger k raises ValueError here, before a pipeline is created."""
+        _refuse_deep_k(k, "recommend_iter")
+        return self._recommend_iter(feeds, k, dtype, want_scores)
+
+    def _recommend_iter(self, feeds, k, dtype, want_scores):
         """`recommend` over a stream of batches with the host and the device overlapped (the loop of
         main_challenge.py:72-93 / main_train.py:62-96): `feeds` yields (x_positions, x_ones, seeds, n_rows) (DAE_title:
         + titles, titles_use); the generator yields (idx [n_rows,k], score [n_rows,k] or None) in order, one pair per feed.
@@ -707,6 +733,12 @@ class DAE_tied:
             yield idx, (score if want_scores else None)
 
     def evaluate_iter(self, feeds, k=500, dtype=None):
+        """The evaluation loop with the metrics computed on the device (`_evaluate_iter`).  k <= 1024 (the pipeline and the metrics
+        kernel): a larger k raises ValueError here, before a pipeline is created."""
+        _refuse_deep_k(k, "evaluate_iter")
+        return self._evaluate_iter(feeds, k, dtype)
+
+    def _evaluate_iter(self, feeds, k, dtype):
         """The evaluation loop (main_train.py:48-100) with the metrics computed on the device: `feeds` yields
         (feed, answers) -- `feed` what `recommend_iter` takes, `answers` one id list per row of the feed (the reader's
         `test_answer`: ints, -1 and duplicates allowed) -- and the generator yields, per feed and in order, the rows' records
@@ -1399,6 +1431,7 @@ class DAE_title(DAE):
         the mix, the threshold and the ranking stay fp32."""
         if titles is None or titles_use is None or not np.any(np.asarray(titles_use)):
             return DAE.recommend(self, x_positions, x_ones, seeds, k=k, n_rows=n_rows, dtype=dtype)
+        _refuse_deep_k(k, "DAE_title.recommend with titles in use")       # (before any upload)
         if self._score_shard is not None:
             raise _lib.DaeError("title-mixed batches are not vocabulary-sharded: run --challenge with titles on one "
                                 "GPU per process group (playlist partitioning), or without the title variables")
