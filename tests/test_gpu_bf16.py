@@ -201,15 +201,24 @@ def test_bf16_fused_equals_unfused_across_shapes(ctx, V, nt, B, k):
     assert np.max(np.abs(z.cpu().numpy() - z_ref)) <= 3e-5
 
 
-@pytest.mark.parametrize("B", [1024, 2048])
-def test_bf16_fused_equals_unfused_at_the_loops_launch_sizes(B):
-    """Full vocabulary, the launches the drivers' loop issues (1 024 / 2 048 rows): phase A takes per-WAVE group maxima there
-    (decode_bf16_h256_wavemax_kernel; waves paired at 1 024 rows).  A threshold that was too high would lose winners: the fused
-    lists must equal the dense bf16 logits ranked by the same rule, indices and scores."""
+# the un-hinted pair branch's row of tests/golden/score_plans.txt (tests/test_score_plan_cpu.py pins the planner to it): its last[8]
+PAIR_ROW = "10_bf16_1024_rows_131072_tracks_pair"
+
+
+@pytest.mark.parametrize("V,nt,B", [pytest.param(170000, 140000, 1024, id="1024"), pytest.param(170000, 140000, 2048, id="2048"),
+                                    pytest.param(140000, 131072, 1024, id="131072-tracks-1024")])
+def test_bf16_fused_equals_unfused_at_the_loops_launch_sizes(V, nt, B):
+    """The launches the drivers' loop issues (1 024 / 2 048 rows).  Full vocabulary at 1 024 rows: since ranking calls walk the
+    ranked tiles only the sample is 487 tiles, fewer than two per wave slot (2 x 32 x 8), so phase A takes the generic
+    group-maxima kernel on the band-dealt list.  At 2 048 rows it takes per-WAVE group maxima (decode_bf16_h256_wavemax_kernel,
+    gmax_per_wave 3).  131 072 tracks of 140 000 columns at 1 024 rows plan a sample of 512 tiles: the per-wave kernel with
+    waves w and w + 4 paired (gmax_per_wave 4) -- the pair branch without the overlap hint, at the loop's launch size
+    (tests/test_gpu_overlap_hint.py runs it under the hint).  A threshold that was too high would lose winners: the fused lists
+    must equal the dense bf16 logits ranked by the same rule, indices and scores."""
     import torch
     c = _lib.Context(0)
     try:
-        V, nt, H, k = 170000, 140000, 256, 500
+        H, k = 256, 500
         W_enc, b_enc, W_dec, b_dec = make_weights(V, H, seed=0, bias="zipf", n_tracks=nt)
         pos, ones, seeds = make_playlists(B, nt, V - nt, seed=21)
         rp, col, val = coo_to_csr(pos, ones, B, V)
@@ -219,6 +228,11 @@ def test_bf16_fused_equals_unfused_at_the_loops_launch_sizes(B):
         s16 = torch.empty((B, k), device="cuda"); i16 = torch.empty((B, k), dtype=torch.int32, device="cuda")
         c.score_topk(d[0], d[1], d[2], d[3], d[4], nt, d[7], d[8], k, s16, i16, dtype=BF)
         assert c.last_plan()["fused"] == 1
+        if nt == 131072:
+            with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "score_plans.txt")) as f:
+                words = [ln.split("|")[2].split() for ln in f if ln.startswith(PAIR_ROW + " ")][0]
+            assert (words[17], words[21]) == ("1", "4")                    # wave_groups, gmax_per_wave
+            assert list(c.last_plan().values()) == [int(x) for x in words[26:]], c.last_plan()
         h = torch.empty((B, H), device="cuda")
         c.encode(d[0], d[1], d[2], d[3], d[4], h)
         z = torch.empty((B, V), device="cuda")
