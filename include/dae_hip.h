@@ -256,6 +256,16 @@ int dae_set_filter_skip(dae_ctx* ctx, int on);
 int dae_filter_skip_read(dae_ctx* ctx, uint64_t out3[3]);
 int dae_filter_skip_last(dae_ctx* ctx, int32_t* live_out, int cap, int* n_rg_out);
 int dae_tile_bounds_read(dae_ctx* ctx, float* ub_out, int cap_tiles, int* ntiles_out);
+/* The same switch covers the threshold SAMPLE of such a call where it runs in half row groups (65..256 rows, a sample of one
+ * round of tiles): per column the image also keeps lo_c with fp32 logit(r, c) >= lo_c - d * m_c, so a lower bound tau_safe of
+ * every row's threshold is known before the sample runs, and a wave whose tile has A_t + d M_t < tau_safe decodes nothing
+ * (its logits could neither move tau nor survive it).  Thresholds, lists and scores stay bit for bit those of the full walk.
+ *   dae_sample_skip_read: out3 = {sample launches that could skip, wave-tiles they planned (sum), wave-tiles they decoded
+ *                         (sum)} since the last read; resets the counters; synchronises the ctx stream. */
+int dae_sample_skip_read(dae_ctx* ctx, uint64_t out3[3]);
+/* The thresholds the context's last dae_score_topk / dae_decode_topk (its last slab of rows) computed and gave its own filter
+ * launch: tau_out[0 .. B) on the HOST (what dae_score_topk_begin returns to its caller).  Synchronises the ctx stream. */
+int dae_last_tau_read(dae_ctx* ctx, float* tau_out, int B);
 
 /* Factor on every eps_c computed by the NEXT dae_prepack_decoder(DAE_DTYPE_BF16_EXACT) of this context (default 1).
  * > 1 widens the bounds: a safety margin for a caller who distrusts the error model (more survivors to recompute, same

@@ -93,6 +93,7 @@ int dae_destroy(dae_ctx* ctx)
                        &ctx->h_packed16, &ctx->h_scratch, &ctx->train_a, &ctx->train_b, &ctx->train_c, &ctx->train_d, &ctx->csr_tmp,
                        &ctx->feed_tmp, &ctx->row_bad, &ctx->guard, &ctx->refined, &ctx->refstat, &ctx->mix_fhat, &ctx->title_scratch,
                        &ctx->tile_band, &ctx->title_tab, &ctx->audit, &ctx->audit_stat, &ctx->title_y1, &ctx->live, &ctx->skip_stat, &ctx->live_sync,
+                       &ctx->row_d, &ctx->samp_tab, &ctx->sskip_stat,
                        &ctx->cand_list})
         release(*b);
     for (hipEvent_t ev : ctx->prof_ev) (void)hipEventDestroy(ev);
@@ -320,6 +321,33 @@ int dae_filter_skip_read(dae_ctx* ctx, uint64_t out3[3])
     DAE_HIP_CHECK(ctx, hipMemsetAsync(ctx->skip_stat.p, 0, sizeof(h), ctx->stream));
     DAE_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     for (int i = 0; i < 3; ++i) out3[i] = (uint64_t)h[i];
+    return DAE_OK;
+}
+
+int dae_sample_skip_read(dae_ctx* ctx, uint64_t out3[3])
+{
+    if (!ctx) return DAE_ERR_ARG;
+    if (!out3) return dae_fail(ctx, DAE_ERR_ARG, "null pointer");
+    out3[0] = out3[1] = out3[2] = 0;
+    if (!ctx->sskip_stat.p) return DAE_OK;
+    unsigned long long slots[DAE_SSKIP_SLOTS];              // one word per workgroup of the sample launch: summed here
+    DAE_HIP_CHECK(ctx, hipMemcpyAsync(slots, ctx->sskip_stat.p, sizeof(slots), hipMemcpyDeviceToHost, ctx->stream));
+    DAE_HIP_CHECK(ctx, hipMemsetAsync(ctx->sskip_stat.p, 0, sizeof(slots), ctx->stream));
+    DAE_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    unsigned long long h = 0;
+    for (unsigned long long v : slots) h += v;
+    out3[0] = (uint64_t)ctx->sskip_launches; out3[1] = (uint64_t)ctx->sskip_planned; out3[2] = (uint64_t)h;
+    ctx->sskip_launches = ctx->sskip_planned = 0;
+    return DAE_OK;
+}
+
+int dae_last_tau_read(dae_ctx* ctx, float* tau_out, int B)
+{
+    if (!ctx) return DAE_ERR_ARG;
+    if (!tau_out || B < 1) return dae_fail(ctx, DAE_ERR_ARG, "dae_last_tau_read: bad arguments");
+    if (!ctx->tau.p || (size_t)B * sizeof(float) > ctx->tau.bytes) return dae_fail(ctx, DAE_ERR_STATE, "no thresholds of %d rows on this context", B);
+    DAE_HIP_CHECK(ctx, hipMemcpyAsync(tau_out, ctx->tau.p, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    DAE_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return DAE_OK;
 }
 

@@ -44,7 +44,9 @@ struct dae_packed {            // one prepacked decoder image
     // Layout: [ntiles][2] fp32 {A_t, M_t} (the two floats per tile the skip needs), then -- MORE than the per-tile pair -- the
     // columns' own {a_c, m_c}, [ntiles * 32][2]: the tile that holds a call's last ranked column is bounded over its ranked
     // columns alone (its other columns are the first artists, whose biases are the image's largest).  ub_valid: the bounds
-    // belong to the current image (the training step's re-tiling leaves them out: such an image skips nothing)
+    // belong to the current image (the training step's re-tiling leaves them out: such an image skips nothing).
+    // Behind the columns' pairs their LOWER bounds, [ntiles * 32] fp32 lo_c with z32(r, c) >= lo_c - d m_c (-inf: no such column)
+    // -- what the threshold sample's bound table is built from (prepack.hip sample_bound_kernel)
     dae_buf tile_ub; bool ub_valid = false;
     dae_buf bias16;            // bf16 image: [ntiles][64] uint4 bias fragments (prepack.hip)
     // tiles ordered by the largest bias among their rankable columns, descending (the threshold
@@ -157,6 +159,16 @@ struct dae_ctx {
     dae_buf live_sync; void* live_sync_zeroed = nullptr; size_t live_sync_zeroed_bytes = 0;   // (which allocation was zeroed)
     dae_buf cand_list;         // dae_rank_candidates: [B][row_cap] (key, column) pairs | [B] counts (candidates.hip)
     dae_buf skip_stat;         // 3 x uint64 {launches, planned tiles x row groups, live tiles} since the last dae_filter_skip_read
+    // the threshold sample in half row groups skips the tiles a bound puts below tau (decode_generic.hip decode_f32_kernel's HALF):
+    // row_d = [Bpad][4] floats, the rows' max |h - 0.5| by quarters, written by whoever wrote the packed fp32 hidden image
+    // (the encode kernels, pack_h_d_kernel); row_d_fresh: ... for the image as it stands (set by that launch, taken by the next
+    // threshold sample: an image with no published d skips nothing)
+    dae_buf row_d; bool row_d_fresh = false;
+    // the sample's bound table (prepack.hip sample_bound_kernel): 4 floats {mu_max, -, -, -} | [n_samp] {A_t, M_t} | [n_beta] beta
+    // sorted descending; built for one tile order and sample geometry, like tile_band
+    dae_buf samp_tab; long long tab_gen = -1; int tab_nsamp = 0, tab_nbrg = 0, tab_waves = 0;
+    dae_buf sskip_stat;        // DAE_SSKIP_SLOTS x uint64, one per workgroup of the sample launch: wave-tiles it decoded since the last dae_sample_skip_read
+    unsigned long long sskip_launches = 0, sskip_planned = 0;   // ... and the launches / planned wave-tiles (known on the host)
 
     // profiling of the dominant kernel
     bool prof_on = false;
@@ -297,7 +309,7 @@ int dae_launch_encode(dae_ctx* ctx, const int32_t* row_ptr, const int32_t* col, 
                       const float* W_enc, const float* b_enc, int V, int H, int B,
                       float ikp, float kp, uint32_t seed, float* h_out,
                       float* h_packed, int G, int RB, float* sg_out = nullptr,
-                      float* xhat_out = nullptr, unsigned short* h_packed16 = nullptr, int NS = 0);
+                      float* xhat_out = nullptr, unsigned short* h_packed16 = nullptr, int NS = 0, float* d_out = nullptr);
 
 // prepack.hip
 // bounds: also the per-tile logit bounds (dae_packed::tile_ub) -- the scoring images; the training step's re-tiling passes false
@@ -305,7 +317,8 @@ int dae_launch_prepack_f32(dae_ctx* ctx, const float* W, const float* b, int V, 
                            int col_lo, int col_hi, bool bounds = true);
 int dae_launch_prepack_bf16(dae_ctx* ctx, const float* W, const float* b, int V, int H,
                             int col_lo, int col_hi, int exact = 0);
-int dae_launch_pack_h(dae_ctx* ctx, const float* h, int B, int H, const dae_rowgeom& g);
+// d_out (nullable): [g.Bpad][4], the rows' max |h - 0.5| by quarters of the hidden units (dae_ctx::row_d)
+int dae_launch_pack_h(dae_ctx* ctx, const float* h, int B, int H, const dae_rowgeom& g, float* d_out = nullptr);
 // row_bad (nullable): [g.Bpad] int32, 1 where a row of h has an entry outside [0, 1] (the exact mode's precondition)
 int dae_launch_pack_h_bf16(dae_ctx* ctx, const float* h, int B, int H, const dae_rowgeom& g, int* row_bad = nullptr);
 int dae_launch_tile_iota(dae_ctx* ctx, int* dst, int ntiles);      // dst[i] = i
@@ -317,6 +330,11 @@ bool dae_tile_order_sorted(int n_rank_tiles);    // the bias sort (true) or the 
 int dae_launch_tile_band(dae_ctx* ctx, const int* order, int ntiles, int n_samp, int nb_rg, int waves, int* band);
 // the live lists of an fp32 filter launch over `list[0 .. n_items)` (128-row groups, hidden tile packed in ctx->h_packed):
 // live_cnt[rg] tiles of the list, in its order, at live_list[rg * n_items ..), can hold a logit >= min over the group's rows of tau
+// the bound table of a threshold sample of n_items tiles of `list`, decoded by nb_rg workgroups of `waves` waves per half row
+// group (item = wave * nb_rg + workgroup): head[0] = mu_max, ub_out[i] = {A_t, M_t} of item i, beta_out[0 .. n_beta) the largest
+// group lower bounds, descending
+int dae_launch_sample_bounds(dae_ctx* ctx, const dae_packed& pk, const int* list, int n_items, int nb_rg, int waves, int nrank,
+                             float* head, float2* ub_out, float* beta_out, int n_beta);
 int dae_launch_live_tiles(dae_ctx* ctx, const dae_packed& pk, const dae_rowgeom& g, int B, const int* list, int n_items,
                           const float* tau, int nrank, int* live_cnt, int* live_list, unsigned long long* stat);
 
@@ -327,13 +345,24 @@ struct dae_tileset {        // which wave tiles a decode launch walks
     int mode;               // informational: 0 = all tiles (identity list), 3 = ordered list
     const int* list;        // tile of item i; never null
 };
+constexpr int DAE_SSKIP_SLOTS = 2 * DAE_NUM_CU;      // workgroups of a half-row-group sample launch: 2 n_rg nb_rg <= 2 x 256
+// what decode_f32_kernel's HALF skips sample tiles by (ub == nullptr: the full walk) -- DESIGN.md section 2
+struct dae_sample_skip {
+    const float2* ub;                 // [n_items] {A_t, M_t} of the sample's items, in list order
+    const float* beta; int n_beta;    // the group lower bounds, sorted descending
+    const float* mu;                  // -> mu_max
+    const float* row_d;               // [Bpad][4] the rows' max |h - 0.5| by quarters
+    const int32_t* seed_row_ptr; int k;   // need = k + seeds of the row, as tau_select_kernel's
+    unsigned long long* stat;         // [grid of the launch] += wave-tiles decoded, per workgroup (DAE_SSKIP_SLOTS words)
+};
 // dense epilogue: out[row*ld + item*32 + vl] (item = position of the tile in the set)
 // gmax (nullable): [B][ld_gmax] maxima of every lane's two 8-column groups, 4 per (row, item) -- the threshold
 // sample's input to dae_launch_tau_select
 int dae_launch_decode_dense_f32(dae_ctx* ctx, const dae_rowgeom& g, int B, const dae_tileset& ts,
                                 int apply_sigmoid, int mask_from_col, float* out, int64_t ld,
                                 int fill_pad, int dtype = DAE_DTYPE_F32, float* gmax = nullptr,
-                                int64_t ld_gmax = 0, int gmax_per_wave = 0, int bias_sel = 0);
+                                int64_t ld_gmax = 0, int gmax_per_wave = 0, int bias_sel = 0,
+                                const dae_sample_skip* skip = nullptr);      // (taken by the half-row-group sample only)
 // gmax_per_wave: 0 = one maximum per (workgroup, round, position) over the workgroup's waves; 1 = every wave slot's value (small
 // samples); 3 = per-WAVE groups over all of a wave's tiles, 8 wave slots per workgroup (dae_sample_wave_groups: ld_gmax = 8 nb_rg 32);
 // 4 = the same with waves w and w + 4 sharing a group (ld_gmax = 4 nb_rg 32)

@@ -66,6 +66,7 @@ struct dae_decp {          // argument block of the decode kernels on the prepac
     const float* tau; int n_valid_col; uint2* cand; int* cand_cnt; int cap;
     // decode_f32_h256_filter_kernel (nullable): row group rg walks live_cnt[rg] tiles at live_list[rg * ts.n_items ..), not ts.list
     const int* live_cnt; const int* live_list;
+    dae_sample_skip sk;            // decode_f32_kernel's HALF (the threshold sample in half row groups): tiles skipped by their bound
     // title mix (models/DAEs.py:180 of the reference: y = title_score * w_title + dae_score * w_playlist):
     //   DAE side, EPI_DENSE: outT[column * ld_outT + row] = sigmoid(z) * row_scale[row] -- the second term, transposed
     //   title side, EPI_GMAX / EPI_FILTER: every value becomes sigmoid(z) * mix_w[row] + mixT[column * mix_ld + row]

@@ -1039,7 +1039,8 @@ int fill_common(dae_ctx* ctx, const dae_rowgeom& g, int B, const dae_tileset& ts
 // (which kernel a geometry takes: the predicates of score_plan.h, shared with the plan of a scoring call)
 int dae_launch_decode_dense_f32(dae_ctx* ctx, const dae_rowgeom& g, int B, const dae_tileset& ts,
                                 int apply_sigmoid, int mask_from_col, float* out, int64_t ld,
-                                int fill_pad, int dtype, float* gmax, int64_t ld_gmax, int gmax_per_wave, int bias_sel)
+                                int fill_pad, int dtype, float* gmax, int64_t ld_gmax, int gmax_per_wave, int bias_sel,
+                                const dae_sample_skip* skip)
 {
     dae_decp p;
     int rc = fill_common(ctx, g, B, ts, p, dtype, bias_sel);
@@ -1063,9 +1064,10 @@ int dae_launch_decode_dense_f32(dae_ctx* ctx, const dae_rowgeom& g, int B, const
     }
     if (gmax) {
         if (g.waves != 4) return dae_fail(ctx, DAE_ERR_ARG, "group maxima need 4-wave workgroups");
-        if (dtype == DAE_DTYPE_F32 && g.R_TILE == 128 && p.G == 32 && !gmax_per_wave && !p.mixT &&
-            ts.n_items <= g.nb_rg * 4)
+        if (dae_sample_takes_half(g, dtype, p.G * DAE_KG, p.mixT != nullptr, gmax_per_wave, ts.n_items)) {
+            if (skip) p.sk = *skip;                            // (tiles a bound puts below tau: the kernel's prologue)
             return dae_launch_decode_gmax_half(ctx, g, p);     // one round of tiles (the threshold sample at batch <= 256)
+        }
         return dae_launch_decode_generic(ctx, EPI_GMAX, dt, g, p);
     }
     return dae_launch_decode_generic(ctx, EPI_DENSE, dt, g, p);

@@ -46,8 +46,96 @@ __global__ __launch_bounds__(NW * 64, HALF ? 2 : NW / 4) void decode_f32_kernel(
     // in front of the first MFMA).
     const int tv_cur = tile_of_item(p.ts, has0 ? item0 : 0);
     const int tv_nxt = tile_of_item(p.ts, has0 ? (item0 + n_ws < p.ts.n_items ? item0 + n_ws : item0) : 0);
-    // ---- hidden tile of this row group -> LDS, once ------------------------------------------
     const int n_h4 = RB * 64 * G;
+    // ---- HALF: tiles a bound puts below every threshold of the half group are not decoded ---------------
+    // Before the sample runs, the image's bounds give a lower bound of every row's threshold: each group maximum is >= lo_c -
+    // d m_c for each of its members, so the need-th largest maximum of a row is >= x = beta_(need) - d mu_max (beta: the groups'
+    // max lo_c, sorted descending; d over the half group's real rows; need = k + the most seeds a row of it has), and the
+    // threshold, which tau_select_kernel cuts to 16 key bits, is >= tau_safe = the same cut of x.  A tile with A_t + d M_t <
+    // tau_safe holds no element that reaches any row's threshold: its maxima are not counted at the prefix the search returns and
+    // none of its logits passes the threshold launch's >= tau -- so the wave stores -inf for it and decodes nothing.  Roundings go
+    // the safe way (d rounded up by its producer, x down, U up as in dae_tile_is_live, whose !(U < tau) keeps a tile on any NaN).
+    // Every wave takes the half group's d and need itself (64 lanes = its 64 rows; one trip to memory with the window of beta
+    // that starts at k - 1 and the wave's own {A_t, M_t}): no LDS and no barrier before the workgroup's vote.
+    bool skip_w = false;                                         // wave-uniform: this wave's tile is skipped
+    if constexpr (HALF) {
+        static_assert(RB == 2 && EPI == EPI_GMAX, "half row groups: the threshold sample, 64 rows");
+        if (p.sk.ub) {
+            int* const sk_live = reinterpret_cast<int*>(lds4 + n_h4);   // (the R_TILE ints behind the hidden tile: the filter epilogue's)
+            const int row = rg * R_TILE + lane;
+            const bool real = row < p.B;
+            const float4 d4 = real ? reinterpret_cast<const float4*>(p.sk.row_d)[row] : make_float4(0.f, 0.f, 0.f, 0.f);
+            int ns = (real && p.sk.seed_row_ptr) ? p.sk.seed_row_ptr[row + 1] - p.sk.seed_row_ptr[row] : 0;
+            const int kb = p.sk.k - 1;
+            float bw[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int idx = kb + lane + 64 * u;
+                bw[u] = idx < p.sk.n_beta ? p.sk.beta[idx] : -__builtin_inff();
+            }
+            const float mu = *p.sk.mu;
+            const float2 ub = p.sk.ub[has0 ? item0 : 0];
+            // (the workgroup's own counter word, asked for with the rest: launches of a context run one after the other)
+            const unsigned long long cnt_was = tid == 0 ? p.sk.stat[blockIdx.x] : 0ull;
+            float dq = dae_max_nan(dae_max_nan(d4.x, d4.y), dae_max_nan(d4.z, d4.w));
+            ns = ns < 0 ? 0 : ns;
+#pragma unroll
+            for (int sh = 1; sh < 64; sh <<= 1) {
+                dq = dae_max_nan(dq, __shfl_xor(dq, sh));
+                const int o = __shfl_xor(ns, sh);
+                ns = o > ns ? o : ns;
+            }
+            ns = __builtin_amdgcn_readfirstlane(ns);
+            float beta_k;
+            if (ns < 256) {
+                const float sel = ns < 64 ? bw[0] : ns < 128 ? bw[1] : ns < 192 ? bw[2] : bw[3];
+                beta_k = __shfl(sel, ns & 63);
+            } else {                                             // (more seeds than the window: one more trip)
+                beta_k = kb + ns < p.sk.n_beta ? p.sk.beta[kb + ns] : -__builtin_inff();
+            }
+            const double pm = (double)dq * (double)mu;           // exact: two floats
+            double xd = (double)beta_k - pm;
+            xd -= (fabs((double)beta_k) + fabs(pm)) * 0x1p-48;   // (more than the one rounding above)
+            float xf = (float)xd;
+            if ((double)xf > xd) xf = nextafterf(xf, -__builtin_inff());
+            const float tau_safe = dae_tau_value(dae_okey(xf) >> 16, 1);      // tau_search.h: the cut tau itself gets
+            // (a half group of pad rows alone stores nothing: nothing of it is decoded or counted)
+            skip_w = has0 && (rg * R_TILE >= p.B || !dae_tile_is_live(ub.x, ub.y, (double)dq, tau_safe));
+            skip_w = __builtin_amdgcn_readfirstlane((int)skip_w) != 0;
+            if (lane == 0) sk_live[wave] = (has0 && !skip_w) ? 1 : 0;
+            __syncthreads();
+            int n_live = 0;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) n_live += sk_live[w];
+            if (n_live == 0) {
+                // nothing to decode in this workgroup: -inf into its maxima and its dense sample slots (what the exchange
+                // stores when no wave holds a tile: gmax_round below), and it ends before the hidden tile is copied
+                const float4 ninf = make_float4(-__builtin_inff(), -__builtin_inff(), -__builtin_inff(), -__builtin_inff());
+                for (int sl = tid; sl < 256 * RB; sl += NW * 64) {
+                    const int rb = sl >> 8, s2 = sl & 255;
+                    const int r2 = rg * R_TILE + rb * 32 + (s2 & 31);
+                    if (r2 < p.B)
+                        *reinterpret_cast<float4*>(p.gmax + (size_t)r2 * p.ld_gmax + (size_t)bir * 32 + (s2 >> 5) * 4) = ninf;
+                }
+                for (int t2 = tid; t2 < NW * 64 * RB && p.out; t2 += NW * 64) {
+                    const int rb = t2 / (NW * 64), t3 = t2 % (NW * 64);
+                    const int w = t3 >> 6, jj = (t3 & 63) >> 1, half = t3 & 1;
+                    const int item_w = w * p.nb_rg + bir;
+                    const int r2 = rg * R_TILE + rb * 32 + jj;
+                    if (item_w < p.ts.n_items && r2 < p.B) {
+                        float* orow = p.out + (size_t)r2 * p.ld + (size_t)item_w * 32 + half * 16;
+#pragma unroll
+                        for (int q4 = 0; q4 < 4; ++q4) *reinterpret_cast<float4*>(orow + 4 * q4) = ninf;
+                    }
+                }
+                return;
+            }
+            // wave-tiles decoded, into the workgroup's OWN word: a plain store (512 atomics on one address, one per live workgroup
+            // of a model that skips nothing, are a queue the launch cannot end before)
+            if (tid == 0) p.sk.stat[blockIdx.x] = cnt_was + (unsigned long long)n_live;
+        }
+    }
+    // ---- hidden tile of this row group -> LDS, once ------------------------------------------
     {
         // 8 independent 16 B loads in flight per thread (a load->wait->ds_write chain per element
         // costs one L2 round trip each: ~25k cycles for the 128 KiB tile, measured with SQ_WAIT_ANY)
@@ -196,7 +284,8 @@ __global__ __launch_bounds__(NW * 64, HALF ? 2 : NW / 4) void decode_f32_kernel(
         }
     };
 
-    for (int item = item0; item < p.ts.n_items; item += n_ws) {
+    // (a wave whose tile is skipped walks nothing and joins the exchange below with -inf, as a wave without a tile does)
+    for (int item = skip_w ? p.ts.n_items : item0; item < p.ts.n_items; item += n_ws) {
         const int t = t_cur;
         const float4* wp = p.Wp + (size_t)t * G * 64 + lane;
         // next tile of this wave (or this one again at the end: in-bounds, values unused)
@@ -472,7 +561,7 @@ __global__ __launch_bounds__(NW * 64, HALF ? 2 : NW / 4) void decode_f32_kernel(
     if (EPI == EPI_GMAX) {
         // rounds this wave had no tile for: still joins the exchange (block-uniform trip count in total)
         const int rounds = (p.ts.n_items + n_ws - 1) / n_ws;
-        const int mine = item0 < p.ts.n_items ? (p.ts.n_items - item0 + n_ws - 1) / n_ws : 0;
+        const int mine = (item0 < p.ts.n_items && !skip_w) ? (p.ts.n_items - item0 + n_ws - 1) / n_ws : 0;
         f32x16 dummy_acc[RB];
         float4 dummy_b[4];
 #pragma unroll

@@ -13,7 +13,7 @@
 //
 // Optionally the hidden row is also written in the MFMA B-operand order of prepack.hip's pack_h kernels
 // (the fused dae_score_topk path), which removes the separate re-pack pass.
-#include "dae_internal.h"
+#include "decode_common.h"      // dae_max_nan
 
 namespace {
 
@@ -56,7 +56,20 @@ struct EncP {
     float* sg_out;       // [B,H] sigmoid BEFORE hidden dropout (training backward) or null
     float* xhat_out;     // [nnz] normalised, dropped-out input weights (training backward) or null
     unsigned w_bytes;    // V * H * 4 (< 4 GiB: buffer descriptor range)
+    // [rows][4] or null: max |h - 0.5| over the row's units, by quarters -- what the threshold sample skips tiles by
+    // (decode_generic.hip; each wave reduces over its OWN units and stores: no atomics, nothing to zero)
+    float* d_out;
 };
+
+// max over the wave's lanes of d (a NaN if any lane holds one), rounded UP to float
+__device__ __forceinline__ float enc_wave_d(double d)
+{
+#pragma unroll
+    for (int sh = 1; sh < 64; sh <<= 1) d = dae_max_nan(d, __shfl_xor(d, sh));
+    float df = (float)d;
+    if ((double)df < d) df = nextafterf(df, __builtin_inff());
+    return df;
+}
 
 // issue the loads of one group of 16 non-zeros (indices base..base+15 of the current 64-chunk);
 // indices past n re-read the chunk's last row (cache hit) and get weight 0: fmaf(0, w, acc) == acc.
@@ -105,6 +118,7 @@ __global__ __launch_bounds__(NW * 64) void encode_kernel(const EncP p)
         const float denom = s + 1e-10f;
 
         // ---- pass 2: gather, one hidden pass of 256 units at a time ---------------------------
+        double d_row = 0.0;
         for (int hbase = 0; hbase < H; hbase += 256) {
             const int hoff = hbase + lane * 4;
             const bool active = hoff < H;
@@ -158,6 +172,10 @@ __global__ __launch_bounds__(NW * 64) void encode_kernel(const EncP p)
                 if (p.h_out)
                     *reinterpret_cast<float4*>(p.h_out + (size_t)row * H + hoff) =
                         make_float4(hv[0], hv[1], hv[2], hv[3]);
+                if (p.d_out) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) d_row = dae_max_nan(d_row, fabs((double)hv[e] - 0.5));
+                }
                 if (p.hp) {
                     // k = hoff + e  ->  group g = k >> 3, slot (e2 = (k & 7) >> 1, hi = k & 1)
                     const int R_TILE = p.RB * 32;
@@ -182,6 +200,10 @@ __global__ __launch_bounds__(NW * 64) void encode_kernel(const EncP p)
                                                               dae_bf16_rne(hv[2]) | (dae_bf16_rne(hv[3]) << 16));
                 }
             }
+        }
+        if (p.d_out) {                                       // (one wave owns the whole row: the same value in all four quarters)
+            const float df = enc_wave_d(d_row);
+            if (lane < 4) p.d_out[(size_t)row * 4 + lane] = df;
         }
     }
 }
@@ -264,6 +286,7 @@ __global__ __launch_bounds__(64 * WGW) void encode_split_kernel(const EncP p)
                     acc = fmaf(rl_f(WL, (OFF) + u), X[u], acc);                                \
             }
 
+    double d_q = 0.0;                            // max |h - 0.5| over this wave's units
     for (int hb = 0; hb < hq; hb += 64) {
         const int hu = q * hq + hb + lane;       // this lane's hidden unit
         const bool active = hb + lane < hq;
@@ -329,6 +352,7 @@ __global__ __launch_bounds__(64 * WGW) void encode_split_kernel(const EncP p)
                 hv = (hv / p.kp) * floorf(p.kp + u);
             }
             if (p.h_out) p.h_out[(size_t)row * H + hu] = hv;
+            if (p.d_out) d_q = dae_max_nan(d_q, fabs((double)hv - 0.5));
             if (p.hp) {
                 const int R_TILE = p.RB * 32;
                 const int rg = row / R_TILE, rl = row - rg * R_TILE;
@@ -346,6 +370,11 @@ __global__ __launch_bounds__(64 * WGW) void encode_split_kernel(const EncP p)
             }
         }
     }
+    if (p.d_out) {
+        static_assert(HS == 4, "dae_ctx::row_d holds four quarters per row");
+        const float df = enc_wave_d(d_q);
+        if (lane == 0) p.d_out[(size_t)row * 4 + q] = df;
+    }
 #undef ENC_ISSUE
 #undef ENC_CHAIN
 }
@@ -355,7 +384,8 @@ __global__ __launch_bounds__(64 * WGW) void encode_split_kernel(const EncP p)
 int dae_launch_encode(dae_ctx* ctx, const int32_t* row_ptr, const int32_t* col, const float* val,
                       const float* W_enc, const float* b_enc, int V, int H, int B,
                       float ikp, float kp, uint32_t seed, float* h_out,
-                      float* h_packed, int G, int RB, float* sg_out, float* xhat_out, unsigned short* h_packed16, int NS)
+                      float* h_packed, int G, int RB, float* sg_out, float* xhat_out, unsigned short* h_packed16, int NS,
+                      float* d_out)
 {
     if (B <= 0) return DAE_OK;
     EncP p;
@@ -363,7 +393,7 @@ int dae_launch_encode(dae_ctx* ctx, const int32_t* row_ptr, const int32_t* col, 
     p.row_ptr = row_ptr; p.col = col; p.val = val; p.W = W_enc; p.b_enc = b_enc;
     p.H = H; p.B = B; p.ikp = ikp; p.kp = kp; p.seed = seed;
     p.h_out = h_out; p.hp = h_packed; p.G = G; p.RB = RB;
-    p.sg_out = sg_out; p.xhat_out = xhat_out;
+    p.sg_out = sg_out; p.xhat_out = xhat_out; p.d_out = d_out;
     if ((size_t)V * H * 4 >= 0xFFFFFFFFull)
         return dae_fail(ctx, DAE_ERR_ARG, "W_enc of %d x %d exceeds the 4 GiB buffer range", V, H);
     p.w_bytes = (unsigned)((size_t)V * H * 4);

@@ -94,7 +94,11 @@ __global__ __launch_bounds__(256) void prepack_tile_kernel(const float* __restri
             for (int k = part; k < H; k += 8) { const double w = (double)wrow[k]; sw += w; nw += fabs(w); }
 #pragma unroll
             for (int sh = 1; sh < 8; sh <<= 1) { sw += __shfl_xor(sw, sh); nw += __shfl_xor(nw, sh); }
-            float a_f = -__builtin_inff(), m_f = 0.0f;                   // a column past the image bounds nothing
+            // The LOWER bound of the same chain (what the threshold sample skips tiles by: sample_bound_kernel below, DESIGN.md
+            // section 2): z >= b + 0.5 s - d n and |z32 - z| <= rho (0.5 + d) n + rho |b| + (H + 2) 2^-125 give
+            //     z32(r, c) >= lo_c - d m_c,     lo_c = b + 0.5 s - rho (0.5 n + |b|) - (H + 2) 2^-125,
+            // with the SAME m_c; the double sums' own error comes off as 2^-40 (n + |b|), and lo_c is rounded DOWN to float.
+            float a_f = -__builtin_inff(), m_f = 0.0f, lo_f = -__builtin_inff();      // a column past the image bounds nothing
             if (v0 + c < col_hi) {
                 const double bv = (double)b[v0 + c], ab = fabs(bv);
                 const double rho = (double)(H + 2) * 0x1p-24 * (1.0 + 0x1p-10);
@@ -102,10 +106,15 @@ __global__ __launch_bounds__(256) void prepack_tile_kernel(const float* __restri
                 const double m = (1.0 + rho) * nw * (1.0 + 0x1p-40);
                 a_f = (float)a; if ((double)a_f < a) a_f = nextafterf(a_f, __builtin_inff());
                 m_f = (float)m; if ((double)m_f < m) m_f = nextafterf(m_f, __builtin_inff());
+                const double lo = bv + 0.5 * sw - rho * (0.5 * nw + ab) - (double)(H + 2) * 0x1p-125 - 0x1p-40 * (nw + ab);
+                lo_f = (float)lo; if ((double)lo_f > lo) lo_f = nextafterf(lo_f, -__builtin_inff());
             }
             // (the columns' own pairs behind the tiles': the tile that holds the LAST ranked column of a call is bounded over its
             // ranked columns alone -- live_tiles_kernel -- since its other columns, the first artists, carry the largest biases)
-            if (part == 0) { tile_ub[2 * (ntiles + t * 32 + c)] = a_f; tile_ub[2 * (ntiles + t * 32 + c) + 1] = m_f; }
+            if (part == 0) {
+                tile_ub[2 * (ntiles + t * 32 + c)] = a_f; tile_ub[2 * (ntiles + t * 32 + c) + 1] = m_f;
+                tile_ub[(size_t)66 * ntiles + t * 32 + c] = lo_f;
+            }
 #pragma unroll
             for (int sh = 8; sh < 64; sh <<= 1) {
                 a_f = dae_max_nan(a_f, __shfl_xor(a_f, sh));
@@ -336,6 +345,87 @@ __global__ __launch_bounds__(1024) void tile_order_kernel(const float* __restric
         order[i] = (int)(0xFFFFFFFFu - (unsigned)(keys[i] & 0xFFFFFFFFULL));
 }
 
+// ---- the bound table of the threshold sample (score.hip topk_phase_a; decode_generic.hip decode_f32_kernel's HALF) ------------
+// Built once per (tile order, sample geometry).  The sample launch in half row groups decodes item w * nb_rg + bir in wave w of
+// workgroup bir and takes, per position c of the tile, the maximum over the workgroup's waves: group (bir, c).
+//   ub_out[i]   = {A_t, M_t} of item i's tile, in list order (the edge tile bounded over its ranked columns);
+//   beta_out[j] = the j-th largest of beta_g = max lo_c over the RANKED columns of group g (-inf: a group without one), for the
+//                 leading n_beta of the nb_rg * 32 groups;
+//   head[0]     = mu_max = max M_t over the items -- a NaN if any lo_c or M_t is one, which keeps every tile (the bound says
+//                 nothing about an image that holds a NaN).
+// One workgroup; the sort is tile_order_kernel's network on 32-bit keys.
+constexpr int BOUND_MAX_GROUPS = 8192;              // nb_rg <= DAE_NUM_CU workgroups x 32 positions
+__global__ __launch_bounds__(1024) void sample_bound_kernel(const int* __restrict__ list, int n_items, int nb_rg, int waves,
+                                                            const float* __restrict__ tile_ub, int ntiles, int nrank,
+                                                            float* __restrict__ head, float2* __restrict__ ub_out,
+                                                            float* __restrict__ beta_out, int n_beta)
+{
+    __shared__ unsigned keys[BOUND_MAX_GROUPS];
+    __shared__ float sh_edge[2], sh_mu[16];
+    __shared__ int sh_nan;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* const lo = tile_ub + (size_t)66 * ntiles;
+    const int t_edge = (nrank & 31) ? (nrank >> 5) : -1;
+    if (tid == 0) sh_nan = 0;
+    if (wave == 0 && t_edge >= 0) {
+        float ea, em;
+        dae_edge_tile_bound(tile_ub, ntiles, nrank, lane, ea, em);
+        if (lane == 0) { sh_edge[0] = ea; sh_edge[1] = em; }
+    }
+    __syncthreads();
+    float mu = 0.0f;
+    for (int i = tid; i < n_items; i += 1024) {
+        const int t = list[i];
+        const float2 ub = t == t_edge ? make_float2(sh_edge[0], sh_edge[1]) : make_float2(tile_ub[2 * t], tile_ub[2 * t + 1]);
+        ub_out[i] = ub;
+        mu = dae_max_nan(mu, ub.y);
+    }
+    const int n_groups = nb_rg * 32;
+    int n2 = 1024;
+    while (n2 < n_groups) n2 <<= 1;
+    bool nan = false;
+    for (int gi = tid; gi < n2; gi += 1024) {
+        unsigned key = 0u;                                  // padding sorts last (below the key of -inf)
+        if (gi < n_groups) {
+            const int bir = gi >> 5, c = gi & 31;
+            float b = -__builtin_inff();
+            for (int w = 0; w < waves; ++w) {
+                const int item = w * nb_rg + bir;
+                if (item >= n_items) continue;
+                const int col = list[item] * 32 + c;
+                if (col < nrank) b = dae_max_nan(b, lo[col]);
+            }
+            nan = nan || b != b;
+            key = b != b ? 0xFFFFFFFFu : dae_okey(b);
+        }
+        keys[gi] = key;
+    }
+#pragma unroll
+    for (int sh = 1; sh < 64; sh <<= 1) mu = dae_max_nan(mu, __shfl_xor(mu, sh));
+    if (lane == 0) sh_mu[wave] = mu;
+    if (nan) sh_nan = 1;
+    __syncthreads();
+    for (int size = 2; size <= n2; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int i = tid; i < n2; i += 1024) {
+                const int jx = i ^ stride;
+                if (jx > i) {
+                    const unsigned a = keys[i], b = keys[jx];
+                    const bool desc = (i & size) == 0;
+                    if (desc ? (a < b) : (a > b)) { keys[i] = b; keys[jx] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (int i = tid; i < n_beta; i += 1024) beta_out[i] = dae_okey_inv(keys[i]);
+    if (tid == 0) {
+        float m = sh_mu[0];
+        for (int w = 1; w < 16; ++w) m = dae_max_nan(m, sh_mu[w]);
+        head[0] = sh_nan ? __builtin_nanf("") : m;
+    }
+}
+
 __global__ __launch_bounds__(256) void tile_iota_kernel(int n, int* __restrict__ out)
 {
     for (int t = blockIdx.x * 256 + threadIdx.x; t < n; t += gridDim.x * 256) out[t] = t;
@@ -400,6 +490,44 @@ __global__ __launch_bounds__(256) void pack_h_kernel(const float* __restrict__ h
             e[c] = (r < B && k < H) ? h[(size_t)r * H + k] : 0.0f;
         }
         hp[o] = make_float4(e[0], e[1], e[2], e[3]);
+    }
+}
+
+// The same image for a ranking call (score.hip pack_hidden), which also wants the rows' d: one workgroup per (row group, row
+// block, quarter of the k groups); wave w takes the quarter's groups w, w + 4, ...
+// d_out: [Bpad][4] floats, d_out[r * 4 + q] = max |h[r][k] - 0.5| over the quarter's units k < H of the real row r, in double,
+// rounded UP, a NaN if an entry is one (what the threshold sample's skip takes the row's d from, as from the encode kernels:
+// decode_generic.hip).  The zero padding takes no part: it would read 0.5.
+__global__ __launch_bounds__(256) void pack_h_d_kernel(const float* __restrict__ h, int B, int H,
+                                                       int G, int RB, int n_rg,
+                                                       float4* __restrict__ hp, float* __restrict__ d_out)
+{
+    __shared__ double sh_d[4][32];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int q = blockIdx.x & 3, rb = (blockIdx.x >> 2) % RB, rg = (blockIdx.x >> 2) / RB;
+    const int hi = lane >> 5, jj = lane & 31;
+    const int r = (rg * RB + rb) * 32 + jj;
+    const int Gq = G >> 2;                                   // (Hp is a multiple of DAE_HPAD = 32: G of 4)
+    double d = 0.0;
+    for (int g = q * Gq + wave; g < (q + 1) * Gq; g += 4) {
+        float e[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int k = 8 * g + 2 * c + hi;
+            const bool in = r < B && k < H;
+            e[c] = in ? h[(size_t)r * H + k] : 0.0f;
+            if (in) d = dae_max_nan(d, fabs((double)e[c] - 0.5));
+        }
+        hp[(((size_t)rg * G + g) * RB + rb) * 64 + lane] = make_float4(e[0], e[1], e[2], e[3]);
+    }
+    d = dae_max_nan(d, __shfl_xor(d, 32));
+    if (hi == 0) sh_d[wave][jj] = d;
+    __syncthreads();
+    if (threadIdx.x < 32 && r < B) {
+        d = dae_max_nan(dae_max_nan(sh_d[0][jj], sh_d[1][jj]), dae_max_nan(sh_d[2][jj], sh_d[3][jj]));
+        float df = (float)d;
+        if ((double)df < d) df = nextafterf(df, __builtin_inff());
+        d_out[(size_t)r * 4 + q] = df;
     }
 }
 
@@ -532,7 +660,7 @@ int dae_launch_prepack_f32(dae_ctx* ctx, const float* W, const float* b, int V, 
     rc = dae_reserve(ctx, pk.bias, (size_t)ntiles * 32 * sizeof(float));
     if (rc) return rc;
     if (bounds) {
-        rc = dae_reserve(ctx, pk.tile_ub, (size_t)(ntiles > 0 ? ntiles : 1) * 33 * 2 * sizeof(float));      // [ntiles][2] | [ntiles * 32][2]
+        rc = dae_reserve(ctx, pk.tile_ub, (size_t)(ntiles > 0 ? ntiles : 1) * (33 * 2 + 32) * sizeof(float));      // [ntiles][2] | [ntiles * 32][2] | [ntiles * 32]
         if (rc) return rc;
     }
     rc = launch_prepack_tiles<DT_F32>(ctx, W, b, H, Hp, col_lo, col_hi, ntiles, pk.W.p,
@@ -604,17 +732,33 @@ int dae_launch_live_tiles(dae_ctx* ctx, const dae_packed& pk, const dae_rowgeom&
     return DAE_OK;
 }
 
-int dae_launch_pack_h(dae_ctx* ctx, const float* h, int B, int H, const dae_rowgeom& g)
+int dae_launch_pack_h(dae_ctx* ctx, const float* h, int B, int H, const dae_rowgeom& g, float* d_out)
 {
     const int Hp = dae_round_up(H, DAE_HPAD);
     const int G = Hp / DAE_KG, RB = g.R_TILE / 32;
     const size_t total = (size_t)g.n_rg * G * RB * 64;
     int rc = dae_reserve(ctx, ctx->h_packed, total * sizeof(float4));
     if (rc) return rc;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(pack_h_kernel, dim3(blocks), dim3(256), 0, ctx->stream, h, B, H, G, RB,
-                       g.n_rg, static_cast<float4*>(ctx->h_packed.p));
-    DAE_CHECK_LAUNCH(ctx, "pack_h_kernel");
+    if (d_out) {
+        hipLaunchKernelGGL(pack_h_d_kernel, dim3(g.n_rg * RB * 4), dim3(256), 0, ctx->stream, h, B, H, G, RB,
+                           g.n_rg, static_cast<float4*>(ctx->h_packed.p), d_out);
+    } else {
+        int blocks = (int)((total + 255) / 256);
+        if (blocks > 2048) blocks = 2048;
+        hipLaunchKernelGGL(pack_h_kernel, dim3(blocks), dim3(256), 0, ctx->stream, h, B, H, G, RB,
+                           g.n_rg, static_cast<float4*>(ctx->h_packed.p));
+    }
+    DAE_CHECK_LAUNCH(ctx, d_out ? "pack_h_d_kernel" : "pack_h_kernel");
+    return DAE_OK;
+}
+
+int dae_launch_sample_bounds(dae_ctx* ctx, const dae_packed& pk, const int* list, int n_items, int nb_rg, int waves, int nrank,
+                             float* head, float2* ub_out, float* beta_out, int n_beta)
+{
+    if (!pk.ub_valid || !pk.tile_ub.p || n_items <= 0 || nb_rg * 32 > BOUND_MAX_GROUPS || n_beta > nb_rg * 32)
+        return dae_fail(ctx, DAE_ERR_STATE, "sample bound table: fp32 image with bounds, at most %d groups", BOUND_MAX_GROUPS);
+    hipLaunchKernelGGL(sample_bound_kernel, dim3(1), dim3(1024), 0, ctx->stream, list, n_items, nb_rg, waves,
+                       static_cast<const float*>(pk.tile_ub.p), pk.ntiles, nrank, head, ub_out, beta_out, n_beta);
+    DAE_CHECK_LAUNCH(ctx, "sample_bound_kernel");
     return DAE_OK;
 }

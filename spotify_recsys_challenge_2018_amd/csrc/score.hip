@@ -43,7 +43,15 @@ int hidden_pads_zeroed(dae_ctx* ctx, long long& key, void*& ptr, const dae_buf& 
     return DAE_OK;
 }
 
-int pack_hidden(dae_ctx* ctx, int dtype, const float* h, int B, int H, const dae_rowgeom& g)
+// the rows' max |h - 0.5| by quarters, published by whoever writes the packed fp32 hidden image (dae_ctx::row_d)
+int reserve_row_d(dae_ctx* ctx, const dae_rowgeom& g)
+{
+    ctx->row_d_fresh = false;
+    return dae_reserve(ctx, ctx->row_d, (size_t)g.Bpad * 4 * sizeof(float));
+}
+
+// want_d: the call ranks (dae_decode_topk) -- the packing launch also publishes the rows' d for the threshold sample's skip
+int pack_hidden(dae_ctx* ctx, int dtype, const float* h, int B, int H, const dae_rowgeom& g, bool want_d = false)
 {
     if (dtype == DAE_DTYPE_BF16_EXACT) {
         // the bound behind the exact mode holds for hidden rows in [0, 1]: the packing pass flags the others
@@ -52,8 +60,12 @@ int pack_hidden(dae_ctx* ctx, int dtype, const float* h, int B, int H, const dae
         return dae_launch_pack_h_bf16(ctx, h, B, H, g, static_cast<int*>(ctx->row_bad.p));
     }
     if (dtype == DAE_DTYPE_F32) {
-        int rc = dae_launch_pack_h(ctx, h, B, H, g);          // rewrites the whole image incl. zero pads
+        int rc = want_d ? reserve_row_d(ctx, g) : DAE_OK;
         if (rc) return rc;
+        ctx->row_d_fresh = false;
+        rc = dae_launch_pack_h(ctx, h, B, H, g, want_d ? static_cast<float*>(ctx->row_d.p) : nullptr);   // rewrites the whole image incl. zero pads
+        if (rc) return rc;
+        ctx->row_d_fresh = want_d;
         return hidden_pads_zeroed(ctx, ctx->h_geom_key, ctx->h_geom_ptr, ctx->h_packed, 0, B, H, g.R_TILE);
     }
     return dae_launch_pack_h_bf16(ctx, h, B, H, g);
@@ -216,10 +228,43 @@ static int topk_phase_a(dae_ctx* ctx, const dae_packed* pk, const dae_rowgeom& g
         if (rc) return rc;
         gmax = static_cast<float*>(ctx->gmax.p);
     }
+    // SKIPPED SAMPLE TILES (dae_score_plan::sample_skip, under dae_set_filter_skip): the sample in half row groups knows, before it
+    // decodes anything, a lower bound of every row's threshold (from the columns' lower bounds lo_c) and skips the tiles whose upper
+    // bound stays below it.  The bound table belongs to the tile order and the launch geometry, like the band list; the rows' d comes
+    // from the launch that wrote the packed hidden image (none published for this image: the full walk).
+    dae_sample_skip sk{};
+    const bool d_fresh = ctx->row_d_fresh;
+    ctx->row_d_fresh = false;                              // (taken: the next sample needs its own image's)
+    if (pl.sample_skip && ctx->filter_skip) {
+        const int n_beta = g.nb_rg * 32 < 4096 ? g.nb_rg * 32 : 4096;
+        const void* tab_was = ctx->samp_tab.p;
+        rc = dae_reserve(ctx, ctx->samp_tab, (4 + (size_t)2 * pl.n_samp + n_beta) * sizeof(float));
+        if (rc) return rc;
+        if (ctx->samp_tab.p != tab_was) ctx->tab_gen = -1;
+        if (!ctx->sskip_stat.p) {
+            rc = dae_reserve(ctx, ctx->sskip_stat, DAE_SSKIP_SLOTS * sizeof(unsigned long long));
+            if (rc) return rc;
+            DAE_HIP_CHECK(ctx, hipMemsetAsync(ctx->sskip_stat.p, 0, DAE_SSKIP_SLOTS * sizeof(unsigned long long), ctx->stream));
+        }
+        float* head = static_cast<float*>(ctx->samp_tab.p);
+        float2* ub = reinterpret_cast<float2*>(head + 4);
+        float* beta = head + 4 + (size_t)2 * pl.n_samp;
+        if (ctx->tab_gen != pk->order_gen || ctx->tab_nsamp != pl.n_samp || ctx->tab_nbrg != g.nb_rg || ctx->tab_waves != g.waves) {
+            rc = dae_launch_sample_bounds(ctx, *pk, order, pl.n_samp, g.nb_rg, g.waves, pl.nrank, head, ub, beta, n_beta);
+            if (rc) return rc;
+            ctx->tab_gen = pk->order_gen; ctx->tab_nsamp = pl.n_samp; ctx->tab_nbrg = g.nb_rg; ctx->tab_waves = g.waves;
+        }
+        if (d_fresh && 2 * g.grid <= DAE_SSKIP_SLOTS && ctx->row_d.p && ctx->row_d.bytes >= (size_t)g.Bpad * 4 * sizeof(float)) {
+            sk = dae_sample_skip{ub, beta, n_beta, head, static_cast<const float*>(ctx->row_d.p), seed_row_ptr, k,
+                                 static_cast<unsigned long long*>(ctx->sskip_stat.p)};
+            ctx->sskip_launches += 1;
+            ctx->sskip_planned += (unsigned long long)((B + 63) / 64) * (unsigned long long)pl.n_samp;   // half groups with a real row
+        }
+    }
     if (!pl.fused) { rc = prof_begin(ctx); if (rc) return rc; }
     // (gA != g only with per-wave groups: the generic kernels run on the filter launch's geometry)
     rc = dae_launch_decode_dense_f32(ctx, pl.wave_groups ? pl.gA : g, B, tsA, 0, pl.n_valid_col, pl.whole_b ? nullptr : sample, pl.ld_s,
-                                     1, pl.dtype, gmax, pl.ld_g, pl.gmax_per_wave, pl.exact ? 1 : 0);
+                                     1, pl.dtype, gmax, pl.ld_g, pl.gmax_per_wave, pl.exact ? 1 : 0, sk.ub ? &sk : nullptr);
     if (rc) return rc;
     if (!pl.fused) {                                       // phase B ranks the dense rows; no threshold exists
         ctx->prof_armed = false;
@@ -477,9 +522,12 @@ static int score_encode(dae_ctx* ctx, const int32_t* row_ptr, const int32_t* col
     if (rc) return rc;
     rc = hidden_pads_zeroed(ctx, ctx->h_geom_key, ctx->h_geom_ptr, ctx->h_packed, bytes, B, H, g.R_TILE);
     if (rc) return rc;
-    rc = dae_launch_encode(ctx, row_ptr, col, val, W_enc, b_enc, V, H, B, 1.0f, 1.0f, 0U, nullptr,
-                           static_cast<float*>(ctx->h_packed.p), G, RB);
+    rc = reserve_row_d(ctx, g);
     if (rc) return rc;
+    rc = dae_launch_encode(ctx, row_ptr, col, val, W_enc, b_enc, V, H, B, 1.0f, 1.0f, 0U, nullptr,
+                           static_cast<float*>(ctx->h_packed.p), G, RB, nullptr, nullptr, nullptr, 0, static_cast<float*>(ctx->row_d.p));
+    if (rc) return rc;
+    ctx->row_d_fresh = true;
     *g_out = g;
     return DAE_OK;
 }
@@ -499,7 +547,7 @@ int dae_decode_topk(dae_ctx* ctx, const float* h, int B, int H, int dtype, int n
     return for_row_slabs(B, k, seed_row_ptr, out_score, out_idx, [&](int r0, int nb, const int32_t* srp, float* os, int32_t* oi) {
         const float* hs = h + (size_t)r0 * H;
         const dae_rowgeom g = geom_for(dtype, nb, pk->Hp);
-        const int rc = pack_hidden(ctx, dtype, hs, nb, H, g);
+        const int rc = pack_hidden(ctx, dtype, hs, nb, H, g, ctx->mixT == nullptr);      // (the mixed score never skips)
         if (rc) return rc;
         return decode_topk_core(ctx, pk, g, nb, n_tracks, srp, seed_col, k, out_kind, os, oi, dtype, hs,
                                 static_cast<const int*>(ctx->row_bad.p));

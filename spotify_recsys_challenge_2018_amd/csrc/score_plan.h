@@ -77,6 +77,14 @@ inline bool dae_filter_takes_live(const dae_rowgeom& g, int dtype, int Hp, bool 
     return dtype == DAE_DTYPE_F32 && g.R_TILE == 128 && Hp / DAE_KG == 32 && g.waves == 4 && !mixed;
 }
 
+// does the threshold sample run in HALF row groups (decode_generic.hip decode_f32_kernel's HALF: fp32, hidden 256, 128-row groups,
+// cross-wave group maxima, ONE round of tiles)?  The launcher (decode_f32.hip dae_launch_decode_dense_f32) asks the same.
+inline bool dae_sample_takes_half(const dae_rowgeom& g, int dtype, int Hp, bool mixed, int gmax_per_wave, int n_samp)
+{
+    return dtype == DAE_DTYPE_F32 && g.R_TILE == 128 && Hp / DAE_KG == 32 && g.waves == 4 && !gmax_per_wave && !mixed &&
+           n_samp <= g.nb_rg * 4;
+}
+
 struct dae_plan_in {
     int ntiles, col_lo, col_hi, Hp;   // the decoder image (dae_packed)
     bool ub_valid;                    // ... holds per-tile logit bounds of its own (dae_packed::tile_ub)
@@ -114,6 +122,8 @@ struct dae_score_plan {
     int32_t last[8];        // what dae_last_plan reports
     bool live_in_tau;       // build_live, and the threshold launch builds the lists itself (tau_select_kernel's tail, tau_select.hip): no
                             // launch of live_tiles_kernel
+    bool sample_skip;       // the sample runs in half row groups (dae_sample_takes_half) on an image that holds bounds: its waves
+                            // may skip the tiles a bound puts below every row's threshold (under dae_set_filter_skip)
 };
 
 inline dae_score_plan dae_plan_topk(const dae_plan_in& in)
@@ -223,6 +233,7 @@ inline dae_score_plan dae_plan_topk(const dae_plan_in& in)
     const bool whole_b = fused && dtype == DAE_DTYPE_BF16 && ((gmax_per_wave != 1 && !mixed) || exact);
     if (whole_b) p.last[5] = ntiles;
     p.gA = gA; p.wave_groups = wave_groups; p.ld_s = ld_s; p.ld_g = ld_g; p.gmax_per_wave = gmax_per_wave; p.whole_b = whole_b;
+    p.sample_skip = fused && in.ub_valid && dae_sample_takes_half(gA, dtype, in.Hp, mixed, gmax_per_wave, n_samp);
 
     // ---- phase B: everything else through the threshold filter ----------------------------------------------------------------
     p.n_filter = whole_b ? ntiles : n_other;
