@@ -168,6 +168,7 @@ struct dae_ctx {
     // sorted descending; built for one tile order and sample geometry, like tile_band
     dae_buf samp_tab; long long tab_gen = -1; int tab_nsamp = 0, tab_nbrg = 0, tab_waves = 0;
     dae_buf sskip_stat;        // DAE_SSKIP_SLOTS x uint64, one per workgroup of the sample launch: wave-tiles it decoded since the last dae_sample_skip_read
+                               // | DAE_SSKIP_SLOTS x uint32: the decoded-tile table of the last sample launch that skipped (dae_sample_skip::tab)
     unsigned long long sskip_launches = 0, sskip_planned = 0;   // ... and the launches / planned wave-tiles (known on the host)
 
     // profiling of the dominant kernel
@@ -354,6 +355,8 @@ struct dae_sample_skip {
     const float* row_d;               // [Bpad][4] the rows' max |h - 0.5| by quarters
     const int32_t* seed_row_ptr; int k;   // need = k + seeds of the row, as tau_select_kernel's
     unsigned long long* stat;         // [grid of the launch] += wave-tiles decoded, per workgroup (DAE_SSKIP_SLOTS words)
+    unsigned* tab;                    // nullable: [2 n_rg][nb_rg] the decoded-tile table (score_plan.h dae_sample_item_slot) -- the launch
+                                      // stores the decoded tiles' slots only, and dae_launch_tau_select must be given the same table
 };
 // dense epilogue: out[row*ld + item*32 + vl] (item = position of the tile in the set)
 // gmax (nullable): [B][ld_gmax] maxima of every lane's two 8-column groups, 4 per (row, item) -- the threshold
@@ -547,6 +550,8 @@ int dae_launch_topk_dense(dae_ctx* ctx, const dae_dense_src& src, const dae_topk
 //   live (nullable; the workgroup-per-row kernel of an fp32 launch with a dense sample only -- dae_score_plan::live_in_tau):
 //   the launch also builds the live lists of the filter launch that takes these thresholds, as dae_launch_live_tiles would
 //   from them: the last workgroup of each 128-row group to finish does it, so nothing waits and no launch is added
+//   samp_tab (nullable; the workgroup-per-row kernel only), nb_rg: the decoded-tile table of the half-row-group sample that wrote
+//   gmax and samp (dae_sample_skip::tab, n_g == nb_rg * 32): slots the table does not mark are -inf and are never read
 struct dae_tau_live {
     const float4* hp; int B, H, G;                               // the packed fp32 hidden image in 128-row groups; G = Hp / 8 = 32
     const float* tile_ub; int ntiles, nrank;                     // dae_packed::tile_ub of the image's ntiles tiles; ranked columns
@@ -557,7 +562,8 @@ struct dae_tau_live {
 };
 int dae_launch_tau_select(dae_ctx* ctx, const float* gmax, int64_t ld_g, int n_g, const float* samp, int64_t ld_s,
                           int n_s, const int* samp_list, int col_lo, int B, int k, const int32_t* seed_row_ptr,
-                          float* tau, uint2* out_pairs, int64_t pairs_stride, int* out_cnt, const dae_tau_live* live);
+                          float* tau, uint2* out_pairs, int64_t pairs_stride, int* out_cnt, const dae_tau_live* live,
+                          const unsigned* samp_tab = nullptr, int nb_rg = 0);
 int dae_launch_topk_pairs(dae_ctx* ctx, const dae_pair_group& g0, const dae_pair_group& g1,
                           const dae_topk_args& a);
 int dae_launch_topk_soa(dae_ctx* ctx, int G, const float* logit, const int32_t* idx,

@@ -1068,6 +1068,8 @@ int dae_launch_decode_dense_f32(dae_ctx* ctx, const dae_rowgeom& g, int B, const
             if (skip) p.sk = *skip;                            // (tiles a bound puts below tau: the kernel's prologue)
             return dae_launch_decode_gmax_half(ctx, g, p);     // one round of tiles (the threshold sample at batch <= 256)
         }
+        // (a table nobody writes would be read by the threshold launch: the plan gives one to the half-row-group sample only)
+        if (skip && skip->tab) return dae_fail(ctx, DAE_ERR_STATE, "a decoded-tile table for a sample launch that is not in half row groups");
         return dae_launch_decode_generic(ctx, EPI_GMAX, dt, g, p);
     }
     return dae_launch_decode_generic(ctx, EPI_DENSE, dt, g, p);

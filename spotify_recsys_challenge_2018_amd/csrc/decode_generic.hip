@@ -36,7 +36,7 @@ __global__ __launch_bounds__(NW * 64, HALF ? 2 : NW / 4) void decode_f32_kernel(
     // wave-major slots: consecutive tiles go to different workgroups, so a partial round of tiles is
     // spread over all CUs (and, with two waves per SIMD, over all SIMDs) instead of filling a few
     const int n_ws = p.nb_rg * NW;
-    const int item0 = wave * p.nb_rg + bir;
+    const int item0 = dae_sample_slot_item(bir, wave, p.nb_rg);  // = wave * nb_rg + bir (score_plan.h: the decoded-tile table's mapping)
     const bool has0 = item0 < p.ts.n_items;
     // Tile indices come from a list in global memory.  A vector load that the code then waits for
     // drains the WHOLE in-order load queue (s_waitcnt vmcnt(0)), i.e. the W prefetch ring; so the
@@ -53,7 +53,8 @@ __global__ __launch_bounds__(NW * 64, HALF ? 2 : NW / 4) void decode_f32_kernel(
     // max lo_c, sorted descending; d over the half group's real rows; need = k + the most seeds a row of it has), and the
     // threshold, which tau_select_kernel cuts to 16 key bits, is >= tau_safe = the same cut of x.  A tile with A_t + d M_t <
     // tau_safe holds no element that reaches any row's threshold: its maxima are not counted at the prefix the search returns and
-    // none of its logits passes the threshold launch's >= tau -- so the wave stores -inf for it and decodes nothing.  Roundings go
+    // none of its logits passes the threshold launch's >= tau -- so the wave stores -inf for it and decodes nothing (with a
+    // decoded-tile table, p.sk.tab, it stores nothing at all and the threshold launch supplies the -inf: section 4).  Roundings go
     // the safe way (d rounded up by its producer, x down, U up as in dae_tile_is_live, whose !(U < tau) keeps a tile on any NaN).
     // Every wave takes the half group's d and need itself (64 lanes = its 64 rows; one trip to memory with the window of beta
     // that starts at k - 1 and the wave's own {A_t, M_t}): no LDS and no barrier before the workgroup's vote.
@@ -105,8 +106,15 @@ __global__ __launch_bounds__(NW * 64, HALF ? 2 : NW / 4) void decode_f32_kernel(
             if (lane == 0) sk_live[wave] = (has0 && !skip_w) ? 1 : 0;
             __syncthreads();
             int n_live = 0;
+            unsigned word = 0;                                   // the workgroup's word of the decoded-tile table (score_plan.h)
 #pragma unroll
-            for (int w = 0; w < NW; ++w) n_live += sk_live[w];
+            for (int w = 0; w < NW; ++w) {
+                n_live += sk_live[w];
+                word |= (unsigned)sk_live[w] << (8 * w);
+            }
+            // (every workgroup of the launch stores its own word, this one included when it is zero: nobody clears the table)
+            if (p.sk.tab && tid == 0) p.sk.tab[(size_t)rg * p.nb_rg + bir] = word;
+            if (n_live == 0 && p.sk.tab) return;                 // ... and its maxima and dense slots stay as they stand, unread
             if (n_live == 0) {
                 // nothing to decode in this workgroup: -inf into its maxima and its dense sample slots (what the exchange
                 // stores when no wave holds a tile: gmax_round below), and it ends before the hidden tile is copied
@@ -274,7 +282,12 @@ __global__ __launch_bounds__(NW * 64, HALF ? 2 : NW / 4) void decode_f32_kernel(
                 const int w = t2 >> 6, jj = (t2 & 63) >> 1, half = t2 & 1;
                 const int item_w = w * p.nb_rg + bir + round * (p.nb_rg * NW);
                 const int row = rg * R_TILE + rb * 32 + jj;
-                if (item_w < p.ts.n_items && row < p.B) {
+                // HALF with a decoded-tile table: a skipped wave's 32 slots are not stored (sk_live[] sits behind the hidden tile,
+                // i.e. behind these exchange slots, which end at 256 NW <= n_h4 float4: still what the vote left there)
+                bool stored = true;
+                if constexpr (HALF)
+                    if (p.sk.tab) stored = reinterpret_cast<const int*>(lds4 + n_h4)[w] != 0;
+                if (item_w < p.ts.n_items && row < p.B && stored) {
                     float* orow = p.out + (size_t)row * p.ld + (size_t)item_w * 32 + half * 16;
 #pragma unroll
                     for (int q4 = 0; q4 < 4; ++q4)

@@ -241,8 +241,8 @@ static int topk_phase_a(dae_ctx* ctx, const dae_packed* pk, const dae_rowgeom& g
         rc = dae_reserve(ctx, ctx->samp_tab, (4 + (size_t)2 * pl.n_samp + n_beta) * sizeof(float));
         if (rc) return rc;
         if (ctx->samp_tab.p != tab_was) ctx->tab_gen = -1;
-        if (!ctx->sskip_stat.p) {
-            rc = dae_reserve(ctx, ctx->sskip_stat, DAE_SSKIP_SLOTS * sizeof(unsigned long long));
+        if (!ctx->sskip_stat.p) {                          // (the counter words | the decoded-tile table, which nobody clears)
+            rc = dae_reserve(ctx, ctx->sskip_stat, DAE_SSKIP_SLOTS * (sizeof(unsigned long long) + sizeof(unsigned)));
             if (rc) return rc;
             DAE_HIP_CHECK(ctx, hipMemsetAsync(ctx->sskip_stat.p, 0, DAE_SSKIP_SLOTS * sizeof(unsigned long long), ctx->stream));
         }
@@ -255,8 +255,13 @@ static int topk_phase_a(dae_ctx* ctx, const dae_packed* pk, const dae_rowgeom& g
             ctx->tab_gen = pk->order_gen; ctx->tab_nsamp = pl.n_samp; ctx->tab_nbrg = g.nb_rg; ctx->tab_waves = g.waves;
         }
         if (d_fresh && 2 * g.grid <= DAE_SSKIP_SLOTS && ctx->row_d.p && ctx->row_d.bytes >= (size_t)g.Bpad * 4 * sizeof(float)) {
-            sk = dae_sample_skip{ub, beta, n_beta, head, static_cast<const float*>(ctx->row_d.p), seed_row_ptr, k,
-                                 static_cast<unsigned long long*>(ctx->sskip_stat.p)};
+            // SKIPPED TILES ARE NOT STORED: with the workgroup-per-row threshold kernel behind it, the launch writes which wave-tiles
+            // it decoded into a table (2 g.grid <= DAE_SSKIP_SLOTS words behind the counters) and leaves the others' maxima and
+            // dense slots as they stand; the threshold launch takes the table and reads the decoded ones only.  The wave-per-row
+            // kernel keeps the dense exchange (-inf stored and read back)
+            unsigned long long* const stat = static_cast<unsigned long long*>(ctx->sskip_stat.p);
+            unsigned* const tab = dae_tau_wave_per_row(B, pl.ld_g, pl.ld_s) ? nullptr : reinterpret_cast<unsigned*>(stat + DAE_SSKIP_SLOTS);
+            sk = dae_sample_skip{ub, beta, n_beta, head, static_cast<const float*>(ctx->row_d.p), seed_row_ptr, k, stat, tab};
             ctx->sskip_launches += 1;
             ctx->sskip_planned += (unsigned long long)((B + 63) / 64) * (unsigned long long)pl.n_samp;   // half groups with a real row
         }
@@ -306,7 +311,7 @@ static int topk_phase_a(dae_ctx* ctx, const dae_packed* pk, const dae_rowgeom& g
     rc = dae_launch_tau_select(ctx, gmax, pl.ld_g, (int)pl.ld_g, pl.whole_b ? gmax : sample, pl.whole_b ? 0 : pl.ld_s,
                                pl.whole_b ? 0 : (int)pl.ld_s, order, pk->col_lo, B, k,
                                seed_row_ptr, tau_dst, static_cast<uint2*>(ctx->sample_top.p),
-                               pstride, tk.sample_cnt, pl.live_in_tau ? &lv : nullptr);
+                               pstride, tk.sample_cnt, pl.live_in_tau ? &lv : nullptr, sk.ub ? sk.tab : nullptr, g.nb_rg);
     if (rc) return rc;
     tk.live_built = pl.live_in_tau;
     if (pl.live_in_tau) ctx->live_n_rg = g.n_rg;

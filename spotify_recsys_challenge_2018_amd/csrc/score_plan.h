@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "../../include/dae_hip.h"
+#include "tau_search.h"           // DAE_HD
 
 constexpr int DAE_KG = 8;         // k values per packed group (4 MFMA 32x32x2 steps)
 constexpr int DAE_MAX_K = 1024;   // largest top-k of the paths that keep one 2048-key sort buffer: the exact mode, the title mix, the pipeline, the metrics kernel
@@ -84,6 +85,18 @@ inline bool dae_sample_takes_half(const dae_rowgeom& g, int dtype, int Hp, bool 
     return dtype == DAE_DTYPE_F32 && g.R_TILE == 128 && Hp / DAE_KG == 32 && g.waves == 4 && !gmax_per_wave && !mixed &&
            n_samp <= g.nb_rg * 4;
 }
+
+// THE DECODED-TILE TABLE of a half-row-group sample that skips (decode_f32_kernel's HALF -> tau_select_kernel):
+// one 32-bit word per workgroup of the sample launch, [2 n_rg][nb_rg]; byte w of word bir of half group hg is 1 iff wave w of that
+// workgroup decoded its item w * nb_rg + bir (items are wave-major: decode_f32_kernel).  The sample launch stores a row's maxima
+// [bir * 32, bir * 32 + 32) only where the word is non-zero and the 32 dense logits of an item only where its byte is; the
+// threshold launch takes every other slot as -inf without reading it.  The ONE mapping both kernels and the host test
+// (tests/host/sample_sparse_main.cpp) use:
+struct dae_samp_slot { int word, byte; };
+DAE_HD dae_samp_slot dae_sample_item_slot(int item, int nb_rg) { return dae_samp_slot{item % nb_rg, item / nb_rg}; }
+DAE_HD int dae_sample_slot_item(int word, int byte, int nb_rg) { return byte * nb_rg + word; }
+// float4 f of a row's dense sample (32 logits = 8 float4 per item) belongs to item ...
+DAE_HD int dae_sample_f4_item(int f) { return f >> 3; }
 
 struct dae_plan_in {
     int ntiles, col_lo, col_hi, Hp;   // the decoder image (dae_packed)

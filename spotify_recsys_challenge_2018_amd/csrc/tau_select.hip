@@ -91,6 +91,14 @@ __device__ __forceinline__ unsigned block_scan_excl(unsigned v, int lane, int wv
 //     leaves arrive[rg] at zero for the next launch on the stream.
 using TauLive = dae_tau_live;      // (dae_internal.h: filled by score.hip topk_phase_a)
 struct TauNoLive {};
+// SPARSE: the sample launch skipped tiles and stored the decoded ones only (decode_generic.hip decode_f32_kernel's HALF); its
+// decoded-tile table (score_plan.h dae_sample_item_slot) says which.  A slot it does not mark holds whatever an earlier call
+// left there -- this kernel never reads it and takes the -inf the sample used to store: a maximum whose workgroup decoded
+// nothing gets the key that is never counted, a dense float4 of a skipped item is four -inf that passes() never lets through.
+struct TauTab { const unsigned* tab; int nb_rg; };               // [2 n_rg][nb_rg]; n_g == nb_rg * 32
+struct TauNoTab {};
+// where the byte of `item` sits in the kernel's LDS copy: items u * 32 + j (u < 16) of one j side by side
+__device__ __forceinline__ int tau_ipos(int item) { return (item >> 9) * 512 + (item & 31) * 16 + ((item >> 5) & 15); }
 constexpr int LIVE_PER = 16;       // items per thread and chunk of the reducer
 
 // ---- 4. publish {d_row, tau}, arrive; the group's last workgroup builds its live list ----------------------------
@@ -172,10 +180,17 @@ __device__ __forceinline__ void tau_live_tail(const TauP& p, const TauLive& lv, 
 
 // HAS_S = false: no dense sample to scan (n_s == 0: the bf16 / exact filter launch decodes every tile itself) -- tau only,
 // a third of the registers, so that the workgroup fits on a CU NEXT to a filter workgroup of another batch.
-template <int TAU_PER, bool HAS_S = true, bool LIVE = false>   // TAU_PER: maxima per thread held in registers (rows of <= 256 * TAU_PER maxima in one sweep)
-__global__ __launch_bounds__(256) void tau_select_kernel(const TauP p, const std::conditional_t<LIVE, TauLive, TauNoLive> lv)
+template <int TAU_PER, bool HAS_S = true, bool LIVE = false, bool SPARSE = false>   // TAU_PER: maxima per thread held in registers (rows of <= 256 * TAU_PER maxima in one sweep)
+__global__ __launch_bounds__(256) void tau_select_kernel(const TauP p, const std::conditional_t<LIVE, TauLive, TauNoLive> lv,
+                                                         const std::conditional_t<SPARSE, TauTab, TauNoTab> tb)
 {
     static_assert(!LIVE || HAS_S, "the live lists belong to a filter launch that does not decode the sample again");
+    static_assert(!SPARSE || (HAS_S && TAU_PER <= 32), "the table: a dense sample, rows of nb_rg * 32 <= 256 * TAU_PER maxima, nb_rg <= 256 threads");
+    // SPARSE: the table of the row's half group, spread out in LDS in the order the threads ask: one byte per workgroup w (it
+    // stored its 32 maxima) at lgrp[(w & 7) * TAU_PER + (w >> 3)], one per item (< 4 nb_rg <= 32 TAU_PER) at litem[tau_ipos(item)]
+    // -- a thread's TAU_PER groups and its 16 preloaded float4 are 16 contiguous bytes each: one LDS read, not one per register
+    __shared__ __attribute__((aligned(16))) unsigned char lgrp[SPARSE ? 8 * TAU_PER : 16];
+    __shared__ __attribute__((aligned(16))) unsigned char litem[SPARSE ? 32 * TAU_PER : 16];
     __shared__ unsigned wcnt[2][4][3];
     __shared__ unsigned wsum[4];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -195,10 +210,32 @@ __global__ __launch_bounds__(256) void tau_select_kernel(const TauP p, const std
         const int i = u * 256 + tid;
         graw[u] = (one_sweep && i < n) ? g[i] : -__builtin_inff();
     }
+    // SPARSE: the table word of workgroup `tid` of the row's half group, asked for with the maxima (no trip of its own)
+    unsigned tword = 0;
+    if constexpr (SPARSE)
+        if (tid < tb.nb_rg) tword = tb.tab[(size_t)(row >> 6) * tb.nb_rg + tid];
     __builtin_amdgcn_sched_barrier(0);
     unsigned kreg[TAU_PER];
 #pragma unroll
     for (int u = 0; u < TAU_PER; ++u) kreg[u] = dae_okey(graw[u]);     // -inf -> NEG_INF key: never counted
+    if constexpr (SPARSE) {
+        if (tid < tb.nb_rg) {
+            lgrp[(tid & 7) * TAU_PER + (tid >> 3)] = tword != 0u ? 1 : 0;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) litem[tau_ipos(dae_sample_slot_item(tid, b, tb.nb_rg))] = (unsigned char)((tword >> (8 * b)) & 0xFFu);
+        }
+        __syncthreads();
+        // masked at the KEY: an unmarked slot may hold anything, a NaN included.  Maximum u * 256 + tid belongs to workgroup
+        // u * 8 + (tid >> 5); bytes of workgroups >= nb_rg were never written and meet keys that are absent already
+#pragma unroll
+        for (int q = 0; q < TAU_PER / 16; ++q) {
+            const uint4 gb = reinterpret_cast<const uint4*>(lgrp)[(tid >> 5) * (TAU_PER / 16) + q];
+            const unsigned gw[4] = {gb.x, gb.y, gb.z, gb.w};
+#pragma unroll
+            for (int u = 0; u < 16; ++u)
+                kreg[q * 16 + u] = ((gw[u >> 2] >> (8 * (u & 3))) & 0xFFu) ? kreg[q * 16 + u] : DAE_KEY_NEG_INF;
+        }
+    }
     __builtin_amdgcn_sched_barrier(0);
     const float4* srow = reinterpret_cast<const float4*>(p.samp + (size_t)row * p.ld_s);
     const int n4 = HAS_S ? p.n_s >> 2 : 0;
@@ -207,10 +244,20 @@ __global__ __launch_bounds__(256) void tau_select_kernel(const TauP p, const std
     // tiles of the preloaded part (one id per 8 float4) -> LDS: consumed only where something passes
     __shared__ int ltile[HAS_S ? TAU_PRE * 256 / 8 : 1];
     if (HAS_S) {
+        // SPARSE: float4 u * 256 + tid belongs to item u * 32 + (tid >> 3) = dae_sample_f4_item(f): the thread's 16 bytes
+        static_assert(TAU_PRE == 16, "tau_ipos lays 16 items side by side");
+        uint4 ib = make_uint4(0u, 0u, 0u, 0u);
+        if constexpr (SPARSE) ib = reinterpret_cast<const uint4*>(litem)[tid >> 3];
+        const unsigned iw[4] = {ib.x, ib.y, ib.z, ib.w};
 #pragma unroll
         for (int u = 0; u < NPRE; ++u) {
             const int f = u * 256 + tid;
-            zpre[u] = srow[f < n4 ? f : 0];
+            if constexpr (SPARSE) {                              // a skipped item's float4: no request, four -inf
+                zpre[u] = make_float4(-__builtin_inff(), -__builtin_inff(), -__builtin_inff(), -__builtin_inff());
+                if (f < n4 && ((iw[u >> 2] >> (8 * (u & 3))) & 0xFFu)) zpre[u] = srow[f];
+            } else {
+                zpre[u] = srow[f < n4 ? f : 0];
+            }
         }
         for (int i = tid; i < TAU_PRE * 256 / 8; i += 256) ltile[i] = p.samp_list[i < (n4 + 7) / 8 ? i : 0];
     }
@@ -285,7 +332,13 @@ __global__ __launch_bounds__(256) void tau_select_kernel(const TauP p, const std
             if (u * 256 + tid < n4) mine += count4(zpre[u], tv);
         }
     }
-    for (int f = TAU_PRE * 256 + tid; f < n4; f += 256) mine += count4(srow[f], tv);   // rows longer than the preloaded part: read again
+    // rows longer than the preloaded part: read again (SPARSE: the decoded items only)
+    auto decoded = [&](int f) -> bool {
+        if constexpr (SPARSE) return litem[tau_ipos(dae_sample_f4_item(f))] != 0;
+        else return true;
+    };
+    for (int f = TAU_PRE * 256 + tid; f < n4; f += 256)
+        if (decoded(f)) mine += count4(srow[f], tv);
     __syncthreads();
     unsigned at = block_scan_excl(mine, lane, wv, wsum);
     if (tid == 255) p.out_cnt[row] = (int)(at + mine);
@@ -293,7 +346,8 @@ __global__ __launch_bounds__(256) void tau_select_kernel(const TauP p, const std
 #pragma unroll
     for (int u = 0; u < NPRE; ++u)
         if (((live >> u) & 1u) && u * 256 + tid < n4) emit4(p, dst, at, tv, zpre[u], u * 256 + tid, ltile[(u * 256 + tid) >> 3]);
-    for (int f = TAU_PRE * 256 + tid; f < n4; f += 256) emit4(p, dst, at, tv, srow[f], f, p.samp_list[f >> 3]);
+    for (int f = TAU_PRE * 256 + tid; f < n4; f += 256)
+        if (decoded(f)) emit4(p, dst, at, tv, srow[f], f, p.samp_list[f >> 3]);
     if constexpr (LIVE) {
         if constexpr (!HV_EARLY) take_d_row();
         tau_live_tail(p, lv, row, tid, lane, wv, tv, d_row, wsum);
@@ -366,12 +420,19 @@ __global__ __launch_bounds__(256) void tau_select_wave_kernel(const TauP p, cons
 template <bool HAS_S, bool LIVE, typename Lv>
 void launch_tau_per(dae_ctx* ctx, const TauP& p, int B, int per, const Lv& lv)
 {
-    if (per == 16) hipLaunchKernelGGL((tau_select_kernel<16, HAS_S, LIVE>), dim3(B), dim3(256), 0, ctx->stream, p, lv);
-    else if (per == 32) hipLaunchKernelGGL((tau_select_kernel<32, HAS_S, LIVE>), dim3(B), dim3(256), 0, ctx->stream, p, lv);
-    else hipLaunchKernelGGL((tau_select_kernel<64, true, LIVE>), dim3(B), dim3(256), 0, ctx->stream, p, lv);
+    if (per == 16) hipLaunchKernelGGL((tau_select_kernel<16, HAS_S, LIVE>), dim3(B), dim3(256), 0, ctx->stream, p, lv, TauNoTab{});
+    else if (per == 32) hipLaunchKernelGGL((tau_select_kernel<32, HAS_S, LIVE>), dim3(B), dim3(256), 0, ctx->stream, p, lv, TauNoTab{});
+    else hipLaunchKernelGGL((tau_select_kernel<64, true, LIVE>), dim3(B), dim3(256), 0, ctx->stream, p, lv, TauNoTab{});
+}
+// ... with the sample's decoded-tile table (a half-row-group sample: nb_rg <= 256 workgroups, i.e. <= 8 192 maxima per row)
+template <bool LIVE, typename Lv>
+void launch_tau_sparse(dae_ctx* ctx, const TauP& p, int B, int per, const Lv& lv, const TauTab& tb)
+{
+    if (per == 16) hipLaunchKernelGGL((tau_select_kernel<16, true, LIVE, true>), dim3(B), dim3(256), 0, ctx->stream, p, lv, tb);
+    else hipLaunchKernelGGL((tau_select_kernel<32, true, LIVE, true>), dim3(B), dim3(256), 0, ctx->stream, p, lv, tb);
 }
 
-int launch_tau_select(dae_ctx* ctx, const TauP& p, int B, const TauLive* lv)
+int launch_tau_select(dae_ctx* ctx, const TauP& p, int B, const TauLive* lv, const unsigned* samp_tab, int nb_rg)
 {
     if (B <= 0) return DAE_OK;
     // many short rows (>= 4 per CU, <= 2048 maxima and sample logits each: the 8-rank shard of the global batch): a wave
@@ -380,6 +441,7 @@ int launch_tau_select(dae_ctx* ctx, const TauP& p, int B, const TauLive* lv)
     // (score_plan.h dae_tau_wave_per_row: the plan asks the same question before it gives this launch the live lists to build)
     if (dae_tau_wave_per_row(B, p.n_g, p.n_s)) {
         if (lv) return dae_fail(ctx, DAE_ERR_STATE, "the wave-per-row threshold kernel builds no live lists");
+        if (samp_tab) return dae_fail(ctx, DAE_ERR_STATE, "the wave-per-row threshold kernel reads the whole sample: no decoded-tile table");
         hipLaunchKernelGGL((tau_select_wave_kernel<32, 8>), dim3((B + 3) / 4), dim3(256), 0, ctx->stream, p, B);
         DAE_CHECK_LAUNCH(ctx, "tau_select_wave_kernel");
         return DAE_OK;
@@ -387,7 +449,14 @@ int launch_tau_select(dae_ctx* ctx, const TauP& p, int B, const TauLive* lv)
     if (lv && (p.n_s == 0 || lv->G != 32 || lv->n_items <= 0))
         return dae_fail(ctx, DAE_ERR_STATE, "live lists from the threshold launch: fp32 image of hidden 256 with a dense sample only");
     const int per = p.n_g <= 256 * 16 ? 16 : p.n_g <= 256 * 32 ? 32 : 64;
-    if (lv) launch_tau_per<true, true>(ctx, p, B, per, *lv);
+    if (samp_tab) {
+        if (p.n_s == 0 || nb_rg <= 0 || nb_rg > 256 || p.n_g != nb_rg * 32 || p.n_s > 4 * nb_rg * 32)
+            return dae_fail(ctx, DAE_ERR_STATE, "decoded-tile table: a dense one-round sample of nb_rg <= 256 workgroups per half row group only");
+        const TauTab tb{samp_tab, nb_rg};
+        if (lv) launch_tau_sparse<true>(ctx, p, B, per, *lv, tb);
+        else launch_tau_sparse<false>(ctx, p, B, per, TauNoLive{}, tb);
+    }
+    else if (lv) launch_tau_per<true, true>(ctx, p, B, per, *lv);
     else if (p.n_s == 0) launch_tau_per<false, false>(ctx, p, B, per, TauNoLive{});
     else launch_tau_per<true, false>(ctx, p, B, per, TauNoLive{});
     DAE_CHECK_LAUNCH(ctx, "tau_select_kernel");
@@ -398,10 +467,11 @@ int launch_tau_select(dae_ctx* ctx, const TauP& p, int B, const TauLive* lv)
 
 int dae_launch_tau_select(dae_ctx* ctx, const float* gmax, int64_t ld_g, int n_g, const float* samp, int64_t ld_s,
                           int n_s, const int* samp_list, int col_lo, int B, int k, const int32_t* seed_row_ptr,
-                          float* tau, uint2* out_pairs, int64_t pairs_stride, int* out_cnt, const dae_tau_live* live)
+                          float* tau, uint2* out_pairs, int64_t pairs_stride, int* out_cnt, const dae_tau_live* live,
+                          const unsigned* samp_tab, int nb_rg)
 {
     if ((n_s & 31) || (ld_s & 3) || (reinterpret_cast<uintptr_t>(samp) & 15))
         return dae_fail(ctx, DAE_ERR_ARG, "sample rows must be whole tiles, 16-byte aligned");
     TauP p{gmax, ld_g, n_g, samp, ld_s, n_s, samp_list, col_lo, seed_row_ptr, k, tau, out_pairs, pairs_stride, out_cnt};
-    return launch_tau_select(ctx, p, B, live);
+    return launch_tau_select(ctx, p, B, live, samp_tab, nb_rg);
 }
