@@ -547,6 +547,66 @@ int dae_rank_candidates(dae_ctx* ctx, int B, int V, const int32_t* cand_row_ptr,
                         int row_cap, const int32_t* seed_row_ptr, const int32_t* seed_col, int k, int out_kind,
                         float* out_score, int32_t* out_idx);
 
+/* ---- a catalogue: rank a SHARED subset of the track columns (csrc/catalogue.hip) -------------------------------------------
+ *
+ * "The k best tracks among THESE columns, the same for every row" -- a market's catalogue, the non-explicit tracks, the tracks
+ * still licensed, a second generator's pool: main_challenge.py:26-36's ranking with `cand` restricted to a column set.  The
+ * candidate calls above answer it per row from the row-major tensors and lose to a dense decode from a few thousand columns per
+ * row on; handing the complement to every row as seeds decodes the whole vocabulary to discard most of it.  A catalogue call
+ * ranks an image made of the catalogue's decoder rows alone with the fused path of dae_score_topk: n columns of work, not V,
+ * the same kernels and plans, the same bits.
+ *
+ * dae_catalogue_create: cols [n] (DEVICE int32) are GLOBAL track columns, STRICTLY ASCENDING (each once), inside [0, n_tracks),
+ *   1 <= n <= n_tracks.  One launch validates the list and builds the inverse table local_of[n_tracks] (-1: not in the
+ *   catalogue); the call copies the list, reads one status word back and so synchronises the context's stream (once per
+ *   catalogue).  A violation: DAE_ERR_ARG, the message naming the first offending position and its value.  Memory: 4 (n + n_tracks)
+ *   bytes.  Ascending order is the contract everything else rests on: local order equals global order, so the canonical
+ *   tie-break (key descending, column ascending) is the same in both spaces.  The object belongs to ctx's device and is used
+ *   read-only: any number of contexts of that device may rank with it.  dae_catalogue_destroy waits for the device first.
+ * dae_prepack_decoder_catalogue: the context's image of `dtype` from rows cols[0 .. n) of the caller's row-major W_dec [V, H] and
+ *   b_dec[cols] (V >= n_tracks; a title scorer's Output_W^T / Output_b likewise): LOCAL columns [0, n), col_lo = 0, no artist
+ *   part, with everything dae_prepack_decoder leaves with an image -- the fp32 per-tile {A_t, M_t} bounds and the per-column
+ *   lower bounds of the threshold sample, the exact mode's eps_c under dae_set_exact_margin (dae_set_exact_margin_range then
+ *   names LOCAL columns) -- all computed from the gathered rows: a bound of a tile covers the 32 catalogue columns it holds.
+ *   The rows are gathered into a temporary [n, H] that is freed before the call returns (it synchronises the stream); the image
+ *   itself is n x H x 4 (fp32) or 2 (bf16) bytes plus bounds, and under DAE_DTYPE_BF16_EXACT the fp32 rows as well.  The image
+ *   records which catalogue it was gathered from; any other prepack of the slot forgets it.
+ * dae_score_topk_catalogue / dae_decode_topk_catalogue: dae_score_topk / dae_decode_topk with `cat` in the place of n_tracks.
+ *   Seeds are GLOBAL columns, as everywhere else; out_idx holds GLOBAL columns, -1 padding.  n_seeds: the entries of seed_col,
+ *   seed_row_ptr[B], passed by the caller as n_cand is to the candidate calls -- it sizes the translated lists in the context's
+ *   scratch, nothing is read back and nothing at or past it is written (0 with NULL seeds).  Inside, per slab of 4096 rows:
+ *   (a) two small launches translate the seed CSR into the image's columns -- per row the seeds that lie in the catalogue, in
+ *   order, with fresh row pointers; seeds outside it cannot be ranked, and dropping them keeps the thresholds' k + n_seeds
+ *   tight -- (b) the existing call runs on the image with n_tracks = n, (c) one launch maps out_idx through cols in place.
+ *   The result is, bit for bit, the canonical ranking of the FULL image's logits restricted to the catalogue's columns: a logit
+ *   depends on its own decoder row and the hidden row only, and every kernel runs the canonical chain per element.
+ *   k: as the underlying call (4096; 1024 with DAE_DTYPE_BF16_EXACT).  An image that was not gathered from `cat` (a plain
+ *   image, another catalogue's): DAE_ERR_STATE.  Every refusal comes before any launch.
+ * dae_title_score_catalogue: dae_title_score plus `cat`, for DAE_DTYPE_F32 / DAE_DTYPE_BF16 (DAE_DTYPE_BF16_EXACT: DAE_ERR_ARG
+ *   before any launch -- rank with DAE_DTYPE_F32, the same lists).  BOTH contexts hold catalogue images of `dtype` gathered from
+ *   the same `cat`: the DAE's decoder and the title scorer's Output_W^T / Output_b.  The feed keeps its global columns (CSR,
+ *   encode, mixing weights, seeds = the playlist's own tracks < n_tracks, which must be the catalogue's n_tracks); the seeds are
+ *   translated behind that, the mix term and the ranking run over the n local columns, the indices are mapped back.
+ *   n_rows <= 4096. */
+typedef struct dae_catalogue dae_catalogue;
+int dae_catalogue_create(dae_ctx* ctx, const int32_t* cols, int n, int n_tracks, dae_catalogue** out);
+int dae_catalogue_destroy(dae_catalogue* cat);
+int dae_prepack_decoder_catalogue(dae_ctx* ctx, const dae_catalogue* cat, const float* W_dec, const float* b_dec, int V, int H,
+                                  int dtype);
+int dae_score_topk_catalogue(dae_ctx* ctx, const int32_t* row_ptr, const int32_t* col, const float* val, const float* W_enc,
+                             const float* b_enc, int V, int H, int B, int dtype, const dae_catalogue* cat,
+                             const int32_t* seed_row_ptr, const int32_t* seed_col, int n_seeds, int k, int out_kind,
+                             float* out_score, int32_t* out_idx);
+int dae_decode_topk_catalogue(dae_ctx* ctx, const float* h, int B, int H, int dtype, const dae_catalogue* cat,
+                              const int32_t* seed_row_ptr, const int32_t* seed_col, int n_seeds, int k, int out_kind,
+                              float* out_score, int32_t* out_idx);
+int dae_title_score_catalogue(dae_ctx* title_ctx, dae_ctx* dae, int dtype, const int64_t* positions, const float* values,
+                              int values_broadcast, int64_t nnz, int n_rows, int V, const float* W_enc, const float* b_enc, int H,
+                              const int32_t* titles, int L, const float* emb, int n_char, int E, const float* conv_w,
+                              const float* conv_b, const int32_t* filter_sizes, int n_sizes, int F, int ld_feat,
+                              const float* titles_use, int n_tracks, int k, float* out_score, int32_t* out_idx,
+                              int32_t* guard_out, int32_t* csr_status, const dae_catalogue* cat);
+
 /* ---- training step (DAEs.py:98-102) ------------------------------------------------------ */
 
 /* Arithmetic of the three GEMMs of the training step of this context (forward hidden x W_dec^T, gW_dec = dz^T h,

@@ -31,6 +31,8 @@ EXPORTS = [
     "dae_pipeline_release", "dae_pipeline_stats", "dae_pipeline_exact_margin", "dae_pipeline_times", "dae_pipeline_last_error",
     "dae_rank_metrics", "dae_pipeline_enable_eval", "dae_pipeline_submit_eval", "dae_pipeline_poll_eval",
     "dae_decode_candidates", "dae_score_candidates", "dae_mix_candidates", "dae_rank_candidates",
+    "dae_catalogue_create", "dae_catalogue_destroy", "dae_prepack_decoder_catalogue", "dae_score_topk_catalogue",
+    "dae_decode_topk_catalogue", "dae_title_score_catalogue",
 ]
 DAE_PIPE_BUSY = 1
 
@@ -172,6 +174,13 @@ def load():
     lib.dae_mix_candidates.argtypes = [vp, vp, vp, c_i64, c_int, vp, vp, vp, c_i64, vp, vp, vp, vp, c_int, c_int, vp, vp,
                                        c_int, vp, vp]
     lib.dae_rank_candidates.argtypes = [vp, c_int, c_int, vp, vp, vp, c_int, vp, vp, c_int, c_int, vp, vp]
+    lib.dae_catalogue_create.argtypes = [vp, vp, c_int, c_int, ctypes.POINTER(vp)]
+    lib.dae_catalogue_destroy.argtypes = [vp]
+    lib.dae_prepack_decoder_catalogue.argtypes = [vp, vp, vp, vp, c_int, c_int, c_int]
+    lib.dae_score_topk_catalogue.argtypes = [vp, vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, vp, vp, vp, c_int,
+                                             c_int, c_int, vp, vp]
+    lib.dae_decode_topk_catalogue.argtypes = [vp, vp, c_int, c_int, c_int, vp, vp, vp, c_int, c_int, c_int, vp, vp]
+    lib.dae_title_score_catalogue.argtypes = lib.dae_title_score.argtypes + [vp]
     for name in EXPORTS:
         if name not in ("dae_last_error", "dae_scratch_bytes", "dae_profile_kernel", "dae_pipeline_last_error"):
             getattr(lib, name).restype = c_int
@@ -599,6 +608,48 @@ class Context:
                                                 _ptr(seed_row_ptr), _ptr(seed_col), int(k), int(out_kind), _ptr(out_score),
                                                 _ptr(out_idx)))
 
+    # ---- a catalogue: a shared, ascending subset of the track columns (csrc/catalogue.hip; `Catalogue` below) ------------------
+    def prepack_decoder_catalogue(self, cat, W_dec, b_dec, dtype=DAE_DTYPE_F32):
+        """This context's image of `dtype` from rows cat.columns of W_dec [V, H] / b_dec [V] (dae_prepack_decoder_catalogue): local
+        columns [0, n).  The gathered copy is a temporary of the call."""
+        V, H = W_dec.shape
+        assert W_dec.is_contiguous() and b_dec.is_contiguous() and b_dec.numel() == V
+        self.check(self.lib.dae_prepack_decoder_catalogue(self.h, cat.h, _ptr(W_dec), _ptr(b_dec), int(V), int(H), int(dtype)))
+        self._drop_share(dtype)
+
+    def score_topk_catalogue(self, cat, row_ptr, col, val, W_enc, b_enc, seed_row_ptr, seed_col, k, out_score, out_idx,
+                             out_kind=DAE_OUT_SCORE, dtype=DAE_DTYPE_F32):
+        """`score_topk` over the catalogue's columns (dae_score_topk_catalogue): seeds and out_idx are GLOBAL columns."""
+        V, H = W_enc.shape
+        B = row_ptr.numel() - 1
+        n_seeds = int(seed_col.numel()) if seed_col is not None else 0
+        self.check(self.lib.dae_score_topk_catalogue(self.h, _ptr(row_ptr), _ptr(col), _ptr(val), _ptr(W_enc), _ptr(b_enc), V, H, B,
+                                                     int(dtype), cat.h, _ptr(seed_row_ptr), _ptr(seed_col), n_seeds, int(k),
+                                                     int(out_kind), _ptr(out_score), _ptr(out_idx)))
+
+    def decode_topk_catalogue(self, cat, h, seed_row_ptr, seed_col, k, out_score, out_idx, out_kind=DAE_OUT_SCORE,
+                              dtype=DAE_DTYPE_F32):
+        """`decode_topk` over the catalogue's columns (dae_decode_topk_catalogue)."""
+        B, H = h.shape
+        n_seeds = int(seed_col.numel()) if seed_col is not None else 0
+        self.check(self.lib.dae_decode_topk_catalogue(self.h, _ptr(h), B, H, int(dtype), cat.h, _ptr(seed_row_ptr), _ptr(seed_col),
+                                                      n_seeds, int(k), int(out_kind), _ptr(out_score), _ptr(out_idx)))
+
+    def title_score_catalogue(self, cat, dae_ctx, dtype, positions, values, n_rows, W_enc, b_enc, titles, emb, n_char, conv_w,
+                              conv_b, filter_sizes, F, ld_feat, titles_use, n_tracks, k, out_score, out_idx, csr_status,
+                              guard_out=None):
+        """On the title scorer's context: one titled launch over the catalogue's columns (dae_title_score_catalogue).  positions
+        int64 [nnz, 2] / values float32 [nnz] or [1]: the feed on the device; titles int32 [n_rows, L]; filter_sizes a ctypes
+        int32 array.  Both contexts hold images gathered from `cat`."""
+        V, H = W_enc.shape
+        nnz = int(positions.shape[0])
+        bcast = 1 if (values.numel() == 1 and nnz != 1) else 0
+        self.check(self.lib.dae_title_score_catalogue(
+            self.h, dae_ctx.h, int(dtype), _ptr(positions), _ptr(values), bcast, nnz, int(n_rows), int(V), _ptr(W_enc), _ptr(b_enc),
+            int(H), _ptr(titles), int(titles.shape[1]), _ptr(emb), int(n_char), int(emb.shape[1]), _ptr(conv_w), _ptr(conv_b),
+            filter_sizes, len(filter_sizes), int(F), int(ld_feat), _ptr(titles_use), int(n_tracks), int(k), _ptr(out_score),
+            _ptr(out_idx), _ptr(guard_out), _ptr(csr_status), cat.h))
+
     def topk_merge(self, cand_logit, cand_idx, out_score, out_idx, out_kind=DAE_OUT_SCORE):
         G, B, k = cand_logit.shape
         self.check(self.lib.dae_topk_merge(self.h, G, B, k, _ptr(cand_logit), _ptr(cand_idx),
@@ -649,6 +700,32 @@ class Context:
         keys = ["R_TILE", "n_rg", "nb_rg", "S", "n_sample_tiles", "n_filter_tiles", "fused",
                 "n_tiles"]
         return dict(zip(keys, list(arr)))
+
+
+class Catalogue:
+    """Owns one dae_catalogue: an ascending list of global track columns and its inverse table on the device of `ctx`
+    (dae_catalogue_create validates the list on the device: unsorted, repeated or non-track ids raise DaeError naming the first
+    offender).  columns: an int32 CUDA tensor [n] (copied by the library).  Any context of that device ranks with it."""
+
+    def __init__(self, ctx, columns, n_tracks):
+        import torch
+        self.ctx, self.h = ctx, None
+        assert columns.dtype == torch.int32 and columns.is_cuda and columns.dim() == 1 and columns.is_contiguous()
+        self.n, self.n_tracks = int(columns.numel()), int(n_tracks)
+        h = ctypes.c_void_p()
+        ctx.check(ctx.lib.dae_catalogue_create(ctx.h, _ptr(columns), self.n, self.n_tracks, ctypes.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.dae_catalogue_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class _Block:

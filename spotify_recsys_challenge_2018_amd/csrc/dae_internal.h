@@ -69,6 +69,10 @@ struct dae_packed {            // one prepacked decoder image
     // |z32 - z16| <= F_r alpha_c + beta_c; the bias fragments carry b -+ beta in k-slots 0..2 and -+alpha (bf16) in slot 3
     dae_buf mix_alpha, mix_beta;    // [ntiles*32] fp32 (alpha: the bf16 value the fragments hold)
     dae_buf mix16_lo, mix16_hi;     // [ntiles][64] uint4
+    // the dae_catalogue the image was gathered from (catalogue.hip dae_prepack_decoder_catalogue; its columns are then the
+    // catalogue's LOCAL ones), 0 = an image of the vocabulary's own columns.  Every prepack launcher resets it; it travels with
+    // dae_share_decoder
+    uint64_t cat_id = 0;
 };
 
 // the buffers of an image that dae_share_decoder lends to another context (`order` / `ident` stay each context's own)
@@ -158,6 +162,7 @@ struct dae_ctx {
     // launch that never completes (a device fault) leaves them standing for the life of the context, like the rest of its state
     dae_buf live_sync; void* live_sync_zeroed = nullptr; size_t live_sync_zeroed_bytes = 0;   // (which allocation was zeroed)
     dae_buf cand_list;         // dae_rank_candidates: [B][row_cap] (key, column) pairs | [B] counts (candidates.hip)
+    dae_buf cat_seeds;         // the catalogue calls: a slab's seed lists in the catalogue's columns, [4097] row pointers | [4096] counts | the columns (catalogue.hip)
     dae_buf skip_stat;         // 3 x uint64 {launches, planned tiles x row groups, live tiles} since the last dae_filter_skip_read
     // the threshold sample in half row groups skips the tiles a bound puts below tau (decode_generic.hip decode_f32_kernel's HALF):
     // row_d = [Bpad][4] floats, the rows' max |h - 0.5| by quarters, written by whoever wrote the packed fp32 hidden image
@@ -449,6 +454,7 @@ struct dae_title_bufs {
     int32_t *rp, *col, *srp, *sc;     // CSR of the feed [B + 1], [nnz]; seed lists [B + 1], [nnz]
     float *val, *h, *feat, *wt, *wp;  // values [nnz]; DAE hidden rows [B][H]; title features [B][ld_feat]; mixing weights [B]
 };
+int dae_title_bufs_reserve(dae_ctx* tc, int64_t nnz, int B, int H, int ld_feat, dae_title_bufs& b);      // out of tc->title_scratch
 int dae_title_prepare(dae_ctx* tc, dae_ctx* dc, const int64_t* positions, const float* values, int values_broadcast, int64_t nnz,
                       int B, int V, const float* W_enc, const float* b_enc, int H, const int32_t* titles, int L, const float* emb,
                       int n_char, int E, const float* conv_w, const float* conv_b, const int32_t* filter_sizes, int n_sizes, int F,
@@ -513,6 +519,9 @@ int dae_launch_mix_pass(dae_ctx* tc, const dae_mix_plan& pl, bool sample, const 
 int dae_launch_mix_refine(dae_ctx* tc, const dae_mix_plan& pl, const dae_packed& pd, const dae_packed& pt, const dae_mix_call& c);   // mix_refine.hip
 int dae_launch_mix_audit(dae_ctx* tc, dae_ctx* dc, int n_valid_col, const dae_mix_call& c);                           // audit.hip
 void dae_note_plan(const int32_t last[8]);      // score.hip: what dae_last_plan reports
+// score.hip: what every ranking call refuses before any launch -- null outputs, an unknown dtype, k beyond the dtype's limit, half a seed CSR
+int dae_check_topk_args(dae_ctx* ctx, int dtype, int k, const int32_t* seed_row_ptr, const int32_t* seed_col,
+                        const void* out_score, const void* out_idx);
 int dae_mix_topk_exact_impl(dae_ctx* tc, dae_ctx* dc, const float* feat, int64_t ld_feat, const float* h, int64_t ld_h, int B,
                             const float* w_title, const float* w_playlist, int n_tracks, const int32_t* seed_row_ptr,
                             const int32_t* seed_col, int k, float* out_score, int32_t* out_idx);

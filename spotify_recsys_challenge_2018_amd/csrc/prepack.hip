@@ -580,7 +580,7 @@ int dae_launch_prepack_bf16(dae_ctx* ctx, const float* W, const float* b, int V,
                             int col_lo, int col_hi, int exact)
 {
     dae_packed& pk = ctx->pk_bf16;
-    pk.valid = false; pk.order_nrank = -1; pk.exact = false;
+    pk.valid = false; pk.order_nrank = -1; pk.exact = false; pk.cat_id = 0;
     if (exact && (H & 3)) return dae_fail(ctx, DAE_ERR_ARG, "DAE_DTYPE_BF16_EXACT needs H %% 4 == 0 (H=%d)", H);
     const int Hp = dae_round_up(H, DAE_HPAD);
     if ((size_t)32 * Hp * 2 > 128 * 1024)
@@ -649,7 +649,7 @@ int dae_launch_prepack_f32(dae_ctx* ctx, const float* W, const float* b, int V, 
                            int col_lo, int col_hi, bool bounds)
 {
     dae_packed& pk = ctx->pk_f32;
-    pk.valid = false; pk.order_nrank = -1; pk.ub_valid = false;
+    pk.valid = false; pk.order_nrank = -1; pk.ub_valid = false; pk.cat_id = 0;
     const int Hp = dae_round_up(H, DAE_HPAD);
     if ((size_t)32 * Hp * 4 > 128 * 1024)
         return dae_fail(ctx, DAE_ERR_ARG, "hidden size %d too large (max 1024)", H);

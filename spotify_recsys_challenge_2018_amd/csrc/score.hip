@@ -454,8 +454,8 @@ static int check_k(dae_ctx* ctx, int dtype, int k)
     return DAE_OK;
 }
 
-static int check_topk_args(dae_ctx* ctx, int dtype, int k, const int32_t* seed_row_ptr,
-                           const int32_t* seed_col, const void* out_score, const void* out_idx)
+int dae_check_topk_args(dae_ctx* ctx, int dtype, int k, const int32_t* seed_row_ptr,
+                        const int32_t* seed_col, const void* out_score, const void* out_idx)
 {
     if (!out_score || !out_idx) return dae_fail(ctx, DAE_ERR_ARG, "null pointer");
     if (!dae_known_dtype(dtype)) return dae_fail(ctx, DAE_ERR_ARG, "unknown dtype %d", dtype);
@@ -545,7 +545,7 @@ int dae_decode_topk(dae_ctx* ctx, const float* h, int B, int H, int dtype, int n
 {
     if (!ctx) return DAE_ERR_ARG;
     if (!h) return dae_fail(ctx, DAE_ERR_ARG, "null pointer");
-    int rc = check_topk_args(ctx, dtype, k, seed_row_ptr, seed_col, out_score, out_idx);
+    int rc = dae_check_topk_args(ctx, dtype, k, seed_row_ptr, seed_col, out_score, out_idx);
     if (rc) return rc;
     const dae_packed* pk = packed_for(ctx, dtype, H);
     if (!pk) return DAE_ERR_STATE;
@@ -565,7 +565,7 @@ int dae_score_topk(dae_ctx* ctx, const int32_t* row_ptr, const int32_t* col, con
                    int k, int out_kind, float* out_score, int32_t* out_idx)
 {
     if (!ctx) return DAE_ERR_ARG;
-    int rc = check_topk_args(ctx, dtype, k, seed_row_ptr, seed_col, out_score, out_idx);
+    int rc = dae_check_topk_args(ctx, dtype, k, seed_row_ptr, seed_col, out_score, out_idx);
     if (rc) return rc;
     if (B <= 0) return packed_for(ctx, dtype, H) ? DAE_OK : DAE_ERR_STATE;
     return for_row_slabs(B, k, seed_row_ptr, out_score, out_idx, [&](int r0, int nb, const int32_t* srp, float* os, int32_t* oi) {
@@ -642,7 +642,7 @@ int dae_mix_topk_exact(dae_ctx* title_ctx, dae_ctx* dae_ctx_, const float* feat,
     if (title_ctx->device != dae_ctx_->device) return dae_fail(title_ctx, DAE_ERR_ARG, "dae_mix_topk_exact: contexts on different devices");
     if (!feat || !h || !w_title || !w_playlist) return dae_fail(title_ctx, DAE_ERR_ARG, "null pointer");
     if (B < 0 || n_tracks <= 0) return dae_fail(title_ctx, DAE_ERR_ARG, "bad shape B=%d n_tracks=%d", B, n_tracks);
-    int rc = check_topk_args(title_ctx, DAE_DTYPE_BF16_EXACT, k, seed_row_ptr, seed_col, out_score, out_idx);
+    int rc = dae_check_topk_args(title_ctx, DAE_DTYPE_BF16_EXACT, k, seed_row_ptr, seed_col, out_score, out_idx);
     if (rc) return rc;
     if (title_ctx->mixT) return dae_fail(title_ctx, DAE_ERR_STATE, "dae_mix_topk_exact takes the DAE's hidden rows itself: clear dae_set_score_mix");
     rc = dae_mix_topk_exact_impl(title_ctx, dae_ctx_, feat, ld_feat, h, ld_h, B, w_title, w_playlist, n_tracks, seed_row_ptr,
@@ -661,7 +661,26 @@ int dae_mix_topk_exact(dae_ctx* title_ctx, dae_ctx* dae_ctx_, const float* feat,
 // dae_title_score in two halves (round 6): everything of a titled launch that does not depend on the lane's previous launch --
 // title features, the feed -> CSR + seed lists, the DAE's hidden rows, the mixing weights -- and the ranking itself.
 // dae_title_score runs them back to back on one stream; dae_pipeline runs the first half of launch n + 1 on its prep stream
-// (contexts of its own) while the lane still ranks launch n.
+// (contexts of its own) while the lane still ranks launch n.  What travels between the halves (dae_title_bufs), for the calls that
+// run both themselves (dae_title_score, dae_title_score_catalogue), is carved out of one buffer of the title context:
+int dae_title_bufs_reserve(dae_ctx* tc, int64_t nnz, int B, int H, int ld_feat, dae_title_bufs& b)
+{
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t nz = (size_t)(nnz > 0 ? nnz : 1);
+    const size_t o_rp = 0, o_col = o_rp + up((size_t)(B + 1) * 4), o_val = o_col + up(nz * 4), o_srp = o_val + up(nz * 4),
+                 o_sc = o_srp + up((size_t)(B + 1) * 4), o_h = o_sc + up(nz * 4), o_ft = o_h + up((size_t)B * H * 4),
+                 o_wt = o_ft + up((size_t)B * ld_feat * 4), o_wp = o_wt + up((size_t)B * 4), total = o_wp + up((size_t)B * 4);
+    const int rc = dae_reserve(tc, tc->title_scratch, total);
+    if (rc) return rc;
+    char* base = static_cast<char*>(tc->title_scratch.p);
+    b.rp = reinterpret_cast<int32_t*>(base + o_rp); b.col = reinterpret_cast<int32_t*>(base + o_col);
+    b.val = reinterpret_cast<float*>(base + o_val); b.srp = reinterpret_cast<int32_t*>(base + o_srp);
+    b.sc = reinterpret_cast<int32_t*>(base + o_sc); b.h = reinterpret_cast<float*>(base + o_h);
+    b.feat = reinterpret_cast<float*>(base + o_ft); b.wt = reinterpret_cast<float*>(base + o_wt);
+    b.wp = reinterpret_cast<float*>(base + o_wp);
+    return DAE_OK;
+}
+
 int dae_title_prepare(dae_ctx* tc, dae_ctx* dc, const int64_t* positions, const float* values, int values_broadcast, int64_t nnz,
                       int B, int V, const float* W_enc, const float* b_enc, int H, const int32_t* titles, int L, const float* emb,
                       int n_char, int E, const float* conv_w, const float* conv_b, const int32_t* filter_sizes, int n_sizes, int F,
@@ -724,21 +743,9 @@ int dae_title_score(dae_ctx* tc, dae_ctx* dc, int dtype, const int64_t* position
         return dae_fail(tc, DAE_ERR_ARG, "bad shape");
     if (dc->stream != tc->stream) return dae_fail(tc, DAE_ERR_STATE, "both contexts must be bound to the same stream");
     const int B = n_rows;
-    // the launch's intermediates, carved out of one buffer of the title context
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t nz = (size_t)(nnz > 0 ? nnz : 1);
-    const size_t o_rp = 0, o_col = o_rp + up((size_t)(B + 1) * 4), o_val = o_col + up(nz * 4), o_srp = o_val + up(nz * 4),
-                 o_sc = o_srp + up((size_t)(B + 1) * 4), o_h = o_sc + up(nz * 4), o_ft = o_h + up((size_t)B * H * 4),
-                 o_wt = o_ft + up((size_t)B * ld_feat * 4), o_wp = o_wt + up((size_t)B * 4), total = o_wp + up((size_t)B * 4);
-    int rc = dae_reserve(tc, tc->title_scratch, total);
-    if (rc) return rc;
-    char* base = static_cast<char*>(tc->title_scratch.p);
     dae_title_bufs b;
-    b.rp = reinterpret_cast<int32_t*>(base + o_rp); b.col = reinterpret_cast<int32_t*>(base + o_col);
-    b.val = reinterpret_cast<float*>(base + o_val); b.srp = reinterpret_cast<int32_t*>(base + o_srp);
-    b.sc = reinterpret_cast<int32_t*>(base + o_sc); b.h = reinterpret_cast<float*>(base + o_h);
-    b.feat = reinterpret_cast<float*>(base + o_ft); b.wt = reinterpret_cast<float*>(base + o_wt);
-    b.wp = reinterpret_cast<float*>(base + o_wp);
+    int rc = dae_title_bufs_reserve(tc, nnz, B, H, ld_feat, b);
+    if (rc) return rc;
     rc = dae_title_prepare(tc, dc, positions, values, values_broadcast, nnz, B, V, W_enc, b_enc, H, titles, L, emb, n_char, E, conv_w,
                            conv_b, filter_sizes, n_sizes, F, ld_feat, titles_use, n_tracks, b, csr_status);
     if (rc) return rc;

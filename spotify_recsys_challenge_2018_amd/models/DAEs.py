@@ -189,6 +189,97 @@ def seeds_to_csr(seeds, n_rows, n_tracks):
     return row_ptr.astype(np.int32), flat.astype(np.int32)
 
 
+def catalogue_columns(columns, n_tracks):
+    """The columns of a catalogue (`model.catalogue`) -> int32 array, or ValueError naming the first offender: the list holds
+    track columns, each once, in ascending order (local order then equals global order: the canonical tie-break by column is the
+    same inside the catalogue and outside).  Pure numpy: needs no device."""
+    a = np.asarray(columns)
+    if a.ndim != 1:
+        raise ValueError("catalogue: a flat sequence of column ids is required, got shape %s" % (a.shape,))
+    if a.size == 0:
+        raise ValueError("catalogue: the list of columns is empty")
+    if a.dtype.kind not in "iu":
+        raise ValueError("catalogue: integer column ids are required, got %s" % a.dtype)
+    a = a.astype(np.int64)
+    bad = np.nonzero(a < 0)[0]
+    if bad.size:
+        raise ValueError("catalogue: columns[%d] = %d is negative" % (bad[0], a[bad[0]]))
+    bad = np.nonzero(a >= n_tracks)[0]
+    if bad.size:
+        raise ValueError("catalogue: columns[%d] = %d is no track column (tracks are [0, %d); artist columns are never ranked)"
+                         % (bad[0], a[bad[0]], n_tracks))
+    bad = np.nonzero(np.diff(a) <= 0)[0]
+    if bad.size:
+        i = int(bad[0]) + 1
+        if a[i] == a[i - 1]:
+            raise ValueError("catalogue: columns[%d] = %d is listed twice (a duplicate of columns[%d])" % (i, a[i], i - 1))
+        raise ValueError("catalogue: columns[%d] = %d is below columns[%d] = %d: the list must be sorted ascending"
+                         % (i, a[i], i - 1, a[i - 1]))
+    return a.astype(np.int32)
+
+
+class CatalogueHandle:
+    """What `model.catalogue(columns)` returns and `recommend(..., catalogue=handle)` takes: the column set on the device
+    (_lib.Catalogue) and contexts of its OWN that hold the decoder rows of those columns as images -- one for the DAE's decoder
+    and, on a DAE_title, one for the title scorer's output layer -- packed lazily per dtype.  The model's own full images are
+    never re-tiled when full and catalogue calls alternate.  The images follow the model's weights: after a parameter change
+    (`_mark_dirty` / the title model's `_params_gen`) the next call re-packs.  Memory per dtype in use: n x hidden x 4 (fp32) or
+    2 (bf16) bytes plus bounds (exact_bf16: the fp32 rows as well), the same for the title rows; 4 (n + n_tracks) bytes for the
+    column tables.  `close()` frees everything."""
+
+    def __init__(self, model, cols):
+        import torch
+        self.model, self.columns = model, cols
+        self.ctx = _lib.Context(model.device_index)
+        dev = torch.device("cuda", model.device_index)
+        self.cat = _lib.Catalogue(self.ctx, torch.from_numpy(cols).to(dev), model.n_tracks)
+        self.n = int(cols.size)
+        self.title_ctx = _lib.Context(model.device_index) if model._title_scorer() is not None else None
+        self._packed, self._title_packed = {}, {}        # image slot -> (weights generation, holds the exact mode's bounds)
+        self._exact_title_said = False
+
+    @staticmethod
+    def _fresh(packed, slot, gen, dtype):
+        have = packed.get(slot)
+        return have is not None and have[0] == gen and (dtype != _lib.DAE_DTYPE_BF16_EXACT or have[1])
+
+    def _ensure(self, dtype):
+        """The DAE context's image of `dtype` holds the catalogue's rows of the model's CURRENT decoder."""
+        m = self.model
+        m.sync_params()
+        slot = _lib.Context._slot(dtype)
+        if not self._fresh(self._packed, slot, m._weights_gen, dtype):
+            self.ctx.bind_stream()
+            self.ctx.prepack_decoder_catalogue(self.cat, m.weights["decoder_h"], m.biases["decoder_b"], dtype)
+            self._packed[slot] = (m._weights_gen, dtype == _lib.DAE_DTYPE_BF16_EXACT)
+
+    def _ensure_title(self, dtype):
+        """The same for the title scorer's Output_W^T / Output_b on the title context."""
+        tm = self.model.title_model
+        if dtype == _lib.DAE_DTYPE_F32:
+            tm._check_f32_features()
+        slot = _lib.Context._slot(dtype)
+        if not self._fresh(self._title_packed, slot, tm._params_gen, dtype):
+            self.title_ctx.bind_stream()
+            self.title_ctx.prepack_decoder_catalogue(self.cat, tm.p["Output_WT"], tm.p["Output_b"], dtype)
+            self._title_packed[slot] = (tm._params_gen, dtype == _lib.DAE_DTYPE_BF16_EXACT)
+
+    def close(self):
+        if getattr(self, "cat", None) is not None:
+            self.cat.close()
+            self.cat = None
+            for c in (self.ctx, self.title_ctx):
+                if c is not None:
+                    c.close()
+            self.ctx = self.title_ctx = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class DAE_tied:
     """Tied-weight denoising autoencoder (reference DAEs.py:13-111)."""
 
@@ -567,11 +658,70 @@ class DAE_tied:
         self._guard_fallbacks += n
         warnings.warn(what, stacklevel=2)
 
-    def recommend(self, x_positions, x_ones, seeds, k=500, n_rows=None, dtype=None):
+    # -- a catalogue: the same column subset for every row (csrc/catalogue.hip) -----------------------------------------------------
+    def catalogue(self, columns):
+        """A handle for `recommend(..., catalogue=handle)`: the k best tracks among THESE columns -- a market's catalogue, the
+        tracks still licensed, another generator's pool -- at the cost of a ranking over len(columns) columns instead of n_tracks.
+        columns: any integer sequence or array of track columns, ascending, each once; an unsorted, repeated, negative or
+        non-track id or an empty list raises ValueError naming the offender, before anything touches the device.  The handle
+        (CatalogueHandle) owns its contexts and images and follows this model's weights; `handle.close()` frees it.
+        Not built: `recommend_iter` / `evaluate_iter` / the pipeline, `rank_candidates` inside a catalogue, vocabulary shards (a
+        model with a scoring shard is refused here) and a config.ini key."""
+        if self._score_shard is not None:
+            raise _lib.DaeError("catalogue scoring is not vocabulary-sharded: this model has a scoring shard (shard_scoring); "
+                                "rank a catalogue on a model that holds the whole decoder")
+        cols = catalogue_columns(columns, self.n_tracks)
+        if self.ctx is None:
+            raise _lib.DaeError("catalogue(): call fit() first -- the handle lives on the model's device")
+        return CatalogueHandle(self, cols)
+
+    def _catalogue_begin(self, cat):
+        if not isinstance(cat, CatalogueHandle) or cat.model is not self:
+            raise ValueError("catalogue: a handle from this model's `catalogue(columns)` is required")
+        if cat.cat is None:
+            raise ValueError("catalogue: the handle has been closed")
+        if self._score_shard is not None:
+            raise _lib.DaeError("catalogue scoring is not vocabulary-sharded: this model has a scoring shard (shard_scoring); "
+                                "rank a catalogue on a model that holds the whole decoder")
+
+    def _recommend_catalogue(self, cat, x_positions, x_ones, seeds, k, n_rows, dtype):
+        """`recommend` inside a catalogue: the feed's CSR and seed lists as always (global columns, built on this model's
+        context), then dae_score_topk_catalogue on the handle's context -- its image holds the catalogue's rows only."""
+        import torch
+        dtype = _deep_k_dtype(self._dtype_of(dtype), k, self)
+        cat._ensure(dtype)
+        self.ctx.bind_stream()
+        cat.ctx.bind_stream()
+        n_rows = self.n_batch if n_rows is None else n_rows
+        dev = self.weights["encoder_h"].device
+        csr = self._upload_csr(x_positions, x_ones)
+        d_srp, d_sc = self._seed_csr_dev(seeds, csr)
+        score = torch.empty((self.n_batch, k), dtype=torch.float32, device=dev)
+        idx = torch.empty((self.n_batch, k), dtype=torch.int32, device=dev)
+        cat.ctx.score_topk_catalogue(cat.cat, csr[0], csr[1], csr[2], self.weights["encoder_h"], self.biases["encoder_b"],
+                                     d_srp, d_sc, k, score, idx, dtype=dtype)
+        res = idx[:n_rows].cpu().numpy(), score[:n_rows].cpu().numpy()
+        self._check_feed()
+        if dtype == _lib.DAE_DTYPE_BF16_EXACT:
+            # the exact mode's bound guard, on the handle's context: the same call again on the catalogue's fp32 image
+            n_bad, col = cat.ctx.exact_guard_read()
+            if n_bad:
+                self._guard_fell_back("exact_bf16 (catalogue): the bound guard fired (%d survivors, e.g. catalogue position %d): "
+                                      "this batch is re-scored with the fp32 kernels" % (n_bad, col))
+                return self._recommend_catalogue(cat, x_positions, x_ones, seeds, k, n_rows, _lib.DAE_DTYPE_F32)
+        return res
+
+    def recommend(self, x_positions, x_ones, seeds, k=500, n_rows=None, dtype=None, catalogue=None):
         """Fused scoring path: encode -> decode -> top-k (track columns, seeds removed).
         Equivalent of main_challenge.py:80-90 / main_train.py:66-89 without the dense matrix.
-        Returns (idx [n_rows,k] int32 with -1 padding, score [n_rows,k] float32)."""
+        Returns (idx [n_rows,k] int32 with -1 padding, score [n_rows,k] float32).
+        catalogue: a handle of `catalogue(columns)` -- the ranking is restricted to its columns (seeds and indices stay global
+        columns; rows with fewer than k rankable columns are padded with -1): bit for bit the canonical ranking of the full
+        image's scores over those columns, in every decode dtype, SEEDS_FROM_INPUT included."""
         import torch
+        if catalogue is not None:
+            self._catalogue_begin(catalogue)
+            return self._recommend_catalogue(catalogue, x_positions, x_ones, seeds, k, n_rows, dtype)
         dtype = _deep_k_dtype(self._dtype_of(dtype), k, self)
         sh = self._score_shard
         self._ensure_packed(dtype, None if sh is None else sh["cols"])
@@ -1423,15 +1573,64 @@ class DAE_title(DAE):
                               % ("rows overflow the refine launch" if col in (-2, -3) else "column %d" % col))
         return self._submit(x_positions, x_ones, seeds, k, _lib.DAE_DTYPE_F32, titles, titles_use, n_rows=n_rows)
 
-    def recommend(self, x_positions, x_ones, seeds, k=500, n_rows=None, dtype=None, titles=None, titles_use=None):
+    def _recommend_catalogue_titled(self, cat, x_positions, x_ones, seeds, k, n_rows, dtype, titles, titles_use):
+        """The titled `recommend` inside a catalogue: `_submit`'s fused mix with the two vocabulary-wide GEMMs on the handle's
+        images -- the DAE term of the catalogue's n columns (dae_decode_mix_term on its DAE context), then the threshold path of
+        its title context over sigmoid(z_title) * w_title + that term (dae_decode_topk_catalogue: seeds translated, ranked over
+        n columns, indices mapped back).  Encode, mixing weights and title features are the model's own launches.  fp32 and
+        plain bf16; exact_bf16 has no catalogue mix and runs on the fp32 kernels (the lists it promises), said once."""
+        import torch
+        dtype = self._dtype_of(dtype)
+        if dtype == _lib.DAE_DTYPE_BF16_EXACT:
+            if not cat._exact_title_said:
+                cat._exact_title_said = True
+                import sys
+                print("[dae] decode_dtype = exact_bf16: the exact title mix does not rank inside a catalogue; titled catalogue "
+                      "calls run on the fp32 kernels (same lists, slower)", file=sys.stderr)
+            dtype = _lib.DAE_DTYPE_F32
+        tm = self.title_model
+        if cat.title_ctx is None:
+            raise _lib.DaeError("catalogue: the handle was made before the title scorer was fitted; make a new one")
+        cat._ensure(dtype)
+        cat._ensure_title(dtype)
+        for c in (self.ctx, tm.ctx, cat.ctx, cat.title_ctx):
+            c.bind_stream()
+        nb = self.n_batch
+        n_rows = nb if n_rows is None else n_rows
+        dev = self.weights["encoder_h"].device
+        csr = self._upload_csr(x_positions, x_ones)
+        h = torch.empty((nb, self.n_hidden), dtype=torch.float32, device=dev)
+        self.ctx.encode(csr[0], csr[1], csr[2], self.weights["encoder_h"], self.biases["encoder_b"], h)
+        w_t, w_p = self._mix_weights(csr, titles_use)
+        feat = tm.features(titles, nb)
+        d_srp, d_sc = self._seed_csr_dev(seeds, csr)
+        score = torch.empty((nb, k), dtype=torch.float32, device=dev)
+        idx = torch.empty((nb, k), dtype=torch.int32, device=dev)
+        y1T = torch.empty((cat.n, nb), dtype=torch.float32, device=dev)
+        cat.ctx.decode_mix_term(h, w_p, cat.n, y1T, dtype=dtype)
+        cat.title_ctx.set_score_mix(y1T, w_t)
+        try:
+            cat.title_ctx.decode_topk_catalogue(cat.cat, feat, d_srp, d_sc, k, score, idx, out_kind=_lib.DAE_OUT_LOGIT, dtype=dtype)
+        finally:
+            cat.title_ctx.set_score_mix()
+        res = idx[:n_rows].cpu().numpy(), score[:n_rows].cpu().numpy()
+        self._check_feed()
+        return res
+
+    def recommend(self, x_positions, x_ones, seeds, k=500, n_rows=None, dtype=None, titles=None, titles_use=None, catalogue=None):
         """Top-k of the MIXED score (DAEs.py:176-181 + main_challenge.py:26-41) without either [batch, n_input] matrix
         (see `_submit`).  Same operations in the same order as `mixed_scores` + dae_topk_dense, hence the same bits
         (fp32).  dtype "bf16" (or [BASE] decode_dtype = bf16) runs BOTH vocabulary-wide GEMMs -- the DAE decoder and
         the title scorer's output layer -- on bf16 operands with fp32 accumulate; encode, title features, sigmoids,
-        the mix, the threshold and the ranking stay fp32."""
+        the mix, the threshold and the ranking stay fp32.
+        catalogue: as `DAE.recommend` takes it -- the mixed score ranked over the handle's columns alone
+        (`_recommend_catalogue_titled`)."""
         if titles is None or titles_use is None or not np.any(np.asarray(titles_use)):
-            return DAE.recommend(self, x_positions, x_ones, seeds, k=k, n_rows=n_rows, dtype=dtype)
+            return DAE.recommend(self, x_positions, x_ones, seeds, k=k, n_rows=n_rows, dtype=dtype, catalogue=catalogue)
         _refuse_deep_k(k, "DAE_title.recommend with titles in use")       # (before any upload)
+        if catalogue is not None:
+            self._catalogue_begin(catalogue)
+            return self._recommend_catalogue_titled(catalogue, x_positions, x_ones, seeds, k, n_rows, dtype, titles, titles_use)
         if self._score_shard is not None:
             raise _lib.DaeError("title-mixed batches are not vocabulary-sharded: run --challenge with titles on one "
                                 "GPU per process group (playlist partitioning), or without the title variables")
