@@ -607,6 +607,24 @@ int dae_title_score_catalogue(dae_ctx* title_ctx, dae_ctx* dae, int dtype, const
                               const float* titles_use, int n_tracks, int k, float* out_score, int32_t* out_idx,
                               int32_t* guard_out, int32_t* csr_status, const dae_catalogue* cat);
 
+/* The pipeline inside a catalogue: from this call on EVERY launch of `p` ranks cat's columns -- plain launches as
+ * dae_score_topk_catalogue ranks them, titled ones as dae_title_score_catalogue, bit for bit; lists (and, in evaluation mode, the
+ * candidates of dae_rank_metrics) are global columns.
+ *   Once, before the first submit (like dae_pipeline_enable_eval; either order): DAE_ERR_STATE afterwards, or when a catalogue is
+ *   set already.  DAE_ERR_ARG: a catalogue of another device; one created over another n_tracks than the pipeline's; a titled
+ *   pipeline of DAE_DTYPE_BF16_EXACT (dae_title_score_catalogue has no such mode: create the pipeline with DAE_DTYPE_F32, the same
+ *   lists).  A refused call leaves the pipeline as it was.
+ *   The pipeline gathers images of its OWN from the W_dec / b_dec (and Output_W^T / Output_b) it was created with: lane 0 tiles
+ *   them, the other lanes borrow them, and an fp32 image a lane needs later (the exact mode's guard re-run) is the catalogue's too.
+ *   The seed translation runs on the pipeline's preparation stream, behind the launch's CSR, into buffers of the launch slot
+ *   (4 (2 group_rows + max_nnz) bytes per slot); the lane's stream carries the ranking and the map-back.
+ *   Evaluation mode: dae_rank_metrics runs AFTER the map-back, so an answer outside the catalogue can never be hit and counts in
+ *   the record's denominators, exactly as a -1 answer does; a caller who wants recall within the catalogue filters the answers
+ *   on the host before it feeds them.
+ *   LIFETIME: the pipeline keeps the pointer, not a copy -- the caller keeps `cat` alive until dae_pipeline_destroy(p) has
+ *   returned. */
+int dae_pipeline_set_catalogue(dae_pipeline* p, const dae_catalogue* cat);
+
 /* ---- training step (DAEs.py:98-102) ------------------------------------------------------ */
 
 /* Arithmetic of the three GEMMs of the training step of this context (forward hidden x W_dec^T, gW_dec = dz^T h,

@@ -12,7 +12,14 @@ time per call, `--iters` calls between two events, the median of `--runs` altern
 compared with the candidate route's (indices) before anything is timed.  Also measured: the one-off cost of dae_catalogue_create +
 dae_prepack_decoder_catalogue per n (wall clock, both calls synchronise).  `--bias zeros` runs the same with b_dec = 0: the zipf
 bias of the default model lets the fp32 path skip most tiles, which is no property of every model.
-Prints one line per case and a final JSON line; `--out FILE` also writes the JSON there."""
+Prints one line per case and a final JSON line; `--out FILE` also writes the JSON there.
+
+`--loop`: playlists/s THROUGH THE LOOP instead -- feeds of 250 rows (host COO in, host lists out), k = 500, catalogues of `--sizes`
+(default 7 500 and 35 000 columns), three routes alternating in one process, the median of `--runs` runs each:
+  (a) recommend_iter(..., catalogue=h)       the pipeline in catalogue mode
+  (b) recommend(..., catalogue=h) per feed    the per-batch call, the caller's thread driving each launch and fetching after it
+  (c) recommend_iter over the full vocabulary
+(a)'s lists are compared with (b)'s before anything is timed."""
 import argparse
 import json
 import os
@@ -40,6 +47,79 @@ def timed(fn, iters):
     return e0.elapsed_time(e1) / iters          # ms per call
 
 
+def loop_bench(a):
+    import pickle
+    import tempfile
+    import torch
+    from spotify_recsys_challenge_2018_amd.models.DAEs import DAE, SEEDS_FROM_INPUT
+    nt, na, H, k, B = a.tracks, a.artists, a.hidden, a.k, 250
+    V = nt + na
+    W_enc, b_enc, W_dec, b_dec = make_weights(V, H, seed=0, bias=a.bias, n_tracks=nt)
+    tmp = tempfile.mkdtemp(prefix="bench_catalogue_")
+    path = os.path.join(tmp, "init.pkl")
+    with open(path, "wb") as f:
+        pickle.dump([W_enc, W_dec, b_enc, b_dec], f)
+
+    class C:
+        save = os.path.join(tmp, "unused"); batch = B; n_input = V; hidden = H; lr = 0.005; reg_lambda = 0.0
+        n_tracks = nt; initval = path
+    # one model per pipeline: a model keeps ONE at a time, alternating the loops on one model would time its re-creation
+    m, m_full = DAE(C()), DAE(C())
+    m.fit(); m_full.fit()
+    feeds = [make_playlists(B, nt, na, seed=200 + s)[:2] + (SEEDS_FROM_INPUT, B) for s in range(16)]
+    rng = np.random.default_rng(0)
+    n_a, n_b, n_c = a.feeds
+    res = {"loop": True, "V": V, "tracks": nt, "H": H, "rows_per_feed": B, "k": k, "bias": a.bias, "runs": a.runs, "feeds": a.feeds,
+           "cases": []}
+    print("loop: V = %d (%d tracks), hidden = %d, feeds of %d rows, k = %d; playlists/s, %d alternating runs" % (V, nt, H, B, k, a.runs))
+
+    def run(gen, n):
+        t0 = time.perf_counter()
+        rows = 0
+        for idx, _s in gen:
+            rows += len(idx)
+        dt = time.perf_counter() - t0
+        assert rows == n * B
+        return rows / dt
+
+    for n in a.sizes or [7500, 35000]:
+        h = m.catalogue(np.sort(rng.permutation(nt)[:n]).astype(np.int32))
+        for name in a.dtypes:
+            def route_a(nf):
+                return m.recommend_iter((feeds[i % 16] for i in range(nf)), k=k, dtype=name, want_scores=False, catalogue=h)
+
+            def route_b(nf):
+                return (m.recommend(*feeds[i % 16][:3], k=k, n_rows=B, dtype=name, catalogue=h) for i in range(nf))
+
+            def route_c(nf):
+                return m_full.recommend_iter((feeds[i % 16] for i in range(nf)), k=k, dtype=name, want_scores=False)
+            same = all(np.array_equal(x[0], y[0]) for x, y in zip(route_a(16), route_b(16)))
+            run(route_a(max(64, n_a // 8)), max(64, n_a // 8)); run(route_b(16), 16); run(route_c(max(64, n_c // 8)), max(64, n_c // 8))
+            torch.cuda.synchronize()
+            ra, rb, rc = [], [], []
+            for _ in range(a.runs):
+                ra.append(run(route_a(n_a), n_a)); rb.append(run(route_b(n_b), n_b)); rc.append(run(route_c(n_c), n_c))
+            case = {"dtype": name, "n": n, "lists_equal": same, "a_playlists_per_s": [round(x) for x in ra],
+                    "b_playlists_per_s": [round(x) for x in rb], "c_playlists_per_s": [round(x) for x in rc],
+                    "a_median": round(float(np.median(ra))), "b_median": round(float(np.median(rb))), "c_median": round(float(np.median(rc))),
+                    "a_ahead_in_every_pair": all(x > y for x, y in zip(ra, rb)),
+                    "a_over_b_median": round(float(np.median(ra) / np.median(rb)), 2)}
+            res["cases"].append(case)
+            print("%-4s n = %6d: (a) %9d (%s)  (b) %9d (%s)  (c) %9d (%s)  | a / b %.2f, ahead in every pair: %s | lists %s"
+                  % (name, n, case["a_median"], " ".join(str(x) for x in case["a_playlists_per_s"]), case["b_median"],
+                     " ".join(str(x) for x in case["b_playlists_per_s"]), case["c_median"],
+                     " ".join(str(x) for x in case["c_playlists_per_s"]), case["a_over_b_median"], case["a_ahead_in_every_pair"],
+                     "equal" if same else "DIFFER"), flush=True)
+        h.close()
+    m.close_pipelines(); m_full.close_pipelines()
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    return 0 if all(c["lists_equal"] for c in res["cases"]) else 1
+
+
 def main():
     import torch
     ap = argparse.ArgumentParser()
@@ -55,7 +135,11 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--runs", type=int, default=4)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--loop", action="store_true", help="playlists/s through the streamed loop (see the module docstring)")
+    ap.add_argument("--feeds", type=int, nargs=3, default=[20000, 2000, 20000], help="--loop: feeds of a timed run of (a), (b), (c)")
     a = ap.parse_args()
+    if a.loop:
+        return loop_bench(a)
     nt, na, H, B, k = a.tracks, a.artists, a.hidden, a.rows, a.k
     V = nt + na
     sizes = a.sizes or [1000, 7500, 35000, 70000, nt]
@@ -160,4 +244,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())

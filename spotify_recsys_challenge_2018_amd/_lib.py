@@ -32,7 +32,7 @@ EXPORTS = [
     "dae_rank_metrics", "dae_pipeline_enable_eval", "dae_pipeline_submit_eval", "dae_pipeline_poll_eval",
     "dae_decode_candidates", "dae_score_candidates", "dae_mix_candidates", "dae_rank_candidates",
     "dae_catalogue_create", "dae_catalogue_destroy", "dae_prepack_decoder_catalogue", "dae_score_topk_catalogue",
-    "dae_decode_topk_catalogue", "dae_title_score_catalogue",
+    "dae_decode_topk_catalogue", "dae_title_score_catalogue", "dae_pipeline_set_catalogue",
 ]
 DAE_PIPE_BUSY = 1
 
@@ -181,6 +181,7 @@ def load():
                                              c_int, c_int, vp, vp]
     lib.dae_decode_topk_catalogue.argtypes = [vp, vp, c_int, c_int, c_int, vp, vp, vp, c_int, c_int, c_int, vp, vp]
     lib.dae_title_score_catalogue.argtypes = lib.dae_title_score.argtypes + [vp]
+    lib.dae_pipeline_set_catalogue.argtypes = [vp, vp]
     for name in EXPORTS:
         if name not in ("dae_last_error", "dae_scratch_bytes", "dae_profile_kernel", "dae_pipeline_last_error"):
             getattr(lib, name).restype = c_int
@@ -832,6 +833,13 @@ class Pipeline:
         disc = discount_table(self.k)
         self._check(self.lib.dae_pipeline_enable_eval(self.h, disc.ctypes.data_as(ctypes.c_void_p), int(max_answers)))
         self.eval, self.max_answers = True, int(max_answers)
+
+    def set_catalogue(self, cat):
+        """Catalogue mode (dae_pipeline_set_catalogue), before the first submit: every launch ranks the columns of `cat` (a
+        `Catalogue` of this device and of the pipeline's n_tracks); lists and metric records keep global columns.  The pipeline
+        holds `cat` and so keeps it alive; close the pipeline before the catalogue."""
+        self._check(self.lib.dae_pipeline_set_catalogue(self.h, cat.h))
+        self._cat = cat
 
     def _feed_arrays(self, positions, values):
         import numpy as np

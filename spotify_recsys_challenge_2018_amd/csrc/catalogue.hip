@@ -157,6 +157,19 @@ int reserve_seeds(dae_ctx* ctx, int cap)
     return dae_reserve(ctx, ctx->cat_seeds, (CAT_HEAD_INTS + (size_t)(cap > 0 ? cap : 1)) * sizeof(int32_t));
 }
 
+// a. into buffers the caller owns: rp [B + 1], cnt [B], out [cap] (the pipeline's launch slots; the offsets' sum in
+// cat_seed_compact_kernel walks the counts before the row, whatever B is)
+int translate_seeds_into(dae_ctx* ctx, const dae_catalogue* cat, const int32_t* srp, const int32_t* sc, int B, int cap, int32_t* rp,
+                         int* cnt, int32_t* out)
+{
+    const dim3 grid((B + 3) / 4), block(256);
+    hipLaunchKernelGGL(cat_seed_count_kernel, grid, block, 0, ctx->stream, srp, sc, B, cat->local_of, cat->n_tracks, cnt);
+    DAE_CHECK_LAUNCH(ctx, "cat_seed_count_kernel");
+    hipLaunchKernelGGL(cat_seed_compact_kernel, grid, block, 0, ctx->stream, srp, sc, B, cat->local_of, cat->n_tracks, cnt, rp, out, cap);
+    DAE_CHECK_LAUNCH(ctx, "cat_seed_compact_kernel");
+    return DAE_OK;
+}
+
 // a.: rows [0, B) of the seed CSR (srp holds absolute offsets into sc) -> ctx->cat_seeds; B <= CAT_SLAB, reserve_seeds(cap) done
 int translate_seeds(dae_ctx* ctx, const dae_catalogue* cat, const int32_t* srp, const int32_t* sc, int B, int cap,
                     const int32_t** srp_out, const int32_t** sc_out)
@@ -164,11 +177,8 @@ int translate_seeds(dae_ctx* ctx, const dae_catalogue* cat, const int32_t* srp, 
     int32_t* rp = static_cast<int32_t*>(ctx->cat_seeds.p);
     int* cnt = rp + CAT_RP_INTS;
     int32_t* out = rp + CAT_HEAD_INTS;
-    const dim3 grid((B + 3) / 4), block(256);
-    hipLaunchKernelGGL(cat_seed_count_kernel, grid, block, 0, ctx->stream, srp, sc, B, cat->local_of, cat->n_tracks, cnt);
-    DAE_CHECK_LAUNCH(ctx, "cat_seed_count_kernel");
-    hipLaunchKernelGGL(cat_seed_compact_kernel, grid, block, 0, ctx->stream, srp, sc, B, cat->local_of, cat->n_tracks, cnt, rp, out, cap);
-    DAE_CHECK_LAUNCH(ctx, "cat_seed_compact_kernel");
+    const int rc = translate_seeds_into(ctx, cat, srp, sc, B, cap, rp, cnt, out);
+    if (rc) return rc;
     *srp_out = rp; *sc_out = out;
     return DAE_OK;
 }
@@ -205,6 +215,54 @@ int rank_slabs(dae_ctx* ctx, const dae_catalogue* cat, int B, int k, const int32
 }
 
 }  // namespace
+
+// ---- what the pipeline needs of a catalogue (dae_internal.h): the translation on ITS prep stream into ITS slot's buffers, then
+// the ranking calls with the local seed lists ready ----------------------------------------------------------------------------
+void dae_catalogue_shape(const dae_catalogue* cat, int* device, int* n, int* n_tracks)
+{
+    *device = cat->device; *n = cat->n; *n_tracks = cat->n_tracks;
+}
+
+int dae_catalogue_translate_seeds(dae_ctx* ctx, const dae_catalogue* cat, const int32_t* srp, const int32_t* sc, int B, int cap,
+                                  int32_t* rp_out, int32_t* cnt, int32_t* sc_out)
+{
+    if (!ctx) return DAE_ERR_ARG;
+    if (!cat || !srp || !sc || !rp_out || !cnt || !sc_out) return dae_fail(ctx, DAE_ERR_ARG, "null pointer");
+    if (B < 1 || cap < 0) return dae_fail(ctx, DAE_ERR_ARG, "dae_catalogue_translate_seeds: B=%d cap=%d", B, cap);
+    return translate_seeds_into(ctx, cat, srp, sc, B, cap, rp_out, cnt, sc_out);
+}
+
+// dae_score_topk_catalogue behind a translation that has run already: local_srp / local_sc are the image's columns (any B: the
+// seeds' row pointers are absolute, dae_score_topk walks its own slabs), one map-back over the call's lists
+int dae_score_topk_catalogue_local(dae_ctx* ctx, const int32_t* row_ptr, const int32_t* col, const float* val, const float* W_enc,
+                                   const float* b_enc, int V, int H, int B, int dtype, const dae_catalogue* cat,
+                                   const int32_t* local_srp, const int32_t* local_sc, int k, int out_kind, float* out_score,
+                                   int32_t* out_idx)
+{
+    if (!ctx) return DAE_ERR_ARG;
+    int rc = check_rank_args(ctx, cat, dtype, k, local_srp, local_sc, 0, out_score, out_idx);
+    if (rc) return rc;
+    if (H != slot_of(ctx, dtype).H) return dae_fail(ctx, DAE_ERR_ARG, "H=%d does not match prepacked H=%d", H, slot_of(ctx, dtype).H);
+    if (B <= 0) return DAE_OK;
+    rc = dae_score_topk(ctx, row_ptr, col, val, W_enc, b_enc, V, H, B, dtype, cat->n, local_srp, local_sc, k, out_kind, out_score, out_idx);
+    if (rc) return rc;
+    return map_back(ctx, cat, out_idx, (size_t)B * k);
+}
+
+// the titled ranking inside a catalogue, between the seed translation and the end of the call: both contexts' images are the
+// catalogue's, b.srp / b.sc hold LOCAL columns; the mix term and the ranking over the n local columns (both images end at column
+// n), then the map-back.  dae_title_score_catalogue and the pipeline's titled launches both end here.
+int dae_title_rank_catalogue(dae_ctx* tc, dae_ctx* dc, int dtype, int B, int H, int ld_feat, const dae_title_bufs& b,
+                             const dae_catalogue* cat, int k, float* out_score, int32_t* out_idx, int32_t* guard_out)
+{
+    int rc = check_image(tc, dc, cat, dtype, "the DAE context's");
+    if (rc) return rc;
+    rc = check_image(tc, tc, cat, dtype, "the title context's");
+    if (rc) return rc;
+    rc = dae_title_rank(tc, dc, dtype, B, cat->n, H, ld_feat, b, cat->n, k, out_score, out_idx, guard_out);
+    if (rc) return rc;
+    return map_back(tc, cat, out_idx, (size_t)B * k);
+}
 
 extern "C" {
 
@@ -376,10 +434,7 @@ int dae_title_score_catalogue(dae_ctx* tc, dae_ctx* dc, int dtype, const int64_t
     rc = translate_seeds(tc, cat, b.srp, b.sc, B, cap, &srp, &sc);
     if (rc) return rc;
     b.srp = const_cast<int32_t*>(srp); b.sc = const_cast<int32_t*>(sc);
-    // the mix term and the ranking over the n local columns: both images end at column n
-    rc = dae_title_rank(tc, dc, dtype, B, cat->n, H, ld_feat, b, cat->n, k, out_score, out_idx, guard_out);
-    if (rc) return rc;
-    return map_back(tc, cat, out_idx, (size_t)B * k);
+    return dae_title_rank_catalogue(tc, dc, dtype, B, H, ld_feat, b, cat, k, out_score, out_idx, guard_out);
 }
 
 }  // extern "C"

@@ -471,6 +471,18 @@ int dae_launch_coo32_to_csr_seeds(dae_ctx* ctx, const int32_t* positions, const 
 int dae_launch_seeds_from_csr(dae_ctx* ctx, const int32_t* row_ptr, const int32_t* col, int B, int n_tracks,
                               int32_t* seed_row_ptr, int32_t* seed_col);
 
+// catalogue.hip, for the pipeline: the seed translation into caller-owned buffers (rp_out [B + 1], cnt [B], sc_out [cap]; any B,
+// on the context's stream), and the ranking calls that take the translated (LOCAL) seed lists and end with the map-back
+void dae_catalogue_shape(const dae_catalogue* cat, int* device, int* n, int* n_tracks);
+int dae_catalogue_translate_seeds(dae_ctx* ctx, const dae_catalogue* cat, const int32_t* srp, const int32_t* sc, int B, int cap,
+                                  int32_t* rp_out, int32_t* cnt, int32_t* sc_out);
+int dae_score_topk_catalogue_local(dae_ctx* ctx, const int32_t* row_ptr, const int32_t* col, const float* val, const float* W_enc,
+                                   const float* b_enc, int V, int H, int B, int dtype, const dae_catalogue* cat,
+                                   const int32_t* local_srp, const int32_t* local_sc, int k, int out_kind, float* out_score,
+                                   int32_t* out_idx);
+int dae_title_rank_catalogue(dae_ctx* tc, dae_ctx* dc, int dtype, int B, int H, int ld_feat, const dae_title_bufs& b,
+                             const dae_catalogue* cat, int k, float* out_score, int32_t* out_idx, int32_t* guard_out);
+
 // title.hip
 int dae_launch_title_features(dae_ctx* ctx, const int32_t* titles, int B, int L, const float* emb, int n_char,
                               int E, const float* conv_w, const float* conv_b, const int32_t* filter_sizes,

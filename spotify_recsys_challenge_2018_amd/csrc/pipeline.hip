@@ -53,6 +53,10 @@ struct Slot {                     // one launch from staging to its last polled 
     int64_t* d_pos = nullptr; float* d_val = nullptr;      // the feed on the device (uploaded on the copy stream, ahead of the lane)
     // the launch's CSR and seed lists (plain launches), built on the PREP stream while the lane still scores its previous launch
     int32_t *d_rp = nullptr, *d_col = nullptr, *d_srp = nullptr, *d_scol = nullptr, *d_status = nullptr; float* d_cval = nullptr;
+    // catalogue mode (dae_pipeline_set_catalogue): the launch's seed lists in the catalogue's LOCAL columns -- row pointers
+    // [group_rows + 1], the rows' counts [group_rows], columns [max_nnz] -- written on the prep stream behind the seed lists.  They
+    // belong to the slot, not to a context: the lane's previous launch may still be reading its own
+    int32_t *d_lrp = nullptr, *d_lcnt = nullptr, *d_lscol = nullptr;
     float *t_h = nullptr, *t_feat = nullptr, *t_wt = nullptr, *t_wp = nullptr;   // titled: hidden rows, title features, mixing weights
     hipEvent_t ev_prep = nullptr;
     int32_t* d_idx = nullptr; float* d_score = nullptr;    // the launch's lists on the device (moved out on the OUT stream, round 6)
@@ -126,6 +130,7 @@ struct dae_pipeline {
     TitleW tw;
     int exact_pause = 0, overflow_streak = 0;      // titled + exact: launches left on the fp32 kernels / overflow events in a row
     bool eval = false;            // dae_pipeline_enable_eval: feeds carry answers, records go out instead of lists
+    const dae_catalogue* cat = nullptr;   // dae_pipeline_set_catalogue: every launch ranks ITS columns (the caller keeps it alive)
     int64_t max_answers = 0;
     double* d_disc = nullptr;     // the caller's discount table [k]
     uint64_t issue_ns = 0, idle_ns = 0, submit_ns = 0, wait_ns = 0;      // where the host side of the loop spends its time (dae_pipeline_times)
@@ -203,6 +208,14 @@ __global__ void flags_snapshot_kernel(int32_t* dst, const int32_t* status, const
     }
 }
 
+// an image of `dtype` on a context that owns it (lane 0's): the vocabulary's columns, or in catalogue mode the catalogue's rows
+// of the same arrays (W [V][ld], b [V]: the DAE's decoder, or the title scorer's Output_W^T / Output_b)
+int pack_image(dae_pipeline* p, dae_ctx* ctx, const float* W, const float* b, int ld, int dtype)
+{
+    return p->cat ? dae_prepack_decoder_catalogue(ctx, p->cat, W, b, p->V, ld, dtype)
+                  : dae_prepack_decoder(ctx, W, b, p->V, ld, 0, p->V, dtype);
+}
+
 // fp32 images on a lane (the bound guard's fallback; a paused exact mode): the DAE's and, on a titled pipeline, the title
 // scorer's -- lane 0 re-tiles them, the other lanes borrow lane 0's (issue_mu held)
 int ensure_f32(dae_pipeline* p, int lane)
@@ -211,13 +224,13 @@ int ensure_f32(dae_pipeline* p, int lane)
     Lane& L = p->lanes[lane];
     int rc = DAE_OK;
     if (!L0.has_f32) {
-        rc = dae_prepack_decoder(L0.ctx, p->W_dec, p->b_dec, p->V, p->H, 0, p->V, DAE_DTYPE_F32);
+        rc = pack_image(p, L0.ctx, p->W_dec, p->b_dec, p->H, DAE_DTYPE_F32);
         if (rc) return pfatal(p, rc, dae_last_error(L0.ctx));
         PIPE_HIP(p, hipStreamSynchronize(L0.stream));
         L0.has_f32 = true;
     }
     if (p->has_title && !L0.t_has_f32) {
-        rc = dae_prepack_decoder(L0.tctx, p->tw.out_WT, p->tw.out_b, p->V, p->tw.ld_feat, 0, p->V, DAE_DTYPE_F32);
+        rc = pack_image(p, L0.tctx, p->tw.out_WT, p->tw.out_b, p->tw.ld_feat, DAE_DTYPE_F32);
         if (rc) return pfatal(p, rc, dae_last_error(L0.tctx));
         PIPE_HIP(p, hipStreamSynchronize(L0.stream));
         L0.t_has_f32 = true;
@@ -283,9 +296,17 @@ int issue(dae_pipeline* p, Slot& S, int dtype)
                                t.L, t.emb, t.n_char, t.E, t.conv_w, t.conv_b, t.fs.data(), t.n_sizes, t.F, t.ld_feat, S.d_use,
                                p->n_tracks, tb, S.d_status);
         if (rc) return pfatal(p, rc, dae_last_error(p->prep_tctx));
+        if (p->cat) {
+            // catalogue mode: the seed lists into the catalogue's columns, still on the prep stream (they depend on the feed alone);
+            // the lane ranks the two catalogue images and maps the lists back (catalogue.hip)
+            rc = dae_catalogue_translate_seeds(p->prep_ctx, p->cat, S.d_srp, S.d_scol, S.rows, (int)S.nnz, S.d_lrp, S.d_lcnt, S.d_lscol);
+            if (rc) return pfatal(p, rc, dae_last_error(p->prep_ctx));
+            tb.srp = S.d_lrp; tb.sc = S.d_lscol;
+        }
         PIPE_HIP(p, hipEventRecord(S.ev_prep, p->prep_stream));
         PIPE_HIP(p, hipStreamWaitEvent(L.stream, S.ev_prep, 0));
-        rc = dae_title_rank(L.tctx, L.ctx, dtype, S.rows, p->V, p->H, t.ld_feat, tb, p->n_tracks, p->k, out_score, out_idx, L.d_guard);
+        rc = p->cat ? dae_title_rank_catalogue(L.tctx, L.ctx, dtype, S.rows, p->H, t.ld_feat, tb, p->cat, p->k, out_score, out_idx, L.d_guard)
+                    : dae_title_rank(L.tctx, L.ctx, dtype, S.rows, p->V, p->H, t.ld_feat, tb, p->n_tracks, p->k, out_score, out_idx, L.d_guard);
         if (rc) return pfatal(p, rc, dae_last_error(L.tctx));
     } else {
         // the feed -> CSR and the seed lists (the playlist's own tracks) in ONE group of four launches (round 6: six + a wider feed)
@@ -294,15 +315,23 @@ int issue(dae_pipeline* p, Slot& S, int dtype)
         rc = dae_launch_coo32_to_csr_seeds(p->prep_ctx, reinterpret_cast<const int32_t*>(S.d_pos), S.d_val, 0, S.nnz, S.rows, p->V, S.d_rp,
                                            S.d_col, S.d_cval, S.d_status, p->n_tracks, S.d_srp, S.d_scol);
         if (rc) return pfatal(p, rc, dae_last_error(p->prep_ctx));
+        if (p->cat) {                                        // (the launch's nnz bounds its seeds: nothing is written at or past it)
+            rc = dae_catalogue_translate_seeds(p->prep_ctx, p->cat, S.d_srp, S.d_scol, S.rows, (int)S.nnz, S.d_lrp, S.d_lcnt, S.d_lscol);
+            if (rc) return pfatal(p, rc, dae_last_error(p->prep_ctx));
+        }
         PIPE_HIP(p, hipEventRecord(S.ev_prep, p->prep_stream));
         PIPE_HIP(p, hipStreamWaitEvent(L.stream, S.ev_prep, 0));
-        rc = dae_score_topk(L.ctx, S.d_rp, S.d_col, S.d_cval, p->W_enc, p->b_enc, p->V, p->H, S.rows, dtype, p->n_tracks,
-                            S.d_srp, S.d_scol, p->k, DAE_OUT_SCORE, out_score, out_idx);
+        rc = p->cat ? dae_score_topk_catalogue_local(L.ctx, S.d_rp, S.d_col, S.d_cval, p->W_enc, p->b_enc, p->V, p->H, S.rows, dtype, p->cat,
+                                                     S.d_lrp, S.d_lscol, p->k, DAE_OUT_SCORE, out_score, out_idx)
+                    : dae_score_topk(L.ctx, S.d_rp, S.d_col, S.d_cval, p->W_enc, p->b_enc, p->V, p->H, S.rows, dtype, p->n_tracks,
+                                     S.d_srp, S.d_scol, p->k, DAE_OUT_SCORE, out_score, out_idx);
         if (rc) return pfatal(p, rc, dae_last_error(L.ctx));
     }
     if (p->eval) {
         // the rows' metrics from the lists where they are (the answers came up with the feed: ev_h2d -> ev_prep -> this stream).
-        // A guard re-run comes through here again, so its records are the fp32 lists'.
+        // A guard re-run comes through here again, so its records are the fp32 lists'.  Catalogue mode: the lists have been
+        // mapped back, candidates and answers are both global columns (an answer outside the catalogue is never hit and counts
+        // in the denominators, as a -1 answer does).
         rc = dae_rank_metrics(L.ctx, out_idx, p->k, S.rows, p->k, S.d_arp, S.d_acol, p->d_disc, S.d_rec);
         if (rc) return pfatal(p, rc, dae_last_error(L.ctx));
     }
@@ -515,7 +544,7 @@ int dae_pipeline_destroy(dae_pipeline* p)
         if (S.ev_scored) (void)hipEventDestroy(S.ev_scored);
         if (S.ev_prep) (void)hipEventDestroy(S.ev_prep);
         void* outs[] = {S.d_idx, S.d_score, S.d_flags, S.d_rp, S.d_col, S.d_srp, S.d_scol, S.d_status, S.d_cval, S.t_h, S.t_feat, S.t_wt, S.t_wp,
-                        S.d_arp, S.d_acol, S.d_rec};
+                        S.d_arp, S.d_acol, S.d_rec, S.d_lrp, S.d_lcnt, S.d_lscol};
         for (void* q : outs) if (q) (void)hipFree(q);
         if (S.ev_h2d) (void)hipEventDestroy(S.ev_h2d);
         if (S.ev_gate) (void)hipEventDestroy(S.ev_gate);
@@ -846,6 +875,61 @@ int dae_pipeline_enable_eval(dae_pipeline* p, const double* disc_host, int64_t m
     return DAE_OK;
 }
 
+// Before the first submit: the catalogue's images in the place of the vocabulary's on every lane (lane 0 gathers and tiles them,
+// the others borrow: the catalogue's id travels with a shared image) and the slots' buffers for the translated seed lists.
+int dae_pipeline_set_catalogue(dae_pipeline* p, const dae_catalogue* cat)
+{
+    if (!p) return DAE_ERR_ARG;
+    if (!cat) return pfail(p, DAE_ERR_ARG, "null pointer");
+    std::unique_lock<std::mutex> lk(p->mu);
+    if (p->err_code) return p->err_code;
+    if (p->cat || p->next_ticket != 1) return pfail(p, DAE_ERR_STATE, "dae_pipeline_set_catalogue: once, before the first submit");
+    int cat_dev = -1, cat_n = 0, cat_tracks = 0;
+    dae_catalogue_shape(cat, &cat_dev, &cat_n, &cat_tracks);
+    if (cat_dev != p->device) return pfail(p, DAE_ERR_ARG, "dae_pipeline_set_catalogue: the catalogue lives on another device than the pipeline");
+    if (cat_tracks != p->n_tracks)
+        return pfail(p, DAE_ERR_ARG, "dae_pipeline_set_catalogue: the catalogue was created over another number of track columns (n_tracks) "
+                                     "than the pipeline ranks");
+    if (p->has_title && p->dtype == DAE_DTYPE_BF16_EXACT)
+        return pfail(p, DAE_ERR_ARG, "dae_pipeline_set_catalogue: a titled pipeline of DAE_DTYPE_BF16_EXACT does not rank inside a catalogue "
+                                     "(dae_title_score_catalogue); create it with DAE_DTYPE_F32, the same lists");
+    std::lock_guard<std::mutex> g(p->issue_mu);
+    DeviceGuard dev_guard(p->device);
+    const size_t rows = (size_t)p->group_rows, nz = (size_t)p->max_nnz;
+    bool ok = true;
+    for (Slot& S : p->slots)
+        ok = ok && hipMalloc(reinterpret_cast<void**>(&S.d_lrp), (rows + 1) * sizeof(int32_t)) == hipSuccess &&
+             hipMalloc(reinterpret_cast<void**>(&S.d_lcnt), rows * sizeof(int32_t)) == hipSuccess &&
+             hipMalloc(reinterpret_cast<void**>(&S.d_lscol), nz * sizeof(int32_t)) == hipSuccess;
+    if (!ok) return pfatal(p, DAE_ERR_NOMEM, "dae_pipeline_set_catalogue: allocation failed");
+    p->cat = cat;
+    Lane& L0 = p->lanes[0];
+    for (Lane& L : p->lanes) PIPE_HIP(p, hipStreamSynchronize(L.stream));
+    int rc = pack_image(p, L0.ctx, p->W_dec, p->b_dec, p->H, p->dtype);
+    if (rc) return pfatal(p, rc, dae_last_error(L0.ctx));
+    if (p->has_title) {
+        rc = pack_image(p, L0.tctx, p->tw.out_WT, p->tw.out_b, p->tw.ld_feat, p->dtype);
+        if (rc) return pfatal(p, rc, dae_last_error(L0.tctx));
+    }
+    PIPE_HIP(p, hipStreamSynchronize(L0.stream));
+    for (size_t i = 0; i < p->lanes.size(); ++i) {
+        Lane& L = p->lanes[i];
+        if (i > 0) {
+            rc = dae_share_decoder(L.ctx, L0.ctx, p->dtype);
+            if (rc) return pfatal(p, rc, dae_last_error(L.ctx));
+            if (p->has_title) {
+                rc = dae_share_decoder(L.tctx, L0.tctx, p->dtype);
+                if (rc) return pfatal(p, rc, dae_last_error(L.tctx));
+            }
+        }
+        // (an fp32 image a lane needs later -- a guard re-run, a paused exact mix -- is then the catalogue's: ensure_f32)
+        L.has_f32 = p->has_title && p->dtype == DAE_DTYPE_F32;
+        L.t_has_f32 = L.has_f32;
+    }
+    for (Lane& L : p->lanes) PIPE_HIP(p, hipStreamSynchronize(L.stream));
+    return DAE_OK;
+}
+
 static int poll_impl(dae_pipeline* p, int wait, uint64_t* ticket, const int32_t** idx, const float** score,
                      const dae_metric_rec** rec, int* n_rows, int* block)
 {
@@ -998,7 +1082,7 @@ int dae_pipeline_exact_margin(dae_pipeline* p, float scale)
     Lane& L0 = p->lanes[0];
     for (Lane& L : p->lanes) (void)hipStreamSynchronize(L.stream);
     int rc = dae_set_exact_margin(L0.ctx, scale);
-    if (!rc) rc = dae_prepack_decoder(L0.ctx, p->W_dec, p->b_dec, p->V, p->H, 0, p->V, p->dtype);
+    if (!rc) rc = pack_image(p, L0.ctx, p->W_dec, p->b_dec, p->H, p->dtype);
     if (rc) return pfail(p, rc, dae_last_error(L0.ctx));
     if (hipStreamSynchronize(L0.stream) != hipSuccess) return pfatal(p, DAE_ERR_HIP, "prepack failed");
     for (size_t i = 1; i < p->lanes.size(); ++i) {
@@ -1007,7 +1091,7 @@ int dae_pipeline_exact_margin(dae_pipeline* p, float scale)
     }
     if (p->has_title) {                                      // the title scorer's bounds as well (alpha_c, beta_c scale with the margin)
         rc = dae_set_exact_margin(L0.tctx, scale);
-        if (!rc) rc = dae_prepack_decoder(L0.tctx, p->tw.out_WT, p->tw.out_b, p->V, p->tw.ld_feat, 0, p->V, p->dtype);
+        if (!rc) rc = pack_image(p, L0.tctx, p->tw.out_WT, p->tw.out_b, p->tw.ld_feat, p->dtype);
         if (rc) return pfail(p, rc, dae_last_error(L0.tctx));
         if (hipStreamSynchronize(L0.stream) != hipSuccess) return pfatal(p, DAE_ERR_HIP, "prepack failed");
         for (size_t i = 1; i < p->lanes.size(); ++i) {

@@ -8,7 +8,7 @@ the same config.ini schema:
     [DAE] epochs batch lr reg_lambda hidden test_seed update_seed keep_prob input_kp firstN_range initval save
     [PRETRAIN] epochs batch lr reg_lambda save
     [TITLE] ... (parsed for compatibility; the title models are outside the scoring path)
-    [CHALLENGE] batch challenge_data result   (+ optional, this build only: allow_no_title, shard_exchange, shard_tau_exchange)
+    [CHALLENGE] batch challenge_data result   (+ optional, this build only: allow_no_title, shard_exchange, shard_tau_exchange, catalogue)
 
 Kept on purpose: `[DAE]` is always read first, so --pretrain inherits hidden / keep_prob /
 input_kp / firstN_range / test_seed from it (main.py:121, load-bearing per SURVEY App. A).
@@ -141,13 +141,16 @@ class Conf:
     def set_challenge_oonf(self):          # (sic) the reference's spelling, main.py:88
         os.makedirs(self.result_dir, exist_ok=True)
         sec = self._load('CHALLENGE')
-        # three OPTIONAL [CHALLENGE] keys this build adds (absent from the reference's files):
+        # four OPTIONAL [CHALLENGE] keys this build adds (absent from the reference's files):
         #   allow_no_title = True        score with the plain DAE when <[TITLE] save>.pkl is missing (default: error --
         #                                the reference fails there too; also an error while any playlist has no seeds)
         #   shard_exchange = allgather | alltoall    under torch.distributed.run: how the per-shard top-500 meet
         #   shard_tau_exchange = False   ... without the exchange of the shards' thresholds before their filter launches
         #                                (default True: one more collective of 4 bytes per row and rank, same result,
         #                                the ranks holding unpopular tracks stop keeping 10x the candidates)
+        #   catalogue = <file>           rank inside a catalogue: a text file in [BASE] data_dir, one track per line
+        #                                ('spotify:track:<id>' or the bare id; blank lines and '#' lines skipped) -- the
+        #                                submission holds tracks of that list only (main_challenge.read_catalogue)
         if 'allow_no_title' in sec:
             self.allow_no_title = _truth(sec['allow_no_title'])
         if 'shard_tau_exchange' in sec:
@@ -157,6 +160,8 @@ class Conf:
             if val not in ('allgather', 'alltoall'):
                 raise ValueError("[CHALLENGE] shard_exchange must be allgather or alltoall, not %r" % val)
             self.shard_exchange = val
+        if 'catalogue' in sec and sec['catalogue'].strip():
+            self.catalogue = sec['catalogue'].strip()
 
     set_challenge_conf = set_challenge_oonf
 

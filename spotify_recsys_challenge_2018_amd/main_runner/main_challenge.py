@@ -15,6 +15,10 @@ the threshold path (dae_decode_mix_term + dae_set_score_mix: no [batch, n_input]
 When it does not, the run fails like the reference's restore does, unless [CHALLENGE] allow_no_title = True
 (optional key of this build) asks for the plain DAE: titles_use = 0 reduces the mix exactly to it (App. B.6)
 on the weights the [TITLE] section names (DAEval); playlists without seeds still make that an error.
+
+[CHALLENGE] catalogue = <file> (optional key of this build): the submission is ranked inside a catalogue -- the tracks the
+file lists (`read_catalogue`) become `model.catalogue(columns)`, and the handle goes to `recommend_iter` / `recommend` as
+`catalogue=`; rows may then hold fewer than 500 tracks.
 """
 import datetime
 import os
@@ -61,6 +65,36 @@ def cand_to_uris(cand_idx, id2uri):
     return ['spotify:track:' + id2uri[str(int(i))] for i in cand_idx if i >= 0]
 
 
+def read_catalogue(path, id2uri):
+    """The catalogue file of [CHALLENGE] catalogue -> (columns, n_unknown).  Text, one track per line: 'spotify:track:<id>'
+    or the bare id (the values of the reader's `id2uri`); blank lines and lines starting with '#' are skipped, duplicates
+    collapse.  columns: the track columns the file names, ascending, each once (int64); n_unknown: distinct entries that
+    name no track of the vocabulary (counted, not an error).  An empty intersection is a ValueError naming the file.  Pure
+    Python: needs no device."""
+    import numpy as np
+    col_of = {u: int(i) for i, u in id2uri.items()}
+    prefix = 'spotify:track:'
+    seen, cols, n_unknown = set(), [], 0
+    with open(path) as f:
+        for line in f:
+            t = line.strip()
+            if not t or t.startswith('#'):
+                continue
+            if t.startswith(prefix):
+                t = t[len(prefix):]
+            if t in seen:
+                continue
+            seen.add(t)
+            c = col_of.get(t)
+            if c is None:
+                n_unknown += 1
+            else:
+                cols.append(c)
+    if not cols:
+        raise ValueError("[CHALLENGE] catalogue = %s: none of its %d entries is a track of the vocabulary" % (path, len(seen)))
+    return np.unique(np.asarray(cols, np.int64)), n_unknown
+
+
 class UriTable:
     """The same mapping for whole batches: the 'spotify:track:<uri>' string of every track id built ONCE (an object
     array), a batch of ranked ids turned into rows by one fancy index.  The per-id str() / dict lookup / concatenation of
@@ -89,9 +123,22 @@ class UriTable:
         return [self.table[r[r >= 0]].tolist() for r in idx]
 
 
+def _mixes_titles(conf, model):
+    """Will `run` score with the title mix (batches dealt to the ranks) rather than the plain DAE (vocabulary-sharded)?"""
+    if model is not None:
+        return bool(getattr(model, 'title_model', None))
+    return getattr(conf, 'char_model', None) == 'Char_CNN' and os.path.exists(str(getattr(conf, 'title_save', '')) + '.pkl')
+
+
 def run(conf, model=None):
     """`model`: None -> built from conf (DAE / DAE_title on the GPU); tests pass their own object with the same
     `recommend` / `shard_scoring` / `owned_rows` protocol."""
+    cat_file = getattr(conf, 'catalogue', None)
+    if cat_file and int(os.environ.get("WORLD_SIZE", "1")) > 1 and not _mixes_titles(conf, model):
+        # (every rank raises this, before the process group and long before shard_scoring)
+        raise ValueError("[CHALLENGE] catalogue = %s, and the plain DAE would run vocabulary-sharded over %s ranks: catalogue "
+                         "scoring is not vocabulary-sharded -- run one process, or with the title scorer (its batches are "
+                         "dealt to the ranks)" % (cat_file, os.environ["WORLD_SIZE"]))
     rank, world = _init_distributed(conf)
     reader = data_reader_challenge(data_dir=conf.data_dir, filename=conf.challenge_data,
                                    batch_size=conf.batch)
@@ -104,6 +151,13 @@ def run(conf, model=None):
 
     log_write(conf, '*' * 10)
     log_write(conf, '[challenge mode] start at ' + str(datetime.datetime.now()))
+
+    # [CHALLENGE] catalogue: read, and an empty intersection refused, before a model is built
+    cat_cols = None
+    if cat_file:
+        cat_path = conf.data_dir + '/' + cat_file              # (as challenge_data resolves)
+        cat_cols, cat_unknown = read_catalogue(cat_path, reader.id2uri)
+        log_write(conf, 'catalogue %s: %d track columns kept, %d unknown entries' % (cat_path, len(cat_cols), cat_unknown))
 
     use_titles = False
     exchange = getattr(conf, 'shard_exchange', 'allgather')
@@ -163,6 +217,12 @@ def run(conf, model=None):
         # (whole model on every GPU, no collective in the data path)
         log_write(conf, 'title model: batches partitioned over %d ranks' % world)
 
+    # the catalogue's handle: the kwarg exists only when the key is set (a model object without the parameter still works)
+    cat_kw = {}
+    if cat_cols is not None:
+        from ..models.DAEs import catalogue_columns
+        cat_kw = {'catalogue': model.catalogue(catalogue_columns(cat_cols, reader.num_tracks))}
+
     cands = []                  # (position in the file, [pid, uris...]) of the rows THIS rank holds results for
     # The challenge seeds ARE the playlist's tracks (reader: seed = playlists[i][0], the ids x_positions feeds), so the
     # model cuts the seed lists out of the input on the device; batches are streamed through recommend_iter (upload and
@@ -188,19 +248,19 @@ def run(conf, model=None):
     def results():
         if use_titles and hasattr(model, 'recommend_iter'):
             stream = ((xp, xo, SEEDS_FROM_INPUT, len(seed), t, [e[0] for e in te]) for xp, xo, seed, t, te in feeds())
-            for idx, _score in model.recommend_iter(stream, k=500, want_scores=False):
+            for idx, _score in model.recommend_iter(stream, k=500, want_scores=False, **cat_kw):
                 yield idx
         elif use_titles:
             for x_positions, x_ones, seed, titles, titles_exist in feeds():
                 yield model.recommend(x_positions, x_ones, seed, k=500, n_rows=len(seed), titles=titles,
-                                      titles_use=[t[0] for t in titles_exist])[0]
+                                      titles_use=[t[0] for t in titles_exist], **cat_kw)[0]
         elif hasattr(model, 'recommend_iter'):
             stream = ((xp, xo, SEEDS_FROM_INPUT, len(seed)) for xp, xo, seed, _t, _e in feeds())
-            for idx, _score in model.recommend_iter(stream, k=500, want_scores=False):
+            for idx, _score in model.recommend_iter(stream, k=500, want_scores=False, **cat_kw):
                 yield idx
         else:                   # a model object without the streaming entry point (tests)
             for x_positions, x_ones, seed, _t, _e in feeds():
-                yield model.recommend(x_positions, x_ones, seed, k=500, n_rows=len(seed))[0]
+                yield model.recommend(x_positions, x_ones, seed, k=500, n_rows=len(seed), **cat_kw)[0]
 
     uris = UriTable(reader.id2uri, reader.num_tracks)
     # one full collection now and the survivors frozen: the loop allocates a few tracked objects per batch, and the
@@ -227,6 +287,8 @@ def run(conf, model=None):
                 cands = sorted((c for part in parts for c in part), key=lambda c: c[0])
         dist.barrier()
     total_cands = [c for _pos, c in cands]
+    if cat_kw and hasattr(cat_kw['catalogue'], 'close'):
+        cat_kw['catalogue'].close()
     if rank == 0:
         with open(conf.result, 'wb') as f:                 # main_challenge.py:95-96
             pickle.dump(total_cands, f)

@@ -225,7 +225,8 @@ class CatalogueHandle:
     never re-tiled when full and catalogue calls alternate.  The images follow the model's weights: after a parameter change
     (`_mark_dirty` / the title model's `_params_gen`) the next call re-packs.  Memory per dtype in use: n x hidden x 4 (fp32) or
     2 (bf16) bytes plus bounds (exact_bf16: the fp32 rows as well), the same for the title rows; 4 (n + n_tracks) bytes for the
-    column tables.  `close()` frees everything."""
+    column tables.  The streamed loops (`recommend_iter` / `evaluate_iter(..., catalogue=handle)`) run on pipelines in catalogue mode
+    that hold images of their own; the handle remembers them.  `close()` closes those pipelines first, then frees everything."""
 
     def __init__(self, model, cols):
         import torch
@@ -237,6 +238,19 @@ class CatalogueHandle:
         self.title_ctx = _lib.Context(model.device_index) if model._title_scorer() is not None else None
         self._packed, self._title_packed = {}, {}        # image slot -> (weights generation, holds the exact mode's bounds)
         self._exact_title_said = False
+        self._pipes = []                                 # the streamed loops' pipelines in catalogue mode (stream_loop.pipeline_for)
+
+    def _title_dtype(self, dtype):
+        """Arithmetic of a titled launch inside this catalogue: exact_bf16 has no catalogue mix and runs on the fp32 kernels (the
+        lists it promises), said once per handle."""
+        if dtype != _lib.DAE_DTYPE_BF16_EXACT:
+            return dtype
+        if not self._exact_title_said:
+            self._exact_title_said = True
+            import sys
+            print("[dae] decode_dtype = exact_bf16: the exact title mix does not rank inside a catalogue; titled catalogue "
+                  "calls run on the fp32 kernels (same lists, slower)", file=sys.stderr)
+        return _lib.DAE_DTYPE_F32
 
     @staticmethod
     def _fresh(packed, slot, gen, dtype):
@@ -266,6 +280,20 @@ class CatalogueHandle:
 
     def close(self):
         if getattr(self, "cat", None) is not None:
+            # the pipelines read the column tables: gone first, and out of the model's cache.  One whose result arrays are still
+            # alive in the caller's hands only stops taking feeds (`Pipeline.close`); it has nothing in flight once drained
+            for pipe in self._pipes:
+                if pipe.h is not None:
+                    try:
+                        pipe.flush()
+                        while pipe.pending and (pipe.poll_eval(True) if pipe.eval else pipe.poll(True, copy=True)) is not None:
+                            pass
+                    except _lib.DaeError:
+                        pass
+                    pipe.close()
+            for key in [key for key, (_gen, pipe) in self.model._pipes.items() if pipe in self._pipes]:
+                self.model._pipes.pop(key, None)
+            self._pipes = []
             self.cat.close()
             self.cat = None
             for c in (self.ctx, self.title_ctx):
@@ -665,8 +693,9 @@ class DAE_tied:
         columns: any integer sequence or array of track columns, ascending, each once; an unsorted, repeated, negative or
         non-track id or an empty list raises ValueError naming the offender, before anything touches the device.  The handle
         (CatalogueHandle) owns its contexts and images and follows this model's weights; `handle.close()` frees it.
-        Not built: `recommend_iter` / `evaluate_iter` / the pipeline, `rank_candidates` inside a catalogue, vocabulary shards (a
-        model with a scoring shard is refused here) and a config.ini key."""
+        `recommend_iter`, `evaluate_iter` and `rank_candidates` take the handle as `catalogue=` too, and `main.py --challenge`
+        reads one from `[CHALLENGE] catalogue`.  Not built: vocabulary shards (a model with a scoring shard is refused here), a
+        catalogue key for `main_train.py eval`, deep k in the loops."""
         if self._score_shard is not None:
             raise _lib.DaeError("catalogue scoring is not vocabulary-sharded: this model has a scoring shard (shard_scoring); "
                                 "rank a catalogue on a model that holds the whole decoder")
@@ -832,11 +861,26 @@ class DAE_tied:
         self._check_feed()
         return self._cand_result(values, candidates, rp)
 
-    def rank_candidates(self, x_positions, x_ones, candidates, seeds, k=500, n_rows=None):
+    def _cand_in_catalogue(self, candidates, n_rows, catalogue):
+        """The rows' candidate lists restricted to the catalogue's columns, on the host (the call de-duplicates there anyway):
+        per row the sorted unique candidates that `handle.columns` holds.  Ids out of range are refused as without a catalogue."""
+        if catalogue is None:
+            return candidates
+        self._catalogue_begin(catalogue)
+        n = self.n_batch if n_rows is None else n_rows
+        if n > self.n_batch:
+            raise ValueError("n_rows = %d exceeds the model's batch of %d" % (n, self.n_batch))
+        rp, col = candidates_to_csr(candidates, n, self.n_input, unique=True)
+        keep = np.isin(col, catalogue.columns)
+        return [col[rp[r]:rp[r + 1]][keep[rp[r]:rp[r + 1]]] for r in range(len(rp) - 1)]
+
+    def rank_candidates(self, x_positions, x_ones, candidates, seeds, k=500, n_rows=None, catalogue=None):
         """`recommend` restricted to the caller's candidates: per row the k best of its candidate columns (each once, however
         often it is listed; seeds removed), logit descending then column ascending -> (idx [n_rows, k] int32 with -1 padding,
         score [n_rows, k] float32, -inf beside a -1).  seeds: as `recommend` takes them, SEEDS_FROM_INPUT included.  With
-        candidates = range(n_tracks) this is `recommend`."""
+        candidates = range(n_tracks) this is `recommend`.  catalogue: a handle of `catalogue(columns)` -- only the row's
+        candidates that lie in the catalogue are ranked (a row with none comes back all -1)."""
+        candidates = self._cand_in_catalogue(candidates, n_rows, catalogue)
         n_rows, rp, col, cand, status = self._cand_begin(candidates, n_rows, unique=True)
         key, csr = self._cand_scores(x_positions, x_ones, cand, int(col.size), _lib.DAE_OUT_LOGIT, status)
         return self._cand_rank(cand, rp, key, seeds, csr, k, n_rows, _lib.DAE_OUT_SCORE)
@@ -852,13 +896,18 @@ class DAE_tied:
         self._check_feed()
         return res
 
-    def recommend_iter(self, feeds, k=500, dtype=None, want_scores=True):
+    def recommend_iter(self, feeds, k=500, dtype=None, want_scores=True, catalogue=None):
         """`recommend` over a stream of batches (`_recommend_iter`).  k <= 1024: the pipeline behind the loop keeps that limit, and a
-        larger k raises ValueError here, before a pipeline is created."""
+        larger k raises ValueError here, before a pipeline is created.
+        catalogue: a handle of `catalogue(columns)` -- every feed gets what `recommend(feed, catalogue=handle)` returns for it
+        alone, bit for bit, from a pipeline in catalogue mode (dae_pipeline_set_catalogue); feeds the pipeline
+        does not take go through that call, in order."""
         _refuse_deep_k(k, "recommend_iter")
-        return self._recommend_iter(feeds, k, dtype, want_scores)
+        if catalogue is not None:
+            self._catalogue_begin(catalogue)
+        return self._recommend_iter(feeds, k, dtype, want_scores, catalogue)
 
-    def _recommend_iter(self, feeds, k, dtype, want_scores):
+    def _recommend_iter(self, feeds, k, dtype, want_scores, catalogue=None):
         """`recommend` over a stream of batches with the host and the device overlapped (the loop of
         main_challenge.py:72-93 / main_train.py:62-96): `feeds` yields (x_positions, x_ones, seeds, n_rows) (DAE_title:
         + titles, titles_use); the generator yields (idx [n_rows,k], score [n_rows,k] or None) in order, one pair per feed.
@@ -867,7 +916,7 @@ class DAE_tied:
         pad to 256 alone), three library contexts take the launches in turn, the CSR of launch n + 1 is built while launch n
         scores, the lists leave through the copy engine.  Rows are scored independently: every feed gets the bits
         `recommend` returns for it alone (tests/test_gpu_stream_loop.py)."""
-        if self._score_shard is not None:
+        if self._score_shard is not None:                             # (`_catalogue_begin` has refused a catalogue here)
             for f in feeds:                                           # the exchange is a collective: no run-ahead
                 x_positions, x_ones, seeds, n_rows = f[:4]
                 idx, score = self.recommend(x_positions, x_ones, seeds, k=k, n_rows=n_rows, dtype=dtype)
@@ -876,19 +925,25 @@ class DAE_tied:
         # THE LOOP LIVES IN THE LIBRARY (include/dae_hip.h dae_pipeline_*): stream_loop.py copies feeds in and hands views of
         # pinned result blocks out; what the pipeline does not take goes through `recommend` feed by feed, in order.
         if self.device_csr:
-            yield from self._stream(feeds, k, self._dtype_of(dtype), want_scores)
+            yield from self._stream(feeds, k, self._dtype_of(dtype), want_scores, catalogue=catalogue)
             return
         for f in feeds:                  # (device_csr = False: host-built CSRs -- the per-batch call)
-            idx, score = self._recommend_feed(f, k, dtype)
+            idx, score = self._recommend_feed(f, k, dtype, catalogue)
             yield idx, (score if want_scores else None)
 
-    def evaluate_iter(self, feeds, k=500, dtype=None):
+    def evaluate_iter(self, feeds, k=500, dtype=None, catalogue=None):
         """The evaluation loop with the metrics computed on the device (`_evaluate_iter`).  k <= 1024 (the pipeline and the metrics
-        kernel): a larger k raises ValueError here, before a pipeline is created."""
+        kernel): a larger k raises ValueError here, before a pipeline is created.
+        catalogue: a handle of `catalogue(columns)` -- the records are those of `recommend(feed, catalogue=handle)`'s lists.  The
+        metrics see global columns (they run after the lists have been mapped back): an answer OUTSIDE the catalogue can never be
+        hit and counts in the denominators, exactly as a -1 answer does.  A caller who wants recall within the catalogue filters
+        the answers on the host before feeding them."""
         _refuse_deep_k(k, "evaluate_iter")
-        return self._evaluate_iter(feeds, k, dtype)
+        if catalogue is not None:
+            self._catalogue_begin(catalogue)
+        return self._evaluate_iter(feeds, k, dtype, catalogue)
 
-    def _evaluate_iter(self, feeds, k, dtype):
+    def _evaluate_iter(self, feeds, k, dtype, catalogue=None):
         """The evaluation loop (main_train.py:48-100) with the metrics computed on the device: `feeds` yields
         (feed, answers) -- `feed` what `recommend_iter` takes, `answers` one id list per row of the feed (the reader's
         `test_answer`: ints, -1 and duplicates allowed) -- and the generator yields, per feed and in order, the rows' records
@@ -899,29 +954,33 @@ class DAE_tied:
         the row's k indices.  Every other case (a vocabulary-sharded model, device_csr = False, explicit seed lists, a feed
         or its answers larger than a launch slot) goes feed by feed through `recommend` and `metrics.rank_records`."""
         if self._score_shard is None and self.device_csr:
-            yield from self._stream(feeds, k, self._dtype_of(dtype), False, eval_mode=True)
+            yield from self._stream(feeds, k, self._dtype_of(dtype), False, eval_mode=True, catalogue=catalogue)
             return
         from ..utils.metrics import rank_records
         for f, answers in feeds:
-            yield rank_records(self._recommend_feed(f, k, dtype)[0], answers)
+            yield rank_records(self._recommend_feed(f, k, dtype, catalogue)[0], answers)
 
-    def _recommend_feed(self, f, k, dtype):
+    def _recommend_feed(self, f, k, dtype, catalogue=None):
         """`recommend` of one feed of a loop.  Only a DAE_title takes the title items of a 5- or 6-item feed; a plain DAE scores
         the feed's first four items and ignores the rest."""
         kw = {"titles": f[4], "titles_use": f[5] if len(f) > 5 else None} if len(f) > 4 and isinstance(self, DAE_title) else {}
+        if catalogue is not None:
+            kw["catalogue"] = catalogue
         return self.recommend(f[0], f[1], f[2], k=k, n_rows=f[3], dtype=dtype, **kw)
 
-    def _stream(self, feeds, k, dtype, want_scores, eval_mode=False):
-        """`stream_loop.stream` over this model's cached pipeline."""
+    def _stream(self, feeds, k, dtype, want_scores, eval_mode=False, catalogue=None):
+        """`stream_loop.stream` over this model's cached pipeline (catalogue: the one in that handle's catalogue mode)."""
         scorer = self._title_scorer()
         if scorer is not None:
+            if catalogue is not None:            # (a titled exact_bf16 pipeline is refused inside a catalogue: fp32, said once)
+                dtype = catalogue._title_dtype(dtype)
             dtype = _title_dtype(dtype, self)
-        key, pipe = stream_loop.pipeline_for(self, scorer, dtype, k, want_scores, eval_mode)
+        key, pipe = stream_loop.pipeline_for(self, scorer, dtype, k, want_scores, eval_mode, catalogue)
 
         def on_guard(n_fb):
             self._guard_fell_back("exact_bf16: the bound guard fired in %d launch(es) of the streamed loop: they were re-scored "
                                   "with the fp32 kernels" % n_fb, n_fb)
-        return stream_loop.stream(pipe, feeds, lambda f: self._recommend_feed(f, k, dtype), self.n_batch, want_scores, eval_mode,
+        return stream_loop.stream(pipe, feeds, lambda f: self._recommend_feed(f, k, dtype, catalogue), self.n_batch, want_scores, eval_mode,
                                   isinstance(self, DAE_title), on_guard if dtype == _lib.DAE_DTYPE_BF16_EXACT else None,
                                   self._pipes, key)
 
@@ -1257,9 +1316,9 @@ class DAE_title(DAE):
             self.title_model.ctx.bind_stream()
             self._title_sharded.sync_title_params(self.title_model)
 
-    def _stream(self, feeds, k, dtype, want_scores, eval_mode=False):
+    def _stream(self, feeds, k, dtype, want_scores, eval_mode=False, catalogue=None):
         self.sync_params()            # (the pipeline copies the title variables: current ones)
-        return DAE._stream(self, feeds, k, dtype, want_scores, eval_mode)
+        return DAE._stream(self, feeds, k, dtype, want_scores, eval_mode, catalogue)
 
     def _row_sums(self, x_positions, x_ones):
         rp, _c, v = coo_to_csr(x_positions, x_ones, self.n_batch, self.n_input)
@@ -1508,9 +1567,11 @@ class DAE_title(DAE):
         self._check_feed()
         return self._cand_result(values, candidates, rp)
 
-    def rank_candidates(self, x_positions, x_ones, candidates, seeds, k=500, n_rows=None, titles=None, titles_use=None):
-        """`DAE.rank_candidates`; with titles in use the candidates are ranked by the mixed score (score = y), as the titled
-        `recommend` ranks the whole track range."""
+    def rank_candidates(self, x_positions, x_ones, candidates, seeds, k=500, n_rows=None, titles=None, titles_use=None,
+                        catalogue=None):
+        """`DAE.rank_candidates` (catalogue= included); with titles in use the candidates are ranked by the mixed score (score = y),
+        as the titled `recommend` ranks the whole track range."""
+        candidates = self._cand_in_catalogue(candidates, n_rows, catalogue)
         if titles is None or titles_use is None or not np.any(np.asarray(titles_use)):
             return DAE.rank_candidates(self, x_positions, x_ones, candidates, seeds, k=k, n_rows=n_rows)
         n_rows, rp, col, cand, status = self._cand_begin(candidates, n_rows, unique=True)
@@ -1580,14 +1641,7 @@ class DAE_title(DAE):
         n columns, indices mapped back).  Encode, mixing weights and title features are the model's own launches.  fp32 and
         plain bf16; exact_bf16 has no catalogue mix and runs on the fp32 kernels (the lists it promises), said once."""
         import torch
-        dtype = self._dtype_of(dtype)
-        if dtype == _lib.DAE_DTYPE_BF16_EXACT:
-            if not cat._exact_title_said:
-                cat._exact_title_said = True
-                import sys
-                print("[dae] decode_dtype = exact_bf16: the exact title mix does not rank inside a catalogue; titled catalogue "
-                      "calls run on the fp32 kernels (same lists, slower)", file=sys.stderr)
-            dtype = _lib.DAE_DTYPE_F32
+        dtype = cat._title_dtype(self._dtype_of(dtype))
         tm = self.title_model
         if cat.title_ctx is None:
             raise _lib.DaeError("catalogue: the handle was made before the title scorer was fitted; make a new one")

@@ -133,10 +133,14 @@ def stream(pipe, feeds, fallback, n_batch, want_scores=True, eval_mode=False, mi
             pipe.close()
 
 
-def pipeline_for(model, scorer, dtype, k, want_scores, eval_mode=False):
+def pipeline_for(model, scorer, dtype, k, want_scores, eval_mode=False, catalogue=None):
     """-> (key, pipeline) out of `model._pipes`: created on first use, and again after the weights, the title variables of
-    `scorer` (the Char_CNN its launches mix in, or None) or the exact margin changed."""
+    `scorer` (the Char_CNN its launches mix in, or None) or the exact margin changed.  catalogue: an open CatalogueHandle of
+    `model` -> a pipeline in catalogue mode (`Pipeline.set_catalogue`: images of its own, gathered from the model's current
+    weights); the handle remembers it and closes it before it frees its column tables."""
     key = (int(dtype), int(k), bool(want_scores), model.n_batch) + (("eval",) if eval_mode else ())
+    if catalogue is not None:
+        key += (("catalogue", id(catalogue)),)
     # (dae_set_exact_margin on the model's contexts -- the guard's test hook -- reaches the pipeline's own images as well)
     margins = [getattr(c, "_exact_margin", 1.0) for c in ([model.ctx] + ([] if scorer is None else [scorer.ctx]))]
     margin = next((m_ for m_ in margins if m_ != 1.0), 1.0)
@@ -170,6 +174,13 @@ def pipeline_for(model, scorer, dtype, k, want_scores, eval_mode=False):
                              model.biases["decoder_b"], model.n_tracks, dtype=dtype, k=k, group_rows=group,
                              max_nnz=max(1 << 18, group * 1024), lanes=int(model.n_lanes or 3), want_scores=want_scores,
                              device_index=model.device_index, title=scorer)
+        if catalogue is not None:
+            try:
+                pipe.set_catalogue(catalogue.cat)
+            except _lib.DaeError:
+                pipe.close()
+                raise
+            catalogue._pipes = [q for q in catalogue._pipes if q.h is not None] + [pipe]
         if margin != 1.0 and dtype == _lib.DAE_DTYPE_BF16_EXACT:
             pipe.exact_margin(margin)
         if eval_mode:            # (the challenge's playlists hold at most 250 tracks; a feed with more answers than a launch
