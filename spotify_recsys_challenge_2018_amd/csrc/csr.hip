@@ -504,7 +504,7 @@ int dae_launch_coo_to_csr(dae_ctx* ctx, const int64_t* positions, const float* v
                                       0, nullptr, nullptr);
 }
 
-// the drivers' loop (pipeline.hip): 32-bit (row, col) pairs as dae_pipeline stages them, and the seed lists (the playlist's own
+// the drivers' loop (pipeline_issue.hip): 32-bit (row, col) pairs as dae_pipeline stages them, and the seed lists (the playlist's own
 // tracks: columns < n_tracks) from the same four launches
 int dae_launch_coo32_to_csr_seeds(dae_ctx* ctx, const int32_t* positions, const float* values, int values_broadcast,
                                   int64_t nnz, int n_rows, int n_cols, int32_t* row_ptr, int32_t* col, float* val,

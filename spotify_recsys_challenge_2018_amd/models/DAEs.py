@@ -429,7 +429,7 @@ class DAE_tied:
         and blocks the host until it has happened; on the compute stream that means "until everything queued before
         it has run", so the training loop could never get ahead of the GPU (0.25 ms per feed measured).  On its own
         stream the copy waits for earlier copies only; the compute stream waits for its event.  (The scoring loop
-        stages its feeds inside the library: csrc/pipeline.hip.)"""
+        stages its feeds inside the library: csrc/pipeline_stage.h.)"""
         import torch
         src = torch.from_numpy(np.ascontiguousarray(a))
         dev = torch.device("cuda", self.device_index)
@@ -911,7 +911,7 @@ class DAE_tied:
         """`recommend` over a stream of batches with the host and the device overlapped (the loop of
         main_challenge.py:72-93 / main_train.py:62-96): `feeds` yields (x_positions, x_ones, seeds, n_rows) (DAE_title:
         + titles, titles_use); the generator yields (idx [n_rows,k], score [n_rows,k] or None) in order, one pair per feed.
-        The loop itself is the library's (`dae_pipeline_*`, csrc/pipeline.hip): consecutive feeds are scored in
+        The loop itself is the library's (`dae_pipeline_*`, csrc/pipeline.hip + pipeline_issue.hip): consecutive feeds are scored in
         ONE launch of up to 1024 rows (2048 in the bf16 modes; `_coalesce_count`: the reference's batches of 150 / 250 rows
         pad to 256 alone), three library contexts take the launches in turn, the CSR of launch n + 1 is built while launch n
         scores, the lists leave through the copy engine.  Rows are scored independently: every feed gets the bits

@@ -1,5 +1,6 @@
 """GPU (-m gpu): the streamed loops inside a catalogue -- `recommend_iter` / `evaluate_iter(..., catalogue=handle)` on a pipeline in
-catalogue mode (include/dae_hip.h dae_pipeline_set_catalogue; csrc/pipeline.hip, csrc/catalogue.hip) and
+catalogue mode (include/dae_hip.h dae_pipeline_set_catalogue; csrc/pipeline.hip, csrc/pipeline_issue.hip,
+csrc/catalogue.hip) and
 `rank_candidates(..., catalogue=handle)`.
 
 The expected lists of a feed are `model.recommend(feed, catalogue=handle)` of that feed ALONE -- the call tests/test_gpu_catalogue.py

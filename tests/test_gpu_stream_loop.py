@@ -270,3 +270,95 @@ def test_native_pipeline_feed_semantics_duplicates_long_rows_and_bad_indices(tmp
         assert np.array_equal(gi, want[3][0])
     finally:
         pipe.close()
+
+
+def test_pipeline_closes_with_launches_in_flight(tmp_path):
+    """dae_pipeline_destroy with launches queued, running or waiting to be polled, for every optional group of buffers a pipeline
+    can own: a plain pipeline, one in evaluation mode, one in catalogue mode, a titled one.  Six feeds, flush, none or one of them
+    polled, close(): no error.  A fresh pipeline of the same kind then gives every feed, bit for bit, what `recommend` gives for
+    it alone (the evaluation pipeline: `rank_records` of those lists)."""
+    import torch
+    from oracle import title_numpy as tn
+    from spotify_recsys_challenge_2018_amd.models.DAEs import DAE_title
+    from spotify_recsys_challenge_2018_amd.models.title_models import get_model
+    from spotify_recsys_challenge_2018_amd.utils import metrics as met
+    nt, na, H, k, B, L, n_char = 6000, 1000, 64, 100, 8, 25, 41
+    V = nt + na
+
+    class C:
+        lr = 0.01; reg_lambda = 0.0; charsize = n_char; char_model = 'Char_CNN'; save = str(tmp_path / "unused")
+        initval = "NULL"; title_lr = 0.002; batch = B; n_input = V; n_output = V; n_tracks = nt; hidden = H
+        char_emb = 25; filter_size = [3, 5]; filter_num = 40; strmaxlen = L; DAEval = str(tmp_path / "w_dae")
+    with open(C.DAEval, "wb") as f:
+        W_enc, b_enc, W_dec, b_dec = make_weights(V, H, seed=4, bias="zipf", n_tracks=nt)
+        pickle.dump([W_enc, W_dec, b_enc, b_dec], f)
+    mt = get_model(C())
+    mt.fit(tn.make_params(n_char, C.char_emb, C.filter_size, C.filter_num, V, seed=4))
+    m = DAE_title(C(), mt); m.fit()
+    rng = np.random.default_rng(11)
+    feeds = [make_playlists(B, nt, na, seed=300 + i)[:2] for i in range(6)]
+    titles = [rng.integers(0, n_char, (B, L)).astype(np.int32) for _ in feeds]
+    use = [(np.arange(B) % 3 != i % 3).astype(np.float32) for i in range(len(feeds))]
+    cols = np.arange(0, nt, 3, dtype=np.int32)                  # the catalogue: every third track column
+    h = m.catalogue(cols)
+    ctx = _lib.Context(0)
+    cat = _lib.Catalogue(ctx, torch.from_numpy(cols).cuda(), nt)
+    want = {"plain": [m.recommend(p, o, SEEDS_FROM_INPUT, k=k, dtype="f32") for p, o in feeds],
+            "catalogue": [m.recommend(p, o, SEEDS_FROM_INPUT, k=k, dtype="f32", catalogue=h) for p, o in feeds],
+            "titled": [m.recommend(p, o, SEEDS_FROM_INPUT, k=k, dtype="f32", titles=t, titles_use=u)
+                       for (p, o), t, u in zip(feeds, titles, use)]}
+    want["eval"] = want["plain"]
+    assert not np.array_equal(want["catalogue"][0][0], want["plain"][0][0]) and not np.array_equal(want["titled"][0][0], want["plain"][0][0])
+    # the evaluation feeds' answers: the head of the row's own list (hits), tracks at random, a -1 and a duplicate
+    answers = [[row[:5].tolist() + rng.integers(0, nt, 7).tolist() + [-1, int(row[0])] for row in wi] for wi, _ws in want["plain"]]
+    weights = (m.weights["encoder_h"], m.biases["encoder_b"], m.weights["decoder_h"], m.biases["decoder_b"], nt)
+
+    def make(kind):
+        pipe = _lib.Pipeline(*weights, dtype=_lib.DAE_DTYPE_F32, k=k, group_rows=2 * B, max_nnz=1 << 14, lanes=2,
+                             title=m._title_scorer() if kind == "titled" else None)
+        if kind == "eval":
+            pipe.enable_eval(max_answers=1 << 12)
+        if kind == "catalogue":
+            pipe.set_catalogue(cat)
+        return pipe
+
+    def submit_all(pipe, kind):
+        for i, (p, o) in enumerate(feeds):
+            kw = {}
+            if kind == "titled":
+                kw = {"titles": titles[i], "titles_use": use[i]}
+            if kind == "eval":
+                kw = {"answers": (np.cumsum([0] + [len(a) for a in answers[i]]).astype(np.int32), np.concatenate(answers[i]).astype(np.int32))}
+            assert pipe.submit(p, o, B, **kw)
+        pipe.flush()
+
+    def poll(pipe, kind):
+        return pipe.poll_eval(True) if kind == "eval" else pipe.poll(True, copy=True)
+    try:
+        for kind in ("plain", "eval", "catalogue", "titled"):
+            for n_polled in (0, 1):
+                pipe = make(kind)
+                try:
+                    submit_all(pipe, kind)
+                    for _ in range(n_polled):
+                        assert poll(pipe, kind) is not None
+                finally:
+                    pipe.close()                                # three launches staged, queued, running or scored
+                assert pipe.h is None
+            pipe = make(kind)
+            try:
+                submit_all(pipe, kind)
+                got = [poll(pipe, kind) for _ in feeds]
+                assert poll(pipe, kind) is None and pipe.stats()["launches"] == 3
+            finally:
+                pipe.close()
+            for i, (g, (wi, ws)) in enumerate(zip(got, want[kind])):
+                if kind == "eval":
+                    rec = met.rank_records(wi, answers[i])
+                    assert g.dtype == met.RECORD_DTYPE and all(np.array_equal(g[f], rec[f]) for f in ("hits_r", "first", "m", "n_answer"))
+                    assert np.array_equal(g["dcg"].view(np.uint64), rec["dcg"].view(np.uint64)) and int(g["hits_r"].sum()) > 0
+                else:
+                    assert np.array_equal(g[0], wi) and np.array_equal(g[1].view(np.uint32), ws.view(np.uint32)), (kind, i)
+    finally:
+        cat.close(); ctx.close(); h.close()
+        m.close_pipelines()
