@@ -263,6 +263,13 @@ int dae_tile_bounds_read(dae_ctx* ctx, float* ub_out, int cap_tiles, int* ntiles
  *   dae_sample_skip_read: out3 = {sample launches that could skip, wave-tiles they planned (sum), wave-tiles they decoded
  *                         (sum)} since the last read; resets the counters; synchronises the ctx stream. */
 int dae_sample_skip_read(dae_ctx* ctx, uint64_t out3[3]);
+/* Where such a sample ran, the threshold launch that builds the live lists knows, per half row group, D >= the d of its rows and
+ * tau_safe <= their thresholds, and the context keeps max over the filter launch's tiles of A_t + d M_t on a grid of d.  A row
+ * group these prove to have NO live tile gets its empty list without the hand-off between the rows' workgroups; every other
+ * group takes it as before.  Lists, counts and the counters of dae_filter_skip_read are the same either way.
+ *   dae_live_proof_read: *groups_proved = row groups whose live list was proved empty since the last read; resets the counter;
+ *                        synchronises the ctx stream. */
+int dae_live_proof_read(dae_ctx* ctx, uint64_t* groups_proved);
 /* The thresholds the context's last dae_score_topk / dae_decode_topk (its last slab of rows) computed and gave its own filter
  * launch: tau_out[0 .. B) on the HOST (what dae_score_topk_begin returns to its caller).  Synchronises the ctx stream. */
 int dae_last_tau_read(dae_ctx* ctx, float* tau_out, int B);

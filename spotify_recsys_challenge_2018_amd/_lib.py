@@ -21,7 +21,7 @@ EXPORTS = [
     "dae_scratch_bytes", "dae_profile_enable", "dae_profile_read", "dae_profile_kernel", "dae_clock_probe", "dae_last_plan",
     "dae_coo_to_csr", "dae_seeds_from_csr", "dae_train_set_create", "dae_train_set_destroy", "dae_train_batch", "dae_train_set_attach_titles", "dae_train_titles", "dae_encode", "dae_prepack_decoder", "dae_prepack_decoder_rows", "dae_share_decoder", "dae_exact_bounds",
     "dae_exact_guard_read", "dae_exact_guard_words", "dae_exact_guard_snapshot", "dae_exact_stats_read", "dae_set_exact_margin", "dae_set_exact_margin_range", "dae_set_exact_audit", "dae_exact_audit_read",
-    "dae_set_filter_skip", "dae_filter_skip_read", "dae_filter_skip_last", "dae_tile_bounds_read", "dae_sample_skip_read", "dae_last_tau_read", "dae_decode_dense", "dae_decode_topk",
+    "dae_set_filter_skip", "dae_filter_skip_read", "dae_filter_skip_last", "dae_tile_bounds_read", "dae_sample_skip_read", "dae_live_proof_read", "dae_last_tau_read", "dae_decode_dense", "dae_decode_topk",
     "dae_score_topk", "dae_score_topk_begin", "dae_score_topk_finish", "dae_topk_dense", "dae_topk_merge", "dae_set_train_dtype", "dae_train_forward_backward",
     "dae_train_shard_encode", "dae_train_shard_decode", "dae_train_shard_finish", "dae_title_features", "dae_title_prepack_features",
     "dae_mix_scores", "dae_decode_mix_term", "dae_set_score_mix", "dae_mix_topk_exact", "dae_mix_exact_shape_ok", "dae_title_score_exact", "dae_title_score", "dae_row_sums", "dae_mix_weights", "dae_title_loss_backward", "dae_title_loss_backward_cols", "dae_title_conv_backward", "dae_adam_step",
@@ -97,6 +97,7 @@ def load():
     lib.dae_filter_skip_read.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     lib.dae_filter_skip_last.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), c_int, ctypes.POINTER(c_int)]
     lib.dae_sample_skip_read.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
+    lib.dae_live_proof_read.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     lib.dae_last_tau_read.argtypes = [vp, ctypes.c_void_p, c_int]
     lib.dae_tile_bounds_read.argtypes = [vp, vp, c_int, ctypes.POINTER(c_int)]
     lib.dae_decode_dense.argtypes = [vp, vp, c_int, c_int, c_int, c_int, vp, c_i64]
@@ -472,6 +473,13 @@ class Context:
         a = (ctypes.c_uint64 * 3)()
         self.check(self.lib.dae_sample_skip_read(self.h, a))
         return {"launches": int(a[0]), "planned": int(a[1]), "decoded": int(a[2])}
+
+    def live_proof_read(self):
+        """Row groups whose live list the threshold launch proved empty (no hand-off between the rows' workgroups:
+        include/dae_hip.h) since the last read; resets; synchronises."""
+        a = ctypes.c_uint64(0)
+        self.check(self.lib.dae_live_proof_read(self.h, ctypes.byref(a)))
+        return int(a.value)
 
     def last_tau(self, B):
         """The thresholds of the context's last score_topk / decode_topk as a float32 array [B] (dae_last_tau_read); synchronises."""

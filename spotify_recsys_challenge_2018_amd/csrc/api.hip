@@ -324,6 +324,21 @@ int dae_filter_skip_read(dae_ctx* ctx, uint64_t out3[3])
     return DAE_OK;
 }
 
+int dae_live_proof_read(dae_ctx* ctx, uint64_t* groups_proved)
+{
+    if (!ctx) return DAE_ERR_ARG;
+    if (!groups_proved) return dae_fail(ctx, DAE_ERR_ARG, "null pointer");
+    *groups_proved = 0;
+    if (!ctx->skip_stat.p) return DAE_OK;
+    unsigned long long h = 0;                               // the fourth word: dae_filter_skip_read keeps its three
+    unsigned long long* const word = static_cast<unsigned long long*>(ctx->skip_stat.p) + 3;
+    DAE_HIP_CHECK(ctx, hipMemcpyAsync(&h, word, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    DAE_HIP_CHECK(ctx, hipMemsetAsync(word, 0, sizeof(h), ctx->stream));
+    DAE_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    *groups_proved = (uint64_t)h;
+    return DAE_OK;
+}
+
 int dae_sample_skip_read(dae_ctx* ctx, uint64_t out3[3])
 {
     if (!ctx) return DAE_ERR_ARG;

@@ -15,6 +15,7 @@
 #include "score_plan.h"            // dae_rowgeom, the host planners, DAE_KG / DAE_MAX_K / DAE_NUM_CU / DAE_NUM_XCD
 #include "mix_plan.h"              // dae_mix_plan: the same for the exact title mix
 #include "tau_search.h"            // DAE_KEY_NEG_INF, the threshold search (host and device)
+#include "empty_proof.h"           // the envelope of a filter list and the proof that its live list is empty (host and device)
 
 // ---------------------------------------------------------------------------------------------
 // geometry constants of the decode path (see DESIGN.md "HBM layout")
@@ -163,17 +164,20 @@ struct dae_ctx {
     dae_buf live_sync; void* live_sync_zeroed = nullptr; size_t live_sync_zeroed_bytes = 0;   // (which allocation was zeroed)
     dae_buf cand_list;         // dae_rank_candidates: [B][row_cap] (key, column) pairs | [B] counts (candidates.hip)
     dae_buf cat_seeds;         // the catalogue calls: a slab's seed lists in the catalogue's columns, [4097] row pointers | [4096] counts | the columns (catalogue.hip)
-    dae_buf skip_stat;         // 3 x uint64 {launches, planned tiles x row groups, live tiles} since the last dae_filter_skip_read
+    dae_buf skip_stat;         // 4 x uint64 {launches, planned tiles x row groups, live tiles} since the last dae_filter_skip_read |
+                               // {row groups whose live list the threshold launch proved empty} since the last dae_live_proof_read
     // the threshold sample in half row groups skips the tiles a bound puts below tau (decode_generic.hip decode_f32_kernel's HALF):
     // row_d = [Bpad][4] floats, the rows' max |h - 0.5| by quarters, written by whoever wrote the packed fp32 hidden image
     // (the encode kernels, pack_h_d_kernel); row_d_fresh: ... for the image as it stands (set by that launch, taken by the next
     // threshold sample: an image with no published d skips nothing)
     dae_buf row_d; bool row_d_fresh = false;
     // the sample's bound table (prepack.hip sample_bound_kernel): 4 floats {mu_max, -, -, -} | [n_samp] {A_t, M_t} | [n_beta] beta
-    // sorted descending; built for one tile order and sample geometry, like tile_band
-    dae_buf samp_tab; long long tab_gen = -1; int tab_nsamp = 0, tab_nbrg = 0, tab_waves = 0;
+    // sorted descending | [DAE_PROOF_ENV] the envelope of the filter list (filter_envelope_kernel; empty_proof.h); built for one
+    // tile order, sample geometry, filter list length and ranked-column count, like tile_band
+    dae_buf samp_tab; long long tab_gen = -1; int tab_nsamp = 0, tab_nbrg = 0, tab_waves = 0, tab_nfilter = -1, tab_nrank = -1;
     dae_buf sskip_stat;        // DAE_SSKIP_SLOTS x uint64, one per workgroup of the sample launch: wave-tiles it decoded since the last dae_sample_skip_read
                                // | DAE_SSKIP_SLOTS x uint32: the decoded-tile table of the last sample launch that skipped (dae_sample_skip::tab)
+                               // | DAE_SSKIP_PAIRS x float2: {dq, tau_safe} of its half groups (dae_sample_skip::pair)
     unsigned long long sskip_launches = 0, sskip_planned = 0;   // ... and the launches / planned wave-tiles (known on the host)
 
     // profiling of the dominant kernel
@@ -340,7 +344,7 @@ int dae_launch_tile_band(dae_ctx* ctx, const int* order, int ntiles, int n_samp,
 // group (item = wave * nb_rg + workgroup): head[0] = mu_max, ub_out[i] = {A_t, M_t} of item i, beta_out[0 .. n_beta) the largest
 // group lower bounds, descending
 int dae_launch_sample_bounds(dae_ctx* ctx, const dae_packed& pk, const int* list, int n_items, int nb_rg, int waves, int nrank,
-                             float* head, float2* ub_out, float* beta_out, int n_beta);
+                             float* head, float2* ub_out, float* beta_out, int n_beta, int n_filter, float* env_out);
 int dae_launch_live_tiles(dae_ctx* ctx, const dae_packed& pk, const dae_rowgeom& g, int B, const int* list, int n_items,
                           const float* tau, int nrank, int* live_cnt, int* live_list, unsigned long long* stat);
 
@@ -352,6 +356,7 @@ struct dae_tileset {        // which wave tiles a decode launch walks
     const int* list;        // tile of item i; never null
 };
 constexpr int DAE_SSKIP_SLOTS = 2 * DAE_NUM_CU;      // workgroups of a half-row-group sample launch: 2 n_rg nb_rg <= 2 x 256
+constexpr int DAE_SSKIP_PAIRS = DAE_SSKIP_SLOTS / DAE_NUM_XCD;   // ... and its half groups: nb_rg >= DAE_NUM_XCD
 // what decode_f32_kernel's HALF skips sample tiles by (ub == nullptr: the full walk) -- DESIGN.md section 2
 struct dae_sample_skip {
     const float2* ub;                 // [n_items] {A_t, M_t} of the sample's items, in list order
@@ -362,6 +367,8 @@ struct dae_sample_skip {
     unsigned long long* stat;         // [grid of the launch] += wave-tiles decoded, per workgroup (DAE_SSKIP_SLOTS words)
     unsigned* tab;                    // nullable: [2 n_rg][nb_rg] the decoded-tile table (score_plan.h dae_sample_item_slot) -- the launch
                                       // stores the decoded tiles' slots only, and dae_launch_tau_select must be given the same table
+    float2* pair;                     // nullable: [2 n_rg] {dq, tau_safe} of every half group, stored by its workgroup 0 (what the threshold
+                                      // launch proves an empty live list from: dae_tau_live::pair)
 };
 // dense epilogue: out[row*ld + item*32 + vl] (item = position of the tile in the set)
 // gmax (nullable): [B][ld_gmax] maxima of every lane's two 8-column groups, 4 per (row, item) -- the threshold
@@ -579,7 +586,11 @@ struct dae_tau_live {
     const int* list; int n_items;                                // the filter launch's tile list
     unsigned long long* d_row;                                   // [Bpad] scratch: the bits of each row's max |h - 0.5| (double)
     unsigned* arrive;                                            // [n_rg] rows of the group that have published; ZERO between launches
-    int* live_cnt; int* live_list; unsigned long long* stat;     // as dae_launch_live_tiles
+    int* live_cnt; int* live_list; unsigned long long* stat;     // as dae_launch_live_tiles; stat[3] += row groups proved empty
+    // THE EMPTY LIST PROVED (nullable, both or neither; the instances with a decoded-tile table only): the {dq, tau_safe} pairs this
+    // call's sample launch stored per half group and the envelope of `list` (empty_proof.h).  A group whose pairs prove that the
+    // tail would keep nothing gets live_cnt = 0 and the counters from the workgroup of its first row; no workgroup of it arrives
+    const float2* pair; const float* env;
 };
 int dae_launch_tau_select(dae_ctx* ctx, const float* gmax, int64_t ld_g, int n_g, const float* samp, int64_t ld_s,
                           int n_s, const int* samp_list, int col_lo, int B, int k, const int32_t* seed_row_ptr,

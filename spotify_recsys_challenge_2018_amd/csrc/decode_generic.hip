@@ -114,6 +114,9 @@ __global__ __launch_bounds__(NW * 64, HALF ? 2 : NW / 4) void decode_f32_kernel(
             }
             // (every workgroup of the launch stores its own word, this one included when it is zero: nobody clears the table)
             if (p.sk.tab && tid == 0) p.sk.tab[(size_t)rg * p.nb_rg + bir] = word;
+            // ... and workgroup 0 of the half group its {dq, tau_safe}: D >= the d of every row of it, T <= every threshold of it --
+            // what the threshold launch proves the filter launch's live list empty from (empty_proof.h), rewritten by every launch
+            if (p.sk.pair && bir == 0 && tid == 0) p.sk.pair[rg] = make_float2(dq, tau_safe);
             if (n_live == 0 && p.sk.tab) return;                 // ... and its maxima and dense slots stay as they stand, unread
             if (n_live == 0) {
                 // nothing to decode in this workgroup: -inf into its maxima and its dense sample slots (what the exchange

@@ -426,6 +426,37 @@ __global__ __launch_bounds__(1024) void sample_bound_kernel(const int* __restric
     }
 }
 
+// THE ENVELOPE OF THE FILTER LIST (empty_proof.h), behind the bound table and rebuilt with it: workgroup j
+// takes env[j] = the maximum over the filter launch's items of U_t(d_j), the value dae_tile_is_live compares with tau_min, in
+// double, rounded UP to float; the edge tile by its ranked columns' pair.  A NaN pair or M_t < 0 anywhere: env[j] = NaN.
+__global__ __launch_bounds__(256) void filter_envelope_kernel(const int* __restrict__ list, int n_items,
+                                                              const float* __restrict__ tile_ub, int ntiles, int nrank,
+                                                              float* __restrict__ env)
+{
+    __shared__ float sh_edge[2];
+    __shared__ double sh_u[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int j = blockIdx.x;
+    const int t_edge = (nrank & 31) ? (nrank >> 5) : -1;
+    if (wave == 0 && t_edge >= 0) {
+        float ea, em;
+        dae_edge_tile_bound(tile_ub, ntiles, nrank, lane, ea, em);
+        if (lane == 0) { sh_edge[0] = ea; sh_edge[1] = em; }
+    }
+    __syncthreads();
+    double u = -__builtin_inf();
+    for (int i = tid; i < n_items; i += 256) {
+        const int t = list[i];
+        const float a = t == t_edge ? sh_edge[0] : tile_ub[2 * t], m = t == t_edge ? sh_edge[1] : tile_ub[2 * t + 1];
+        u = dae_max_nan(u, dae_proof_item(a, m, j));
+    }
+#pragma unroll
+    for (int sh = 1; sh < 64; sh <<= 1) u = dae_max_nan(u, __shfl_xor(u, sh));
+    if (lane == 0) sh_u[wave] = u;
+    __syncthreads();
+    if (tid == 0) env[j] = dae_proof_float_up(dae_max_nan(dae_max_nan(sh_u[0], sh_u[1]), dae_max_nan(sh_u[2], sh_u[3])));
+}
+
 __global__ __launch_bounds__(256) void tile_iota_kernel(int n, int* __restrict__ out)
 {
     for (int t = blockIdx.x * 256 + threadIdx.x; t < n; t += gridDim.x * 256) out[t] = t;
@@ -753,12 +784,16 @@ int dae_launch_pack_h(dae_ctx* ctx, const float* h, int B, int H, const dae_rowg
 }
 
 int dae_launch_sample_bounds(dae_ctx* ctx, const dae_packed& pk, const int* list, int n_items, int nb_rg, int waves, int nrank,
-                             float* head, float2* ub_out, float* beta_out, int n_beta)
+                             float* head, float2* ub_out, float* beta_out, int n_beta, int n_filter, float* env_out)
 {
-    if (!pk.ub_valid || !pk.tile_ub.p || n_items <= 0 || nb_rg * 32 > BOUND_MAX_GROUPS || n_beta > nb_rg * 32)
+    if (!pk.ub_valid || !pk.tile_ub.p || n_items <= 0 || nb_rg * 32 > BOUND_MAX_GROUPS || n_beta > nb_rg * 32 || n_filter < 0)
         return dae_fail(ctx, DAE_ERR_STATE, "sample bound table: fp32 image with bounds, at most %d groups", BOUND_MAX_GROUPS);
     hipLaunchKernelGGL(sample_bound_kernel, dim3(1), dim3(1024), 0, ctx->stream, list, n_items, nb_rg, waves,
                        static_cast<const float*>(pk.tile_ub.p), pk.ntiles, nrank, head, ub_out, beta_out, n_beta);
     DAE_CHECK_LAUNCH(ctx, "sample_bound_kernel");
+    // (the filter launch's items follow the sample's in the order)
+    hipLaunchKernelGGL(filter_envelope_kernel, dim3(DAE_PROOF_ENV), dim3(256), 0, ctx->stream, list + n_items, n_filter,
+                       static_cast<const float*>(pk.tile_ub.p), pk.ntiles, nrank, env_out);
+    DAE_CHECK_LAUNCH(ctx, "filter_envelope_kernel");
     return DAE_OK;
 }

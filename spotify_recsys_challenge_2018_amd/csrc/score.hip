@@ -158,9 +158,9 @@ static int reserve_live(dae_ctx* ctx, const dae_rowgeom& g, int n_filter, int** 
     int rc = dae_reserve(ctx, ctx->live, (cnt_ints + (size_t)g.n_rg * n_filter) * sizeof(int));
     if (rc) return rc;
     if (!ctx->skip_stat.p) {
-        rc = dae_reserve(ctx, ctx->skip_stat, 3 * sizeof(unsigned long long));
+        rc = dae_reserve(ctx, ctx->skip_stat, 4 * sizeof(unsigned long long));
         if (rc) return rc;
-        DAE_HIP_CHECK(ctx, hipMemsetAsync(ctx->skip_stat.p, 0, 3 * sizeof(unsigned long long), ctx->stream));
+        DAE_HIP_CHECK(ctx, hipMemsetAsync(ctx->skip_stat.p, 0, 4 * sizeof(unsigned long long), ctx->stream));
     }
     *live_cnt = static_cast<int*>(ctx->live.p);
     *live_list = *live_cnt + cnt_ints;
@@ -233,26 +233,30 @@ static int topk_phase_a(dae_ctx* ctx, const dae_packed* pk, const dae_rowgeom& g
     // bound stays below it.  The bound table belongs to the tile order and the launch geometry, like the band list; the rows' d comes
     // from the launch that wrote the packed hidden image (none published for this image: the full walk).
     dae_sample_skip sk{};
+    float* env = nullptr;
     const bool d_fresh = ctx->row_d_fresh;
     ctx->row_d_fresh = false;                              // (taken: the next sample needs its own image's)
     if (pl.sample_skip && ctx->filter_skip) {
         const int n_beta = g.nb_rg * 32 < 4096 ? g.nb_rg * 32 : 4096;
         const void* tab_was = ctx->samp_tab.p;
-        rc = dae_reserve(ctx, ctx->samp_tab, (4 + (size_t)2 * pl.n_samp + n_beta) * sizeof(float));
+        rc = dae_reserve(ctx, ctx->samp_tab, (4 + (size_t)2 * pl.n_samp + n_beta + DAE_PROOF_ENV) * sizeof(float));
         if (rc) return rc;
         if (ctx->samp_tab.p != tab_was) ctx->tab_gen = -1;
-        if (!ctx->sskip_stat.p) {                          // (the counter words | the decoded-tile table, which nobody clears)
-            rc = dae_reserve(ctx, ctx->sskip_stat, DAE_SSKIP_SLOTS * (sizeof(unsigned long long) + sizeof(unsigned)));
+        if (!ctx->sskip_stat.p) {                          // (the counter words | the decoded-tile table and the half groups' pairs, which nobody clears)
+            rc = dae_reserve(ctx, ctx->sskip_stat, DAE_SSKIP_SLOTS * (sizeof(unsigned long long) + sizeof(unsigned)) + DAE_SSKIP_PAIRS * sizeof(float2));
             if (rc) return rc;
             DAE_HIP_CHECK(ctx, hipMemsetAsync(ctx->sskip_stat.p, 0, DAE_SSKIP_SLOTS * sizeof(unsigned long long), ctx->stream));
         }
         float* head = static_cast<float*>(ctx->samp_tab.p);
         float2* ub = reinterpret_cast<float2*>(head + 4);
         float* beta = head + 4 + (size_t)2 * pl.n_samp;
-        if (ctx->tab_gen != pk->order_gen || ctx->tab_nsamp != pl.n_samp || ctx->tab_nbrg != g.nb_rg || ctx->tab_waves != g.waves) {
-            rc = dae_launch_sample_bounds(ctx, *pk, order, pl.n_samp, g.nb_rg, g.waves, pl.nrank, head, ub, beta, n_beta);
+        env = beta + n_beta;                               // the envelope of the filter list: the same table, the same size in every call
+        if (ctx->tab_gen != pk->order_gen || ctx->tab_nsamp != pl.n_samp || ctx->tab_nbrg != g.nb_rg || ctx->tab_waves != g.waves ||
+            ctx->tab_nfilter != pl.n_filter || ctx->tab_nrank != pl.nrank) {
+            rc = dae_launch_sample_bounds(ctx, *pk, order, pl.n_samp, g.nb_rg, g.waves, pl.nrank, head, ub, beta, n_beta, pl.n_filter, env);
             if (rc) return rc;
             ctx->tab_gen = pk->order_gen; ctx->tab_nsamp = pl.n_samp; ctx->tab_nbrg = g.nb_rg; ctx->tab_waves = g.waves;
+            ctx->tab_nfilter = pl.n_filter; ctx->tab_nrank = pl.nrank;
         }
         if (d_fresh && 2 * g.grid <= DAE_SSKIP_SLOTS && ctx->row_d.p && ctx->row_d.bytes >= (size_t)g.Bpad * 4 * sizeof(float)) {
             // SKIPPED TILES ARE NOT STORED: with the workgroup-per-row threshold kernel behind it, the launch writes which wave-tiles
@@ -261,7 +265,9 @@ static int topk_phase_a(dae_ctx* ctx, const dae_packed* pk, const dae_rowgeom& g
             // kernel keeps the dense exchange (-inf stored and read back)
             unsigned long long* const stat = static_cast<unsigned long long*>(ctx->sskip_stat.p);
             unsigned* const tab = dae_tau_wave_per_row(B, pl.ld_g, pl.ld_s) ? nullptr : reinterpret_cast<unsigned*>(stat + DAE_SSKIP_SLOTS);
-            sk = dae_sample_skip{ub, beta, n_beta, head, static_cast<const float*>(ctx->row_d.p), seed_row_ptr, k, stat, tab};
+            // ... and every half group's {dq, tau_safe} behind the table (2 n_rg <= DAE_SSKIP_PAIRS: nb_rg >= DAE_NUM_XCD)
+            float2* const pair = reinterpret_cast<float2*>(reinterpret_cast<unsigned*>(stat + DAE_SSKIP_SLOTS) + DAE_SSKIP_SLOTS);
+            sk = dae_sample_skip{ub, beta, n_beta, head, static_cast<const float*>(ctx->row_d.p), seed_row_ptr, k, stat, tab, pair};
             ctx->sskip_launches += 1;
             ctx->sskip_planned += (unsigned long long)((B + 63) / 64) * (unsigned long long)pl.n_samp;   // half groups with a real row
         }
@@ -306,7 +312,10 @@ static int topk_phase_a(dae_ctx* ctx, const dae_packed* pk, const dae_rowgeom& g
         lv = dae_tau_live{static_cast<const float4*>(ctx->h_packed.p), B, pk->H, pk->Hp / DAE_KG,
                           static_cast<const float*>(pk->tile_ub.p), pk->ntiles, pl.nrank, order + pl.n_samp, pl.n_filter,
                           reinterpret_cast<unsigned long long*>(arrive + n_arrive), arrive, lc, ll,
-                          static_cast<unsigned long long*>(ctx->skip_stat.p)};
+                          static_cast<unsigned long long*>(ctx->skip_stat.p), nullptr, nullptr};
+        // THE EMPTY LIST PROVED: where this call's sample ran with the skip and the table, the launch has the half groups' pairs and
+        // the list's envelope, and a row group they prove empty runs no arrival tail (tau_select.hip; DESIGN.md sections 2 and 4)
+        if (sk.ub && sk.tab) { lv.pair = sk.pair; lv.env = env; }
     }
     rc = dae_launch_tau_select(ctx, gmax, pl.ld_g, (int)pl.ld_g, pl.whole_b ? gmax : sample, pl.whole_b ? 0 : pl.ld_s,
                                pl.whole_b ? 0 : (int)pl.ld_s, order, pk->col_lo, B, k,

@@ -214,6 +214,21 @@ __global__ __launch_bounds__(256) void tau_select_kernel(const TauP p, const std
     unsigned tword = 0;
     if constexpr (SPARSE)
         if (tid < tb.nb_rg) tword = tb.tab[(size_t)(row >> 6) * tb.nb_rg + tid];
+    // LIVE && SPARSE, THE EMPTY LIST PROVED (empty_proof.h): the {dq, tau_safe} pairs the sample launch stored
+    // for the row group's half groups, asked for by every thread with the maxima (a wave-uniform address).  D = max dq >= the d the
+    // tail would compute, T = min tau_safe <= every threshold of the group: every workgroup of the group takes the same four floats
+    // and reaches the same verdict, so nobody has to arrive anywhere.  A second half group without a real row takes no part.
+    constexpr bool PROOF = LIVE && SPARSE;
+    float2 pr0 = make_float2(0.0f, 0.0f), pr1 = pr0;
+    bool proof_on = false;
+    if constexpr (PROOF) {
+        proof_on = lv.pair != nullptr;
+        if (proof_on) {
+            const int hg = (row >> 7) * 2;
+            pr0 = lv.pair[hg];
+            pr1 = lv.pair[(hg + 1) * 64 < lv.B ? hg + 1 : hg];
+        }
+    }
     __builtin_amdgcn_sched_barrier(0);
     unsigned kreg[TAU_PER];
 #pragma unroll
@@ -234,6 +249,18 @@ __global__ __launch_bounds__(256) void tau_select_kernel(const TauP p, const std
 #pragma unroll
             for (int u = 0; u < 16; ++u)
                 kreg[q * 16 + u] = ((gw[u >> 2] >> (8 * (u & 3))) & 0xFFu) ? kreg[q * 16 + u] : DAE_KEY_NEG_INF;
+        }
+    }
+    // PROOF: the one envelope entry for D (the pairs arrived with the table word above), asked for here -- ahead of the
+    // dense row's requests, so that no wait for it stands in front of the search -- and consumed behind the search
+    float genv = __builtin_nanf("");
+    float proof_T = -__builtin_inff();
+    if constexpr (PROOF) {
+        if (proof_on) {
+            const float D = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(dae_max_nan(pr0.x, pr1.x))));
+            proof_T = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(dae_min_nan(pr0.y, pr1.y))));
+            const int jd = dae_proof_index(D);
+            if (jd >= 0) genv = lv.env[jd];                      // (no proof for this D: the NaN stands)
         }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -299,6 +326,8 @@ __global__ __launch_bounds__(256) void tau_select_kernel(const TauP p, const std
     });
     const float tv = dae_tau_value(lo, p.n_s);
     if (!LIVE && tid == 0) p.tau[row] = tv;                      // (LIVE: published at the end, with d_row)
+    bool proved = false;                                         // block-uniform
+    if constexpr (PROOF) proved = __builtin_amdgcn_readfirstlane((int)(proof_on && dae_proof_holds(genv, proof_T))) != 0;
     double d_row = 0.0;                                          // LIVE, wave 0: max |h - 0.5| over the row's units k < H (the zero pad would read 0.5)
     auto take_d_row = [&]() {
         if constexpr (LIVE) {
@@ -315,7 +344,9 @@ __global__ __launch_bounds__(256) void tau_select_kernel(const TauP p, const std
             }
         }
     };
-    if constexpr (LIVE && HV_EARLY) take_d_row();
+    if constexpr (LIVE && HV_EARLY) {
+        if (!proved) take_d_row();                               // (a proved group has no tail to give it to)
+    }
     if constexpr (LIVE && !HV_EARLY) load_hv();
     if (!HAS_S) {                                                // no sample to scan: the (empty) survivor list
         if (tid == 0) p.out_cnt[row] = 0;
@@ -350,6 +381,24 @@ __global__ __launch_bounds__(256) void tau_select_kernel(const TauP p, const std
         if (decoded(f)) emit4(p, dst, at, tv, srow[f], f, p.samp_list[f >> 3]);
     if constexpr (LIVE) {
         if constexpr (!HV_EARLY) take_d_row();
+        if constexpr (PROOF) {
+            if (proved) {
+                // the answer the arrival tail would have given, from the workgroup of the group's first row: an empty list and the
+                // reducer's counters (+ the groups proved).  The arrival counter and lv.d_row are not touched
+                if (tid == 0) {
+                    p.tau[row] = tv;
+                    if ((row & 127) == 0) {
+                        const int rg = row >> 7;
+                        lv.live_cnt[rg] = 0;
+                        if (rg == 0) atomicAdd(&lv.stat[0], 1ull);
+                        atomicAdd(&lv.stat[1], (unsigned long long)lv.n_items);
+                        atomicAdd(&lv.stat[2], 0ull);
+                        atomicAdd(&lv.stat[3], 1ull);
+                    }
+                }
+                return;
+            }
+        }
         tau_live_tail(p, lv, row, tid, lane, wv, tv, d_row, wsum);
     }
 }
