@@ -554,6 +554,47 @@ int dae_rank_candidates(dae_ctx* ctx, int B, int V, const int32_t* cand_row_ptr,
                         int row_cap, const int32_t* seed_row_ptr, const int32_t* seed_col, int k, int out_kind,
                         float* out_score, int32_t* out_idx);
 
+/* ---- rank_of: the exact rank of given tracks among ALL rankable tracks of a row (csrc/rank_of.hip) --------------------------
+ *
+ * Where does this track stand for this playlist -- what MRR, mean / median rank, AUC, a recall curve at every cut-off and
+ * hard-negative mining ask, and what no top-k list answers below position k -- without the [B, V] matrix, a sort and a search.
+ *
+ * The answers are a CSR on the device, as dae_rank_metrics and the candidate calls take theirs: ans_row_ptr [B + 1], ans_col
+ * [n_ans] int32 GLOBAL column ids in any order, duplicates allowed; n_ans is passed by the caller (nothing is read back to size
+ * a launch; nothing at or past n_ans is touched).  For answer i, column c of row r:
+ *   UNRANKABLE: rank[i] = -1 when c == -1 (padding), c >= n_tracks (an artist column) or c is one of the row's seeds.
+ *   OUT OF RANGE: any other id outside [0, V) also gives -1, is never dereferenced and ORs bit 0 into *status (DEVICE int32,
+ *     nullable; the caller zeroes it), as in the candidate calls.
+ *   OTHERWISE rank[i] = the number of columns c' in [0, n_tracks), c' != c, c' no seed of r, that PRECEDE c in the library's
+ *     canonical order: fp32 logit descending under the composite key (orc_okey's order: -0 equal to +0, a NaN where that key
+ *     puts it), ties broken by column ascending.  Ranks are 0-based, so rank_of(r, list[r][p]) == p for every position p of a
+ *     list the fp32 (or exact-bf16) ranking calls return for the same seeds.  A duplicated answer gets the same rank twice.
+ *   out_logit [n_ans] (nullable): the answer's canonical fp32 logit (the value of dae_decode_dense at [r, c], bit for bit);
+ *     -inf beside rank -1 for padding, artists and seeds; NaN for an out-of-range id, like dae_decode_candidates.
+ * Arithmetic: fp32 only -- a rank is a statement about the canonical fp32 logits, which DAE_DTYPE_F32 and DAE_DTYPE_BF16_EXACT
+ * list by; a DAE_DTYPE_BF16 list may differ from them in its tail.
+ *
+ * The context must hold a plain DAE_DTYPE_F32 image over [0, V) of the same weights (dae_prepack_decoder): no fp32 image, a
+ * catalogue image or a shard image (col_lo > 0 or col_hi < V) give DAE_ERR_STATE, the message saying which.  1 <= B <= 4096;
+ * H % 4 == 0, H <= 1024; 1 <= n_tracks <= V; W_dec 16-byte aligned.  Any number of answers per row, 0 included: a row with more
+ * than one pass of the counting launch holds (dae_rank_of_plan's C) takes more passes of the GEMM inside the same launch.
+ * Asynchronous on the context's stream; all scratch (24 bytes per answer) sits in the context, and a steady state allocates
+ * nothing; the counters are zeroed by the call itself.  Every refusal (a null pointer other than out_logit / status / both
+ * seed arrays, n_ans < 0, a bad n_tracks, seeds given half, the image) comes before any launch.
+ * dae_score_rank_of: the same behind dae_encode with the inference keep-probabilities, as dae_score_candidates.
+ * dae_rank_of_plan: out = {rows per row group, answers of a row per pass C, row groups, workgroups per row group} of a call of
+ *   these sizes (csrc/rank_of_plan.h); host only.
+ * NOT BUILT: a bf16 count (the thresholds would have to come out of the bf16 MFMA chain), vocabulary shards, catalogue images,
+ * the titled (mixed) score, the pipeline. */
+int dae_rank_of_plan(int B, int H, int n_ans, int32_t out[4]);
+int dae_decode_rank_of(dae_ctx* ctx, const float* h, int B, int H, const float* W_dec, const float* b_dec, int V, int n_tracks,
+                       const int32_t* seed_row_ptr, const int32_t* seed_col, const int32_t* ans_row_ptr, const int32_t* ans_col,
+                       int n_ans, int32_t* out_rank, float* out_logit, int32_t* status);
+int dae_score_rank_of(dae_ctx* ctx, const int32_t* row_ptr, const int32_t* col, const float* val, const float* W_enc,
+                      const float* b_enc, int V, int H, int B, const float* W_dec, const float* b_dec, int n_tracks,
+                      const int32_t* seed_row_ptr, const int32_t* seed_col, const int32_t* ans_row_ptr, const int32_t* ans_col,
+                      int n_ans, int32_t* out_rank, float* out_logit, int32_t* status);
+
 /* ---- a catalogue: rank a SHARED subset of the track columns (csrc/catalogue.hip) -------------------------------------------
  *
  * "The k best tracks among THESE columns, the same for every row" -- a market's catalogue, the non-explicit tracks, the tracks

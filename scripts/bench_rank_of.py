@@ -1,0 +1,130 @@
+#!/usr/bin/env python
+"""Exact ranks of given tracks through the fused call against the route a caller had before it, on the same device in the same
+session: V = 170 000, 140 000 tracks, hidden 256, 256 rows.
+
+  fused   dae_score_rank_of(answers)
+  dense   dae_encode + dae_decode_dense (logits) into [B, V] + the seeds set to -inf + torch.sort of the track columns +
+          torch.searchsorted of the answers' own logits -- none of it is code of rank_of
+
+per (model, answers per row) for the zipf bench model and the same weights with b_dec = 0, and 10, 100 and 250 answers per row.
+Everything is resident on the device (the CSR, the seed CSR, the seeds' flat index, the answers, the outputs): the figures are
+device time per call, `--iters` calls between two events, the median of `--runs` alternating runs (fused, dense, fused, dense,
+...), all values printed.  The two routes' ranks are compared before anything is timed: the dense route gives tied logits one
+shared rank and knows no column order, so "answers that differ" is reported, not required to be 0; a tie can only add to the
+canonical rank, and the differences that is not true of are counted too (0 expected).  Each case also reports the
+plan (rows per row group, answers per pass, passes of the GEMM).  Prints one line per case and a final JSON line; `--out FILE`
+also writes the JSON there."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from spotify_recsys_challenge_2018_amd import _lib                                                # noqa: E402
+from spotify_recsys_challenge_2018_amd.models.DAEs import coo_to_csr, seeds_to_csr               # noqa: E402
+from spotify_recsys_challenge_2018_amd.utils.synthetic import make_playlists, make_weights        # noqa: E402
+
+
+def timed(fn, iters):
+    import torch
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / iters          # ms per call
+
+
+def main():
+    import torch
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tracks", type=int, default=140000)
+    ap.add_argument("--artists", type=int, default=30000)
+    ap.add_argument("--hidden", type=int, default=256)
+    ap.add_argument("--rows", type=int, default=256)
+    ap.add_argument("--answers", type=int, nargs="*", default=[10, 100, 250])
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--runs", type=int, default=4)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    nt, na, H, B = a.tracks, a.artists, a.hidden, a.rows
+    V = nt + na
+    W_enc, b_enc, W_dec, b_dec = make_weights(V, H, seed=0, bias="zipf", n_tracks=nt)
+    pos, ones, seeds = make_playlists(B, nt, na, seed=1)
+    rp, col, val = coo_to_csr(pos, ones, B, V)
+    srp, sc = seeds_to_csr(seeds, B, nt)
+
+    def dev(x):
+        return torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    d_rp, d_col, d_val, d_srp, d_sc = dev(rp), dev(col), dev(val), dev(srp), dev(sc)
+    d_We, d_be, d_Wd = dev(W_enc), dev(b_enc), dev(W_dec)
+    seed_rows = dev(np.repeat(np.arange(B, dtype=np.int64), np.diff(srp)))
+    seed_cols = dev(sc.astype(np.int64))
+    ctx = _lib.Context(0)
+    h = torch.empty((B, H), device="cuda")
+    z = torch.empty((B, V), device="cuda")
+    neg_inf = torch.tensor(float("-inf"), device="cuda")
+    res = {"V": V, "tracks": nt, "H": H, "B": B, "iters": a.iters, "runs": a.runs, "cases": []}
+    print("V = %d, tracks = %d, hidden = %d, rows = %d; ms per call (device), median of %d alternating runs of %d calls"
+          % (V, nt, H, B, a.runs, a.iters))
+    rng = np.random.default_rng(2)
+    for model, bias in (("zipf", b_dec), ("b_dec=0", np.zeros_like(b_dec))):
+        d_bd = dev(bias)
+        ctx.prepack_decoder(d_Wd, d_bd, dtype=_lib.DAE_DTYPE_F32)
+        for A in a.answers:
+            cols = rng.integers(0, nt, (B, A))
+            d_ans = (dev(np.arange(B + 1, dtype=np.int32) * A), dev(cols.reshape(-1).astype(np.int32)))
+            d_cols64 = dev(cols.astype(np.int64))
+            rank = torch.empty(B * A, dtype=torch.int32, device="cuda")
+            status = torch.zeros(1, dtype=torch.int32, device="cuda")
+
+            def fused():
+                ctx.score_rank_of(d_rp, d_col, d_val, d_We, d_be, d_Wd, d_bd, nt, d_srp, d_sc, d_ans, B * A, rank, status=status)
+
+            def dense():
+                ctx.encode(d_rp, d_col, d_val, d_We, d_be, h)
+                ctx.decode_dense(h, z, apply_sigmoid=False)
+                z.index_put_((seed_rows, seed_cols), neg_inf)
+                zt = z[:, :nt]
+                mine = torch.gather(zt, 1, d_cols64)
+                srt = torch.sort(-zt, dim=1).values                # ascending of -z = logits descending
+                r = torch.searchsorted(srt, -mine)                 # how many logits are strictly larger
+                return torch.where(torch.isneginf(mine), torch.full_like(r, -1), r)
+
+            fused(); want = dense()                                 # (also the warm-up of both routes)
+            got = rank.view(B, A).to(torch.int64)
+            differ = int((got != want).sum().item())
+            # a tie can only ADD the tied smaller columns to the canonical rank: anything else would be an error of one route
+            unexplained = int((((got < 0) != (want < 0)) | (got < want)).sum().item())
+            plan = _lib.rank_of_plan(B, H, B * A)
+            passes = -(-A // plan["capacity"])
+            t_f, t_d = [], []
+            for _ in range(a.runs):
+                t_f.append(timed(fused, a.iters))
+                t_d.append(timed(dense, a.iters))
+            mf, md = float(np.median(t_f)), float(np.median(t_d))
+            spread = max(max(t_f) - min(t_f), max(t_d) - min(t_d))
+            case = {"model": model, "answers_per_row": A, "answers_that_differ": differ, "differences_no_tie_explains": unexplained,
+                    "fused_ms": t_f, "dense_ms": t_d,
+                    "fused_median_ms": mf, "dense_median_ms": md, "fused_ahead_in_every_pair": all(x < y for x, y in zip(t_f, t_d)),
+                    "medians_apart_by_3_spreads": bool(md - mf >= 3 * spread), "rows_per_group": plan["rows"],
+                    "answers_per_pass": plan["capacity"], "passes": passes}
+            res["cases"].append(case)
+            print("%-8s %3d answers/row: fused %8.3f ms (%s)  dense + mask + sort + searchsorted %8.3f ms (%s)  ratio %.2fx  "
+                  "every pair ahead: %s  3 x spread: %s  %d-row groups, %d answers/pass, %d pass(es)  %d of %d answers differ (%d not by ties)"
+                  % (model, A, mf, " ".join("%.3f" % x for x in t_f), md, " ".join("%.3f" % x for x in t_d), md / mf,
+                     case["fused_ahead_in_every_pair"], case["medians_apart_by_3_spreads"], plan["rows"], plan["capacity"],
+                     passes, differ, B * A, unexplained))
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()

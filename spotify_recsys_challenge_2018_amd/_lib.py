@@ -31,6 +31,7 @@ EXPORTS = [
     "dae_pipeline_release", "dae_pipeline_stats", "dae_pipeline_exact_margin", "dae_pipeline_times", "dae_pipeline_last_error",
     "dae_rank_metrics", "dae_pipeline_enable_eval", "dae_pipeline_submit_eval", "dae_pipeline_poll_eval",
     "dae_decode_candidates", "dae_score_candidates", "dae_mix_candidates", "dae_rank_candidates",
+    "dae_rank_of_plan", "dae_decode_rank_of", "dae_score_rank_of",
     "dae_catalogue_create", "dae_catalogue_destroy", "dae_prepack_decoder_catalogue", "dae_score_topk_catalogue",
     "dae_decode_topk_catalogue", "dae_title_score_catalogue", "dae_pipeline_set_catalogue",
 ]
@@ -175,6 +176,9 @@ def load():
     lib.dae_mix_candidates.argtypes = [vp, vp, vp, c_i64, c_int, vp, vp, vp, c_i64, vp, vp, vp, vp, c_int, c_int, vp, vp,
                                        c_int, vp, vp]
     lib.dae_rank_candidates.argtypes = [vp, c_int, c_int, vp, vp, vp, c_int, vp, vp, c_int, c_int, vp, vp]
+    lib.dae_rank_of_plan.argtypes = [c_int, c_int, c_int, ctypes.POINTER(ctypes.c_int32)]
+    lib.dae_decode_rank_of.argtypes = [vp, vp, c_int, c_int, vp, vp, c_int, c_int, vp, vp, vp, vp, c_int, vp, vp, vp]
+    lib.dae_score_rank_of.argtypes = [vp, vp, vp, vp, vp, vp, c_int, c_int, c_int, vp, vp, c_int, vp, vp, vp, vp, c_int, vp, vp, vp]
     lib.dae_catalogue_create.argtypes = [vp, vp, c_int, c_int, ctypes.POINTER(vp)]
     lib.dae_catalogue_destroy.argtypes = [vp]
     lib.dae_prepack_decoder_catalogue.argtypes = [vp, vp, vp, vp, c_int, c_int, c_int]
@@ -188,6 +192,15 @@ def load():
             getattr(lib, name).restype = c_int
     _lib = lib
     return lib
+
+
+def rank_of_plan(n_rows, hidden, n_ans):
+    """How a rank_of call of these sizes is cut (dae_rank_of_plan; host only): {"rows": rows per row group of the counting
+    launch, "capacity": answers of a row one pass of the GEMM takes, "row_groups", "blocks_per_group"}."""
+    out = (ctypes.c_int32 * 4)()
+    if load().dae_rank_of_plan(int(n_rows), int(hidden), int(n_ans), out):
+        raise ValueError("rank_of_plan: no geometry for %d rows, hidden %d, %d answers" % (n_rows, hidden, n_ans))
+    return {"rows": int(out[0]), "capacity": int(out[1]), "row_groups": int(out[2]), "blocks_per_group": int(out[3])}
 
 
 def mix_exact_shape_ok(hidden, ld_feat):
@@ -616,6 +629,27 @@ class Context:
         self.check(self.lib.dae_rank_candidates(self.h, B, int(n_cols), _ptr(cand[0]), _ptr(cand[1]), _ptr(key), int(row_cap),
                                                 _ptr(seed_row_ptr), _ptr(seed_col), int(k), int(out_kind), _ptr(out_score),
                                                 _ptr(out_idx)))
+
+    # ---- exact ranks of given tracks over the whole vocabulary (csrc/rank_of.hip): ans = (row_ptr int32 [B + 1], col int32 [>= n_ans])
+    def decode_rank_of(self, h, W_dec, b_dec, n_tracks, seed_row_ptr, seed_col, ans, n_ans, out_rank, out_logit=None, status=None):
+        """out_rank[i] = how many rankable non-seed tracks precede column ans_col[i] in its row's canonical fp32 order, -1 for
+        what cannot be ranked (dae_decode_rank_of); needs the plain fp32 image of W_dec / b_dec over all columns."""
+        B, H = h.shape
+        if not h.is_contiguous():
+            raise ValueError("decode_rank_of: contiguous hidden rows are required")
+        self.check(self.lib.dae_decode_rank_of(self.h, _ptr(h), B, H, _ptr(W_dec), _ptr(b_dec), int(W_dec.shape[0]), int(n_tracks),
+                                               _ptr(seed_row_ptr), _ptr(seed_col), _ptr(ans[0]), _ptr(ans[1]), int(n_ans),
+                                               _ptr(out_rank), _ptr(out_logit), _ptr(status)))
+
+    def score_rank_of(self, row_ptr, col, val, W_enc, b_enc, W_dec, b_dec, n_tracks, seed_row_ptr, seed_col, ans, n_ans, out_rank,
+                      out_logit=None, status=None):
+        """dae_encode (inference) + decode_rank_of in one call; the hidden rows stay in the context."""
+        V, H = W_enc.shape
+        B = row_ptr.numel() - 1
+        self.check(self.lib.dae_score_rank_of(self.h, _ptr(row_ptr), _ptr(col), _ptr(val), _ptr(W_enc), _ptr(b_enc), V, H, B,
+                                              _ptr(W_dec), _ptr(b_dec), int(n_tracks), _ptr(seed_row_ptr), _ptr(seed_col),
+                                              _ptr(ans[0]), _ptr(ans[1]), int(n_ans), _ptr(out_rank), _ptr(out_logit),
+                                              _ptr(status)))
 
     # ---- a catalogue: a shared, ascending subset of the track columns (csrc/catalogue.hip; `Catalogue` below) ------------------
     def prepack_decoder_catalogue(self, cat, W_dec, b_dec, dtype=DAE_DTYPE_F32):

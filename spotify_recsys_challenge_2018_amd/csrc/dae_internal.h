@@ -163,6 +163,7 @@ struct dae_ctx {
     // launch that never completes (a device fault) leaves them standing for the life of the context, like the rest of its state
     dae_buf live_sync; void* live_sync_zeroed = nullptr; size_t live_sync_zeroed_bytes = 0;   // (which allocation was zeroed)
     dae_buf cand_list;         // dae_rank_candidates: [B][row_cap] (key, column) pairs | [B] counts (candidates.hip)
+    dae_buf rank_of;           // dae_decode_rank_of: [n_ans] thresholds (u64) | logits | places | buckets, then [n_rg] longest rows (rank_of.hip)
     dae_buf cat_seeds;         // the catalogue calls: a slab's seed lists in the catalogue's columns, [4097] row pointers | [4096] counts | the columns (catalogue.hip)
     dae_buf skip_stat;         // 4 x uint64 {launches, planned tiles x row groups, live tiles} since the last dae_filter_skip_read |
                                // {row groups whose live list the threshold launch proved empty} since the last dae_live_proof_read

@@ -1,0 +1,534 @@
+// rank_of.hip -- the exact rank of GIVEN track columns among all rankable tracks of a row, without the [B, V] matrix a dense
+// decode, a sort and a search would take (include/dae_hip.h "rank_of").
+//
+// THE ORDER.  Column c' precedes column c of a row iff  key(z') > key(z)  or  (key(z') == key(z) and c' < c), key = dae_okey of
+// the canonical fp32 logit: the order every ranking call of the library lists by.  Both halves live in ONE 64-bit word,
+//     comp(z, c) = (~dae_okey(z) << 32) | c,        c' precedes c  <=>  comp' < comp,
+// so ties need no path of their own and a column never precedes itself.
+//
+// THE LAUNCHES of a call (all on the context's stream, all scratch in the context):
+//   1. dae_decode_candidates over the answers: z_a, the canonical logit of every listed (row, column), from the row-major tensors.
+//   2. a memset of the global counters and of the row groups' longest-row words;
+//   3. rank_of_prep_kernel, a workgroup per row: a row's answers are cut into CHUNKS of C in the caller's order
+//      (rank_of_plan.h), each chunk's composites sorted ascending into thr[] at the answers' own CSR offsets, inv[i] = the place
+//      of answer i in its chunk.  An answer that cannot be ranked by its id (-1, an artist, out of range) becomes ~0, which
+//      sorts behind every real composite.
+//   4. rank_of_count_kernel: the fp32 MFMA decode over the tiles that hold a ranked column, hidden tile resident in LDS, W
+//      streamed through a register ring as in decode_generic.hip.  Per pass q the workgroup holds chunk q of each of its rows
+//      in LDS and drops every logit x of a ranked column into the bucket j = #{a in chunk : comp(a) <= comp(x)}.  x precedes
+//      the answer at sorted place p iff j <= p, so that answer's count is the PREFIX sum of the buckets up to p; bucket `len` is
+//      never read and not kept.  One compare each against the chunk's first and last threshold settles the common cases
+//      (bucket 0 is counted in a register, bucket `len` dropped); only what lies between takes the binary search and an LDS
+//      atomic.  The answer's own column gives comp(x) == comp(a) -- the accumulator IS the candidate chain's value -- hence j > p:
+//      it is left out by identity.  Workgroups add their buckets to the global ones with integer atomics: sums of integers, the
+//      same whatever the order.
+//   5. rank_of_finish_kernel, a workgroup per row: prefix sums -> counts; then the row's SEEDS (each distinct seed track once):
+//      their canonical logits by the same chain, one subtracted from every answer a seed precedes, and an answer that is a seed
+//      becomes (-1, -inf).  Results go out in the caller's order.
+#include "decode_common.h"
+#include "rank_of_plan.h"
+
+namespace {
+
+constexpr int RO_NW = 4;                       // waves of a counting workgroup: one per SIMD
+constexpr int RO_THREADS = RO_NW * 64;
+constexpr unsigned long long RO_NONE = ~0ull;  // an answer whose id cannot be ranked
+constexpr int RO_MAXH = 1024;
+
+__device__ __forceinline__ unsigned long long ro_comp(float z, int c)
+{
+    return ((unsigned long long)(~dae_okey(z)) << 32) | (unsigned)c;
+}
+
+struct RankP {
+    const float4* Wp; const float* bias; const float4* hp;   // the fp32 image over [0, V) and the packed hidden rows
+    int G, ntiles_r, n_tracks, V;              // k groups; tiles with a ranked column; ranked columns; all columns
+    int B, n_rg, nb_rg, C;
+    const int32_t* ans_row_ptr; const int32_t* ans_col; int n_ans;
+    const int32_t* seed_row_ptr; const int32_t* seed_col;
+    const float* z;                            // [n_ans] candidate logits
+    unsigned long long* thr; int* inv;         // [n_ans] sorted composites per chunk; place of an answer in its chunk
+    unsigned* gcnt; int* glen;                 // [n_ans] buckets; [n_rg] longest row of a group
+    int R_TILE;
+    const float* h; int H; const float* W; const float* b;   // row-major tensors (the seeds' chains)
+    int32_t* out_rank; float* out_logit;
+};
+
+// a row's answers: [beg, end) of ans_col, clamped to what the caller said exists
+__device__ __forceinline__ void ro_row_span(const RankP& p, int row, int& beg, int& end)
+{
+    const int a = p.ans_row_ptr[row], b = p.ans_row_ptr[row + 1];
+    beg = a > 0 ? a : 0;
+    end = b < p.n_ans ? b : p.n_ans;
+    if (end < beg) end = beg;
+}
+
+__global__ __launch_bounds__(256) void rank_of_prep_kernel(const RankP p)
+{
+    __shared__ unsigned long long comp[DAE_RO_MAX_C];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    int beg, end;
+    ro_row_span(p, row, beg, end);
+    if (tid == 0 && end > beg) atomicMax(&p.glen[row / p.R_TILE], end - beg);
+    for (int c0 = beg; c0 < end; c0 += p.C) {
+        const int len = end - c0 < p.C ? end - c0 : p.C;
+        __syncthreads();
+        for (int t = tid; t < len; t += 256) {
+            const int c = p.ans_col[c0 + t];
+            comp[t] = (c >= 0 && c < p.n_tracks) ? ro_comp(p.z[c0 + t], c) : RO_NONE;
+        }
+        __syncthreads();
+        for (int t = tid; t < len; t += 256) {
+            const unsigned long long a = comp[t];
+            int pos = 0;
+            for (int u = 0; u < len; ++u) {
+                const unsigned long long o = comp[u];
+                pos += (o < a || (o == a && u < t)) ? 1 : 0;
+            }
+            p.thr[c0 + pos] = a;
+            p.inv[c0 + t] = pos;
+        }
+    }
+}
+
+template <int RB, int GT>
+__global__ __launch_bounds__(RO_THREADS, 1) void rank_of_count_kernel(const RankP p)
+{
+    extern __shared__ __attribute__((aligned(16))) float4 lds4[];
+    constexpr int R_TILE = RB * 32;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int hi = lane >> 5;
+    const int j = lane & 31;
+    const int G = GT > 0 ? GT : p.G;
+    const int C = p.C;
+
+    // XCD-aware block -> (row group, slot in row group), as the decode kernels
+    const int gs = DAE_NUM_XCD * p.n_rg;
+    const int q = blockIdx.x / gs, rem = blockIdx.x % gs;
+    const int rg = rem / DAE_NUM_XCD;
+    const int bir = q * DAE_NUM_XCD + (rem % DAE_NUM_XCD);
+    if (rg >= p.n_rg || bir >= p.nb_rg) return;
+
+    const int longest = p.glen[rg];                               // block-uniform
+    if (longest <= 0) return;                                     // no row of the group asks anything
+
+    const int n_h4 = RB * 64 * G;
+    unsigned long long* lthr = reinterpret_cast<unsigned long long*>(lds4 + n_h4);
+    unsigned* lcnt = reinterpret_cast<unsigned*>(lthr + (size_t)R_TILE * C);
+    int* llen = reinterpret_cast<int*>(lcnt + (size_t)R_TILE * C);
+    int* lbeg = llen + R_TILE;
+
+    // ---- hidden tile of this row group -> LDS, once ------------------------------------------
+    {
+        const float4* src = p.hp + (size_t)rg * n_h4;
+        int i = tid;
+        for (; i + 7 * RO_THREADS < n_h4; i += 8 * RO_THREADS) {
+            float4 v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = src[i + u * RO_THREADS];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) lds4[i + u * RO_THREADS] = v[u];
+        }
+        for (; i < n_h4; i += RO_THREADS) lds4[i] = src[i];
+    }
+
+    const int n_ws = p.nb_rg * RO_NW;
+    const int item0 = wave * p.nb_rg + bir;                       // wave-major: a short tile list is spread over all workgroups
+
+    for (int pass = 0; pass * C < longest; ++pass) {
+        // ---- chunk `pass` of every row of the group: thresholds into LDS, buckets zeroed ------
+        for (int i = tid; i < R_TILE; i += RO_THREADS) {
+            const int row = rg * R_TILE + i;
+            int len = 0, beg = 0;
+            if (row < p.B) {
+                int rb0, re;
+                ro_row_span(p, row, rb0, re);
+                beg = rb0 + pass * C;
+                len = re - beg;
+                len = len < 0 ? 0 : (len > C ? C : len);
+                // the unrankable answers sort to the chunk's end: they are no thresholds (first index holding RO_NONE)
+                int lo = 0, hi2 = len;
+                while (lo < hi2) {
+                    const int mid = (lo + hi2) >> 1;
+                    if (p.thr[beg + mid] == RO_NONE) hi2 = mid; else lo = mid + 1;
+                }
+                len = lo;
+            }
+            llen[i] = len; lbeg[i] = beg;
+        }
+        __syncthreads();
+        for (int s = tid; s < R_TILE * C; s += RO_THREADS) {
+            const int i = s / C, t = s - i * C;
+            lcnt[s] = 0u;
+            if (t < llen[i]) lthr[s] = p.thr[lbeg[i] + t];
+        }
+        __syncthreads();
+
+        int len_r[RB];
+        unsigned n0[RB];
+        unsigned long long first[RB], last[RB];
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb) {
+            const int i = rb * 32 + j;
+            len_r[rb] = llen[i];
+            n0[rb] = 0u;
+            first[rb] = len_r[rb] > 0 ? lthr[(size_t)i * C] : 0ull;                       // (no x is below 0 ...
+            last[rb] = len_r[rb] > 0 ? lthr[(size_t)i * C + len_r[rb] - 1] : 0ull;        //  ... and every x is >= 0: nothing counts)
+        }
+
+        // ---- the GEMM over the ranked tiles (decode_generic.hip decode_f32_kernel's fp32 body) -
+        if (item0 < p.ntiles_r) {
+            float4 wb0, wb1, wb2, wb3;
+            float4 bA[RB], bB[RB];
+            {
+                const float4* w0 = p.Wp + (size_t)item0 * G * 64 + lane;
+                wb0 = w0[0]; wb1 = w0[64]; wb2 = w0[128]; wb3 = w0[192];
+            }
+#pragma unroll
+            for (int rb = 0; rb < RB; ++rb) bA[rb] = lds4[rb * 64 + lane];
+
+            for (int t = item0; t < p.ntiles_r; t += n_ws) {
+                const float4* wp = p.Wp + (size_t)t * G * 64 + lane;
+                const int t_n = t + n_ws < p.ntiles_r ? t + n_ws : t;   // (the last tile again: in bounds, unused)
+                const float4* wn = p.Wp + (size_t)t_n * G * 64 + lane;
+                const float* bp = p.bias + (size_t)t * 32 + 4 * hi;
+                float4 bq[4];
+#pragma unroll
+                for (int qd = 0; qd < 4; ++qd) bq[qd] = *reinterpret_cast<const float4*>(bp + 8 * qd);
+
+                f32x16 acc[RB];
+#pragma unroll
+                for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) acc[rb][e] = 0.0f;
+
+#define RO_STEP(WB, PF, BC, BN, GNEXT)                                                         \
+    {                                                                                          \
+        const float4 a = WB;                                                                   \
+        WB = *(PF);                                                                            \
+        const float4* hl = lds4 + (size_t)(GNEXT) * (RB * 64) + lane;                          \
+        _Pragma("unroll") for (int rb = 0; rb < RB; ++rb) BN[rb] = hl[rb * 64];                \
+        __builtin_amdgcn_sched_barrier(0);                                                     \
+        _Pragma("unroll") for (int rb = 0; rb < RB; ++rb)                                      \
+            acc[rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, BC[rb].x, acc[rb], 0, 0, 0);   \
+        _Pragma("unroll") for (int rb = 0; rb < RB; ++rb)                                      \
+            acc[rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, BC[rb].y, acc[rb], 0, 0, 0);   \
+        _Pragma("unroll") for (int rb = 0; rb < RB; ++rb)                                      \
+            acc[rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, BC[rb].z, acc[rb], 0, 0, 0);   \
+        _Pragma("unroll") for (int rb = 0; rb < RB; ++rb)                                      \
+            acc[rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, BC[rb].w, acc[rb], 0, 0, 0);   \
+        __builtin_amdgcn_sched_barrier(0);                                                     \
+    }
+                int g = 0;
+#pragma unroll
+                for (; g < G - 4; g += 4) {
+                    const float4* pf = wp + (size_t)(g + 4) * 64;
+                    RO_STEP(wb0, pf,       bA, bB, g + 1)
+                    RO_STEP(wb1, pf + 64,  bB, bA, g + 2)
+                    RO_STEP(wb2, pf + 128, bA, bB, g + 3)
+                    RO_STEP(wb3, pf + 192, bB, bA, g + 4)
+                }
+                RO_STEP(wb0, wn,       bA, bB, g + 1)
+                RO_STEP(wb1, wn + 64,  bB, bA, g + 2)
+                RO_STEP(wb2, wn + 128, bA, bB, g + 3)
+                RO_STEP(wb3, wn + 192, bB, bA, 0)
+#undef RO_STEP
+
+                // ---- the counting epilogue: lane holds, for row j of row block rb, the columns
+                //   tcol0 + (reg & 3) + 8 * (reg >> 2)                                    (reg = 0..15)
+                const int tcol0 = t * 32 + 4 * hi;
+#pragma unroll
+                for (int rb = 0; rb < RB; ++rb) {
+                    if (len_r[rb] == 0) continue;
+                    const unsigned long long* th = lthr + (size_t)(rb * 32 + j) * C;
+                    unsigned* cn = lcnt + (size_t)(rb * 32 + j) * C;
+#pragma unroll
+                    for (int qd = 0; qd < 4; ++qd) {
+                        const float z4[4] = {acc[rb][4 * qd + 0] + bq[qd].x, acc[rb][4 * qd + 1] + bq[qd].y,
+                                             acc[rb][4 * qd + 2] + bq[qd].z, acc[rb][4 * qd + 3] + bq[qd].w};
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const int col = tcol0 + 8 * qd + e;
+                            if (col >= p.n_tracks) continue;     // artists in the last ranked tile, the image's padding
+                            const unsigned long long x = ro_comp(z4[e], col);
+                            if (x < first[rb]) {
+                                ++n0[rb];
+                            } else if (x < last[rb]) {
+                                // first[] <= x < last[]: the bucket is the first place in [1, len - 1] whose threshold is > x
+                                int lo = 1, hi2 = len_r[rb] - 1;
+                                while (lo < hi2) {
+                                    const int mid = (lo + hi2) >> 1;
+                                    if (th[mid] <= x) lo = mid + 1; else hi2 = mid;
+                                }
+                                atomicAdd(&cn[lo], 1u);
+                            }
+                        }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb)
+            if (n0[rb]) atomicAdd(&lcnt[(size_t)(rb * 32 + j) * C], n0[rb]);
+        __syncthreads();
+        // ---- this workgroup's buckets -> the global ones ---------------------------------------
+        for (int s = tid; s < R_TILE * C; s += RO_THREADS) {
+            const int i = s / C, t = s - i * C;
+            if (t < llen[i]) {
+                const unsigned v = lcnt[s];
+                if (v) atomicAdd(&p.gcnt[lbeg[i] + t], v);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void rank_of_finish_kernel(const RankP p)
+{
+    __shared__ float hrow[RO_MAXH];
+    __shared__ unsigned long long scomp[256];
+    __shared__ int scol[256];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    int beg, end;
+    ro_row_span(p, row, beg, end);
+    if (end <= beg) return;
+    const float ninf = -__builtin_inff();
+
+    // counts from the buckets; what cannot be ranked by its id
+    for (int i = beg + tid; i < end; i += 256) {
+        const int c = p.ans_col[i];
+        int rank = -1;
+        float zl = p.z[i];                                        // (-inf for -1, NaN for an id outside [0, V): candidates.hip)
+        if (c >= 0 && c < p.n_tracks) {
+            const int c0 = beg + (i - beg) / p.C * p.C;
+            const int pos = p.inv[i];
+            unsigned s = 0;
+            for (int u = 0; u <= pos; ++u) s += p.gcnt[c0 + u];
+            rank = (int)s;
+        } else if (c >= p.n_tracks && c < p.V) {
+            zl = ninf;                                            // an artist column: -inf beside -1
+        }
+        p.out_rank[i] = rank;
+        if (p.out_logit) p.out_logit[i] = zl;
+    }
+    if (!p.seed_row_ptr) return;
+    const int sb = p.seed_row_ptr[row], se = p.seed_row_ptr[row + 1];
+    if (se <= sb) return;
+    for (int k = tid; k < RO_MAXH; k += 256) hrow[k] = k < p.H ? p.h[(size_t)row * p.H + k] : 0.0f;
+    __syncthreads();                                              // (also orders this workgroup's stores to out_rank before its reads below)
+
+    // the seeds in blocks of 256, a lane each: the canonical chain over the row-major tensor; a seed listed twice counts once
+    for (int s0 = sb; s0 < se; s0 += 256) {
+        const int si = s0 + tid;
+        int c = -1;
+        unsigned long long sc = RO_NONE;
+        if (si < se) {
+            c = p.seed_col[si];
+            bool ok = c >= 0 && c < p.n_tracks;
+            for (int u = sb; ok && u < si; ++u) ok = p.seed_col[u] != c;
+            if (ok) {
+                const float4* wr = reinterpret_cast<const float4*>(p.W + (size_t)c * p.H);
+                float acc = 0.0f;
+                const int n4 = p.H >> 2;
+                int k4 = 0;
+                for (; k4 + 3 < n4; k4 += 4) {
+                    float4 w[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) w[u] = wr[k4 + u];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const int kb = 4 * (k4 + u);
+                        acc = fmaf(hrow[kb], w[u].x, acc);
+                        acc = fmaf(hrow[kb + 1], w[u].y, acc);
+                        acc = fmaf(hrow[kb + 2], w[u].z, acc);
+                        acc = fmaf(hrow[kb + 3], w[u].w, acc);
+                    }
+                }
+                for (; k4 < n4; ++k4) {
+                    const float4 w = wr[k4];
+                    const int kb = 4 * k4;
+                    acc = fmaf(hrow[kb], w.x, acc);
+                    acc = fmaf(hrow[kb + 1], w.y, acc);
+                    acc = fmaf(hrow[kb + 2], w.z, acc);
+                    acc = fmaf(hrow[kb + 3], w.w, acc);
+                }
+                sc = ro_comp(acc + p.b[c], c);
+            } else {
+                c = -1;
+            }
+        }
+        __syncthreads();
+        scomp[tid] = sc; scol[tid] = c;
+        __syncthreads();
+        const int ns = se - s0 < 256 ? se - s0 : 256;
+        for (int i = beg + tid; i < end; i += 256) {
+            const int rank = p.out_rank[i];
+            if (rank < 0) continue;
+            const int ca = p.ans_col[i];
+            const unsigned long long a = ro_comp(p.z[i], ca);
+            int sub = 0;
+            bool is_seed = false;
+            for (int u = 0; u < ns; ++u) {
+                sub += scomp[u] < a ? 1 : 0;
+                is_seed = is_seed || scol[u] == ca;
+            }
+            if (is_seed) {
+                p.out_rank[i] = -1;
+                if (p.out_logit) p.out_logit[i] = ninf;
+            } else if (sub) {
+                p.out_rank[i] = rank - sub;
+            }
+        }
+    }
+}
+
+template <int RB, int GT>
+int launch_count(dae_ctx* ctx, const dae_ro_plan& pl, const RankP& p)
+{
+    DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &rank_of_count_kernel<RB, GT>, DAE_RO_LDS_BYTES));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    dae_take_profile_events(ctx, "rank_of_count_kernel", e0, e1);
+    if (e0) DAE_HIP_CHECK(ctx, hipEventRecord(e0, ctx->stream));
+    hipLaunchKernelGGL((rank_of_count_kernel<RB, GT>), dim3(pl.grid), dim3(RO_THREADS), pl.lds_bytes, ctx->stream, p);
+    DAE_CHECK_LAUNCH(ctx, "rank_of_count_kernel");
+    if (e1) DAE_HIP_CHECK(ctx, hipEventRecord(e1, ctx->stream));
+    return DAE_OK;
+}
+
+// everything both entry points refuse, before any launch
+int check_rank_of(dae_ctx* ctx, const void* h_or_enc, int B, int H, const float* W_dec, const float* b_dec, int V, int n_tracks,
+                  const int32_t* seed_row_ptr, const int32_t* seed_col, const int32_t* ans_row_ptr, const int32_t* ans_col,
+                  int n_ans, const int32_t* out_rank, dae_ro_plan* pl)
+{
+    if (!h_or_enc || !W_dec || !b_dec || !ans_row_ptr || !ans_col || !out_rank) return dae_fail(ctx, DAE_ERR_ARG, "null pointer");
+    if (n_ans < 0) return dae_fail(ctx, DAE_ERR_ARG, "n_ans=%d is negative", n_ans);
+    if (B < 1 || B > DAE_RO_MAX_B) return dae_fail(ctx, DAE_ERR_ARG, "B=%d out of [1, %d]", B, DAE_RO_MAX_B);
+    if (H <= 0 || (H % 4) != 0 || H > RO_MAXH) return dae_fail(ctx, DAE_ERR_ARG, "H=%d must be a multiple of 4 in [4, %d]", H, RO_MAXH);
+    if (V <= 0) return dae_fail(ctx, DAE_ERR_ARG, "bad shape V=%d", V);
+    if (n_tracks < 1 || n_tracks > V) return dae_fail(ctx, DAE_ERR_ARG, "n_tracks=%d out of [1, V=%d]", n_tracks, V);
+    if ((seed_row_ptr == nullptr) != (seed_col == nullptr))
+        return dae_fail(ctx, DAE_ERR_ARG, "seed_row_ptr and seed_col must both be given or both null");
+    if (reinterpret_cast<uintptr_t>(W_dec) % 16) return dae_fail(ctx, DAE_ERR_ARG, "the decoder tensor must be 16-byte aligned");
+    const dae_packed& pk = ctx->pk_f32;
+    if (!pk.valid) return dae_fail(ctx, DAE_ERR_STATE, "rank_of needs a DAE_DTYPE_F32 image of the decoder: none is prepacked");
+    if (pk.cat_id != 0) return dae_fail(ctx, DAE_ERR_STATE, "rank_of: the fp32 image is a catalogue image, not one of the vocabulary's own columns");
+    if (pk.col_lo != 0 || pk.col_hi != V || pk.V != V)
+        return dae_fail(ctx, DAE_ERR_STATE, "rank_of: the fp32 image is a shard image over [%d, %d) of %d columns, not one over [0, %d)",
+                        pk.col_lo, pk.col_hi, pk.V, V);
+    if (pk.H != H) return dae_fail(ctx, DAE_ERR_ARG, "H=%d does not match prepacked H=%d", H, pk.H);
+    *pl = dae_plan_rank_of(B, H, n_ans);
+    if (pl->C <= 0) return dae_fail(ctx, DAE_ERR_ARG, "rank_of: no geometry for B=%d H=%d", B, H);
+    return DAE_OK;
+}
+
+int rank_of_core(dae_ctx* ctx, const dae_ro_plan& pl, const float* h, int B, int H, const float* W_dec, const float* b_dec,
+                 int V, int n_tracks, const int32_t* seed_row_ptr, const int32_t* seed_col, const int32_t* ans_row_ptr,
+                 const int32_t* ans_col, int n_ans, int32_t* out_rank, float* out_logit, int32_t* status)
+{
+    if (n_ans == 0) return DAE_OK;
+    const dae_packed& pk = ctx->pk_f32;
+    // scratch: thr [n_ans] u64 | z [n_ans] | inv [n_ans] | gcnt [n_ans] | glen [n_rg]   (gcnt and glen zeroed together)
+    const size_t na = (size_t)n_ans;
+    const size_t bytes = na * 8 + na * 4 * 3 + (size_t)pl.n_rg * 4;
+    int rc = dae_reserve(ctx, ctx->rank_of, bytes);
+    if (rc) return rc;
+    char* base = static_cast<char*>(ctx->rank_of.p);
+    RankP p{};
+    p.thr = reinterpret_cast<unsigned long long*>(base);
+    float* z = reinterpret_cast<float*>(base + na * 8);
+    p.z = z;
+    p.inv = reinterpret_cast<int*>(base + na * 12);
+    p.gcnt = reinterpret_cast<unsigned*>(base + na * 16);
+    p.glen = reinterpret_cast<int*>(base + na * 20);
+
+    // (a) the thresholds: the candidate chain over the answers
+    rc = dae_decode_candidates(ctx, h, H, B, H, W_dec, b_dec, V, ans_row_ptr, ans_col, n_ans, DAE_OUT_LOGIT, z, status);
+    if (rc) return rc;
+    DAE_HIP_CHECK(ctx, hipMemsetAsync(p.gcnt, 0, na * 4 + (size_t)pl.n_rg * 4, ctx->stream));
+
+    // the hidden rows in the MFMA operand order, for this call's row groups
+    dae_rowgeom g{};
+    g.R_TILE = pl.R_TILE; g.n_rg = pl.n_rg; g.Bpad = pl.n_rg * pl.R_TILE; g.nb_rg = pl.nb_rg; g.grid = pl.grid; g.waves = RO_NW;
+    // the packed hidden image becomes this call's: its pads are for this geometry (the ranking calls re-zero theirs), no row d
+    // belongs to it, and a dae_score_topk_begin waiting for its _finish on this context has lost its rows (it is refused then)
+    ctx->row_d_fresh = false;
+    ctx->h_geom_key = -1;
+    ctx->tk.valid = false;
+    rc = dae_launch_pack_h(ctx, h, B, H, g, nullptr);
+    if (rc) return rc;
+
+    p.Wp = static_cast<const float4*>(pk.W.p); p.bias = static_cast<const float*>(pk.bias.p);
+    p.hp = static_cast<const float4*>(ctx->h_packed.p);
+    p.G = pl.G; p.ntiles_r = (n_tracks + 31) / 32; p.n_tracks = n_tracks; p.V = V;
+    p.B = B; p.n_rg = pl.n_rg; p.nb_rg = pl.nb_rg; p.C = pl.C; p.R_TILE = pl.R_TILE;
+    p.ans_row_ptr = ans_row_ptr; p.ans_col = ans_col; p.n_ans = n_ans;
+    p.seed_row_ptr = seed_row_ptr; p.seed_col = seed_col;
+    p.h = h; p.H = H; p.W = W_dec; p.b = b_dec;
+    p.out_rank = out_rank; p.out_logit = out_logit;
+
+    hipLaunchKernelGGL(rank_of_prep_kernel, dim3(B), dim3(256), 0, ctx->stream, p);
+    DAE_CHECK_LAUNCH(ctx, "rank_of_prep_kernel");
+    const bool h256 = pl.G == 32;
+    switch (pl.R_TILE) {
+        case 128: rc = h256 ? launch_count<4, 32>(ctx, pl, p) : launch_count<4, 0>(ctx, pl, p); break;
+        case 64:  rc = h256 ? launch_count<2, 32>(ctx, pl, p) : launch_count<2, 0>(ctx, pl, p); break;
+        case 32:  rc = launch_count<1, 0>(ctx, pl, p); break;
+        default:  rc = dae_fail(ctx, DAE_ERR_ARG, "bad R_TILE %d", pl.R_TILE);
+    }
+    if (rc) return rc;
+    hipLaunchKernelGGL(rank_of_finish_kernel, dim3(B), dim3(256), 0, ctx->stream, p);
+    DAE_CHECK_LAUNCH(ctx, "rank_of_finish_kernel");
+    return DAE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dae_rank_of_plan(int B, int H, int n_ans, int32_t out[4])
+{
+    if (!out || n_ans < 0) return DAE_ERR_ARG;
+    const dae_ro_plan pl = dae_plan_rank_of(B, H, n_ans);
+    if (pl.C <= 0) return DAE_ERR_ARG;
+    out[0] = pl.R_TILE; out[1] = pl.C; out[2] = pl.n_rg; out[3] = pl.nb_rg;
+    return DAE_OK;
+}
+
+int dae_decode_rank_of(dae_ctx* ctx, const float* h, int B, int H, const float* W_dec, const float* b_dec, int V, int n_tracks,
+                       const int32_t* seed_row_ptr, const int32_t* seed_col, const int32_t* ans_row_ptr, const int32_t* ans_col,
+                       int n_ans, int32_t* out_rank, float* out_logit, int32_t* status)
+{
+    if (!ctx) return DAE_ERR_ARG;
+    dae_ro_plan pl;
+    int rc = check_rank_of(ctx, h, B, H, W_dec, b_dec, V, n_tracks, seed_row_ptr, seed_col, ans_row_ptr, ans_col, n_ans, out_rank, &pl);
+    if (rc) return rc;
+    return rank_of_core(ctx, pl, h, B, H, W_dec, b_dec, V, n_tracks, seed_row_ptr, seed_col, ans_row_ptr, ans_col, n_ans, out_rank,
+                        out_logit, status);
+}
+
+int dae_score_rank_of(dae_ctx* ctx, const int32_t* row_ptr, const int32_t* col, const float* val, const float* W_enc,
+                      const float* b_enc, int V, int H, int B, const float* W_dec, const float* b_dec, int n_tracks,
+                      const int32_t* seed_row_ptr, const int32_t* seed_col, const int32_t* ans_row_ptr, const int32_t* ans_col,
+                      int n_ans, int32_t* out_rank, float* out_logit, int32_t* status)
+{
+    if (!ctx) return DAE_ERR_ARG;
+    if (!row_ptr || !W_enc || !b_enc) return dae_fail(ctx, DAE_ERR_ARG, "null pointer");
+    if ((reinterpret_cast<uintptr_t>(W_enc) | reinterpret_cast<uintptr_t>(b_enc)) % 16)
+        return dae_fail(ctx, DAE_ERR_ARG, "W_enc, b_enc must be 16-byte aligned");
+    dae_ro_plan pl;
+    int rc = check_rank_of(ctx, W_enc, B, H, W_dec, b_dec, V, n_tracks, seed_row_ptr, seed_col, ans_row_ptr, ans_col, n_ans, out_rank,
+                           &pl);
+    if (rc) return rc;
+    if (n_ans == 0) return DAE_OK;
+    rc = dae_reserve(ctx, ctx->h_scratch, (size_t)B * H * sizeof(float));      // the hidden rows stay in the context, as dae_score_candidates'
+    if (rc) return rc;
+    float* h = static_cast<float*>(ctx->h_scratch.p);
+    rc = dae_launch_encode(ctx, row_ptr, col, val, W_enc, b_enc, V, H, B, 1.0f, 1.0f, 0u, h, nullptr, 0, 0);
+    if (rc) return rc;
+    return rank_of_core(ctx, pl, h, B, H, W_dec, b_dec, V, n_tracks, seed_row_ptr, seed_col, ans_row_ptr, ans_col, n_ans, out_rank,
+                        out_logit, status);
+}
+
+}  // extern "C"

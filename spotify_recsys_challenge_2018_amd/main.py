@@ -4,7 +4,8 @@ the same config.ini schema:
     python -m spotify_recsys_challenge_2018_amd.main --dir D {--pretrain|--dae|--challenge} [--testmode]
 
     [BASE] verbose data_dir result_dir testsize   (+ optional, this build only: train_dtype = f32 | bf16, decode_dtype = f32 | bf16 | exact_bf16,
-                                                  eval_metrics = rprecision | all, train_feed = host | device)
+                                                  eval_metrics = rprecision | all, train_feed = host | device,
+                                                  eval_ranks = off | on)
     [DAE] epochs batch lr reg_lambda hidden test_seed update_seed keep_prob input_kp firstN_range initval save
     [PRETRAIN] epochs batch lr reg_lambda save
     [TITLE] ... (parsed for compatibility; the title models are outside the scoring path)
@@ -70,7 +71,7 @@ class Conf:
         self.dir = dir
         self.ini = ini
         self._load('BASE')
-        # four OPTIONAL [BASE] keys this build adds (absent from the reference's files, which then mean fp32 / rprecision):
+        # five OPTIONAL [BASE] keys this build adds (absent from the reference's files, which then mean fp32 / rprecision):
         #   train_dtype  = f32 | bf16   arithmetic of the training step's three GEMMs (BASELINE.json configs[3])
         #   decode_dtype = f32 | bf16 | exact_bf16   arithmetic of the scoring decode: fp32 MFMA (bit-exact path), bf16
         #                  (configs[4]), or the bf16 GEMM as a filter with the survivors recomputed in fp32 (north_star:
@@ -81,10 +82,16 @@ class Conf:
         #   train_feed   = host | device      where the training batches of --pretrain / --dae / --title are built: by the reader on the host
         #                  (default), or on the device from a resident copy of the training set -- only the reader's draws
         #                  go over the link (models/DAEs.py train_step_draw); same batches, same random draws
+        #   eval_ranks   = off | on           with `on` the evaluation of a test split logs one more line behind the others: MRR, median
+        #                  rank and recall@500 / 1 000 / 5 000 / 10 000 of the held-out tracks, from their EXACT ranks among all
+        #                  rankable tracks (models/DAEs.py rank_of; feed by feed).  Refused under --title (main_train.run): ranks under
+        #                  the title mix are not built
         self.eval_metrics = 'rprecision'
         self.train_feed = 'host'
+        self.eval_ranks = 'off'
         for key, allowed in (('train_dtype', ('f32', 'bf16')), ('decode_dtype', ('f32', 'bf16', 'exact_bf16')),
-                             ('eval_metrics', ('rprecision', 'all')), ('train_feed', ('host', 'device'))):
+                             ('eval_metrics', ('rprecision', 'all')), ('train_feed', ('host', 'device')),
+                             ('eval_ranks', ('off', 'on'))):
             if key in self.ini['BASE']:
                 val = self.ini['BASE'][key].strip().lower()
                 if val not in allowed:

@@ -142,6 +142,42 @@ def _log_splits(conf, readers_test, rprecs, extras):
             log_write(conf, "seed num: %s clicks: %f" % (seed_num, extras[seed_num][1]))
 
 
+RANK_CUTS = (500, 1000, 5000, 10000)
+
+
+def eval_ranks(reader_test, conf, model):
+    """[BASE] eval_ranks = on: the EXACT ranks of one test split's held-out tracks among all rankable tracks of their rows
+    (model.rank_of, feed by feed; seeds = the input's tracks, as in eval) -> (MRR, median rank, recall at RANK_CUTS).  A
+    held-out track outside the vocabulary (-1) is a miss that counts in the denominators."""
+    from ..models.DAEs import SEEDS_FROM_INPUT
+    ranks = []
+    while True:
+        x_positions, test_seed, test_answer, _titles, x_ones = reader_test.next_batch_test()
+        for row in model.rank_of(x_positions, x_ones, [list(a) for a in test_answer], SEEDS_FROM_INPUT, n_rows=len(test_seed)):
+            ranks.append(row)
+        if reader_test.test_idx == 0:
+            break
+    ranks = np.concatenate(ranks) if ranks else np.zeros(0, np.int32)
+    return met.mean_reciprocal_rank(ranks), met.median_rank(ranks), met.recall_at(ranks, RANK_CUTS)
+
+
+def _log_ranks(conf, readers_test, model):
+    """One more line per split, behind the existing ones.  Every rank of a distributed run computes it (the model's calls may
+    be collective); rank 0 logs."""
+    if getattr(conf, 'eval_ranks', 'off') != 'on':
+        return
+    for seed_num in readers_test:
+        mrr, med, rec = eval_ranks(readers_test[seed_num], conf, model)
+        log_write(conf, "seed num: %s ranks: mrr %f median %.1f %s"
+                  % (seed_num, mrr, med, ' '.join("recall@%d %f" % (k, v) for k, v in zip(RANK_CUTS, rec))))
+
+
+def _refuse_ranks_under_title(conf):
+    if getattr(conf, 'eval_ranks', 'off') == 'on' and getattr(conf, 'mode', None) == 'title':
+        raise ValueError("[BASE] eval_ranks = on is not available under --title: ranks under the title mix are not built "
+                         "(remove the key or set eval_ranks = off)")
+
+
 def _init_distributed(conf):
     """One process per GPU under torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE in the env):
     RCCL process group, this rank's device, and the SAME host RNG streams on every rank so that all
@@ -165,6 +201,7 @@ def _init_distributed(conf):
 
 
 def run(conf, only_testmode):
+    _refuse_ranks_under_title(conf)
     rank, world = _init_distributed(conf)
     # the training reader (main_train.py:129-133): whole playlists, or -- with a [DAE] firstN_range -- their first-N prefixes
     reader_args = dict(data_dir=conf.data_dir, filename='train', batch_size=conf.batch)
@@ -214,6 +251,7 @@ def run(conf, only_testmode):
         extras = {} if getattr(conf, 'eval_metrics', 'rprecision') == 'all' else None
         out = _eval_splits(readers_test, conf, model, rank, world, extras)
         _log_splits(conf, readers_test, out, extras)
+        _log_ranks(conf, readers_test, model)
         return out
 
     # [BASE] train_feed = device: the training set lives on the device and a batch goes up as the reader's draws alone
@@ -268,6 +306,7 @@ def run(conf, only_testmode):
             extras = {} if getattr(conf, 'eval_metrics', 'rprecision') == 'all' else None
             rprecs = _eval_splits(readers_test, conf, model, rank, world, extras)
             _log_splits(conf, readers_test, rprecs, extras)
+            _log_ranks(conf, readers_test, model)
             for seed_num in readers_test:
                 if seed_num in conf.update_seed:
                     cur_eval += rprecs[seed_num]

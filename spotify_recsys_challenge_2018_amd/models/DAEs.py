@@ -896,6 +896,47 @@ class DAE_tied:
         self._check_feed()
         return res
 
+    # -- exact ranks of given tracks over the whole vocabulary (csrc/rank_of.hip) --------------------------------------------------
+    def rank_of(self, x_positions, x_ones, columns, seeds, n_rows=None, want_logits=False):
+        """Where THESE tracks stand for each playlist among all its rankable tracks: per listed (row, column) the number of
+        non-seed track columns that precede it in the canonical order (fp32 logit descending, column ascending), 0-based, so
+        `rank_of(feed, recommend(feed, seeds)[0], seeds)` is `arange(k)` per row -- without the [n_batch, n_input] matrix, a sort
+        and a search.  -1 for what cannot be ranked: a -1 (padding), an artist column, one of the row's seeds.
+        columns: the two forms `score_candidates` takes -- a list of per-row id sequences (any order, repeats allowed; ragged,
+        possibly empty) -> a list of int32 arrays aligned with them; or a 2-D int array [n_rows, C] with -1 padding -> int32
+        [n_rows, C].  seeds: as `recommend` takes them, SEEDS_FROM_INPUT included.  want_logits: -> (ranks, logits), the
+        canonical fp32 logits in the same form (-inf beside a rank of -1).  An id outside -1 / [0, n_input) raises ValueError
+        before any launch; a model with a scoring shard refuses like the candidate calls.
+        Always fp32, whatever the model's decode dtype: the ranks describe the canonical fp32 logits, the order an fp32 or
+        exact_bf16 `recommend` lists by; a bf16 list may differ from them in its tail."""
+        import torch
+        n_rows, rp, col, ans, status = self._cand_begin(columns, n_rows, unique=False)
+        self._ensure_packed(_lib.DAE_DTYPE_F32)
+        self.ctx.bind_stream()
+        csr = self._upload_csr(x_positions, x_ones)
+        d_srp, d_sc = self._seed_csr_dev(seeds, csr)
+        n = int(col.size)
+        rank = torch.empty(max(n, 1), dtype=torch.int32, device=csr[0].device)
+        logit = torch.empty(max(n, 1), dtype=torch.float32, device=csr[0].device) if want_logits else None
+        self.ctx.score_rank_of(csr[0], csr[1], csr[2], self.weights["encoder_h"], self.biases["encoder_b"],
+                               self.weights["decoder_h"], self.biases["decoder_b"], self.n_tracks, d_srp, d_sc, ans, n, rank,
+                               out_logit=logit, status=status)
+        self._cand_status(status)
+        ranks = rank.cpu().numpy()[:n]
+        logits = logit.cpu().numpy()[:n] if want_logits else None
+        self._check_feed()
+
+        def shaped(values, fill):
+            if isinstance(columns, np.ndarray) and columns.ndim == 2:
+                out = np.full((n_rows, columns.shape[1]), fill, values.dtype)
+                out[:columns.shape[0]] = values.reshape(columns.shape)
+                return out
+            return [values[rp[r]:rp[r + 1]] for r in range(n_rows)]
+
+        if want_logits:
+            return shaped(ranks, -1), shaped(logits, -np.inf)
+        return shaped(ranks, -1)
+
     def recommend_iter(self, feeds, k=500, dtype=None, want_scores=True, catalogue=None):
         """`recommend` over a stream of batches (`_recommend_iter`).  k <= 1024: the pipeline behind the loop keeps that limit, and a
         larger k raises ValueError here, before a pipeline is created.
@@ -1566,6 +1607,14 @@ class DAE_title(DAE):
         values = out.cpu().numpy()[:col.size]
         self._check_feed()
         return self._cand_result(values, candidates, rp)
+
+    def rank_of(self, x_positions, x_ones, columns, seeds, n_rows=None, want_logits=False, titles=None, titles_use=None):
+        """`DAE.rank_of`: the ranks under the plain DAE logits.  Ranks under the title mix are not built: with titles in use
+        the call raises ValueError."""
+        if titles is not None and titles_use is not None and np.any(np.asarray(titles_use)):
+            raise ValueError("rank_of: ranks under the title mix (titles / titles_use) are not built; call it without titles "
+                             "for the ranks of the DAE's own logits")
+        return DAE.rank_of(self, x_positions, x_ones, columns, seeds, n_rows=n_rows, want_logits=want_logits)
 
     def rank_candidates(self, x_positions, x_ones, candidates, seeds, k=500, n_rows=None, titles=None, titles_use=None,
                         catalogue=None):

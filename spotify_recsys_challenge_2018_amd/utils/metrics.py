@@ -164,3 +164,74 @@ def finish_ndcg_rows(rec):
 
 def finish_rsc_rows(rec):
     return [f // 10 if f >= 0 else 51 for f in rec["first"].tolist()]
+
+
+# ---- metrics over EXACT ranks (models/DAEs.py rank_of): pure host helpers over a rank array -------------------------------------
+# `ranks`: any int array of 0-based ranks, -1 for an answer that could not be ranked (a track outside the vocabulary, padding).
+# Such an answer is a miss: it can never be hit but counts in every denominator, as a -1 answer counts in get_r_precision.
+def _rank_array(ranks):
+    r = np.asarray(ranks, dtype=np.int64).reshape(-1)
+    if r.size and r.min() < -1:
+        raise ValueError("ranks: 0-based ranks or -1, got %d" % r.min())
+    return r
+
+
+def reciprocal_rank(ranks):
+    """Per answer 1 / (rank + 1), 0.0 for a rank of -1 -> float64 array of the input's shape."""
+    r = np.asarray(ranks, dtype=np.int64)
+    _rank_array(r)
+    out = np.zeros(r.shape, np.float64)
+    ok = r >= 0
+    out[ok] = 1.0 / (r[ok] + 1.0)
+    return out
+
+
+def mean_reciprocal_rank(ranks):
+    """MRR over all answers, the unranked ones counting 0 (0.0 for no answers)."""
+    rr = reciprocal_rank(ranks).reshape(-1)
+    return float(rr.mean()) if rr.size else 0.0
+
+
+def mean_rank(ranks):
+    """Mean of the ranks of the RANKED answers (nan when there is none): a miss has no rank to average."""
+    r = _rank_array(ranks)
+    r = r[r >= 0]
+    return float(r.mean()) if r.size else float("nan")
+
+
+def median_rank(ranks):
+    """Median of the ranks of the ranked answers (nan when there is none)."""
+    r = _rank_array(ranks)
+    r = r[r >= 0]
+    return float(np.median(r)) if r.size else float("nan")
+
+
+def recall_at(ranks, ks):
+    """The recall curve at every cut-off at once: for each k of `ks` the share of the answers with 0 <= rank < k, among ALL
+    answers (-1 included in the denominator) -> float64 array [len(ks)] (zeros for no answers)."""
+    r = _rank_array(ranks)
+    ks = np.asarray(ks, dtype=np.int64).reshape(-1)
+    if r.size == 0:
+        return np.zeros(ks.size, np.float64)
+    hit = np.sort(r[r >= 0])
+    return np.searchsorted(hit, ks, side="left") / float(r.size)
+
+
+def auc_row(ranks, n_rankable):
+    """AUC of one row from the ranks of its answers among n_rankable columns:
+
+        AUC = 1 - rank_mean_corrected / (n_rankable - 1),
+        rank_mean_corrected = mean over the row's distinct ranked answers, sorted ascending r_(0) < r_(1) < ..., of r_(i) - i
+
+    r_(i) - i is the number of NON-answer columns ranked before answer i (the i answers before it taken out), so for a single
+    answer this is 1 - rank / (n_rankable - 1): 1.0 at rank 0, 0.0 at the last rank.  With P answers the non-answers number
+    n_rankable - P, so the value is the pairwise AUC times (n_rankable - P) / (n_rankable - 1): off by P / n_rankable at most.
+    Unranked answers (-1) take no part; nan for a row without a ranked answer or with n_rankable < 2."""
+    r = _rank_array(ranks)
+    r = np.unique(r[r >= 0])
+    if r.size == 0 or n_rankable < 2:
+        return float("nan")
+    if r[-1] >= n_rankable:
+        raise ValueError("rank %d among %d rankable columns" % (r[-1], n_rankable))
+    corrected = r - np.arange(r.size)
+    return 1.0 - float(corrected.mean()) / (n_rankable - 1.0)
