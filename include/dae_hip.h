@@ -584,8 +584,26 @@ int dae_rank_candidates(dae_ctx* ctx, int B, int V, const int32_t* cand_row_ptr,
  * dae_score_rank_of: the same behind dae_encode with the inference keep-probabilities, as dae_score_candidates.
  * dae_rank_of_plan: out = {rows per row group, answers of a row per pass C, row groups, workgroups per row group} of a call of
  *   these sizes (csrc/rank_of_plan.h); host only.
+ *
+ * dae_mix_rank_of (on the TITLE scorer's context; `dae` the DAE's, same stream): the same ranks under the TITLE MIX, the score
+ *   `--challenge` ranks for every titled batch,
+ *       y[r, c] = sigmoid(feat[r,:] . OutW_T[c,:] + Out_b[c]) * w_title[r] + sigmoid(h[r,:] . W_dec[c,:] + b_dec[c]) * w_playlist[r]
+ *   with dae_mix_scores' operations in its order (the value of dae_mix_candidates at [r, c], bit for bit, and the value the titled
+ *   ranking calls list by).  The contract is dae_decode_rank_of's with "fp32 logit" replaced by "mixed score y": the order is y
+ *   descending under the same composite key, ties -- the common case, since sigmoids saturate -- by column ascending; out_score
+ *   [n_ans] (nullable) holds y, -inf beside rank -1 for padding, artists and seeds, NaN for an out-of-range id (which ORs bit 0
+ *   into *status).  Every row is ranked by y, rows with w_title == 0 included.  Arguments as dae_mix_candidates takes them (h [B][H]
+ *   contiguous: ld_h == H; feat [B][ld_feat], OutW_T [V][ld_feat]; ld_feat % 4 == 0, ld_feat <= 1024; both tensors 16-byte aligned),
+ *   then n_tracks, the seed CSR and the answers as above.  BOTH contexts must hold a plain DAE_DTYPE_F32 image over [0, V) (the
+ *   title context's of OutW_T / Out_b, the DAE's of W_dec / b_dec) and be bound to one stream: no fp32 image, a catalogue image, a
+ *   shard image, or dae_set_score_mix left set on either give DAE_ERR_STATE, the message naming the context; every refusal comes
+ *   before any launch.  Launches (all on the shared stream, nothing read back): dae_mix_candidates over the answers,
+ *   dae_decode_mix_term on the DAE's context, the memset, the sort, the counting launch with a mix epilogue over the title image,
+ *   the finishing launch (the seeds leave by their mixed value).  Geometry: dae_rank_of_plan(B, ld_feat, n_ans).  Scratch, all in
+ *   the title context (the DAE's keeps its packed hidden rows): 24 bytes per answer, plus 4 x B x nt32 bytes for the DAE's term
+ *   (nt32 = n_tracks rounded up to 32, never past V); a steady state allocates nothing.
  * NOT BUILT: a bf16 count (the thresholds would have to come out of the bf16 MFMA chain), vocabulary shards, catalogue images,
- * the titled (mixed) score, the pipeline. */
+ * the pipeline (plain and titled alike). */
 int dae_rank_of_plan(int B, int H, int n_ans, int32_t out[4]);
 int dae_decode_rank_of(dae_ctx* ctx, const float* h, int B, int H, const float* W_dec, const float* b_dec, int V, int n_tracks,
                        const int32_t* seed_row_ptr, const int32_t* seed_col, const int32_t* ans_row_ptr, const int32_t* ans_col,
@@ -594,6 +612,11 @@ int dae_score_rank_of(dae_ctx* ctx, const int32_t* row_ptr, const int32_t* col, 
                       const float* b_enc, int V, int H, int B, const float* W_dec, const float* b_dec, int n_tracks,
                       const int32_t* seed_row_ptr, const int32_t* seed_col, const int32_t* ans_row_ptr, const int32_t* ans_col,
                       int n_ans, int32_t* out_rank, float* out_logit, int32_t* status);
+int dae_mix_rank_of(dae_ctx* title_ctx, dae_ctx* dae, const float* h, int64_t ld_h, int H, const float* W_dec,
+                    const float* b_dec, const float* feat, int64_t ld_feat, const float* OutW_T, const float* Out_b,
+                    const float* w_title, const float* w_playlist, int B, int V, int n_tracks,
+                    const int32_t* seed_row_ptr, const int32_t* seed_col, const int32_t* ans_row_ptr,
+                    const int32_t* ans_col, int n_ans, int32_t* out_rank, float* out_score, int32_t* status);
 
 /* ---- a catalogue: rank a SHARED subset of the track columns (csrc/catalogue.hip) -------------------------------------------
  *

@@ -31,7 +31,7 @@ EXPORTS = [
     "dae_pipeline_release", "dae_pipeline_stats", "dae_pipeline_exact_margin", "dae_pipeline_times", "dae_pipeline_last_error",
     "dae_rank_metrics", "dae_pipeline_enable_eval", "dae_pipeline_submit_eval", "dae_pipeline_poll_eval",
     "dae_decode_candidates", "dae_score_candidates", "dae_mix_candidates", "dae_rank_candidates",
-    "dae_rank_of_plan", "dae_decode_rank_of", "dae_score_rank_of",
+    "dae_rank_of_plan", "dae_decode_rank_of", "dae_score_rank_of", "dae_mix_rank_of",
     "dae_catalogue_create", "dae_catalogue_destroy", "dae_prepack_decoder_catalogue", "dae_score_topk_catalogue",
     "dae_decode_topk_catalogue", "dae_title_score_catalogue", "dae_pipeline_set_catalogue",
 ]
@@ -179,6 +179,8 @@ def load():
     lib.dae_rank_of_plan.argtypes = [c_int, c_int, c_int, ctypes.POINTER(ctypes.c_int32)]
     lib.dae_decode_rank_of.argtypes = [vp, vp, c_int, c_int, vp, vp, c_int, c_int, vp, vp, vp, vp, c_int, vp, vp, vp]
     lib.dae_score_rank_of.argtypes = [vp, vp, vp, vp, vp, vp, c_int, c_int, c_int, vp, vp, c_int, vp, vp, vp, vp, c_int, vp, vp, vp]
+    lib.dae_mix_rank_of.argtypes = [vp, vp, vp, c_i64, c_int, vp, vp, vp, c_i64, vp, vp, vp, vp, c_int, c_int, c_int, vp, vp, vp, vp,
+                                    c_int, vp, vp, vp]
     lib.dae_catalogue_create.argtypes = [vp, vp, c_int, c_int, ctypes.POINTER(vp)]
     lib.dae_catalogue_destroy.argtypes = [vp]
     lib.dae_prepack_decoder_catalogue.argtypes = [vp, vp, vp, vp, c_int, c_int, c_int]
@@ -650,6 +652,20 @@ class Context:
                                               _ptr(W_dec), _ptr(b_dec), int(n_tracks), _ptr(seed_row_ptr), _ptr(seed_col),
                                               _ptr(ans[0]), _ptr(ans[1]), int(n_ans), _ptr(out_rank), _ptr(out_logit),
                                               _ptr(status)))
+
+    def mix_rank_of(self, dae_ctx, h, W_dec, b_dec, feat, OutW_T, Out_b, w_title, w_playlist, n_tracks, seed_row_ptr, seed_col, ans,
+                    n_ans, out_rank, out_score=None, status=None):
+        """On the title scorer's context: decode_rank_of under the title mix -- the ranks by y = sigmoid(z_title) * w_title +
+        sigmoid(z_dae) * w_playlist, out_score = y (dae_mix_rank_of).  Both contexts hold their plain fp32 image over all
+        columns and are bound to one stream; h [B, H] contiguous."""
+        B, H = h.shape
+        if not (h.is_contiguous() and feat.is_contiguous()):
+            raise ValueError("mix_rank_of: contiguous hidden and feature rows are required")
+        self.check(self.lib.dae_mix_rank_of(self.h, dae_ctx.h, _ptr(h), H, H, _ptr(W_dec),
+                                            _ptr(b_dec), _ptr(feat), int(feat.shape[1]), _ptr(OutW_T), _ptr(Out_b), _ptr(w_title),
+                                            _ptr(w_playlist), B, int(W_dec.shape[0]), int(n_tracks), _ptr(seed_row_ptr),
+                                            _ptr(seed_col), _ptr(ans[0]), _ptr(ans[1]), int(n_ans), _ptr(out_rank),
+                                            _ptr(out_score), _ptr(status)))
 
     # ---- a catalogue: a shared, ascending subset of the track columns (csrc/catalogue.hip; `Catalogue` below) ------------------
     def prepack_decoder_catalogue(self, cat, W_dec, b_dec, dtype=DAE_DTYPE_F32):

@@ -54,7 +54,7 @@ int dae_ensure_guard(dae_ctx* ctx)
 
 extern "C" {
 
-int dae_version(void) { return 1001; }
+int dae_version(void) { return 1002; }
 
 int dae_create(int device, dae_ctx** out)
 {

@@ -25,7 +25,17 @@
 //   5. rank_of_finish_kernel, a workgroup per row: prefix sums -> counts; then the row's SEEDS (each distinct seed track once):
 //      their canonical logits by the same chain, one subtracted from every answer a seed precedes, and an answer that is a seed
 //      becomes (-1, -inf).  Results go out in the caller's order.
+//
+// THE TITLED CALL (dae_mix_rank_of; DESIGN.md section 4d "Under the title mix") ranks by the MIXED score
+//     y[r, c] = sigmoid(z_title[r, c]) * w_title[r] + sigmoid(z_dae[r, c]) * w_playlist[r]                    (mixf, mix_common.h)
+// with the same launches on the TITLE scorer's context: y_a from dae_mix_candidates; the DAE's term of the track columns stored
+// transposed by dae_decode_mix_term (on the DAE's context); the counting launch is the MIX instantiation of the kernel below
+// over the title image (Output_W^T / Output_b against the title features), whose epilogue turns every accumulator element into
+// y with the operations and order of the fp32 mix epilogue of decode_generic.hip before it is counted; the finishing launch
+// takes the seeds out by their mixed value (both canonical chains per distinct seed).  The composite, the buckets, the prefix
+// sums are the plain call's: the kernels are the same templates.
 #include "decode_common.h"
+#include "mix_common.h"             // mixf
 #include "rank_of_plan.h"
 
 namespace {
@@ -52,6 +62,11 @@ struct RankP {
     int R_TILE;
     const float* h; int H; const float* W; const float* b;   // row-major tensors (the seeds' chains)
     int32_t* out_rank; float* out_logit;
+    // the titled call alone (the MIX instantiations): the DAE's term of the track columns, transposed; the mixing weights; the
+    // title scorer's row-major tensors and feature rows (the seeds' second chain).  h / H / W / b above are then the DAE's,
+    // Wp / bias / hp / G the title image's, z the mixed values y_a.
+    const float* mixT; int64_t mix_ld; const float* w_title; const float* w_playlist;
+    const float* feat; int HF; const float* WT; const float* bT;
 };
 
 // a row's answers: [beg, end) of ans_col, clamped to what the caller said exists
@@ -91,7 +106,8 @@ __global__ __launch_bounds__(256) void rank_of_prep_kernel(const RankP p)
     }
 }
 
-template <int RB, int GT>
+// MIX: the titled call -- the image is the title scorer's, and what is counted is y, not the logit (the mix epilogue below)
+template <int RB, int GT, bool MIX>
 __global__ __launch_bounds__(RO_THREADS, 1) void rank_of_count_kernel(const RankP p)
 {
     extern __shared__ __attribute__((aligned(16))) float4 lds4[];
@@ -169,10 +185,12 @@ __global__ __launch_bounds__(RO_THREADS, 1) void rank_of_count_kernel(const Rank
         int len_r[RB];
         unsigned n0[RB];
         unsigned long long first[RB], last[RB];
+        float wt_r[MIX ? RB : 1];
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) {
             const int i = rb * 32 + j;
             len_r[rb] = llen[i];
+            if (MIX) wt_r[rb] = len_r[rb] > 0 ? p.w_title[rg * R_TILE + i] : 0.0f;      // (a row at or past B has no answers)
             n0[rb] = 0u;
             first[rb] = len_r[rb] > 0 ? lthr[(size_t)i * C] : 0ull;                       // (no x is below 0 ...
             last[rb] = len_r[rb] > 0 ? lthr[(size_t)i * C + len_r[rb] - 1] : 0ull;        //  ... and every x is >= 0: nothing counts)
@@ -197,6 +215,22 @@ __global__ __launch_bounds__(RO_THREADS, 1) void rank_of_count_kernel(const Rank
                 float4 bq[4];
 #pragma unroll
                 for (int qd = 0; qd < 4; ++qd) bq[qd] = *reinterpret_cast<const float4*>(bp + 8 * qd);
+
+                // the titled call: the DAE's term of this tile's elements, requested now, consumed in the epilogue (as
+                // decode_generic.hip loads mixv).  A half wave reads 32 consecutive rows of one column; a row without
+                // answers in this pass -- every row at or past B is one -- and a column that is not ranked form no address
+                float mixv[MIX ? RB : 1][16];
+                if (MIX) {
+#pragma unroll
+                    for (int rb = 0; rb < RB; ++rb) {
+                        const int row = rg * R_TILE + rb * 32 + j;
+#pragma unroll
+                        for (int e = 0; e < 16; ++e) {
+                            const int lc = t * 32 + 4 * hi + (e & 3) + 8 * (e >> 2);
+                            mixv[rb][e] = (len_r[rb] > 0 && lc < p.n_tracks) ? p.mixT[(size_t)lc * p.mix_ld + row] : 0.0f;
+                        }
+                    }
+                }
 
                 f32x16 acc[RB];
 #pragma unroll
@@ -246,8 +280,17 @@ __global__ __launch_bounds__(RO_THREADS, 1) void rank_of_count_kernel(const Rank
                     unsigned* cn = lcnt + (size_t)(rb * 32 + j) * C;
 #pragma unroll
                     for (int qd = 0; qd < 4; ++qd) {
-                        const float z4[4] = {acc[rb][4 * qd + 0] + bq[qd].x, acc[rb][4 * qd + 1] + bq[qd].y,
-                                             acc[rb][4 * qd + 2] + bq[qd].z, acc[rb][4 * qd + 3] + bq[qd].w};
+                        float z4[4] = {acc[rb][4 * qd + 0] + bq[qd].x, acc[rb][4 * qd + 1] + bq[qd].y,
+                                       acc[rb][4 * qd + 2] + bq[qd].z, acc[rb][4 * qd + 3] + bq[qd].w};
+                        if (MIX) {
+                            // THE MIX EPILOGUE: the operations and order of decode_generic.hip's fp32 mix epilogue (title * w_title
+                            // + the stored DAE term; two roundings, no contraction), so x == y_a bit for bit at an answer's own column
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) {
+                                const float ts = dae_sigmoidf(z4[e]) * wt_r[rb];
+                                z4[e] = ts + mixv[rb][4 * qd + e];
+                            }
+                        }
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             const int col = tcol0 + 8 * qd + e;
@@ -285,9 +328,43 @@ __global__ __launch_bounds__(RO_THREADS, 1) void rank_of_count_kernel(const Rank
     }
 }
 
+// the canonical chain of one column over a row held in LDS: acc = fmaf(hrow[k], Wrow[k], acc) over k = 0 .. H-1 from +0 (H % 4 == 0)
+__device__ __forceinline__ float ro_chain(const float* hrow, const float* Wrow, int H)
+{
+    const float4* wr = reinterpret_cast<const float4*>(Wrow);
+    float acc = 0.0f;
+    const int n4 = H >> 2;
+    int k4 = 0;
+    for (; k4 + 3 < n4; k4 += 4) {
+        float4 w[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) w[u] = wr[k4 + u];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int kb = 4 * (k4 + u);
+            acc = fmaf(hrow[kb], w[u].x, acc);
+            acc = fmaf(hrow[kb + 1], w[u].y, acc);
+            acc = fmaf(hrow[kb + 2], w[u].z, acc);
+            acc = fmaf(hrow[kb + 3], w[u].w, acc);
+        }
+    }
+    for (; k4 < n4; ++k4) {
+        const float4 w = wr[k4];
+        const int kb = 4 * k4;
+        acc = fmaf(hrow[kb], w.x, acc);
+        acc = fmaf(hrow[kb + 1], w.y, acc);
+        acc = fmaf(hrow[kb + 2], w.z, acc);
+        acc = fmaf(hrow[kb + 3], w.w, acc);
+    }
+    return acc;
+}
+
+// MIX: the seeds leave by their MIXED value -- both canonical chains and mixf per distinct seed
+template <bool MIX>
 __global__ __launch_bounds__(256) void rank_of_finish_kernel(const RankP p)
 {
     __shared__ float hrow[RO_MAXH];
+    __shared__ float frow[MIX ? RO_MAXH : 1];
     __shared__ unsigned long long scomp[256];
     __shared__ int scol[256];
     const int row = blockIdx.x, tid = threadIdx.x;
@@ -316,7 +393,10 @@ __global__ __launch_bounds__(256) void rank_of_finish_kernel(const RankP p)
     if (!p.seed_row_ptr) return;
     const int sb = p.seed_row_ptr[row], se = p.seed_row_ptr[row + 1];
     if (se <= sb) return;
-    for (int k = tid; k < RO_MAXH; k += 256) hrow[k] = k < p.H ? p.h[(size_t)row * p.H + k] : 0.0f;
+    for (int k = tid; k < RO_MAXH; k += 256) {
+        hrow[k] = k < p.H ? p.h[(size_t)row * p.H + k] : 0.0f;
+        if (MIX) frow[k] = k < p.HF ? p.feat[(size_t)row * p.HF + k] : 0.0f;
+    }
     __syncthreads();                                              // (also orders this workgroup's stores to out_rank before its reads below)
 
     // the seeds in blocks of 256, a lane each: the canonical chain over the row-major tensor; a seed listed twice counts once
@@ -329,32 +409,13 @@ __global__ __launch_bounds__(256) void rank_of_finish_kernel(const RankP p)
             bool ok = c >= 0 && c < p.n_tracks;
             for (int u = sb; ok && u < si; ++u) ok = p.seed_col[u] != c;
             if (ok) {
-                const float4* wr = reinterpret_cast<const float4*>(p.W + (size_t)c * p.H);
-                float acc = 0.0f;
-                const int n4 = p.H >> 2;
-                int k4 = 0;
-                for (; k4 + 3 < n4; k4 += 4) {
-                    float4 w[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) w[u] = wr[k4 + u];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int kb = 4 * (k4 + u);
-                        acc = fmaf(hrow[kb], w[u].x, acc);
-                        acc = fmaf(hrow[kb + 1], w[u].y, acc);
-                        acc = fmaf(hrow[kb + 2], w[u].z, acc);
-                        acc = fmaf(hrow[kb + 3], w[u].w, acc);
-                    }
+                const float zd = ro_chain(hrow, p.W + (size_t)c * p.H, p.H) + p.b[c];
+                if (MIX) {
+                    const float zt = ro_chain(frow, p.WT + (size_t)c * p.HF, p.HF) + p.bT[c];
+                    sc = ro_comp(mixf(zt, zd, p.w_title[row], p.w_playlist[row]), c);
+                } else {
+                    sc = ro_comp(zd, c);
                 }
-                for (; k4 < n4; ++k4) {
-                    const float4 w = wr[k4];
-                    const int kb = 4 * k4;
-                    acc = fmaf(hrow[kb], w.x, acc);
-                    acc = fmaf(hrow[kb + 1], w.y, acc);
-                    acc = fmaf(hrow[kb + 2], w.z, acc);
-                    acc = fmaf(hrow[kb + 3], w.w, acc);
-                }
-                sc = ro_comp(acc + p.b[c], c);
             } else {
                 c = -1;
             }
@@ -384,23 +445,36 @@ __global__ __launch_bounds__(256) void rank_of_finish_kernel(const RankP p)
     }
 }
 
-template <int RB, int GT>
+template <int RB, int GT, bool MIX>
 int launch_count(dae_ctx* ctx, const dae_ro_plan& pl, const RankP& p)
 {
-    DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &rank_of_count_kernel<RB, GT>, DAE_RO_LDS_BYTES));
+    DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &rank_of_count_kernel<RB, GT, MIX>, DAE_RO_LDS_BYTES));
     hipEvent_t e0 = nullptr, e1 = nullptr;
     dae_take_profile_events(ctx, "rank_of_count_kernel", e0, e1);
     if (e0) DAE_HIP_CHECK(ctx, hipEventRecord(e0, ctx->stream));
-    hipLaunchKernelGGL((rank_of_count_kernel<RB, GT>), dim3(pl.grid), dim3(RO_THREADS), pl.lds_bytes, ctx->stream, p);
+    hipLaunchKernelGGL((rank_of_count_kernel<RB, GT, MIX>), dim3(pl.grid), dim3(RO_THREADS), pl.lds_bytes, ctx->stream, p);
     DAE_CHECK_LAUNCH(ctx, "rank_of_count_kernel");
     if (e1) DAE_HIP_CHECK(ctx, hipEventRecord(e1, ctx->stream));
     return DAE_OK;
 }
 
-// everything both entry points refuse, before any launch
+// the context's fp32 image is a plain one of H-wide rows over [0, V); `who` names the context in the titled call's messages
+int check_image(dae_ctx* ctx, const dae_packed& pk, int V, int H, const char* who)
+{
+    if (!pk.valid) return dae_fail(ctx, DAE_ERR_STATE, "rank_of%s needs a DAE_DTYPE_F32 image of the decoder: none is prepacked", who);
+    if (pk.cat_id != 0)
+        return dae_fail(ctx, DAE_ERR_STATE, "rank_of%s: the fp32 image is a catalogue image, not one of the vocabulary's own columns", who);
+    if (pk.col_lo != 0 || pk.col_hi != V || pk.V != V)
+        return dae_fail(ctx, DAE_ERR_STATE, "rank_of%s: the fp32 image is a shard image over [%d, %d) of %d columns, not one over [0, %d)",
+                        who, pk.col_lo, pk.col_hi, pk.V, V);
+    if (pk.H != H) return dae_fail(ctx, DAE_ERR_ARG, "rank_of%s: H=%d does not match prepacked H=%d", who, H, pk.H);
+    return DAE_OK;
+}
+
+// everything the entry points refuse, before any launch (the titled call: on the title context, with the title scorer's tensors)
 int check_rank_of(dae_ctx* ctx, const void* h_or_enc, int B, int H, const float* W_dec, const float* b_dec, int V, int n_tracks,
                   const int32_t* seed_row_ptr, const int32_t* seed_col, const int32_t* ans_row_ptr, const int32_t* ans_col,
-                  int n_ans, const int32_t* out_rank, dae_ro_plan* pl)
+                  int n_ans, const int32_t* out_rank, dae_ro_plan* pl, const char* who = "")
 {
     if (!h_or_enc || !W_dec || !b_dec || !ans_row_ptr || !ans_col || !out_rank) return dae_fail(ctx, DAE_ERR_ARG, "null pointer");
     if (n_ans < 0) return dae_fail(ctx, DAE_ERR_ARG, "n_ans=%d is negative", n_ans);
@@ -411,21 +485,23 @@ int check_rank_of(dae_ctx* ctx, const void* h_or_enc, int B, int H, const float*
     if ((seed_row_ptr == nullptr) != (seed_col == nullptr))
         return dae_fail(ctx, DAE_ERR_ARG, "seed_row_ptr and seed_col must both be given or both null");
     if (reinterpret_cast<uintptr_t>(W_dec) % 16) return dae_fail(ctx, DAE_ERR_ARG, "the decoder tensor must be 16-byte aligned");
-    const dae_packed& pk = ctx->pk_f32;
-    if (!pk.valid) return dae_fail(ctx, DAE_ERR_STATE, "rank_of needs a DAE_DTYPE_F32 image of the decoder: none is prepacked");
-    if (pk.cat_id != 0) return dae_fail(ctx, DAE_ERR_STATE, "rank_of: the fp32 image is a catalogue image, not one of the vocabulary's own columns");
-    if (pk.col_lo != 0 || pk.col_hi != V || pk.V != V)
-        return dae_fail(ctx, DAE_ERR_STATE, "rank_of: the fp32 image is a shard image over [%d, %d) of %d columns, not one over [0, %d)",
-                        pk.col_lo, pk.col_hi, pk.V, V);
-    if (pk.H != H) return dae_fail(ctx, DAE_ERR_ARG, "H=%d does not match prepacked H=%d", H, pk.H);
+    const int rc = check_image(ctx, ctx->pk_f32, V, H, who);
+    if (rc) return rc;
     *pl = dae_plan_rank_of(B, H, n_ans);
     if (pl->C <= 0) return dae_fail(ctx, DAE_ERR_ARG, "rank_of: no geometry for B=%d H=%d", B, H);
     return DAE_OK;
 }
 
+// the titled call: the DAE's side of the mix (ctx is then the title context, h / H / W_dec / b_dec the title features and tensors)
+struct RoMix {
+    dae_ctx* dae; const float* h; int H; const float* W_dec; const float* b_dec;
+    const float* w_title; const float* w_playlist;
+};
+
 int rank_of_core(dae_ctx* ctx, const dae_ro_plan& pl, const float* h, int B, int H, const float* W_dec, const float* b_dec,
                  int V, int n_tracks, const int32_t* seed_row_ptr, const int32_t* seed_col, const int32_t* ans_row_ptr,
-                 const int32_t* ans_col, int n_ans, int32_t* out_rank, float* out_logit, int32_t* status)
+                 const int32_t* ans_col, int n_ans, int32_t* out_rank, float* out_logit, int32_t* status,
+                 const RoMix* mix = nullptr)
 {
     if (n_ans == 0) return DAE_OK;
     const dae_packed& pk = ctx->pk_f32;
@@ -434,6 +510,12 @@ int rank_of_core(dae_ctx* ctx, const dae_ro_plan& pl, const float* h, int B, int
     const size_t bytes = na * 8 + na * 4 * 3 + (size_t)pl.n_rg * 4;
     int rc = dae_reserve(ctx, ctx->rank_of, bytes);
     if (rc) return rc;
+    // the titled call: the DAE's term of the track columns, [n_tracks rounded up to 32, never past the image][B] (dae_title_rank's buffer)
+    const size_t nt32 = (size_t)((n_tracks + 31) / 32 * 32 < V ? (n_tracks + 31) / 32 * 32 : V);
+    if (mix) {
+        rc = dae_reserve(ctx, ctx->title_y1, nt32 * (size_t)B * sizeof(float));
+        if (rc) return rc;
+    }
     char* base = static_cast<char*>(ctx->rank_of.p);
     RankP p{};
     p.thr = reinterpret_cast<unsigned long long*>(base);
@@ -443,9 +525,18 @@ int rank_of_core(dae_ctx* ctx, const dae_ro_plan& pl, const float* h, int B, int
     p.gcnt = reinterpret_cast<unsigned*>(base + na * 16);
     p.glen = reinterpret_cast<int*>(base + na * 20);
 
-    // (a) the thresholds: the candidate chain over the answers
-    rc = dae_decode_candidates(ctx, h, H, B, H, W_dec, b_dec, V, ans_row_ptr, ans_col, n_ans, DAE_OUT_LOGIT, z, status);
-    if (rc) return rc;
+    // (a) the thresholds: the candidate chain(s) over the answers -- the logit, or the mixed value with the DAE's term behind it
+    if (mix) {
+        rc = dae_mix_candidates(ctx, mix->dae, mix->h, mix->H, mix->H, mix->W_dec, mix->b_dec, h, H, W_dec, b_dec, mix->w_title,
+                                mix->w_playlist, B, V, ans_row_ptr, ans_col, n_ans, z, status);
+        if (rc) return rc;
+        rc = dae_decode_mix_term(mix->dae, mix->h, B, mix->H, DAE_DTYPE_F32, mix->w_playlist, n_tracks,
+                                 static_cast<float*>(ctx->title_y1.p), B);
+        if (rc) return dae_fail(ctx, rc, "%s", mix->dae->err.c_str());
+    } else {
+        rc = dae_decode_candidates(ctx, h, H, B, H, W_dec, b_dec, V, ans_row_ptr, ans_col, n_ans, DAE_OUT_LOGIT, z, status);
+        if (rc) return rc;
+    }
     DAE_HIP_CHECK(ctx, hipMemsetAsync(p.gcnt, 0, na * 4 + (size_t)pl.n_rg * 4, ctx->stream));
 
     // the hidden rows in the MFMA operand order, for this call's row groups
@@ -467,18 +558,34 @@ int rank_of_core(dae_ctx* ctx, const dae_ro_plan& pl, const float* h, int B, int
     p.seed_row_ptr = seed_row_ptr; p.seed_col = seed_col;
     p.h = h; p.H = H; p.W = W_dec; p.b = b_dec;
     p.out_rank = out_rank; p.out_logit = out_logit;
+    if (mix) {
+        p.h = mix->h; p.H = mix->H; p.W = mix->W_dec; p.b = mix->b_dec;
+        p.feat = h; p.HF = H; p.WT = W_dec; p.bT = b_dec;
+        p.mixT = static_cast<const float*>(ctx->title_y1.p); p.mix_ld = B;
+        p.w_title = mix->w_title; p.w_playlist = mix->w_playlist;
+    }
 
     hipLaunchKernelGGL(rank_of_prep_kernel, dim3(B), dim3(256), 0, ctx->stream, p);
     DAE_CHECK_LAUNCH(ctx, "rank_of_prep_kernel");
     const bool h256 = pl.G == 32;
-    switch (pl.R_TILE) {
-        case 128: rc = h256 ? launch_count<4, 32>(ctx, pl, p) : launch_count<4, 0>(ctx, pl, p); break;
-        case 64:  rc = h256 ? launch_count<2, 32>(ctx, pl, p) : launch_count<2, 0>(ctx, pl, p); break;
-        case 32:  rc = launch_count<1, 0>(ctx, pl, p); break;
-        default:  rc = dae_fail(ctx, DAE_ERR_ARG, "bad R_TILE %d", pl.R_TILE);
+    if (mix) {                                  // (the run-time k-group count at every title feature width)
+        switch (pl.R_TILE) {
+            case 128: rc = launch_count<4, 0, true>(ctx, pl, p); break;
+            case 64:  rc = launch_count<2, 0, true>(ctx, pl, p); break;
+            case 32:  rc = launch_count<1, 0, true>(ctx, pl, p); break;
+            default:  rc = dae_fail(ctx, DAE_ERR_ARG, "bad R_TILE %d", pl.R_TILE);
+        }
+    } else {
+        switch (pl.R_TILE) {
+            case 128: rc = h256 ? launch_count<4, 32, false>(ctx, pl, p) : launch_count<4, 0, false>(ctx, pl, p); break;
+            case 64:  rc = h256 ? launch_count<2, 32, false>(ctx, pl, p) : launch_count<2, 0, false>(ctx, pl, p); break;
+            case 32:  rc = launch_count<1, 0, false>(ctx, pl, p); break;
+            default:  rc = dae_fail(ctx, DAE_ERR_ARG, "bad R_TILE %d", pl.R_TILE);
+        }
     }
     if (rc) return rc;
-    hipLaunchKernelGGL(rank_of_finish_kernel, dim3(B), dim3(256), 0, ctx->stream, p);
+    if (mix) hipLaunchKernelGGL(rank_of_finish_kernel<true>, dim3(B), dim3(256), 0, ctx->stream, p);
+    else hipLaunchKernelGGL(rank_of_finish_kernel<false>, dim3(B), dim3(256), 0, ctx->stream, p);
     DAE_CHECK_LAUNCH(ctx, "rank_of_finish_kernel");
     return DAE_OK;
 }
@@ -529,6 +636,37 @@ int dae_score_rank_of(dae_ctx* ctx, const int32_t* row_ptr, const int32_t* col, 
     if (rc) return rc;
     return rank_of_core(ctx, pl, h, B, H, W_dec, b_dec, V, n_tracks, seed_row_ptr, seed_col, ans_row_ptr, ans_col, n_ans, out_rank,
                         out_logit, status);
+}
+
+int dae_mix_rank_of(dae_ctx* title_ctx, dae_ctx* dae, const float* h, int64_t ld_h, int H, const float* W_dec,
+                    const float* b_dec, const float* feat, int64_t ld_feat, const float* OutW_T, const float* Out_b,
+                    const float* w_title, const float* w_playlist, int B, int V, int n_tracks,
+                    const int32_t* seed_row_ptr, const int32_t* seed_col, const int32_t* ans_row_ptr,
+                    const int32_t* ans_col, int n_ans, int32_t* out_rank, float* out_score, int32_t* status)
+{
+    dae_ctx* ctx = title_ctx;
+    if (!ctx) return DAE_ERR_ARG;
+    if (!dae || dae == ctx) return dae_fail(ctx, DAE_ERR_ARG, "dae_mix_rank_of: needs the DAE's context");
+    if (!h || !W_dec || !b_dec || !w_title || !w_playlist) return dae_fail(ctx, DAE_ERR_ARG, "null pointer");
+    if (ctx->device != dae->device) return dae_fail(ctx, DAE_ERR_ARG, "dae_mix_rank_of: contexts on different devices");
+    if (ctx->stream != dae->stream) return dae_fail(ctx, DAE_ERR_STATE, "both contexts must be bound to the same stream");
+    if (ctx->mixT) return dae_fail(ctx, DAE_ERR_STATE, "dae_mix_rank_of sets the mix itself: clear dae_set_score_mix on the title context");
+    if (dae->mixT) return dae_fail(ctx, DAE_ERR_STATE, "dae_mix_rank_of: clear dae_set_score_mix on the DAE's context");
+    if (H <= 0 || (H % 4) != 0 || H > RO_MAXH) return dae_fail(ctx, DAE_ERR_ARG, "H=%d must be a multiple of 4 in [4, %d]", H, RO_MAXH);
+    if (ld_h != H) return dae_fail(ctx, DAE_ERR_ARG, "ld_h=%lld: contiguous hidden rows (ld_h == H = %d) are required", (long long)ld_h, H);
+    if (ld_feat <= 0 || (ld_feat % 4) != 0 || ld_feat > RO_MAXH)
+        return dae_fail(ctx, DAE_ERR_ARG, "ld_feat=%lld must be a multiple of 4 in [4, %d]", (long long)ld_feat, RO_MAXH);
+    if ((reinterpret_cast<uintptr_t>(W_dec) | reinterpret_cast<uintptr_t>(OutW_T)) % 16)
+        return dae_fail(ctx, DAE_ERR_ARG, "the decoder tensor and Output_W^T must be 16-byte aligned");
+    dae_ro_plan pl;
+    int rc = check_rank_of(ctx, feat, B, (int)ld_feat, OutW_T, Out_b, V, n_tracks, seed_row_ptr, seed_col, ans_row_ptr, ans_col, n_ans,
+                           out_rank, &pl, " (the title context)");
+    if (rc) return rc;
+    rc = check_image(ctx, dae->pk_f32, V, H, " (the DAE's context)");
+    if (rc) return rc;
+    const RoMix mix{dae, h, H, W_dec, b_dec, w_title, w_playlist};
+    return rank_of_core(ctx, pl, feat, B, (int)ld_feat, OutW_T, Out_b, V, n_tracks, seed_row_ptr, seed_col, ans_row_ptr, ans_col, n_ans,
+                        out_rank, out_score, status, &mix);
 }
 
 }  // extern "C"

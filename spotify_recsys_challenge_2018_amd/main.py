@@ -5,7 +5,7 @@ the same config.ini schema:
 
     [BASE] verbose data_dir result_dir testsize   (+ optional, this build only: train_dtype = f32 | bf16, decode_dtype = f32 | bf16 | exact_bf16,
                                                   eval_metrics = rprecision | all, train_feed = host | device,
-                                                  eval_ranks = off | on)
+                                                  eval_ranks = off | on, eval_mixed_ranks = off | on)
     [DAE] epochs batch lr reg_lambda hidden test_seed update_seed keep_prob input_kp firstN_range initval save
     [PRETRAIN] epochs batch lr reg_lambda save
     [TITLE] ... (parsed for compatibility; the title models are outside the scoring path)
@@ -71,7 +71,7 @@ class Conf:
         self.dir = dir
         self.ini = ini
         self._load('BASE')
-        # five OPTIONAL [BASE] keys this build adds (absent from the reference's files, which then mean fp32 / rprecision):
+        # six OPTIONAL [BASE] keys this build adds (absent from the reference's files, which then mean fp32 / rprecision):
         #   train_dtype  = f32 | bf16   arithmetic of the training step's three GEMMs (BASELINE.json configs[3])
         #   decode_dtype = f32 | bf16 | exact_bf16   arithmetic of the scoring decode: fp32 MFMA (bit-exact path), bf16
         #                  (configs[4]), or the bf16 GEMM as a filter with the survivors recomputed in fp32 (north_star:
@@ -85,13 +85,17 @@ class Conf:
         #   eval_ranks   = off | on           with `on` the evaluation of a test split logs one more line behind the others: MRR, median
         #                  rank and recall@500 / 1 000 / 5 000 / 10 000 of the held-out tracks, from their EXACT ranks among all
         #                  rankable tracks (models/DAEs.py rank_of; feed by feed).  Refused under --title (main_train.run): ranks under
-        #                  the title mix are not built
+        #                  the title mix are eval_mixed_ranks'
+        #   eval_mixed_ranks = off | on       --title only: with `on` one more line per test split behind the others, "mixed ranks: ...",
+        #                  the same figures from the EXACT ranks under the title mix (models/DAEs.py DAE_title.mixed_rank_of, with the
+        #                  split's titles and titles_use as the title evaluation feeds them).  Refused outside --title (main_train.run)
         self.eval_metrics = 'rprecision'
         self.train_feed = 'host'
         self.eval_ranks = 'off'
+        self.eval_mixed_ranks = 'off'
         for key, allowed in (('train_dtype', ('f32', 'bf16')), ('decode_dtype', ('f32', 'bf16', 'exact_bf16')),
                              ('eval_metrics', ('rprecision', 'all')), ('train_feed', ('host', 'device')),
-                             ('eval_ranks', ('off', 'on'))):
+                             ('eval_ranks', ('off', 'on')), ('eval_mixed_ranks', ('off', 'on'))):
             if key in self.ini['BASE']:
                 val = self.ini['BASE'][key].strip().lower()
                 if val not in allowed:
@@ -213,6 +217,9 @@ def main(argv=None):
         conf.set_title_conf()
         main_train.run(conf, args.testmode)
     elif args.challenge:
+        if conf.eval_mixed_ranks == 'on':
+            raise ValueError("[BASE] eval_mixed_ranks = on is available under --title only: --challenge evaluates nothing "
+                             "(remove the key or set eval_mixed_ranks = off)")
         conf.set_title_conf()
         conf.set_challenge_oonf()
         main_challenge.run(conf)

@@ -172,10 +172,43 @@ def _log_ranks(conf, readers_test, model):
                   % (seed_num, mrr, med, ' '.join("recall@%d %f" % (k, v) for k, v in zip(RANK_CUTS, rec))))
 
 
+def eval_mixed_ranks(reader_test, conf, model):
+    """[BASE] eval_mixed_ranks = on (--title): `eval_ranks` under the title mix -- model.mixed_rank_of, feed by feed, with the
+    split's titles and titles_use as `eval` feeds them (a row without a title takes titles_use = 0 and an all-padding title)
+    -> (MRR, median rank, recall at RANK_CUTS).  A held-out track outside the vocabulary (-1) is a miss that counts in the
+    denominators."""
+    from ..models.DAEs import SEEDS_FROM_INPUT
+    pad = [-1] * conf.strmaxlen
+    ranks = []
+    while True:
+        x_positions, test_seed, test_answer, titles, x_ones = reader_test.next_batch_test()
+        use = np.array([0.0 if t is None else 1.0 for t in titles], np.float32)
+        for row in model.mixed_rank_of(x_positions, x_ones, [list(a) for a in test_answer], SEEDS_FROM_INPUT,
+                                       [t if t is not None else pad for t in titles], use, n_rows=len(test_seed)):
+            ranks.append(row)
+        if reader_test.test_idx == 0:
+            break
+    ranks = np.concatenate(ranks) if ranks else np.zeros(0, np.int32)
+    return met.mean_reciprocal_rank(ranks), met.median_rank(ranks), met.recall_at(ranks, RANK_CUTS)
+
+
+def _log_mixed_ranks(conf, readers_test, model):
+    """As `_log_ranks`, for [BASE] eval_mixed_ranks under --title: one more line per split, behind the existing ones."""
+    if getattr(conf, 'eval_mixed_ranks', 'off') != 'on' or getattr(conf, 'mode', None) != 'title':
+        return
+    for seed_num in readers_test:
+        mrr, med, rec = eval_mixed_ranks(readers_test[seed_num], conf, model)
+        log_write(conf, "seed num: %s mixed ranks: mrr %f median %.1f %s"
+                  % (seed_num, mrr, med, ' '.join("recall@%d %f" % (k, v) for k, v in zip(RANK_CUTS, rec))))
+
+
 def _refuse_ranks_under_title(conf):
     if getattr(conf, 'eval_ranks', 'off') == 'on' and getattr(conf, 'mode', None) == 'title':
-        raise ValueError("[BASE] eval_ranks = on is not available under --title: ranks under the title mix are not built "
-                         "(remove the key or set eval_ranks = off)")
+        raise ValueError("[BASE] eval_ranks = on is not available under --title: it ranks by the DAE's own logits; the ranks "
+                         "under the title mix are [BASE] eval_mixed_ranks = on (remove the key or set eval_ranks = off)")
+    if getattr(conf, 'eval_mixed_ranks', 'off') == 'on' and getattr(conf, 'mode', None) != 'title':
+        raise ValueError("[BASE] eval_mixed_ranks = on is available under --title only: the other modes have no title mix "
+                         "(remove the key, set eval_mixed_ranks = off, or use eval_ranks)")
 
 
 def _init_distributed(conf):
@@ -252,6 +285,7 @@ def run(conf, only_testmode):
         out = _eval_splits(readers_test, conf, model, rank, world, extras)
         _log_splits(conf, readers_test, out, extras)
         _log_ranks(conf, readers_test, model)
+        _log_mixed_ranks(conf, readers_test, model)
         return out
 
     # [BASE] train_feed = device: the training set lives on the device and a batch goes up as the reader's draws alone
@@ -307,6 +341,7 @@ def run(conf, only_testmode):
             rprecs = _eval_splits(readers_test, conf, model, rank, world, extras)
             _log_splits(conf, readers_test, rprecs, extras)
             _log_ranks(conf, readers_test, model)
+            _log_mixed_ranks(conf, readers_test, model)
             for seed_num in readers_test:
                 if seed_num in conf.update_seed:
                     cur_eval += rprecs[seed_num]

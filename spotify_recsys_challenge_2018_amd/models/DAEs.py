@@ -845,6 +845,16 @@ class DAE_tied:
             return out
         return [values[rp[r]:rp[r + 1]] for r in range(len(rp) - 1)]
 
+    @staticmethod
+    def _rank_result(values, columns, rp, n_rows, fill):
+        """`rank_of`'s values in the caller's form: [n_rows, C] for the 2-D form (`fill` on the rows behind it), else one array
+        per row."""
+        if isinstance(columns, np.ndarray) and columns.ndim == 2:
+            out = np.full((n_rows, columns.shape[1]), fill, values.dtype)
+            out[:columns.shape[0]] = values.reshape(columns.shape)
+            return out
+        return [values[rp[r]:rp[r + 1]] for r in range(n_rows)]
+
     def score_candidates(self, x_positions, x_ones, candidates, n_rows=None, kind="sigmoid"):
         """What the model thinks of THESE columns for each playlist: `predict(...)[r][candidates[r]]` without the
         [n_batch, n_input] matrix -- per listed (row, column) the canonical fp32 chain of the dense decode, the same bits.
@@ -927,11 +937,7 @@ class DAE_tied:
         self._check_feed()
 
         def shaped(values, fill):
-            if isinstance(columns, np.ndarray) and columns.ndim == 2:
-                out = np.full((n_rows, columns.shape[1]), fill, values.dtype)
-                out[:columns.shape[0]] = values.reshape(columns.shape)
-                return out
-            return [values[rp[r]:rp[r + 1]] for r in range(n_rows)]
+            return self._rank_result(values, columns, rp, n_rows, fill)
 
         if want_logits:
             return shaped(ranks, -1), shaped(logits, -np.inf)
@@ -1609,12 +1615,59 @@ class DAE_title(DAE):
         return self._cand_result(values, candidates, rp)
 
     def rank_of(self, x_positions, x_ones, columns, seeds, n_rows=None, want_logits=False, titles=None, titles_use=None):
-        """`DAE.rank_of`: the ranks under the plain DAE logits.  Ranks under the title mix are not built: with titles in use
-        the call raises ValueError."""
+        """`DAE.rank_of`: the ranks under the plain DAE logits.  With titles in use the call raises ValueError: the ranks under
+        the title mix are `mixed_rank_of`'s."""
         if titles is not None and titles_use is not None and np.any(np.asarray(titles_use)):
-            raise ValueError("rank_of: ranks under the title mix (titles / titles_use) are not built; call it without titles "
-                             "for the ranks of the DAE's own logits")
+            raise ValueError("rank_of: ranks under the title mix (titles / titles_use) are mixed_rank_of's; call rank_of without "
+                             "titles for the ranks of the DAE's own logits")
         return DAE.rank_of(self, x_positions, x_ones, columns, seeds, n_rows=n_rows, want_logits=want_logits)
+
+    def mixed_rank_of(self, x_positions, x_ones, columns, seeds, titles, titles_use, n_rows=None, want_scores=False,
+                      catalogue=None):
+        """`rank_of` under the score the titled `recommend` ranks: per listed (row, column) the number of non-seed track columns
+        that precede it by y = title_score * w_title + dae_score * w_playlist (descending, ties by column ascending), so
+        `mixed_rank_of(feed, recommend(feed, seeds, titles=, titles_use=)[0], seeds, titles, titles_use)` is `arange(k)` per
+        row -- below position 1 024 too, where the titled lists end.  columns, seeds, n_rows, the -1 results: as `rank_of`.
+        The dispatch is `recommend`'s: with no title in use this is `DAE.rank_of(...)`, and want_scores then returns the plain
+        call's LOGITS; otherwise every row is ranked by y (rows with titles_use = 0 included) and want_scores returns y
+        (-inf beside a rank of -1), `recommend`'s score column bit for bit.  Always fp32, whatever the model's decode dtype
+        (both fp32 images are packed for the call).  A scoring shard is refused like the candidate calls, and so is
+        catalogue= (`recommend`'s handle): ranks inside a catalogue are not built."""
+        if catalogue is not None:
+            raise ValueError("mixed_rank_of: ranks inside a catalogue are not built; the ranks are over all track columns "
+                             "(call it without catalogue=)")
+        if titles is None or titles_use is None or not np.any(np.asarray(titles_use)):
+            return DAE.rank_of(self, x_positions, x_ones, columns, seeds, n_rows=n_rows, want_logits=want_scores)
+        import torch
+        n_rows, rp, col, ans, status = self._cand_begin(columns, n_rows, unique=False)
+        tm = self.title_model
+        self._ensure_packed(_lib.DAE_DTYPE_F32)
+        tm._ensure_packed(_lib.DAE_DTYPE_F32)
+        self.ctx.bind_stream()
+        tm.ctx.bind_stream()
+        csr = self._upload_csr(x_positions, x_ones)
+        dev = csr[0].device
+        h = torch.empty((self.n_batch, self.n_hidden), dtype=torch.float32, device=dev)
+        self.ctx.encode(csr[0], csr[1], csr[2], self.weights["encoder_h"], self.biases["encoder_b"], h)
+        w_t, w_p = self._mix_weights(csr, titles_use)
+        feat = tm.features(titles, self.n_batch)
+        d_srp, d_sc = self._seed_csr_dev(seeds, csr)
+        n = int(col.size)
+        rank = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        score = torch.empty(max(n, 1), dtype=torch.float32, device=dev) if want_scores else None
+        tm.ctx.mix_rank_of(self.ctx, h, self.weights["decoder_h"], self.biases["decoder_b"], feat, tm.p["Output_WT"],
+                           tm.p["Output_b"], w_t, w_p, self.n_tracks, d_srp, d_sc, ans, n, rank, out_score=score, status=status)
+        self._cand_status(status)
+        ranks = rank.cpu().numpy()[:n]
+        scores = score.cpu().numpy()[:n] if want_scores else None
+        self._check_feed()
+
+        def shaped(values, fill):
+            return self._rank_result(values, columns, rp, n_rows, fill)
+
+        if want_scores:
+            return shaped(ranks, -1), shaped(scores, -np.inf)
+        return shaped(ranks, -1)
 
     def rank_candidates(self, x_positions, x_ones, candidates, seeds, k=500, n_rows=None, titles=None, titles_use=None,
                         catalogue=None):
