@@ -817,6 +817,39 @@ int dae_decode_mix_term(dae_ctx* ctx, const float* h, int B, int H, int dtype, c
                         float* outT, int64_t ldT);
 int dae_set_score_mix(dae_ctx* ctx, const float* mixT, int64_t ld, int n_cols, const float* w_title);
 
+/* ---- ensembles: rank by a weighted sum of several DAEs' scores ----
+ * THE CANONICAL VALUE.  M >= 1 members in the caller's order m = 0 .. M-1, each with its own encoder and decoder over the same
+ * V columns / n_tracks tracks (hidden sizes may differ).  z_m[r,c]: member m's canonical fp32 logit of its own hidden row (the
+ * chain of dae_decode_dense); a_m[r]: a per-row fp32 weight.  Every operation a single fp32 rounding, no contraction, in this
+ * order:
+ *     t_m[r,c] = dae_sigmoidf(z_m[r,c]) * a_m[r]
+ *     acc      = t_0;   acc = acc + t_m   for m = 1 .. M-2        (untitled: the last member is not in acc)
+ *     untitled:  y = t_{M-1} + acc                                (M = 1: y = t_0)
+ *     titled:    acc also takes t_{M-1};  y = dae_sigmoidf(z_title) * w_title[r] + acc
+ * -- the operations and order of dae_mix_scores and of the fused mix above: titled, M = 1, a_0 = w_playlist is the title mix
+ * bit for bit; untitled, M = 2 is dae_decode_mix_term + dae_set_score_mix + dae_decode_topk.  Ranked in the library's canonical
+ * order over the track columns: y descending, then column ascending, seeds removed, (-1, -inf) padding; out_score holds y.
+ *
+ * dae_decode_mix_term_add: accT[c * ldT + r] = accT[c * ldT + r] + sigmoid(h[r,:] . W_dec[c,:] + b_dec[c]) * row_scale[r] --
+ *   a further member's term added to the buffer dae_decode_mix_term wrote: the same columns and whole 32-column tiles (never
+ *   past the image), rows >= B untouched, DAE_DTYPE_F32 and DAE_DTYPE_BF16 images, any hidden size dae_decode_dense takes.  A
+ *   read-modify-write: one call at a time per buffer.
+ * dae_ensemble_topk: the ranking half in one call, on resident inputs.  members / h / H / row_scale: HOST arrays of M entries --
+ *   member m's context (holding its decoder prepacked in `dtype` over all V columns), its hidden rows [B][H[m]] and its weights
+ *   a_m [B] (device arrays).  title_ctx (nullable) with feat [B][ld_feat] / w_title [B]: the titled form; without it feat and
+ *   w_title are NULL.  It launches dae_decode_mix_term for member 0, dae_decode_mix_term_add for the other members that go into
+ *   acc, then dae_set_score_mix + dae_decode_topk on the RANKING context -- the title context, or member M-1's -- and clears the
+ *   mix.  Scratch: the 4 * B * nt32 bytes of the term (nt32 = n_tracks rounded up to 32, never past V) in the ranking context,
+ *   which also takes the error message.  Refused before any launch: null pointers or half a seed CSR (DAE_ERR_ARG);
+ *   DAE_DTYPE_BF16_EXACT; k outside [1, 1024]; B > 4096; a context on another device, or bound to another stream (DAE_ERR_STATE);
+ *   a context with no image of `dtype`, with a catalogue image or a shard image, or with dae_set_score_mix set (DAE_ERR_STATE);
+ *   a context listed twice; images of different V or an H that is not its image's. */
+int dae_decode_mix_term_add(dae_ctx* ctx, const float* h, int B, int H, int dtype, const float* row_scale, int n_cols,
+                            float* accT, int64_t ldT);
+int dae_ensemble_topk(dae_ctx* const* members, int M, const float* const* h, const int* H, const float* const* row_scale,
+                      dae_ctx* title_ctx, const float* feat, int ld_feat, const float* w_title, int B, int dtype, int n_tracks,
+                      const int32_t* seed_row_ptr, const int32_t* seed_col, int k, float* out_score, int32_t* out_idx);
+
 /* DAE_DTYPE_BF16_EXACT for the title mix: the top-k of y = sigmoid(z_title) * w_title + sigmoid(z_dae) * w_playlist
  * (DAEs.py:176-181; what main_challenge.py:80-90 ranks for every titled batch) BIT-IDENTICAL to the fp32 path above
  * (dae_decode_mix_term + dae_set_score_mix + dae_decode_topk, or dae_mix_scores + dae_topk_dense), with both vocabulary-

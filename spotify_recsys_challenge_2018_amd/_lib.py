@@ -24,7 +24,7 @@ EXPORTS = [
     "dae_set_filter_skip", "dae_filter_skip_read", "dae_filter_skip_last", "dae_tile_bounds_read", "dae_sample_skip_read", "dae_live_proof_read", "dae_last_tau_read", "dae_decode_dense", "dae_decode_topk",
     "dae_score_topk", "dae_score_topk_begin", "dae_score_topk_finish", "dae_topk_dense", "dae_topk_merge", "dae_set_train_dtype", "dae_train_forward_backward",
     "dae_train_shard_encode", "dae_train_shard_decode", "dae_train_shard_finish", "dae_title_features", "dae_title_prepack_features",
-    "dae_mix_scores", "dae_decode_mix_term", "dae_set_score_mix", "dae_mix_topk_exact", "dae_mix_exact_shape_ok", "dae_title_score_exact", "dae_title_score", "dae_row_sums", "dae_mix_weights", "dae_title_loss_backward", "dae_title_loss_backward_cols", "dae_title_conv_backward", "dae_adam_step",
+    "dae_mix_scores", "dae_decode_mix_term", "dae_set_score_mix", "dae_decode_mix_term_add", "dae_ensemble_topk", "dae_mix_topk_exact", "dae_mix_exact_shape_ok", "dae_title_score_exact", "dae_title_score", "dae_row_sums", "dae_mix_weights", "dae_title_loss_backward", "dae_title_loss_backward_cols", "dae_title_conv_backward", "dae_adam_step",
     "dae_adam_rows_begin", "dae_adam_rows_apply", "dae_adam_rows_flush", "dae_set_enc_grad_prezeroed",
     "dae_arm_decoder_adam", "dae_set_decode_gate", "dae_set_overlap_hint",
     "dae_pipeline_create", "dae_pipeline_create_titled", "dae_pipeline_destroy", "dae_pipeline_submit", "dae_pipeline_submit_titled", "dae_pipeline_flush", "dae_pipeline_poll",
@@ -124,6 +124,9 @@ def load():
     lib.dae_mix_scores.argtypes = [vp, vp, c_i64, vp, c_i64, vp, vp, c_int, c_int]
     lib.dae_decode_mix_term.argtypes = [vp, vp, c_int, c_int, c_int, vp, c_int, vp, c_i64]
     lib.dae_set_score_mix.argtypes = [vp, vp, c_i64, c_int, vp]
+    lib.dae_decode_mix_term_add.argtypes = lib.dae_decode_mix_term.argtypes
+    lib.dae_ensemble_topk.argtypes = [ctypes.POINTER(vp), c_int, ctypes.POINTER(vp), ctypes.POINTER(c_int), ctypes.POINTER(vp),
+                                      vp, vp, c_int, vp, c_int, c_int, c_int, vp, vp, c_int, vp, vp]
     lib.dae_mix_topk_exact.argtypes = [vp, vp, vp, c_i64, vp, c_i64, c_int, vp, vp, c_int, vp, vp, c_int, vp, vp, vp]
     lib.dae_mix_exact_shape_ok.argtypes = [c_int, c_int]
     lib.dae_row_sums.argtypes = [vp, vp, vp, vp, c_int, c_f, c_u32, vp]
@@ -586,10 +589,41 @@ class Context:
         self.check(self.lib.dae_decode_mix_term(self.h, _ptr(h), B, H, int(dtype), _ptr(row_scale), int(n_cols),
                                                 _ptr(outT), int(outT.stride(0))))
 
+    def decode_mix_term_add(self, h, row_scale, n_cols, accT, dtype=DAE_DTYPE_F32):
+        """accT[c, r] = accT[c, r] + row_scale[r] * sigmoid(logit[r, c]) for the prepacked columns c < n_cols: a further member's
+        term of an ensemble, added to the buffer `decode_mix_term` wrote (dae_decode_mix_term_add)."""
+        B, H = h.shape
+        self.check(self.lib.dae_decode_mix_term_add(self.h, _ptr(h), B, H, int(dtype), _ptr(row_scale), int(n_cols),
+                                                    _ptr(accT), int(accT.stride(0))))
+
     def set_score_mix(self, mixT=None, w_title=None):
         """dae_decode_topk on this context ranks sigmoid(.) * w_title[r] + mixT[c, r] until cleared (no arguments)."""
         self.check(self.lib.dae_set_score_mix(self.h, _ptr(mixT), int(mixT.stride(0)) if mixT is not None else 0,
                                               int(mixT.shape[0]) if mixT is not None else 0, _ptr(w_title)))
+
+    def ensemble_topk(self, members, hs, row_scales, n_tracks, seed_row_ptr, seed_col, k, out_score, out_idx,
+                      dtype=DAE_DTYPE_F32, feat=None, w_title=None):
+        """On the RANKING context of an ensemble -- the title scorer's when feat / w_title are given, else the last member's:
+        the top-k of the members' weighted sigmoids summed in the order include/dae_hip.h fixes (dae_ensemble_topk).  members:
+        their contexts, this one last when untitled; hs / row_scales: per member its hidden rows [B, H_m] and weights [B]."""
+        M = len(members)
+        if M < 1 or len(hs) != M or len(row_scales) != M:
+            raise ValueError("ensemble_topk: one hidden-row tensor and one weight vector per member")
+        titled = feat is not None
+        if not titled and members[-1] is not self:
+            raise ValueError("ensemble_topk: untitled, the last member's context ranks -- call it on that context")
+        vp = ctypes.c_void_p
+        B = int(hs[0].shape[0])
+        for t in list(hs) + list(row_scales) + ([feat] if titled else []):
+            if t is not None and not t.is_contiguous():
+                raise ValueError("ensemble_topk: contiguous tensors are required")
+        c_m = (vp * M)(*[m.h for m in members])
+        c_h = (vp * M)(*[vp(t.data_ptr()) if t is not None else None for t in hs])
+        c_H = (ctypes.c_int * M)(*[int(t.shape[1]) if t is not None else 0 for t in hs])
+        c_a = (vp * M)(*[vp(t.data_ptr()) if t is not None else None for t in row_scales])
+        self.check(self.lib.dae_ensemble_topk(c_m, M, c_h, c_H, c_a, self.h if titled else None, _ptr(feat),
+                                              int(feat.shape[1]) if titled else 0, _ptr(w_title), B, int(dtype), int(n_tracks),
+                                              _ptr(seed_row_ptr), _ptr(seed_col), int(k), _ptr(out_score), _ptr(out_idx)))
 
     def mix_topk_exact(self, dae_ctx, feat, h, w_title, w_playlist, n_tracks, seed_row_ptr, seed_col, k, out_score, out_idx,
                        guard_out=None):

@@ -392,7 +392,7 @@ int dae_launch_decode_filter_f32(dae_ctx* ctx, const dae_rowgeom& g, int B, cons
 // bias_sel (bf16 image prepacked with DAE_DTYPE_BF16_EXACT): 0 = b, 1 = b - eps (lower bounds), 2 = b + eps (upper bounds)
 
 int dae_launch_decode_scaled_T(dae_ctx* ctx, const dae_rowgeom& g, int B, const dae_tileset& ts, const float* row_scale,
-                               float* outT, int64_t ldT, int dtype = DAE_DTYPE_F32);
+                               float* outT, int64_t ldT, int dtype = DAE_DTYPE_F32, bool add = false);
 
 // training forward: all tiles; the epilogue takes every element as a negative (target 0), writes dL/dz
 // TRANSPOSED ([ncols, ldT]: what both backward GEMMs read) and one loss partial per workgroup

@@ -39,6 +39,7 @@ constexpr int EPI_DENSE = 0;
 constexpr int EPI_FILTER = 1;
 constexpr int EPI_LOSS = 2;        // training: logits -> loss + dL/dz (DAEs.py:98-100)
 constexpr int EPI_GMAX = 3;        // EPI_DENSE (raw logits) + cross-wave group maxima: the threshold sample (phase A)
+constexpr int EPI_TERM_ADD = 4;    // an ensemble member's term ADDED to the transposed buffer: outT[c][r] = outT[c][r] + sigmoid(z) * row_scale[r]
 
 struct dae_decp {          // argument block of the decode kernels on the prepacked image (filled by decode_f32.hip fill_common)
     const float4* Wp;      // f32: [ntiles][G][64] float4   bf16: [ntiles][G][64] uint4 (8 bf16)
@@ -69,6 +70,7 @@ struct dae_decp {          // argument block of the decode kernels on the prepac
     dae_sample_skip sk;            // decode_f32_kernel's HALF (the threshold sample in half row groups): tiles skipped by their bound
     // title mix (models/DAEs.py:180 of the reference: y = title_score * w_title + dae_score * w_playlist):
     //   DAE side, EPI_DENSE: outT[column * ld_outT + row] = sigmoid(z) * row_scale[row] -- the second term, transposed
+    //   (EPI_TERM_ADD: the same element becomes outT[...] + sigmoid(z) * row_scale[row], a further member of an ensemble)
     //   title side, EPI_GMAX / EPI_FILTER: every value becomes sigmoid(z) * mix_w[row] + mixT[column * mix_ld + row]
     //   before it is stored / compared, i.e. the launch ranks the MIXED score; no [B, V] matrix of either scorer exists
     float* outT; int64_t ld_outT; const float* row_scale;

@@ -1076,15 +1076,16 @@ int dae_launch_decode_dense_f32(dae_ctx* ctx, const dae_rowgeom& g, int B, const
 }
 
 // DAE term of the title mix: outT[c * ldT + r] = sigmoid(logit[r, c]) * row_scale[r] for the first n_items tiles
+// (add: outT[c * ldT + r] + that, the read-modify-write instances of the kernel -- a further member of an ensemble)
 int dae_launch_decode_scaled_T(dae_ctx* ctx, const dae_rowgeom& g, int B, const dae_tileset& ts, const float* row_scale,
-                               float* outT, int64_t ldT, int dtype)
+                               float* outT, int64_t ldT, int dtype, bool add)
 {
     dae_decp p;
     int rc = fill_common(ctx, g, B, ts, p, dtype);
     if (rc) return rc;
     p.mixT = nullptr;
     p.outT = outT; p.ld_outT = ldT; p.row_scale = row_scale; p.mask_from_col = INT_MAX;
-    return dae_launch_decode_generic(ctx, EPI_DENSE, dtype == DAE_DTYPE_F32 ? DT_F32 : DT_BF16, g, p);
+    return dae_launch_decode_generic(ctx, add ? EPI_TERM_ADD : EPI_DENSE, dtype == DAE_DTYPE_F32 ? DT_F32 : DT_BF16, g, p);
 }
 
 // K5 from the row-major decoder (fp32, hidden = 256, 128-row groups); returns DAE_ERR_STATE when the shape does not apply

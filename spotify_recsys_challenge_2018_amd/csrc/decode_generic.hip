@@ -333,6 +333,22 @@ __global__ __launch_bounds__(NW * 64, HALF ? 2 : NW / 4) void decode_f32_kernel(
             }
         }
 
+        // EPI_TERM_ADD: what the transposed buffer holds of this tile's elements, requested now like the mix term above (a load
+        // instruction reads the 32 consecutive rows of one column that the store below it writes)
+        float oldv[EPI == EPI_TERM_ADD ? RB : 1][16];
+        if (EPI == EPI_TERM_ADD) {
+#pragma unroll
+            for (int rb = 0; rb < RB; ++rb) {
+                const int row = rg * R_TILE + rb * 32 + j;
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int lc = t * 32 + 4 * hi + (e & 3) + 8 * (e >> 2);
+                    oldv[EPI == EPI_TERM_ADD ? rb : 0][e] =
+                        (row < p.B && lc < p.ncols) ? p.outT[(size_t)(p.col_lo + lc) * p.ld_outT + row] : 0.0f;
+                }
+            }
+        }
+
         f32x16 acc[RB];
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb)
@@ -445,7 +461,26 @@ __global__ __launch_bounds__(NW * 64, HALF ? 2 : NW / 4) void decode_f32_kernel(
             for (int qd = 0; qd < 4; ++qd) bq[qd] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
 
-        if (EPI == EPI_DENSE && p.outT) {
+        if (EPI == EPI_TERM_ADD) {
+            // a further member's term joins the transposed buffer: old + sigmoid(z) * scale, two roundings, no contraction
+#pragma unroll
+            for (int rb = 0; rb < RB; ++rb) {
+                const int row = rg * R_TILE + rb * 32 + j;
+                if (row >= p.B) continue;
+                const float sc = p.row_scale[row];
+#pragma unroll
+                for (int qd = 0; qd < 4; ++qd) {
+                    const float zb[4] = {bq[qd].x, bq[qd].y, bq[qd].z, bq[qd].w};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int lc = tcol0 + 8 * qd + e;
+                        const float term = dae_sigmoidf(acc[rb][4 * qd + e] + zb[e]) * sc;
+                        if (lc < p.ncols)
+                            p.outT[(size_t)(p.col_lo + lc) * p.ld_outT + row] = oldv[EPI == EPI_TERM_ADD ? rb : 0][4 * qd + e] + term;
+                    }
+                }
+            }
+        } else if (EPI == EPI_DENSE && p.outT) {
             // DAE term of the title mix, transposed: a store instruction writes 32 consecutive rows of one column
 #pragma unroll
             for (int rb = 0; rb < RB; ++rb) {
@@ -672,6 +707,7 @@ int dae_launch_decode_generic(dae_ctx* ctx, int epi, int dt, const dae_rowgeom& 
         case EPI_FILTER: return dt == DT_F32 ? launch_decode_rb<EPI_FILTER>(ctx, g, p) : launch_decode_rb_bf16<EPI_FILTER>(ctx, g, p);
         case EPI_LOSS:   return dt == DT_F32 ? launch_decode_rb<EPI_LOSS>(ctx, g, p) : launch_decode_rb_bf16<EPI_LOSS>(ctx, g, p);
         case EPI_GMAX:   return dt == DT_F32 ? launch_decode_rb<EPI_GMAX>(ctx, g, p) : launch_decode_rb_bf16<EPI_GMAX>(ctx, g, p);
+        case EPI_TERM_ADD: return dt == DT_F32 ? launch_decode_rb<EPI_TERM_ADD>(ctx, g, p) : launch_decode_rb_bf16<EPI_TERM_ADD>(ctx, g, p);
     }
     return dae_fail(ctx, DAE_ERR_ARG, "bad epilogue %d", epi);
 }

@@ -614,8 +614,12 @@ int dae_score_topk_finish(dae_ctx* ctx, const float* tau, const int32_t* seed_ro
     return topk_phase_b(ctx, tau, seed_row_ptr, seed_col, out_kind, out_score, out_idx, ctx->tk.pend_h32, nullptr, true);
 }
 
-int dae_decode_mix_term(dae_ctx* ctx, const float* h, int B, int H, int dtype, const float* row_scale, int n_cols,
-                        float* outT, int64_t ldT)
+}  // extern "C"
+
+// dae_decode_mix_term (add = false) and dae_decode_mix_term_add: the same checks, tiles and launch geometry; the second runs the
+// read-modify-write instances of the kernel (decode_generic.hip EPI_TERM_ADD)
+static int decode_mix_term(dae_ctx* ctx, const float* h, int B, int H, int dtype, const float* row_scale, int n_cols,
+                           float* outT, int64_t ldT, bool add)
 {
     if (!ctx) return DAE_ERR_ARG;
     if (!h || !row_scale || !outT) return dae_fail(ctx, DAE_ERR_ARG, "null pointer");
@@ -631,7 +635,21 @@ int dae_decode_mix_term(dae_ctx* ctx, const float* h, int B, int H, int dtype, c
     int rc = pack_hidden(ctx, dtype, h, B, H, g);
     if (rc) return rc;
     dae_tileset ts{(n_loc + 31) / 32, 1, 0, static_cast<const int*>(pk->ident.p)};
-    return dae_launch_decode_scaled_T(ctx, g, B, ts, row_scale, outT, ldT, dtype);
+    return dae_launch_decode_scaled_T(ctx, g, B, ts, row_scale, outT, ldT, dtype, add);
+}
+
+extern "C" {
+
+int dae_decode_mix_term(dae_ctx* ctx, const float* h, int B, int H, int dtype, const float* row_scale, int n_cols,
+                        float* outT, int64_t ldT)
+{
+    return decode_mix_term(ctx, h, B, H, dtype, row_scale, n_cols, outT, ldT, false);
+}
+
+int dae_decode_mix_term_add(dae_ctx* ctx, const float* h, int B, int H, int dtype, const float* row_scale, int n_cols,
+                            float* accT, int64_t ldT)
+{
+    return decode_mix_term(ctx, h, B, H, dtype, row_scale, n_cols, accT, ldT, true);
 }
 
 int dae_set_score_mix(dae_ctx* ctx, const float* mixT, int64_t ld, int n_cols, const float* w_title)
@@ -732,6 +750,84 @@ int dae_title_rank(dae_ctx* tc, dae_ctx* dc, int dtype, int B, int V, int H, int
 }
 
 extern "C" {
+
+// An ensemble's ranking half (include/dae_hip.h): the members' weighted sigmoids summed in the transposed
+// term buffer of the ranking context -- member 0 writes it, the others add to it -- and the ranking context's threshold path on
+// its own weighted sigmoid plus that buffer (dae_set_score_mix), cleared afterwards as dae_title_rank clears it.  Every refusal
+// comes before the first launch.
+int dae_ensemble_topk(dae_ctx* const* members, int M, const float* const* h, const int* H, const float* const* row_scale,
+                      dae_ctx* title_ctx, const float* feat, int ld_feat, const float* w_title, int B, int dtype, int n_tracks,
+                      const int32_t* seed_row_ptr, const int32_t* seed_col, int k, float* out_score, int32_t* out_idx)
+{
+    if (!members || M < 1 || !members[M - 1]) return dae_fail(title_ctx, DAE_ERR_ARG, "dae_ensemble_topk: needs M >= 1 member contexts");
+    const bool titled = title_ctx != nullptr;
+    dae_ctx* rc_ctx = titled ? title_ctx : members[M - 1];                 // the ranking context: it takes the messages too
+    if (!h || !H || !row_scale || !out_score || !out_idx) return dae_fail(rc_ctx, DAE_ERR_ARG, "null pointer");
+    if (titled ? (!feat || !w_title) : (feat || w_title))
+        return dae_fail(rc_ctx, DAE_ERR_ARG, titled ? "null pointer (feat / w_title of the title context)"
+                                                    : "dae_ensemble_topk: feat / w_title without a title context");
+    if ((seed_row_ptr == nullptr) != (seed_col == nullptr))
+        return dae_fail(rc_ctx, DAE_ERR_ARG, "seed_row_ptr and seed_col must both be given or both null");
+    if (dtype == DAE_DTYPE_BF16_EXACT)
+        return dae_fail(rc_ctx, DAE_ERR_ARG, "DAE_DTYPE_BF16_EXACT is not available with dae_ensemble_topk: rank with DAE_DTYPE_F32 (the same lists)");
+    if (dtype != DAE_DTYPE_F32 && dtype != DAE_DTYPE_BF16) return dae_fail(rc_ctx, DAE_ERR_ARG, "unknown dtype %d", dtype);
+    if (k < 1 || k > DAE_MAX_K) return dae_fail(rc_ctx, DAE_ERR_ARG, "k=%d out of [1,%d] (dae_ensemble_topk)", k, DAE_MAX_K);
+    if (B < 0 || B > DAE_ROW_SLAB || n_tracks <= 0)
+        return dae_fail(rc_ctx, DAE_ERR_ARG, "bad shape B=%d (at most %d rows a call) n_tracks=%d", B, DAE_ROW_SLAB, n_tracks);
+    // every context: its rows and weights, one device and stream, no mix of its own, an image of `dtype` over the whole vocabulary
+    const int n_ctx = M + (titled ? 1 : 0);
+    auto ctx_at = [&](int i) { return i < M ? members[i] : title_ctx; };
+    auto name_of = [&](int i, char* buf, size_t n) {
+        if (i < M) snprintf(buf, n, "member %d", i); else snprintf(buf, n, "the title context");
+        return buf;
+    };
+    char who[32];
+    int V = 0;
+    for (int i = 0; i < n_ctx; ++i) {
+        dae_ctx* c = ctx_at(i);
+        name_of(i, who, sizeof(who));
+        if (!c) return dae_fail(rc_ctx, DAE_ERR_ARG, "dae_ensemble_topk: %s is a null context", who);
+        if (i < M && (!h[i] || !row_scale[i])) return dae_fail(rc_ctx, DAE_ERR_ARG, "null pointer (hidden rows / row_scale of %s)", who);
+        for (int o = 0; o < i; ++o)
+            if (ctx_at(o) == c) return dae_fail(rc_ctx, DAE_ERR_ARG, "dae_ensemble_topk: %s is listed twice (every scorer needs a context of its own)", who);
+        if (c->device != rc_ctx->device) return dae_fail(rc_ctx, DAE_ERR_ARG, "dae_ensemble_topk: %s is on another device", who);
+        if (c->stream != rc_ctx->stream) return dae_fail(rc_ctx, DAE_ERR_STATE, "dae_ensemble_topk: %s is bound to another stream", who);
+        if (c->mixT) return dae_fail(rc_ctx, DAE_ERR_STATE, "dae_ensemble_topk sets the mix itself: clear dae_set_score_mix on %s", who);
+        const dae_packed& pk = dtype == DAE_DTYPE_F32 ? c->pk_f32 : c->pk_bf16;
+        const int Hi = i < M ? H[i] : ld_feat;
+        if (!pk.valid) return dae_fail(rc_ctx, DAE_ERR_STATE, "dae_ensemble_topk: %s holds no image prepacked for dtype %d", who, dtype);
+        if (pk.cat_id != 0) return dae_fail(rc_ctx, DAE_ERR_STATE, "dae_ensemble_topk: %s holds a catalogue image", who);
+        if (pk.col_lo != 0 || pk.col_hi != pk.V)
+            return dae_fail(rc_ctx, DAE_ERR_STATE, "dae_ensemble_topk: %s holds a shard image (columns [%d, %d) of %d)", who, pk.col_lo, pk.col_hi, pk.V);
+        if (pk.H != Hi) return dae_fail(rc_ctx, DAE_ERR_ARG, "H=%d of %s does not match its prepacked H=%d", Hi, who, pk.H);
+        if (i == 0) V = pk.V;
+        if (pk.V != V) return dae_fail(rc_ctx, DAE_ERR_ARG, "dae_ensemble_topk: %s holds %d columns, member 0 holds %d", who, pk.V, V);
+    }
+    if (n_tracks > V) return dae_fail(rc_ctx, DAE_ERR_ARG, "n_tracks=%d exceeds the images' %d columns", n_tracks, V);
+    if (B == 0) return DAE_OK;
+
+    const size_t nt32 = (size_t)((n_tracks + 31) / 32 * 32 < V ? (n_tracks + 31) / 32 * 32 : V);
+    int rc = dae_reserve(rc_ctx, rc_ctx->title_y1, nt32 * (size_t)B * sizeof(float));
+    if (rc) return rc;
+    float* accT = static_cast<float*>(rc_ctx->title_y1.p);
+    const int n_acc = titled ? M : M - 1;                  // members summed in the buffer (untitled: the last one ranks)
+    if (n_acc == 0) {
+        // one member alone: y = t_0.  The mix epilogue adds the buffer's element; -0.0f is the one value that leaves every t_0,
+        // a zero of either sign included, as it is
+        DAE_HIP_CHECK(rc_ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(accT), (int)0x80000000u, nt32 * (size_t)B, rc_ctx->stream));
+    }
+    for (int m = 0; m < n_acc; ++m) {
+        dae_ctx* c = members[m];
+        rc = decode_mix_term(c, h[m], B, H[m], dtype, row_scale[m], n_tracks, accT, B, m > 0);
+        if (rc) return c == rc_ctx ? rc : dae_fail(rc_ctx, rc, "%s", c->err.c_str());
+    }
+    rc = dae_set_score_mix(rc_ctx, accT, B, (int)nt32, titled ? w_title : row_scale[M - 1]);
+    if (rc) return rc;
+    rc = dae_decode_topk(rc_ctx, titled ? feat : h[M - 1], B, titled ? ld_feat : H[M - 1], dtype, n_tracks, seed_row_ptr, seed_col, k,
+                         DAE_OUT_LOGIT, out_score, out_idx);
+    (void)dae_set_score_mix(rc_ctx, nullptr, 0, 0, nullptr);
+    return rc;
+}
 
 int dae_title_score(dae_ctx* tc, dae_ctx* dc, int dtype, const int64_t* positions, const float* values, int values_broadcast,
                     int64_t nnz, int n_rows, int V, const float* W_enc, const float* b_enc, int H,

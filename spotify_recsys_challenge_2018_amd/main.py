@@ -5,7 +5,8 @@ the same config.ini schema:
 
     [BASE] verbose data_dir result_dir testsize   (+ optional, this build only: train_dtype = f32 | bf16, decode_dtype = f32 | bf16 | exact_bf16,
                                                   eval_metrics = rprecision | all, train_feed = host | device,
-                                                  eval_ranks = off | on, eval_mixed_ranks = off | on)
+                                                  eval_ranks = off | on, eval_mixed_ranks = off | on,
+                                                  ensemble = <pickle>[, <pickle> ...], ensemble_alpha = a0, a1, ...)
     [DAE] epochs batch lr reg_lambda hidden test_seed update_seed keep_prob input_kp firstN_range initval save
     [PRETRAIN] epochs batch lr reg_lambda save
     [TITLE] ... (parsed for compatibility; the title models are outside the scoring path)
@@ -101,6 +102,31 @@ class Conf:
                 if val not in allowed:
                     raise ValueError("[BASE] %s must be one of %s, not %r" % (key, ' | '.join(allowed), val))
                 setattr(self, key, val)
+        # two more OPTIONAL [BASE] keys: an ensemble around the run's own model (models/ensemble.py)
+        #   ensemble       = <pickle>[, <pickle> ...]   further members: pickles of the four arrays a --pretrain / --dae run saves, over
+        #                    the same vocabulary (any hidden size); paths resolve in the run directory, as [TITLE] DAEval does.
+        #                    Honoured by --challenge (titled when the title pickle exists, exactly as today's choice) and by
+        #                    --dae --testmode / --title --testmode; refused in every other run (`refuse_ensemble`) and where the
+        #                    plain DAE would run vocabulary-sharded.  Absent: every run is what it is without the key
+        #   ensemble_alpha = a0, a1, ...                one weight per member, the section's own model first; default uniform
+        self.ensemble, self.ensemble_alpha = [], None
+        if 'ensemble' in self.ini['BASE'] and self.ini['BASE']['ensemble'].strip():
+            names = _csv(self.ini['BASE']['ensemble'])
+            if not all(names):
+                raise ValueError("[BASE] ensemble = %r: an empty entry in the list of pickles" % self.ini['BASE']['ensemble'])
+            self.ensemble = [os.path.join(self.dir, n) for n in names]
+        if 'ensemble_alpha' in self.ini['BASE'] and self.ini['BASE']['ensemble_alpha'].strip():
+            if not self.ensemble:
+                raise ValueError("[BASE] ensemble_alpha is set without [BASE] ensemble: there are no members to weigh")
+            try:
+                alpha = _floats(self.ini['BASE']['ensemble_alpha'])
+            except ValueError:
+                raise ValueError("[BASE] ensemble_alpha = %r: a comma-separated list of numbers is required"
+                                 % self.ini['BASE']['ensemble_alpha']) from None
+            if len(alpha) != len(self.ensemble) + 1:
+                raise ValueError("[BASE] ensemble_alpha lists %d weights for %d members (the section's own model first, then the "
+                                 "%d of [BASE] ensemble)" % (len(alpha), len(self.ensemble) + 1, len(self.ensemble)))
+            self.ensemble_alpha = alpha
 
     def _load(self, section):
         sec = self.ini[section]
@@ -183,6 +209,20 @@ def load_conf(dir):
     return Conf(dir, ini)
 
 
+def refuse_ensemble(conf, args):
+    """[BASE] ensemble is for runs that only score: --challenge, --dae --testmode, --title --testmode.  Any other run -- a
+    training run, --pretrain --testmode -- refuses the key by name, before a reader or a model is built."""
+    if not getattr(conf, 'ensemble', None):
+        return
+    if args.challenge or (args.testmode and not args.pretrain and (args.dae or args.title)):
+        return
+    what = ("--pretrain" if args.pretrain else "--dae" if args.dae else "--title" if args.title else "this run") + \
+        (" --testmode" if args.testmode else "")
+    raise ValueError("[BASE] ensemble is set, and %s %s: the key is honoured by --challenge, --dae --testmode and "
+                     "--title --testmode only (remove [BASE] ensemble / ensemble_alpha to run it)"
+                     % (what, "evaluates the tied model alone" if args.testmode else "is a training run"))
+
+
 def build_parser():
     ap = argparse.ArgumentParser(description="args")
     ap.add_argument('--dir', type=str, default='qwerty', help="directory name which contains config file")
@@ -206,6 +246,7 @@ def main(argv=None):
         return 0
     conf = load_conf(dir)
     conf.set_dae_conf()                                   # always first (main.py:121)
+    refuse_ensemble(conf, args)
     from .main_runner import main_challenge, main_train
     if args.pretrain:
         conf.set_pretrain_conf()

@@ -16,6 +16,10 @@ When it does not, the run fails like the reference's restore does, unless [CHALL
 (optional key of this build) asks for the plain DAE: titles_use = 0 reduces the mix exactly to it (App. B.6)
 on the weights the [TITLE] section names (DAEval); playlists without seeds still make that an error.
 
+[BASE] ensemble = <pickle>[, ...] (optional key of this build): the run's model becomes member 0 of a `DAE_ensemble`
+(models/ensemble.py) with one more member per pickle; refused with a catalogue and where the plain DAE would run
+vocabulary-sharded.
+
 [CHALLENGE] catalogue = <file> (optional key of this build): the submission is ranked inside a catalogue -- the tracks the
 file lists (`read_catalogue`) become `model.catalogue(columns)`, and the handle goes to `recommend_iter` / `recommend` as
 `catalogue=`; rows may then hold fewer than 500 tracks.
@@ -139,6 +143,14 @@ def run(conf, model=None):
         raise ValueError("[CHALLENGE] catalogue = %s, and the plain DAE would run vocabulary-sharded over %s ranks: catalogue "
                          "scoring is not vocabulary-sharded -- run one process, or with the title scorer (its batches are "
                          "dealt to the ranks)" % (cat_file, os.environ["WORLD_SIZE"]))
+    ens = getattr(conf, 'ensemble', None)
+    if ens and cat_file:
+        raise ValueError("[BASE] ensemble and [CHALLENGE] catalogue = %s are both set: an ensemble does not rank inside a "
+                         "catalogue -- remove one of the keys" % cat_file)
+    if ens and int(os.environ.get("WORLD_SIZE", "1")) > 1 and not _mixes_titles(conf, model):
+        raise ValueError("[BASE] ensemble is set, and the plain DAE would run vocabulary-sharded over %s ranks: an ensemble is "
+                         "not vocabulary-sharded -- run one process, or with the title scorer (its batches are dealt to the "
+                         "ranks)" % os.environ["WORLD_SIZE"])
     rank, world = _init_distributed(conf)
     reader = data_reader_challenge(data_dir=conf.data_dir, filename=conf.challenge_data,
                                    batch_size=conf.batch)
@@ -194,6 +206,11 @@ def run(conf, model=None):
             # every rank ends with every row) | alltoall (every rank ends with the rows it owns)
             model.shard_scoring(rank, world, exchange=exchange, tau_exchange=tau_x)
         model.fit()
+        if ens:
+            # [BASE] ensemble: the run's model becomes member 0 of an ensemble (models/ensemble.py), titled exactly when it is
+            from ..models.ensemble import from_conf
+            model = from_conf(conf, model)
+            log_write(conf, 'ensemble: %d members, alphas %s' % (len(model.members), ', '.join('%g' % a for a in model.alphas)))
     else:
         use_titles = bool(getattr(model, 'title_model', None))
         sharded = world > 1 and not use_titles

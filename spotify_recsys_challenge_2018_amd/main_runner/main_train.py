@@ -233,8 +233,24 @@ def _init_distributed(conf):
     return rank, world
 
 
+def _refuse_ensemble(conf, only_testmode):
+    """[BASE] ensemble outside the runs that honour it (main.py refuse_ensemble says the same from the command line)."""
+    if not getattr(conf, 'ensemble', None):
+        return
+    if not only_testmode:
+        raise ValueError("[BASE] ensemble is set, and this is a training run: the key is honoured by --challenge, --dae --testmode "
+                         "and --title --testmode only (remove [BASE] ensemble / ensemble_alpha to train)")
+    if getattr(conf, 'mode', None) not in ('dae', 'title'):
+        raise ValueError("[BASE] ensemble is set, and --%s --testmode evaluates that model alone: the key is honoured by "
+                         "--challenge, --dae --testmode and --title --testmode only" % getattr(conf, 'mode', None))
+    for key in ('eval_ranks', 'eval_mixed_ranks'):
+        if getattr(conf, key, 'off') == 'on':
+            raise ValueError("[BASE] ensemble is set with [BASE] %s = on: an ensemble has no rank_of (set %s = off)" % (key, key))
+
+
 def run(conf, only_testmode):
     _refuse_ranks_under_title(conf)
+    _refuse_ensemble(conf, only_testmode)
     rank, world = _init_distributed(conf)
     # the training reader (main_train.py:129-133): whole playlists, or -- with a [DAE] firstN_range -- their first-N prefixes
     reader_args = dict(data_dir=conf.data_dir, filename='train', batch_size=conf.batch)
@@ -281,6 +297,11 @@ def run(conf, only_testmode):
 
     if only_testmode:                                               # main_train.py:181-191
         log_write(conf, '<<only test mode>>')
+        if getattr(conf, 'ensemble', None):
+            # [BASE] ensemble: the splits are ranked by the ensemble around this model (models/ensemble.py), feed by feed
+            from ..models.ensemble import from_conf
+            model = from_conf(conf, model)
+            log_write(conf, 'ensemble: %d members, alphas %s' % (len(model.members), ', '.join('%g' % a for a in model.alphas)))
         extras = {} if getattr(conf, 'eval_metrics', 'rprecision') == 'all' else None
         out = _eval_splits(readers_test, conf, model, rank, world, extras)
         _log_splits(conf, readers_test, out, extras)
