@@ -850,6 +850,47 @@ int dae_ensemble_topk(dae_ctx* const* members, int M, const float* const* h, con
                       dae_ctx* title_ctx, const float* feat, int ld_feat, const float* w_title, int B, int dtype, int n_tracks,
                       const int32_t* seed_row_ptr, const int32_t* seed_col, int k, float* out_score, int32_t* out_idx);
 
+/* ---- ranks under the ensemble (csrc/ensemble.hip, csrc/rank_of.hip; DESIGN.md section 4e "Ranks under the ensemble") ----
+ * Both calls take the scorers as dae_ensemble_topk takes them -- members / h / H / row_scale: HOST arrays of M entries; title_ctx
+ * (nullable) with feat [B][ld_feat] / w_title [B] -- plus what the candidate chains read: W_dec / b_dec, HOST arrays of the
+ * members' row-major [V][H[m]] decoder tensors and [V] biases (device arrays, 16-byte aligned), and OutW_T [V][ld_feat] / Out_b
+ * of the title scorer (all four title arguments NULL when untitled).  Both run on the RANKING context of dae_ensemble_topk --
+ * the title context, or member M-1's -- which takes the scratch and the messages; every context on one device and one stream,
+ * none listed twice, none with dae_set_score_mix set.  Always fp32.
+ *
+ * dae_ensemble_candidates: out[i] = the canonical value y (above) of column cand_col[i] for its row, for the candidate CSR of
+ *   dae_decode_candidates (cand_row_ptr [B + 1], cand_col, the host-known n_cand; nothing at or past n_cand is touched, nothing
+ *   is read back).  Per scorer dae_decode_candidates with DAE_OUT_SCORE -- the canonical chain over the row-major tensors, the
+ *   title scorer's over feat / OutW_T / Out_b -- into scratch, then one combining launch per 8 members: t_m = s_m * a_m[row], acc
+ *   over m ascending, y as above, every product and sum a single fp32 rounding.  Bit for bit the value dae_ensemble_topk lists
+ *   by and DAE_ensemble.score_candidates computes.  Ids: -1 gives -inf; another id outside [0, V) gives a quiet NaN and ORs bit 0
+ *   into *status (DEVICE int32, nullable).  1 <= B <= 4096; H[m] and ld_feat multiples of 4, at most 1024.  No image is needed.
+ *   Scratch: 4 * (M (+ 1)) * n_cand bytes (csrc/ensemble_rank_of_plan.h).
+ * dae_ensemble_rank_of: dae_mix_rank_of's contract under y -- per listed (row, column) the 0-based number of non-seed track
+ *   columns that precede it, y descending under the composite key, then column ascending; -1 for padding, artists, seeds and ids
+ *   out of range (which OR bit 0 into *status); out_score (nullable) holds y, -inf beside a -1 (NaN for an id out of range).
+ *   n_seed: the length of seed_col, an upper bound of seed_row_ptr[B] (slots that belong to no row are never read); an
+ *   out-of-range seed is ignored and raises no status.  EVERY context must hold a plain DAE_DTYPE_F32 image over [0, V) of its
+ *   tensors.  Launches, all on the one stream: dae_ensemble_candidates' over the answers (the thresholds) and over the seed CSR
+ *   (the seeds' values); the term buffer exactly as dae_ensemble_topk builds it ([nt32][B] in the ranking context;
+ *   dae_decode_mix_term for member 0, dae_decode_mix_term_add for the others in acc, a -0.0f fill when there are none); the
+ *   memset, the sort, the counting launch with the mix epilogue over the ranking scorer's image (weights: w_title, or a_{M-1}
+ *   untitled), whose two operations are the combining launch's last two on the same operands -- an answer's own column meets its
+ *   own value; the finishing launch, which takes each distinct seed out by its value from the seeds' pass.  Geometry:
+ *   dae_rank_of_plan(B, H of the ranking scorer, n_ans).  Refused before any launch: everything dae_ensemble_topk refuses about
+ *   its contexts; everything dae_decode_rank_of refuses about B, H, n_ans, alignment and half a seed CSR; n_seed < 0, or n_seed > 0
+ *   without seeds; V that is not the images'.  n_ans == 0 returns DAE_OK and writes nothing.
+ * NOT BUILT: a bf16 count, vocabulary shards, catalogues, the pipeline, one launch decoding all members per tile. */
+int dae_ensemble_candidates(dae_ctx* const* members, int M, const float* const* h, const int* H, const float* const* row_scale,
+                            const float* const* W_dec, const float* const* b_dec, dae_ctx* title_ctx, const float* feat,
+                            int ld_feat, const float* OutW_T, const float* Out_b, const float* w_title, int B, int V,
+                            const int32_t* cand_row_ptr, const int32_t* cand_col, int n_cand, float* out, int32_t* status);
+int dae_ensemble_rank_of(dae_ctx* const* members, int M, const float* const* h, const int* H, const float* const* row_scale,
+                         const float* const* W_dec, const float* const* b_dec, dae_ctx* title_ctx, const float* feat, int ld_feat,
+                         const float* OutW_T, const float* Out_b, const float* w_title, int B, int V, int n_tracks,
+                         const int32_t* seed_row_ptr, const int32_t* seed_col, int n_seed, const int32_t* ans_row_ptr,
+                         const int32_t* ans_col, int n_ans, int32_t* out_rank, float* out_score, int32_t* status);
+
 /* DAE_DTYPE_BF16_EXACT for the title mix: the top-k of y = sigmoid(z_title) * w_title + sigmoid(z_dae) * w_playlist
  * (DAEs.py:176-181; what main_challenge.py:80-90 ranks for every titled batch) BIT-IDENTICAL to the fp32 path above
  * (dae_decode_mix_term + dae_set_score_mix + dae_decode_topk, or dae_mix_scores + dae_topk_dense), with both vocabulary-

@@ -32,6 +32,7 @@ EXPORTS = [
     "dae_rank_metrics", "dae_pipeline_enable_eval", "dae_pipeline_submit_eval", "dae_pipeline_poll_eval",
     "dae_decode_candidates", "dae_score_candidates", "dae_mix_candidates", "dae_rank_candidates",
     "dae_rank_of_plan", "dae_decode_rank_of", "dae_score_rank_of", "dae_mix_rank_of",
+    "dae_ensemble_candidates", "dae_ensemble_rank_of",
     "dae_catalogue_create", "dae_catalogue_destroy", "dae_prepack_decoder_catalogue", "dae_score_topk_catalogue",
     "dae_decode_topk_catalogue", "dae_title_score_catalogue", "dae_pipeline_set_catalogue",
 ]
@@ -127,6 +128,11 @@ def load():
     lib.dae_decode_mix_term_add.argtypes = lib.dae_decode_mix_term.argtypes
     lib.dae_ensemble_topk.argtypes = [ctypes.POINTER(vp), c_int, ctypes.POINTER(vp), ctypes.POINTER(c_int), ctypes.POINTER(vp),
                                       vp, vp, c_int, vp, c_int, c_int, c_int, vp, vp, c_int, vp, vp]
+    pvp, pci = ctypes.POINTER(vp), ctypes.POINTER(c_int)
+    lib.dae_ensemble_candidates.argtypes = [pvp, c_int, pvp, pci, pvp, pvp, pvp, vp, vp, c_int, vp, vp, vp, c_int, c_int,
+                                            vp, vp, c_int, vp, vp]
+    lib.dae_ensemble_rank_of.argtypes = [pvp, c_int, pvp, pci, pvp, pvp, pvp, vp, vp, c_int, vp, vp, vp, c_int, c_int, c_int,
+                                         vp, vp, c_int, vp, vp, c_int, vp, vp, vp]
     lib.dae_mix_topk_exact.argtypes = [vp, vp, vp, c_i64, vp, c_i64, c_int, vp, vp, c_int, vp, vp, c_int, vp, vp, vp]
     lib.dae_mix_exact_shape_ok.argtypes = [c_int, c_int]
     lib.dae_row_sums.argtypes = [vp, vp, vp, vp, c_int, c_f, c_u32, vp]
@@ -624,6 +630,43 @@ class Context:
         self.check(self.lib.dae_ensemble_topk(c_m, M, c_h, c_H, c_a, self.h if titled else None, _ptr(feat),
                                               int(feat.shape[1]) if titled else 0, _ptr(w_title), B, int(dtype), int(n_tracks),
                                               _ptr(seed_row_ptr), _ptr(seed_col), int(k), _ptr(out_score), _ptr(out_idx)))
+
+    def _ensemble_args(self, name, members, hs, row_scales, W_decs, b_decs, feat, OutW_T, Out_b, w_title):
+        """The scorers of an ensemble call as the C ABI takes them (dae_ensemble_candidates / dae_ensemble_rank_of), this context
+        being the ranking one."""
+        M = len(members)
+        if M < 1 or not (len(hs) == len(row_scales) == len(W_decs) == len(b_decs) == M):
+            raise ValueError("%s: one hidden-row tensor, weight vector, decoder tensor and bias per member" % name)
+        titled = feat is not None
+        if not titled and members[-1] is not self:
+            raise ValueError("%s: untitled, the last member's context ranks -- call it on that context" % name)
+        for t in list(hs) + list(row_scales) + list(W_decs) + list(b_decs) + ([feat, OutW_T] if titled else []):
+            if t is not None and not t.is_contiguous():
+                raise ValueError("%s: contiguous tensors are required" % name)
+        vp = ctypes.c_void_p
+        arr = lambda ts: (vp * M)(*[vp(t.data_ptr()) if t is not None else None for t in ts])      # noqa: E731
+        c_H = (ctypes.c_int * M)(*[int(t.shape[1]) if t is not None else 0 for t in hs])
+        return ((vp * M)(*[m.h for m in members]), M, arr(hs), c_H, arr(row_scales), arr(W_decs), arr(b_decs),
+                self.h if titled else None, _ptr(feat), int(feat.shape[1]) if titled else 0, _ptr(OutW_T), _ptr(Out_b),
+                _ptr(w_title), int(hs[0].shape[0]), int(W_decs[0].shape[0]))
+
+    def ensemble_candidates(self, members, hs, row_scales, W_decs, b_decs, cand, n_cand, out, feat=None, OutW_T=None, Out_b=None,
+                            w_title=None, status=None):
+        """On the RANKING context of an ensemble (as ensemble_topk): out[i] = the canonical value y of column cand_col[i] for its
+        row (dae_ensemble_candidates).  W_decs / b_decs: per member its row-major decoder tensor [V, H_m] and bias [V]."""
+        args = self._ensemble_args("ensemble_candidates", members, hs, row_scales, W_decs, b_decs, feat, OutW_T, Out_b, w_title)
+        self.check(self.lib.dae_ensemble_candidates(*args, _ptr(cand[0]), _ptr(cand[1]), int(n_cand), _ptr(out), _ptr(status)))
+
+    def ensemble_rank_of(self, members, hs, row_scales, W_decs, b_decs, n_tracks, seed_row_ptr, seed_col, ans, n_ans, out_rank,
+                         out_score=None, feat=None, OutW_T=None, Out_b=None, w_title=None, status=None, n_seed=None):
+        """On the RANKING context of an ensemble: decode_rank_of under the ensemble's y (dae_ensemble_rank_of).  Every context
+        holds its plain fp32 image over all columns.  n_seed: the length of seed_col by default."""
+        args = self._ensemble_args("ensemble_rank_of", members, hs, row_scales, W_decs, b_decs, feat, OutW_T, Out_b, w_title)
+        if n_seed is None:
+            n_seed = int(seed_col.numel()) if seed_col is not None else 0
+        self.check(self.lib.dae_ensemble_rank_of(*args, int(n_tracks), _ptr(seed_row_ptr), _ptr(seed_col), int(n_seed),
+                                                 _ptr(ans[0]), _ptr(ans[1]), int(n_ans), _ptr(out_rank), _ptr(out_score),
+                                                 _ptr(status)))
 
     def mix_topk_exact(self, dae_ctx, feat, h, w_title, w_playlist, n_tracks, seed_row_ptr, seed_col, k, out_score, out_idx,
                        guard_out=None):

@@ -629,3 +629,21 @@ bool dae_exact_refine_can_fuse(const dae_topk_args& a);
 int dae_launch_exact_refine(dae_ctx* ctx, const dae_pair_group& g1, const dae_exact_src& x, int B, int k,
                             const int32_t* seed_row_ptr, uint2* out = nullptr, int* out_cnt = nullptr, int out_cap = 0,
                             int* stat = nullptr, const dae_topk_args* fused = nullptr);
+// ensemble.hip -- what the ensemble calls share
+// The scorers of an ensemble call, as the entry points take them: M member contexts with their hidden rows, widths and weights
+// (HOST arrays of M entries), and the title context (nullable) with the width of its feature rows.  dae_ensemble_check refuses
+// what dae_ensemble_topk refuses about them -- a null, doubled, foreign-device or foreign-stream context, one with
+// dae_set_score_mix set, one without a plain image of `dtype` over the whole vocabulary, images of different V, an H that is not
+// its image's -- with `fn` as the call's name in the message, which goes to rc_ctx; *V_out = the images' column count.  dtype < 0:
+// the call reads no image, so none is asked for (*V_out = 0).
+int dae_ensemble_check(const char* fn, dae_ctx* rc_ctx, dae_ctx* const* members, int M, const float* const* h, const int* H,
+                       const float* const* row_scale, dae_ctx* title_ctx, int ld_feat, int dtype, int* V_out);
+// The canonical value y at the listed pairs into out[n_cand], everything on rc_ctx's stream: per scorer the candidate chain with
+// the sigmoid into s + i * s_stride (i < M + (feat ? 1 : 0)), then the combining launch.  No check of its own but
+// dae_decode_candidates'.
+struct dae_ens_tensors {
+    int M; const float* const* h; const int* H; const float* const* row_scale; const float* const* W_dec; const float* const* b_dec;
+    const float* feat; int ld_feat; const float* OutW_T; const float* Out_b; const float* w_title;      // all null / 0 when untitled
+};
+int dae_launch_ensemble_candidates(dae_ctx* rc_ctx, const dae_ens_tensors& t, int B, int V, const int32_t* row_ptr, const int32_t* col,
+                                   int n_cand, float* s, size_t s_stride, float* out, int32_t* status);

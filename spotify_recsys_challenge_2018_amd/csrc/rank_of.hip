@@ -34,9 +34,16 @@
 // y with the operations and order of the fp32 mix epilogue of decode_generic.hip before it is counted; the finishing launch
 // takes the seeds out by their mixed value (both canonical chains per distinct seed).  The composite, the buckets, the prefix
 // sums are the plain call's: the kernels are the same templates.
+//
+// THE ENSEMBLE'S CALL (dae_ensemble_rank_of; DESIGN.md section 4e "Ranks under the ensemble") ranks by the canonical value y of a
+// weighted sum of several scorers with the same launches again: y_a and the seeds' values from the candidate chains of
+// ensemble.hip, the other scorers' terms in the transposed buffer dae_ensemble_topk builds, the MIX counting kernel over the
+// ranking scorer's image, and the GIVEN instantiation of the finishing kernel, which reads the seeds' values instead of
+// recomputing chains.
 #include "decode_common.h"
 #include "mix_common.h"             // mixf
 #include "rank_of_plan.h"
+#include "ensemble_rank_of_plan.h"
 
 namespace {
 
@@ -67,6 +74,8 @@ struct RankP {
     // Wp / bias / hp / G the title image's, z the mixed values y_a.
     const float* mixT; int64_t mix_ld; const float* w_title; const float* w_playlist;
     const float* feat; int HF; const float* WT; const float* bT;
+    // the ensemble's call alone (the GIVEN finish): the seeds' values, one per slot of seed_col, computed before the launch
+    const float* seed_y; int n_seed;
 };
 
 // a row's answers: [beg, end) of ans_col, clamped to what the caller said exists
@@ -360,7 +369,8 @@ __device__ __forceinline__ float ro_chain(const float* hrow, const float* Wrow, 
 }
 
 // MIX: the seeds leave by their MIXED value -- both canonical chains and mixf per distinct seed
-template <bool MIX>
+// GIVEN (dae_ensemble_rank_of; never with MIX): the seeds leave by the value the caller computed for each slot, p.seed_y[] -- no chain
+template <bool MIX, bool GIVEN = false>
 __global__ __launch_bounds__(256) void rank_of_finish_kernel(const RankP p)
 {
     __shared__ float hrow[RO_MAXH];
@@ -391,11 +401,17 @@ __global__ __launch_bounds__(256) void rank_of_finish_kernel(const RankP p)
         if (p.out_logit) p.out_logit[i] = zl;
     }
     if (!p.seed_row_ptr) return;
-    const int sb = p.seed_row_ptr[row], se = p.seed_row_ptr[row + 1];
+    int sb = p.seed_row_ptr[row], se = p.seed_row_ptr[row + 1];
+    if (GIVEN) {                                                  // nothing is read at or past the caller's n_seed
+        sb = sb > 0 ? sb : 0;
+        se = se < p.n_seed ? se : p.n_seed;
+    }
     if (se <= sb) return;
-    for (int k = tid; k < RO_MAXH; k += 256) {
-        hrow[k] = k < p.H ? p.h[(size_t)row * p.H + k] : 0.0f;
-        if (MIX) frow[k] = k < p.HF ? p.feat[(size_t)row * p.HF + k] : 0.0f;
+    if (!GIVEN) {
+        for (int k = tid; k < RO_MAXH; k += 256) {
+            hrow[k] = k < p.H ? p.h[(size_t)row * p.H + k] : 0.0f;
+            if (MIX) frow[k] = k < p.HF ? p.feat[(size_t)row * p.HF + k] : 0.0f;
+        }
     }
     __syncthreads();                                              // (also orders this workgroup's stores to out_rank before its reads below)
 
@@ -408,7 +424,9 @@ __global__ __launch_bounds__(256) void rank_of_finish_kernel(const RankP p)
             c = p.seed_col[si];
             bool ok = c >= 0 && c < p.n_tracks;
             for (int u = sb; ok && u < si; ++u) ok = p.seed_col[u] != c;
-            if (ok) {
+            if (ok && GIVEN) {
+                sc = ro_comp(p.seed_y[si], c);
+            } else if (ok) {
                 const float zd = ro_chain(hrow, p.W + (size_t)c * p.H, p.H) + p.b[c];
                 if (MIX) {
                     const float zt = ro_chain(frow, p.WT + (size_t)c * p.HF, p.HF) + p.bT[c];
@@ -498,13 +516,63 @@ struct RoMix {
     const float* w_title; const float* w_playlist;
 };
 
+// which value is counted and how the seeds leave: the plain logit (their own chain), the title mix (both chains), the ensemble's
+// y (the values in p.seed_y)
+enum RoMode { RO_PLAIN, RO_MIX, RO_ENSEMBLE };
+
+// The launches every call ends with, once p.z holds the answers' values and the counters are zeroed: the ranking scorer's rows
+// h [B][H] packed for this call's row groups, the sort, the count over ctx's fp32 image, the finish.  The caller has filled what
+// differs between the calls: the lists, the scratch, the outputs, the row-major tensors and the mix fields of its mode.
+int rank_of_launches(dae_ctx* ctx, const dae_ro_plan& pl, RankP& p, const float* h, int B, int H, RoMode mode)
+{
+    const dae_packed& pk = ctx->pk_f32;
+    // the hidden rows in the MFMA operand order, for this call's row groups
+    dae_rowgeom g{};
+    g.R_TILE = pl.R_TILE; g.n_rg = pl.n_rg; g.Bpad = pl.n_rg * pl.R_TILE; g.nb_rg = pl.nb_rg; g.grid = pl.grid; g.waves = RO_NW;
+    // the packed hidden image becomes this call's: its pads are for this geometry (the ranking calls re-zero theirs), no row d
+    // belongs to it, and a dae_score_topk_begin waiting for its _finish on this context has lost its rows (it is refused then)
+    ctx->row_d_fresh = false;
+    ctx->h_geom_key = -1;
+    ctx->tk.valid = false;
+    int rc = dae_launch_pack_h(ctx, h, B, H, g, nullptr);
+    if (rc) return rc;
+    p.Wp = static_cast<const float4*>(pk.W.p); p.bias = static_cast<const float*>(pk.bias.p);
+    p.hp = static_cast<const float4*>(ctx->h_packed.p);
+    p.G = pl.G; p.ntiles_r = (p.n_tracks + 31) / 32;
+    p.B = B; p.n_rg = pl.n_rg; p.nb_rg = pl.nb_rg; p.C = pl.C; p.R_TILE = pl.R_TILE;
+
+    hipLaunchKernelGGL(rank_of_prep_kernel, dim3(B), dim3(256), 0, ctx->stream, p);
+    DAE_CHECK_LAUNCH(ctx, "rank_of_prep_kernel");
+    const bool h256 = pl.G == 32;
+    if (mode != RO_PLAIN) {                     // (the run-time k-group count at every width of the ranking scorer's rows)
+        switch (pl.R_TILE) {
+            case 128: rc = launch_count<4, 0, true>(ctx, pl, p); break;
+            case 64:  rc = launch_count<2, 0, true>(ctx, pl, p); break;
+            case 32:  rc = launch_count<1, 0, true>(ctx, pl, p); break;
+            default:  rc = dae_fail(ctx, DAE_ERR_ARG, "bad R_TILE %d", pl.R_TILE);
+        }
+    } else {
+        switch (pl.R_TILE) {
+            case 128: rc = h256 ? launch_count<4, 32, false>(ctx, pl, p) : launch_count<4, 0, false>(ctx, pl, p); break;
+            case 64:  rc = h256 ? launch_count<2, 32, false>(ctx, pl, p) : launch_count<2, 0, false>(ctx, pl, p); break;
+            case 32:  rc = launch_count<1, 0, false>(ctx, pl, p); break;
+            default:  rc = dae_fail(ctx, DAE_ERR_ARG, "bad R_TILE %d", pl.R_TILE);
+        }
+    }
+    if (rc) return rc;
+    if (mode == RO_MIX) hipLaunchKernelGGL(rank_of_finish_kernel<true>, dim3(B), dim3(256), 0, ctx->stream, p);
+    else if (mode == RO_ENSEMBLE) hipLaunchKernelGGL((rank_of_finish_kernel<false, true>), dim3(B), dim3(256), 0, ctx->stream, p);
+    else hipLaunchKernelGGL(rank_of_finish_kernel<false>, dim3(B), dim3(256), 0, ctx->stream, p);
+    DAE_CHECK_LAUNCH(ctx, "rank_of_finish_kernel");
+    return DAE_OK;
+}
+
 int rank_of_core(dae_ctx* ctx, const dae_ro_plan& pl, const float* h, int B, int H, const float* W_dec, const float* b_dec,
                  int V, int n_tracks, const int32_t* seed_row_ptr, const int32_t* seed_col, const int32_t* ans_row_ptr,
                  const int32_t* ans_col, int n_ans, int32_t* out_rank, float* out_logit, int32_t* status,
                  const RoMix* mix = nullptr)
 {
     if (n_ans == 0) return DAE_OK;
-    const dae_packed& pk = ctx->pk_f32;
     // scratch: thr [n_ans] u64 | z [n_ans] | inv [n_ans] | gcnt [n_ans] | glen [n_rg]   (gcnt and glen zeroed together)
     const size_t na = (size_t)n_ans;
     const size_t bytes = na * 8 + na * 4 * 3 + (size_t)pl.n_rg * 4;
@@ -539,21 +607,7 @@ int rank_of_core(dae_ctx* ctx, const dae_ro_plan& pl, const float* h, int B, int
     }
     DAE_HIP_CHECK(ctx, hipMemsetAsync(p.gcnt, 0, na * 4 + (size_t)pl.n_rg * 4, ctx->stream));
 
-    // the hidden rows in the MFMA operand order, for this call's row groups
-    dae_rowgeom g{};
-    g.R_TILE = pl.R_TILE; g.n_rg = pl.n_rg; g.Bpad = pl.n_rg * pl.R_TILE; g.nb_rg = pl.nb_rg; g.grid = pl.grid; g.waves = RO_NW;
-    // the packed hidden image becomes this call's: its pads are for this geometry (the ranking calls re-zero theirs), no row d
-    // belongs to it, and a dae_score_topk_begin waiting for its _finish on this context has lost its rows (it is refused then)
-    ctx->row_d_fresh = false;
-    ctx->h_geom_key = -1;
-    ctx->tk.valid = false;
-    rc = dae_launch_pack_h(ctx, h, B, H, g, nullptr);
-    if (rc) return rc;
-
-    p.Wp = static_cast<const float4*>(pk.W.p); p.bias = static_cast<const float*>(pk.bias.p);
-    p.hp = static_cast<const float4*>(ctx->h_packed.p);
-    p.G = pl.G; p.ntiles_r = (n_tracks + 31) / 32; p.n_tracks = n_tracks; p.V = V;
-    p.B = B; p.n_rg = pl.n_rg; p.nb_rg = pl.nb_rg; p.C = pl.C; p.R_TILE = pl.R_TILE;
+    p.n_tracks = n_tracks; p.V = V;
     p.ans_row_ptr = ans_row_ptr; p.ans_col = ans_col; p.n_ans = n_ans;
     p.seed_row_ptr = seed_row_ptr; p.seed_col = seed_col;
     p.h = h; p.H = H; p.W = W_dec; p.b = b_dec;
@@ -564,30 +618,7 @@ int rank_of_core(dae_ctx* ctx, const dae_ro_plan& pl, const float* h, int B, int
         p.mixT = static_cast<const float*>(ctx->title_y1.p); p.mix_ld = B;
         p.w_title = mix->w_title; p.w_playlist = mix->w_playlist;
     }
-
-    hipLaunchKernelGGL(rank_of_prep_kernel, dim3(B), dim3(256), 0, ctx->stream, p);
-    DAE_CHECK_LAUNCH(ctx, "rank_of_prep_kernel");
-    const bool h256 = pl.G == 32;
-    if (mix) {                                  // (the run-time k-group count at every title feature width)
-        switch (pl.R_TILE) {
-            case 128: rc = launch_count<4, 0, true>(ctx, pl, p); break;
-            case 64:  rc = launch_count<2, 0, true>(ctx, pl, p); break;
-            case 32:  rc = launch_count<1, 0, true>(ctx, pl, p); break;
-            default:  rc = dae_fail(ctx, DAE_ERR_ARG, "bad R_TILE %d", pl.R_TILE);
-        }
-    } else {
-        switch (pl.R_TILE) {
-            case 128: rc = h256 ? launch_count<4, 32, false>(ctx, pl, p) : launch_count<4, 0, false>(ctx, pl, p); break;
-            case 64:  rc = h256 ? launch_count<2, 32, false>(ctx, pl, p) : launch_count<2, 0, false>(ctx, pl, p); break;
-            case 32:  rc = launch_count<1, 0, false>(ctx, pl, p); break;
-            default:  rc = dae_fail(ctx, DAE_ERR_ARG, "bad R_TILE %d", pl.R_TILE);
-        }
-    }
-    if (rc) return rc;
-    if (mix) hipLaunchKernelGGL(rank_of_finish_kernel<true>, dim3(B), dim3(256), 0, ctx->stream, p);
-    else hipLaunchKernelGGL(rank_of_finish_kernel<false>, dim3(B), dim3(256), 0, ctx->stream, p);
-    DAE_CHECK_LAUNCH(ctx, "rank_of_finish_kernel");
-    return DAE_OK;
+    return rank_of_launches(ctx, pl, p, h, B, H, mix ? RO_MIX : RO_PLAIN);
 }
 
 }  // namespace
@@ -667,6 +698,100 @@ int dae_mix_rank_of(dae_ctx* title_ctx, dae_ctx* dae, const float* h, int64_t ld
     const RoMix mix{dae, h, H, W_dec, b_dec, w_title, w_playlist};
     return rank_of_core(ctx, pl, feat, B, (int)ld_feat, OutW_T, Out_b, V, n_tracks, seed_row_ptr, seed_col, ans_row_ptr, ans_col, n_ans,
                         out_rank, out_score, status, &mix);
+}
+
+// THE ENSEMBLE'S CALL (DESIGN.md section 4e "Ranks under the ensemble"): the ranks under the canonical value y of a weighted sum
+// of M members (+ the title scorer), on the ranking context of dae_ensemble_topk.  The thresholds and the seeds' values come from
+// the candidate chains (ensemble.hip), the other scorers' terms from the transposed buffer dae_ensemble_topk builds, and the
+// counting launch is the MIX instantiation over the ranking scorer's image: its epilogue, fl(fl(sigmoid(z_rank) * w) + accT), is
+// the combining kernel's last two operations on the same operands, so an answer's own column meets its own value.
+int dae_ensemble_rank_of(dae_ctx* const* members, int M, const float* const* h, const int* H, const float* const* row_scale,
+                         const float* const* W_dec, const float* const* b_dec, dae_ctx* title_ctx, const float* feat, int ld_feat,
+                         const float* OutW_T, const float* Out_b, const float* w_title, int B, int V, int n_tracks,
+                         const int32_t* seed_row_ptr, const int32_t* seed_col, int n_seed, const int32_t* ans_row_ptr,
+                         const int32_t* ans_col, int n_ans, int32_t* out_rank, float* out_score, int32_t* status)
+{
+    static const char* fn = "dae_ensemble_rank_of";
+    if (!members || M < 1 || !members[M - 1]) return dae_fail(title_ctx, DAE_ERR_ARG, "%s: needs M >= 1 member contexts", fn);
+    const bool titled = title_ctx != nullptr;
+    dae_ctx* ctx = titled ? title_ctx : members[M - 1];                    // the ranking context: it takes the messages too
+    if (!h || !H || !row_scale || !W_dec || !b_dec) return dae_fail(ctx, DAE_ERR_ARG, "null pointer");
+    if (titled ? (!feat || !w_title || !OutW_T || !Out_b) : (feat || w_title || OutW_T || Out_b))
+        return dae_fail(ctx, DAE_ERR_ARG, titled ? "null pointer (feat / Output_W^T / Output_b / w_title of the title context)"
+                                                 : "%s: title tensors without a title context", fn);
+    int Vimg = 0;
+    int rc = dae_ensemble_check(fn, ctx, members, M, h, H, row_scale, title_ctx, ld_feat, DAE_DTYPE_F32, &Vimg);
+    if (rc) return rc;
+    if (V != Vimg) return dae_fail(ctx, DAE_ERR_ARG, "%s: V=%d, the images hold %d columns", fn, V, Vimg);
+    for (int m = 0; m < M; ++m) {
+        if (!W_dec[m] || !b_dec[m]) return dae_fail(ctx, DAE_ERR_ARG, "null pointer (W_dec / b_dec of member %d)", m);
+        if (H[m] <= 0 || (H[m] % 4) != 0 || H[m] > RO_MAXH)
+            return dae_fail(ctx, DAE_ERR_ARG, "H=%d of member %d must be a multiple of 4 in [4, %d]", H[m], m, RO_MAXH);
+        if (reinterpret_cast<uintptr_t>(W_dec[m]) % 16)
+            return dae_fail(ctx, DAE_ERR_ARG, "the decoder tensor of member %d must be 16-byte aligned", m);
+    }
+    // the ranking scorer: its rows, row width and row-major tensors
+    const float* hr = titled ? feat : h[M - 1];
+    const int Hr = titled ? ld_feat : H[M - 1];
+    const float* Wr = titled ? OutW_T : W_dec[M - 1];
+    const float* br = titled ? Out_b : b_dec[M - 1];
+    dae_ro_plan pl;
+    rc = check_rank_of(ctx, hr, B, Hr, Wr, br, V, n_tracks, seed_row_ptr, seed_col, ans_row_ptr, ans_col, n_ans, out_rank, &pl,
+                       titled ? " (the title context)" : " (the last member's context)");
+    if (rc) return rc;
+    if (n_seed < 0) return dae_fail(ctx, DAE_ERR_ARG, "n_seed=%d is negative", n_seed);
+    if (n_seed > 0 && !seed_col) return dae_fail(ctx, DAE_ERR_ARG, "n_seed=%d without a seed CSR", n_seed);
+    if (n_ans == 0) return DAE_OK;
+    const bool seeded = seed_col != nullptr && n_seed > 0;
+
+    const int K = M + (titled ? 1 : 0);
+    const dae_ens_scratch sp = dae_plan_ensemble_scratch(K, n_ans, seeded ? n_seed : 0, pl.n_rg);
+    rc = dae_reserve(ctx, ctx->rank_of, sp.total);
+    if (rc) return rc;
+    const size_t nt32 = (size_t)((n_tracks + 31) / 32 * 32 < V ? (n_tracks + 31) / 32 * 32 : V);
+    rc = dae_reserve(ctx, ctx->title_y1, nt32 * (size_t)B * sizeof(float));
+    if (rc) return rc;
+    char* base = static_cast<char*>(ctx->rank_of.p);
+    float* z = reinterpret_cast<float*>(base + sp.o_z);
+    float* seed_y = reinterpret_cast<float*>(base + sp.o_seed_y);
+    float* s = reinterpret_cast<float*>(base + sp.o_s);
+    float* accT = static_cast<float*>(ctx->title_y1.p);
+
+    // 1. the thresholds, 2. the seeds' values (a status word of their own: none -- an out-of-range seed is ignored, as ever)
+    const dae_ens_tensors t{M, h, H, row_scale, W_dec, b_dec, feat, ld_feat, OutW_T, Out_b, w_title};
+    rc = dae_launch_ensemble_candidates(ctx, t, B, V, ans_row_ptr, ans_col, n_ans, s, sp.s_stride, z, status);
+    if (rc) return rc;
+    if (seeded) {
+        rc = dae_launch_ensemble_candidates(ctx, t, B, V, seed_row_ptr, seed_col, n_seed, s, sp.s_stride, seed_y, nullptr);
+        if (rc) return rc;
+    }
+    // 3. the other scorers' terms, transposed: dae_ensemble_topk's buffer
+    const int n_acc = titled ? M : M - 1;
+    if (n_acc == 0)
+        DAE_HIP_CHECK(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(accT), (int)0x80000000u, nt32 * (size_t)B, ctx->stream));
+    for (int m = 0; m < n_acc; ++m) {
+        dae_ctx* c = members[m];
+        rc = m == 0 ? dae_decode_mix_term(c, h[m], B, H[m], DAE_DTYPE_F32, row_scale[m], n_tracks, accT, B)
+                    : dae_decode_mix_term_add(c, h[m], B, H[m], DAE_DTYPE_F32, row_scale[m], n_tracks, accT, B);
+        if (rc) return dae_fail(ctx, rc, "%s", c->err.c_str());
+    }
+    DAE_HIP_CHECK(ctx, hipMemsetAsync(base + sp.o_gcnt, 0, sp.zero_bytes, ctx->stream));
+
+    // 4. the count over the ranking scorer's image, 5. the finish: the seeds leave by seed_y
+    RankP p{};
+    p.thr = reinterpret_cast<unsigned long long*>(base + sp.o_thr);
+    p.z = z;
+    p.inv = reinterpret_cast<int*>(base + sp.o_inv);
+    p.gcnt = reinterpret_cast<unsigned*>(base + sp.o_gcnt);
+    p.glen = reinterpret_cast<int*>(base + sp.o_glen);
+    p.n_tracks = n_tracks; p.V = V;
+    p.ans_row_ptr = ans_row_ptr; p.ans_col = ans_col; p.n_ans = n_ans;
+    p.seed_row_ptr = seeded ? seed_row_ptr : nullptr; p.seed_col = seeded ? seed_col : nullptr;
+    p.seed_y = seed_y; p.n_seed = seeded ? n_seed : 0;
+    p.out_rank = out_rank; p.out_logit = out_score;
+    p.mixT = accT; p.mix_ld = B;
+    p.w_title = titled ? w_title : row_scale[M - 1];
+    return rank_of_launches(ctx, pl, p, hr, B, Hr, RO_ENSEMBLE);
 }
 
 }  // extern "C"

@@ -775,39 +775,15 @@ int dae_ensemble_topk(dae_ctx* const* members, int M, const float* const* h, con
     if (B < 0 || B > DAE_ROW_SLAB || n_tracks <= 0)
         return dae_fail(rc_ctx, DAE_ERR_ARG, "bad shape B=%d (at most %d rows a call) n_tracks=%d", B, DAE_ROW_SLAB, n_tracks);
     // every context: its rows and weights, one device and stream, no mix of its own, an image of `dtype` over the whole vocabulary
-    const int n_ctx = M + (titled ? 1 : 0);
-    auto ctx_at = [&](int i) { return i < M ? members[i] : title_ctx; };
-    auto name_of = [&](int i, char* buf, size_t n) {
-        if (i < M) snprintf(buf, n, "member %d", i); else snprintf(buf, n, "the title context");
-        return buf;
-    };
-    char who[32];
+    // (ensemble.hip: the checks every ensemble call shares)
     int V = 0;
-    for (int i = 0; i < n_ctx; ++i) {
-        dae_ctx* c = ctx_at(i);
-        name_of(i, who, sizeof(who));
-        if (!c) return dae_fail(rc_ctx, DAE_ERR_ARG, "dae_ensemble_topk: %s is a null context", who);
-        if (i < M && (!h[i] || !row_scale[i])) return dae_fail(rc_ctx, DAE_ERR_ARG, "null pointer (hidden rows / row_scale of %s)", who);
-        for (int o = 0; o < i; ++o)
-            if (ctx_at(o) == c) return dae_fail(rc_ctx, DAE_ERR_ARG, "dae_ensemble_topk: %s is listed twice (every scorer needs a context of its own)", who);
-        if (c->device != rc_ctx->device) return dae_fail(rc_ctx, DAE_ERR_ARG, "dae_ensemble_topk: %s is on another device", who);
-        if (c->stream != rc_ctx->stream) return dae_fail(rc_ctx, DAE_ERR_STATE, "dae_ensemble_topk: %s is bound to another stream", who);
-        if (c->mixT) return dae_fail(rc_ctx, DAE_ERR_STATE, "dae_ensemble_topk sets the mix itself: clear dae_set_score_mix on %s", who);
-        const dae_packed& pk = dtype == DAE_DTYPE_F32 ? c->pk_f32 : c->pk_bf16;
-        const int Hi = i < M ? H[i] : ld_feat;
-        if (!pk.valid) return dae_fail(rc_ctx, DAE_ERR_STATE, "dae_ensemble_topk: %s holds no image prepacked for dtype %d", who, dtype);
-        if (pk.cat_id != 0) return dae_fail(rc_ctx, DAE_ERR_STATE, "dae_ensemble_topk: %s holds a catalogue image", who);
-        if (pk.col_lo != 0 || pk.col_hi != pk.V)
-            return dae_fail(rc_ctx, DAE_ERR_STATE, "dae_ensemble_topk: %s holds a shard image (columns [%d, %d) of %d)", who, pk.col_lo, pk.col_hi, pk.V);
-        if (pk.H != Hi) return dae_fail(rc_ctx, DAE_ERR_ARG, "H=%d of %s does not match its prepacked H=%d", Hi, who, pk.H);
-        if (i == 0) V = pk.V;
-        if (pk.V != V) return dae_fail(rc_ctx, DAE_ERR_ARG, "dae_ensemble_topk: %s holds %d columns, member 0 holds %d", who, pk.V, V);
-    }
+    int rc = dae_ensemble_check("dae_ensemble_topk", rc_ctx, members, M, h, H, row_scale, title_ctx, ld_feat, dtype, &V);
+    if (rc) return rc;
     if (n_tracks > V) return dae_fail(rc_ctx, DAE_ERR_ARG, "n_tracks=%d exceeds the images' %d columns", n_tracks, V);
     if (B == 0) return DAE_OK;
 
     const size_t nt32 = (size_t)((n_tracks + 31) / 32 * 32 < V ? (n_tracks + 31) / 32 * 32 : V);
-    int rc = dae_reserve(rc_ctx, rc_ctx->title_y1, nt32 * (size_t)B * sizeof(float));
+    rc = dae_reserve(rc_ctx, rc_ctx->title_y1, nt32 * (size_t)B * sizeof(float));
     if (rc) return rc;
     float* accT = static_cast<float*>(rc_ctx->title_y1.p);
     const int n_acc = titled ? M : M - 1;                  // members summed in the buffer (untitled: the last one ranks)

@@ -6,7 +6,8 @@ the same config.ini schema:
     [BASE] verbose data_dir result_dir testsize   (+ optional, this build only: train_dtype = f32 | bf16, decode_dtype = f32 | bf16 | exact_bf16,
                                                   eval_metrics = rprecision | all, train_feed = host | device,
                                                   eval_ranks = off | on, eval_mixed_ranks = off | on,
-                                                  ensemble = <pickle>[, <pickle> ...], ensemble_alpha = a0, a1, ...)
+                                                  ensemble = <pickle>[, <pickle> ...], ensemble_alpha = a0, a1, ...,
+                                                  eval_ensemble_ranks = off | on, ensemble_fit = <seed>[, mrr | recall@N])
     [DAE] epochs batch lr reg_lambda hidden test_seed update_seed keep_prob input_kp firstN_range initval save
     [PRETRAIN] epochs batch lr reg_lambda save
     [TITLE] ... (parsed for compatibility; the title models are outside the scoring path)
@@ -94,9 +95,11 @@ class Conf:
         self.train_feed = 'host'
         self.eval_ranks = 'off'
         self.eval_mixed_ranks = 'off'
+        self.eval_ensemble_ranks = 'off'
         for key, allowed in (('train_dtype', ('f32', 'bf16')), ('decode_dtype', ('f32', 'bf16', 'exact_bf16')),
                              ('eval_metrics', ('rprecision', 'all')), ('train_feed', ('host', 'device')),
-                             ('eval_ranks', ('off', 'on')), ('eval_mixed_ranks', ('off', 'on'))):
+                             ('eval_ranks', ('off', 'on')), ('eval_mixed_ranks', ('off', 'on')),
+                             ('eval_ensemble_ranks', ('off', 'on'))):
             if key in self.ini['BASE']:
                 val = self.ini['BASE'][key].strip().lower()
                 if val not in allowed:
@@ -127,6 +130,29 @@ class Conf:
                 raise ValueError("[BASE] ensemble_alpha lists %d weights for %d members (the section's own model first, then the "
                                  "%d of [BASE] ensemble)" % (len(alpha), len(self.ensemble) + 1, len(self.ensemble)))
             self.ensemble_alpha = alpha
+        # ... and two about the ranks under the ensemble (models/ensemble.py rank_of / fit_alphas):
+        #   eval_ensemble_ranks = off | on              --dae --testmode / --title --testmode with [BASE] ensemble: one more line per
+        #                    test split behind the others, "ensemble ranks: ...", eval_ranks' figures from the EXACT ranks under the
+        #                    ensemble's y.  Refused without [BASE] ensemble and in every other run (`refuse_ensemble_keys`)
+        #   ensemble_fit   = <seed>[, mrr | recall@N]   before it evaluates or writes a submission, the run fits the alphas on that
+        #                    test split (written as in test_seed: 5 for test-5) by the metric (default mrr) of the held-out tracks'
+        #                    exact ranks (DAE_ensemble.fit_alphas) and logs them.  Honoured where [BASE] ensemble is; refused
+        #                    beside ensemble_alpha, without ensemble, or when the split's file is missing
+        self.ensemble_fit = None
+        if 'ensemble_fit' in self.ini['BASE'] and self.ini['BASE']['ensemble_fit'].strip():
+            raw = self.ini['BASE']['ensemble_fit']
+            if not self.ensemble:
+                raise ValueError("[BASE] ensemble_fit is set without [BASE] ensemble: there are no alphas to fit")
+            if self.ensemble_alpha is not None:
+                raise ValueError("[BASE] ensemble_fit and [BASE] ensemble_alpha are both set: the alphas are either fitted or "
+                                 "given -- remove one of the keys")
+            parts = _csv(raw)
+            if len(parts) > 2 or not parts[0]:
+                raise ValueError("[BASE] ensemble_fit = %r: <seed>[, <metric>] is required, e.g. 5 or 5, recall@500" % raw)
+            metric = parts[1].lower() if len(parts) > 1 else 'mrr'
+            if metric != 'mrr' and not (metric.startswith('recall@') and metric[7:].isdigit() and int(metric[7:]) >= 1):
+                raise ValueError("[BASE] ensemble_fit = %r: the metric must be mrr or recall@N, not %r" % (raw, metric))
+            self.ensemble_fit = (_seeds(parts[0])[0], metric)
 
     def _load(self, section):
         sec = self.ini[section]
@@ -223,6 +249,22 @@ def refuse_ensemble(conf, args):
                      % (what, "evaluates the tied model alone" if args.testmode else "is a training run"))
 
 
+def refuse_ensemble_keys(conf, args):
+    """[BASE] eval_ensemble_ranks = on needs an ensemble and a run that evaluates with it (--dae --testmode, --title --testmode);
+    [BASE] ensemble_fit needs its split's file.  Refused by name before a reader or a model is built."""
+    if getattr(conf, 'eval_ensemble_ranks', 'off') == 'on':
+        if not getattr(conf, 'ensemble', None):
+            raise ValueError("[BASE] eval_ensemble_ranks = on is set without [BASE] ensemble: there is no ensemble to rank under "
+                             "(remove the key, set eval_ensemble_ranks = off, or use eval_ranks)")
+        if not (args.testmode and not args.pretrain and (args.dae or args.title)):
+            raise ValueError("[BASE] eval_ensemble_ranks = on is honoured by --dae --testmode and --title --testmode only: this run "
+                             "evaluates no ensemble (remove the key or set eval_ensemble_ranks = off)")
+    if getattr(conf, 'ensemble_fit', None):
+        path = os.path.join(conf.data_dir, conf.ensemble_fit[0])
+        if not os.path.exists(path):
+            raise ValueError("[BASE] ensemble_fit = %s: the split's file %s is missing" % (conf.ensemble_fit[0], path))
+
+
 def build_parser():
     ap = argparse.ArgumentParser(description="args")
     ap.add_argument('--dir', type=str, default='qwerty', help="directory name which contains config file")
@@ -247,6 +289,7 @@ def main(argv=None):
     conf = load_conf(dir)
     conf.set_dae_conf()                                   # always first (main.py:121)
     refuse_ensemble(conf, args)
+    refuse_ensemble_keys(conf, args)
     from .main_runner import main_challenge, main_train
     if args.pretrain:
         conf.set_pretrain_conf()

@@ -18,7 +18,7 @@ on the weights the [TITLE] section names (DAEval); playlists without seeds still
 
 [BASE] ensemble = <pickle>[, ...] (optional key of this build): the run's model becomes member 0 of a `DAE_ensemble`
 (models/ensemble.py) with one more member per pickle; refused with a catalogue and where the plain DAE would run
-vocabulary-sharded.
+vocabulary-sharded.  [BASE] ensemble_fit = <seed>[, <metric>] fits its alphas on that test split before the submission is ranked.
 
 [CHALLENGE] catalogue = <file> (optional key of this build): the submission is ranked inside a catalogue -- the tracks the
 file lists (`read_catalogue`) become `model.catalogue(columns)`, and the handle goes to `recommend_iter` / `recommend` as
@@ -208,9 +208,12 @@ def run(conf, model=None):
         model.fit()
         if ens:
             # [BASE] ensemble: the run's model becomes member 0 of an ensemble (models/ensemble.py), titled exactly when it is
-            from ..models.ensemble import from_conf
+            from ..models.ensemble import fit_from_conf, from_conf
             model = from_conf(conf, model)
             log_write(conf, 'ensemble: %d members, alphas %s' % (len(model.members), ', '.join('%g' % a for a in model.alphas)))
+            fitted = fit_from_conf(conf, model, use_titles)           # [BASE] ensemble_fit: before the submission is ranked
+            if fitted:
+                log_write(conf, fitted)
     else:
         use_titles = bool(getattr(model, 'title_model', None))
         sharded = world > 1 and not use_titles

@@ -202,6 +202,32 @@ def _log_mixed_ranks(conf, readers_test, model):
                   % (seed_num, mrr, med, ' '.join("recall@%d %f" % (k, v) for k, v in zip(RANK_CUTS, rec))))
 
 
+def eval_ensemble_ranks(reader_test, conf, model):
+    """[BASE] eval_ensemble_ranks = on: `eval_ranks` under the ensemble's y -- model.rank_of (models/ensemble.py), feed by feed
+    over the feeds of `eval_mixed_ranks` (titles and titles_use under --title) with the seeds cut out of the input
+    -> (MRR, median rank, recall at RANK_CUTS).  A held-out track outside the vocabulary (-1) is a miss that counts in the
+    denominators."""
+    from ..models.ensemble import split_feeds
+    titled = getattr(conf, 'mode', None) == 'title'
+    ranks = []
+    for f in split_feeds(reader_test, titled, getattr(conf, 'strmaxlen', None)):
+        kw = {"titles": f[5], "titles_use": f[6]} if titled else {}
+        for row in model.rank_of(f[0], f[1], f[2], f[3], n_rows=f[4], **kw):
+            ranks.append(row)
+    ranks = np.concatenate(ranks) if ranks else np.zeros(0, np.int32)
+    return met.mean_reciprocal_rank(ranks), met.median_rank(ranks), met.recall_at(ranks, RANK_CUTS)
+
+
+def _log_ensemble_ranks(conf, readers_test, model):
+    """As `_log_ranks`, for [BASE] eval_ensemble_ranks beside [BASE] ensemble: one more line per split, behind the existing ones."""
+    if getattr(conf, 'eval_ensemble_ranks', 'off') != 'on':
+        return
+    for seed_num in readers_test:
+        mrr, med, rec = eval_ensemble_ranks(readers_test[seed_num], conf, model)
+        log_write(conf, "seed num: %s ensemble ranks: mrr %f median %.1f %s"
+                  % (seed_num, mrr, med, ' '.join("recall@%d %f" % (k, v) for k, v in zip(RANK_CUTS, rec))))
+
+
 def _refuse_ranks_under_title(conf):
     if getattr(conf, 'eval_ranks', 'off') == 'on' and getattr(conf, 'mode', None) == 'title':
         raise ValueError("[BASE] eval_ranks = on is not available under --title: it ranks by the DAE's own logits; the ranks "
@@ -236,6 +262,9 @@ def _init_distributed(conf):
 def _refuse_ensemble(conf, only_testmode):
     """[BASE] ensemble outside the runs that honour it (main.py refuse_ensemble says the same from the command line)."""
     if not getattr(conf, 'ensemble', None):
+        if getattr(conf, 'eval_ensemble_ranks', 'off') == 'on':
+            raise ValueError("[BASE] eval_ensemble_ranks = on is set without [BASE] ensemble: there is no ensemble to rank under "
+                             "(remove the key, set eval_ensemble_ranks = off, or use eval_ranks)")
         return
     if not only_testmode:
         raise ValueError("[BASE] ensemble is set, and this is a training run: the key is honoured by --challenge, --dae --testmode "
@@ -246,6 +275,9 @@ def _refuse_ensemble(conf, only_testmode):
     for key in ('eval_ranks', 'eval_mixed_ranks'):
         if getattr(conf, key, 'off') == 'on':
             raise ValueError("[BASE] ensemble is set with [BASE] %s = on: an ensemble has no rank_of (set %s = off)" % (key, key))
+    split = getattr(conf, 'ensemble_fit', None)
+    if split and not os.path.exists(os.path.join(conf.data_dir, split[0])):
+        raise ValueError("[BASE] ensemble_fit = %s: the split's file %s is missing" % (split[0], os.path.join(conf.data_dir, split[0])))
 
 
 def run(conf, only_testmode):
@@ -299,14 +331,18 @@ def run(conf, only_testmode):
         log_write(conf, '<<only test mode>>')
         if getattr(conf, 'ensemble', None):
             # [BASE] ensemble: the splits are ranked by the ensemble around this model (models/ensemble.py), feed by feed
-            from ..models.ensemble import from_conf
+            from ..models.ensemble import fit_from_conf, from_conf
             model = from_conf(conf, model)
             log_write(conf, 'ensemble: %d members, alphas %s' % (len(model.members), ', '.join('%g' % a for a in model.alphas)))
+            fitted = fit_from_conf(conf, model, conf.mode == 'title')         # [BASE] ensemble_fit: before anything is evaluated
+            if fitted:
+                log_write(conf, fitted)
         extras = {} if getattr(conf, 'eval_metrics', 'rprecision') == 'all' else None
         out = _eval_splits(readers_test, conf, model, rank, world, extras)
         _log_splits(conf, readers_test, out, extras)
         _log_ranks(conf, readers_test, model)
         _log_mixed_ranks(conf, readers_test, model)
+        _log_ensemble_ranks(conf, readers_test, model)
         return out
 
     # [BASE] train_feed = device: the training set lives on the device and a batch goes up as the reader's draws alone

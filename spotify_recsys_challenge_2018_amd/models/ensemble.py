@@ -10,6 +10,8 @@ every operation one fp32 rounding in this order (include/dae_hip.h: the canonica
 [n_rows, n_input] matrix: the members' terms meet in one transposed buffer (dae_decode_mix_term, dae_decode_mix_term_add) and
 the last scorer's threshold path ranks its own weighted sigmoid plus that buffer (dae_ensemble_topk).  `ensemble_scores` is
 the readable definition: the dense y from per-member dense decodes and elementwise torch operations in the same order.
+`rank_of` gives the exact rank of given tracks under y over the whole vocabulary (dae_ensemble_rank_of), and `fit_alphas`
+chooses the alphas by those ranks (utils/ensemble_fit.py).
 
 The reference trains a tied `--pretrain` and an untied `--dae` model per challenge category and can use one at a time; their
 pickles are interchangeable "if both have same number of tracks & artists" -- which is all an ensemble asks of its members.
@@ -278,8 +280,79 @@ class DAE_ensemble:
         m0._check_feed()
         return m0._cand_result(values, candidates, rp)
 
+    # -- exact ranks of given tracks under y (dae_ensemble_rank_of) --------------------------------------------------------------------
+    def rank_of(self, x_positions, x_ones, columns, seeds, n_rows=None, titles=None, titles_use=None, want_scores=False,
+                catalogue=None):
+        """Where THESE tracks stand for each playlist under the ensemble's y: per listed (row, column) the number of non-seed
+        track columns that precede it (y descending, ties by column ascending), 0-based, so
+        `rank_of(feed, recommend(feed, seeds)[0], seeds)` is `arange(k)` per row -- below position 1 024 too, where the lists
+        end.  columns, seeds (SEEDS_FROM_INPUT included), n_rows, the return forms and the -1 results (padding, an artist, a
+        seed) are `DAE_title.mixed_rank_of`'s; want_scores -> (ranks, y), -inf beside a rank of -1: `recommend`'s fp32 score
+        column bit for bit.  The dispatch on titles in use is `recommend`'s.  Always fp32 (every scorer's fp32 image is packed
+        for the call); no k applies.  A member with a scoring shard and catalogue= raise ValueError before anything is launched."""
+        import torch
+        if catalogue is not None:
+            raise ValueError("DAE_ensemble.rank_of: ranks inside a catalogue are not built; the ranks are over all n_tracks = %d "
+                             "track columns (call it without catalogue=)" % self.n_tracks)
+        self._refuse()
+        m0, tm = self.members[0], self.title_model
+        n_rows, rp, col, ans, status = m0._cand_begin(columns, n_rows, unique=False)
+        nb, n = self.n_batch, int(col.size)
+        csr, hs, a, feat, w_t = self._begin(x_positions, x_ones, nb, _lib.DAE_DTYPE_F32, titles, titles_use)
+        dev = csr[0].device
+        d_srp, d_sc = m0._seed_csr_dev(seeds, csr, n_rows=nb)
+        rank = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        score = torch.empty(max(n, 1), dtype=torch.float32, device=dev) if want_scores else None
+        ctxs = [m.ctx for m in self.members]
+        title_kw = {} if feat is None else {"feat": feat, "OutW_T": tm.p["Output_WT"], "Out_b": tm.p["Output_b"], "w_title": w_t}
+        ranker = tm.ctx if feat is not None else ctxs[-1]
+        ranker.ensemble_rank_of(ctxs, hs, a, [m.weights["decoder_h"] for m in self.members],
+                                [m.biases["decoder_b"] for m in self.members], self.n_tracks, d_srp, d_sc, ans, n, rank,
+                                out_score=score, status=status, **title_kw)
+        m0._cand_status(status)
+        ranks = rank.cpu().numpy()[:n]
+        scores = score.cpu().numpy()[:n] if want_scores else None
+        m0._check_feed()
+        if want_scores:
+            return m0._rank_result(ranks, columns, rp, n_rows, -1), m0._rank_result(scores, columns, rp, n_rows, -np.inf)
+        return m0._rank_result(ranks, columns, rp, n_rows, -1)
 
-# -- the drivers' keys: [BASE] ensemble = <pickle>[, <pickle> ...], ensemble_alpha = a0, a1, ... ------------------------------------
+    def _ranks_of_feeds(self, feeds):
+        """`rank_of` feed by feed over (x_positions, x_ones, answers, seeds, n_rows[, titles, titles_use]) -> every listed
+        answer's rank, concatenated in order (int32; -1 for what cannot be ranked)."""
+        out = []
+        for f in feeds:
+            kw = {"titles": f[5], "titles_use": f[6] if len(f) > 6 else None} if len(f) > 5 else {}
+            out.extend(np.asarray(r, np.int32).reshape(-1) for r in self.rank_of(f[0], f[1], f[2], f[3], n_rows=f[4], **kw))
+        return np.concatenate(out) if out else np.zeros(0, np.int32)
+
+    def fit_alphas(self, feeds, metric="mrr", steps=10, rounds=4):
+        """Choose the alphas by the exact ranks of held-out tracks: the grid search of utils/ensemble_fit.py `search_simplex` over
+        alphas = i / steps, each point evaluated as `metric` ("mrr" or "recall@N"; utils/metrics.py, a -1 rank a miss that counts
+        in the denominator) of the concatenated `rank_of` ranks of all feeds.  feeds: a re-iterable sequence of
+        (x_positions, x_ones, answers, seeds, n_rows[, titles, titles_use]).  Sets self.alphas to the best point and returns
+        (alphas, value, trace).  Between evaluations only the alphas change.  An ensemble with per-row alphas ([M, n_rows])
+        raises ValueError: the search is over one weight per member."""
+        from ..utils.ensemble_fit import parse_metric, search_simplex
+        if self.alphas.ndim != 1:
+            raise ValueError("DAE_ensemble.fit_alphas: per-row alphas (an array [M, n_rows]) cannot be fitted; the search is over one "
+                             "weight per member")
+        score = parse_metric(metric)
+        kept = self.alphas
+
+        def evaluate(alphas):
+            self.alphas = self._check_alphas(alphas, len(self.members))
+            return score(self._ranks_of_feeds(feeds))
+        try:
+            alphas, value, trace = search_simplex(evaluate, len(self.members), steps=steps, rounds=rounds)
+        except BaseException:
+            self.alphas = kept
+            raise
+        self.alphas = self._check_alphas(alphas, len(self.members))
+        return self.alphas.copy(), value, trace
+
+
+# -- the drivers' keys: [BASE] ensemble = <pickle>[, <pickle> ...], ensemble_alpha = a0, a1, ..., ensemble_fit = <seed>[, <metric>] ------
 def load_member(conf, path):
     """A further member from a pickle of the four arrays a `--pretrain` / `--dae` run saves ([enc_W, dec_W, enc_b, dec_b];
     a tied model's pickle holds its one matrix twice): an untied `DAE` over the run's vocabulary whose hidden size is the
@@ -304,3 +377,33 @@ def from_conf(conf, model):
     pickle of conf.ensemble, conf.ensemble_alpha (or uniform weights), titled when `model` carries a title model."""
     members = [model] + [load_member(conf, p) for p in conf.ensemble]
     return DAE_ensemble(members, alphas=getattr(conf, "ensemble_alpha", None), title_model=getattr(model, "title_model", None))
+
+
+def split_feeds(reader_test, titled, strmaxlen=None):
+    """One test split as `rank_of` feeds, batch by batch as the drivers' evaluations read it: (x_positions, x_ones, the held-out
+    answers, SEEDS_FROM_INPUT, n_rows) and, `titled`, the titles and titles_use as the title evaluation feeds them (a row
+    without a title takes titles_use = 0 and an all-padding title)."""
+    pad = [-1] * int(strmaxlen) if titled else None
+    while True:
+        x_positions, test_seed, test_answer, titles, x_ones = reader_test.next_batch_test()
+        feed = (x_positions, x_ones, [list(a) for a in test_answer], SEEDS_FROM_INPUT, len(test_seed))
+        if titled:
+            use = np.array([0.0 if t is None else 1.0 for t in titles], np.float32)
+            feed += ([t if t is not None else pad for t in titles], use)
+        yield feed
+        if reader_test.test_idx == 0:
+            break
+
+
+def fit_from_conf(conf, ens, titled):
+    """[BASE] ensemble_fit = <seed>[, <metric>]: fit `ens.alphas` on that test split (`DAE_ensemble.fit_alphas` over
+    `split_feeds`) -> the line the drivers log, or None without the key."""
+    if not getattr(conf, "ensemble_fit", None):
+        return None
+    from ..utils.data_reader import data_reader_test
+    split, metric = conf.ensemble_fit
+    reader = data_reader_test(data_dir=conf.data_dir, filename=split, batch_size=ens.n_batch, test_num=conf.testsize)
+    feeds = list(split_feeds(reader, titled, getattr(conf, "strmaxlen", None)))
+    alphas, value, trace = ens.fit_alphas(feeds, metric=metric)
+    return "ensemble: fitted alphas %s (%s %f on %s, %d points evaluated)" % (", ".join("%g" % a for a in alphas), metric, value,
+                                                                              split, len(trace))
