@@ -537,7 +537,7 @@ int dae_pipeline_poll_eval(dae_pipeline* p, int wait, uint64_t* ticket, const da
  *   dae_set_score_mix.  The existing selection kernel ranks the lists (no kernel of its own): they are written at a fixed row
  *   stride, so the call takes row_cap >= the longest row (entries of a row beyond row_cap are not ranked) and V (ids outside
  *   [0, V), -1 included, are absent; the seed bitmap covers [0, V)).  A column listed twice is ranked twice: de-duplicate
- *   before the call (models/DAEs.py does).  1 <= k <= 4096.  Scratch: 8 bytes x B x row_cap. */
+ *   before the call (models/DAEs.py does on the host, dae_candidates_unique on the device).  1 <= k <= 4096.  Scratch: 8 bytes x B x row_cap. */
 #define DAE_CAND_CHUNK 256    /* candidates of one row a workgroup of the candidate kernels takes (a lane each) */
 int dae_decode_candidates(dae_ctx* ctx, const float* h, int64_t ld_h, int B, int H, const float* W_dec, const float* b_dec, int V,
                           const int32_t* cand_row_ptr, const int32_t* cand_col, int n_cand, int out_kind, float* out,
@@ -553,6 +553,52 @@ int dae_mix_candidates(dae_ctx* title_ctx, dae_ctx* dae, const float* h, int64_t
 int dae_rank_candidates(dae_ctx* ctx, int B, int V, const int32_t* cand_row_ptr, const int32_t* cand_col, const float* key,
                         int row_cap, const int32_t* seed_row_ptr, const int32_t* seed_col, int k, int out_kind,
                         float* out_score, int32_t* out_idx);
+/* dae_candidates_unique: the de-duplication dae_rank_candidates asks for, on the device.  cand_col_out[i] = cand_col_in[i], except
+ *   that of all occurrences of a column within ONE row exactly one keeps its id and every other one becomes -1 (padding: absent
+ *   for the ranking, -inf for the scoring calls).  Which occurrence survives is unspecified; it changes no output of
+ *   dae_rank_candidates, because a column's key does not depend on its position.  -1 and ids outside [0, V) pass through
+ *   untouched; nothing at or past n_cand is read or written; in == out is allowed (in place).  One workgroup per row with a
+ *   bitmap over [0, V) in LDS, the row walked in chunks of DAE_CAND_CHUNK: V <= DAE_CAND_UNIQUE_MAX_V, a wider vocabulary is
+ *   refused.  1 <= B <= 4096.  Asynchronous on the context's stream, no scratch. */
+#define DAE_CAND_UNIQUE_MAX_V 1048576    /* a 128 KiB bitmap: the width at which the selection kernel gives up its own seed bitmap */
+int dae_candidates_unique(dae_ctx* ctx, int B, int V, const int32_t* cand_row_ptr, const int32_t* cand_col_in, int32_t* cand_col_out,
+                          int n_cand);
+
+/* The pipeline's CANDIDATES mode: the three calls above over a stream of feeds -- a reranker's candidates, held-out answers among
+ * sampled negatives, a market's columns, for very many playlists -- without a CSR build, an upload, a launch, a fetch and a
+ * synchronisation per batch on the caller's side.  Every feed brings its candidate ids; what comes back is the value of every
+ * listed pair (rank = 0) or each row's k best candidates (rank = 1).
+ *   enable_candidates : once, before the first submit (DAE_ERR_STATE after it, on an evaluation pipeline and on a pipeline with a
+ *                 catalogue; dae_pipeline_enable_eval and dae_pipeline_set_catalogue refuse a candidates pipeline in turn).
+ *                 max_candidates = candidate ids one launch may hold (a launch closes when the next feed's would not fit, as with
+ *                 max_answers).  rank = 0: the values of the listed pairs; rank = 1: per row the k best of its candidates, k as
+ *                 the pipeline was created.  out_kind = DAE_OUT_SCORE or DAE_OUT_LOGIT (the values of rank = 0, the score column
+ *                 of rank = 1); a titled pipeline takes DAE_OUT_SCORE only: the title mix has no logit.  group_rows <= 4096,
+ *                 H % 4 == 0, H <= 1024 (the candidate kernels' limits).
+ *   submit_candidates : dae_pipeline_submit / _submit_titled (titles, titles_use NULL: a plain feed) plus the feed's candidates as
+ *                 a HOST CSR: cand_row_ptr [n_rows + 1] (any base), cand_col int32 GLOBAL column ids -- tracks and artists, -1
+ *                 padding, duplicates allowed.  Staged and uploaded with the feed.  A feed with more ids than max_candidates is
+ *                 refused (DAE_ERR_ARG: score it per batch); a refused feed leaves nothing staged, the pipeline takes the next.
+ *   poll_candidates : rank = 0.  dae_pipeline_poll with *out -> the feed's *n_out floats inside pinned result block *block, in
+ *                 the order of the feed's cand_col: -inf beside a -1, a quiet NaN beside another id outside [0, V).  The launch's
+ *                 status word travels with the block: the call returns DAE_PIPE_BAD_ID (> 0, the results are valid and the
+ *                 block is out) for every feed of a launch that held such an id -- a NaN then marks a bad id, not arithmetic.
+ *                 rank = 1: the lists leave through dae_pipeline_poll ([n_rows, k], (-1, -inf) beyond a row's candidates,
+ *                 scores when want_scores; an id outside [0, V) is absent).  The wrong poll for the mode: DAE_ERR_STATE.
+ * What a lane issues per launch is nothing new: plain launches dae_score_candidates, titled ones the pipeline's title preamble
+ * and dae_mix_candidates; rank = 1 runs dae_candidates_unique in front and dae_rank_candidates behind, over the logits (plain) or
+ * the mixed values (titled, DAE_OUT_LOGIT: the score column holds y), seeds = the playlist's own tracks, row_cap = the launch's
+ * longest row.  The chain is fp32 whatever dtype the pipeline was created with and reads no packed image.  Rows are independent:
+ * every feed gets the bits those calls give it alone; coalescing, lanes, ordering, DAE_PIPE_BUSY, release and stats as above.
+ * Memory: per launch slot 8 bytes per id (cand_col and the values, device; 4 pinned) and a row pointer; per result block
+ * 4 * max_candidates pinned bytes instead of the lists (rank = 0); dae_rank_candidates' scratch in the lane's context. */
+#define DAE_PIPE_BAD_ID 2
+int dae_pipeline_enable_candidates(dae_pipeline* p, int64_t max_candidates, int rank, int out_kind);
+int dae_pipeline_submit_candidates(dae_pipeline* p, const int64_t* positions, const float* values, int values_broadcast, int64_t nnz,
+                                   int n_rows, const int32_t* titles, const float* titles_use, const int32_t* cand_row_ptr,
+                                   const int32_t* cand_col, uint64_t* ticket_out);
+int dae_pipeline_poll_candidates(dae_pipeline* p, int wait, uint64_t* ticket, const float** out, int64_t* n_out, int* n_rows,
+                                 int* block);
 
 /* ---- rank_of: the exact rank of given tracks among ALL rankable tracks of a row (csrc/rank_of.hip) --------------------------
  *

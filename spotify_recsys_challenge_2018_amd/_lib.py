@@ -30,13 +30,16 @@ EXPORTS = [
     "dae_pipeline_create", "dae_pipeline_create_titled", "dae_pipeline_destroy", "dae_pipeline_submit", "dae_pipeline_submit_titled", "dae_pipeline_flush", "dae_pipeline_poll",
     "dae_pipeline_release", "dae_pipeline_stats", "dae_pipeline_exact_margin", "dae_pipeline_times", "dae_pipeline_last_error",
     "dae_rank_metrics", "dae_pipeline_enable_eval", "dae_pipeline_submit_eval", "dae_pipeline_poll_eval",
-    "dae_decode_candidates", "dae_score_candidates", "dae_mix_candidates", "dae_rank_candidates",
+    "dae_decode_candidates", "dae_score_candidates", "dae_mix_candidates", "dae_rank_candidates", "dae_candidates_unique",
+    "dae_pipeline_enable_candidates", "dae_pipeline_submit_candidates", "dae_pipeline_poll_candidates",
     "dae_rank_of_plan", "dae_decode_rank_of", "dae_score_rank_of", "dae_mix_rank_of",
     "dae_ensemble_candidates", "dae_ensemble_rank_of",
     "dae_catalogue_create", "dae_catalogue_destroy", "dae_prepack_decoder_catalogue", "dae_score_topk_catalogue",
     "dae_decode_topk_catalogue", "dae_title_score_catalogue", "dae_pipeline_set_catalogue",
 ]
 DAE_PIPE_BUSY = 1
+DAE_PIPE_BAD_ID = 2             # dae_pipeline_poll_candidates: the feed's launch held an id outside -1 / [0, V) (its slot is a NaN)
+DAE_CAND_UNIQUE_MAX_V = 1 << 20
 
 _lib = None
 
@@ -185,6 +188,10 @@ def load():
     lib.dae_mix_candidates.argtypes = [vp, vp, vp, c_i64, c_int, vp, vp, vp, c_i64, vp, vp, vp, vp, c_int, c_int, vp, vp,
                                        c_int, vp, vp]
     lib.dae_rank_candidates.argtypes = [vp, c_int, c_int, vp, vp, vp, c_int, vp, vp, c_int, c_int, vp, vp]
+    lib.dae_candidates_unique.argtypes = [vp, c_int, c_int, vp, vp, vp, c_int]
+    lib.dae_pipeline_enable_candidates.argtypes = [vp, c_i64, c_int, c_int]
+    lib.dae_pipeline_submit_candidates.argtypes = [vp, vp, vp, c_int, c_i64, c_int, vp, vp, vp, vp, u64p]
+    lib.dae_pipeline_poll_candidates.argtypes = [vp, c_int, u64p, f32pp, ctypes.POINTER(c_i64), ip, ip]
     lib.dae_rank_of_plan.argtypes = [c_int, c_int, c_int, ctypes.POINTER(ctypes.c_int32)]
     lib.dae_decode_rank_of.argtypes = [vp, vp, c_int, c_int, vp, vp, c_int, c_int, vp, vp, vp, vp, c_int, vp, vp, vp]
     lib.dae_score_rank_of.argtypes = [vp, vp, vp, vp, vp, vp, c_int, c_int, c_int, vp, vp, c_int, vp, vp, vp, vp, c_int, vp, vp, vp]
@@ -709,6 +716,12 @@ class Context:
                                                 _ptr(seed_row_ptr), _ptr(seed_col), int(k), int(out_kind), _ptr(out_score),
                                                 _ptr(out_idx)))
 
+    def candidates_unique(self, n_cols, cand, n_cand, out=None):
+        """Per row, every repeated column but one -> -1 (dae_candidates_unique); out=None: in place."""
+        B = cand[0].numel() - 1
+        self.check(self.lib.dae_candidates_unique(self.h, B, int(n_cols), _ptr(cand[0]), _ptr(cand[1]),
+                                                  _ptr(cand[1] if out is None else out), int(n_cand)))
+
     # ---- exact ranks of given tracks over the whole vocabulary (csrc/rank_of.hip): ans = (row_ptr int32 [B + 1], col int32 [>= n_ans])
     def decode_rank_of(self, h, W_dec, b_dec, n_tracks, seed_row_ptr, seed_col, ans, n_ans, out_rank, out_logit=None, status=None):
         """out_rank[i] = how many rankable non-seed tracks precede column ans_col[i] in its row's canonical fp32 order, -1 for
@@ -934,6 +947,7 @@ class Pipeline:
             raise DaeError("dae_pipeline_create failed (%d): %s" % (rc, self.lib.dae_pipeline_last_error(None).decode()))
         self.h = h
         self.eval = False
+        self.cand = self.cand_rank = False
         self.pending = 0                     # feeds submitted and not yet yielded
         self.users = 0                       # streamed loops running on this pipeline (models/stream_loop.py)
         # the foreign calls' out-parameters, made once (a feed is ~25 us of this thread: five ctypes objects and their byref()
@@ -1042,6 +1056,72 @@ class Pipeline:
             return False
         self.pending += 1
         return True
+
+    def enable_candidates(self, max_candidates=1 << 20, rank=False, out_kind=DAE_OUT_SCORE):
+        """The candidates mode (dae_pipeline_enable_candidates), before the first submit: every feed then goes through
+        `submit_candidates`; `poll_candidates` hands out the listed pairs' values (rank=False), `poll` each row's k best
+        candidates (rank=True)."""
+        self._check(self.lib.dae_pipeline_enable_candidates(self.h, int(max_candidates), 1 if rank else 0, int(out_kind)))
+        self.cand, self.cand_rank, self.max_candidates = True, bool(rank), int(max_candidates)
+        self._cp, self._cn = ctypes.POINTER(ctypes.c_float)(), ctypes.c_int64()
+        self._poll_cand_args = (ctypes.byref(self._t), ctypes.byref(self._cp), ctypes.byref(self._cn), ctypes.byref(self._n),
+                                ctypes.byref(self._b))
+
+    def submit_candidates(self, positions, values, n_rows, candidates, titles=None, titles_use=None):
+        """`submit` on a pipeline in candidates mode: the feed with its candidates = (row_ptr int32 [n_rows + 1], col int32), a
+        host CSR over the feed's rows (global column ids; -1 and duplicates allowed).  -> True, or False when every launch slot
+        is taken (poll first)."""
+        import numpy as np
+        pos, val, nnz = self._feed_arrays(positions, values)
+        crp, ccol = candidates
+        if not (type(crp) is np.ndarray and crp.dtype == np.int32 and crp.flags.c_contiguous):
+            crp = np.ascontiguousarray(crp, np.int32)
+        if not (type(ccol) is np.ndarray and ccol.dtype == np.int32 and ccol.flags.c_contiguous):
+            ccol = np.ascontiguousarray(ccol, np.int32)
+        if crp.size != int(n_rows) + 1 or crp[-1] > ccol.size or crp[0] < 0:
+            raise ValueError("candidates: (row_ptr [n_rows + 1], col) with row_ptr[-1] <= len(col)")
+        tt = uu = None
+        if titles is not None:
+            tt = np.ascontiguousarray(titles, np.int32).reshape(-1)
+            uu = np.ascontiguousarray(titles_use, np.float32).reshape(-1)
+            if tt.size != int(n_rows) * (self.title_len or 0) or uu.size != int(n_rows):
+                raise ValueError("titles must be [n_rows, %s] and titles_use [n_rows]" % self.title_len)
+        vp_ = ctypes.c_void_p
+        rc = self._check(self.lib.dae_pipeline_submit_candidates(
+            self.h, vp_(pos.__array_interface__["data"][0]), vp_(val.__array_interface__["data"][0]),
+            1 if (val.size == 1 and nnz != 1) else 0, nnz, int(n_rows),
+            None if tt is None else tt.ctypes.data_as(vp_), None if uu is None else uu.ctypes.data_as(vp_),
+            vp_(crp.__array_interface__["data"][0]), vp_(ccol.__array_interface__["data"][0]), self._t_ref))
+        if rc == DAE_PIPE_BUSY:
+            return False
+        self.pending += 1
+        return True
+
+    def poll_candidates(self, wait=True, copy=False):
+        """The next feed in submission order of a scoring candidates pipeline -> (values float32 [n_out] in the order of the
+        feed's candidate ids, a view of the pinned result block as `poll` hands its lists out; bad: the feed's launch held an
+        id outside -1 / [0, V), whose value is a NaN), or None when it is not ready (wait=False) or nothing is pending."""
+        import numpy as np
+        if self.pending == 0:
+            return None
+        rc = self.lib.dae_pipeline_poll_candidates(self.h, 1 if wait else 0, *self._poll_cand_args)
+        if rc < 0:
+            self._check(rc)
+        if rc == DAE_PIPE_BUSY:
+            raise DaeError("dae_pipeline: every result block is held (drop or copy the arrays of earlier feeds)")
+        if self._n.value == 0:
+            return None
+        self.pending -= 1
+        n, b = int(self._cn.value), self._b.value
+        if n == 0:
+            self._check(self.lib.dae_pipeline_release(self.h, b))
+            return np.zeros(0, np.float32), rc == DAE_PIPE_BAD_ID
+        copy = copy or (b not in self._held and len(self._held) >= self.max_held)
+        owner = _Block(self, b)                  # (the block returns to the pipeline when the last array viewing it dies: `poll`)
+        buf = (ctypes.c_float * n).from_address(ctypes.addressof(self._cp.contents))
+        buf._owner = owner
+        values = np.frombuffer(buf, dtype=np.float32)
+        return (values.copy() if copy else values), rc == DAE_PIPE_BAD_ID
 
     def flush(self):
         self._check(self.lib.dae_pipeline_flush(self.h))

@@ -218,6 +218,37 @@ __global__ __launch_bounds__(256) void candidate_pairs_kernel(const int32_t* __r
     }
 }
 
+// A row's repeated columns -> -1, so that dae_rank_candidates ranks every column once.  One workgroup per row, a bitmap over
+// [0, V) in dynamic LDS (bm_words dwords, zeroed by the workgroup); the row is walked in chunks of DAE_CAND_CHUNK, a lane per id.
+// ds_or_rtn decides: of all lanes that name a column -- in one chunk or in different ones -- exactly one finds its bit clear
+// and keeps the id, every other one writes -1, so no barrier separates the chunks.  -1 and ids outside [0, V) are copied as
+// they are.  A lane reads in[e] before it writes out[e] and touches no other slot: in == out is fine.  Bank conflicts: ids of
+// one wave that fall into the same dword serialise in the LDS atomic unit; random ids over a bitmap of V / 32 dwords rarely do,
+// and a row of one repeated id costs 64 serial atomics per wave -- small next to the 2 x H fetches the row's chains save.
+__global__ __launch_bounds__(DAE_CAND_CHUNK) void candidates_unique_kernel(const int32_t* __restrict__ row_ptr, const int32_t* in,
+                                                                            int32_t* out, int n_cand, int V, int bm_words)
+{
+    extern __shared__ unsigned cu_bitmap[];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const int rb_ = row_ptr[row], re_ = row_ptr[row + 1];
+    const int rb = rb_ > 0 ? rb_ : 0;
+    const int re = re_ < n_cand ? re_ : n_cand;                // nothing is read or written at or past the caller's n_cand
+    if (re - rb < 2) {                                         // (block-uniform) nothing to compare: the copy alone
+        if (tid == 0 && re > rb) out[rb] = in[rb];
+        return;
+    }
+    for (int i = tid; i < bm_words; i += DAE_CAND_CHUNK) cu_bitmap[i] = 0u;
+    __syncthreads();
+    for (int e = rb + tid; e < re; e += DAE_CAND_CHUNK) {
+        int c = in[e];
+        if (c >= 0 && c < V) {                                 // (c >> 5 < bm_words = ceil(V / 32))
+            const unsigned bit = 1u << (c & 31);
+            if (atomicOr(&cu_bitmap[c >> 5], bit) & bit) c = -1;
+        }
+        out[e] = c;
+    }
+}
+
 int check_cand_args(dae_ctx* ctx, const void* h, int64_t ld_h, int B, int H, const void* W, const void* b, int V,
                     const void* row_ptr, const void* col, int n_cand, const void* out)
 {
@@ -308,6 +339,26 @@ int dae_mix_candidates(dae_ctx* title_ctx, dae_ctx* dae, const float* h, int64_t
     p.row_ptr = cand_row_ptr; p.col = cand_col; p.n_cand = n_cand; p.B = B;
     p.out_kind = DAE_OUT_LOGIT; p.out = out; p.status = status;
     return launch_candidates(ctx, p, true);
+}
+
+int dae_candidates_unique(dae_ctx* ctx, int B, int V, const int32_t* cand_row_ptr, const int32_t* cand_col_in, int32_t* cand_col_out,
+                          int n_cand)
+{
+    if (!ctx) return DAE_ERR_ARG;
+    if (!cand_row_ptr || !cand_col_in || !cand_col_out) return dae_fail(ctx, DAE_ERR_ARG, "null pointer");
+    if (B < 1 || B > 4096) return dae_fail(ctx, DAE_ERR_ARG, "B=%d out of [1, 4096]", B);
+    if (V <= 0 || n_cand < 0) return dae_fail(ctx, DAE_ERR_ARG, "bad shape V=%d n_cand=%d", V, n_cand);
+    if (V > DAE_CAND_UNIQUE_MAX_V)
+        return dae_fail(ctx, DAE_ERR_ARG, "dae_candidates_unique: V=%d is too wide for the LDS bitmap over [0, V) (at most %d columns)", V,
+                        DAE_CAND_UNIQUE_MAX_V);
+    if (n_cand == 0) return DAE_OK;
+    const int bm_words = (V + 31) >> 5;
+    const size_t lds = (size_t)bm_words * sizeof(unsigned);
+    DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, candidates_unique_kernel, (size_t)DAE_CAND_UNIQUE_MAX_V / 8));
+    hipLaunchKernelGGL(candidates_unique_kernel, dim3(B), dim3(DAE_CAND_CHUNK), lds, ctx->stream, cand_row_ptr, cand_col_in, cand_col_out,
+                       n_cand, V, bm_words);
+    DAE_CHECK_LAUNCH(ctx, "candidates_unique_kernel");
+    return DAE_OK;
 }
 
 int dae_rank_candidates(dae_ctx* ctx, int B, int V, const int32_t* cand_row_ptr, const int32_t* cand_col, const float* key,

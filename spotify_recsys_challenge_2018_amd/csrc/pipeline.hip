@@ -301,32 +301,42 @@ int dae_pipeline_flush(dae_pipeline* p)
 
 static int submit_impl(dae_pipeline* p, const int64_t* positions, const float* values, int values_broadcast, int64_t nnz,
                        int n_rows, const int32_t* titles, const float* titles_use, const int32_t* ans_rp, const int32_t* ans_col,
-                       uint64_t* ticket_out)
+                       const int32_t* cand_rp, const int32_t* cand_col, uint64_t* ticket_out)
 {
     if (!p) return DAE_ERR_ARG;
     const int titled = titles != nullptr ? 1 : 0;
-    int64_t n_ans = 0;
+    int64_t n_ans = 0, n_cand = 0;
+    int longest = 0;
+    // (p->cand, like p->eval, is set once, before the first submit, by the caller's own thread)
+    if (p->cand != (cand_rp != nullptr))
+        return pfail(p, DAE_ERR_STATE, p->cand ? "dae_pipeline: a candidates pipeline takes dae_pipeline_submit_candidates only"
+                                               : "dae_pipeline_submit_candidates: dae_pipeline_enable_candidates was not called");
+    if (p->cand)
+        if (const StageErr e = p->check_candidates(n_rows, cand_rp, cand_col, &n_cand, &longest)) return stage_fail(p, e);
     // (p->eval is set once, before the first submit, by the caller's own thread)
     if (const StageErr e = p->check_feed(p->eval, positions, values, nnz, n_rows, ans_rp, ans_col, &n_ans)) return stage_fail(p, e);
     const auto t_sub = std::chrono::steady_clock::now();
     if (titled && !p->rows_inside(positions, nnz, n_rows)) return stage_fail(p, p->bad_row());
     std::unique_lock<std::mutex> lk(p->mu);
     if (p->err_code) return p->err_code;
-    if (p->open_slot >= 0 && !p->fits_open(n_rows, nnz, titled, n_ans)) {
+    if (p->open_slot >= 0 && (!p->fits_open(n_rows, nnz, titled, n_ans) || (p->cand && !p->cand_fits_open(n_cand)))) {
         const int rc = close_open(p);
         if (rc) return rc;
     }
     Staged at;
     if (const StageErr e = p->begin(n_rows, nnz, titled, n_ans, &at)) return stage_fail(p, e);
-    lk.unlock();                                            // the copy runs outside the lock (the worker never touches an open slot)
+    if (p->cand) p->begin_candidates(&at, n_cand, longest);
+    lk.unlock();                                           // the copy runs outside the lock (the worker never touches an open slot)
     if (!p->copy_positions(at, titled, positions, nnz, n_rows)) {
         lk.lock();                                           // nothing of this feed stays: the slot is as it was before the call
+        if (p->cand) p->rollback_candidates(at, n_cand);
         p->rollback(at, n_rows, nnz, n_ans);
         return stage_fail(p, p->bad_row());
     }
     p->copy_values(at, values, values_broadcast, nnz);
     if (titled) p->copy_titles(at, titles, titles_use, n_rows);
     if (ans_rp) p->copy_answers(at, ans_rp, ans_col, n_rows, n_ans);
+    if (cand_rp) p->copy_candidates(at, cand_rp, cand_col, n_rows, n_cand);
     if (ticket_out) *ticket_out = at.ticket;
     lk.lock();
     if (p->open_is_full_for(n_rows)) (void)close_open(p);   // the next feed of this size would not fit: off it goes
@@ -337,7 +347,7 @@ static int submit_impl(dae_pipeline* p, const int64_t* positions, const float* v
 int dae_pipeline_submit(dae_pipeline* p, const int64_t* positions, const float* values, int values_broadcast, int64_t nnz,
                         int n_rows, uint64_t* ticket_out)
 {
-    return submit_impl(p, positions, values, values_broadcast, nnz, n_rows, nullptr, nullptr, nullptr, nullptr, ticket_out);
+    return submit_impl(p, positions, values, values_broadcast, nnz, n_rows, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ticket_out);
 }
 
 int dae_pipeline_submit_titled(dae_pipeline* p, const int64_t* positions, const float* values, int values_broadcast, int64_t nnz,
@@ -346,7 +356,7 @@ int dae_pipeline_submit_titled(dae_pipeline* p, const int64_t* positions, const 
     if (!p) return DAE_ERR_ARG;
     if (!p->has_title) return pfail(p, DAE_ERR_STATE, "dae_pipeline_submit_titled: not a titled pipeline (dae_pipeline_create_titled)");
     if (!titles || !titles_use) return pfail(p, DAE_ERR_ARG, "null pointer");
-    return submit_impl(p, positions, values, values_broadcast, nnz, n_rows, titles, titles_use, nullptr, nullptr, ticket_out);
+    return submit_impl(p, positions, values, values_broadcast, nnz, n_rows, titles, titles_use, nullptr, nullptr, nullptr, nullptr, ticket_out);
 }
 
 int dae_pipeline_submit_eval(dae_pipeline* p, const int64_t* positions, const float* values, int values_broadcast, int64_t nnz,
@@ -357,7 +367,62 @@ int dae_pipeline_submit_eval(dae_pipeline* p, const int64_t* positions, const fl
     if (!ans_row_ptr) return pfail(p, DAE_ERR_ARG, "null pointer");
     if ((titles != nullptr) != (titles_use != nullptr)) return pfail(p, DAE_ERR_ARG, "titles and titles_use come together");
     if (titles && !p->has_title) return pfail(p, DAE_ERR_STATE, "dae_pipeline_submit_eval: not a titled pipeline (dae_pipeline_create_titled)");
-    return submit_impl(p, positions, values, values_broadcast, nnz, n_rows, titles, titles_use, ans_row_ptr, ans_col, ticket_out);
+    return submit_impl(p, positions, values, values_broadcast, nnz, n_rows, titles, titles_use, ans_row_ptr, ans_col, nullptr, nullptr,
+                       ticket_out);
+}
+
+int dae_pipeline_submit_candidates(dae_pipeline* p, const int64_t* positions, const float* values, int values_broadcast, int64_t nnz,
+                                   int n_rows, const int32_t* titles, const float* titles_use, const int32_t* cand_row_ptr,
+                                   const int32_t* cand_col, uint64_t* ticket_out)
+{
+    if (!p) return DAE_ERR_ARG;
+    if (!cand_row_ptr) return pfail(p, DAE_ERR_ARG, "null pointer");
+    if ((titles != nullptr) != (titles_use != nullptr)) return pfail(p, DAE_ERR_ARG, "titles and titles_use come together");
+    if (titles && !p->has_title)
+        return pfail(p, DAE_ERR_STATE, "dae_pipeline_submit_candidates: not a titled pipeline (dae_pipeline_create_titled)");
+    return submit_impl(p, positions, values, values_broadcast, nnz, n_rows, titles, titles_use, nullptr, nullptr, cand_row_ptr, cand_col,
+                       ticket_out);
+}
+
+// Before the first submit: the candidates' staging and device arrays per launch slot; in score mode the values' pinned blocks
+// take the place of the lists' (which go back: nothing will be copied into them).
+int dae_pipeline_enable_candidates(dae_pipeline* p, int64_t max_candidates, int rank, int out_kind)
+{
+    if (!p) return DAE_ERR_ARG;
+    if (max_candidates < 1 || max_candidates >= ((int64_t)1 << 31) || (rank != 0 && rank != 1))
+        return pfail(p, DAE_ERR_ARG, "dae_pipeline_enable_candidates: needs 1 <= max_candidates < 2^31 and rank = 0 or 1");
+    if (out_kind != DAE_OUT_SCORE && out_kind != DAE_OUT_LOGIT)
+        return pfail(p, DAE_ERR_ARG, "dae_pipeline_enable_candidates: out_kind is DAE_OUT_SCORE or DAE_OUT_LOGIT");
+    std::unique_lock<std::mutex> lk(p->mu);
+    if (p->err_code) return p->err_code;
+    if (p->eval) return pfail(p, DAE_ERR_STATE, "dae_pipeline_enable_candidates: an evaluation pipeline (dae_pipeline_enable_eval) takes no candidates");
+    if (p->cat) return pfail(p, DAE_ERR_STATE, "dae_pipeline_enable_candidates: a pipeline with a catalogue (dae_pipeline_set_catalogue) takes no candidates");
+    if (p->cand || p->next_ticket != 1) return pfail(p, DAE_ERR_STATE, "dae_pipeline_enable_candidates: once, before the first submit");
+    if (p->has_title && out_kind != DAE_OUT_SCORE)
+        return pfail(p, DAE_ERR_ARG, "dae_pipeline_enable_candidates: DAE_OUT_LOGIT on a titled pipeline -- the title mix has no logit "
+                                     "(DAE_OUT_SCORE)");
+    // what the candidate kernels take (candidates.hip check_cand_args), refused here instead of at the first launch
+    if (p->group_rows > 4096 || (p->H % 4) != 0 || p->H > 1024 || (p->has_title && ((p->tw.ld_feat % 4) != 0 || p->tw.ld_feat > 1024)))
+        return pfail(p, DAE_ERR_ARG, "dae_pipeline_enable_candidates: the candidate kernels take launches of at most 4096 rows "
+                                     "(group_rows) and hidden / title feature rows that are multiples of 4 up to 1024");
+    DeviceGuard dev_guard(p->device);
+    const size_t rows = (size_t)p->group_rows, nc = (size_t)max_candidates;
+    PipeMem& M = p->mem;
+    for (Slot& S : p->slots) {
+        S.h_crp = M.pinned<int32_t>(rows + 1); S.h_ccol = M.pinned<int32_t>(nc);
+        S.d_crp = M.dev<int32_t>(rows + 1); S.d_ccol = M.dev<int32_t>(nc);
+        S.d_cout = M.dev<float>(nc); S.d_cstatus = M.dev<int32_t>(1);
+    }
+    if (!rank)
+        for (OutBlock& b : p->blocks) {
+            b.cand = M.pinned<float>(nc + 4);                // (the launch's status word sits behind the values)
+            M.give_back(b.idx); M.give_back(b.score);
+        }
+    if (!M.ok) return pfatal(p, DAE_ERR_NOMEM, "dae_pipeline_enable_candidates: allocation failed");
+    p->max_candidates = max_candidates;
+    p->cand_rank = rank; p->cand_out_kind = out_kind;
+    p->cand = true;
+    return DAE_OK;
 }
 
 // Before the first submit: the discount table on the device, the answers' staging and the records' blocks; the lists' pinned
@@ -369,6 +434,7 @@ int dae_pipeline_enable_eval(dae_pipeline* p, const double* disc_host, int64_t m
         return pfail(p, DAE_ERR_ARG, "dae_pipeline_enable_eval: needs a discount table and 1 <= max_answers < 2^31");
     std::unique_lock<std::mutex> lk(p->mu);
     if (p->err_code) return p->err_code;
+    if (p->cand) return pfail(p, DAE_ERR_STATE, "dae_pipeline_enable_eval: a candidates pipeline (dae_pipeline_enable_candidates) has no evaluation mode");
     if (p->eval || p->next_ticket != 1) return pfail(p, DAE_ERR_STATE, "dae_pipeline_enable_eval: once, before the first submit");
     DeviceGuard dev_guard(p->device);
     const size_t rows = (size_t)p->group_rows, na = (size_t)max_answers;
@@ -398,6 +464,7 @@ int dae_pipeline_set_catalogue(dae_pipeline* p, const dae_catalogue* cat)
     if (!cat) return pfail(p, DAE_ERR_ARG, "null pointer");
     std::unique_lock<std::mutex> lk(p->mu);
     if (p->err_code) return p->err_code;
+    if (p->cand) return pfail(p, DAE_ERR_STATE, "dae_pipeline_set_catalogue: a candidates pipeline (dae_pipeline_enable_candidates) ranks no catalogue");
     if (p->cat || p->next_ticket != 1) return pfail(p, DAE_ERR_STATE, "dae_pipeline_set_catalogue: once, before the first submit");
     int cat_dev = -1, cat_n = 0, cat_tracks = 0;
     dae_catalogue_shape(cat, &cat_dev, &cat_n, &cat_tracks);
@@ -434,10 +501,17 @@ int dae_pipeline_set_catalogue(dae_pipeline* p, const dae_catalogue* cat)
 }
 
 static int poll_impl(dae_pipeline* p, int wait, uint64_t* ticket, const int32_t** idx, const float** score,
-                     const dae_metric_rec** rec, int* n_rows, int* block)
+                     const dae_metric_rec** rec, const float** cout, int64_t* n_out, int* n_rows, int* block)
 {
     if (!p) return DAE_ERR_ARG;
-    if ((!idx && !rec) || !n_rows || !block) return pfail(p, DAE_ERR_ARG, "null pointer");
+    if ((!idx && !rec && !cout) || !n_rows || !block) return pfail(p, DAE_ERR_ARG, "null pointer");
+    // candidates mode: the values of a scoring pipeline leave through dae_pipeline_poll_candidates, the lists of a ranking one
+    // through dae_pipeline_poll
+    if (cout && !(p->cand && !p->cand_rank))
+        return pfail(p, DAE_ERR_STATE, p->cand ? "dae_pipeline_poll_candidates: a ranking candidates pipeline (rank = 1) hands out lists (dae_pipeline_poll)"
+                                               : "dae_pipeline_poll_candidates: dae_pipeline_enable_candidates was not called");
+    if (idx && p->cand && !p->cand_rank)
+        return pfail(p, DAE_ERR_STATE, "dae_pipeline_poll: a scoring candidates pipeline (rank = 0) hands out values (dae_pipeline_poll_candidates)");
     if (p->eval != (rec != nullptr))
         return pfail(p, DAE_ERR_STATE, p->eval ? "dae_pipeline: an evaluation pipeline hands out records (dae_pipeline_poll_eval)"
                                                : "dae_pipeline_poll_eval: dae_pipeline_enable_eval was not called");
@@ -446,6 +520,7 @@ static int poll_impl(dae_pipeline* p, int wait, uint64_t* ticket, const int32_t*
     if (idx) *idx = nullptr;
     if (rec) *rec = nullptr;
     if (score) *score = nullptr;
+    if (cout) { *cout = nullptr; *n_out = 0; }
     Slot& S = p->slots[p->poll_slot];
     if (S.state == 0) return p->err_code;                    // nothing pending (0 rows), or the worker's error
     if (S.state == 1) {
@@ -479,7 +554,9 @@ static int poll_impl(dae_pipeline* p, int wait, uint64_t* ticket, const int32_t*
             lk.lock();
             return pfatal(p, DAE_ERR_ARG, "dae_pipeline: a feed of the launch holds a column index out of range");
         }
-        if (S.titled && S.ran_dtype == DAE_DTYPE_BF16_EXACT && S.h_flags[1] != p->lanes[S.lane].guard_seen) {
+        if (p->cand) {
+            lk.lock();                                           // (the candidate chain is fp32 whatever the dtype: no guard to ask)
+        } else if (S.titled && S.ran_dtype == DAE_DTYPE_BF16_EXACT && S.h_flags[1] != p->lanes[S.lane].guard_seen) {
             // the exact title mix (dae_mix_topk_exact): the title context's guard words moved under this launch -- a recomputed
             // logit left its promised interval (column >= 0), or rows hold more survivors than the refine launch lists (column
             // -2 / -3: scores no bound can tell apart; such rows came back without recommendations) -> the launch again on the
@@ -513,28 +590,40 @@ static int poll_impl(dae_pipeline* p, int wait, uint64_t* ticket, const int32_t*
     const auto h = p->hand_out();                            // (the references, and behind a launch's last feed the ring)
     const OutBlock& ob = p->blocks[h.block];
     if (ticket) *ticket = h.feed.ticket;
+    int rc_out = DAE_OK;
     if (rec) {
         *rec = ob.rec + h.feed.row0;
+    } else if (cout) {
+        *cout = ob.cand + h.feed.coff;
+        *n_out = h.feed.n_cand;
+        // the launch's status word came out with the block: an id outside -1 / [0, V) somewhere in the launch (its slot holds a NaN)
+        if (*reinterpret_cast<const int32_t*>(ob.cand + p->max_candidates) != 0) rc_out = DAE_PIPE_BAD_ID;
     } else {
         *idx = ob.idx + (size_t)h.feed.row0 * p->k;
         if (score) *score = p->want_scores ? ob.score + (size_t)h.feed.row0 * p->k : nullptr;
     }
     *n_rows = h.feed.n_rows;
     *block = h.block;
-    return DAE_OK;
+    return rc_out;
 }
 
 int dae_pipeline_poll(dae_pipeline* p, int wait, uint64_t* ticket, const int32_t** idx, const float** score, int* n_rows,
                       int* block)
 {
     if (p && !idx) return pfail(p, DAE_ERR_ARG, "null pointer");
-    return poll_impl(p, wait, ticket, idx, score, nullptr, n_rows, block);
+    return poll_impl(p, wait, ticket, idx, score, nullptr, nullptr, nullptr, n_rows, block);
 }
 
 int dae_pipeline_poll_eval(dae_pipeline* p, int wait, uint64_t* ticket, const dae_metric_rec** rec, int* n_rows, int* block)
 {
     if (p && !rec) return pfail(p, DAE_ERR_ARG, "null pointer");
-    return poll_impl(p, wait, ticket, nullptr, nullptr, rec, n_rows, block);
+    return poll_impl(p, wait, ticket, nullptr, nullptr, rec, nullptr, nullptr, n_rows, block);
+}
+
+int dae_pipeline_poll_candidates(dae_pipeline* p, int wait, uint64_t* ticket, const float** out, int64_t* n_out, int* n_rows, int* block)
+{
+    if (p && (!out || !n_out)) return pfail(p, DAE_ERR_ARG, "null pointer");
+    return poll_impl(p, wait, ticket, nullptr, nullptr, nullptr, out, n_out, n_rows, block);
 }
 
 int dae_pipeline_release(dae_pipeline* p, int block)

@@ -136,8 +136,13 @@ int pipe_issue(dae_pipeline* p, Slot& S, int dtype)
         if (S.n_ans > 0)
             PIPE_HIP(p, hipMemcpyAsync(S.d_acol, S.h_acol, (size_t)S.n_ans * sizeof(int32_t), hipMemcpyHostToDevice, p->copy_stream));
     }
+    if (p->cand) {
+        PIPE_HIP(p, hipMemcpyAsync(S.d_crp, S.h_crp, (size_t)(S.rows + 1) * sizeof(int32_t), hipMemcpyHostToDevice, p->copy_stream));
+        if (S.n_cand > 0)
+            PIPE_HIP(p, hipMemcpyAsync(S.d_ccol, S.h_ccol, (size_t)S.n_cand * sizeof(int32_t), hipMemcpyHostToDevice, p->copy_stream));
+    }
     PIPE_HIP(p, hipEventRecord(S.ev_h2d, p->copy_stream));
-    if (p->dtype == DAE_DTYPE_F32 && p->lanes.size() > 1) {
+    if (p->dtype == DAE_DTYPE_F32 && p->lanes.size() > 1 && !p->cand) {       // (a candidates launch has no decode launch to gate)
         // the fp32 filter launch takes every CU, two of them in flight only queue behind each other: this launch's waits for
         // the one issued before it (on another lane) and announces its own end.  One event per launch SLOT: re-recording a
         // lane's event while its previous record was still pending made hipEventRecord wait for it (0.7 ms per launch).
@@ -154,7 +159,7 @@ int pipe_issue(dae_pipeline* p, Slot& S, int dtype)
     int32_t* const out_idx = S.d_idx;
     float* const out_score = p->want_scores ? S.d_score : L.d_score;     // (scores nobody fetches stay on the lane)
     const TitleW& t = p->tw;
-    if (S.titled && dtype == DAE_DTYPE_F32) { rc = pipe_ensure_f32(p, S.lane); if (rc) return rc; }
+    if (S.titled && dtype == DAE_DTYPE_F32 && !p->cand) { rc = pipe_ensure_f32(p, S.lane); if (rc) return rc; }
     // The half that does not depend on the lane's previous launch, on the PREP stream (contexts of its own), behind the upload;
     // the lane's stream only waits for its event.  Plain launches: the feed -> CSR and the seed lists (the playlist's own
     // tracks) in ONE group of four launches (round 6: six + a wider feed).  Titled ones (main_challenge.py:80-90 with DAE_title;
@@ -179,7 +184,32 @@ int pipe_issue(dae_pipeline* p, Slot& S, int dtype)
     }
     PIPE_HIP(p, hipEventRecord(S.ev_prep, p->prep_stream));
     PIPE_HIP(p, hipStreamWaitEvent(L.stream, S.ev_prep, 0));
-    if (S.titled) {
+    if (p->cand) {
+        // candidates mode: the value of every listed (row, column) -- fp32 chains over the model's row-major tensors whatever the
+        // pipeline's dtype, no packed image -- in the order of the launch's candidate CSR; a ranking pipeline drops a row's repeated
+        // columns first (in place: the upload is this launch's own) and ranks the values behind them: the logits (plain) or the
+        // mixed values (titled: DAE_OUT_LOGIT, so that out_score holds y), seeds = the playlist's own tracks
+        const int nc = (int)S.n_cand;
+        PIPE_HIP(p, hipMemsetAsync(S.d_cstatus, 0, sizeof(int32_t), L.stream));
+        if (p->cand_rank) {
+            rc = dae_candidates_unique(L.ctx, S.rows, p->V, S.d_crp, S.d_ccol, S.d_ccol, nc);
+            if (rc) return pfatal(p, rc, dae_last_error(L.ctx));
+        }
+        if (S.titled) {
+            rc = dae_mix_candidates(L.tctx, L.ctx, S.t_h, p->H, p->H, p->W_dec, p->b_dec, S.t_feat, t.ld_feat, t.out_WT, t.out_b, S.t_wt,
+                                    S.t_wp, S.rows, p->V, S.d_crp, S.d_ccol, nc, S.d_cout, S.d_cstatus);
+            if (rc) return pfatal(p, rc, dae_last_error(L.tctx));
+        } else {
+            rc = dae_score_candidates(L.ctx, S.d_rp, S.d_col, S.d_cval, p->W_enc, p->b_enc, p->V, p->H, S.rows, p->W_dec, p->b_dec, S.d_crp,
+                                      S.d_ccol, nc, p->cand_rank ? DAE_OUT_LOGIT : p->cand_out_kind, S.d_cout, S.d_cstatus);
+            if (rc) return pfatal(p, rc, dae_last_error(L.ctx));
+        }
+        if (p->cand_rank) {
+            rc = dae_rank_candidates(L.ctx, S.rows, p->V, S.d_crp, S.d_ccol, S.d_cout, S.cand_cap, S.d_srp, S.d_scol, p->k,
+                                     S.titled ? DAE_OUT_LOGIT : p->cand_out_kind, out_score, out_idx);
+            if (rc) return pfatal(p, rc, dae_last_error(L.ctx));
+        }
+    } else if (S.titled) {
         rc = p->cat ? dae_title_rank_catalogue(L.tctx, L.ctx, dtype, S.rows, p->H, t.ld_feat, tb, p->cat, p->k, out_score, out_idx, L.d_guard)
                     : dae_title_rank(L.tctx, L.ctx, dtype, S.rows, p->V, p->H, t.ld_feat, tb, p->n_tracks, p->k, out_score, out_idx, L.d_guard);
         if (rc) return pfatal(p, rc, dae_last_error(L.tctx));
@@ -201,7 +231,9 @@ int pipe_issue(dae_pipeline* p, Slot& S, int dtype)
     // The small words first pass through one device block (flags: status, guard words), so the out thread's copies of a
     // launch are two or three.
     const int32_t* gw = nullptr;                             // the guard words as this launch left them (titled fp32: zeros)
-    if (S.titled) {
+    if (p->cand) {
+        // (no bound to guard: fp32 chains)
+    } else if (S.titled) {
         gw = L.d_guard;
     } else if (dtype == DAE_DTYPE_BF16_EXACT) {
         rc = dae_exact_guard_words(L.ctx, &gw);
@@ -250,6 +282,13 @@ void pipe_out_worker_main(dae_pipeline* p)
             // the word is seen, so the wait costs nothing and the copies do not rest on the kernel-end write-back alone)
             if (e == hipSuccess) e = hipStreamWaitEvent(p->out_stream, S.ev_scored, 0);
             if (e == hipSuccess) e = hipMemcpyAsync(ob.rec, S.d_rec, (size_t)S.rows * sizeof(dae_metric_rec), hipMemcpyDeviceToHost, p->out_stream);
+        } else if (p->cand && !p->cand_rank) {
+            // the values instead of the lists, and the candidate kernels' status word behind the block's values
+            if (e == hipSuccess) e = hipStreamWaitEvent(p->out_stream, S.ev_scored, 0);
+            if (e == hipSuccess && S.n_cand > 0)
+                e = hipMemcpyAsync(ob.cand, S.d_cout, (size_t)S.n_cand * sizeof(float), hipMemcpyDeviceToHost, p->out_stream);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(ob.cand + p->max_candidates, S.d_cstatus, sizeof(int32_t), hipMemcpyDeviceToHost, p->out_stream);
         } else {
             if (e == hipSuccess) e = hipMemcpyAsync(ob.idx, S.d_idx, nb * sizeof(int32_t), hipMemcpyDeviceToHost, p->out_stream);
             if (e == hipSuccess && p->want_scores) e = hipMemcpyAsync(ob.score, S.d_score, nb * sizeof(float), hipMemcpyDeviceToHost, p->out_stream);

@@ -1,6 +1,6 @@
 // pipeline_stage.h -- the CALLER THREAD's half of the streaming pipeline (pipeline.hip): what dae_pipeline_submit*, _flush, _poll*
 // and _release do that touches no device -- the feed checks, the fit test that closes a launch, the ring of launch slots, the
-// staging copies with the rollback of a refused feed, the answers' CSR and the result blocks' reference counts.  Host arithmetic
+// staging copies with the rollback of a refused feed, the answers' and the candidates' CSR and the result blocks' reference counts.  Host arithmetic
 // on host memory: no HIP, nothing of dae_internal.h, only the standard library (tests/host/pipeline_stage_main.cpp drives it
 // without a device).  pipeline.hip calls these under its lock `mu`, except the copies, which run outside it (the worker never
 // touches an open slot).  Everything is defined in the class, hence inline: the plain feed's copy stays one inlined pass.
@@ -19,7 +19,7 @@ struct StageErr {                 // kind 0: fine; otherwise the message of the 
     explicit operator bool() const { return kind != STAGE_OK; }
 };
 
-struct Feed { uint64_t ticket; int row0, n_rows; };
+struct Feed { uint64_t ticket; int row0, n_rows; int64_t coff = 0, n_cand = 0; };   // (coff, n_cand: candidates mode -- the feed's ids in the launch)
 
 struct StageSlot {                // the host side of one launch from staging to its last polled feed; more slots than lanes, so that
     int64_t* h_pos = nullptr;     // the caller stages launch n + lanes while the lanes still score / hand out the ones before
@@ -28,6 +28,10 @@ struct StageSlot {                // the host side of one launch from staging to
     // evaluation mode: the launch's answers as a CSR over its rows, staged and uploaded with the feed
     int32_t *h_arp = nullptr, *h_acol = nullptr;
     int64_t n_ans = 0;
+    // candidates mode: the launch's candidate ids as a CSR over its rows, staged and uploaded with the feed; its longest row
+    int32_t *h_crp = nullptr, *h_ccol = nullptr;
+    int64_t n_cand = 0;
+    int cand_cap = 0;
     int titled = 0;               // this launch ranks the title-mixed score (its feeds came through dae_pipeline_submit_titled)
     int state = 0;                // 0 free, 1 staging (open launch), 2 queued for the worker, 3 issued
     int rows = 0; int64_t nnz = 0;
@@ -40,12 +44,16 @@ struct StageBlock {
     int refs = 0;                 // feeds handed out and not yet released (+1 while its launch is pending)
 };
 
-struct Staged { int slot; int row0; int64_t off, aoff; uint64_t ticket; };   // where begin() put a feed
+struct Staged {                   // where begin() put a feed (coff, cap_before: begin_candidates())
+    int slot; int row0; int64_t off, aoff; uint64_t ticket;
+    int64_t coff = 0; int cap_before = 0;
+};
 
 template <class SlotT, class BlockT>
 struct Stage {
     int group_rows = 0, title_len = 0;                      // the limits of one launch
     int64_t max_nnz = 0, max_answers = 0;
+    int64_t max_candidates = 0;                             // candidates mode: the ids one launch may hold
     std::vector<SlotT> slots;
     std::vector<BlockT> blocks;
     uint64_t next_ticket = 1;
@@ -124,7 +132,7 @@ struct Stage {
                                                   "yet (poll before submitting more)"};
             open_slot = next_slot;
             next_slot = (next_slot + 1) % (int)slots.size();
-            N.state = 1; N.rows = 0; N.nnz = 0; N.n_ans = 0; N.feeds.clear(); N.next_feed = 0; N.titled = titled;
+            N.state = 1; N.rows = 0; N.nnz = 0; N.n_ans = 0; N.n_cand = 0; N.cand_cap = 0; N.feeds.clear(); N.next_feed = 0; N.titled = titled;
         }
         SlotT& S = slots[open_slot];
         *at = Staged{open_slot, S.rows, S.nnz, S.n_ans, next_ticket++};
@@ -193,6 +201,55 @@ struct Stage {
         if (at.row0 == 0) S.h_arp[0] = 0;
         for (int r = 0; r < n_rows; ++r) S.h_arp[at.row0 + r + 1] = (int32_t)(at.aoff + (ans_rp[r + 1] - base));
         if (n_ans > 0) memcpy(S.h_acol + at.aoff, ans_col + base, (size_t)n_ans * sizeof(int32_t));
+    }
+
+    // ---- candidates mode (dae_pipeline_enable_candidates): every feed brings its candidate ids as a host CSR ------------------------
+    // what the feed's candidates must satisfy before anything is touched; *n_cand: its ids, *longest: its longest row
+    StageErr check_candidates(int n_rows, const int32_t* cand_rp, const int32_t* cand_col, int64_t* n_cand, int* longest) const
+    {
+        *n_cand = 0; *longest = 0;
+        if (!cand_rp) return {STAGE_ARG, "dae_pipeline_submit_candidates: cand_row_ptr is null"};
+        if (n_rows < 1 || n_rows > group_rows)
+            return {STAGE_ARG, "dae_pipeline_submit: a feed must fit one launch (rows <= group_rows, nnz <= max_nnz)"};
+        int64_t big = 0;
+        for (int r = 0; r < n_rows; ++r) {
+            const int64_t len = (int64_t)cand_rp[r + 1] - cand_rp[r];
+            if (len < 0) return {STAGE_ARG, "dae_pipeline_submit_candidates: cand_row_ptr decreases"};
+            if (len > big) big = len;
+        }
+        const int64_t n = (int64_t)cand_rp[n_rows] - cand_rp[0];
+        if (n > max_candidates)
+            return {STAGE_ARG, "dae_pipeline_submit_candidates: a feed's candidates must fit one launch (max_candidates); score "
+                               "this feed per batch"};
+        if (n > 0 && !cand_col) return {STAGE_ARG, "dae_pipeline_submit_candidates: cand_col is null"};
+        *n_cand = n; *longest = (int)big;
+        return {STAGE_OK, nullptr};
+    }
+    // would the feed's ids still fit the open launch?  (beside fits_open)
+    bool cand_fits_open(int64_t n_cand) const { return slots[open_slot].n_cand + n_cand <= max_candidates; }
+    // behind begin(): the feed's place in the launch's candidate CSR
+    void begin_candidates(Staged* at, int64_t n_cand, int longest)
+    {
+        SlotT& S = slots[at->slot];
+        at->coff = S.n_cand; at->cap_before = S.cand_cap;
+        S.feeds.back().coff = S.n_cand; S.feeds.back().n_cand = n_cand;
+        S.n_cand += n_cand;
+        if (longest > S.cand_cap) S.cand_cap = longest;
+    }
+    // before rollback(): the refused feed's ids leave the launch's counts
+    void rollback_candidates(const Staged& at, int64_t n_cand)
+    {
+        SlotT& S = slots[at.slot];
+        S.n_cand -= n_cand; S.cand_cap = at.cap_before;
+    }
+    // the feed's candidates behind the launch's, row pointers in the launch's CSR (any base in, 0 out)
+    void copy_candidates(const Staged& at, const int32_t* cand_rp, const int32_t* cand_col, int n_rows, int64_t n_cand)
+    {
+        SlotT& S = slots[at.slot];
+        const int32_t base = cand_rp[0];
+        if (at.row0 == 0) S.h_crp[0] = 0;
+        for (int r = 0; r < n_rows; ++r) S.h_crp[at.row0 + r + 1] = (int32_t)(at.coff + (cand_rp[r + 1] - base));
+        if (n_cand > 0) memcpy(S.h_ccol + at.coff, cand_col + base, (size_t)n_cand * sizeof(int32_t));
     }
 
     // the next feed of the launch at poll_slot goes out: the caller's reference to its block; behind the launch's last feed the

@@ -51,6 +51,7 @@ private:
 struct OutBlock : StageBlock {    // pinned result block of one launch: idx [rows][k] (+ score), handed out by pointer
     int32_t* idx = nullptr; float* score = nullptr;
     dae_metric_rec* rec = nullptr;                    // evaluation mode: the launch's [rows] records (idx is not kept then)
+    float* cand = nullptr;                            // candidates mode, scores: [max_candidates] values, then the launch's status word
 };
 
 struct Lane {                     // a context + stream + the device buffers its launches reuse in stream order
@@ -91,6 +92,10 @@ struct Slot : StageSlot {         // one launch: its staging (pipeline_stage.h) 
     // thread moves THEM, d_idx stays on the device)
     int32_t *d_arp = nullptr, *d_acol = nullptr;
     dae_metric_rec* d_rec = nullptr;
+    // candidates mode (dae_pipeline_enable_candidates): the launch's candidate CSR on the device, the value per listed id (the
+    // scores that go out, or the keys dae_rank_candidates ranks) and the candidate kernels' status word
+    int32_t *d_crp = nullptr, *d_ccol = nullptr, *d_cstatus = nullptr;
+    float* d_cout = nullptr;
     unsigned polls = 0;           // non-waiting polls of this issue that found its word missing (every 256th asks the runtime)
     int32_t seq = 0;              // the sequence word this launch's last kernel writes into h_flags[3] (the caller's wait watches it)
     int ran_dtype = 0;            // arithmetic the launch was issued with (a paused exact mode issues DAE_DTYPE_F32)
@@ -139,6 +144,8 @@ struct dae_pipeline : dae_pipe::Stage<dae_pipe::Slot, dae_pipe::OutBlock> {     
     dae_pipe::TitleW tw;
     int exact_pause = 0, overflow_streak = 0;      // titled + exact: launches left on the fp32 kernels / overflow events in a row
     bool eval = false;            // dae_pipeline_enable_eval: feeds carry answers, records go out instead of lists
+    bool cand = false;            // dae_pipeline_enable_candidates: feeds carry candidate ids; their scores, or the k best of them, go out
+    int cand_rank = 0, cand_out_kind = 0;
     const dae_catalogue* cat = nullptr;   // dae_pipeline_set_catalogue: every launch ranks ITS columns (the caller keeps it alive)
     double* d_disc = nullptr;     // the caller's discount table [k]
     uint64_t issue_ns = 0, idle_ns = 0, submit_ns = 0, wait_ns = 0;      // where the host side of the loop spends its time (dae_pipeline_times)

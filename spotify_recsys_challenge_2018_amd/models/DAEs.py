@@ -1007,6 +1007,63 @@ class DAE_tied:
         for f, answers in feeds:
             yield rank_records(self._recommend_feed(f, k, dtype, catalogue)[0], answers)
 
+    # -- the candidate calls over a stream of feeds (the pipeline's candidates mode: DESIGN.md 4b, 7) ---------------------------------
+    cand_launch_ids = 1 << 21         # candidate ids one launch of the streamed candidate loops holds (a feed with more: per batch)
+
+    def _cand_iter_begin(self, what, catalogue):
+        """What the streamed candidate calls refuse before a pipeline is created."""
+        if catalogue is not None:
+            raise ValueError("%s: candidates inside a catalogue are not streamed (call it without catalogue=; "
+                             "`rank_candidates(..., catalogue=)` takes one per batch)" % what)
+        if self._score_shard is not None:
+            raise _lib.DaeError("candidate scoring is not vocabulary-sharded: this model has a scoring shard (shard_scoring); "
+                                "score candidates on a model that holds the whole decoder")
+
+    def _title_kw(self, f):
+        return {"titles": f[4], "titles_use": f[5] if len(f) > 5 else None} if len(f) > 4 and isinstance(self, DAE_title) else {}
+
+    def score_candidates_iter(self, feeds, kind="sigmoid", catalogue=None):
+        """`score_candidates` over a stream: `feeds` yields (feed, candidates) -- `feed` what `recommend_iter` takes (its seeds are
+        not used), `candidates` what `score_candidates` takes -- and the generator yields, per feed and in order, what
+        `score_candidates` returns for that feed alone: same containers, same bits (tests/test_gpu_candidates_loop.py).  The loop
+        is the library's (the pipeline's candidates mode): the ids are staged and uploaded with the feed, consecutive
+        feeds share a launch, nothing is synchronised per feed; a 2-D candidate array reaches the staging copy without a pass over
+        its rows.  A feed the pipeline does not take (device_csr = False, more rows / entries / ids than a launch slot:
+        `cand_launch_ids`) goes through `score_candidates`, in order.  An id outside -1 / [0, n_input) raises ValueError at its
+        feed (those before it have been yielded).  catalogue= is refused: not built."""
+        if kind not in self._CAND_KINDS:
+            raise ValueError("kind %r: one of %s" % (kind, sorted(self._CAND_KINDS)))
+        self._cand_iter_begin("score_candidates_iter", catalogue)
+
+        def per_batch(f, cands):
+            return self.score_candidates(f[0], f[1], cands, n_rows=f[3], kind=kind, **self._title_kw(f))
+        return self._candidates_iter(feeds, False, self._CAND_KINDS[kind], 1, False, per_batch)
+
+    def rank_candidates_iter(self, feeds, k=500, want_scores=True, catalogue=None):
+        """`rank_candidates` over a stream (see `score_candidates_iter`): per feed, in order, (idx [n_rows, k], score [n_rows, k] or
+        None) as `rank_candidates` returns them for that feed alone.  The rows' repeated candidates are dropped on the device
+        (dae_candidates_unique), not by a pass over the lists here.  k <= 1024, the pipeline's limit: a larger k raises ValueError
+        before a pipeline is created.  Feeds with explicit seed lists go through `rank_candidates`, in order."""
+        if k > _lib.DAE_MAX_K:
+            raise ValueError("rank_candidates_iter takes k <= %d, the pipeline's limit (got %d): deeper lists come from "
+                             "`rank_candidates` per batch, k <= %d" % (_lib.DAE_MAX_K, k, _lib.DAE_MAX_K_DEEP))
+        self._cand_iter_begin("rank_candidates_iter", catalogue)
+
+        def per_batch(f, cands):
+            idx, score = self.rank_candidates(f[0], f[1], cands, f[2], k=k, n_rows=f[3], **self._title_kw(f))
+            return idx, (score if want_scores else None)
+        return self._candidates_iter(feeds, True, _lib.DAE_OUT_SCORE, k, want_scores, per_batch)
+
+    def _candidates_iter(self, feeds, rank, out_kind, k, want_scores, per_batch):
+        if not self.device_csr:          # (host-built CSRs: the per-batch call)
+            for f, cands in feeds:
+                yield per_batch(f, cands)
+            return
+        self.sync_params()               # (the pipeline reads the weights, a titled one copies the title variables: current ones)
+        cand = (bool(rank), int(out_kind), int(self.cand_launch_ids))
+        key, pipe = stream_loop.pipeline_for(self, self._title_scorer(), _lib.DAE_DTYPE_F32, k, want_scores, candidates=cand)
+        yield from stream_loop.stream_candidates(pipe, feeds, per_batch, self.n_batch, self.n_input, want_scores, self._pipes, key)
+
     def _recommend_feed(self, f, k, dtype, catalogue=None):
         """`recommend` of one feed of a loop.  Only a DAE_title takes the title items of a 5- or 6-item feed; a plain DAE scores
         the feed's first four items and ignores the rest."""
@@ -1583,6 +1640,14 @@ class DAE_title(DAE):
         finally:
             tm.ctx.set_score_mix()
         return score, idx
+
+    def score_candidates_iter(self, feeds, kind="sigmoid", catalogue=None):
+        """`DAE.score_candidates_iter` on a titled pipeline: feeds carry titles and titles_use, and every feed gets what this
+        class's `score_candidates` returns for it -- the mixed score where titles are in use, the plain DAE's otherwise.
+        kind "sigmoid" only: a stream may mix both kinds of feed, and the title mix has no logit."""
+        if kind != "sigmoid":
+            raise ValueError("kind %r: a titled stream scores kind = \"sigmoid\" only (the title-mixed score has no logit)" % (kind,))
+        return DAE.score_candidates_iter(self, feeds, kind=kind, catalogue=catalogue)
 
     def _cand_mixed(self, x_positions, x_ones, titles, titles_use, cand, n_cand, status):
         """Enqueue the titled score of the listed pairs: encode, mixing weights, title features, then both chains per pair and
