@@ -773,6 +773,40 @@ int dae_train_forward_backward(dae_ctx* ctx,
         float* gW_enc, float* gb_enc, float* gW_dec, float* gb_dec,
         float* cost_out);
 
+/* ---- the loss without a step: the cost of a batch and the loss of each of its rows ----------------------------------
+ * What sess.run(model.cost, feed) on a held-out batch is in the reference: the forward pass and the loss head of the step
+ * (DAEs.py:98-100), no gradient, no Adam.  Nothing per element is kept in memory (no dz^T, no logits): the decode GEMM sums
+ * every element's negative term per row, the rows' targets are redone from their own dot products as in the step.
+ *
+ * dae_decode_loss_rows: row_loss[r] (device, [B]) = sum over ALL V columns c of L(z[r][c], y[r][c]) for the hidden rows
+ * h [B][H] (row-major, 16-byte aligned), y = the target CSR (0 where it has no entry; one entry per (row, column): the CSR
+ * contract; a row may hold any number; a column outside [0, V) is the caller's error and is left out).  The GEMM runs over
+ * the context's prepacked image of `dtype` (DAE_DTYPE_F32 or DAE_DTYPE_BF16; dae_prepack_decoder over [0, V), as for
+ * dae_decode_dense), the targets' chains over the row-major W_dec [V][H] / b_dec [V] the image was packed from (as the
+ * candidate calls take them).  DAE_ERR_STATE when the context holds no image of that dtype over [0, V); DAE_ERR_ARG for
+ * B outside [1, 4096], H % 32 != 0, H > 1024.
+ *
+ * dae_score_loss: the step's encode (the same dropout masks as dae_train_forward_backward for the same seed and keep
+ * probabilities), then the call above in the arithmetic of dae_set_train_dtype, then
+ *   cost_out (device scalar, nullable) = (float)(sum_r (double)row_loss[r] / n_batch + reg_lambda * l2),
+ * l2 over the tensors the step counts (W_enc, b_dec, b_enc, and W_dec unless tied).  row_loss: device [B], nullable.
+ * tied != 0: W_dec is ignored (W_enc is the decoder, and the image must be of it).  DAE_ERR_ARG also when both outputs are
+ * null.  There are no 256-row panels: B up to 4096 is one GEMM launch.
+ *
+ * Both write only their outputs and context scratch (reserved for the call's own shape), and the packed hidden image as
+ * every decode call does: never the parameters, the Adam moments, the armed decoder Adam, dae_set_enc_grad_prezeroed or a
+ * prepacked image.  Every sum runs in an order fixed by indices (no float atomics): the same inputs give the same bits. */
+int dae_decode_loss_rows(dae_ctx* ctx, const float* h, int B, int H, int dtype,
+                         const int32_t* y_row_ptr, const int32_t* y_col, const float* y_val,
+                         const float* W_dec, const float* b_dec, int V, float* row_loss);
+int dae_score_loss(dae_ctx* ctx,
+        const int32_t* x_row_ptr, const int32_t* x_col, const float* x_val,
+        const int32_t* y_row_ptr, const int32_t* y_col, const float* y_val,
+        const float* W_enc, const float* b_enc, const float* W_dec, const float* b_dec,
+        int V, int H, int B, int n_batch, int tied,
+        float ikp, float kp, uint32_t seed, float reg_lambda,
+        float* row_loss, float* cost_out);
+
 /* ---- the same step with the vocabulary ROW-SHARDED over ranks (training) ------
  * Rank g owns rows [col_lo, col_hi) of W_enc, W_dec and b_dec (pointers *_loc address the shard's
  * own [col_hi-col_lo, H] / [col_hi-col_lo] arrays); b_enc is replicated.  Every rank receives the

@@ -23,6 +23,7 @@ EXPORTS = [
     "dae_exact_guard_read", "dae_exact_guard_words", "dae_exact_guard_snapshot", "dae_exact_stats_read", "dae_set_exact_margin", "dae_set_exact_margin_range", "dae_set_exact_audit", "dae_exact_audit_read",
     "dae_set_filter_skip", "dae_filter_skip_read", "dae_filter_skip_last", "dae_tile_bounds_read", "dae_sample_skip_read", "dae_live_proof_read", "dae_last_tau_read", "dae_decode_dense", "dae_decode_topk",
     "dae_score_topk", "dae_score_topk_begin", "dae_score_topk_finish", "dae_topk_dense", "dae_topk_merge", "dae_set_train_dtype", "dae_train_forward_backward",
+    "dae_decode_loss_rows", "dae_score_loss",
     "dae_train_shard_encode", "dae_train_shard_decode", "dae_train_shard_finish", "dae_title_features", "dae_title_prepack_features",
     "dae_mix_scores", "dae_decode_mix_term", "dae_set_score_mix", "dae_decode_mix_term_add", "dae_ensemble_topk", "dae_mix_topk_exact", "dae_mix_exact_shape_ok", "dae_title_score_exact", "dae_title_score", "dae_row_sums", "dae_mix_weights", "dae_title_loss_backward", "dae_title_loss_backward_cols", "dae_title_conv_backward", "dae_adam_step",
     "dae_adam_rows_begin", "dae_adam_rows_apply", "dae_adam_rows_flush", "dae_set_enc_grad_prezeroed",
@@ -117,6 +118,9 @@ def load():
     lib.dae_set_train_dtype.restype = c_int
     lib.dae_train_forward_backward.argtypes = (
         [vp] + [vp] * 6 + [vp] * 4 + [c_int] * 5 + [c_f, c_f, c_u32, c_f] + [vp] * 5)
+    lib.dae_decode_loss_rows.argtypes = [vp, vp, c_int, c_int, c_int, vp, vp, vp, vp, vp, c_int, vp]
+    lib.dae_score_loss.argtypes = (
+        [vp] + [vp] * 6 + [vp] * 4 + [c_int] * 5 + [c_f, c_f, c_u32, c_f] + [vp] * 2)
     lib.dae_train_shard_encode.argtypes = [vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_f, c_u32, vp]
     lib.dae_train_shard_decode.argtypes = (
         [vp, vp, vp] + [vp] * 3 + [vp] * 3 + [c_int] * 6 + [c_f, c_u32, c_f] + [vp] * 4)
@@ -539,6 +543,28 @@ class Context:
         self.check(self.lib.dae_decode_dense(self.h, _ptr(h), B, H, int(dtype),
                                              1 if apply_sigmoid else 0, _ptr(out),
                                              int(out.stride(0))))
+
+    def decode_loss_rows(self, h, y_csr, W_dec, b_dec, row_loss, dtype=DAE_DTYPE_F32):
+        """row_loss[r] = the loss of row r of the hidden rows h [B, H] over all V columns against the target CSR y_csr =
+        (row_ptr, col, val), over the context's prepacked image of `dtype` (dae_decode_loss_rows; nothing per element is
+        stored)."""
+        B, H = h.shape
+        V = W_dec.shape[0]
+        self.check(self.lib.dae_decode_loss_rows(self.h, _ptr(h), B, H, int(dtype), _ptr(y_csr[0]), _ptr(y_csr[1]), _ptr(y_csr[2]),
+                                                 _ptr(W_dec), _ptr(b_dec), int(V), _ptr(row_loss)))
+
+    def score_loss(self, x_csr, y_csr, W_enc, b_enc, W_dec, b_dec, n_batch, tied, ikp=1.0, kp=1.0, seed=0, reg_lambda=0.0,
+                   row_loss=None, cost_out=None):
+        """The cost of a batch without a step (dae_score_loss): the step's encode with its dropout masks, the loss of every
+        row into row_loss [B] and / or cost_out [1] = sum(row_loss) / n_batch + reg_lambda * l2 (CUDA tensors; either may be
+        None).  The image of the context's train dtype must be current (prepack_decoder)."""
+        V, H = W_enc.shape
+        B = x_csr[0].numel() - 1
+        self.check(self.lib.dae_score_loss(
+            self.h, _ptr(x_csr[0]), _ptr(x_csr[1]), _ptr(x_csr[2]), _ptr(y_csr[0]), _ptr(y_csr[1]), _ptr(y_csr[2]),
+            _ptr(W_enc), _ptr(b_enc), _ptr(W_dec) if W_dec is not None else None, _ptr(b_dec), int(V), int(H), int(B),
+            int(n_batch), 1 if tied else 0, float(ikp), float(kp), int(seed) & 0xFFFFFFFF, float(reg_lambda),
+            _ptr(row_loss) if row_loss is not None else None, _ptr(cost_out) if cost_out is not None else None))
 
     def decode_topk(self, h, n_tracks, seed_row_ptr, seed_col, k, out_score, out_idx,
                     out_kind=DAE_OUT_SCORE, dtype=DAE_DTYPE_F32):

@@ -163,6 +163,7 @@ struct dae_ctx {
     // launch that never completes (a device fault) leaves them standing for the life of the context, like the rest of its state
     dae_buf live_sync; void* live_sync_zeroed = nullptr; size_t live_sync_zeroed_bytes = 0;   // (which allocation was zeroed)
     dae_buf cand_list;         // dae_rank_candidates: [B][row_cap] (key, column) pairs | [B] counts (candidates.hip)
+    dae_buf loss_rows;         // the loss without a step: hidden rows [B][H] | partial table [grid][R_TILE] | row losses [B] | l2 partials (loss_rows.hip)
     dae_buf rank_of;           // dae_decode_rank_of: [n_ans] thresholds (u64) | logits | places | buckets, then [n_rg] longest rows (rank_of.hip)
     dae_buf cat_seeds;         // the catalogue calls: a slab's seed lists in the catalogue's columns, [4097] row pointers | [4096] counts | the columns (catalogue.hip)
     dae_buf skip_stat;         // 4 x uint64 {launches, planned tiles x row groups, live tiles} since the last dae_filter_skip_read |
@@ -401,6 +402,10 @@ int dae_launch_decode_loss_f32(dae_ctx* ctx, const dae_rowgeom& g, int B, float 
                                float* dzT, int64_t ldT, float* loss_part, int dtype = DAE_DTYPE_F32,
                                int dz16 = 0);
 
+// the loss without a step (loss_rows.hip): ALL tiles of the image of `dtype`, every element a negative, summed per row and
+// workgroup into the partial table row_part[g.n_rg][g.nb_rg][g.R_TILE] (decode_f32_kernel's EPI_ROWLOSS); stores nothing else
+int dae_launch_decode_rowloss(dae_ctx* ctx, const dae_rowgeom& g, int B, int dtype, float* row_part);
+
 int dae_launch_decode_loss_rowmajor(dae_ctx* ctx, const dae_rowgeom& g, int B, int V, int H, const float* W,
                                     const float* bias, const float* h, float inv_n_batch, float* dzT, int64_t ldT,
                                     float* loss_part);
@@ -437,6 +442,8 @@ int dae_train_shard_finish_f32(dae_ctx* ctx, const float* dh, const int32_t* x_r
                                float ikp, float kp, uint32_t seed, float reg_lambda,
                                float* gW_enc_loc, float* gb_enc, float* gW_dec_loc, float* gb_dec_loc);
 int dae_launch_grad_h(dae_ctx* ctx, const float* dzT, int64_t ldT, const float* W, int H, int V, int B, float* dh);
+// tf.nn.l2_loss partials of the listed tensors (null / empty entries left out), at most 1024 doubles per tensor, side by side
+int dae_launch_l2_partials(dae_ctx* ctx, const float* const* ts, const size_t* ns, int n_t, double* l2_part, int* n_l2);
 
 // grad_wdec.hip (K6).  dae_armed_adam: the dense TF1-Adam of the [V, H] tensor p that an armed K6 applies in its epilogue
 struct dae_armed_adam { float* p; float* m; float* v; float alpha, b1, b2, eps; };

@@ -40,6 +40,7 @@ constexpr int EPI_FILTER = 1;
 constexpr int EPI_LOSS = 2;        // training: logits -> loss + dL/dz (DAEs.py:98-100)
 constexpr int EPI_GMAX = 3;        // EPI_DENSE (raw logits) + cross-wave group maxima: the threshold sample (phase A)
 constexpr int EPI_TERM_ADD = 4;    // an ensemble member's term ADDED to the transposed buffer: outT[c][r] = outT[c][r] + sigmoid(z) * row_scale[r]
+constexpr int EPI_ROWLOSS = 5;     // the loss without a step: every element a negative, summed per ROW; nothing stored per element (loss_rows.hip)
 
 struct dae_decp {          // argument block of the decode kernels on the prepacked image (filled by decode_f32.hip fill_common)
     const float4* Wp;      // f32: [ntiles][G][64] float4   bf16: [ntiles][G][64] uint4 (8 bf16)
@@ -78,6 +79,8 @@ struct dae_decp {          // argument block of the decode kernels on the prepac
     // loss epilogue
     float inv_nb; float* dzT; int64_t ldT; float* loss_part;
     int dz16;                      // dzT holds bf16 (the bf16 backward GEMMs read it as such)
+    // EPI_ROWLOSS: loss_part is the partial table [n_rg][nb_rg][R_TILE] -- the negatives' sum of row (rg, i) over the tiles of
+    // workgroup `bir` of its row group, at ((rg * nb_rg + bir) * R_TILE + i); no mean folded in (inv_nb, dzT unused)
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -156,6 +159,14 @@ __device__ __forceinline__ float dae_loss_head(float pr, float y, float inv_nb, 
     const float l1 = __builtin_amdgcn_logf(a1), l0 = __builtin_amdgcn_logf(a0);
     corr -= 0.69314718f * y * (l1 - 0.55f * l0);
     return -(y * __builtin_amdgcn_rcpf(a1) - 0.55f * (1.0f - y) * __builtin_amdgcn_rcpf(a0)) * pr * (1.0f - pr) * inv_nb;
+}
+// the loss part of dae_loss_head alone (loss_rows.hip loss_rows_finish_kernel: the loss without a step has no dL/dz): adds
+// L(y) - L(0) of an element with target y to corr, in dae_loss_head's operations
+__device__ __forceinline__ void dae_loss_pos_corr(float pr, float y, float& corr)
+{
+    const float a1 = pr + 1e-10f, a0 = 1.0f - pr + 1e-10f;
+    const float l1 = __builtin_amdgcn_logf(a1), l0 = __builtin_amdgcn_logf(a0);
+    corr -= 0.69314718f * y * (l1 - 0.55f * l0);
 }
 // the same head on the MIXED score yp of the title scorer (title.hip title_loss_kernel), which is no sigmoid of one logit:
 // natural logarithms and IEEE quotients, the whole term L(y) subtracted from `loss`; returns dL/dyp / n_batch

@@ -1136,6 +1136,18 @@ int dae_launch_decode_loss_f32(dae_ctx* ctx, const dae_rowgeom& g, int B, float 
     return dae_launch_decode_generic(ctx, EPI_LOSS, dtype == DAE_DTYPE_BF16 ? DT_BF16 : DT_F32, g, p);
 }
 
+int dae_launch_decode_rowloss(dae_ctx* ctx, const dae_rowgeom& g, int B, int dtype, float* row_part)
+{
+    dae_decp p;
+    const dae_packed& pk = dtype == DAE_DTYPE_F32 ? ctx->pk_f32 : ctx->pk_bf16;
+    dae_tileset ts{pk.ntiles, 1, 0, static_cast<const int*>(pk.ident.p)};      // every tile, the artists' included
+    int rc = fill_common(ctx, g, B, ts, p, dtype);
+    if (rc) return rc;
+    p.mixT = nullptr;
+    p.loss_part = row_part;
+    return dae_launch_decode_generic(ctx, EPI_ROWLOSS, dtype == DAE_DTYPE_BF16 ? DT_BF16 : DT_F32, g, p);
+}
+
 int dae_launch_decode_filter_f32(dae_ctx* ctx, const dae_rowgeom& g, int B, const dae_tileset& ts,
                                  const float* tau, int n_valid_col, uint2* cand, int* cand_cnt,
                                  int cap, int dtype, int bias_sel, const int* live_cnt, const int* live_list)

@@ -1,5 +1,5 @@
 // decode_generic.hip -- K2 on the prepacked image for ANY hidden size and row-group height: the generic decode kernel
-// (decode_f32_kernel, fp32 and bf16 MFMA, four epilogues) and its instance table.  The hidden-256 shapes of the hot paths have
+// (decode_f32_kernel, fp32 and bf16 MFMA, its compile-time epilogues) and its instance table.  The hidden-256 shapes of the hot paths have
 // kernels of their own in decode_f32.hip, whose launchers fall through to dae_launch_decode_generic for every other shape;
 // the structure (hidden tile in LDS once per persistent workgroup, W streamed through a register ring, XCD-aware block
 // order) is described at the head of that file.
@@ -176,6 +176,9 @@ __global__ __launch_bounds__(NW * 64, HALF ? 2 : NW / 4) void decode_f32_kernel(
     }
 
     float loss_acc = 0.0f;
+    float row_acc[RB];            // EPI_ROWLOSS: the negatives' sum of row (rb, j) over this lane's column quads of all the wave's tiles
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb) row_acc[rb] = 0.0f;
     // W stream: the wave's tiles back to back; the register ring always holds the next 4 groups
     // of that stream, so the prefetch runs across tile boundaries (and under the epilogue).
     float4 wb0, wb1, wb2, wb3;
@@ -563,6 +566,26 @@ __global__ __launch_bounds__(NW * 64, HALF ? 2 : NW / 4) void decode_f32_kernel(
                     }
                 }
             }
+        } else if (EPI == EPI_ROWLOSS) {
+            // The loss without a step: what EPI_LOSS does for the loss (every element a negative, the head of decode_common.h)
+            // and nothing else -- no dL/dz, no logits; the sums stay per row.  The positives: loss_rows.hip.
+#pragma unroll
+            for (int rb = 0; rb < RB; ++rb) {
+                const int row = rg * R_TILE + rb * 32 + j;
+                if (row >= p.B) continue;
+#pragma unroll
+                for (int qd = 0; qd < 4; ++qd) {
+                    const int lc = tcol0 + 8 * qd;
+                    const float zb[4] = {bq[qd].x, bq[qd].y, bq[qd].z, bq[qd].w};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        if (lc + e < p.ncols) {
+                            const float pr = dae_train_sigmoid(acc[rb][4 * qd + e] + zb[e]);
+                            row_acc[rb] -= dae_loss_neg_term(pr);
+                        }
+                    }
+                }
+            }
         } else if ((t * 32 < p.ncols) && (p.col_lo + t * 32 < p.n_valid_col)) {
             // filter: tiles without a rankable column (the artist columns) need no epilogue at all; in
             // the others the common case -- this launch walks the LOW-bias tiles -- is "no value of
@@ -627,6 +650,25 @@ __global__ __launch_bounds__(NW * 64, HALF ? 2 : NW / 4) void decode_f32_kernel(
         __syncthreads();
         if (tid < R_TILE) p.cand_cnt[(size_t)bir * p.Bpad + rg * R_TILE + tid] = lcnt[tid];
     }
+    if (EPI == EPI_ROWLOSS) {
+        // Fixed order, no atomics: the two half-waves hold the same 32 rows and different column quads -> one shuffle; the
+        // waves meet in LDS ([NW][R_TILE] floats behind the hidden tile, which stays untouched) and are added in wave order;
+        // one float per row of the group goes to the workgroup's place in the partial table.  A wave without a tile adds +0.
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb) row_acc[rb] += __shfl_xor(row_acc[rb], 32);
+        float* wrow = reinterpret_cast<float*>(lcnt);
+        if (hi == 0) {
+#pragma unroll
+            for (int rb = 0; rb < RB; ++rb) wrow[wave * R_TILE + rb * 32 + j] = row_acc[rb];
+        }
+        __syncthreads();
+        for (int i = tid; i < R_TILE; i += NW * 64) {
+            float s = wrow[i];
+#pragma unroll
+            for (int w = 1; w < NW; ++w) s += wrow[w * R_TILE + i];
+            p.loss_part[((size_t)rg * p.nb_rg + bir) * R_TILE + i] = s;
+        }
+    }
     if (EPI == EPI_LOSS) {
         // deterministic: lanes -> wave (shuffle tree), waves -> block (fixed order), one slot/block
 #pragma unroll
@@ -648,7 +690,8 @@ int launch_decode(dae_ctx* ctx, const dae_rowgeom& g, const dae_decp& p)
 {
     const size_t lds = (size_t)RB * 64 * p.G * sizeof(float4) + (size_t)RB * 32 * sizeof(int) +
                        (EPI == EPI_GMAX ? (size_t)NW * 256 * sizeof(float4) : 0) +
-                       (EPI == EPI_FILTER ? (size_t)RB * 32 * sizeof(float) : 0);
+                       (EPI == EPI_FILTER ? (size_t)RB * 32 * sizeof(float) : 0) +
+                       (EPI == EPI_ROWLOSS ? (size_t)NW * RB * 32 * sizeof(float) : 0);
     DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &decode_f32_kernel<RB, EPI, GT, NW, DT>, 160 * 1024));
     if (ctx->prof_armed) {
         char name[96];
@@ -708,6 +751,7 @@ int dae_launch_decode_generic(dae_ctx* ctx, int epi, int dt, const dae_rowgeom& 
         case EPI_LOSS:   return dt == DT_F32 ? launch_decode_rb<EPI_LOSS>(ctx, g, p) : launch_decode_rb_bf16<EPI_LOSS>(ctx, g, p);
         case EPI_GMAX:   return dt == DT_F32 ? launch_decode_rb<EPI_GMAX>(ctx, g, p) : launch_decode_rb_bf16<EPI_GMAX>(ctx, g, p);
         case EPI_TERM_ADD: return dt == DT_F32 ? launch_decode_rb<EPI_TERM_ADD>(ctx, g, p) : launch_decode_rb_bf16<EPI_TERM_ADD>(ctx, g, p);
+        case EPI_ROWLOSS: return dt == DT_F32 ? launch_decode_rb<EPI_ROWLOSS>(ctx, g, p) : launch_decode_rb_bf16<EPI_ROWLOSS>(ctx, g, p);
     }
     return dae_fail(ctx, DAE_ERR_ARG, "bad epilogue %d", epi);
 }

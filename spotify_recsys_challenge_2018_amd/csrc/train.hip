@@ -88,39 +88,7 @@ __global__ __launch_bounds__(256) void loss_fixup_kernel(const int32_t* __restri
             const int lc = c - col_lo;
             const float y = val[i];
             const float4* w = reinterpret_cast<const float4*>(Wd + (size_t)lc * H);
-            float z = 0.0f;
-            int k = 0;
-            for (; k + 16 <= H4; k += 16) {                        // (16 loads in flight: the same chain, half the round trips)
-                float4 wv[16];
-#pragma unroll
-                for (int u = 0; u < 16; ++u) wv[u] = w[k + u];
-#pragma unroll
-                for (int u = 0; u < 16; ++u) {
-                    if (BF16) wv[u] = make_float4(dae_bf16_value(wv[u].x), dae_bf16_value(wv[u].y), dae_bf16_value(wv[u].z), dae_bf16_value(wv[u].w));
-                    const float4 hv = sh[k + u];
-                    z = fmaf(wv[u].x, hv.x, z); z = fmaf(wv[u].y, hv.y, z);
-                    z = fmaf(wv[u].z, hv.z, z); z = fmaf(wv[u].w, hv.w, z);
-                }
-            }
-            for (; k + 8 <= H4; k += 8) {
-                float4 wv[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) wv[u] = w[k + u];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    if (BF16) wv[u] = make_float4(dae_bf16_value(wv[u].x), dae_bf16_value(wv[u].y), dae_bf16_value(wv[u].z), dae_bf16_value(wv[u].w));
-                    const float4 hv = sh[k + u];
-                    z = fmaf(wv[u].x, hv.x, z); z = fmaf(wv[u].y, hv.y, z);
-                    z = fmaf(wv[u].z, hv.z, z); z = fmaf(wv[u].w, hv.w, z);
-                }
-            }
-            for (; k < H4; ++k) {
-                float4 wv = w[k];
-                const float4 hv = sh[k];
-                if (BF16) wv = make_float4(dae_bf16_value(wv.x), dae_bf16_value(wv.y), dae_bf16_value(wv.z), dae_bf16_value(wv.w));
-                z = fmaf(wv.x, hv.x, z); z = fmaf(wv.y, hv.y, z); z = fmaf(wv.z, hv.z, z); z = fmaf(wv.w, hv.w, z);
-            }
-            z += bias[lc];
+            const float z = dae_positive_logit<BF16>(w, sh, H4, bias + lc);          // train_common.h: THE positives' chain
             const float dzv = dae_loss_head(dae_train_sigmoid(z), y, inv_nb, corr);
             if (DZ16) {
                 unsigned short* dst = reinterpret_cast<unsigned short*>(dzT) + (size_t)lc * ldT + row;
@@ -554,6 +522,26 @@ __global__ __launch_bounds__(256) void l2_partial_kernel(const float* __restrict
     if (threadIdx.x == 0) part[blockIdx.x] = 0.5 * (ws[0] + ws[1] + ws[2] + ws[3]);
 }
 
+}  // namespace
+
+// the l2 partials of the listed tensors (null / empty ones left out), side by side at l2_part: at most 1024 per tensor; *n_l2 of
+// them.  What the step's cost and the loss without a step (loss_rows.hip) both add up
+int dae_launch_l2_partials(dae_ctx* ctx, const float* const* ts, const size_t* ns, int n_t, double* l2_part, int* n_l2)
+{
+    int n = 0;
+    for (int i = 0; i < n_t; ++i) {
+        if (!ts[i] || ns[i] == 0) continue;
+        const int nb = grid_for(ns[i]) > 1024 ? 1024 : grid_for(ns[i]);
+        hipLaunchKernelGGL(l2_partial_kernel, dim3(nb), dim3(256), 0, ctx->stream, ts[i], ns[i], l2_part + n);
+        DAE_CHECK_LAUNCH(ctx, "l2_partial_kernel");
+        n += nb;
+    }
+    *n_l2 = n;
+    return DAE_OK;
+}
+
+namespace {
+
 // cost = sum(loss partials) + lambda * sum(l2 partials), in double, fixed order (lane-strided sums, then
 // a shuffle tree): one wave
 __global__ __launch_bounds__(64) void finish_cost_kernel(const float* __restrict__ loss_part, int n_loss,
@@ -803,13 +791,8 @@ int train_cost(dae_ctx* ctx, const TrainPlan& t, float reg_lambda, const float* 
     hipStream_t st = ctx->stream;
     int n_l2 = 0;
     if (reg_lambda != 0.0f) {
-        for (int i = 0; i < n_t; ++i) {
-            if (!ts[i] || ns[i] == 0) continue;
-            const int nb = grid_for(ns[i]) > 1024 ? 1024 : grid_for(ns[i]);
-            hipLaunchKernelGGL(l2_partial_kernel, dim3(nb), dim3(256), 0, st, ts[i], ns[i], t.l2_part + n_l2);
-            DAE_CHECK_LAUNCH(ctx, "l2_partial_kernel");
-            n_l2 += nb;
-        }
+        const int rc = dae_launch_l2_partials(ctx, ts, ns, n_t, t.l2_part, &n_l2);
+        if (rc) return rc;
     }
     hipLaunchKernelGGL(finish_cost_kernel, dim3(1), dim3(64), 0, st, t.loss_part, t.n_loss, t.l2_part, n_l2,
                        reg_lambda, cost_out);

@@ -45,5 +45,48 @@ __device__ __forceinline__ void dae_adam_el4(float4& p, float4& m, float4& v, co
     dae_adam_el(p.w, m.w, v.w, g.w, alpha, b1, b2, eps);
 }
 
+// THE positives' chain: the logit of one (row, column) as the fp32 MFMA of the forward GEMM computes it -- fmaf over
+// k = 0..H-1 from +0, then + bias -- from the decoder row w ([H4] float4, row-major) and the hidden row sh ([H4] float4 in LDS,
+// already rounded under BF16); BF16 rounds W the same way (dae_bf16_value).  loss_fixup_kernel (train.hip, the step) and
+// loss_rows_finish_kernel (loss_rows.hip, the loss without a step) both call this, so a positive's logit is the same in both.
+template <bool BF16>
+__device__ __forceinline__ float dae_positive_logit(const float4* __restrict__ w, const float4* sh, int H4, const float* __restrict__ bias_c)
+{
+    float z = 0.0f;
+    int k = 0;
+    for (; k + 16 <= H4; k += 16) {                        // (16 loads in flight: the same chain, half the round trips)
+        float4 wv[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) wv[u] = w[k + u];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+            if (BF16) wv[u] = make_float4(dae_bf16_value(wv[u].x), dae_bf16_value(wv[u].y), dae_bf16_value(wv[u].z), dae_bf16_value(wv[u].w));
+            const float4 hv = sh[k + u];
+            z = fmaf(wv[u].x, hv.x, z); z = fmaf(wv[u].y, hv.y, z);
+            z = fmaf(wv[u].z, hv.z, z); z = fmaf(wv[u].w, hv.w, z);
+        }
+    }
+    for (; k + 8 <= H4; k += 8) {
+        float4 wv[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) wv[u] = w[k + u];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            if (BF16) wv[u] = make_float4(dae_bf16_value(wv[u].x), dae_bf16_value(wv[u].y), dae_bf16_value(wv[u].z), dae_bf16_value(wv[u].w));
+            const float4 hv = sh[k + u];
+            z = fmaf(wv[u].x, hv.x, z); z = fmaf(wv[u].y, hv.y, z);
+            z = fmaf(wv[u].z, hv.z, z); z = fmaf(wv[u].w, hv.w, z);
+        }
+    }
+    for (; k < H4; ++k) {
+        float4 wv = w[k];
+        const float4 hv = sh[k];
+        if (BF16) wv = make_float4(dae_bf16_value(wv.x), dae_bf16_value(wv.y), dae_bf16_value(wv.z), dae_bf16_value(wv.w));
+        z = fmaf(wv.x, hv.x, z); z = fmaf(wv.y, hv.y, z); z = fmaf(wv.z, hv.z, z); z = fmaf(wv.w, hv.w, z);
+    }
+    z += *bias_c;
+    return z;
+}
+
 // blocks of 256 threads for a grid-stride loop over n elements
 inline int grid_for(size_t n) { size_t b = (n + 255) / 256; return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b)); }

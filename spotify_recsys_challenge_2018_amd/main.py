@@ -5,7 +5,7 @@ the same config.ini schema:
 
     [BASE] verbose data_dir result_dir testsize   (+ optional, this build only: train_dtype = f32 | bf16, decode_dtype = f32 | bf16 | exact_bf16,
                                                   eval_metrics = rprecision | all, train_feed = host | device,
-                                                  eval_ranks = off | on, eval_mixed_ranks = off | on,
+                                                  eval_ranks = off | on, eval_mixed_ranks = off | on, eval_loss = off | on,
                                                   ensemble = <pickle>[, <pickle> ...], ensemble_alpha = a0, a1, ...,
                                                   eval_ensemble_ranks = off | on, ensemble_fit = <seed>[, mrr | recall@N])
     [DAE] epochs batch lr reg_lambda hidden test_seed update_seed keep_prob input_kp firstN_range initval save
@@ -91,15 +91,21 @@ class Conf:
         #   eval_mixed_ranks = off | on       --title only: with `on` one more line per test split behind the others, "mixed ranks: ...",
         #                  the same figures from the EXACT ranks under the title mix (models/DAEs.py DAE_title.mixed_rank_of, with the
         #                  split's titles and titles_use as the title evaluation feeds them).  Refused outside --title (main_train.run)
+        #   eval_loss    = off | on           with `on` one more line per test split behind the others, "heldout loss: ...": the mean
+        #                  over the split's playlists of the loss the optimiser minimises (models/DAEs.py loss, per row, feed by
+        #                  feed; input = the test feed, targets = its entries and the held-out answers in the vocabulary, keep
+        #                  probabilities 1, no lambda term).  Refused under --title, beside [BASE] ensemble and for a
+        #                  vocabulary-sharded training run (main_train.run)
         self.eval_metrics = 'rprecision'
         self.train_feed = 'host'
+        self.eval_loss = 'off'
         self.eval_ranks = 'off'
         self.eval_mixed_ranks = 'off'
         self.eval_ensemble_ranks = 'off'
         for key, allowed in (('train_dtype', ('f32', 'bf16')), ('decode_dtype', ('f32', 'bf16', 'exact_bf16')),
                              ('eval_metrics', ('rprecision', 'all')), ('train_feed', ('host', 'device')),
                              ('eval_ranks', ('off', 'on')), ('eval_mixed_ranks', ('off', 'on')),
-                             ('eval_ensemble_ranks', ('off', 'on'))):
+                             ('eval_ensemble_ranks', ('off', 'on')), ('eval_loss', ('off', 'on'))):
             if key in self.ini['BASE']:
                 val = self.ini['BASE'][key].strip().lower()
                 if val not in allowed:

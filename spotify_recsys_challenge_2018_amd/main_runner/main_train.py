@@ -228,7 +228,51 @@ def _log_ensemble_ranks(conf, readers_test, model):
                   % (seed_num, mrr, med, ' '.join("recall@%d %f" % (k, v) for k, v in zip(RANK_CUTS, rec))))
 
 
-def _refuse_ranks_under_title(conf):
+def heldout_targets(x_positions, test_answer, n_input):
+    """The targets of a test feed's held-out loss as COO positions: the input's entries plus the held-out answers that lie in the
+    vocabulary, one entry per (row, column)."""
+    pos = [np.asarray(x_positions, np.int64).reshape(-1, 2)]
+    for r, ans in enumerate(test_answer):
+        a = np.asarray([c for c in ans if 0 <= c < n_input], np.int64)
+        pos.append(np.stack([np.full(a.size, r, np.int64), a], axis=1))
+    return np.unique(np.concatenate(pos), axis=0)
+
+
+def eval_loss(reader_test, conf, model):
+    """[BASE] eval_loss = on: the mean over one test split's playlists of the row loss (model.loss per row, feed by feed, so a
+    short last feed is averaged correctly): input = the reader's test feed, targets = `heldout_targets`, all with weight 1;
+    keep probabilities 1, no lambda term."""
+    total, count = 0.0, 0
+    while True:
+        x_positions, test_seed, test_answer, _titles, x_ones = reader_test.next_batch_test()
+        y_positions = heldout_targets(x_positions, test_answer, model.n_input)
+        _cost, rows = model.loss(x_positions, x_ones, y_positions, np.ones(len(y_positions), np.float32), n_rows=len(test_seed),
+                                 per_row=True)
+        total += float(np.sum(rows, dtype=np.float64))
+        count += len(test_seed)
+        if reader_test.test_idx == 0:
+            break
+    return total / max(count, 1)
+
+
+def _log_loss(conf, readers_test, model):
+    """As `_log_ranks`, for [BASE] eval_loss: one more line per split, behind the existing ones; every rank computes, rank 0 logs."""
+    if getattr(conf, 'eval_loss', 'off') != 'on':
+        return
+    for seed_num in readers_test:
+        log_write(conf, "seed num: %s heldout loss: %f" % (seed_num, eval_loss(readers_test[seed_num], conf, model)))
+
+
+def _refuse_ranks_under_title(conf, only_testmode=True):
+    if getattr(conf, 'eval_loss', 'off') == 'on':
+        if getattr(conf, 'mode', None) == 'title':
+            raise ValueError("[BASE] eval_loss = on is not available under --title: the loss of the mixed score is another kernel "
+                             "(remove the key or set eval_loss = off)")
+        if getattr(conf, 'ensemble', None):
+            raise ValueError("[BASE] eval_loss = on is set beside [BASE] ensemble: an ensemble has no loss (set eval_loss = off)")
+        if not only_testmode and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise ValueError("[BASE] eval_loss = on is not available for a vocabulary-sharded model (a training run under "
+                             "torch.distributed.run): partial costs across ranks are not built (set eval_loss = off)")
     if getattr(conf, 'eval_ranks', 'off') == 'on' and getattr(conf, 'mode', None) == 'title':
         raise ValueError("[BASE] eval_ranks = on is not available under --title: it ranks by the DAE's own logits; the ranks "
                          "under the title mix are [BASE] eval_mixed_ranks = on (remove the key or set eval_ranks = off)")
@@ -281,7 +325,7 @@ def _refuse_ensemble(conf, only_testmode):
 
 
 def run(conf, only_testmode):
-    _refuse_ranks_under_title(conf)
+    _refuse_ranks_under_title(conf, only_testmode)
     _refuse_ensemble(conf, only_testmode)
     rank, world = _init_distributed(conf)
     # the training reader (main_train.py:129-133): whole playlists, or -- with a [DAE] firstN_range -- their first-N prefixes
@@ -343,6 +387,7 @@ def run(conf, only_testmode):
         _log_ranks(conf, readers_test, model)
         _log_mixed_ranks(conf, readers_test, model)
         _log_ensemble_ranks(conf, readers_test, model)
+        _log_loss(conf, readers_test, model)
         return out
 
     # [BASE] train_feed = device: the training set lives on the device and a batch goes up as the reader's draws alone
@@ -399,6 +444,7 @@ def run(conf, only_testmode):
             _log_splits(conf, readers_test, rprecs, extras)
             _log_ranks(conf, readers_test, model)
             _log_mixed_ranks(conf, readers_test, model)
+            _log_loss(conf, readers_test, model)
             for seed_num in readers_test:
                 if seed_num in conf.update_seed:
                     cur_eval += rprecs[seed_num]

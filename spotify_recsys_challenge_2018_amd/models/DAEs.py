@@ -638,6 +638,40 @@ class DAE_tied:
         self._check_feed()
         return res
 
+    def loss(self, x_positions, x_ones, y_positions, y_ones, keep_prob=1.0, input_keep_prob=1.0, seed=None, n_rows=None,
+             per_row=False):
+        """sess.run(model.cost, ...): the cost of a batch WITHOUT a step (dae_score_loss) -> float, or (cost, rows) with
+        `per_row`: rows float32 [n_rows], the loss of each row over all columns; cost = sum(rows) / n_batch + reg_lambda * l2,
+        in the arithmetic of the training step (`train_dtype`).  The same dropout masks as a step with the same `seed`; a
+        keep probability below 1 needs an explicit seed (the model's own dropout stream is never drawn from, so a training
+        run with calls of this in between trains the same model).  Nothing of the model changes."""
+        import torch
+        self._refuse_loss()
+        if (float(keep_prob) < 1.0 or float(input_keep_prob) < 1.0) and seed is None:
+            raise ValueError("loss: a keep probability below 1 needs an explicit seed")
+        n = self.n_batch if n_rows is None else int(n_rows)
+        self._ensure_packed(self.train_dtype)                 # (and the encoder's lazily updated rows: sync_params)
+        self.ctx.bind_stream()
+        x = self._upload_csr(x_positions, x_ones, n_rows=n)
+        y = self._upload_csr(y_positions, y_ones, n_rows=n)
+        dev = self.weights["encoder_h"].device
+        cost = torch.empty(1, dtype=torch.float32, device=dev)
+        rows = torch.empty(n, dtype=torch.float32, device=dev) if per_row else None
+        self.ctx.score_loss(x, y, self.weights["encoder_h"], self.biases["encoder_b"],
+                            None if self.tied else self.weights["decoder_h"], self.biases["decoder_b"], self.n_batch, self.tied,
+                            ikp=input_keep_prob, kp=keep_prob, seed=0 if seed is None else seed, reg_lambda=self.reg_lambda,
+                            row_loss=rows, cost_out=cost)
+        c = float(cost.item())
+        res = (c, rows.cpu().numpy()) if per_row else c
+        self._check_feed()
+        return res
+
+    def _refuse_loss(self):
+        """`loss` is refused by name, before any launch, where its kernels do not apply."""
+        if self._sharded is not None or self._score_shard is not None:
+            raise _lib.DaeError("loss: not available on a vocabulary-sharded model (shard_training / shard_scoring): partial "
+                                "costs across ranks are not built")
+
     def _dtype_of(self, dtype):
         if dtype is None:
             return self.decode_dtype
@@ -1317,11 +1351,12 @@ class DAE(DAE_tied):
 
 class Session:
     """Minimal stand-in for tf.Session so that reference-style driver code runs unchanged:
-    `sess.run(model.y_pred, feed_dict=...)`, `sess.run([model.optimizer, model.cost], ...)`,
+    `sess.run(model.y_pred, feed_dict=...)`, `sess.run([model.optimizer, model.cost], ...)`, `sess.run(model.cost, ...)`,
     `sess.run(model.init_op)`, `sess.run(model.d_params)`."""
 
     def __init__(self, model=None):
         self.model = model
+        self._loss_rng = np.random.RandomState(4321)      # seeds of `run(model.cost)`: not the model's dropout stream
 
     def run(self, fetches, feed_dict=None):
         m = self.model
@@ -1339,6 +1374,12 @@ class Session:
         if fetches is m.y_pred:
             return m.predict(g(m.x_positions), g(m.x_ones), g(m.keep_prob, 1.0),
                              g(m.input_keep_prob, 1.0))
+        if fetches is m.cost or (isinstance(fetches, (list, tuple)) and len(fetches) == 1 and fetches[0] is m.cost):
+            # the cost without a step (model.loss), dropout seeded from this session's own generator: fetching it never
+            # changes a training run
+            cost = m.loss(g(m.x_positions), g(m.x_ones), g(m.y_positions), g(m.y_ones), g(m.keep_prob, 1.0),
+                          g(m.input_keep_prob, 1.0), seed=int(self._loss_rng.randint(0, 2 ** 31 - 1)))
+            return cost if fetches is m.cost else [cost]
         if isinstance(fetches, (list, tuple)) and len(fetches) == 2 and fetches[0] is m.optimizer \
                 and fetches[1] is m.cost:
             cost = m.train_step(g(m.x_positions), g(m.x_ones), g(m.y_positions), g(m.y_ones),
@@ -1377,6 +1418,17 @@ class DAE_title(DAE):
     def _title_scorer(self):
         tm = self.title_model
         return tm if tm is not None and tm.ctx is not None else None
+
+    def loss(self, x_positions, x_ones, y_positions, y_ones, keep_prob=1.0, input_keep_prob=1.0, seed=None, n_rows=None,
+             per_row=False, titles=None, titles_use=None):
+        """`DAE.loss` of the frozen DAE alone.  With titles in use it is refused by name: the loss head of the mixed score is
+        another kernel (csrc/title.hip title_loss_kernel, inside the title training step only)."""
+        if titles_use is not None and np.any(np.asarray(titles_use) != 0):
+            raise _lib.DaeError("DAE_title.loss: not available with titles in use (titles_use != 0): the mixed-score loss head "
+                                "is another kernel; without titles it is the DAE's own loss")
+        if self._title_sharded is not None:
+            raise _lib.DaeError("DAE_title.loss: not available on a vocabulary-sharded model (shard_title_training)")
+        return DAE.loss(self, x_positions, x_ones, y_positions, y_ones, keep_prob, input_keep_prob, seed, n_rows, per_row)
 
     # -- multi-GPU title training: the output layer's columns sharded over the ranks (DESIGN.md section 6) ----
     def shard_title_training(self, rank, world, group=None):
