@@ -807,6 +807,36 @@ int dae_score_loss(dae_ctx* ctx,
         float ikp, float kp, uint32_t seed, float reg_lambda,
         float* row_loss, float* cost_out);
 
+/* ---- the loss of the title scorer's MIXED score without a step --------------------------------------------------------
+ * What the title step (main_train.py:214-221, DAEs.py:176-196) reports as its cost, with no gradient and no Adam: per row r and
+ * column c of ALL V columns, in the title step's fp32 operations and order (no contraction),
+ *   st = 1.0f / (1.0f + __expf(-z_title[r][c]));  pd = sigmoid(z_dae[r][c]) * w_playlist[r]  (the canonical sigmoid: the element
+ *   dae_decode_mix_term writes);  yp = st * w_title[r] + pd;
+ *   L(r, c) = -[y ln(yp + 1e-10f) + 0.55f (1 - y) ln(1 - yp + 1e-10f)],  y = the target CSR (0 where it has no entry; one entry
+ *   per (row, column); a row may hold any number; a column outside [0, V) is the caller's error and is left out, never read),
+ *   row_loss[r] (device [B], nullable) = sum_c L(r, c),
+ *   cost_out (device scalar, nullable) = (float)(sum_r (double)row_loss[r] / n_batch)   (the title cost has no lambda term).
+ * Nothing per element is kept: the title GEMM over the prepacked image sums every element's y = 0 term per row, the targets are
+ * redone from their own two fmaf chains (over Output_W^T [V][ld_feat] / Out_b and W_dec [V][H] / b_dec, the tensors the images
+ * were packed from), which in fp32 give the bits the GEMMs saw, and add L(y) - L(0).
+ *
+ * Called on the TITLE scorer's context with `dae` the DAE's, both bound to one stream (as dae_mix_candidates); h [B][H]
+ * (ld_h == H), feat [B][ld_feat], w_title / w_playlist [B] (dae_mix_weights).  Both contexts need their plain fp32 image over
+ * [0, V) (dae_prepack_decoder): DAE_ERR_STATE otherwise.  DAE_ERR_ARG: both outputs null, B outside [1, 4096], H % 32 != 0,
+ * H > 1024, ld_feat % 4 != 0, ld_feat > 1024, ld_h != H, n_batch <= 0, h / W_dec / feat / Output_W^T not 16-byte aligned.
+ *
+ * The call walks panels of at most 256 rows: dae_decode_mix_term (n_cols = V) on the DAE's context, the title GEMM, the
+ * finishing launch per panel; one cost launch over all rows at the end.  The transposed term buffer is one panel's
+ * (4 * V32 * 256 bytes at most, V32 = V rounded up to 32), in the title context's scratch, which grows only
+ * (csrc/mix_loss_plan.h).  It writes only its outputs, that scratch and the two packed hidden images: never a parameter, an Adam
+ * moment, the title trainer's state or a prepacked image, and what dae_set_score_mix left in either context is neither read
+ * nor changed.  Every sum runs in an order fixed by indices (no float atomics): the same inputs give the same bits. */
+int dae_mix_loss_rows(dae_ctx* title_ctx, dae_ctx* dae, const float* h, int64_t ld_h, int H, const float* W_dec,
+                      const float* b_dec, const float* feat, int64_t ld_feat, const float* OutW_T, const float* Out_b,
+                      const float* w_title, const float* w_playlist, int B, int V, int n_batch,
+                      const int32_t* y_row_ptr, const int32_t* y_col, const float* y_val,
+                      float* row_loss, float* cost_out);
+
 /* ---- the same step with the vocabulary ROW-SHARDED over ranks (training) ------
  * Rank g owns rows [col_lo, col_hi) of W_enc, W_dec and b_dec (pointers *_loc address the shard's
  * own [col_hi-col_lo, H] / [col_hi-col_lo] arrays); b_enc is replicated.  Every rank receives the

@@ -23,7 +23,7 @@ EXPORTS = [
     "dae_exact_guard_read", "dae_exact_guard_words", "dae_exact_guard_snapshot", "dae_exact_stats_read", "dae_set_exact_margin", "dae_set_exact_margin_range", "dae_set_exact_audit", "dae_exact_audit_read",
     "dae_set_filter_skip", "dae_filter_skip_read", "dae_filter_skip_last", "dae_tile_bounds_read", "dae_sample_skip_read", "dae_live_proof_read", "dae_last_tau_read", "dae_decode_dense", "dae_decode_topk",
     "dae_score_topk", "dae_score_topk_begin", "dae_score_topk_finish", "dae_topk_dense", "dae_topk_merge", "dae_set_train_dtype", "dae_train_forward_backward",
-    "dae_decode_loss_rows", "dae_score_loss",
+    "dae_decode_loss_rows", "dae_score_loss", "dae_mix_loss_rows",
     "dae_train_shard_encode", "dae_train_shard_decode", "dae_train_shard_finish", "dae_title_features", "dae_title_prepack_features",
     "dae_mix_scores", "dae_decode_mix_term", "dae_set_score_mix", "dae_decode_mix_term_add", "dae_ensemble_topk", "dae_mix_topk_exact", "dae_mix_exact_shape_ok", "dae_title_score_exact", "dae_title_score", "dae_row_sums", "dae_mix_weights", "dae_title_loss_backward", "dae_title_loss_backward_cols", "dae_title_conv_backward", "dae_adam_step",
     "dae_adam_rows_begin", "dae_adam_rows_apply", "dae_adam_rows_flush", "dae_set_enc_grad_prezeroed",
@@ -121,6 +121,7 @@ def load():
     lib.dae_decode_loss_rows.argtypes = [vp, vp, c_int, c_int, c_int, vp, vp, vp, vp, vp, c_int, vp]
     lib.dae_score_loss.argtypes = (
         [vp] + [vp] * 6 + [vp] * 4 + [c_int] * 5 + [c_f, c_f, c_u32, c_f] + [vp] * 2)
+    lib.dae_mix_loss_rows.argtypes = [vp, vp, vp, c_i64, c_int, vp, vp, vp, c_i64, vp, vp, vp, vp, c_int, c_int, c_int, vp, vp, vp, vp, vp]
     lib.dae_train_shard_encode.argtypes = [vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_f, c_u32, vp]
     lib.dae_train_shard_decode.argtypes = (
         [vp, vp, vp] + [vp] * 3 + [vp] * 3 + [c_int] * 6 + [c_f, c_u32, c_f] + [vp] * 4)
@@ -782,6 +783,20 @@ class Context:
                                             _ptr(w_playlist), B, int(W_dec.shape[0]), int(n_tracks), _ptr(seed_row_ptr),
                                             _ptr(seed_col), _ptr(ans[0]), _ptr(ans[1]), int(n_ans), _ptr(out_rank),
                                             _ptr(out_score), _ptr(status)))
+
+    def mix_loss_rows(self, dae_ctx, h, W_dec, b_dec, feat, OutW_T, Out_b, w_title, w_playlist, n_batch, y_csr, row_loss=None,
+                      cost_out=None):
+        """On the title scorer's context: the loss of the MIXED score without a step (dae_mix_loss_rows) -- the loss of every
+        row of h [B, H] / feat [B, ld_feat] over all V columns against the target CSR y_csr = (row_ptr, col, val) into row_loss
+        [B] and / or cost_out [1] = sum(row_loss) / n_batch (CUDA tensors; either may be None).  Both contexts hold their plain
+        fp32 image over all columns and are bound to one stream."""
+        B, H = h.shape
+        if not (h.is_contiguous() and feat.is_contiguous()):
+            raise ValueError("mix_loss_rows: contiguous hidden and feature rows are required")
+        self.check(self.lib.dae_mix_loss_rows(
+            self.h, dae_ctx.h, _ptr(h), H, H, _ptr(W_dec), _ptr(b_dec), _ptr(feat), int(feat.shape[1]), _ptr(OutW_T), _ptr(Out_b),
+            _ptr(w_title), _ptr(w_playlist), B, int(W_dec.shape[0]), int(n_batch), _ptr(y_csr[0]), _ptr(y_csr[1]), _ptr(y_csr[2]),
+            _ptr(row_loss) if row_loss is not None else None, _ptr(cost_out) if cost_out is not None else None))
 
     # ---- a catalogue: a shared, ascending subset of the track columns (csrc/catalogue.hip; `Catalogue` below) ------------------
     def prepack_decoder_catalogue(self, cat, W_dec, b_dec, dtype=DAE_DTYPE_F32):

@@ -7,7 +7,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdae_hip.so")
-SOURCES = ["api.hip", "score.hip", "encode.hip", "decode_f32.hip", "decode_generic.hip", "prepack.hip", "topk.hip", "tau_select.hip", "refine.hip", "candidates.hip", "rank_of.hip", "ensemble.hip", "catalogue.hip", "audit.hip", "mixexact.hip", "mix_prep.hip", "mix_filter.hip", "mix_refine.hip", "train.hip", "loss_rows.hip", "grad_wdec.hip", "adam.hip", "csr.hip", "train_feed.hip", "title.hip", "pipeline.hip", "pipeline_issue.hip", "metrics.hip"]
+SOURCES = ["api.hip", "score.hip", "encode.hip", "decode_f32.hip", "decode_generic.hip", "prepack.hip", "topk.hip", "tau_select.hip", "refine.hip", "candidates.hip", "rank_of.hip", "ensemble.hip", "catalogue.hip", "audit.hip", "mixexact.hip", "mix_prep.hip", "mix_filter.hip", "mix_refine.hip", "train.hip", "loss_rows.hip", "mix_loss.hip", "grad_wdec.hip", "adam.hip", "csr.hip", "train_feed.hip", "title.hip", "pipeline.hip", "pipeline_issue.hip", "metrics.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -fno-vectorize: hipcc's LOOP vectorizer miscompiles per-lane strided loops of these kernels (a loop `for (i = lane; i < n;
 # i += 64) { kl[b + i] = f(x[i]); ku[b + i] = g(x[i]); min / max of f }` leaves the key of entry i + 64 m in slot i of the

@@ -94,7 +94,7 @@ int dae_destroy(dae_ctx* ctx)
                        &ctx->feed_tmp, &ctx->row_bad, &ctx->guard, &ctx->refined, &ctx->refstat, &ctx->mix_fhat, &ctx->title_scratch,
                        &ctx->tile_band, &ctx->title_tab, &ctx->audit, &ctx->audit_stat, &ctx->title_y1, &ctx->live, &ctx->skip_stat, &ctx->live_sync,
                        &ctx->row_d, &ctx->samp_tab, &ctx->sskip_stat,
-                       &ctx->cand_list, &ctx->cat_seeds, &ctx->rank_of, &ctx->loss_rows})
+                       &ctx->cand_list, &ctx->cat_seeds, &ctx->rank_of, &ctx->loss_rows, &ctx->mix_loss})
         release(*b);
     for (hipEvent_t ev : ctx->prof_ev) (void)hipEventDestroy(ev);
     delete ctx;

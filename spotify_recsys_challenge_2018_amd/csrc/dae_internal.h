@@ -163,6 +163,7 @@ struct dae_ctx {
     // launch that never completes (a device fault) leaves them standing for the life of the context, like the rest of its state
     dae_buf live_sync; void* live_sync_zeroed = nullptr; size_t live_sync_zeroed_bytes = 0;   // (which allocation was zeroed)
     dae_buf cand_list;         // dae_rank_candidates: [B][row_cap] (key, column) pairs | [B] counts (candidates.hip)
+    dae_buf mix_loss;          // the mixed loss without a step, on the title context: the DAE's term of one panel, transposed | partial table | row losses (mix_loss_plan.h)
     dae_buf loss_rows;         // the loss without a step: hidden rows [B][H] | partial table [grid][R_TILE] | row losses [B] | l2 partials (loss_rows.hip)
     dae_buf rank_of;           // dae_decode_rank_of: [n_ans] thresholds (u64) | logits | places | buckets, then [n_rg] longest rows (rank_of.hip)
     dae_buf cat_seeds;         // the catalogue calls: a slab's seed lists in the catalogue's columns, [4097] row pointers | [4096] counts | the columns (catalogue.hip)
@@ -195,6 +196,24 @@ extern thread_local std::string g_dae_create_err;
 int dae_fail(dae_ctx* ctx, int code, const char* fmt, ...);
 int dae_reserve(dae_ctx* ctx, dae_buf& b, size_t bytes);
 int dae_ensure_guard(dae_ctx* ctx);       // ctx->guard: allocated and zeroed once (api.hip)
+
+// What the context remembers about its packed fp32 hidden image (h_packed): for which (rows, row width, row-group height) and
+// which allocation the pad rows / pad k are known to be zero (h_geom_key / h_geom_ptr: score.hip hidden_pads_zeroed), whether
+// row_d belongs to it, and whether a pending dae_score_topk_begin still owns it.
+inline long long dae_hidden_geom_key(int B, int H, int R_TILE)
+{
+    return ((long long)B << 32) | ((long long)H << 12) | (long long)R_TILE;
+}
+// A call outside the ranking path has just rewritten the WHOLE image, pads included, with dae_launch_pack_h (no row_d output)
+// for B rows of width H in groups of R_TILE (loss_rows.hip, mix_loss.hip): the pads are zero for that geometry, row_d is not
+// this image's, and a pending dae_score_topk_begin's hidden image is gone.
+inline void dae_note_hidden_repacked(dae_ctx* ctx, int B, int H, int R_TILE)
+{
+    ctx->row_d_fresh = false;
+    ctx->h_geom_key = dae_hidden_geom_key(B, H, R_TILE);
+    ctx->h_geom_ptr = ctx->h_packed.p;
+    ctx->tk.valid = false;
+}
 
 #define DAE_HIP_CHECK(ctx, expr)                                                              \
     do {                                                                                      \
@@ -405,6 +424,13 @@ int dae_launch_decode_loss_f32(dae_ctx* ctx, const dae_rowgeom& g, int B, float 
 // the loss without a step (loss_rows.hip): ALL tiles of the image of `dtype`, every element a negative, summed per row and
 // workgroup into the partial table row_part[g.n_rg][g.nb_rg][g.R_TILE] (decode_f32_kernel's EPI_ROWLOSS); stores nothing else
 int dae_launch_decode_rowloss(dae_ctx* ctx, const dae_rowgeom& g, int B, int dtype, float* row_part);
+// the mixed loss without a step (mix_loss.hip): the same walk over the TITLE scorer's fp32 image, every element the negative
+// term of sigmoid(z) * mix_w[row] + mixT[column * mix_ld + row] (decode_f32_kernel's EPI_MIXROWLOSS); the same partial table
+int dae_launch_decode_mixrowloss(dae_ctx* ctx, const dae_rowgeom& g, int B, const float* mixT, int64_t mix_ld, const float* mix_w,
+                                 float* row_part);
+// loss_rows.hip loss_cost_kernel: cost = (float)(sum_r (double)row_loss[r] / n_batch + lambda * sum of the n_l2 partials)
+int dae_launch_loss_cost(dae_ctx* ctx, const float* row_loss, int B, int n_batch, const double* l2_part, int n_l2, float lambda,
+                         float* cost_out);
 
 int dae_launch_decode_loss_rowmajor(dae_ctx* ctx, const dae_rowgeom& g, int B, int V, int H, const float* W,
                                     const float* bias, const float* h, float inv_n_batch, float* dzT, int64_t ldT,

@@ -41,6 +41,7 @@ constexpr int EPI_LOSS = 2;        // training: logits -> loss + dL/dz (DAEs.py:
 constexpr int EPI_GMAX = 3;        // EPI_DENSE (raw logits) + cross-wave group maxima: the threshold sample (phase A)
 constexpr int EPI_TERM_ADD = 4;    // an ensemble member's term ADDED to the transposed buffer: outT[c][r] = outT[c][r] + sigmoid(z) * row_scale[r]
 constexpr int EPI_ROWLOSS = 5;     // the loss without a step: every element a negative, summed per ROW; nothing stored per element (loss_rows.hip)
+constexpr int EPI_MIXROWLOSS = 6;  // EPI_ROWLOSS of the title scorer's MIXED score: the negative term of sigmoid(z) * mix_w[row] + mixT[col][row] (mix_loss.hip)
 
 struct dae_decp {          // argument block of the decode kernels on the prepacked image (filled by decode_f32.hip fill_common)
     const float4* Wp;      // f32: [ntiles][G][64] float4   bf16: [ntiles][G][64] uint4 (8 bf16)
@@ -81,6 +82,7 @@ struct dae_decp {          // argument block of the decode kernels on the prepac
     int dz16;                      // dzT holds bf16 (the bf16 backward GEMMs read it as such)
     // EPI_ROWLOSS: loss_part is the partial table [n_rg][nb_rg][R_TILE] -- the negatives' sum of row (rg, i) over the tiles of
     // workgroup `bir` of its row group, at ((rg * nb_rg + bir) * R_TILE + i); no mean folded in (inv_nb, dzT unused)
+    // EPI_MIXROWLOSS: the same table; mixT / mix_ld / mix_w (above) are the call's own, never dae_set_score_mix's
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -175,4 +177,22 @@ __device__ __forceinline__ float dae_loss_head_mixed(float yp, float y, float in
     const float a1 = yp + 1e-10f, a0 = 1.0f - yp + 1e-10f;
     loss -= y * __logf(a1) + 0.55f * (1.0f - y) * __logf(a0);
     return -(y / a1 - 0.55f * (1.0f - y) / a0) * inv_nb;
+}
+// a NEGATIVE (y = 0) of the mixed score yp: its term 0.55 ln a0 (<= 0; the caller SUBTRACTS it), the bits dae_loss_head_mixed
+// subtracts at y = 0 (there 0 * ln a1 is a zero and 0.55f * 1.0f is 0.55f).  decode_f32_kernel's EPI_MIXROWLOSS sums it per row,
+// mix_loss.hip mix_loss_finish_kernel takes it back out of a target's element: the mixed loss without a step has no dL/dyp
+__device__ __forceinline__ float dae_loss_neg_term_mixed(float yp)
+{
+    return 0.55f * __logf(1.0f - yp + 1e-10f);
+}
+// an element of the mixed score with target y (mix_loss.hip redoes the targets the GEMM took as negatives): adds
+// L(y) - L(0) = -y (ln a1 - 0.55 ln a0) to corr; the 0.55 ln a0 taken out is dae_loss_neg_term_mixed of the same yp, bit for bit
+__device__ __forceinline__ void dae_loss_pos_corr_mixed(float yp, float y, float& corr)
+{
+    corr -= y * (__logf(yp + 1e-10f) - dae_loss_neg_term_mixed(yp));
+}
+// the title step's sigmoid of a title logit (title.hip title_loss_kernel), as the two kernels of the mixed loss repeat it
+__device__ __forceinline__ float dae_title_step_sigmoid(float z)
+{
+    return 1.0f / (1.0f + __expf(-z));
 }

@@ -1148,6 +1148,20 @@ int dae_launch_decode_rowloss(dae_ctx* ctx, const dae_rowgeom& g, int B, int dty
     return dae_launch_decode_generic(ctx, EPI_ROWLOSS, dtype == DAE_DTYPE_BF16 ? DT_BF16 : DT_F32, g, p);
 }
 
+int dae_launch_decode_mixrowloss(dae_ctx* ctx, const dae_rowgeom& g, int B, const float* mixT, int64_t mix_ld, const float* mix_w,
+                                 float* row_part)
+{
+    dae_decp p;
+    const dae_packed& pk = ctx->pk_f32;
+    dae_tileset ts{pk.ntiles, 1, 0, static_cast<const int*>(pk.ident.p)};      // every tile, the artists' included
+    int rc = fill_common(ctx, g, B, ts, p, DAE_DTYPE_F32);
+    if (rc) return rc;
+    // the call's own term buffer and weights: what dae_set_score_mix left in the context is neither read nor changed
+    p.mixT = mixT; p.mix_ld = mix_ld; p.mix_w = mix_w; p.mix_ncols = pk.col_hi;
+    p.loss_part = row_part;
+    return dae_launch_decode_generic(ctx, EPI_MIXROWLOSS, DT_F32, g, p);
+}
+
 int dae_launch_decode_filter_f32(dae_ctx* ctx, const dae_rowgeom& g, int B, const dae_tileset& ts,
                                  const float* tau, int n_valid_col, uint2* cand, int* cand_cnt,
                                  int cap, int dtype, int bias_sel, const int* live_cnt, const int* live_list)

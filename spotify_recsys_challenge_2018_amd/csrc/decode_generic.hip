@@ -336,6 +336,22 @@ __global__ __launch_bounds__(NW * 64, HALF ? 2 : NW / 4) void decode_f32_kernel(
             }
         }
 
+        // EPI_MIXROWLOSS: the DAE's term of this tile's elements (ALL columns of the image, the artists' included), requested
+        // now like the mix term above
+        float mlv[EPI == EPI_MIXROWLOSS ? RB : 1][16];
+        if (EPI == EPI_MIXROWLOSS) {
+#pragma unroll
+            for (int rb = 0; rb < RB; ++rb) {
+                const int row = rg * R_TILE + rb * 32 + j;
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int lc = t * 32 + 4 * hi + (e & 3) + 8 * (e >> 2);
+                    mlv[EPI == EPI_MIXROWLOSS ? rb : 0][e] =
+                        (row < p.B && lc < p.ncols) ? p.mixT[(size_t)(p.col_lo + lc) * p.mix_ld + row] : 0.0f;
+                }
+            }
+        }
+
         // EPI_TERM_ADD: what the transposed buffer holds of this tile's elements, requested now like the mix term above (a load
         // instruction reads the 32 consecutive rows of one column that the store below it writes)
         float oldv[EPI == EPI_TERM_ADD ? RB : 1][16];
@@ -586,6 +602,29 @@ __global__ __launch_bounds__(NW * 64, HALF ? 2 : NW / 4) void decode_f32_kernel(
                     }
                 }
             }
+        } else if (EPI == EPI_MIXROWLOSS) {
+            // The mixed loss without a step: the title step's operations in its order on every element, taken as a negative
+            // (title.hip title_loss_kernel, dae_loss_head_mixed with y = 0; no contraction), summed per row.  The targets:
+            // mix_loss.hip.
+#pragma unroll
+            for (int rb = 0; rb < RB; ++rb) {
+                const int row = rg * R_TILE + rb * 32 + j;
+                if (row >= p.B) continue;
+                const float wt = p.mix_w[row];
+#pragma unroll
+                for (int qd = 0; qd < 4; ++qd) {
+                    const int lc = tcol0 + 8 * qd;
+                    const float zb[4] = {bq[qd].x, bq[qd].y, bq[qd].z, bq[qd].w};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        if (lc + e < p.ncols) {
+                            const float st = dae_title_step_sigmoid(acc[rb][4 * qd + e] + zb[e]);
+                            const float yp = st * wt + mlv[EPI == EPI_MIXROWLOSS ? rb : 0][4 * qd + e];
+                            row_acc[rb] -= dae_loss_neg_term_mixed(yp);
+                        }
+                    }
+                }
+            }
         } else if ((t * 32 < p.ncols) && (p.col_lo + t * 32 < p.n_valid_col)) {
             // filter: tiles without a rankable column (the artist columns) need no epilogue at all; in
             // the others the common case -- this launch walks the LOW-bias tiles -- is "no value of
@@ -650,7 +689,7 @@ __global__ __launch_bounds__(NW * 64, HALF ? 2 : NW / 4) void decode_f32_kernel(
         __syncthreads();
         if (tid < R_TILE) p.cand_cnt[(size_t)bir * p.Bpad + rg * R_TILE + tid] = lcnt[tid];
     }
-    if (EPI == EPI_ROWLOSS) {
+    if (EPI == EPI_ROWLOSS || EPI == EPI_MIXROWLOSS) {
         // Fixed order, no atomics: the two half-waves hold the same 32 rows and different column quads -> one shuffle; the
         // waves meet in LDS ([NW][R_TILE] floats behind the hidden tile, which stays untouched) and are added in wave order;
         // one float per row of the group goes to the workgroup's place in the partial table.  A wave without a tile adds +0.
@@ -691,7 +730,7 @@ int launch_decode(dae_ctx* ctx, const dae_rowgeom& g, const dae_decp& p)
     const size_t lds = (size_t)RB * 64 * p.G * sizeof(float4) + (size_t)RB * 32 * sizeof(int) +
                        (EPI == EPI_GMAX ? (size_t)NW * 256 * sizeof(float4) : 0) +
                        (EPI == EPI_FILTER ? (size_t)RB * 32 * sizeof(float) : 0) +
-                       (EPI == EPI_ROWLOSS ? (size_t)NW * RB * 32 * sizeof(float) : 0);
+                       ((EPI == EPI_ROWLOSS || EPI == EPI_MIXROWLOSS) ? (size_t)NW * RB * 32 * sizeof(float) : 0);
     DAE_HIP_CHECK(ctx, dae_lds_limit_once(ctx, &decode_f32_kernel<RB, EPI, GT, NW, DT>, 160 * 1024));
     if (ctx->prof_armed) {
         char name[96];
@@ -752,6 +791,16 @@ int dae_launch_decode_generic(dae_ctx* ctx, int epi, int dt, const dae_rowgeom& 
         case EPI_GMAX:   return dt == DT_F32 ? launch_decode_rb<EPI_GMAX>(ctx, g, p) : launch_decode_rb_bf16<EPI_GMAX>(ctx, g, p);
         case EPI_TERM_ADD: return dt == DT_F32 ? launch_decode_rb<EPI_TERM_ADD>(ctx, g, p) : launch_decode_rb_bf16<EPI_TERM_ADD>(ctx, g, p);
         case EPI_ROWLOSS: return dt == DT_F32 ? launch_decode_rb<EPI_ROWLOSS>(ctx, g, p) : launch_decode_rb_bf16<EPI_ROWLOSS>(ctx, g, p);
+        case EPI_MIXROWLOSS:
+            // the fp32 image only, at the three row-group heights the geometry can choose (no unrolled hidden-256 body: a title
+            // image's K is ld_feat)
+            if (dt != DT_F32 || g.waves != 4) break;
+            switch (g.R_TILE) {
+                case 128: return launch_decode<4, EPI_MIXROWLOSS, 0, 4, DT_F32>(ctx, g, p);
+                case 64:  return launch_decode<2, EPI_MIXROWLOSS, 0, 4, DT_F32>(ctx, g, p);
+                case 32:  return launch_decode<1, EPI_MIXROWLOSS, 0, 4, DT_F32>(ctx, g, p);
+            }
+            break;
     }
     return dae_fail(ctx, DAE_ERR_ARG, "bad epilogue %d", epi);
 }

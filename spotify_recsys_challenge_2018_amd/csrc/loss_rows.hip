@@ -126,12 +126,12 @@ int loss_rows_launch(dae_ctx* ctx, const LossPlan& t, const float* h, int B, int
 {
     int rc;
     if (dtype == DAE_DTYPE_F32) {
-        ctx->row_d_fresh = false;
         if ((rc = dae_launch_pack_h(ctx, h, B, H, t.g))) return rc;          // (rewrites the whole image, pads included)
-        ctx->h_geom_key = ((long long)B << 32) | ((long long)H << 12) | (long long)t.g.R_TILE;
-        ctx->h_geom_ptr = ctx->h_packed.p;
-    } else if ((rc = dae_launch_pack_h_bf16(ctx, h, B, H, t.g))) return rc;
-    ctx->tk.valid = false;                                                   // (a pending dae_score_topk_begin's hidden image is gone)
+        dae_note_hidden_repacked(ctx, B, H, t.g.R_TILE);
+    } else {
+        if ((rc = dae_launch_pack_h_bf16(ctx, h, B, H, t.g))) return rc;
+        ctx->tk.valid = false;                                               // (a pending dae_score_topk_begin's hidden image is gone)
+    }
     if ((rc = dae_launch_decode_rowloss(ctx, t.g, B, dtype, t.part))) return rc;
     auto finish = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3(B), dim3(256), 0, ctx->stream, y_row_ptr, y_col, y_val, H, V, h, W_dec, b_dec, t.part,
@@ -144,6 +144,14 @@ int loss_rows_launch(dae_ctx* ctx, const LossPlan& t, const float* h, int B, int
 }
 
 }  // namespace
+
+int dae_launch_loss_cost(dae_ctx* ctx, const float* row_loss, int B, int n_batch, const double* l2_part, int n_l2, float lambda,
+                         float* cost_out)
+{
+    hipLaunchKernelGGL(loss_cost_kernel, dim3(1), dim3(64), 0, ctx->stream, row_loss, B, n_batch, l2_part, n_l2, lambda, cost_out);
+    DAE_CHECK_LAUNCH(ctx, "loss_cost_kernel");
+    return DAE_OK;
+}
 
 extern "C" {
 
@@ -198,9 +206,7 @@ int dae_score_loss(dae_ctx* ctx, const int32_t* x_row_ptr, const int32_t* x_col,
         const size_t ns[4] = {(size_t)V * H, (size_t)V, (size_t)H, (size_t)V * H};
         if ((rc = dae_launch_l2_partials(ctx, ts, ns, 4, t.l2_part, &n_l2))) return rc;
     }
-    hipLaunchKernelGGL(loss_cost_kernel, dim3(1), dim3(64), 0, ctx->stream, rows, B, n_batch, t.l2_part, n_l2, reg_lambda, cost_out);
-    DAE_CHECK_LAUNCH(ctx, "loss_cost_kernel");
-    return DAE_OK;
+    return dae_launch_loss_cost(ctx, rows, B, n_batch, t.l2_part, n_l2, reg_lambda, cost_out);
 }
 
 }  // extern "C"

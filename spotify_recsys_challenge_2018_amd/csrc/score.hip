@@ -36,7 +36,7 @@ dae_rowgeom geom_for(int dtype, int B, int Hp)
 // buffer.  bytes = 0: the caller has just rewritten the whole image, pads included (pack_hidden) -- only noted.
 int hidden_pads_zeroed(dae_ctx* ctx, long long& key, void*& ptr, const dae_buf& img, size_t bytes, int B, int H, int R_TILE)
 {
-    const long long want = ((long long)B << 32) | ((long long)H << 12) | (long long)R_TILE;
+    const long long want = dae_hidden_geom_key(B, H, R_TILE);
     if (key == want && ptr == img.p) return DAE_OK;
     if (bytes) DAE_HIP_CHECK(ctx, hipMemsetAsync(img.p, 0, bytes, ctx->stream));
     key = want; ptr = img.p;

@@ -6,6 +6,7 @@ the same config.ini schema:
     [BASE] verbose data_dir result_dir testsize   (+ optional, this build only: train_dtype = f32 | bf16, decode_dtype = f32 | bf16 | exact_bf16,
                                                   eval_metrics = rprecision | all, train_feed = host | device,
                                                   eval_ranks = off | on, eval_mixed_ranks = off | on, eval_loss = off | on,
+                                                  eval_mixed_loss = off | on,
                                                   ensemble = <pickle>[, <pickle> ...], ensemble_alpha = a0, a1, ...,
                                                   eval_ensemble_ranks = off | on, ensemble_fit = <seed>[, mrr | recall@N])
     [DAE] epochs batch lr reg_lambda hidden test_seed update_seed keep_prob input_kp firstN_range initval save
@@ -96,16 +97,23 @@ class Conf:
         #                  feed; input = the test feed, targets = its entries and the held-out answers in the vocabulary, keep
         #                  probabilities 1, no lambda term).  Refused under --title, beside [BASE] ensemble and for a
         #                  vocabulary-sharded training run (main_train.run)
+        #   eval_mixed_loss = off | on        --title only: with `on` one more line per test split behind the others, "mixed heldout
+        #                  loss: ...", the same mean under the loss the title scorer minimises, the loss of the MIXED score (models/
+        #                  DAEs.py DAE_title.mixed_loss, per row, feed by feed; titles and titles_use as eval_mixed_ranks feeds them).
+        #                  Refused outside --title, beside [BASE] ensemble and for a vocabulary-sharded training run
+        #                  (main_train.run)
         self.eval_metrics = 'rprecision'
         self.train_feed = 'host'
         self.eval_loss = 'off'
+        self.eval_mixed_loss = 'off'
         self.eval_ranks = 'off'
         self.eval_mixed_ranks = 'off'
         self.eval_ensemble_ranks = 'off'
         for key, allowed in (('train_dtype', ('f32', 'bf16')), ('decode_dtype', ('f32', 'bf16', 'exact_bf16')),
                              ('eval_metrics', ('rprecision', 'all')), ('train_feed', ('host', 'device')),
                              ('eval_ranks', ('off', 'on')), ('eval_mixed_ranks', ('off', 'on')),
-                             ('eval_ensemble_ranks', ('off', 'on')), ('eval_loss', ('off', 'on'))):
+                             ('eval_ensemble_ranks', ('off', 'on')), ('eval_loss', ('off', 'on')),
+                             ('eval_mixed_loss', ('off', 'on'))):
             if key in self.ini['BASE']:
                 val = self.ini['BASE'][key].strip().lower()
                 if val not in allowed:
@@ -310,6 +318,9 @@ def main(argv=None):
         if conf.eval_mixed_ranks == 'on':
             raise ValueError("[BASE] eval_mixed_ranks = on is available under --title only: --challenge evaluates nothing "
                              "(remove the key or set eval_mixed_ranks = off)")
+        if conf.eval_mixed_loss == 'on':
+            raise ValueError("[BASE] eval_mixed_loss = on is available under --title only: --challenge evaluates nothing "
+                             "(remove the key or set eval_mixed_loss = off)")
         conf.set_title_conf()
         conf.set_challenge_oonf()
         main_challenge.run(conf)

@@ -263,11 +263,49 @@ def _log_loss(conf, readers_test, model):
         log_write(conf, "seed num: %s heldout loss: %f" % (seed_num, eval_loss(readers_test[seed_num], conf, model)))
 
 
+def eval_mixed_loss(reader_test, conf, model):
+    """[BASE] eval_mixed_loss = on (--title): `eval_loss` under the title mix -- the mean over one test split's playlists of the
+    row loss of the MIXED score (model.mixed_loss per row, feed by feed, so a short last feed is averaged correctly): input = the
+    reader's test feed, targets = `heldout_targets`, all with weight 1; titles and titles_use as `eval_mixed_ranks` feeds them (a
+    row without a title takes titles_use = 0 and an all-padding title); keep probabilities 1."""
+    pad = [-1] * conf.strmaxlen
+    total, count = 0.0, 0
+    while True:
+        x_positions, test_seed, test_answer, titles, x_ones = reader_test.next_batch_test()
+        use = np.array([0.0 if t is None else 1.0 for t in titles], np.float32)
+        y_positions = heldout_targets(x_positions, test_answer, model.n_input)
+        _cost, rows = model.mixed_loss(x_positions, x_ones, y_positions, np.ones(len(y_positions), np.float32),
+                                       [t if t is not None else pad for t in titles], use, n_rows=len(test_seed), per_row=True)
+        total += float(np.sum(rows, dtype=np.float64))
+        count += len(test_seed)
+        if reader_test.test_idx == 0:
+            break
+    return total / max(count, 1)
+
+
+def _log_mixed_loss(conf, readers_test, model):
+    """As `_log_loss`, for [BASE] eval_mixed_loss under --title: one more line per split, behind the existing ones."""
+    if getattr(conf, 'eval_mixed_loss', 'off') != 'on' or getattr(conf, 'mode', None) != 'title':
+        return
+    for seed_num in readers_test:
+        log_write(conf, "seed num: %s mixed heldout loss: %f" % (seed_num, eval_mixed_loss(readers_test[seed_num], conf, model)))
+
+
 def _refuse_ranks_under_title(conf, only_testmode=True):
+    if getattr(conf, 'eval_mixed_loss', 'off') == 'on':
+        if getattr(conf, 'mode', None) != 'title':
+            raise ValueError("[BASE] eval_mixed_loss = on is available under --title only: the other modes have no title mix "
+                             "(remove the key, set eval_mixed_loss = off, or use eval_loss)")
+        if getattr(conf, 'ensemble', None):
+            raise ValueError("[BASE] eval_mixed_loss = on is set beside [BASE] ensemble: an ensemble has no loss "
+                             "(set eval_mixed_loss = off)")
+        if not only_testmode and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise ValueError("[BASE] eval_mixed_loss = on is not available for a vocabulary-sharded title scorer (a training run "
+                             "under torch.distributed.run): partial costs across ranks are not built (set eval_mixed_loss = off)")
     if getattr(conf, 'eval_loss', 'off') == 'on':
         if getattr(conf, 'mode', None) == 'title':
-            raise ValueError("[BASE] eval_loss = on is not available under --title: the loss of the mixed score is another kernel "
-                             "(remove the key or set eval_loss = off)")
+            raise ValueError("[BASE] eval_loss = on is not available under --title: the loss of the mixed score is another kernel, "
+                             "[BASE] eval_mixed_loss = on (remove the key or set eval_loss = off)")
         if getattr(conf, 'ensemble', None):
             raise ValueError("[BASE] eval_loss = on is set beside [BASE] ensemble: an ensemble has no loss (set eval_loss = off)")
         if not only_testmode and int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -388,6 +426,7 @@ def run(conf, only_testmode):
         _log_mixed_ranks(conf, readers_test, model)
         _log_ensemble_ranks(conf, readers_test, model)
         _log_loss(conf, readers_test, model)
+        _log_mixed_loss(conf, readers_test, model)
         return out
 
     # [BASE] train_feed = device: the training set lives on the device and a batch goes up as the reader's draws alone
@@ -445,6 +484,7 @@ def run(conf, only_testmode):
             _log_ranks(conf, readers_test, model)
             _log_mixed_ranks(conf, readers_test, model)
             _log_loss(conf, readers_test, model)
+            _log_mixed_loss(conf, readers_test, model)
             for seed_num in readers_test:
                 if seed_num in conf.update_seed:
                     cur_eval += rprecs[seed_num]

@@ -1430,6 +1430,59 @@ class DAE_title(DAE):
             raise _lib.DaeError("DAE_title.loss: not available on a vocabulary-sharded model (shard_title_training)")
         return DAE.loss(self, x_positions, x_ones, y_positions, y_ones, keep_prob, input_keep_prob, seed, n_rows, per_row)
 
+    def mixed_loss(self, x_positions, x_ones, y_positions, y_ones, titles, titles_use, keep_prob=1.0, input_keep_prob=1.0,
+                   title_keep_prob=1.0, seed=None, n_rows=None, per_row=False):
+        """sess.run(model.cost, ...) of the title graph: the cost of a batch under the MIXED score WITHOUT a step
+        (dae_mix_loss_rows) -> float, or (cost, rows) with `per_row`: rows float32 [n_rows], the loss of each row over all
+        columns; cost = sum(rows) / n_batch (the title cost has no lambda term).  What `train_step` computes up to its loss:
+        the frozen DAE's encode, the mixing weights and the title features with the three dropout masks a step with the same
+        `seed` draws, then the mixed head on every column -- for rows, or whole batches, with titles_use = 0 as well (that is
+        what the title step does: there is no dispatch to `DAE.loss`).  Always fp32, like `mixed_rank_of` (both fp32 images
+        are packed for the call).  A keep probability below 1 needs an explicit seed; the model's own dropout stream is never
+        drawn from, so a --title training run with calls of this in between trains the same title scorer.  Nothing of either
+        model changes.  Refused by name before any upload: no fitted title scorer, no titles, a scoring shard,
+        shard_title_training, n_rows > n_batch."""
+        import torch
+        tm = self._title_scorer()
+        if tm is None:
+            raise _lib.DaeError("mixed_loss: the model has no fitted title scorer (the loss of the DAE alone is `loss`)")
+        if titles is None:
+            raise ValueError("mixed_loss: titles are required (the loss of the DAE alone is `loss`)")
+        if self._score_shard is not None:
+            raise _lib.DaeError("mixed_loss: not available on a scoring shard (shard_scoring): partial costs across ranks are not "
+                                "built")
+        if self._title_sharded is not None:
+            raise _lib.DaeError("mixed_loss: not available on a vocabulary-sharded title scorer (shard_title_training): partial "
+                                "costs across ranks are not built")
+        n = self.n_batch if n_rows is None else int(n_rows)
+        if n < 1 or n > self.n_batch:
+            raise ValueError("mixed_loss: n_rows = %d outside [1, n_batch = %d]" % (n, self.n_batch))
+        if (float(keep_prob) < 1.0 or float(input_keep_prob) < 1.0 or float(title_keep_prob) < 1.0) and seed is None:
+            raise ValueError("mixed_loss: a keep probability below 1 needs an explicit seed")
+        seed = 0 if seed is None else int(seed)
+        self._ensure_packed(_lib.DAE_DTYPE_F32)
+        tm._ensure_packed(_lib.DAE_DTYPE_F32, features_table=float(title_keep_prob) == 1.0)
+        self.ctx.bind_stream()
+        tm.ctx.bind_stream()
+        x = self._upload_csr(x_positions, x_ones, n_rows=n)
+        y = self._upload_csr(y_positions, y_ones, n_rows=n)
+        dev = self.weights["encoder_h"].device
+        h = torch.empty((n, self.n_hidden), dtype=torch.float32, device=dev)
+        self.ctx.encode(x[0], x[1], x[2], self.weights["encoder_h"], self.biases["encoder_b"], h,
+                        ikp=input_keep_prob, kp=keep_prob, seed=seed)
+        tu = np.ones(n, np.float32) if titles_use is None else np.asarray(titles_use, np.float32).reshape(-1)
+        w_t, w_p = self._mix_weights(x, tu, input_keep_prob, seed, n_rows=n)
+        feat = tm.features(titles, n, title_keep_prob, seed)
+        cost = torch.empty(1, dtype=torch.float32, device=dev)
+        rows = torch.empty(n, dtype=torch.float32, device=dev) if per_row else None
+        tm.ctx.bind_stream()
+        tm.ctx.mix_loss_rows(self.ctx, h, self.weights["decoder_h"], self.biases["decoder_b"], feat, tm.p["Output_WT"],
+                             tm.p["Output_b"], w_t, w_p, self.n_batch, y, row_loss=rows, cost_out=cost)
+        c = float(cost.item())
+        res = (c, rows.cpu().numpy()) if per_row else c
+        self._check_feed()
+        return res
+
     # -- multi-GPU title training: the output layer's columns sharded over the ranks (DESIGN.md section 6) ----
     def shard_title_training(self, rank, world, group=None):
         """Train the title scorer through sharding.ShardedTitleTrainer: this rank owns the rows
